@@ -20,10 +20,14 @@ Workloads (BASELINE.json configs):
                         sample, resolve (sharded over N), gather, D2H.  RNG draws in the reference's
                         order on one Generator (run_inference.py:378-407), made ahead by a producer thread.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (algorithmic bytes per
-launch over the HIP-event kernel time on the launch stream, SURVEY.md 8d: A = 4*S + 48 B/quartet, plus a
-per-kernel list with the fraction of the roof that actually binds each kernel) and `cpu_baseline` (the
-oracle -- a port of the reference worker -- timed on host cores; N = 1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the
+`--steps` steps, writes the last step's rows if `--dump-outputs DIR` is given, and prints the headline
+(`value`, `ms_per_step`, ...).  `--full` adds everything else, after the timed steps: `roofline` (algorithmic
+bytes per launch over the HIP-event kernel time on the launch stream, SURVEY.md 8d: A = 4*S + 48 B/quartet,
+plus a per-kernel list with the fraction of the roof that actually binds each kernel), `cpu_baseline` (the
+oracle -- a port of the reference worker -- timed on host cores; N = 1 only), the other subsample mode, the
+device-resident and PCIe-inclusive rates, and for N > 1 the gather verification, the in-run one-GPU figure
+and the c4 strong-scaling leg.
 """
 from __future__ import annotations
 
@@ -367,19 +371,26 @@ def parse_args(argv=None):
                     help="default: c3 (one GPU: 1e6 quartets; N GPUs: N x 1e6, weak scaling, then a c4 strong-scaling leg)")
     ap.add_argument("--weak", action="store_true", help="N > 1: every rank its own 1e6 quartets of the c3 matrix (the default)")
     ap.add_argument("--no-c4-leg", action="store_true",
-                    help="N > 1 default run: skip the secondary c4 strong-scaling leg (BASELINE.json configs[3])")
+                    help="N > 1 --full run: skip the secondary c4 strong-scaling leg (BASELINE.json configs[3])")
     ap.add_argument("--quartets", type=int, default=0, help="quartets in the batch (0 = config default)")
-    ap.add_argument("--full", action="store_true", help="subsample_snps=False")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-subsample", action="store_true", help="subsample_snps=False")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: roofline and "
+                         "per-kernel figures, cpu_baseline, the other subsample mode, device-resident / PCIe-inclusive "
+                         "rates; N > 1: gather verification, in-run one-GPU figure, c4 strong-scaling leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the rows the last timed step delivered (rstat, rscor, flags) as DIR/<name>.npy in "
+                         "float64 / float32 (a fixed, seeded sample of rows when they exceed 60 MB)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-other-mode", action="store_true",
-                    help="skip the 3 steps in the other subsample mode (full_mode_value): profiler passes average per kernel name")
+                    help="--full: skip the 3 steps in the other subsample mode (full_mode_value): profiler passes average per kernel name")
     ap.add_argument("--cpu-procs", type=int, default=0,
                     help="processes of the cpu_baseline leg (0 = one per physical core this process may use)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 control flow on a box with fewer GPUs than ranks")
     ap.add_argument("--pieces", type=int, default=0, help="N > 1: result pieces per batch (0 = automatic)")
     ap.add_argument("--gather-ab", action="store_true",
-                    help="N > 1: add a three-step leg with the OTHER --gather mode to the line (other_gather_leg); opt-in, so that "
+                    help="N > 1 --full: add a three-step leg with the OTHER --gather mode to the line (other_gather_leg); opt-in, so that "
                          "the bare command a driver runs on a multi-GPU node exercises one data path only")
     ap.add_argument("--gather", default="collective", choices=["collective", "host"],
                     help="N > 1: 'collective' = one all-gather per piece, rank 0 copies the rows D2H (default); 'host' = every "
@@ -527,6 +538,27 @@ def emit(line: dict):
         os.write(_REAL_STDOUT, data)
 
 
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(out_dir, rstat, rscor, flags):
+    """--dump-outputs: the rows one step delivered, as float64 (rstat, rscor) and float32 (flags) .npy files.  Larger
+    batches are cut to a fixed sample of rows (seed 0, ascending, saved as `rows`), the same for every build."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"rstat": np.asarray(rstat).astype(np.float64), "rscor": np.asarray(rscor).astype(np.float64),
+              "flags": np.asarray(flags).astype(np.float32)}
+    n = len(arrays["flags"])
+    per_row = sum(a[:1].nbytes for a in arrays.values())
+    if n * per_row > DUMP_BUDGET_BYTES:
+        k = DUMP_BUDGET_BYTES // (per_row + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -567,7 +599,7 @@ def main(argv=None):
     weak = multi and cfg == "c3"                  # N > 1 on the c3 shape: per-GPU work fixed (the N = 1 workload per rank)
     if args.weak and cfg != "c3":
         raise SystemExit("--weak is the c3 shape")
-    sub = not args.full
+    sub = not args.no_subsample
     eng = QuartetEngine(dev_index)
     if args.phases:
         eng.set_option("phases", args.phases)
@@ -624,9 +656,10 @@ def main(argv=None):
         torch.cuda.synchronize()
         return n * steps / (time.perf_counter() - t0), out, d_q
 
-    def run_sharded(wl, steps, warmup, timing=True, gather=None, with_one_gpu=True):
+    def run_sharded(wl, steps, warmup, timing=True, gather=None, with_one_gpu=True, checks=True):
         """The N-rank path over workload `wl`: returns a dict with the max-over-ranks elapsed time of `steps`
-        steps, the gathered rows (rank 0), the verification of the gather and the in-run one-GPU figure."""
+        steps, the gathered rows (rank 0) and, with `checks`, the verification of the gather and the in-run
+        one-GPU figure."""
         from tetrad_amd.distributor import ShardedResolver
         Q = wl["Q"]
         res = ShardedResolver(Q, engine=eng, device=dev_index, dst=0, pieces=args.pieces or None,
@@ -659,6 +692,12 @@ def main(argv=None):
         if res.gather == "host" and rstat is not None:          # views of the shared segment, which res.close() unmaps
             rstat, rscor, flags = rstat.copy(), rscor.copy(), flags.copy()
         last[0] = None
+        out = dict(elapsed=elapsed, kms=kms, launches=launches, n_local=res.n_local, rows=(rstat, rscor, flags))
+        if not checks:
+            res.close()
+            del res
+            barrier()
+            return out
         # the gathered rows on rank 0 against what every rank computed itself: a checksum over each rank's
         # own rows and 64 sampled rows per rank, compared bit for bit
         P = res.plan
@@ -673,7 +712,6 @@ def main(argv=None):
                          for i in pick] if mine else [])
         recs = [None] * world
         dist.all_gather_object(recs, rec)
-        out = dict(elapsed=elapsed, kms=kms, launches=launches, n_local=res.n_local, rows=(rstat, rscor, flags))
         if rank == 0:
             ok = True
             for r in recs:
@@ -719,12 +757,19 @@ def main(argv=None):
         for _ in range(args.warmup):
             step()
         barrier()
-        eng.timing_enable(True)
+        eng.timing_enable(True)                 # event marks in every run: plain and --full runs time the same path
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         barrier()
         elapsed = time.perf_counter() - t0
+        rstat, rscor, flags = out
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rstat, rscor, flags)
+        q_rank = Q
+        if not args.full:
+            eng.timing_enable(False)
+    if not multi and args.full:
         kms, launches = eng.timing_read_kernels()
         # per-kernel durations of the singular-value stage: in the timed region two chunks run concurrently on
         # two streams (one chunk's tail is filled by the next), so their event spans overlap; three more steps
@@ -738,8 +783,6 @@ def main(argv=None):
         eng.set_option("svd_streams", 0)
         eng.timing_enable(False)
         step()                                  # results of the default configuration
-        rstat, rscor, flags = out
-        q_rank = Q
         # device-resident rate (no result D2H) and the PCIe-inclusive rate of the host-buffer API (quartets
         # H2D from a page-locked array + results D2H per call); reported beside `value`, never as `value`
         quartets_h = pinned_empty((Q, 4), np.uint32)
@@ -788,11 +831,14 @@ def main(argv=None):
             extra["subsample_mode_value" if not sub else "full_mode_value"] = other
             extra["other_mode_flags"] = {"zero_data": int((out_o[2] & 1).sum()), "degenerate": int(((out_o[2] & 2) > 0).sum()),
                                          "nsnps_mean": float(out_o[0][:, 1].mean())}
-    else:
-        r = run_sharded(wl, args.steps, args.warmup)
+    if multi:
+        r = run_sharded(wl, args.steps, args.warmup, checks=args.full)
         elapsed, kms, launches, q_rank = r["elapsed"], r["kms"], r["launches"], r["n_local"]
         kms_serial, launches_serial = kms, launches
         rstat, rscor, flags = r["rows"]
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, rstat, rscor, flags)
+    if multi and args.full:
         if rank == 0:
             value = Q * args.steps / elapsed
             for k in ("gather_verified", "gather_pieces", "rows_per_piece_per_rank", "one_gpu_same_run_value",
@@ -831,40 +877,16 @@ def main(argv=None):
                     gather_verified=r4["gather_verified"], gather_pieces=r4["gather_pieces"],
                     one_gpu_rows_equal_gathered_rows=r4["one_gpu_rows_equal_gathered_rows"])
 
-    hbm_copy = hbm_copy_rate(torch, dev) if rank == 0 else None
+    hbm_copy = hbm_copy_rate(torch, dev) if rank == 0 and args.full else None
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = Q * args.steps / elapsed
-        A = 4 * S + 48                                   # algorithmic bytes per quartet
-        bytes_per_launch = q_rank * A + 4 * S              # q_rank = quartets one launch of the scan kernel covers here
-        per_pass = {k: v / max(1, launches) for k, v in kms.items()}
-        dominant_ms = per_pass["scan"]
-        achieved = bytes_per_launch / (dominant_ms / 1e3) / 1e9
-        traffic, traffic_src = None, "not measured in this run"
-        tf = REPO / "profiles" / f"traffic_{cfg}_{'sub' if sub else 'full'}.json"
-        if tf.exists() and not multi and not args.quartets:
-            tj = json.loads(tf.read_text())
-            traffic = tj.get("hbm_bytes_per_launch")
-            traffic_src = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, collated in {tf.name} "
-                           f"(commit {tj.get('commit', 'unknown')}); not re-measured in this run")
         what = ("lexicographic (all)" if lexi else "random")
         workload = (f"{cfg}: {T} taxa x {S} SNPs, {Q} {what} quartets"
                     + (f" in one batch cut over {world} GPUs (strong scaling)" if multi and not weak else "")
                     + (f" = {Q // world} per GPU (weak scaling: the N = 1 workload on every GPU)" if weak else "")
                     + f", subsample_snps={sub}, results delivered to host arrays inside the step")
-        dp = None
-        opts = dict(kv.split("=") for kv in args.opt)
-        if (not sub and q_rank >= int(opts.get("dp_min_quartets", 0) or 32768) and T ** 3 < 2 ** 32 and not multi
-                and int(opts.get("scan_dp", 1)) and int(opts.get("scan_f4", -1)) <= 0 and int(opts.get("scan_method", -1)) < 0
-                and int(opts.get("order", 1))
-                and (args.order != 0) and locals().get("quartets_h") is not None):
-            dp = dict(dp_unit_count(np.array(locals()["quartets_h"]), T), quartets=Q)
-        f4_opt = int(opts.get("scan_f4", -1))
-        plain = (int(opts.get("scan_method", -1)) < 0 and int(opts.get("park_t", 1)) and not int(opts.get("scan_pair", 0))
-                 and not int(opts.get("share_c", 0)) and int(opts.get("scan_wg", 0)) in (0, 4))
-        f4 = plain and (f4_opt == 1 or (f4_opt < 0 and sub)) and dp is None
-        kernels = kernel_rooflines(kms_serial, launches_serial, q_rank, S, sub, cfg, dp, f4)
         line = {
             "metric": "resolved quartets/sec (whole node)", "value": value, "unit": "quartets/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -880,8 +902,6 @@ def main(argv=None):
                        "launcher": ("bench.py started the ranks itself" if os.environ.get("TQ_BENCH_SELF_LAUNCHED")
                                     else ("torch.distributed.run / external" if multi else "none (one process)")),
                        "backend": (args.backend if multi else None)},
-            "roofline": roofline_block(achieved, dominant_ms, bytes_per_launch, traffic, traffic_src, hbm_copy, per_pass,
-                                       kernels, multi),
             "flags": {"zero_data": int((flags & 1).sum()), "degenerate": int(((flags & 2) > 0).sum()),
                       "no_convergence": int(((flags & 8) > 0).sum())},
             "commit": git_head(), "library_path": library_path(),
@@ -893,16 +913,43 @@ def main(argv=None):
         if n_diag:
             line["INVALID_diagnostic_rows"] = n_diag
             line["INVALID_diagnostic_options"] = [kv for kv in args.opt if kv.split("=")[0] in ("scan_method", "phases")]
-        if not args.no_cpu and args.phases in (0, 3) and not n_diag and not multi:      # CPU leg: rank 0 at N=1 only
-            quartets_np = np.array(quartets_h)
-            cb, parity = cpu_baseline(tmparr, tmpmap, quartets_np, sub, rstat, rscor, max_procs=args.cpu_procs)
-            line["cpu_baseline"] = cb
-            line["parity_on_cpu_sample"] = parity
-            line["gpu_over_cpu"] = value / cb["value"]                 # against the port on cb["cores"] cores
-            whole_cpu = cb["whole_host"] or cb["whole_host_extrapolated"]
-            line["gpu_over_cpu_whole_host"] = value / whole_cpu
-            line["gpu_over_cpu_whole_host_is_extrapolated"] = cb["whole_host"] is None
-            line["gpu_over_cpu_reference_faithful"] = value / cb["reference_faithful"]["value"]
+        if args.full:
+            A = 4 * S + 48                                   # algorithmic bytes per quartet
+            bytes_per_launch = q_rank * A + 4 * S              # q_rank = quartets one launch of the scan kernel covers here
+            per_pass = {k: v / max(1, launches) for k, v in kms.items()}
+            dominant_ms = per_pass["scan"]
+            achieved = bytes_per_launch / (dominant_ms / 1e3) / 1e9
+            traffic, traffic_src = None, "not measured in this run"
+            tf = REPO / "profiles" / f"traffic_{cfg}_{'sub' if sub else 'full'}.json"
+            if tf.exists() and not multi and not args.quartets:
+                tj = json.loads(tf.read_text())
+                traffic = tj.get("hbm_bytes_per_launch")
+                traffic_src = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, collated in {tf.name} "
+                               f"(commit {tj.get('commit', 'unknown')}); not re-measured in this run")
+            dp = None
+            opts = dict(kv.split("=") for kv in args.opt)
+            if (not sub and q_rank >= int(opts.get("dp_min_quartets", 0) or 32768) and T ** 3 < 2 ** 32 and not multi
+                    and int(opts.get("scan_dp", 1)) and int(opts.get("scan_f4", -1)) <= 0 and int(opts.get("scan_method", -1)) < 0
+                    and int(opts.get("order", 1))
+                    and (args.order != 0) and locals().get("quartets_h") is not None):
+                dp = dict(dp_unit_count(np.array(locals()["quartets_h"]), T), quartets=Q)
+            f4_opt = int(opts.get("scan_f4", -1))
+            plain = (int(opts.get("scan_method", -1)) < 0 and int(opts.get("park_t", 1)) and not int(opts.get("scan_pair", 0))
+                     and not int(opts.get("share_c", 0)) and int(opts.get("scan_wg", 0)) in (0, 4))
+            f4 = plain and (f4_opt == 1 or (f4_opt < 0 and sub)) and dp is None
+            kernels = kernel_rooflines(kms_serial, launches_serial, q_rank, S, sub, cfg, dp, f4)
+            line["roofline"] = roofline_block(achieved, dominant_ms, bytes_per_launch, traffic, traffic_src, hbm_copy,
+                                              per_pass, kernels, multi)
+            if not args.no_cpu and args.phases in (0, 3) and not n_diag and not multi:      # CPU leg: rank 0 at N=1 only
+                quartets_np = np.array(quartets_h)
+                cb, parity = cpu_baseline(tmparr, tmpmap, quartets_np, sub, rstat, rscor, max_procs=args.cpu_procs)
+                line["cpu_baseline"] = cb
+                line["parity_on_cpu_sample"] = parity
+                line["gpu_over_cpu"] = value / cb["value"]                 # against the port on cb["cores"] cores
+                whole_cpu = cb["whole_host"] or cb["whole_host_extrapolated"]
+                line["gpu_over_cpu_whole_host"] = value / whole_cpu
+                line["gpu_over_cpu_whole_host_is_extrapolated"] = cb["whole_host"] is None
+                line["gpu_over_cpu_reference_faithful"] = value / cb["reference_faithful"]["value"]
         emit(line)
     if multi:
         dist.barrier()
@@ -959,15 +1006,17 @@ def bench_c5(args, eng, torch, dist, dev, world, rank):
     Q = args.quartets or 1_000_000
     runner = ReplicateRunner(eng, seqarr, spans, Q, seed=synth.CONFIG_SEEDS["c5"], sampler=args.sampler,
                              pieces=args.pieces or None, gather=args.gather)
-    sub = not args.full
+    sub = not args.no_subsample
     for _ in range(args.warmup):
         runner.run(1, sub)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    last = [None]
+    keep_last = (lambda k, S, rstat, rscor, flags: last.__setitem__(0, (rstat, rscor, flags))) if args.dump_outputs else None
     eng.timing_enable(True)
     t0 = time.perf_counter()
-    stats = runner.run(args.steps, sub)
+    stats = runner.run(args.steps, sub, on_result=keep_last)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -979,10 +1028,12 @@ def bench_c5(args, eng, torch, dist, dev, world, rank):
         t = torch.tensor([elapsed], dtype=torch.float64, device=gdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if last[0] is not None:                 # rank 0, before close(): with --gather host the rows are views of a shared segment
+        dump_outputs(args.dump_outputs, *last[0])
     runner.close()
     # the Generator advanced exactly as the reference's would: the same draws, replayed on a fresh Generator
     rng_check = None
-    if rank == 0 and args.sampler == "host" and (args.warmup + args.steps) <= 130:
+    if rank == 0 and args.full and args.sampler == "host" and (args.warmup + args.steps) <= 130:
         chk = np.random.default_rng(synth.CONFIG_SEEDS["c5"])
         for _ in range(args.warmup + args.steps):
             bootstrap.draw_replicate(len(spans), chk)                       # run_inference.py:117-123
@@ -991,10 +1042,6 @@ def bench_c5(args, eng, torch, dist, dev, world, rank):
     if rank == 0:
         S = int(np.mean(stats["sites"]))
         q_rank = runner.n_local
-        A = 4 * S + 48
-        per_pass = {k: v / max(1, launches) for k, v in kms.items()}
-        bytes_per_launch = q_rank * A + 4 * S
-        achieved = bytes_per_launch / (per_pass["scan"] / 1e3) / 1e9
         line = {
             "metric": "resolved quartets/sec (whole node)", "value": Q * args.steps / elapsed, "unit": "quartets/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -1006,20 +1053,25 @@ def bench_c5(args, eng, torch, dist, dev, world, rank):
                        "quartets_per_replicate": Q, "taxa": T, "snps": S0, "mean_replicate_sites": S,
                        "subsample_snps": sub, "sampler": args.sampler,
                        "parallelism": f"replicate-sequential RNG (run_inference.py:378-407), quartet-sharded x{world}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "kernel": "tq_scan_f4_kernel" if sub else "tq_scan_dp_kernel", "kernel_ms": per_pass["scan"],
-                         "algorithmic_bytes_per_launch": bytes_per_launch, "traffic": None,
-                         "traffic_source": "not measured in this run",
-                         "all_kernels_ms_per_step": sum(per_pass.values()),
-                         "kernels_note": ("event spans of the timed region; the singular-value chunks of a replicate run on two "
-                                          "streams, so the bidiag / bdsqr / score spans overlap and over-state each kernel's own "
-                                          "duration (the c3 line of the default run has them serialised)"),
-                         "kernels": kernel_rooflines(kms, launches, q_rank, S, sub, "c3", None, bool(sub))},
             "host_draw_ms_per_replicate_mean": float(np.mean(stats["host_ms"])),
             "main_thread_wait_for_draws_ms_mean": float(np.mean(stats["wait_ms"])),
             "flags": stats["flags"], "rng_state_matches_reference_draw_order": rng_check,
             "commit": git_head(), "library_path": library_path(),
         }
+        if args.full:
+            A = 4 * S + 48
+            per_pass = {k: v / max(1, launches) for k, v in kms.items()}
+            bytes_per_launch = q_rank * A + 4 * S
+            achieved = bytes_per_launch / (per_pass["scan"] / 1e3) / 1e9
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "kernel": "tq_scan_f4_kernel" if sub else "tq_scan_dp_kernel", "kernel_ms": per_pass["scan"],
+                                "algorithmic_bytes_per_launch": bytes_per_launch, "traffic": None,
+                                "traffic_source": "not measured in this run",
+                                "all_kernels_ms_per_step": sum(per_pass.values()),
+                                "kernels_note": ("event spans of the timed region; the singular-value chunks of a replicate run on "
+                                                 "two streams, so the bidiag / bdsqr / score spans overlap and over-state each "
+                                                 "kernel's own duration (the c3 line of a --full run has them serialised)"),
+                                "kernels": kernel_rooflines(kms, launches, q_rank, S, sub, "c3", None, bool(sub))}
         emit(line)
     if world > 1:
         dist.barrier()

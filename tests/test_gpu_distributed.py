@@ -123,10 +123,10 @@ def test_bare_bench_command_runs_two_ranks():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
-    # the same with --gather host (no collective on the data path)
+    # the same with --gather host (no collective on the data path); --full adds the checks and the other gather leg
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--quartets", "40000", "--gather", "host", "--no-c4-leg", "--gather-ab"], capture_output=True,
-                       text=True, env=env, timeout=900)
+                        "--warmup", "1", "--quartets", "40000", "--gather", "host", "--no-c4-leg", "--gather-ab", "--full"],
+                       capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     assert d["n_gpus"] == 2 and d["gather_verified"] and d["one_gpu_rows_equal_gathered_rows"]

@@ -5,7 +5,7 @@ O=$1; shift
 mkdir -p $O
 for v in "$@"; do
   L=${v%%:*}; A=${v#*:}
-  python3 bench.py --no-cpu --steps 5 --warmup 2 $A > $O/$L.json 2> $O/$L.err
+  python3 bench.py --full --no-cpu --steps 5 --warmup 2 $A > $O/$L.json 2> $O/$L.err
   python3 -c "
 import json,sys
 d=json.load(open('$O/$L.json'))

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=$1; shift
 mkdir -p $O; rm -rf $O/clk
-timeout -k 5 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -d $O/clk --output-format csv -- python3 bench.py --no-other-mode --no-cpu --steps 3 --warmup 1 "$@" > /dev/null 2> $O/clk.err
+timeout -k 5 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -d $O/clk --output-format csv -- python3 bench.py --full --no-other-mode --no-cpu --steps 3 --warmup 1 "$@" > /dev/null 2> $O/clk.err
 python3 - $O/clk <<'PY'
 import csv, sys
 from pathlib import Path
