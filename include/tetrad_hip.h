@@ -291,6 +291,36 @@ int tq_qmc_splits(const uint32_t *quartets, const uint32_t *rstat, const double 
 int tq_qmc_tree(const uint32_t *splits, const double *weights, int64_t n, int64_t ntaxa, uint64_t seed,
                 char *out, int64_t cap, int64_t *written);
 
+/* Quartet concordance on a fixed tree.  Replaces: prepare_fixed_tree + set_quartet_data +
+ * the counting half of set_quartet_stats (tetrad/src/concordance.py:97-244), which re-read every quartets TSV line by
+ * line; here the rows are counted where they are -- host arrays, or device arrays right behind tq_svd_dev.
+ *   tq_conc_create  tree as a parent array: nodes 0..T-1 are the taxa (tips), nodes >= T internal, parent[root] = -1;
+ *                   4 <= T <= 4096.  A root of degree 2 is dissolved (unrooted, as toytree's .unroot()), unary nodes
+ *                   are suppressed; edges = the nontrivial splits of that tree (both sides >= 2 taxa).  min_snps is
+ *                   taken as max(1, min_snps).  `ctx` may be NULL: then only tq_conc_add works.  The context must
+ *                   outlive the accumulator; messages go to tq_last_error(ctx) (tq_last_error(NULL) without one).
+ *   tq_conc_add     host rows (no device involved), synchronous: quartets u32[n,4], rstat u32[n,2] {topology, nsnps},
+ *                   rscor f64[n,3], flags u8[n] or NULL.
+ *   tq_conc_add_dev the same rows as device pointers, enqueued on `stream` (hipStream_t, NULL = default stream),
+ *                   allocation-free; calls on different streams are ordered in call order (the accumulator's slab).
+ *   tq_conc_read    waits for the device adds and returns the sums of every add since create / reset, any output may be
+ *                   NULL: edge_counts i64[E][6] = {nqrts, conc, disc1, disc2, nu, nsnps sum}, edge_sums f64[E][2] =
+ *                   {weight sum, score sum}, masks u64[E][W] = taxa on one side of each edge (bit x of word x/64),
+ *                   tip_counts i64[T][2] = {QFc, QFd}, *skipped = rows counted nowhere (taxon >= T, repeated taxon,
+ *                   topology > 2, flags TQ_FLAG_BAD_INDEX or TQ_FLAG_INVALID_DIAGNOSTIC).  E, W: tq_conc_shape.   */
+typedef struct tq_conc tq_conc;
+int tq_conc_create(tq_conc **out, const int32_t *parent, int64_t n_nodes, int64_t T, int64_t min_snps, double min_ratio,
+                   tq_ctx *ctx);
+void tq_conc_destroy(tq_conc *acc);
+int tq_conc_reset(tq_conc *acc);
+int tq_conc_add(tq_conc *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
+                int64_t n);
+int tq_conc_add_dev(tq_conc *acc, const uint32_t *d_quartets, const uint32_t *d_rstat, const double *d_rscor,
+                    const uint8_t *d_flags, int64_t n, void *stream);
+int tq_conc_shape(const tq_conc *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words);
+int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t *masks, int64_t *tip_counts,
+                 int64_t *skipped);
+
 /* Device facts used by bench.py: writes CU count, wave slots used by the resolve
  * kernel per CU and the padded row pitch in bytes.                                 */
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch);

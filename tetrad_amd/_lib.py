@@ -34,6 +34,7 @@ SYMBOLS = [
     "tq_timing_enable", "tq_timing_read", "tq_timing_read_split", "tq_timing_read_kernels",
     "tq_set_option", "tq_device_info", "tq_debug_fetch", "tq_debug_bdsqr",
     "tq_format_tsv", "tq_format_qmc", "tq_qmc_tree", "tq_qmc_splits", "tq_unrank", "tq_numpy_choice_tail",
+    "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
 ]
 
 
@@ -170,6 +171,20 @@ def load() -> ctypes.CDLL:
     lib.tq_unrank.restype = i32
     lib.tq_qmc_tree.argtypes = [vp, vp, i64, i64, c.c_uint64, vp, i64, c.POINTER(i64)]
     lib.tq_qmc_tree.restype = i32
+    lib.tq_conc_create.argtypes = [c.POINTER(vp), vp, i64, i64, i64, c.c_double, vp]
+    lib.tq_conc_create.restype = i32
+    lib.tq_conc_destroy.argtypes = [vp]
+    lib.tq_conc_destroy.restype = None
+    lib.tq_conc_reset.argtypes = [vp]
+    lib.tq_conc_reset.restype = i32
+    lib.tq_conc_add.argtypes = [vp, vp, vp, vp, vp, i64]
+    lib.tq_conc_add.restype = i32
+    lib.tq_conc_add_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    lib.tq_conc_add_dev.restype = i32
+    lib.tq_conc_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.tq_conc_shape.restype = i32
+    lib.tq_conc_read.argtypes = [vp, vp, vp, vp, vp, c.POINTER(i64)]
+    lib.tq_conc_read.restype = i32
     lib.tq_device_info.argtypes = [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(i64)]
     lib.tq_device_info.restype = i32
     _lib = lib

@@ -28,6 +28,7 @@
 //   hqr.hpp       tq_bidiag_kernel + tq_bdsqr_kernel + tq_score_kernel: singular values (default)
 //   jacobi.hpp    tq_svd_kernel: one-sided Jacobi singular values in registers (alternative)
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
+//   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -66,6 +67,7 @@ namespace {
 #include "bootstrap.hpp"
 #include "format.hpp"
 #include "qmc.hpp"
+#include "concordance.hpp"
 
 }  // namespace
 
@@ -1131,6 +1133,82 @@ int resolve_to_host(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, b
     return sink.finish();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Concordance accumulator (concordance.hpp): device totals u64 [words] = per edge {conc, disc1, disc2, nu, nsnps sum,
+// weight sum (f64 bits), score sum (f64 bits)}, per taxon {QFc, QFd}, skipped rows; host totals of tq_conc_add beside.
+// ---------------------------------------------------------------------------------------------
+}  // namespace
+
+struct tq_conc {
+    tq_ctx *ctx = nullptr;          // device adds need one; messages go to tq_last_error(ctx)
+    ConcTree t;
+    uint32_t min_snps = 1;
+    double min_ratio = 1.0;
+    int64_t words = 0;
+    std::vector<uint64_t> hi;       // host adds: integer words
+    std::vector<double> hf;         // host adds: weight / score sums
+    uint16_t *d_lca = nullptr, *d_dep = nullptr;
+    int32_t *d_eid = nullptr;
+    uint64_t *d_slab = nullptr, *d_tot = nullptr;
+    int gmax = 0;                   // workgroups the slab holds
+    int num_cu = 0;
+    hipEvent_t ev = nullptr;        // recorded behind the last device add
+    bool pending = false;
+    hipStream_t last = nullptr;
+};
+
+namespace {
+
+void conc_free_dev(tq_conc *a)
+{
+    if (a->d_lca) (void)hipFree(a->d_lca);
+    if (a->d_dep) (void)hipFree(a->d_dep);
+    if (a->d_eid) (void)hipFree(a->d_eid);
+    if (a->d_slab) (void)hipFree(a->d_slab);
+    if (a->d_tot) (void)hipFree(a->d_tot);
+    if (a->ev) (void)hipEventDestroy(a->ev);
+}
+
+int conc_launch(tq_conc *acc, const uint32_t *dq, const uint32_t *drs, const double *dsc, const uint8_t *dfl, int64_t n,
+                hipStream_t stream)
+{
+    tq_ctx *ctx = acc->ctx;
+    const ConcTree &t = acc->t;
+    for (int64_t r0 = 0; r0 < n; r0 += CONC_ROWS_PER_LAUNCH) {
+        const int64_t m = std::min<int64_t>(CONC_ROWS_PER_LAUNCH, n - r0);
+        const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(m + 4095) / 4096, (int64_t)acc->num_cu, (int64_t)acc->gmax}));
+        ConcArgs a{dq + 4 * r0, drs + 2 * r0, dsc + 3 * r0, dfl ? dfl + r0 : nullptr, m, acc->d_lca, acc->d_dep, acc->d_eid,
+                   t.T, t.N, t.E, acc->min_snps, acc->min_ratio, 0, t.E, 1, acc->d_slab, acc->words};
+        if (t.T <= 128) {
+            hipLaunchKernelGGL((tq_conc_kernel<true, 128, 128>), dim3(G), dim3(CONC_THREADS), 0, stream, a);
+        } else if (t.T <= 256) {
+            hipLaunchKernelGGL((tq_conc_kernel<true, 256, 256>), dim3(G), dim3(CONC_THREADS), 0, stream, a);
+        } else {
+            for (int32_t e0 = 0; e0 < t.E || e0 == 0; e0 += CONC_EDGE_TILE) {      // a pass per tile of edges
+                a.e_lo = e0;
+                a.e_n = std::min<int32_t>(CONC_EDGE_TILE, t.E - e0);
+                a.tips = e0 == 0;
+                hipLaunchKernelGGL((tq_conc_kernel<false, CONC_T_MAX, CONC_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0,
+                                   stream, a);
+            }
+        }
+        hipLaunchKernelGGL(tq_conc_fold_kernel, dim3((unsigned)((acc->words + CONC_THREADS - 1) / CONC_THREADS)),
+                           dim3(CONC_THREADS), 0, stream, (const uint64_t *)acc->d_slab, G, acc->words, t.E, acc->d_tot);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_conc_add_dev: launch failed: %s", hipGetErrorString(e));
+    }
+    return TQ_OK;
+}
+
+int conc_wait(tq_conc *acc)
+{
+    if (!acc->pending) return TQ_OK;
+    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+    TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
+    acc->pending = false;
+    return TQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1973,6 +2051,155 @@ int tq_qmc_tree(const uint32_t *splits, const double *weights, int64_t n, int64_
         *written = 0;
         return TQ_ERR_OOM;
     }
+}
+
+int tq_conc_create(tq_conc **out, const int32_t *parent, int64_t n_nodes, int64_t T, int64_t min_snps, double min_ratio,
+                   tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: out is NULL");
+    *out = nullptr;
+    if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: parent is NULL");
+    if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: min_ratio is NaN");
+    tq_conc *acc = new (std::nothrow) tq_conc();
+    if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
+    try {
+        const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
+        if (!err.empty()) {
+            delete acc;
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: %s", err.c_str());
+        }
+        acc->ctx = ctx;
+        acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);   // deviation 2
+        acc->min_ratio = min_ratio;
+        acc->words = (int64_t)acc->t.E * CONC_EDGE_WORDS + 2 * T + 1;
+        acc->hi.assign(acc->words, 0);
+        acc->hf.assign(acc->words, 0.0);
+    } catch (const std::bad_alloc &) {
+        delete acc;
+        return fail(ctx, TQ_ERR_OOM, "tq_conc_create: out of host memory");
+    }
+    if (ctx) {
+        const ConcTree &t = acc->t;
+        acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+        acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_lca, (size_t)T * T * 2);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_dep, (size_t)t.N * 2);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_eid, (size_t)t.N * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_slab, (size_t)acc->gmax * acc->words * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_tot, (size_t)acc->words * 8);
+        if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            conc_free_dev(acc);
+            delete acc;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_conc_create: %s", hipGetErrorString(e));
+        }
+    }
+    *out = acc;
+    return TQ_OK;
+}
+
+void tq_conc_destroy(tq_conc *acc)
+{
+    if (!acc) return;
+    if (acc->ctx) {
+        (void)hipSetDevice(acc->ctx->device);
+        if (acc->pending) (void)hipEventSynchronize(acc->ev);
+        conc_free_dev(acc);
+    }
+    delete acc;
+}
+
+int tq_conc_reset(tq_conc *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    std::fill(acc->hi.begin(), acc->hi.end(), 0);
+    std::fill(acc->hf.begin(), acc->hf.end(), 0.0);
+    if (acc->ctx) {
+        if (int rc = conc_wait(acc)) return rc;
+        TQ_HIP(acc->ctx, hipMemset(acc->d_tot, 0, (size_t)acc->words * 8));
+    }
+    return TQ_OK;
+}
+
+int tq_conc_add(tq_conc *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
+                int64_t n)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (n < 0 || (n > 0 && (!quartets || !rstat || !rscor)))
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_conc_add: NULL pointer or negative n");
+    conc_add_host(acc->t, acc->min_snps, acc->min_ratio, quartets, rstat, rscor, flags, n, acc->hi, acc->hf);
+    return TQ_OK;
+}
+
+int tq_conc_add_dev(tq_conc *acc, const uint32_t *d_quartets, const uint32_t *d_rstat, const double *d_rscor,
+                    const uint8_t *d_flags, int64_t n, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: the accumulator was created without a context");
+    if (n < 0 || (n > 0 && (!d_quartets || !d_rstat || !d_rscor)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: NULL pointer or negative n");
+    if (n == 0) return TQ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    if (acc->pending && st != acc->last) TQ_HIP(ctx, hipStreamWaitEvent(st, acc->ev, 0));   // slab / totals in call order
+    if (int rc = conc_launch(acc, d_quartets, d_rstat, d_rscor, d_flags, n, st)) return rc;
+    TQ_HIP(ctx, hipEventRecord(acc->ev, st));
+    acc->pending = true;
+    acc->last = st;
+    return TQ_OK;
+}
+
+int tq_conc_shape(const tq_conc *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->t.T;
+    if (n_edges) *n_edges = acc->t.E;
+    if (mask_words) *mask_words = acc->t.W;
+    return TQ_OK;
+}
+
+int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t *masks, int64_t *tip_counts,
+                 int64_t *skipped)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    const ConcTree &t = acc->t;
+    std::vector<uint64_t> dv;
+    try {
+        dv.assign(acc->words, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_conc_read: out of host memory");
+    }
+    if (acc->ctx) {
+        if (int rc = conc_wait(acc)) return rc;
+        TQ_HIP(acc->ctx, hipMemcpy(dv.data(), acc->d_tot, (size_t)acc->words * 8, hipMemcpyDeviceToHost));
+    }
+    for (int32_t e = 0; e < t.E; ++e) {
+        const uint64_t *d = &dv[(size_t)e * CONC_EDGE_WORDS];
+        const uint64_t *h = &acc->hi[(size_t)e * CONC_EDGE_WORDS];
+        if (edge_counts) {
+            int64_t *o = edge_counts + 6 * (int64_t)e;
+            o[0] = (int64_t)t.nqrts[e];
+            for (int k = 0; k < 5; ++k) o[1 + k] = (int64_t)(d[k] + h[k]);
+        }
+        if (edge_sums)
+            for (int k = 0; k < 2; ++k) {
+                double dvf;
+                memcpy(&dvf, &d[CW_WEIGHT + k], 8);
+                edge_sums[2 * (int64_t)e + k] = dvf + acc->hf[(size_t)e * CONC_EDGE_WORDS + CW_WEIGHT + k];
+            }
+    }
+    if (masks) memcpy(masks, t.masks.data(), t.masks.size() * 8);
+    const int64_t tb = (int64_t)t.E * CONC_EDGE_WORDS;
+    if (tip_counts)
+        for (int64_t i = 0; i < 2 * (int64_t)t.T; ++i) tip_counts[i] = (int64_t)(dv[tb + i] + acc->hi[tb + i]);
+    if (skipped) *skipped = (int64_t)(dv[tb + 2 * t.T] + acc->hi[tb + 2 * t.T]);
+    return TQ_OK;
 }
 
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch)

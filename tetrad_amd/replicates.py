@@ -45,7 +45,7 @@ class ReplicateRunner:
     def __init__(self, engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, *,
                  seed=None, rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None,
                  pieces: Optional[int] = None, dst: Optional[int] = 0, ahead: int = 3, quartets_to_host: bool = False,
-                 gather: str = "collective"):
+                 gather: str = "collective", concordance=None):
         import torch
         if sampler not in ("host", "device"):
             raise ValueError("sampler must be 'host' or 'device'")
@@ -83,6 +83,12 @@ class ReplicateRunner:
             if self.want_quartets else None
         self._d_ranks_full = torch.empty(self.Q, dtype=torch.int64, device=self.dev) \
             if (self.want_quartets and sampler == "host") else None
+        # concordance on a fixed tree (concordance.Concordance made with this engine): every replicate's own rows are
+        # added on the device, in stream order right behind their singular-value kernels and before the next
+        # replicate's unrank / sample overwrites the quartet buffer; run() ends by reducing the ranks to `dst`
+        self.concordance = concordance
+        if concordance is not None and concordance.engine is not engine:
+            raise ValueError("the concordance accumulator must be created with the runner's engine")
 
     # -- the draws of one replicate, in the reference's order ---------------------------------------------
     def _draw(self):
@@ -181,6 +187,8 @@ class ReplicateRunner:
                     else:
                         q_host[...] = self._d_full[b].cpu().numpy().view(np.uint32)
                 res.start(subsample_snps, b)
+                if self.concordance is not None:
+                    self._add_concordance(b, cur)
                 res.sets[b]["keep"] = keep
                 res.sets[b]["quartets"] = q_host
                 if pending is not None:
@@ -188,10 +196,23 @@ class ReplicateRunner:
                 pending = (k, S, b)
             if pending is not None:
                 collect(*pending)
+            if self.concordance is not None:
+                self.concordance.reduce(res.group, 0 if res.dst is None else res.dst)
         finally:
             self._stop.set()
             self._thread.join()
         return stats
+
+    def _add_concordance(self, b: int, cur):
+        """The rows this rank resolved for buffer set `b` -- piece by piece in the slabs the singular-value stage
+        wrote, quartets in the rank's local order -- into the concordance accumulator, on stream `cur`."""
+        res, P, base_q = self.res, self.res.plan, self._d_q.data_ptr()
+        for i in range(P.npieces):
+            lo, hi = res.ranges[i]
+            n, off, p = hi - lo, int(res.offsets[i]), P.part[i]
+            if n:
+                base = res.sets[b]["slabs"][i].data_ptr()
+                self.concordance.add_dev_ptrs(base_q + 16 * off, base, base + 8 * p, base + 32 * p, n, cur.cuda_stream)
 
     def close(self):
         self._stop.set()
@@ -202,16 +223,18 @@ class ReplicateRunner:
 
 def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, nboots: int, *,
                     subsample_snps: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
-                    rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4) -> list:
+                    rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
+                    concordance=None) -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
     the GPUs work on the next replicates.  Returns the newick strings in replicate order on the destination rank
-    (rank 0), an empty list elsewhere.  Tip labels are taxon numbers (`qmc.relabel_tree` turns them into names)."""
+    (rank 0), an empty list elsewhere.  Tip labels are taxon numbers (`qmc.relabel_tree` turns them into names).
+    `concordance` (a `concordance.Concordance` made with `engine`) receives every replicate's rows on the device."""
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
     runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
-                             quartets_to_host=True)
+                             quartets_to_host=True, concordance=concordance)
     ntaxa = int(seqarr.shape[0])
     futures = {}
     with ThreadPoolExecutor(max_workers=max(1, int(workers))) as pool:
