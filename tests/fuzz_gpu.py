@@ -3,10 +3,12 @@ Usage: python tests/fuzz_gpu.py [seconds] [seed]   (prints one line per case, ex
 import sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+sys.path.insert(0, str(Path(__file__).resolve().parent))
 import numpy as np
 from tetrad_amd import synth
 from tetrad_amd.engine import QuartetEngine
 from oracle import oracle
+from exact_ties import check_rows
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -21,7 +23,7 @@ while time.time() < t_end:
     p = float(rng.choice([0.005, 0.02, 0.05, 0.2]))
     missing = float(rng.choice([0.0, 0.05, 0.3, 0.7, 0.95]))
     tmparr, tmpmap = synth.simulate_tmparr(T, S, int(rng.integers(1 << 30)), p=p, missing=missing)
-    style = int(rng.integers(4))
+    style = int(rng.integers(5))
     if style == 1:                       # one locus per site
         tmpmap[:, 0] = np.arange(S)
     elif style == 2:                     # a single locus
@@ -30,6 +32,9 @@ while time.time() < t_end:
         runs = np.cumsum(rng.integers(1, 200, size=S))
         ids = rng.permutation(S + 5)[:S].astype(np.uint32)
         tmpmap[:, 0] = ids[np.searchsorted(runs, np.arange(S), side="right")]
+    elif style == 4:                     # RAD-seq-like: whole (taxon, locus) blocks missing, some taxa nearly empty
+        tmparr, tmpmap = synth.simulate_radseq(T, S, int(rng.integers(1 << 30)), p=p, block=float(rng.choice([0.3, 0.6, 0.85])),
+                                               cell=float(rng.choice([0.0, 0.02])), hi_frac=0.2, dead_taxa=int(rng.integers(2)))
     if rng.random() < 0.3:
         tmparr[rng.integers(T)] = 78     # an all-missing taxon
     Q = int(rng.choice([1, 3, 63, 64, 65, 255, 1000, 1024, 1025, int(rng.integers(1, 6000))]))
@@ -84,11 +89,20 @@ while time.time() < t_end:
         plain = ((flags | o["flags"]) & 3) == 0
         ok_t = np.array_equal(rstat[plain, 0], o_rstat[plain, 0])
         ok_f = np.array_equal(flags & 1, o["flags"] & 1)
-        status = "ok" if (ok_n and ok_s and ok_t and ok_f) else "MISMATCH"
+        # every row, flagged ones included, under the exact bar (tests/exact_ties.py); the debug call == the plain call
+        ok_x, why = True, ""
+        try:
+            d_rstat, d_rscor, d_flags, dbg = eng.resolve(q, sub, debug=True)
+            for a, b in zip((rstat, rscor, flags), (d_rstat, d_rscor, d_flags)):
+                np.testing.assert_array_equal(a, b, err_msg="plain call != debug call")
+            check_rows((rstat, rscor, flags), dbg, (o_rstat, o_rscor, o))
+        except AssertionError as e:
+            ok_x, why = False, str(e)[:2000]
+        status = "ok" if (ok_n and ok_s and ok_t and ok_f and ok_x) else "MISMATCH"
         print(f"case {case} T={T} S={S} p={p} miss={missing} loc={style} Q={Q} sub={sub} {opts} "
               f"flagged={int((~plain).sum())} maxerr={err[~zero].max() if (~zero).any() else 0:.1e} {status}", flush=True)
         if status != "ok":
             np.savez("/tmp/fuzz_fail.npz", tmparr=tmparr, tmpmap=tmpmap, q=q, sub=sub)
-            print(ok_n, ok_s, ok_t, ok_f)
+            print(ok_n, ok_s, ok_t, ok_f, ok_x, why)
             sys.exit(1)
 print(f"{case} cases clean")

@@ -126,6 +126,38 @@ def make_slices(ref):
         print(f"wrote {cfg}_slice.npz  Q={nq}")
 
 
+def make_sparse(ref):
+    # (13) RAD-seq-like sparse inputs at c3 shape (synth.RAD_PROFILES rad60 / rad85, regenerated from the seed by the
+    #      tests and CRC-checked): the reference's rows, count matrices and singular values for 96 quartets of each,
+    #      chosen (with the oracle's exact ranks, subsample mode) as 32 exact ties, 32 rows with one zero score and 32
+    #      others out of 3 000 random ones
+    import zlib
+    sys.path.insert(0, str(REPO / "tests"))
+    from exact_ties import exact_rank, zero_tail_set
+    from oracle import oracle as orc
+    blob = dict(numpy_version=np.array(np.__version__))
+    for name in ("rad60", "rad85"):
+        arr, tmap = synth.radseq_profile(name)
+        cand = synth.random_quartets(arr.shape[0], 3000, seed=31337)
+        _, rstat, _, dbg = orc.new_infer_resolved_quartets(arr, tmap, cand, True, debug=True)
+        live = rstat[:, 1] > 0
+        nz = np.zeros(len(cand), np.int64)
+        nz[live] = [len(zero_tail_set(r)) for r in exact_rank(dbg["cmats"][live])]
+        pick = np.concatenate([np.flatnonzero(nz >= 2)[:32], np.flatnonzero(nz == 1)[:32], np.flatnonzero(nz == 0)[:32]])
+        qrts = np.ascontiguousarray(cand[np.sort(pick)])
+        blob[f"{name}_quartets"] = qrts
+        blob[f"{name}_tmparr_crc32"] = np.array(zlib.crc32(arr.tobytes()))
+        blob[f"{name}_tmpmap_crc32"] = np.array(zlib.crc32(np.ascontiguousarray(tmap).tobytes()))
+        for sub in (False, True):
+            res = run_reference(ref, arr, tmap, qrts, sub, with_cmats=True)
+            tag = "sub" if sub else "full"
+            for k, v in res.items():
+                blob[f"{name}_{tag}_{k}"] = v
+        print(f"{name}: Q={len(qrts)}")
+    np.savez_compressed(OUT / "sparse_c3_slice.npz", **blob)
+    print("wrote sparse_c3_slice.npz")
+
+
 def make_rows(ref):
     # (12) the reference worker's ROWS (rstat, rscor; no count matrices) for thousands of quartets of the c2 / c3 / c4
     #      benchmark inputs: the bulk parity evidence at benchmark size straight from the reference
@@ -147,6 +179,9 @@ def main(only=None):
     ref = load_reference()
     if only == "rows":
         make_rows(ref)
+        return
+    if only == "sparse":
+        make_sparse(ref)
         return
     if only == "slices":
         make_slices(ref)
@@ -299,6 +334,8 @@ if __name__ == "__main__":
         main(only="slices")
     if "rows" in which:
         main(only="rows")
+    if "sparse" in which:
+        main(only="sparse")
     if "resample" in which:
         make_resample_golden()
     if "c5" in which:

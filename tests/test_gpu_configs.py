@@ -226,7 +226,7 @@ def test_kernel_level_mirrors(case):
         np.testing.assert_array_equal(RQ.full_chunk_to_matrices(seqs, tmpmap[:, 0], mask), g["full_cmats"][qi])
 
 
-@pytest.mark.parametrize("cfg,nq", [("c3", 40_000), ("c2", 60_000)])
+@pytest.mark.parametrize("cfg,nq", [("c3", 40_000), ("c2", 60_000), ("rad85", 40_000)])
 def test_scan_kernel_variants_agree_on_sorted_batches(cfg, nq):
     """Batches large enough to be sorted by (a,b,c) and scanned by the cooperative kernels with shared rows
     (>= 32 768 quartets): every alternative form of the scan -- the nibble-code kernel of rounds 1-3 with its lane-contiguous
@@ -235,8 +235,12 @@ def test_scan_kernel_variants_agree_on_sorted_batches(cfg, nq):
     give bitwise the rows of the default forms (subsample: scan_f4.hpp, full: scan_dp.hpp), in both modes."""
     from tetrad_amd import synth
     from tetrad_amd.engine import QuartetEngine
-    T, S, _ = synth.CONFIGS[cfg]
-    tmparr, tmpmap = synth.simulate_tmparr(T, S, synth.CONFIG_SEEDS[cfg])
+    if cfg == "rad85":                      # c3 shape, RAD-seq-like sparse (synth.RAD_PROFILES)
+        T = 128
+        tmparr, tmpmap = synth.radseq_profile(cfg)
+    else:
+        T, S, _ = synth.CONFIGS[cfg]
+        tmparr, tmpmap = synth.simulate_tmparr(T, S, synth.CONFIG_SEEDS[cfg])
     q = synth.all_quartets(T)[:nq] if cfg == "c2" else synth.random_quartets(T, nq, seed=5)
     defaults = {"park_t": 1, "scan_pair": 0, "share_c": 0, "scan_wg": 0, "scan_method": -1, "scan_dp": 1, "scan_f4": -1}
     with QuartetEngine(0) as eng:

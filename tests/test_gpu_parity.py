@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_FULL_CASES, load_golden
+from exact_ties import check_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -79,6 +80,13 @@ def check_against(g, mode, rstat, rscor, flags, dbg):
     assert ((flags & 8) == 0).all(), "singular-value iteration hit its sweep cap"
     ok = ~zero & ~ref_deg & ~dev_deg
     np.testing.assert_array_equal(rstat[ok, 0], ref_rstat[ok, 0])
+    if f"{mode}_cmats" in g:
+        # the rows skipped above are judged exactly (tests/exact_ties.py): exact ranks say which scores are exactly zero
+        from exact_ties import check_topology, exact_rank
+        skipped = np.flatnonzero(~zero & ~ok)
+        exact = np.zeros((len(rstat), 3), np.int32)
+        exact[skipped] = exact_rank(g[f"{mode}_cmats"][skipped]).reshape(-1, 3)
+        check_topology(skipped, exact, g[f"{mode}_cmats"], rstat[:, 0], dev_deg, ref_rscor, ref_rstat[:, 0], smax)
     return int(ok.sum()), int((~zero & ~ok).sum())
 
 
@@ -154,6 +162,8 @@ def test_seeded_vs_oracle(engine, oracle, seed, T, S, missing, p):
         np.testing.assert_array_equal(dbg["ranks"][~zero], o["rank"][~zero])
         ok = ((flags | o["flags"]) & 3) == 0
         np.testing.assert_array_equal(rstat[ok, 0], o_rstat[ok, 0])
+        # flagged rows too: the exact bar of tests/exact_ties.py
+        check_rows((rstat, rscor, flags), dbg, (o_rstat, o_rscor, o))
 
 
 @pytest.mark.parametrize("nrep", [1, 2, 4, 8, 16, 32])

@@ -145,3 +145,32 @@ def test_minrank_fixture_covers_the_low_rank_branch_with_decided_rows():
         decided = (s[:, 1] - s[:, 0]) > 2e-9 * sv.max(axis=(1, 2))
         n = int(((rank < 10) & decided & ~zero).sum())
         assert n >= at_least, (mode, n)
+
+
+@pytest.mark.parametrize("profile", ["rad60", "rad85"])
+def test_oracle_matches_reference_on_sparse_slice(oracle, profile):
+    """`sparse_c3_slice.npz`: the reference's rows, count matrices and singular values for 96 quartets each of the
+    RAD-seq-like rad60 / rad85 inputs at c3 shape (exact ties, lone zero scores and zero-data rows among them): the
+    regenerated input has the stored CRC and the oracle reproduces the reference."""
+    import zlib
+    from tetrad_amd import synth
+    g = load_golden("sparse_c3_slice")
+    tmparr, tmpmap = synth.radseq_profile(profile)
+    assert zlib.crc32(tmparr.tobytes()) == int(g[f"{profile}_tmparr_crc32"])
+    assert zlib.crc32(np.ascontiguousarray(tmpmap).tobytes()) == int(g[f"{profile}_tmpmap_crc32"])
+    for mode in ("full", "sub"):
+        p = f"{profile}_{mode}"
+        _, rstat, rscor, dbg = oracle.new_infer_resolved_quartets(tmparr, tmpmap, g[f"{profile}_quartets"], mode == "sub",
+                                                                  debug=True)
+        zero = g[f"{p}_zero_data"]
+        np.testing.assert_array_equal(dbg["cmats"], g[f"{p}_cmats"])
+        np.testing.assert_array_equal(rstat[:, 1], g[f"{p}_rstat"][:, 1])
+        np.testing.assert_array_equal((dbg["flags"] & 1).astype(bool), zero)
+        np.testing.assert_array_equal(rscor, g[f"{p}_rscor"])
+        np.testing.assert_array_equal(dbg["svds"][~zero], g[f"{p}_svds"][~zero])
+        np.testing.assert_array_equal(rstat[~zero, 0], g[f"{p}_rstat"][~zero, 0])
+    # what the slice is for: exact ties (|Z| >= 2) and lone zero scores (|Z| == 1) in subsample mode
+    from exact_ties import exact_rank, zero_tail_set
+    live = ~g[f"{profile}_sub_zero_data"]
+    nz = np.array([len(zero_tail_set(r)) for r in exact_rank(g[f"{profile}_sub_cmats"][live])])
+    assert (nz >= 2).sum() >= 30 and (nz == 1).sum() >= 30

@@ -48,9 +48,8 @@ def random_tree_children(T: int, rng: np.random.Generator):
     return children, active[0]
 
 
-def simulate_tmparr(T: int, S: int, seed: int, p: float = 0.05, missing: float = 0.10):
-    """Return (tmparr u8[T,S], tmpmap u32[S,2])."""
-    rng = np.random.default_rng(seed)
+def _simulate_sites(T: int, S: int, rng: np.random.Generator, p: float) -> np.ndarray:
+    """Tree + site simulation shared by simulate_tmparr and simulate_radseq: u8[T,S], no missing cells."""
     children, root = random_tree_children(T, rng)
     out = np.empty((T, 0), dtype=np.uint8)
     while out.shape[1] < S:
@@ -72,7 +71,13 @@ def simulate_tmparr(T: int, S: int, seed: int, p: float = 0.05, missing: float =
                 stack.append(ch)
         variable = (tips != tips[0]).any(axis=0)
         out = np.concatenate([out, tips[:, variable]], axis=1)
-    tmparr = np.ascontiguousarray(out[:, :S])
+    return np.ascontiguousarray(out[:, :S])
+
+
+def simulate_tmparr(T: int, S: int, seed: int, p: float = 0.05, missing: float = 0.10):
+    """Return (tmparr u8[T,S], tmpmap u32[S,2])."""
+    rng = np.random.default_rng(seed)
+    tmparr = _simulate_sites(T, S, rng, p)
     tmparr[rng.random(tmparr.shape) < missing] = 78
     # loci: contiguous runs, lengths 1 + Poisson(4)
     lens = 1 + rng.poisson(4, size=S)
@@ -83,14 +88,64 @@ def simulate_tmparr(T: int, S: int, seed: int, p: float = 0.05, missing: float =
     return tmparr, tmpmap
 
 
-def make_c5_source(T: int | None = None, S: int | None = None, seed: int | None = None, ambiguous: float = 0.01):
+#: RAD-seq-like missing-data profiles for simulate_radseq (with the overall missing share each one aims at):
+#: whole (taxon, locus) blocks dropped, a fifth of the taxa 85-98 % missing, a few single cells blanked
+RAD_PROFILES = {
+    "rad30": dict(block=0.14, cell=0.02, hi_frac=0.2, hi_range=(0.85, 0.98), dead_taxa=0, target=0.31),
+    "rad60": dict(block=0.56, cell=0.02, hi_frac=0.2, hi_range=(0.85, 0.98), dead_taxa=0, target=0.64),
+    "rad85": dict(block=0.80, cell=0.02, hi_frac=0.2, hi_range=(0.85, 0.98), dead_taxa=1, target=0.83),
+}
+
+
+def simulate_radseq(T: int, S: int, seed: int, block: float, cell: float, hi_frac: float = 0.0,
+                    hi_range: tuple[float, float] = (0.85, 0.98), dead_taxa: int = 0, p: float = 0.05):
+    """RAD-seq-like (tmparr u8[T,S], tmpmap u32[S,2]): missing data come mostly as whole loci per sample, as
+    write_database.py:157-168 sees them.  Same tree and sites as simulate_tmparr (no cell-level missing there),
+    then: every (taxon, locus) block dropped with a per-taxon probability (``block``; uniform in ``hi_range``
+    for a ``hi_frac`` share of the taxa), a ``cell`` share of single cells blanked, ``dead_taxa`` taxa made
+    entirely missing.  Locus ids have gaps (as snpsmap's do after filtering) and stay non-decreasing."""
+    rng = np.random.default_rng(seed)
+    tmparr = _simulate_sites(T, S, rng, p)
+    lens = 1 + rng.poisson(4, size=S)
+    locus = np.repeat(np.arange(S, dtype=np.int64), lens)[:S]
+    nloci = int(locus[-1]) + 1
+    rate = np.full(T, block)
+    n_hi = int(round(hi_frac * T))
+    perm = rng.permutation(T)
+    rate[perm[:n_hi]] = rng.uniform(hi_range[0], hi_range[1], size=n_hi)
+    drop = rng.random((T, nloci)) < rate[:, None]
+    tmparr[drop[:, locus]] = 78
+    tmparr[rng.random(tmparr.shape) < cell] = 78
+    if dead_taxa:
+        tmparr[perm[:dead_taxa]] = 78
+    ids = np.cumsum(rng.integers(1, 4, size=nloci)) - 1
+    tmpmap = np.empty((S, 2), dtype=np.uint32)
+    tmpmap[:, 0] = ids[locus]
+    tmpmap[:, 1] = np.arange(S, dtype=np.uint32)
+    return tmparr, tmpmap
+
+
+def radseq_profile(name: str, T: int | None = None, S: int | None = None, seed: int | None = None):
+    """simulate_radseq under one of RAD_PROFILES, at the c3 shape and seed unless told otherwise."""
+    T0, S0, _ = CONFIGS["c3"]
+    kw = {k: v for k, v in RAD_PROFILES[name].items() if k != "target"}
+    return simulate_radseq(T or T0, S or S0, CONFIG_SEEDS["c3"] if seed is None else seed, **kw)
+
+
+def make_c5_source(T: int | None = None, S: int | None = None, seed: int | None = None, ambiguous: float = 0.01,
+                   source=None):
     """The project-level inputs of the bootstrap flow (BASELINE.json configs[4], c3 shape): `seqarr`
     u8[T,S] of ASCII bases with `ambiguous` of the cells replaced by IUPAC two-base codes and N for
     missing (write_database.py:157-159), the snpsmap-style `maparr` u32[S,2] and the locus spans
-    i64[nloci,2] (jit/get_spans.py)."""
-    T0, S0, _ = CONFIGS["c3"]
-    T, S = T or T0, S or S0
-    tmparr, tmpmap = simulate_tmparr(T, S, CONFIG_SEEDS["c5"] if seed is None else seed)
+    i64[nloci,2] (jit/get_spans.py).  ``source`` = (tmparr, tmpmap) replaces the simulated matrix
+    (e.g. a simulate_radseq one)."""
+    if source is None:
+        T0, S0, _ = CONFIGS["c3"]
+        T, S = T or T0, S or S0
+        tmparr, tmpmap = simulate_tmparr(T, S, CONFIG_SEEDS["c5"] if seed is None else seed)
+    else:
+        tmparr, tmpmap = source
+        S = tmparr.shape[1]
     ascii_ = np.array([65, 67, 71, 84], np.uint8)
     seqarr = np.where(tmparr <= 3, ascii_[np.minimum(tmparr, 3)], 78).astype(np.uint8)
     rs = np.random.default_rng(0)
