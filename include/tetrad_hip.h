@@ -221,7 +221,7 @@ int tq_timing_read_kernels(tq_ctx *ctx, double *ms, int n_ms, int64_t *calls);
  * are equal are counted too -- what the reference's count kernels do when their caller's mask leaves such a site open,
  * resolve_quartets.py:59-64; one-wave kernel), bdsqr_maxit (QR sweeps per singular value before TQ_FLAG_NO_CONVERGENCE,
  * default 60), bdsqr_stats (1: count rotation steps / issued lane-slots, read with tq_debug_fetch which = 3), phases
- * (timing diagnostics).  scan_method 2..5 and phases 1 / 2 are timing diagnostics whose rows are wrong: every row of a
+ * (timing diagnostics), species_method (-1 auto, 0 VALU, 1 MFMA form of the species-mode pooled counts).  scan_method 2..5 and phases 1 / 2 are timing diagnostics whose rows are wrong: every row of a
  * call made under them carries TQ_FLAG_INVALID_DIAGNOSTIC and a call without a flags array fails.  scan_method 6 = the
  * bank-private counter kernel (scan_pb.hpp; an A/B form, slower).  batch is clamped to 2^31 - 1.
  * scan_dp (1, default: full-mode batches -- subsample = 0 -- of at least dp_min_quartets go to the joint-histogram scan,
@@ -320,6 +320,41 @@ int tq_conc_add_dev(tq_conc *acc, const uint32_t *d_quartets, const uint32_t *d_
 int tq_conc_shape(const tq_conc *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words);
 int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t *masks, int64_t *tip_counts,
                  int64_t *skipped);
+
+/* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
+ * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
+ * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.
+ *   Pooling: the count matrix of species quartet (A, B, C, D) is the sum, over every lineage quartet (i in A, j in B,
+ *   k in C, l in D), of the full-mode count matrix the reference worker builds for (i, j, k, l)
+ *   (full_chunk_to_matrices with the mask of resolve_quartets.py:216-223: sites with a missing base or four equal bases
+ *   are masked).  Equivalently sum_s a_s (x) b_s (x) c_s (x) d_s with the four bins (x,x,x,x) set to 0, where a_s[x] =
+ *   lineages of A with base x at site s.  nsnps = the sum of the 256 bins; the other flattenings, ranks, scores,
+ *   topology and flags come from the singular-value stage of tq_resolve, unchanged.  Full mode only: the reference's
+ *   subsample mode picks a site per locus and LINEAGE quartet, which does not factor over sites.
+ *   Range: bins and nsnps are u32 (resolve_quartets.py:88).  A species call is refused (TQ_ERR_INVALID_ARG) when
+ *   S x (product of the four largest species sizes) >= 2^32; a row that repeats a species can still exceed that for
+ *   its own lineage product: the host call refuses it, the device call gives it zero counts (TQ_FLAG_ZERO_DATA).
+ *   Kernel forms (option "species_method"): 1 = MFMA (v_mfma_i32_16x16x64_i8, species of <= 11 lineages: i8 operands),
+ *   0 = VALU (any size), -1 (default) = MFMA when every species of the map holds <= 11 lineages, else VALU.  Both give
+ *   the same bits.
+ *   tq_set_species  species_of i32[T]: species id in [0,K) per sample, -1 = left out; T must equal the resident (or
+ *                   source) T, K >= 4, at most 255 lineages per species.  Replaces any earlier map.  The per-species
+ *                   base counts (K x S x 8 bytes on the device) are rebuilt after every tq_set_data / tq_bootstrap* on
+ *                   the stream of the next species call.
+ *   tq_resolve_species  squartets u32[Q,4] species ids (host buffers, synchronous; any Q, in pieces of option "batch",
+ *                   result D2H under the kernels as tq_resolve); outputs as tq_resolve.  An id >= K: TQ_ERR_INVALID_ARG.
+ *   tq_resolve_species_dev  device pointers, enqueued on `stream` (the stream rule above); an id >= K gives the row
+ *                   TQ_FLAG_BAD_INDEX (zero data).
+ *   tq_resolve_species_debug  also the pooled cmats u32[Q,3,16,16], svds f64[Q,3,16], ranks i32[Q,3] (any may be NULL).
+ * Species calls fail with TQ_ERR_NO_DATA without data or without a map, TQ_ERR_INVALID_ARG when the map's T differs from
+ * the resident replicate's.                                                                                          */
+int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K);
+int tq_resolve_species(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor,
+                       uint8_t *flags);
+int tq_resolve_species_dev(tq_ctx *ctx, const uint32_t *d_squartets, int64_t Q, uint32_t *d_rstat, double *d_rscor,
+                           uint8_t *d_flags, void *stream);
+int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor,
+                             uint8_t *flags, uint32_t *cmats, double *svds, int32_t *ranks);
 
 /* Device facts used by bench.py: writes CU count, wave slots used by the resolve
  * kernel per CU and the padded row pitch in bytes.                                 */

@@ -35,6 +35,7 @@ SYMBOLS = [
     "tq_set_option", "tq_device_info", "tq_debug_fetch", "tq_debug_bdsqr",
     "tq_format_tsv", "tq_format_qmc", "tq_qmc_tree", "tq_qmc_splits", "tq_unrank", "tq_numpy_choice_tail",
     "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
+    "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
 ]
 
 
@@ -185,6 +186,14 @@ def load() -> ctypes.CDLL:
     lib.tq_conc_shape.restype = i32
     lib.tq_conc_read.argtypes = [vp, vp, vp, vp, vp, c.POINTER(i64)]
     lib.tq_conc_read.restype = i32
+    lib.tq_set_species.argtypes = [vp, vp, i64, i64]
+    lib.tq_set_species.restype = i32
+    lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.tq_resolve_species.restype = i32
+    lib.tq_resolve_species_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.tq_resolve_species_dev.restype = i32
+    lib.tq_resolve_species_debug.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.tq_resolve_species_debug.restype = i32
     lib.tq_device_info.argtypes = [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(i64)]
     lib.tq_device_info.restype = i32
     _lib = lib

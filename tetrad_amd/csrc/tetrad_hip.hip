@@ -29,6 +29,8 @@
 //   jacobi.hpp    tq_svd_kernel: one-sided Jacobi singular values in registers (alternative)
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
+//   species.hpp   tq_species_table_kernel + tq_species_mfma_kernel / tq_species_pool_kernel: pooled count matrices of
+//                 species quartets (species mode; MFMA form, VALU form)
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -37,6 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -68,6 +71,7 @@ namespace {
 #include "format.hpp"
 #include "qmc.hpp"
 #include "concordance.hpp"
+#include "species.hpp"
 
 }  // namespace
 
@@ -155,6 +159,20 @@ struct tq_ctx {
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
     const uint32_t *scanned_q = nullptr;
     int64_t scanned_Q = 0;
+    int64_t scanned_T = 0;          // index bound of its rows (T; K for species rows): the score kernel flags ids >= it
+    // species mode (tq_set_species, species.hpp): sample -> species map and the per-replicate species table, rebuilt
+    // lazily on the stream of the first species call after the resident data changed (data_gen != sp_tab_gen)
+    int64_t sp_T = 0, sp_K = 0;     // sp_K = 0: no map set
+    std::vector<int32_t> sp_size;   // lineages per species
+    uint64_t sp_bound = 0;          // product of the four largest species sizes (range rule: S * sp_bound < 2^32)
+    int32_t sp_max = 0;             // largest species size
+    int32_t *d_sp_members = nullptr;    // offsets [K+1], then the member samples grouped by species
+    uint32_t *d_sp_tab = nullptr;   // u32 [K][Sp]: {n_A, n_C, n_G, n_T} per species and site, then u8 [K][4][Sp] (MFMA form)
+    int64_t sp_tab_cap = 0;         // (species, site) entries allocated (8 bytes each)
+    int species_method = -1;        // -1: MFMA form when every species holds <= SPECIES_MFMA_MAX lineages, else VALU;
+                                    // 0: VALU form (tq_species_pool_kernel); 1: MFMA form (tq_species_mfma_kernel)
+    uint64_t data_gen = 0;          // bumped by tq_set_data / tq_bootstrap(_async)
+    uint64_t sp_tab_gen = ~0ull;    // data_gen the species table was built from (~0: none)
     // host-buffer API: own compute and copy streams, events for the D2H pipeline
     hipStream_t sK = nullptr, sC = nullptr;
     std::vector<hipEvent_t> pipe_events;
@@ -732,7 +750,7 @@ int launch_svd(tq_ctx *ctx, const uint32_t *cm, const uint32_t *dq, int64_t n, c
     int64_t grid;
     int rc = grid_for(ctx, kern, (n + QPW - 1) / QPW, &grid);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVE), 0, stream, cm, dq, n, (int32_t)ctx->T, out);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVE), 0, stream, cm, dq, n, (int32_t)ctx->scanned_T, out);
     TQ_HIP(ctx, hipGetLastError());
     return mark(ctx, TAG_BIDIAG, stream, lane);
 }
@@ -765,7 +783,7 @@ int launch_hqr(tq_ctx *ctx, const uint32_t *cm, const uint32_t *dq, int64_t n, c
     TQ_HIP(ctx, hipGetLastError());
     if ((rc = mark(ctx, TAG_BDSQR, stream, lane))) return rc;
     hipLaunchKernelGGL(tq_score_kernel<DEBUG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                       (const double *)sv, (const uint32_t *)nsnps, dq, n, (int32_t)ctx->T, out);
+                       (const double *)sv, (const uint32_t *)nsnps, dq, n, (int32_t)ctx->scanned_T, out);
     TQ_HIP(ctx, hipGetLastError());
     return mark(ctx, TAG_SCORE, stream, lane);
 }
@@ -821,6 +839,70 @@ int stage_scan(tq_ctx *ctx, const uint32_t *dq, int64_t n, int subsample, bool i
     }
     ctx->scanned_q = dq;
     ctx->scanned_Q = n;
+    ctx->scanned_T = ctx->T;
+    return TQ_OK;
+}
+
+// Species mode: the map is set, matches the resident replicate and the pooled counts fit u32
+int species_ready(tq_ctx *ctx, const char *who)
+{
+    if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "%s: tq_set_data has not been called", who);
+    if (!ctx->sp_K) return fail(ctx, TQ_ERR_NO_DATA, "%s: no species map (call tq_set_species first)", who);
+    if (ctx->sp_T != ctx->T)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: the species map covers T=%lld samples, the resident replicate has T=%lld",
+                    who, (long long)ctx->sp_T, (long long)ctx->T);
+    if ((unsigned __int128)ctx->S * ctx->sp_bound >= ((unsigned __int128)1 << 32))
+        return fail(ctx, TQ_ERR_INVALID_ARG,
+                    "%s: pooled counts may exceed u32: S=%lld x product of the four largest species sizes %llu >= 2^32",
+                    who, (long long)ctx->S, (unsigned long long)ctx->sp_bound);
+    if (ctx->species_method == 1 && ctx->sp_max > SPECIES_MFMA_MAX)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: species_method 1 (MFMA, i8 operands) takes species of at most %d lineages, "
+                    "the map has one of %d", who, SPECIES_MFMA_MAX, (int)ctx->sp_max);
+    return TQ_OK;
+}
+
+// Stage 1 of a species pass: (re)build the species table if the resident data changed, then the pooled counts of
+// species quartets dsq[0..n) into the count slab, where stage_svd finds them as it finds a scanned batch.
+int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t stream)
+{
+    int rc = ensure_cm(ctx, n);
+    if (rc) return rc;
+    ctx->scanned_Q = 0;
+    if ((rc = mark(ctx, TAG_ORIGIN, stream))) return rc;
+    if (ctx->sp_tab_gen != ctx->data_gen) {
+        const int64_t entries = ctx->sp_K * ctx->Sp;
+        if (entries > ctx->sp_tab_cap) {
+            if (ctx->d_sp_tab) {
+                TQ_HIP(ctx, hipDeviceSynchronize());       // a species call on another stream may still read it
+                (void)hipFree(ctx->d_sp_tab);
+            }
+            ctx->d_sp_tab = nullptr;
+            ctx->sp_tab_cap = 0;
+            TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sp_tab, (size_t)entries * 8));
+            ctx->sp_tab_cap = entries;
+        }
+        hipLaunchKernelGGL(tq_species_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
+                           (const uint8_t *)ctx->d_nib5, ctx->Sp, ctx->S, (const int32_t *)(ctx->d_sp_members + ctx->sp_K + 1),
+                           (const int32_t *)ctx->d_sp_members, (int32_t)ctx->sp_K, ctx->d_sp_tab,
+                           (uint8_t *)(ctx->d_sp_tab + entries));
+        TQ_HIP(ctx, hipGetLastError());
+        ctx->sp_tab_gen = ctx->data_gen;
+    }
+    if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
+    const bool mfma = ctx->species_method == 1 || (ctx->species_method < 0 && ctx->sp_max <= SPECIES_MFMA_MAX);
+    const int32_t *offsets = ctx->d_sp_members;
+    if (mfma)
+        hipLaunchKernelGGL(tq_species_mfma_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
+                           (const uint8_t *)(ctx->d_sp_tab + ctx->sp_K * ctx->Sp), ctx->Sp, ctx->S, dsq, n,
+                           (int32_t)ctx->sp_K, offsets, ctx->d_cm);
+    else
+        hipLaunchKernelGGL(tq_species_pool_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
+                           (const uint32_t *)ctx->d_sp_tab, ctx->Sp, ctx->S, dsq, n, (int32_t)ctx->sp_K, offsets, ctx->d_cm);
+    TQ_HIP(ctx, hipGetLastError());
+    if ((rc = mark(ctx, TAG_SCAN, stream))) return rc;
+    ctx->scanned_q = dsq;
+    ctx->scanned_Q = n;
+    ctx->scanned_T = ctx->sp_K;
     return TQ_OK;
 }
 
@@ -901,16 +983,16 @@ struct NoChunkHook {
 // each followed by its singular-value stage.
 template <typename F>
 int launch(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool debug, bool input_sorted,
-           const OutPtrs &out, hipStream_t stream, F &&after_chunk)
+           const OutPtrs &out, hipStream_t stream, F &&after_chunk, bool species = false)
 {
-    int rc = check_ready(ctx, subsample);
+    int rc = species ? species_ready(ctx, "species resolve") : check_ready(ctx, subsample);
     if (rc) return rc;
     if (Q == 0) return TQ_OK;
     if (ctx->timing) ctx->timed_calls++;
     const int64_t batch = Q < ctx->batch ? Q : ctx->batch;
     for (int64_t q0 = 0; q0 < Q; q0 += batch) {
         const int64_t n = (Q - q0) < batch ? (Q - q0) : batch;
-        rc = stage_scan(ctx, dq + q0 * 4, n, subsample, input_sorted, stream);
+        rc = species ? stage_species(ctx, dq + q0 * 4, n, stream) : stage_scan(ctx, dq + q0 * 4, n, subsample, input_sorted, stream);
         if (rc) return rc;
         rc = stage_svd(ctx, 0, n, debug, offset_out(out, q0), stream,
                        [&](int64_t c0, int64_t cn, hipStream_t st) { return after_chunk(q0 + c0, cn, st); });
@@ -1133,6 +1215,75 @@ int resolve_to_host(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, b
     return sink.finish();
 }
 
+// device species quartets -> host results (synchronous), the pipeline of resolve_to_host
+int species_to_host(tq_ctx *ctx, const uint32_t *dsq, int64_t Q, uint32_t *rstat, double *rscor, uint8_t *flags,
+                    uint32_t *d_rstat, double *d_rscor, uint8_t *d_flags)
+{
+    OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
+    HostSink sink{ctx, rstat, rscor, flags, &out};
+    int rc = sink.begin(Q);
+    if (rc) return rc;
+    rc = launch(ctx, dsq, Q, 0, false, false, out, ctx->sK,
+                [&](int64_t q0, int64_t n, hipStream_t st) { return sink.chunk(q0, n, st); }, true);
+    if (rc) return rc;
+    return sink.finish();
+}
+
+// Device scratch of a host-buffer call (tq_resolve*, tq_resolve_species*): the quartets, copied in on stream sK, then
+// the outputs and the debug outputs the caller asked for
+struct HostScratch {
+    char *base = nullptr;
+    size_t o_rstat = 0, o_rscor = 0, o_flags = 0, o_cm = 0, o_sv = 0, o_rk = 0;
+    const uint32_t *dq() const { return (const uint32_t *)base; }
+    uint32_t *rstat() const { return (uint32_t *)(base + o_rstat); }
+    double *rscor() const { return (double *)(base + o_rscor); }
+    uint8_t *flags() const { return (uint8_t *)(base + o_flags); }
+};
+
+int host_scratch(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, bool cmats, bool svds, bool ranks, HostScratch *h)
+{
+    h->o_rstat = align_up((size_t)Q * 16, 256);
+    h->o_rscor = align_up(h->o_rstat + (size_t)Q * 8, 256);
+    h->o_flags = align_up(h->o_rscor + (size_t)Q * 24, 256);
+    h->o_cm = align_up(h->o_flags + (size_t)Q, 256);
+    h->o_sv = align_up(h->o_cm + (cmats ? (size_t)Q * 3072 : 0), 256);
+    h->o_rk = align_up(h->o_sv + (svds ? (size_t)Q * 384 : 0), 256);
+    const size_t total = align_up(h->o_rk + (ranks ? (size_t)Q * 12 : 0), 256);
+    int rc = ensure_scratch(ctx, total);
+    if (rc) return rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    h->base = (char *)ctx->d_scratch;
+    // quartets H2D on the compute stream (asynchronous when the caller's array is page-locked)
+    TQ_HIP(ctx, hipMemcpyAsync(h->base, quartets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
+    return TQ_OK;
+}
+
+// The debug path of a host-buffer call: one launch with the kernel-level outputs, then every array back (synchronous)
+int debug_to_host(tq_ctx *ctx, const HostScratch &h, int64_t Q, int subsample, bool species, bool input_sorted,
+                  uint32_t *rstat, double *rscor, uint8_t *flags, uint32_t *cmats, double *svds, int32_t *ranks)
+{
+    OutPtrs out{};
+    out.rstat = h.rstat();
+    out.rscor = h.rscor();
+    out.flags = h.flags();
+    out.cmats = cmats ? (uint32_t *)(h.base + h.o_cm) : nullptr;
+    out.svds = svds ? (double *)(h.base + h.o_sv) : nullptr;
+    out.ranks = ranks ? (int32_t *)(h.base + h.o_rk) : nullptr;
+    int rc = launch(ctx, h.dq(), Q, subsample, true, input_sorted, out, ctx->sK, NoChunkHook(), species);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->sK);
+        return rc;
+    }
+    TQ_HIP(ctx, hipStreamSynchronize(ctx->sK));
+    TQ_HIP(ctx, hipMemcpy(rstat, out.rstat, (size_t)Q * 8, hipMemcpyDeviceToHost));
+    TQ_HIP(ctx, hipMemcpy(rscor, out.rscor, (size_t)Q * 24, hipMemcpyDeviceToHost));
+    if (flags) TQ_HIP(ctx, hipMemcpy(flags, out.flags, (size_t)Q, hipMemcpyDeviceToHost));
+    if (cmats) TQ_HIP(ctx, hipMemcpy(cmats, out.cmats, (size_t)Q * 3072, hipMemcpyDeviceToHost));
+    if (svds) TQ_HIP(ctx, hipMemcpy(svds, out.svds, (size_t)Q * 384, hipMemcpyDeviceToHost));
+    if (ranks) TQ_HIP(ctx, hipMemcpy(ranks, out.ranks, (size_t)Q * 12, hipMemcpyDeviceToHost));
+    return TQ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Concordance accumulator (concordance.hpp): device totals u64 [words] = per edge {conc, disc1, disc2, nu, nsnps sum,
 // weight sum (f64 bits), score sum (f64 bits)}, per taxon {QFc, QFd}, skipped rows; host totals of tq_conc_add beside.
@@ -1257,6 +1408,8 @@ void tq_destroy(tq_ctx *ctx)
     if (ctx->d_sv) (void)hipFree(ctx->d_sv);
     if (ctx->d_nsnps) (void)hipFree(ctx->d_nsnps);
     if (ctx->d_bdsqr_stats) (void)hipFree(ctx->d_bdsqr_stats);
+    if (ctx->d_sp_members) (void)hipFree(ctx->d_sp_members);
+    if (ctx->d_sp_tab) (void)hipFree(ctx->d_sp_tab);
     if (ctx->sK) (void)hipStreamDestroy(ctx->sK);
     if (ctx->sC) (void)hipStreamDestroy(ctx->sC);
     if (ctx->sX) {
@@ -1296,6 +1449,7 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
                     (long long)S, (long long)locus_stride);
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     free_data(ctx);
+    ctx->data_gen++;
 
     // contiguous copy of the locus column + the run-contiguity check subsample mode relies on
     std::vector<uint32_t> loc;
@@ -1508,58 +1662,128 @@ int tq_resolve_debug(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, int subsa
         }
         input_sorted = sorted && ctx->T < (1 << 21);
     }
-    const bool debug = cmats || svds || ranks;
-    const size_t o_q = 0;
-    const size_t o_rstat = align_up(o_q + (size_t)Q * 16, 256);
-    const size_t o_rscor = align_up(o_rstat + (size_t)Q * 8, 256);
-    const size_t o_flags = align_up(o_rscor + (size_t)Q * 24, 256);
-    const size_t o_cm = align_up(o_flags + (size_t)Q, 256);
-    const size_t o_sv = align_up(o_cm + (cmats ? (size_t)Q * 3072 : 0), 256);
-    const size_t o_rk = align_up(o_sv + (svds ? (size_t)Q * 384 : 0), 256);
-    const size_t total = align_up(o_rk + (ranks ? (size_t)Q * 12 : 0), 256);
-    if ((rc = ensure_scratch(ctx, total))) return rc;
-    if ((rc = ensure_streams(ctx))) return rc;
-    char *base = (char *)ctx->d_scratch;
-    // quartets H2D on the compute stream (asynchronous when the caller's array is page-locked)
-    TQ_HIP(ctx, hipMemcpyAsync(base + o_q, quartets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
-    if (!debug) {
+    HostScratch h;
+    if ((rc = host_scratch(ctx, quartets, Q, cmats, svds, ranks, &h))) return rc;
+    if (!(cmats || svds || ranks)) {
         if (Q <= CHECK_FIRST)
-            return resolve_to_host(ctx, (const uint32_t *)(base + o_q), Q, subsample, input_sorted, rstat, rscor, flags,
-                                   (uint32_t *)(base + o_rstat), (double *)(base + o_rscor), (uint8_t *)(base + o_flags));
-        return resolve_to_host(ctx, (const uint32_t *)(base + o_q), Q, subsample, false, rstat, rscor, flags,
-                               (uint32_t *)(base + o_rstat), (double *)(base + o_rscor), (uint8_t *)(base + o_flags),
+            return resolve_to_host(ctx, h.dq(), Q, subsample, input_sorted, rstat, rscor, flags, h.rstat(), h.rscor(),
+                                   h.flags());
+        return resolve_to_host(ctx, h.dq(), Q, subsample, false, rstat, rscor, flags, h.rstat(), h.rscor(), h.flags(),
                                check_indices);
     }
     if (Q > CHECK_FIRST && (rc = check_indices())) {
         (void)hipStreamSynchronize(ctx->sK);
         return rc;
     }
-    OutPtrs out{};
-    out.rstat = (uint32_t *)(base + o_rstat);
-    out.rscor = (double *)(base + o_rscor);
-    out.flags = (uint8_t *)(base + o_flags);
-    out.cmats = cmats ? (uint32_t *)(base + o_cm) : nullptr;
-    out.svds = svds ? (double *)(base + o_sv) : nullptr;
-    out.ranks = ranks ? (int32_t *)(base + o_rk) : nullptr;
-    rc = launch(ctx, (const uint32_t *)(base + o_q), Q, subsample, true, input_sorted, out, ctx->sK, NoChunkHook());
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->sK);
-        return rc;
-    }
-    TQ_HIP(ctx, hipStreamSynchronize(ctx->sK));
-    TQ_HIP(ctx, hipMemcpy(rstat, out.rstat, (size_t)Q * 8, hipMemcpyDeviceToHost));
-    TQ_HIP(ctx, hipMemcpy(rscor, out.rscor, (size_t)Q * 24, hipMemcpyDeviceToHost));
-    if (flags) TQ_HIP(ctx, hipMemcpy(flags, out.flags, (size_t)Q, hipMemcpyDeviceToHost));
-    if (cmats) TQ_HIP(ctx, hipMemcpy(cmats, out.cmats, (size_t)Q * 3072, hipMemcpyDeviceToHost));
-    if (svds) TQ_HIP(ctx, hipMemcpy(svds, out.svds, (size_t)Q * 384, hipMemcpyDeviceToHost));
-    if (ranks) TQ_HIP(ctx, hipMemcpy(ranks, out.ranks, (size_t)Q * 12, hipMemcpyDeviceToHost));
-    return TQ_OK;
+    return debug_to_host(ctx, h, Q, subsample, false, input_sorted, rstat, rscor, flags, cmats, svds, ranks);
 }
 
 int tq_resolve(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, int subsample, uint32_t *rstat, double *rscor,
                uint8_t *flags)
 {
     return tq_resolve_debug(ctx, quartets, Q, subsample, rstat, rscor, flags, nullptr, nullptr, nullptr);
+}
+
+int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (!species_of) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: NULL pointer");
+    if (K < 4 || K > 0x7FFFFFFF)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: K=%lld species (a species quartet needs K >= 4)", (long long)K);
+    const int64_t known = ctx->have_data ? ctx->T : ctx->d_seqarr ? ctx->src_T : 0;
+    if (T < 1 || (known && T != known))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: T=%lld, the resident / source data have T=%lld", (long long)T,
+                    (long long)known);
+    std::vector<int32_t> size, members;
+    try {
+        size.assign((size_t)K, 0);
+        for (int64_t i = 0; i < T; ++i) {
+            const int32_t k = species_of[i];
+            if (k < -1 || k >= K)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: sample %lld has species id %d outside [-1, %lld)",
+                            (long long)i, k, (long long)K);
+            if (k >= 0 && ++size[(size_t)k] > 255)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: species %d has more than 255 lineages", k);
+        }
+        // offsets [K+1] then the members grouped by species (ascending sample index inside a species)
+        members.assign((size_t)(K + 1 + T), 0);
+        for (int64_t k = 0; k < K; ++k) members[(size_t)k + 1] = members[(size_t)k] + size[(size_t)k];
+        std::vector<int32_t> fill(members.begin(), members.begin() + K);
+        for (int64_t i = 0; i < T; ++i)
+            if (species_of[i] >= 0) members[(size_t)(K + 1 + fill[(size_t)species_of[i]]++)] = (int32_t)i;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_set_species: out of host memory");
+    }
+    std::vector<int32_t> top(size);
+    std::sort(top.begin(), top.end(), [](int32_t a, int32_t b) { return a > b; });
+    uint64_t bound = 1;
+    for (int i = 0; i < 4; ++i) bound *= (uint64_t)top[(size_t)i];
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    TQ_HIP(ctx, hipDeviceSynchronize());         // a species call may still read the old map / table
+    if (ctx->d_sp_members) (void)hipFree(ctx->d_sp_members);
+    ctx->d_sp_members = nullptr;
+    ctx->sp_K = 0;
+    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sp_members, members.size() * sizeof(int32_t)));
+    TQ_HIP(ctx, hipMemcpy(ctx->d_sp_members, members.data(), members.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    ctx->sp_size.swap(size);
+    ctx->sp_T = T;
+    ctx->sp_K = K;
+    ctx->sp_bound = bound;
+    ctx->sp_max = top[0];
+    ctx->sp_tab_gen = ~0ull;
+    return TQ_OK;
+}
+
+int tq_resolve_species_dev(tq_ctx *ctx, const uint32_t *d_squartets, int64_t Q, uint32_t *d_rstat, double *d_rscor,
+                           uint8_t *d_flags, void *stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || (Q > 0 && (!d_squartets || !d_rstat || !d_rscor)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species_dev: NULL pointer or negative Q");
+    if (int rc = species_ready(ctx, "tq_resolve_species_dev")) return rc;
+    if (Q == 0) return TQ_OK;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;      // before any shared scratch is touched
+    OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
+    return note_dev_api(ctx, (hipStream_t)stream,
+                        launch(ctx, d_squartets, Q, 0, false, false, out, (hipStream_t)stream, NoChunkHook(), true));
+}
+
+int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor,
+                             uint8_t *flags, uint32_t *cmats, double *svds, int32_t *ranks)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || (Q > 0 && (!squartets || !rstat || !rscor)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species: NULL pointer or negative Q");
+    int rc = species_ready(ctx, "tq_resolve_species");
+    if (rc) return rc;
+    if (Q == 0) return TQ_OK;
+    // ids on the host (the kernels re-check them and flag the row); a row that repeats a species can exceed the
+    // call's range bound, so its own product is checked when the bound leaves room for that
+    const uint32_t K = (uint32_t)ctx->sp_K;
+    const bool per_row = (unsigned __int128)ctx->S * ((uint64_t)ctx->sp_max * ctx->sp_max * ctx->sp_max * ctx->sp_max) >=
+                         ((unsigned __int128)1 << 32);
+    for (int64_t i = 0; i < Q; ++i) {
+        const uint32_t *q = squartets + 4 * i;
+        if ((q[0] >= K) | (q[1] >= K) | (q[2] >= K) | (q[3] >= K))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld has a species id >= K=%u", (long long)i, K);
+        if (per_row) {
+            const uint64_t p = (uint64_t)ctx->sp_size[q[0]] * ctx->sp_size[q[1]] * ctx->sp_size[q[2]] * ctx->sp_size[q[3]];
+            if ((unsigned __int128)ctx->S * p >= ((unsigned __int128)1 << 32))
+                return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld: S=%lld x its lineage product %llu >= 2^32",
+                            (long long)i, (long long)ctx->S, (unsigned long long)p);
+        }
+    }
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    HostScratch h;
+    if ((rc = host_scratch(ctx, squartets, Q, cmats, svds, ranks, &h))) return rc;
+    if (!(cmats || svds || ranks)) return species_to_host(ctx, h.dq(), Q, rstat, rscor, flags, h.rstat(), h.rscor(), h.flags());
+    return debug_to_host(ctx, h, Q, 0, true, false, rstat, rscor, flags, cmats, svds, ranks);
+}
+
+int tq_resolve_species(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor, uint8_t *flags)
+{
+    return tq_resolve_species_debug(ctx, squartets, Q, rstat, rscor, flags, nullptr, nullptr, nullptr);
 }
 
 int tq_timing_enable(tq_ctx *ctx, int on)
@@ -1724,6 +1948,12 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
         ctx->batch = value ? value : (1 << 23);
         return TQ_OK;
     }
+    if (!strcmp(name, "species_method")) {
+        if (value < -1 || value > 1)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "species_method must be -1 (auto), 0 (VALU form) or 1 (MFMA form)");
+        ctx->species_method = (int)value;
+        return TQ_OK;
+    }
     if (!strcmp(name, "phases")) {
         if (value != 0 && value != 1 && value != 2 && value != 3)
             return fail(ctx, TQ_ERR_INVALID_ARG, "phases must be 1, 2 or 3");
@@ -1853,6 +2083,7 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
     ctx->have_data = true;
     ctx->locus_runs_ok = true;          // locus ids are the ordinals 0..n-1, one run each
     ctx->scanned_Q = 0;
+    ctx->data_gen++;                    // the species table is rebuilt by the next species call
     if (out_S) *out_S = S;
     return note_dev_api(ctx, stream, TQ_OK);       // the host API must not scan a half-built replicate
 }

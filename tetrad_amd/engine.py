@@ -188,6 +188,43 @@ class QuartetEngine:
             self._h, d_quartets, Q, int(bool(subsample_snps)), _ptr(rstat), _ptr(rscor), _ptr(flags)))
         return rstat, rscor, flags
 
+    # -- species-tree mode ------------------------------------------
+    def set_species(self, species_of, K: int | None = None):
+        """species_of i32[T]: species id in [0, K) per sample, -1 = left out; K defaults to max id + 1."""
+        sp = np.ascontiguousarray(species_of, dtype=np.int32).reshape(-1)
+        if K is None:
+            K = int(sp.max()) + 1 if sp.size else 0
+        self._check(self._lib.tq_set_species(self._h, _ptr(sp), sp.shape[0], int(K)))
+
+    def resolve_species(self, squartets: np.ndarray, debug: bool = False):
+        """Species quartets u32[Q,4] resolved from pooled lineages (full mode): (rstat, rscor, flags) as `resolve`,
+        and with ``debug`` a dict with the pooled cmats u32[Q,3,16,16], svds f64[Q,3,16], ranks i32[Q,3]."""
+        q = squartets
+        if not (isinstance(q, np.ndarray) and q.dtype == np.uint32 and q.flags.c_contiguous):
+            src = np.asarray(squartets)
+            q = pinned_empty((src.size // 4, 4), np.uint32)
+            q[...] = src.reshape(-1, 4)
+        q = q.reshape(-1, 4)
+        Q = q.shape[0]
+        rstat = pinned_empty((Q, 2), np.uint32)
+        rscor = pinned_empty((Q, 3), np.float64)
+        flags = pinned_empty(Q, np.uint8)
+        if debug:
+            cm = np.zeros((Q, 3, 16, 16), np.uint32)
+            sv = np.zeros((Q, 3, 16), np.float64)
+            rk = np.zeros((Q, 3), np.int32)
+            self._check(self._lib.tq_resolve_species_debug(self._h, _ptr(q), Q, _ptr(rstat), _ptr(rscor), _ptr(flags),
+                                                           _ptr(cm), _ptr(sv), _ptr(rk)))
+            return rstat, rscor, flags, dict(cmats=cm, svds=sv, ranks=rk)
+        self._check(self._lib.tq_resolve_species(self._h, _ptr(q), Q, _ptr(rstat), _ptr(rscor), _ptr(flags)))
+        return rstat, rscor, flags
+
+    def resolve_species_dev(self, d_squartets: int, Q: int, d_rstat: int, d_rscor: int, d_flags: int = 0,
+                            stream: int = 0):
+        """Species quartets on the device, results to device arrays, enqueued on `stream`."""
+        self._check(self._lib.tq_resolve_species_dev(self._h, d_squartets, Q, d_rstat, d_rscor, d_flags or None,
+                                                     stream or None))
+
     # -- device-pointer API (addresses as ints, e.g. torch.Tensor.data_ptr()) -------
     def resolve_dev(self, d_quartets: int, Q: int, subsample_snps: bool, d_rstat: int,
                     d_rscor: int, d_flags: int = 0, stream: int = 0):

@@ -157,6 +157,62 @@ def make_c5_source(T: int | None = None, S: int | None = None, seed: int | None 
     return seqarr, tmpmap, spans
 
 
+def _newick(children: dict, root: int) -> str:
+    def w(v):
+        return str(v) if v not in children else "(" + ",".join(w(c) for c in children[v]) + ")"
+    return w(root) + ";"
+
+
+def simulate_species(K: int, n_per: int, S: int, seed: int, p: float = 0.05, p_within: float = 0.01,
+                     missing: float = 0.10, block: float = 0.0):
+    """Several lineages per species: a random species tree on K tips, sites evolved down it
+    (root base uniform, per-branch substitution probability ``p`` with a JC-style redraw), then ``n_per`` lineages per
+    species, each its species' sequence with an extra within-species substitution probability ``p_within``.  Only
+    sites variable among all lineages are kept.  Missing data as in simulate_tmparr / simulate_radseq: a ``missing``
+    share of single cells and, with ``block`` > 0, whole (lineage, locus) blocks.  Samples are in random order.
+    Returns (tmparr u8[T,S], tmpmap u32[S,2], species_of i32[T], species tree newick with the species ids as tips),
+    T = K * n_per."""
+    rng = np.random.default_rng(seed)
+    T = K * n_per
+    children, root = random_tree_children(K, rng)
+    species_of = rng.permutation(np.repeat(np.arange(K, dtype=np.int32), n_per))
+    out = np.empty((T, 0), dtype=np.uint8)
+    while out.shape[1] < S:
+        n = max(1024, int((S - out.shape[1]) * 1.3) + 64)
+        states = {root: rng.integers(0, 4, size=n, dtype=np.uint8)}
+        stack = [root]
+        tips = np.empty((K, n), dtype=np.uint8)
+        while stack:
+            node = stack.pop()
+            st = states.pop(node)
+            if node < K:
+                tips[node] = st
+                continue
+            for ch in children[node]:
+                cs = st.copy()
+                mut = rng.random(n) < p
+                cs[mut] = rng.integers(0, 4, size=int(mut.sum()), dtype=np.uint8)
+                states[ch] = cs
+                stack.append(ch)
+        lin = tips[species_of]
+        mut = rng.random(lin.shape) < p_within
+        lin[mut] = rng.integers(0, 4, size=int(mut.sum()), dtype=np.uint8)
+        variable = (lin != lin[0]).any(axis=0)
+        out = np.concatenate([out, lin[:, variable]], axis=1)
+    tmparr = np.ascontiguousarray(out[:, :S])
+    lens = 1 + rng.poisson(4, size=S)
+    locus = np.repeat(np.arange(S, dtype=np.int64), lens)[:S]
+    if block > 0:
+        nloci = int(locus[-1]) + 1
+        drop = rng.random((T, nloci)) < block
+        tmparr[drop[:, locus]] = 78
+    tmparr[rng.random(tmparr.shape) < missing] = 78
+    tmpmap = np.empty((S, 2), dtype=np.uint32)
+    tmpmap[:, 0] = locus
+    tmpmap[:, 1] = np.arange(S, dtype=np.uint32)
+    return tmparr, tmpmap, species_of, _newick(children, root)
+
+
 def all_quartets(T: int) -> np.ndarray:
     """All C(T,4) quartets in lexicographic order (combinations.py:40-55)."""
     n = comb(T, 4)
