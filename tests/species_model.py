@@ -89,6 +89,49 @@ def score_rows(orc, cmats):
     return rstat, rscor, zero
 
 
+def check_rows(rstat, rscor, flags, cm, orc):
+    """Rows against the pooled matrices `cm` scored by the oracle: nsnps exact, the zero-data flag, topology on
+    unflagged rows, scores within the bar of __graft_entry__.smoke."""
+    m_rstat, m_rscor, zero = score_rows(orc, cm)
+    assert np.array_equal(rstat[:, 1], m_rstat[:, 1])
+    assert np.array_equal((flags & 1) != 0, zero)
+    ok = (flags & 3) == 0
+    assert np.array_equal(rstat[ok, 0], m_rstat[ok, 0])
+    smax = np.array([np.linalg.svd(c.astype(np.float64), compute_uv=False).max() if c.any() else 0.0 for c in cm[:, 0]])
+    live = ~zero
+    assert np.all(np.abs(rscor[live] - m_rscor[live]) <= 1e-6 * np.abs(m_rscor[live]) + 1e-12 * smax[live, None])
+
+
+def lineage_data(sizes, S, seed, missing=0.0, p_within=0.0, left_out=1):
+    """(tmparr u8[T,S], tmpmap, species_of i32[T]) for species of the given sizes: one sequence per species from
+    `synth.simulate_species(K, 1, S)` (sites evolved down a random species tree), copied to each of its lineages with
+    a `p_within` share of cells redrawn and a `missing` share set to N; samples in random order, `left_out` of them
+    in no species.  With both shares 0 a species of n lineages has a count of n at every site."""
+    from tetrad_amd import synth
+    K = len(sizes)
+    rng = np.random.default_rng([seed, S, K])
+    base, tmpmap, order, _ = synth.simulate_species(K, 1, S, seed, p_within=0.0, missing=0.0)
+    seq = np.empty_like(base)
+    seq[order] = base                                   # row k = the sequence of species k
+    sp = rng.permutation(np.concatenate([np.repeat(np.arange(K), sizes), np.full(left_out, -1)])).astype(np.int32)
+    tmparr = seq[np.maximum(sp, 0)]
+    mut = rng.random(tmparr.shape) < p_within
+    tmparr[mut] = rng.integers(0, 4, size=int(mut.sum()), dtype=np.uint8)
+    tmparr[rng.random(tmparr.shape) < missing] = 78
+    return np.ascontiguousarray(tmparr), tmpmap, sp
+
+
+def spike_data(S, n=11):
+    """Four species of `n` lineages, each the copies of one sequence; 60 % of the sites hold the pattern (0, 0, 1, 1)
+    across the four species, the rest is uniform.  At n = 11 and S = 293 000 the pooled row (0, 1, 2, 3) has a bin of
+    2 579 729 559 >= 2^31 and nsnps = 4 263 722 738."""
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 4, size=(4, S)).astype(np.uint8)
+    spike = rng.random(S) < 0.6
+    base[:, spike] = np.array([0, 0, 1, 1], np.uint8)[:, None]
+    return np.repeat(base, n, axis=0), np.repeat(np.arange(4, dtype=np.int32), n)
+
+
 def parse_tips_newick(text: str):
     """Bipartitions (frozensets of tip ids, the side without the smallest tip) of a numeric-tip newick."""
     text = text.strip().rstrip(";")

@@ -111,7 +111,46 @@ def test_range_rule():
     assert species.pooled_range_ok(2**32 // 16 - 1, [2, 2, 2, 2, 1])
     assert not species.pooled_range_ok(2**32 // 16, [2, 2, 2, 2, 1])
     assert not species.pooled_range_ok(10, [256, 1, 1, 1])
+    # the edge the GPU tests run at: 11^4 x 293 352 = 4 294 966 632 < 2^32 = 4 294 967 296 <= 11^4 x 293 353
+    assert species.pooled_range_ok(293_352, [11, 11, 11, 11])
+    assert not species.pooled_range_ok(293_353, [11, 11, 11, 11])
+    assert species.pooled_range_ok(1, [255, 255, 255, 255, 2, 1]) and not species.pooled_range_ok(2, [255] * 4)
+    assert species.pooled_range_ok(20_000, [12, 13, 16, 17, 20]) and species.pooled_range_ok(200, [255, 100, 40, 17, 3, 1])
     assert not species.pooled_range_ok(10, [1, 1, 1])
+
+
+def test_rows_with_bit_31_through_the_host_consumers(oracle):
+    """The data of the GPU bit-31 test on the CPU: the model's figures, then rows with nsnps >= 2^31 through the TSV
+    formatter and the host concordance accumulator (u64 nsnps sum)."""
+    from species_model import spike_data
+    from tetrad_amd.concordance import Concordance
+    from tetrad_amd.distributor import format_tsv_bytes
+    tmparr, sp = spike_data(293_000)
+    rows = np.array([[0, 1, 2, 3], [0, 2, 1, 3], [3, 2, 1, 0], [0, 0, 2, 2]], np.uint32)
+    cm = pooled_factored(tmparr, sp, 4, rows)
+    assert int(cm[0].max()) == 2_579_729_559 and int(cm[0, 0].sum(dtype=np.uint64)) == 4_263_722_738
+    rstat, rscor, zero = score_rows(oracle, cm)
+    assert not zero.any() and np.all(np.isfinite(rscor)) and int(rstat[0, 1]) == 4_263_722_738
+    lines = format_tsv_bytes(rows, rscor, rstat).decode().splitlines()
+    assert [ln.split("\t")[8] for ln in lines] == [str(int(n)) for n in rstat[:, 1]]
+    assert lines[0].startswith("0\t1\t2\t3\t") and lines[0].endswith("\t4263722738")
+    acc = Concordance("((0,1),2,(3,4));")
+    acc.add(rows, rscor, rstat)
+    r = acc.raw()
+    assert r["skipped"] == 1 and int(r["edge_counts"][:, 1:5].sum()) == 3
+    assert int(r["edge_counts"][:, 5].sum()) == sum(int(n) for n in rstat[:3, 1]) > 2**33
+
+
+def test_lineage_data_counts():
+    from species_model import lineage_data, species_counts
+    sizes = (255, 100, 40, 17, 3, 1)
+    tmparr, tmpmap, sp = lineage_data(sizes, 200, 31)
+    assert tmparr.shape == (417, 200) and np.bincount(sp[sp >= 0]).tolist() == list(sizes)
+    assert (species_counts(tmparr, sp, 6).max(axis=2) == np.array(sizes)[:, None]).all()
+    noisy, _, sp2 = lineage_data(sizes, 200, 31, missing=0.2, p_within=0.02)
+    assert np.array_equal(sp, sp2) and 0.15 < (noisy == 78).mean() < 0.25
+    cnt = species_counts(noisy, sp, 6)
+    assert cnt[0].max() > 150 and (cnt.sum(axis=2) <= np.array(sizes)[:, None]).all()
 
 
 def test_species_quartets():
