@@ -321,6 +321,50 @@ int tq_conc_shape(const tq_conc *acc, int64_t *T, int64_t *n_edges, int64_t *mas
 int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t *masks, int64_t *tip_counts,
                  int64_t *skipped);
 
+/* Exact quartet supertree: Quartet MaxCut level by level with integer graph weights, the passes
+ * over the quartets on the device next to the resolved rows.  A second path beside tq_qmc_splits + tq_qmc_tree, which
+ * stay as they are; the host and the device execution of it give the same newick string, bit for bit, for any row
+ * order and any split of the rows over several adds.
+ *   Row rule: the filters, split and weight of tq_qmc_splits (weights 0-3, min_snps taken as max(1, min_snps), scores
+ *   as their "%.6f" text reads back); the weight is kept as the integer k = weight x 10^5 rounded as "%.5f" rounds.
+ *   Skipped (counted, kept nowhere): a row the filters drop, a taxon >= ntaxa, a repeated taxon, topology > 2, flags
+ *   TQ_FLAG_BAD_INDEX / TQ_FLAG_INVALID_DIAGNOSTIC, k == 0, a weight that is not finite or >= 4e9.
+ *   tq_stree_create  capacity_rows = rows that may be added between two resets (kept or not), < 2^31.  `ctx` NULL: host
+ *                    back end only, 1 <= ntaxa <= 65535.  With a context: 4 <= ntaxa <= 1024, all device and page-locked
+ *                    memory is allocated here (56 bytes per row of capacity, 24 x ntaxa^2 bytes of each kind for a level's
+ *                    matrices).  The context must outlive the accumulator; messages go to tq_last_error(ctx).
+ *   tq_stree_add     host rows, synchronous; arrays as tq_conc_add.  More rows than the capacity: TQ_ERR_INVALID_ARG,
+ *                    nothing is added.
+ *   tq_stree_add_dev the same rows as device pointers, enqueued on `stream`, allocation-free; calls on different streams
+ *                    are ordered in call order.  Host and device rows do not mix in one accumulator (until a reset).
+ *   tq_stree_graph   the root graph of the rows added so far, any output may be NULL: G / B u64[ntaxa][ntaxa] symmetric,
+ *                    G[u][v] = sum of k over the kept rows that have u and v on different sides of their split, B[u][v] =
+ *                    the same for rows that pair u with v; kept / skipped rows; *sum_k = sum of k (2^64 - 1 when larger).
+ *   tq_stree_rows    the kept rows: splits u32[kept][4] = "a,b|c,d", k u64[kept] (either may be NULL), *n = kept.  Host
+ *                    rows come in the order added, device rows in any order.
+ *   tq_stree_build   the tree of the rows added so far as newick with the taxon numbers as tip labels, *written = its
+ *                    length (TQ_ERR_OOM with the needed size when cap is too small), *levels = levels of the recursion.
+ *                    Device rows: the passes run on `stream`, two synchronisations of it per level.  Refused
+ *                    (TQ_ERR_INVALID_ARG) when 6 x sum of k >= 2^53.  The rows stay: build may be repeated with any seed.
+ *   tq_stree_level_stats  of the last build: *n_levels (at most 64 are kept), out f64[n_levels][6] = {open nodes, live
+ *                    quartets, cells of one matrix, graph pass ms, host search ms, partition pass ms} (wall clock of the
+ *                    calling thread, synchronisation included).
+ * Option "stree_lds" (tq_set_option): 1 (default) = the graph pass sums in private LDS counters where a level's cells fit
+ * (at most 8128 per matrix), 0 = global integer atomics only.  Both are exact.                                        */
+typedef struct tq_stree tq_stree;
+int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int weights, int64_t min_snps, double min_ratio,
+                    tq_ctx *ctx);
+void tq_stree_destroy(tq_stree *acc);
+int tq_stree_reset(tq_stree *acc);
+int tq_stree_add(tq_stree *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
+                 int64_t n);
+int tq_stree_add_dev(tq_stree *acc, const uint32_t *d_quartets, const uint32_t *d_rstat, const double *d_rscor,
+                     const uint8_t *d_flags, int64_t n, void *stream);
+int tq_stree_graph(tq_stree *acc, uint64_t *G, uint64_t *B, int64_t *kept, int64_t *skipped, uint64_t *sum_k);
+int tq_stree_rows(tq_stree *acc, uint32_t *splits, uint64_t *k, int64_t *n);
+int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_t cap, int64_t *written, int64_t *levels);
+int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out);
+
 /* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
  * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
  * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.

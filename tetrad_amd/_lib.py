@@ -35,6 +35,8 @@ SYMBOLS = [
     "tq_set_option", "tq_device_info", "tq_debug_fetch", "tq_debug_bdsqr",
     "tq_format_tsv", "tq_format_qmc", "tq_qmc_tree", "tq_qmc_splits", "tq_unrank", "tq_numpy_choice_tail",
     "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
+    "tq_stree_create", "tq_stree_destroy", "tq_stree_reset", "tq_stree_add", "tq_stree_add_dev", "tq_stree_graph",
+    "tq_stree_rows", "tq_stree_build", "tq_stree_level_stats",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
 ]
 
@@ -186,6 +188,24 @@ def load() -> ctypes.CDLL:
     lib.tq_conc_shape.restype = i32
     lib.tq_conc_read.argtypes = [vp, vp, vp, vp, vp, c.POINTER(i64)]
     lib.tq_conc_read.restype = i32
+    lib.tq_stree_create.argtypes = [c.POINTER(vp), i64, i64, i32, i64, c.c_double, vp]
+    lib.tq_stree_create.restype = i32
+    lib.tq_stree_destroy.argtypes = [vp]
+    lib.tq_stree_destroy.restype = None
+    lib.tq_stree_reset.argtypes = [vp]
+    lib.tq_stree_reset.restype = i32
+    lib.tq_stree_add.argtypes = [vp, vp, vp, vp, vp, i64]
+    lib.tq_stree_add.restype = i32
+    lib.tq_stree_add_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    lib.tq_stree_add_dev.restype = i32
+    lib.tq_stree_graph.argtypes = [vp, vp, vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_uint64)]
+    lib.tq_stree_graph.restype = i32
+    lib.tq_stree_rows.argtypes = [vp, vp, vp, c.POINTER(i64)]
+    lib.tq_stree_rows.restype = i32
+    lib.tq_stree_build.argtypes = [vp, c.c_uint64, vp, vp, i64, c.POINTER(i64), c.POINTER(i64)]
+    lib.tq_stree_build.restype = i32
+    lib.tq_stree_level_stats.argtypes = [vp, c.POINTER(i64), vp]
+    lib.tq_stree_level_stats.restype = i32
     lib.tq_set_species.argtypes = [vp, vp, i64, i64]
     lib.tq_set_species.restype = i32
     lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]

@@ -126,27 +126,11 @@ inline double qmc_local_search(const std::vector<double> &G, const std::vector<d
     return good - alpha * bad;
 }
 
-// best bipartition of n >= 4 vertices; false when the quartets carry no signal at all
-inline bool qmc_best_cut(const std::vector<QmcQuartet> &qs, const std::vector<int32_t> &index_of_label_dense,
-                         int n, QmcRng &rng, std::vector<uint8_t> &best_side)
+// the cut search on a built graph: symmetric n x n matrices G (good edges) and B (bad edges), total = sum of the
+// quartet weights; best bipartition of n >= 4 vertices, false when the quartets carry no signal at all
+inline bool qmc_search(const std::vector<double> &G, const std::vector<double> &B, double total, int n, QmcRng &rng,
+                       std::vector<uint8_t> &best_side)
 {
-    std::vector<double> G((size_t)n * n, 0.0), B((size_t)n * n, 0.0);
-    auto addw = [&](std::vector<double> &M, int u, int v, double w) {
-        M[(size_t)u * n + v] += w;
-        M[(size_t)v * n + u] += w;
-    };
-    double total = 0.0;
-    for (const auto &q : qs) {
-        const int a = index_of_label_dense[q.t[0]], b = index_of_label_dense[q.t[1]], c = index_of_label_dense[q.t[2]],
-                  d = index_of_label_dense[q.t[3]];
-        addw(B, a, b, q.w);
-        addw(B, c, d, q.w);
-        addw(G, a, c, q.w);
-        addw(G, a, d, q.w);
-        addw(G, b, c, q.w);
-        addw(G, b, d, q.w);
-        total += q.w;
-    }
     if (!(total > 0.0)) return false;
     if (n == 4) {                                                   // the three 2|2 splits, exhaustively
         double best = -1.0;
@@ -198,6 +182,30 @@ inline bool qmc_best_cut(const std::vector<QmcQuartet> &qs, const std::vector<in
         alpha = good / bad;                                         // Dinkelbach step for max good / bad
     }
     return best_ratio >= 0.0;
+}
+
+// best bipartition of n >= 4 vertices; false when the quartets carry no signal at all
+inline bool qmc_best_cut(const std::vector<QmcQuartet> &qs, const std::vector<int32_t> &index_of_label_dense,
+                         int n, QmcRng &rng, std::vector<uint8_t> &best_side)
+{
+    std::vector<double> G((size_t)n * n, 0.0), B((size_t)n * n, 0.0);
+    auto addw = [&](std::vector<double> &M, int u, int v, double w) {
+        M[(size_t)u * n + v] += w;
+        M[(size_t)v * n + u] += w;
+    };
+    double total = 0.0;
+    for (const auto &q : qs) {
+        const int a = index_of_label_dense[q.t[0]], b = index_of_label_dense[q.t[1]], c = index_of_label_dense[q.t[2]],
+                  d = index_of_label_dense[q.t[3]];
+        addw(B, a, b, q.w);
+        addw(B, c, d, q.w);
+        addw(G, a, c, q.w);
+        addw(G, a, d, q.w);
+        addw(G, b, c, q.w);
+        addw(G, b, d, q.w);
+        total += q.w;
+    }
+    return qmc_search(G, B, total, n, rng, best_side);
 }
 
 inline int32_t qmc_star(QmcForest &F, const std::vector<int32_t> &taxa)

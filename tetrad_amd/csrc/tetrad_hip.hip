@@ -29,6 +29,7 @@
 //   jacobi.hpp    tq_svd_kernel: one-sided Jacobi singular values in registers (alternative)
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
+//   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
 //   species.hpp   tq_species_table_kernel + tq_species_mfma_kernel / tq_species_pool_kernel: pooled count matrices of
 //                 species quartets (species mode; MFMA form, VALU form)
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
@@ -40,6 +41,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -72,6 +74,7 @@ namespace {
 #include "qmc.hpp"
 #include "concordance.hpp"
 #include "species.hpp"
+#include "supertree.hpp"
 
 }  // namespace
 
@@ -156,6 +159,7 @@ struct tq_ctx {
     int share_c = 0;                // 1: scan kernel variant that also shares row c inside a workgroup (scan.hpp: SHC;
                                     // measured slower everywhere -- the kernel is LDS/VALU-bound, not byte-bound -- kept as an A/B option)
     int svd_wpc = 0;                // blocks per CU of the bidiag / bdsqr grids (0 = one pass per block)
+    int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
     const uint32_t *scanned_q = nullptr;
     int64_t scanned_Q = 0;
@@ -1362,6 +1366,178 @@ int conc_wait(tq_conc *acc)
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------
+// Exact supertree accumulator (supertree.hpp).  Host adds keep the weighted splits in host vectors; device adds append
+// them to the root store on the device.  A build never modifies either, so it may be repeated with any seed.
+// ---------------------------------------------------------------------------------------------
+struct tq_stree {
+    tq_ctx *ctx = nullptr;          // device adds and device builds need one; messages go to tq_last_error(ctx)
+    int64_t ntaxa = 0, capacity = 0;
+    int weights = 0;
+    uint32_t min_snps = 1;
+    double min_ratio = 1.0;
+    int mode = 0;                   // 0: nothing added yet, 1: host rows, 2: device rows (they do not mix)
+    int64_t rows_in = 0;            // rows offered since create / reset (capacity counts these)
+    // host rows
+    std::vector<uint64_t> h_t, h_k;
+    int64_t h_skipped = 0;
+    unsigned __int128 h_sum = 0;
+    // device rows and the working state of a build
+    uint64_t *d_root_t = nullptr, *d_root_k = nullptr;
+    uint64_t *d_wt[2] = {nullptr, nullptr}, *d_wk[2] = {nullptr, nullptr};
+    uint32_t *d_wn[2] = {nullptr, nullptr};
+    unsigned long long *d_cnt = nullptr, *d_mat = nullptr;
+    StreeNode *d_nodes = nullptr;
+    uint32_t *d_map = nullptr;
+    uint64_t *p_mat = nullptr;      // page-locked: a level's matrices, its nodes and side map, the counters
+    StreeNode *p_nodes = nullptr;
+    uint32_t *p_map = nullptr;
+    unsigned long long *p_cnt = nullptr;
+    int64_t max_cells = 0, max_nodes = 0;
+    int num_cu = 1;
+    hipEvent_t ev = nullptr;        // recorded behind the last device add
+    bool pending = false;
+    hipStream_t last = nullptr;
+    hipStream_t own = nullptr;      // stream of tq_stree_graph / tq_stree_rows, which take none
+    std::vector<StreeLevelStat> stats;   // of the last build
+};
+
+namespace {
+
+void stree_free_dev(tq_stree *a)
+{
+    void *dev[] = {a->d_root_t, a->d_root_k, a->d_wt[0], a->d_wt[1], a->d_wk[0], a->d_wk[1], a->d_wn[0], a->d_wn[1],
+                   a->d_cnt, a->d_mat, a->d_nodes, a->d_map};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt};
+    for (void *p : pin)
+        if (p) (void)hipHostFree(p);
+    if (a->ev) (void)hipEventDestroy(a->ev);
+    if (a->own) (void)hipStreamDestroy(a->own);
+}
+
+#define STREE_HIP(call)                                                                       \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            err = std::string(#call) + " failed: " + hipGetErrorString(e_);                   \
+            return e_ == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP;                       \
+        }                                                                                     \
+    } while (0)
+
+// the two operations on the device, everything on the stream of the build call; each ends with one synchronisation
+struct StreeDevBackend : StreeBackend {
+    tq_stree *a = nullptr;
+    hipStream_t st = nullptr;
+    int cur = -1;                   // work buffer that holds the live quartets, -1: the root store
+    int64_t n_live = 0;
+
+    void fill(StreePassArgs &p) const
+    {
+        p.t4 = cur < 0 ? a->d_root_t : a->d_wt[cur];
+        p.k = cur < 0 ? a->d_root_k : a->d_wk[cur];
+        p.node = cur < 0 ? nullptr : a->d_wn[cur];
+        p.n_live = &a->d_cnt[cur < 0 ? SC_KEPT : SC_LIVE0 + cur];
+        p.nodes = a->d_nodes;
+        p.mat = a->d_mat;
+    }
+    int begin(int64_t &live, std::string &err) override
+    {
+        STREE_HIP(hipMemcpyAsync(a->p_cnt, a->d_cnt, SC_WORDS * 8, hipMemcpyDeviceToHost, st));
+        STREE_HIP(hipStreamSynchronize(st));
+        cur = -1;
+        live = n_live = (int64_t)a->p_cnt[SC_KEPT];
+        return TQ_OK;
+    }
+    int graphs(const std::vector<StreeNode> &nodes, int64_t cells, int, const uint64_t *&mat, std::string &err) override
+    {
+        if (cells > a->max_cells || (int64_t)nodes.size() > a->max_nodes) {
+            err = "a level exceeds the cells or nodes the accumulator was created for";
+            return TQ_ERR_INVALID_ARG;
+        }
+        memcpy(a->p_nodes, nodes.data(), nodes.size() * sizeof(StreeNode));
+        STREE_HIP(hipMemcpyAsync(a->d_nodes, a->p_nodes, nodes.size() * sizeof(StreeNode), hipMemcpyHostToDevice, st));
+        STREE_HIP(hipMemsetAsync(a->d_mat, 0, (size_t)(2 * cells) * 8, st));
+        StreePassArgs p{};
+        fill(p);
+        p.n_nodes = (int32_t)nodes.size();
+        p.cells = cells;
+        if (a->ctx->stree_lds && cells <= STREE_LDS_CELLS && n_live >= 4096) {
+            const int pairs = (int)std::max<int64_t>(1, std::min<int64_t>((n_live + 16383) / 16384, 64));
+            hipLaunchKernelGGL(tq_stree_graph_lds_kernel, dim3(2 * pairs), dim3(STREE_LDS_THREADS), 0, st, p);
+        } else {
+            const int G = (int)std::max<int64_t>(1, std::min<int64_t>((n_live + STREE_THREADS - 1) / STREE_THREADS,
+                                                                     8 * (int64_t)a->num_cu));
+            hipLaunchKernelGGL(tq_stree_graph_kernel, dim3(G), dim3(STREE_THREADS), 0, st, p);
+        }
+        STREE_HIP(hipGetLastError());
+        STREE_HIP(hipMemcpyAsync(a->p_mat, a->d_mat, (size_t)(2 * cells) * 8, hipMemcpyDeviceToHost, st));
+        STREE_HIP(hipStreamSynchronize(st));
+        mat = a->p_mat;
+        return TQ_OK;
+    }
+    int partition(const std::vector<StreeNode> &nodes, const std::vector<uint32_t> &map, int, int64_t &live,
+                  std::string &err) override
+    {
+        if ((int64_t)nodes.size() > a->max_nodes || (int64_t)map.size() > 3 * a->max_nodes) {
+            err = "a level exceeds the nodes the accumulator was created for";
+            return TQ_ERR_INVALID_ARG;
+        }
+        const int dst = cur < 0 ? 0 : cur ^ 1;
+        memcpy(a->p_nodes, nodes.data(), nodes.size() * sizeof(StreeNode));
+        memcpy(a->p_map, map.data(), map.size() * 4);
+        STREE_HIP(hipMemcpyAsync(a->d_nodes, a->p_nodes, nodes.size() * sizeof(StreeNode), hipMemcpyHostToDevice, st));
+        STREE_HIP(hipMemcpyAsync(a->d_map, a->p_map, map.size() * 4, hipMemcpyHostToDevice, st));
+        STREE_HIP(hipMemsetAsync(&a->d_cnt[SC_LIVE0 + dst], 0, 8, st));
+        StreePassArgs p{};
+        fill(p);
+        p.n_nodes = (int32_t)nodes.size();
+        p.map = a->d_map;
+        p.out_t4 = a->d_wt[dst];
+        p.out_k = a->d_wk[dst];
+        p.out_node = a->d_wn[dst];
+        p.out_live = &a->d_cnt[SC_LIVE0 + dst];
+        const int G = (int)std::max<int64_t>(1, std::min<int64_t>((n_live + STREE_THREADS - 1) / STREE_THREADS,
+                                                                 8 * (int64_t)a->num_cu));
+        hipLaunchKernelGGL(tq_stree_partition_kernel, dim3(G), dim3(STREE_THREADS), 0, st, p);
+        STREE_HIP(hipGetLastError());
+        STREE_HIP(hipMemcpyAsync(&a->p_cnt[SC_LIVE0 + dst], &a->d_cnt[SC_LIVE0 + dst], 8, hipMemcpyDeviceToHost, st));
+        STREE_HIP(hipStreamSynchronize(st));
+        cur = dst;
+        live = n_live = (int64_t)a->p_cnt[SC_LIVE0 + dst];
+        return TQ_OK;
+    }
+};
+
+// orders `st` behind the device adds made on another stream
+int stree_join(tq_stree *acc, hipStream_t st)
+{
+    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+    if (acc->pending && st != acc->last) TQ_HIP(acc->ctx, hipStreamWaitEvent(st, acc->ev, 0));
+    return TQ_OK;
+}
+
+// kept / skipped rows and the sum of k of everything added so far, read on `st` behind the device adds
+int stree_counts(tq_stree *acc, hipStream_t st, int64_t &kept, int64_t &skipped, unsigned __int128 &sum)
+{
+    if (acc->mode == 2) {
+        if (int rc = stree_join(acc, st)) return rc;
+        TQ_HIP(acc->ctx, hipMemcpyAsync(acc->p_cnt, acc->d_cnt, SC_WORDS * 8, hipMemcpyDeviceToHost, st));
+        TQ_HIP(acc->ctx, hipStreamSynchronize(st));
+        kept = (int64_t)acc->p_cnt[SC_KEPT];
+        skipped = (int64_t)acc->p_cnt[SC_SKIPPED];
+        sum = (unsigned __int128)acc->p_cnt[SC_SUM_LO] + ((unsigned __int128)acc->p_cnt[SC_SUM_HI] << 32);
+    } else {
+        kept = (int64_t)acc->h_t.size();
+        skipped = acc->h_skipped;
+        sum = acc->h_sum;
+    }
+    return TQ_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int tq_create(tq_ctx **out, int device_id)
@@ -1889,6 +2065,11 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
     }
     if (!strcmp(name, "share_c")) {
         ctx->share_c = value != 0;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "stree_lds")) {
+        if (value < 0 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "stree_lds must be 0 or 1");
+        ctx->stree_lds = (int)value;
         return TQ_OK;
     }
     if (!strcmp(name, "svd_wpc")) {
@@ -2430,6 +2611,288 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
     if (tip_counts)
         for (int64_t i = 0; i < 2 * (int64_t)t.T; ++i) tip_counts[i] = (int64_t)(dv[tb + i] + acc->hi[tb + i]);
     if (skipped) *skipped = (int64_t)(dv[tb + 2 * t.T] + acc->hi[tb + 2 * t.T]);
+    return TQ_OK;
+}
+
+int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int weights, int64_t min_snps, double min_ratio,
+                    tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: out is NULL");
+    *out = nullptr;
+    if (ntaxa < 1 || ntaxa > 65535) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: ntaxa must be 1..65535");
+    if (ctx && (ntaxa < 4 || ntaxa > STREE_T_MAX))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: the device path takes 4 <= ntaxa <= %d", STREE_T_MAX);
+    if (capacity_rows < 0 || capacity_rows >= (int64_t(1) << 31))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: capacity_rows must be 0..2^31-1");
+    if (weights < 0 || weights > 3) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: no weight strategy %d", weights);
+    if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: min_ratio is NaN");
+    tq_stree *acc = new (std::nothrow) tq_stree();
+    if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
+    acc->ctx = ctx;
+    acc->ntaxa = ntaxa;
+    acc->capacity = capacity_rows;
+    acc->weights = weights;
+    acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);
+    acc->min_ratio = min_ratio;
+    if (ctx) {
+        acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+        acc->max_nodes = 3 * ntaxa;                                  // the taxa of a level number fewer than 3 ntaxa
+        acc->max_cells = 3 * ntaxa * ntaxa / 2 + 16;                 // sum of n (n - 1) / 2 with n <= ntaxa, sum of n < 3 ntaxa
+        const size_t rows = (size_t)std::max<int64_t>(1, capacity_rows);
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_root_t, rows * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_root_k, rows * 8);
+        for (int b = 0; b < 2; ++b) {
+            if (e == hipSuccess) e = hipMalloc((void **)&acc->d_wt[b], rows * 8);
+            if (e == hipSuccess) e = hipMalloc((void **)&acc->d_wk[b], rows * 8);
+            if (e == hipSuccess) e = hipMalloc((void **)&acc->d_wn[b], rows * 4);
+        }
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_cnt, SC_WORDS * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_mat, (size_t)acc->max_cells * 16);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_nodes, (size_t)acc->max_nodes * sizeof(StreeNode));
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_map, (size_t)acc->max_nodes * 3 * 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_mat, (size_t)acc->max_cells * 16, hipHostMallocDefault);
+        if (e == hipSuccess)
+            e = hipHostMalloc((void **)&acc->p_nodes, (size_t)acc->max_nodes * sizeof(StreeNode), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_map, (size_t)acc->max_nodes * 3 * 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_cnt, SC_WORDS * 8, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMemset(acc->d_cnt, 0, SC_WORDS * 8);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            stree_free_dev(acc);
+            delete acc;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_stree_create: %s", hipGetErrorString(e));
+        }
+    }
+    *out = acc;
+    return TQ_OK;
+}
+
+void tq_stree_destroy(tq_stree *acc)
+{
+    if (!acc) return;
+    if (acc->ctx) {
+        (void)hipSetDevice(acc->ctx->device);
+        if (acc->pending) (void)hipEventSynchronize(acc->ev);
+        stree_free_dev(acc);
+    }
+    delete acc;
+}
+
+int tq_stree_reset(tq_stree *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    acc->h_t.clear();
+    acc->h_k.clear();
+    acc->h_skipped = 0;
+    acc->h_sum = 0;
+    acc->rows_in = 0;
+    acc->mode = 0;
+    if (acc->ctx) {
+        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+        if (acc->pending) TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
+        acc->pending = false;
+        TQ_HIP(acc->ctx, hipMemsetAsync(acc->d_cnt, 0, SC_WORDS * 8, acc->own));   // not the null stream: it would wait
+        TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));                           // for every other stream's work
+    }
+    return TQ_OK;
+}
+
+int tq_stree_add(tq_stree *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
+                 int64_t n)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (n < 0 || (n > 0 && (!quartets || !rstat || !rscor)))
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: NULL pointer or negative n");
+    if (acc->mode == 2) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: device rows were added; host rows do not mix");
+    if (acc->rows_in + n > acc->capacity)
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: %lld rows added, %lld more exceed the capacity of %lld",
+                    (long long)acc->rows_in, (long long)n, (long long)acc->capacity);
+    if (n == 0) return TQ_OK;
+    try {
+        acc->h_t.reserve(acc->h_t.size() + (size_t)n);
+        acc->h_k.reserve(acc->h_k.size() + (size_t)n);
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_add: out of host memory");
+    }
+    acc->mode = 1;
+    acc->rows_in += n;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t *q = quartets + 4 * i;
+        uint32_t sp[4];
+        uint64_t k;
+        if (!stree_row((uint32_t)acc->ntaxa, acc->weights, acc->min_snps, acc->min_ratio, q[0], q[1], q[2], q[3], rstat[2 * i],
+                       rstat[2 * i + 1], rscor[3 * i], rscor[3 * i + 1], rscor[3 * i + 2], flags ? flags[i] : 0u, sp, k)) {
+            ++acc->h_skipped;
+            continue;
+        }
+        acc->h_t.push_back((uint64_t)sp[0] | (uint64_t)sp[1] << 16 | (uint64_t)sp[2] << 32 | (uint64_t)sp[3] << 48);
+        acc->h_k.push_back(k);
+        acc->h_sum += k;
+    }
+    return TQ_OK;
+}
+
+int tq_stree_add_dev(tq_stree *acc, const uint32_t *d_quartets, const uint32_t *d_rstat, const double *d_rscor,
+                     const uint8_t *d_flags, int64_t n, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: the accumulator was created without a context");
+    if (n < 0 || (n > 0 && (!d_quartets || !d_rstat || !d_rscor)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: NULL pointer or negative n");
+    if (acc->mode == 1) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: host rows were added; device rows do not mix");
+    if (acc->rows_in + n > acc->capacity)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: %lld rows added, %lld more exceed the capacity of %lld",
+                    (long long)acc->rows_in, (long long)n, (long long)acc->capacity);
+    if (n == 0) return TQ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = stree_join(acc, st)) return rc;                    // appends in call order
+    StreeAddArgs a{d_quartets, d_rstat, d_rscor, d_flags, n, (uint32_t)acc->ntaxa, acc->min_snps, acc->weights,
+                   acc->min_ratio, acc->d_root_t, acc->d_root_k, acc->capacity, acc->d_cnt};
+    hipLaunchKernelGGL(tq_stree_rows_kernel, dim3((unsigned)((n + STREE_THREADS - 1) / STREE_THREADS)), dim3(STREE_THREADS), 0,
+                       st, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_stree_add_dev: launch failed: %s", hipGetErrorString(e));
+    TQ_HIP(ctx, hipEventRecord(acc->ev, st));
+    acc->pending = true;
+    acc->last = st;
+    acc->mode = 2;
+    acc->rows_in += n;
+    return TQ_OK;
+}
+
+int tq_stree_graph(tq_stree *acc, uint64_t *G, uint64_t *B, int64_t *kept, int64_t *skipped, uint64_t *sum_k)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    int64_t nk = 0, ns = 0;
+    unsigned __int128 sum = 0;
+    if (int rc = stree_counts(acc, acc->own, nk, ns, sum)) return rc;
+    if (kept) *kept = nk;
+    if (skipped) *skipped = ns;
+    if (sum_k) *sum_k = (sum >> 64) ? ~0ull : (uint64_t)sum;
+    if (!G && !B) return TQ_OK;
+    if (sum >> 63) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_graph: the sum of k exceeds 2^63, a cell could wrap");
+    const int64_t T = acc->ntaxa;
+    if (G) memset(G, 0, (size_t)T * T * 8);
+    if (B) memset(B, 0, (size_t)T * T * 8);
+    if (T < 4 || nk == 0) return TQ_OK;
+    try {
+        std::vector<StreeNode> nodes(1);
+        nodes[0].n = (int32_t)T;
+        nodes[0].childA = nodes[0].childB = -1;
+        const int64_t cells = T * (T - 1) / 2;
+        const uint64_t *mat = nullptr;
+        std::string err;
+        StreeHostBackend hb;
+        StreeDevBackend db;
+        int64_t live = 0;
+        int rc;
+        if (acc->mode == 2) {
+            db.a = acc;
+            db.st = acc->own;
+            rc = db.begin(live, err);
+            if (!rc) rc = db.graphs(nodes, cells, 0, mat, err);
+        } else {
+            hb.root_t = &acc->h_t;
+            hb.root_k = &acc->h_k;
+            rc = hb.begin(live, err);
+            if (!rc) rc = hb.graphs(nodes, cells, 0, mat, err);
+        }
+        if (rc) return fail(acc->ctx, rc, "tq_stree_graph: %s", err.c_str());
+        int64_t c = 0;
+        for (int64_t u = 0; u < T; ++u)
+            for (int64_t v = u + 1; v < T; ++v, ++c) {
+                if (G) G[u * T + v] = G[v * T + u] = mat[c];
+                if (B) B[u * T + v] = B[v * T + u] = mat[cells + c];
+            }
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_graph: out of host memory");
+    }
+    return TQ_OK;
+}
+
+int tq_stree_rows(tq_stree *acc, uint32_t *splits, uint64_t *k, int64_t *n)
+{
+    if (!acc || !n) return TQ_ERR_INVALID_ARG;
+    int64_t nk = 0, ns = 0;
+    unsigned __int128 sum = 0;
+    if (int rc = stree_counts(acc, acc->own, nk, ns, sum)) return rc;
+    *n = nk;
+    if (nk == 0 || (!splits && !k)) return TQ_OK;
+    const uint64_t *t4 = acc->h_t.data(), *kk = acc->h_k.data();
+    std::vector<uint64_t> tmp;
+    if (acc->mode == 2) {
+        try {
+            tmp.resize((size_t)nk * 2);
+        } catch (const std::bad_alloc &) {
+            return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_rows: out of host memory");
+        }
+        TQ_HIP(acc->ctx, hipMemcpyAsync(tmp.data(), acc->d_root_t, (size_t)nk * 8, hipMemcpyDeviceToHost, acc->own));
+        TQ_HIP(acc->ctx, hipMemcpyAsync(tmp.data() + nk, acc->d_root_k, (size_t)nk * 8, hipMemcpyDeviceToHost, acc->own));
+        TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));
+        t4 = tmp.data();
+        kk = tmp.data() + nk;
+    }
+    for (int64_t i = 0; i < nk; ++i) {
+        if (splits)
+            for (int j = 0; j < 4; ++j) splits[4 * i + j] = (uint32_t)((t4[i] >> (16 * j)) & 0xFFFF);
+        if (k) k[i] = kk[i];
+    }
+    return TQ_OK;
+}
+
+int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_t cap, int64_t *written, int64_t *levels)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (cap < 0 || !written || (cap > 0 && !out))
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_build: NULL pointer or negative cap");
+    *written = 0;
+    int64_t nk = 0, ns = 0;
+    unsigned __int128 sum = 0;
+    if (int rc = stree_counts(acc, (hipStream_t)stream, nk, ns, sum)) return rc;
+    if (sum >= STREE_SUM_LIMIT)
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG,
+                    "tq_stree_build: 6 x the sum of the integer weights reaches 2^53 (sum of k >= %llu): the graph would "
+                    "not be exact in doubles", (unsigned long long)STREE_SUM_LIMIT);
+    try {
+        std::string nwk, err;
+        int64_t lv = 0;
+        int rc;
+        if (acc->mode == 2) {
+            StreeDevBackend db;
+            db.a = acc;
+            db.st = (hipStream_t)stream;
+            rc = stree_build(db, acc->ntaxa, seed, nwk, lv, acc->stats, err);
+        } else {
+            StreeHostBackend hb;
+            hb.root_t = &acc->h_t;
+            hb.root_k = &acc->h_k;
+            rc = stree_build(hb, acc->ntaxa, seed, nwk, lv, acc->stats, err);
+        }
+        if (rc) return fail(acc->ctx, rc, "tq_stree_build: %s", err.c_str());
+        if (levels) *levels = lv;
+        *written = (int64_t)nwk.size();
+        if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
+        memcpy(out, nwk.data(), nwk.size());
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_build: out of host memory");
+    }
+}
+
+int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out)
+{
+    if (!acc || !n_levels) return TQ_ERR_INVALID_ARG;
+    *n_levels = (int64_t)acc->stats.size();
+    if (out)
+        for (size_t i = 0; i < acc->stats.size(); ++i) {
+            const StreeLevelStat &s = acc->stats[i];
+            double *o = out + 6 * i;
+            o[0] = (double)s.nodes; o[1] = (double)s.live; o[2] = (double)s.cells;
+            o[3] = s.graph_ms; o[4] = s.search_ms; o[5] = s.part_ms;
+        }
     return TQ_OK;
 }
 

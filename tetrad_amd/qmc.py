@@ -91,6 +91,136 @@ def infer_supertree_from_arrays(rqrts, rscor, rstat, ntaxa: int, weights: int = 
     return qmc_tree(splits, w if weights else None, ntaxa, seed)
 
 
+class Supertree:
+    """Exact quartet supertree accumulator (`tq_stree_*`): Quartet MaxCut level by level on
+    integer graph weights.  Rows are added on the host (`add`) or where the engine wrote them (`add_dev_ptrs`, needs
+    `engine`); `tree(seed)` gives the newick with numeric tips.  The host and the device execution give the same
+    string for the same rows, in any order and over any number of adds.
+
+    ntaxa     taxa 0..ntaxa-1 (with an engine: 4..1024)
+    capacity  rows that may be added between two resets
+    weights, min_snps, min_ratio   as `qmc_splits`
+    """
+
+    def __init__(self, ntaxa: int, capacity: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, engine=None):
+        from . import _lib
+        self._lib = _lib.load()
+        if weights not in (0, 1, 2, 3):
+            raise ValueError(f"no weight strategy {weights}")
+        self.ntaxa, self.capacity, self.engine = int(ntaxa), int(capacity), engine
+        self.levels = 0
+        self._h = None
+        h = ctypes.c_void_p()
+        self._check(self._lib.tq_stree_create(ctypes.byref(h), self.ntaxa, self.capacity, int(weights), int(min_snps),
+                                              float(min_ratio), engine._h if engine is not None else None))
+        self._h = h
+
+    def _check(self, rc: int):
+        if rc != 0:
+            from ._lib import TetradHipError
+            ctx = self.engine._h if self.engine is not None else None
+            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tq_stree_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._check(self._lib.tq_stree_reset(self._h))
+
+    def add(self, rqrts, rscor, rstat, flags=None):
+        """Host rows: quartets u32[n,4], scores f64[n,3], rstat u32[n,2] = {topology, nsnps}, flags u8[n] or None."""
+        q = np.ascontiguousarray(rqrts, dtype=np.uint32).reshape(-1, 4)
+        sc = np.ascontiguousarray(rscor, dtype=np.float64).reshape(-1, 3)
+        st = np.ascontiguousarray(rstat, dtype=np.uint32).reshape(-1, 2)
+        n = q.shape[0]
+        if sc.shape[0] != n or st.shape[0] != n:
+            raise ValueError("quartets, scores and rstat must have one row per quartet")
+        fl = None
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            if fl.shape[0] != n:
+                raise ValueError("flags must have one entry per quartet")
+        self._check(self._lib.tq_stree_add(self._h, q.ctypes.data, st.ctypes.data, sc.ctypes.data,
+                                           None if fl is None else fl.ctypes.data, n))
+
+    def add_dev_ptrs(self, d_quartets: int, d_rstat: int, d_rscor: int, d_flags: int, n: int, stream: int = 0):
+        """Device rows by address, enqueued on `stream` (a hipStream_t as int)."""
+        self._check(self._lib.tq_stree_add_dev(self._h, d_quartets, d_rstat, d_rscor, d_flags or None, int(n),
+                                               stream or None))
+
+    def counts(self):
+        """(kept rows, skipped rows, sum of the integer weights k) of everything added so far."""
+        kept, skipped, sum_k = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_uint64()
+        self._check(self._lib.tq_stree_graph(self._h, None, None, ctypes.byref(kept), ctypes.byref(skipped),
+                                             ctypes.byref(sum_k)))
+        return kept.value, skipped.value, sum_k.value
+
+    def graph(self):
+        """The root graph: (G u64[T,T], B u64[T,T], kept, skipped, sum_k)."""
+        G = np.empty((self.ntaxa, self.ntaxa), np.uint64)
+        B = np.empty((self.ntaxa, self.ntaxa), np.uint64)
+        kept, skipped, sum_k = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_uint64()
+        self._check(self._lib.tq_stree_graph(self._h, G.ctypes.data, B.ctypes.data, ctypes.byref(kept),
+                                             ctypes.byref(skipped), ctypes.byref(sum_k)))
+        return G, B, kept.value, skipped.value, sum_k.value
+
+    def rows(self):
+        """The kept rows: (splits u32[n,4] = "a,b|c,d", k u64[n]); weight = k / 10^5."""
+        n = ctypes.c_int64()
+        self._check(self._lib.tq_stree_rows(self._h, None, None, ctypes.byref(n)))
+        sp = np.empty((n.value, 4), np.uint32)
+        k = np.empty(n.value, np.uint64)
+        self._check(self._lib.tq_stree_rows(self._h, sp.ctypes.data, k.ctypes.data, ctypes.byref(n)))
+        return sp, k
+
+    def tree(self, seed: int = 0, stream: int = 0) -> str:
+        """Newick of the rows added so far (numeric tips); `self.levels` = levels of the recursion.  Device rows: the
+        passes run on `stream`."""
+        cap = 16 * self.ntaxa + 64
+        written, levels = ctypes.c_int64(), ctypes.c_int64()
+        for _ in range(2):
+            buf = np.empty(cap, dtype=np.uint8)
+            rc = self._lib.tq_stree_build(self._h, int(seed) & (2**64 - 1), stream or None, buf.ctypes.data, cap,
+                                          ctypes.byref(written), ctypes.byref(levels))
+            if rc == 0:
+                self.levels = levels.value
+                return buf[:written.value].tobytes().decode("ascii")
+            if rc != -6 or written.value <= cap:
+                self._check(rc)
+            cap = written.value
+        self._check(rc)
+
+    def level_stats(self) -> np.ndarray:
+        """Of the last `tree`: f64[levels,6] = {open nodes, live quartets, cells, graph ms, search ms, partition ms}."""
+        n = ctypes.c_int64()
+        out = np.zeros((64, 6), np.float64)
+        self._check(self._lib.tq_stree_level_stats(self._h, ctypes.byref(n), out.ctypes.data))
+        return out[:n.value]
+
+
+def infer_supertree_exact(rqrts, rscor, rstat, ntaxa: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0,
+                          seed: int = 0, flags=None) -> str:
+    """`infer_supertree_from_arrays` on the exact path (host back end): the tree does not depend on the row order."""
+    n = np.asarray(rqrts).reshape(-1, 4).shape[0]
+    with Supertree(ntaxa, n, weights, min_snps, min_ratio) as st:
+        st.add(rqrts, rscor, rstat, flags)
+        return st.tree(seed)
+
+
 def relabel_tree(newick: str, samples) -> str:
     """The tree with the numeric tip labels replaced by sample names -- what run_inference.py:169-181 does with
     toytree.  `samples` maps the taxon number to its name (a dict, or a sequence indexed by taxon number)."""

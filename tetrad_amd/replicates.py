@@ -45,7 +45,7 @@ class ReplicateRunner:
     def __init__(self, engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, *,
                  seed=None, rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None,
                  pieces: Optional[int] = None, dst: Optional[int] = 0, ahead: int = 3, quartets_to_host: bool = False,
-                 gather: str = "collective", concordance=None):
+                 gather: str = "collective", concordance=None, row_sink: Optional[Callable] = None):
         import torch
         if sampler not in ("host", "device"):
             raise ValueError("sampler must be 'host' or 'device'")
@@ -89,6 +89,9 @@ class ReplicateRunner:
         self.concordance = concordance
         if concordance is not None and concordance.engine is not engine:
             raise ValueError("the concordance accumulator must be created with the runner's engine")
+        # row_sink(k, add): called for every replicate right behind its resolve kernels were enqueued; add(acc) enqueues
+        # the rows this rank resolved into `acc` (anything with concordance's `add_dev_ptrs`) on the loop's stream
+        self.row_sink = row_sink
 
     # -- the draws of one replicate, in the reference's order ---------------------------------------------
     def _draw(self):
@@ -188,7 +191,9 @@ class ReplicateRunner:
                         q_host[...] = self._d_full[b].cpu().numpy().view(np.uint32)
                 res.start(subsample_snps, b)
                 if self.concordance is not None:
-                    self._add_concordance(b, cur)
+                    self._add_rows_dev(self.concordance, b, cur)
+                if self.row_sink is not None:
+                    self.row_sink(k, lambda acc, b=b: self._add_rows_dev(acc, b, cur))
                 res.sets[b]["keep"] = keep
                 res.sets[b]["quartets"] = q_host
                 if pending is not None:
@@ -203,16 +208,17 @@ class ReplicateRunner:
             self._thread.join()
         return stats
 
-    def _add_concordance(self, b: int, cur):
+    def _add_rows_dev(self, acc, b: int, cur):
         """The rows this rank resolved for buffer set `b` -- piece by piece in the slabs the singular-value stage
-        wrote, quartets in the rank's local order -- into the concordance accumulator, on stream `cur`."""
+        wrote, quartets in the rank's local order -- into the accumulator `acc` (concordance or supertree), on stream
+        `cur`."""
         res, P, base_q = self.res, self.res.plan, self._d_q.data_ptr()
         for i in range(P.npieces):
             lo, hi = res.ranges[i]
             n, off, p = hi - lo, int(res.offsets[i]), P.part[i]
             if n:
                 base = res.sets[b]["slabs"][i].data_ptr()
-                self.concordance.add_dev_ptrs(base_q + 16 * off, base, base + 8 * p, base + 32 * p, n, cur.cuda_stream)
+                acc.add_dev_ptrs(base_q + 16 * off, base, base + 8 * p, base + 32 * p, n, cur.cuda_stream)
 
     def close(self):
         self._stop.set()
@@ -224,15 +230,23 @@ class ReplicateRunner:
 def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, nboots: int, *,
                     subsample_snps: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
                     rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
-                    concordance=None) -> list:
+                    concordance=None, supertree: str = "host") -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
     the GPUs work on the next replicates.  Returns the newick strings in replicate order on the destination rank
     (rank 0), an empty list elsewhere.  Tip labels are taxon numbers (`qmc.relabel_tree` turns them into names).
-    `concordance` (a `concordance.Concordance` made with `engine`) receives every replicate's rows on the device."""
+    `concordance` (a `concordance.Concordance` made with `engine`) receives every replicate's rows on the device.
+    `supertree="device"`: the exact supertree (`qmc.Supertree`) instead -- no row leaves the
+    device; each replicate's rows are added to one of a small ring of accumulators on the loop's stream and a worker
+    thread builds the tree on a stream of its own, beside the resolve kernels of the next replicates.  One rank only."""
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
+    if supertree not in ("host", "device"):
+        raise ValueError("supertree must be 'host' or 'device'")
+    if supertree == "device":
+        return _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps,
+                                       min_ratio, seed, rng, sampler, group, workers, concordance)
     runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
                              quartets_to_host=True, concordance=concordance)
     ntaxa = int(seqarr.shape[0])
@@ -246,3 +260,51 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
         finally:
             runner.close()
         return [futures[k].result() for k in sorted(futures)]
+
+
+def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
+                            rng, sampler, group, workers, concordance) -> list:
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import qmc
+    runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
+                             concordance=concordance)
+    ring, futures = [], {}
+    try:
+        if runner.res.world > 1:
+            raise NotImplementedError("supertree='device' runs on one rank (the graphs of several ranks are not summed)")
+        workers = max(1, int(workers))
+        ntaxa = int(seqarr.shape[0])
+        ring = [qmc.Supertree(ntaxa, int(nquartets), weights, min_snps, min_ratio, engine=engine) for _ in range(workers + 1)]
+        free: queue.Queue = queue.Queue()
+        for slot in range(len(ring)):
+            free.put(slot)
+        local = threading.local()
+
+        def work(slot, k):
+            # tq_stree_build orders its stream behind the adds (the accumulator's event); the slot goes back only
+            # when its tree is out
+            try:
+                if getattr(local, "stream", None) is None:
+                    torch.cuda.set_device(runner.dev)
+                    local.stream = torch.cuda.Stream(runner.dev)
+                nwk = ring[slot].tree(seed=k, stream=local.stream.cuda_stream)
+                ring[slot].reset()
+                return nwk
+            finally:
+                free.put(slot)
+
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            def sink(k, add):
+                slot = free.get()
+                add(ring[slot])
+                futures[k] = pool.submit(work, slot, k)
+            runner.row_sink = sink
+            runner.run(nboots, subsample_snps)
+            return [futures[k].result() for k in sorted(futures)]
+    finally:
+        for f in futures.values():
+            f.exception()                                   # every worker has let go of its accumulator
+        runner.close()
+        for acc in ring:
+            acc.close()
