@@ -230,13 +230,22 @@ int tq_timing_read_kernels(tq_ctx *ctx, double *ms, int n_ms, int64_t *calls);
  * few pairs), scan_f4 (-1, default: in subsample mode the cooperative scan streams a wavefront's own rows as 12-byte
  * {missing, bit 0, bit 1} records only and makes the pattern of a counted site inside the histogram walk, scan_f4.hpp =
  * SURVEY 8 row f4; 1: in full mode too (slower there); 0: the nibble-code kernel of rounds 1-3 everywhere; NOTE: 0 is a value
- * of its own for this option, the default is -1).                                                                   */
+ * of its own for this option, the default is -1).
+ * site_pack (-1, default; read by tq_set_data): the subsample-mode scans read a second resident copy of the matrix in which
+ * every 32-site lane word holds whole loci and the 64 words of a step hold the same number of them (tq_pack_sites below), so
+ * a wavefront's set-bit walk makes that many trips per step instead of the most any of 64 arbitrary windows holds; the same
+ * rows, bit for bit.  -1: built when the predicted instruction count of the scan falls (dense matrices; not for sparse
+ * RAD-like ones, where the walk is short anyway and only the extra steps would cost -- no second copy is made then);
+ * 1: always built; 0: never built, and a copy already built is no longer used (-1 / 1 set after tq_set_data take effect
+ * with the next one).  Full mode, species mode, tq_get_data and device-built bootstrap replicates use the natural layout.
+ * NOTE: 0 is a value of its own for this option, the default is -1.                                                */
 int tq_set_option(tq_ctx *ctx, const char *name, int64_t value);
 
 /* Test hook: copy the scratch of the last resolve call to the host.  which = 0: count slab
  * u32[n][256] of the last scan batch; 1: bidiagonals f64[3m][32] (d[16], e[16]); 2: singular values
  * f64[3m][16] (unsorted, sign bit = not converged), m = quartets of the last singular-value chunk; 3: the 8 u64 counters
- * of option bdsqr_stats.  No reference counterpart.                                                                    */
+ * of option bdsqr_stats; 4: two i64 about the packed layout set of option site_pack: its padded site count (0 = none is
+ * resident) and 1 if a subsample-mode scan issued now would read it.  No reference counterpart.                        */
 int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes);
 
 /* Test hook: run the bidiagonal-QR kernel (tq_bdsqr_kernel) alone on nmat bidiagonals given on the host -- de f64[nmat][32]
@@ -262,6 +271,19 @@ int tq_format_tsv(const uint32_t *quartets, const uint32_t *rstat, const double 
 int tq_format_qmc(const uint32_t *quartets, const uint32_t *rstat, const double *rscor, int64_t Q,
                   int weights, int64_t min_snps, double min_ratio, char *out, int64_t cap,
                   int64_t *written, int64_t *n_lines);
+
+/* The site order of the packed layout (option site_pack; host code, no device involved): src[p] = the site of the matrix
+ * that packed position p holds, or 0xFFFFFFFF for a pad (missing in every taxon).  Every site appears once; the sites of a
+ * locus (a run of equal ids in `locus`, read with stride `locus_stride`) stay adjacent and in order; a locus of at most 32
+ * sites lies inside one 32-site word, a longer one starts a word and fills consecutive words; words come by falling number
+ * of loci; the length is a multiple of 2048.  *packed_sites = that length; src (cap entries) is filled when cap suffices,
+ * so a first call with cap = 0 sizes the buffer.  With tmparr u8[T][S] (may be NULL) the automatic rule is evaluated too:
+ * *pays = 1 when tq_set_data would build the packed copy under site_pack = -1, and estimate[0..4] = predicted vector
+ * instructions per quartet of the natural and of the packed layout, walk trips per quartet of the two, and the relative gain
+ * in instructions lowered by two standard errors of the sample (the rule takes the packed layout from 0.03 on).  pays and
+ * estimate may be NULL.  TQ_ERR_LOCUS_ORDER when a locus id is 0xFFFFFFFF or does not form one run.                  */
+int tq_pack_sites(const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *locus, int64_t locus_stride, uint32_t *src,
+                  int64_t cap, int64_t *packed_sites, int32_t *pays, double *estimate);
 
 /* The reference's quartet sample, stream-identical and faster (host code): what
  * `Generator.choice(pop, size, replace=False)` (combinations.py:113) returns when size > pop // 50 and

@@ -38,6 +38,7 @@ SYMBOLS = [
     "tq_stree_create", "tq_stree_destroy", "tq_stree_reset", "tq_stree_add", "tq_stree_add_dev", "tq_stree_graph",
     "tq_stree_rows", "tq_stree_build", "tq_stree_level_stats",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
+    "tq_pack_sites",
 ]
 
 
@@ -214,6 +215,8 @@ def load() -> ctypes.CDLL:
     lib.tq_resolve_species_dev.restype = i32
     lib.tq_resolve_species_debug.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.tq_resolve_species_debug.restype = i32
+    lib.tq_pack_sites.argtypes = [vp, i64, i64, vp, i64, vp, i64, c.POINTER(i64), c.POINTER(c.c_int32), vp]
+    lib.tq_pack_sites.restype = i32
     lib.tq_device_info.argtypes = [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(i64)]
     lib.tq_device_info.restype = i32
     _lib = lib

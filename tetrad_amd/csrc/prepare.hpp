@@ -13,9 +13,12 @@ __device__ __forceinline__ void store_planes3(uint32_t *planes3, uint32_t *runbe
 }
 
 // ------------------------------------------------------------------------------------
-// data preparation kernel: one thread per 32-site word of one taxon row
+// data preparation kernel: one thread per 32-site word of one taxon row.  `site_src` = null: the natural layout (position
+// s holds site s); else the packed layout (pack.hpp): position p holds site site_src[p], 0xFFFFFFFF = a pad (missing in
+// every taxon, no run-begin bit) -- the run-begin word is recomputed from the sites the word now holds.  nib5 may be null.
 // ------------------------------------------------------------------------------------
 __global__ void tq_prepare_rows(const uint8_t *__restrict__ raw, const uint32_t *__restrict__ locus,
+                                const uint32_t *__restrict__ site_src,
                                 int64_t S, int64_t Sp, int64_t W, int32_t T, uint8_t *__restrict__ rows,
                                 uint8_t *__restrict__ nib, uint8_t *__restrict__ nib5, uint4 *__restrict__ planes,
                                 uint32_t *__restrict__ planes3, uint32_t *__restrict__ runbeg)
@@ -23,16 +26,17 @@ __global__ void tq_prepare_rows(const uint8_t *__restrict__ raw, const uint32_t 
     int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (int64_t)T * W) return;
     int64_t t = gid / W, w = gid - t * W;
-    const uint8_t *src = raw + t * S + w * 32;
+    const uint8_t *src = raw + t * S;
     uint8_t *dst = rows + t * Sp;
     uint32_t mm = 0, b0 = 0, b1 = 0, rb = 0;
     uint32_t nw[4] = {0, 0, 0, 0}, n5[4] = {0, 0, 0, 0};   // this word's 32 sites = 16 nibble bytes (and with 4 = missing)
     for (int i = 0; i < 32; ++i) {
-        int64_t s = w * 32 + i;
-        uint8_t v = (s < S) ? src[i] : (uint8_t)0xFF;
+        const int64_t p = w * 32 + i;
+        const int64_t s = site_src ? (site_src[p] == 0xFFFFFFFFu ? S : (int64_t)site_src[p]) : p;
+        uint8_t v = (s < S) ? src[s] : (uint8_t)0xFF;
         bool missing = v > 3;
         uint8_t code = missing ? (uint8_t)0 : v;
-        dst[row_offset(s)] = code;
+        dst[row_offset(p)] = code;
         nw[i >> 3] |= (uint32_t)code << (8 * (i & 3) + 4 * ((i >> 2) & 1));
         n5[i >> 3] |= (uint32_t)(missing ? 4 : code) << (8 * (i & 3) + 4 * ((i >> 2) & 1));
         mm |= (uint32_t)missing << i;
@@ -46,7 +50,7 @@ __global__ void tq_prepare_rows(const uint8_t *__restrict__ raw, const uint32_t 
     planes[t * W + w] = make_uint4(mm, b0, b1, rb);
     store_planes3(planes3, runbeg, t, W, w, mm, b0, b1, rb);
     reinterpret_cast<uint4 *>(nib + t * (Sp / 2))[w] = make_uint4(nw[0], nw[1], nw[2], nw[3]);
-    reinterpret_cast<uint4 *>(nib5 + t * (Sp / 2))[w] = make_uint4(n5[0], n5[1], n5[2], n5[3]);
+    if (nib5) reinterpret_cast<uint4 *>(nib5 + t * (Sp / 2))[w] = make_uint4(n5[0], n5[1], n5[2], n5[3]);
 }
 
 // ------------------------------------------------------------------------------------

@@ -16,9 +16,11 @@
 //   nib5    u8   [T][Sp/2] the same with 4 for a missing cell (rows d1, d2 of the joint-histogram scan)
 //   planes  u32x4[T][W]    per 32 sites: {missing bits, base bit 0, base bit 1, run-begin bits}, W = Sp/32
 //   planes3 u32x3[T][W]    compact copy {missing, bit 0, bit 1}; runbeg u32 [W] run-begin bits, stored once
+//   and, when it pays, a second rows / nib / planes / planes3 + runbeg set in the packed site order (pack.hpp)
 //
 // Kernels (each in its own header of this directory, all included below into one translation unit):
 //   prepare.hpp   layout build, lexicographic unranking, sort keys
+//   pack.hpp      (host) packed site order for the subsample-mode scans: whole loci per lane word (option site_pack)
 //   scan.hpp      tq_scan_wg_kernel / tq_scan_kernel: site scan -> 256 pattern counts per quartet (nibble codes + plane
 //                 records; the one-wave-per-quartet kernel of small calls)
 //   scan_f4.hpp   tq_scan_f4_kernel: the cooperative scan on 12-byte plane records only (default of subsample mode)
@@ -63,6 +65,7 @@ namespace {
 
 #include "common.hpp"
 #include "prepare.hpp"
+#include "pack.hpp"
 #include "scan.hpp"
 #include "scan_pb.hpp"
 #include "scan_dp.hpp"
@@ -177,6 +180,16 @@ struct tq_ctx {
                                     // 0: VALU form (tq_species_pool_kernel); 1: MFMA form (tq_species_mfma_kernel)
     uint64_t data_gen = 0;          // bumped by tq_set_data / tq_bootstrap(_async)
     uint64_t sp_tab_gen = ~0ull;    // data_gen the species table was built from (~0: none)
+    // packed layout set (pack.hpp): a second copy of rows / nib / planes / planes3 + runbeg with whole loci per lane word,
+    // read by the subsample-mode scans while it is current (pk_gen == data_gen; a device-built bootstrap replicate
+    // keeps the natural layout only and leaves this set stale).  Everything else reads the natural set.
+    int site_pack = -1;             // -1: tq_set_data builds the set when the predicted scan cost falls (pack.hpp), 1: always
+                                    // (while subsample mode is possible), 0: never, and a built set is not used
+    uint8_t *pk_rows = nullptr, *pk_nib = nullptr;
+    uint4 *pk_planes = nullptr;
+    uint32_t *pk_planes3 = nullptr; // [T][pk_W][3], then runbeg [pk_W]
+    int64_t pk_Sp = 0, pk_W = 0;
+    uint64_t pk_gen = ~0ull;        // data_gen the set was built from (~0: none)
     // host-buffer API: own compute and copy streams, events for the D2H pipeline
     hipStream_t sK = nullptr, sC = nullptr;
     std::vector<hipEvent_t> pipe_events;
@@ -320,6 +333,20 @@ bool is_pinned(const void *p, size_t bytes)
     return a.type == hipMemoryTypeHost;
 }
 
+void free_packed(tq_ctx *ctx)
+{
+    if (ctx->pk_rows) (void)hipFree(ctx->pk_rows);
+    if (ctx->pk_nib) (void)hipFree(ctx->pk_nib);
+    if (ctx->pk_planes) (void)hipFree(ctx->pk_planes);
+    if (ctx->pk_planes3) (void)hipFree(ctx->pk_planes3);
+    ctx->pk_rows = nullptr;
+    ctx->pk_nib = nullptr;
+    ctx->pk_planes = nullptr;
+    ctx->pk_planes3 = nullptr;
+    ctx->pk_Sp = ctx->pk_W = 0;
+    ctx->pk_gen = ~0ull;
+}
+
 void free_data(tq_ctx *ctx)
 {
     if (ctx->d_rows) (void)hipFree(ctx->d_rows);
@@ -327,6 +354,7 @@ void free_data(tq_ctx *ctx)
     if (ctx->d_nib5) (void)hipFree(ctx->d_nib5);
     if (ctx->d_planes) (void)hipFree(ctx->d_planes);
     if (ctx->d_planes3) (void)hipFree(ctx->d_planes3);
+    free_packed(ctx);
     ctx->d_rows = nullptr;
     ctx->d_nib = nullptr;
     ctx->d_nib5 = nullptr;
@@ -526,6 +554,23 @@ DevData dev_data(const tq_ctx *ctx)
     return d;
 }
 
+// the set a scan reads: in subsample mode the packed one while it is current (same counts, fewer walk trips per step)
+DevData scan_data(const tq_ctx *ctx, int subsample)
+{
+    DevData d = dev_data(ctx);
+    if (!subsample || !ctx->site_pack || !ctx->pk_rows || ctx->pk_gen != ctx->data_gen) return d;
+    d.rows = ctx->pk_rows;
+    d.nib = ctx->pk_nib;
+    d.nib5 = nullptr;               // full-mode kernels only (scan_dp.hpp, species.hpp)
+    d.planes = ctx->pk_planes;
+    d.planes3 = ctx->pk_planes3;
+    d.runbeg = ctx->pk_planes3 + (size_t)ctx->T * (size_t)ctx->pk_W * 3;
+    d.pitch = ctx->pk_Sp;
+    d.W = ctx->pk_W;
+    d.ntiles = (int32_t)(ctx->pk_Sp / TILE);
+    return d;
+}
+
 template <typename K>
 int grid_for(tq_ctx *ctx, K kern, int64_t items, int64_t *grid, int wpc_kernel = 0)
 {
@@ -543,19 +588,19 @@ int grid_for(tq_ctx *ctx, K kern, int64_t items, int64_t *grid, int wpc_kernel =
 }
 
 template <int NREP, bool SUB, int METHOD>
-int launch_scan(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+int launch_scan(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
 {
     auto kern = tq_scan_kernel<NREP, SUB, METHOD>;
     int64_t grid;
     int rc = grid_for(ctx, kern, Q, &grid);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVE), 0, stream, dev_data(ctx), dq, order, Q, ctx->d_cm);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVE), 0, stream, d, dq, order, Q, ctx->d_cm);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
 }
 
 template <bool SUB, int METHOD, int NW, bool SHC = false, bool PARK_T = false>
-int launch_scan_wg(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+int launch_scan_wg(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
 {
     auto kern = tq_scan_wg_kernel<SUB, METHOD, NW, SHC, PARK_T>;
     const int wgs = ctx->waves_per_cu > 0 ? (ctx->waves_per_cu + NW - 1) / NW : 0;
@@ -573,7 +618,7 @@ int launch_scan_wg(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64
         }
     }
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), 0, stream, dev_data(ctx), dq, order, Q,
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), 0, stream, d, dq, order, Q,
                        ctx->d_cm, xcd_chunk);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
@@ -581,7 +626,7 @@ int launch_scan_wg(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64
 
 // bank-private counters (scan_pb.hpp): one block of 4 quartets per workgroup, as launch_scan_wg
 template <bool SUB>
-int launch_scan_pb(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+int launch_scan_pb(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
 {
     auto kern = tq_scan_pb_kernel<SUB>;
     const int64_t nblk = (Q + PB_NW - 1) / PB_NW;
@@ -591,7 +636,7 @@ int launch_scan_pb(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64
         grid = xcd_chunk * 8;
     }
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PB_NW * WAVE), 0, stream, dev_data(ctx), dq, order, Q, ctx->d_cm,
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PB_NW * WAVE), 0, stream, d, dq, order, Q, ctx->d_cm,
                        xcd_chunk, (uint32_t *)nullptr);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
@@ -620,7 +665,7 @@ int probe_scan_pb(tq_ctx *ctx)
 }
 
 template <bool SUB, int METHOD, int NW>
-int launch_scan_wg2(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+int launch_scan_wg2(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
 {
     auto kern = tq_scan_wg2_kernel<SUB, METHOD, NW>;
     const int64_t nblk = (Q + 2 * NW - 1) / (2 * NW);
@@ -630,7 +675,7 @@ int launch_scan_wg2(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int6
         grid = xcd_chunk * 8;
     }
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), 0, stream, dev_data(ctx), dq, order, Q, ctx->d_cm,
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), 0, stream, d, dq, order, Q, ctx->d_cm,
                        xcd_chunk);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
@@ -652,18 +697,19 @@ int launch_scan_dp(tq_ctx *ctx, const uint32_t *dq, int64_t Q, hipStream_t strea
 int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_t Q, int subsample,
                   hipStream_t stream)
 {
+    const DevData d = scan_data(ctx, subsample);
     if (ctx->scan_pair && ctx->scan_wg == 4 && Q >= 64 && !ctx->count_invariant && !ctx->share_c && ctx->waves_per_cu == 0 &&
-        ctx->scan_method < 2 && (uint64_t)ctx->T * (uint64_t)ctx->Sp < 0xFFFF0000ull) {
+        ctx->scan_method < 2 && (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
         const int m = ctx->scan_method < 0 ? (subsample ? 1 : 0) : ctx->scan_method;
         if (subsample)
-            return m ? launch_scan_wg2<true, 1, 4>(ctx, dq, order, Q, stream) : launch_scan_wg2<true, 0, 4>(ctx, dq, order, Q, stream);
-        return m ? launch_scan_wg2<false, 1, 4>(ctx, dq, order, Q, stream) : launch_scan_wg2<false, 0, 4>(ctx, dq, order, Q, stream);
+            return m ? launch_scan_wg2<true, 1, 4>(ctx, d, dq, order, Q, stream) : launch_scan_wg2<true, 0, 4>(ctx, d, dq, order, Q, stream);
+        return m ? launch_scan_wg2<false, 1, 4>(ctx, d, dq, order, Q, stream) : launch_scan_wg2<false, 0, 4>(ctx, d, dq, order, Q, stream);
     }
     // row f4 as written (option scan_f4): own rows as 12-byte plane records only, pattern bits pulled out in the walk
     const bool f4 = ctx->scan_f4 < 0 ? (subsample != 0 && ctx->scan_method < 0 && ctx->park_t) : ctx->scan_f4 != 0;
     if (f4 && (ctx->scan_wg == 4 || ctx->scan_wg == 8 || ctx->scan_wg == 2) && Q >= ctx->wg_min_quartets && !ctx->count_invariant &&
         !ctx->share_c && !ctx->scan_pair && ctx->waves_per_cu == 0 && (ctx->scan_method < 0 || ctx->scan_method == 1) &&
-        (uint64_t)ctx->T * (uint64_t)ctx->Sp < 0xFFFF0000ull) {
+        (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
         const int nw = ctx->scan_wg;
         const int64_t nblk = (Q + nw - 1) / nw;
         int64_t grid = nblk, xcd_chunk = 0;
@@ -674,7 +720,7 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
 #define TQ_F4_CASE(SUBF, NWF)                                                                                         \
         if ((subsample != 0) == SUBF && nw == NWF)                                                                    \
             hipLaunchKernelGGL((tq_scan_f4_kernel<SUBF, NWF>), dim3((unsigned)grid), dim3(NWF * WAVE), 0, stream,      \
-                               dev_data(ctx), dq, order, Q, ctx->d_cm, xcd_chunk);
+                               d, dq, order, Q, ctx->d_cm, xcd_chunk);
         TQ_F4_CASE(true, 4) TQ_F4_CASE(false, 4) TQ_F4_CASE(true, 8) TQ_F4_CASE(false, 8) TQ_F4_CASE(true, 2) TQ_F4_CASE(false, 2)
 #undef TQ_F4_CASE
         TQ_HIP(ctx, hipGetLastError());
@@ -684,39 +730,39 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
     // cycles of operand transfer either way and the 64 KiB of counters leave two workgroups per CU -- measured slower,
     // scan_pb.hpp); 16-bit counters, so only while a quartet has at most PB_MAX_TILES steps
     const bool pb_fits = ctx->pb_ok == 1 && ctx->scan_wg == 4 && Q >= 64 && !ctx->count_invariant && !ctx->share_c &&
-                         !ctx->scan_pair && ctx->waves_per_cu == 0 && ctx->Sp / TILE <= PB_MAX_TILES &&
-                         (uint64_t)ctx->T * (uint64_t)ctx->Sp < 0xFFFF0000ull;
+                         !ctx->scan_pair && ctx->waves_per_cu == 0 && d.pitch / TILE <= PB_MAX_TILES &&
+                         (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull;
     if (pb_fits && ctx->scan_method == 6)
-        return subsample ? launch_scan_pb<true>(ctx, dq, order, Q, stream) : launch_scan_pb<false>(ctx, dq, order, Q, stream);
+        return subsample ? launch_scan_pb<true>(ctx, d, dq, order, Q, stream) : launch_scan_pb<false>(ctx, d, dq, order, Q, stream);
     if (ctx->scan_wg >= 2 && Q >= ctx->wg_min_quartets && !ctx->count_invariant &&
-        (uint64_t)ctx->T * (uint64_t)ctx->Sp < 0xFFFF0000ull) {
+        (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
         int m = ctx->scan_method < 0 ? (subsample ? 1 : 0) : ctx->scan_method;
         if (m == 6) m = subsample ? 1 : 0;
 #define TQ_WG_CASE(NW)                                                                                   \
     if (ctx->scan_wg == NW) {                                                                            \
-        if (m == 2) return launch_scan_wg<true, 2, NW>(ctx, dq, order, Q, stream);                       \
-        if (m == 3) return launch_scan_wg<true, 3, NW>(ctx, dq, order, Q, stream);                       \
-        if (NW == 4 && m == 4) return launch_scan_wg<true, 4, 4>(ctx, dq, order, Q, stream);             \
-        if (NW == 4 && m == 5) return launch_scan_wg<true, 5, 4>(ctx, dq, order, Q, stream);             \
+        if (m == 2) return launch_scan_wg<true, 2, NW>(ctx, d, dq, order, Q, stream);                       \
+        if (m == 3) return launch_scan_wg<true, 3, NW>(ctx, d, dq, order, Q, stream);                       \
+        if (NW == 4 && m == 4) return launch_scan_wg<true, 4, 4>(ctx, d, dq, order, Q, stream);             \
+        if (NW == 4 && m == 5) return launch_scan_wg<true, 5, 4>(ctx, d, dq, order, Q, stream);             \
         if (subsample)                                                                                   \
-            return m ? launch_scan_wg<true, 1, NW>(ctx, dq, order, Q, stream)                            \
-                     : launch_scan_wg<true, 0, NW>(ctx, dq, order, Q, stream);                           \
-        return m ? launch_scan_wg<false, 1, NW>(ctx, dq, order, Q, stream)                               \
-                 : launch_scan_wg<false, 0, NW>(ctx, dq, order, Q, stream);                              \
+            return m ? launch_scan_wg<true, 1, NW>(ctx, d, dq, order, Q, stream)                            \
+                     : launch_scan_wg<true, 0, NW>(ctx, d, dq, order, Q, stream);                           \
+        return m ? launch_scan_wg<false, 1, NW>(ctx, d, dq, order, Q, stream)                               \
+                 : launch_scan_wg<false, 0, NW>(ctx, d, dq, order, Q, stream);                              \
     }
         TQ_WG_CASE(2)
         if (ctx->scan_wg == 4 && ctx->park_t && m == 1 && !ctx->share_c)
-            return subsample ? launch_scan_wg<true, 1, 4, false, true>(ctx, dq, order, Q, stream)
-                             : launch_scan_wg<false, 1, 4, false, true>(ctx, dq, order, Q, stream);
+            return subsample ? launch_scan_wg<true, 1, 4, false, true>(ctx, d, dq, order, Q, stream)
+                             : launch_scan_wg<false, 1, 4, false, true>(ctx, d, dq, order, Q, stream);
         if ((ctx->scan_wg == 8 || ctx->scan_wg == 6) && ctx->park_t && m == 1 && subsample && !ctx->share_c)
-            return ctx->scan_wg == 8 ? launch_scan_wg<true, 1, 8, false, true>(ctx, dq, order, Q, stream)
-                                     : launch_scan_wg<true, 1, 6, false, true>(ctx, dq, order, Q, stream);
+            return ctx->scan_wg == 8 ? launch_scan_wg<true, 1, 8, false, true>(ctx, d, dq, order, Q, stream)
+                                     : launch_scan_wg<true, 1, 6, false, true>(ctx, d, dq, order, Q, stream);
         if (ctx->scan_wg == 4 && ctx->share_c && m <= 1) {
             if (subsample)
-                return m ? launch_scan_wg<true, 1, 4, true>(ctx, dq, order, Q, stream)
-                         : launch_scan_wg<true, 0, 4, true>(ctx, dq, order, Q, stream);
-            return m ? launch_scan_wg<false, 1, 4, true>(ctx, dq, order, Q, stream)
-                     : launch_scan_wg<false, 0, 4, true>(ctx, dq, order, Q, stream);
+                return m ? launch_scan_wg<true, 1, 4, true>(ctx, d, dq, order, Q, stream)
+                         : launch_scan_wg<true, 0, 4, true>(ctx, d, dq, order, Q, stream);
+            return m ? launch_scan_wg<false, 1, 4, true>(ctx, d, dq, order, Q, stream)
+                     : launch_scan_wg<false, 0, 4, true>(ctx, d, dq, order, Q, stream);
         }
         TQ_WG_CASE(4)
         TQ_WG_CASE(3)
@@ -728,10 +774,10 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
 #define TQ_SCAN_CASE(N)                                                                              \
     case N:                                                                                          \
         if (method == 0)                                                                             \
-            return subsample ? launch_scan<N, true, 0>(ctx, dq, order, Q, stream)                    \
-                             : launch_scan<N, false, 0>(ctx, dq, order, Q, stream);                  \
-        return subsample ? launch_scan<N, true, 1>(ctx, dq, order, Q, stream)                        \
-                         : launch_scan<N, false, 1>(ctx, dq, order, Q, stream)
+            return subsample ? launch_scan<N, true, 0>(ctx, d, dq, order, Q, stream)                    \
+                             : launch_scan<N, false, 0>(ctx, d, dq, order, Q, stream);                  \
+        return subsample ? launch_scan<N, true, 1>(ctx, d, dq, order, Q, stream)                        \
+                         : launch_scan<N, false, 1>(ctx, d, dq, order, Q, stream)
     const int method = (ctx->scan_method < 0 || ctx->scan_method == 6) ? (subsample ? 1 : 0) : ctx->scan_method;
     switch (ctx->nrep) {
         TQ_SCAN_CASE(2);
@@ -1648,6 +1694,27 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
     }
     ctx->locus_runs_ok = ok;
 
+    // packed layout for the subsample-mode scans (pack.hpp): planned on the host, taken when forced or when it pays
+    std::vector<uint32_t> pack_src;
+    if (ok && ctx->site_pack != 0 && S < 0xFFFFFFFFll) {        // the map holds site indices as u32
+        try {
+            std::vector<LocusRun> runs;
+            locus_runs(loc.data(), S, runs);
+            pack_sites(runs, pack_src);
+            if (ctx->site_pack < 0) {
+                double cost[2], trips[2];
+                const double gain_low = pack_estimate(tmparr, T, S, runs, pack_src, cost, trips);
+                // the cooperative kernels address a set with 32-bit offsets: a packed set past that range while the
+                // natural one is inside it would send the batch to the one-wave kernel
+                const bool fits = (uint64_t)T * (uint64_t)pack_src.size() < 0xFFFF0000ull ||
+                                  (uint64_t)T * (uint64_t)align_up((size_t)S, TILE) >= 0xFFFF0000ull;
+                if (!pack_pays(gain_low) || !fits) pack_src.clear();
+            }
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, TQ_ERR_OOM, "tq_set_data: out of host memory");
+        }
+    }
+
     const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
     const int64_t W = Sp / 32;
     ctx->T = T; ctx->S = S; ctx->Sp = Sp; ctx->W = W;
@@ -1664,9 +1731,19 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
     ctx->plane_cap_W = W;
     if (e == hipSuccess) e = hipMalloc((void **)&d_raw, (size_t)(T * S));
     if (e == hipSuccess) e = hipMalloc((void **)&d_loc, (size_t)S * sizeof(uint32_t));
+    uint32_t *d_src = nullptr;
+    const int64_t pSp = (int64_t)pack_src.size(), pW = pSp / 32;
+    if (pSp) {
+        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_rows, (size_t)(T * pSp));
+        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_nib, (size_t)(T * pSp / 2));
+        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_planes, (size_t)(T * pW) * sizeof(uint4));
+        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_planes3, (size_t)(T * pW * 3 + pW) * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_src, (size_t)pSp * sizeof(uint32_t));
+    }
     if (e != hipSuccess) {
         if (d_raw) (void)hipFree(d_raw);
         if (d_loc) (void)hipFree(d_loc);
+        if (d_src) (void)hipFree(d_src);
         free_data(ctx);
         return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_set_data: hipMalloc failed: %s",
                     hipGetErrorString(e));
@@ -1675,20 +1752,74 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
     if (e == hipSuccess) e = hipMemcpy(d_loc, loc.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const int64_t n = T * W;
-        hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_raw, d_loc, S, Sp,
-                           W, (int32_t)T, ctx->d_rows, ctx->d_nib, ctx->d_nib5, ctx->d_planes,
+        hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_raw, d_loc,
+                           (const uint32_t *)nullptr, S, Sp, W, (int32_t)T, ctx->d_rows, ctx->d_nib, ctx->d_nib5, ctx->d_planes,
                            ctx->d_planes3,
                            ctx->d_planes3 + (size_t)T * (size_t)W * 3);
         e = hipGetLastError();
+        if (e == hipSuccess && pSp) {
+            e = hipMemcpy(d_src, pack_src.data(), (size_t)pSp * sizeof(uint32_t), hipMemcpyHostToDevice);
+            if (e == hipSuccess) {
+                const int64_t np = T * pW;
+                hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, d_raw, d_loc,
+                                   (const uint32_t *)d_src, S, pSp, pW, (int32_t)T, ctx->pk_rows, ctx->pk_nib,
+                                   (uint8_t *)nullptr, ctx->pk_planes, ctx->pk_planes3,
+                                   ctx->pk_planes3 + (size_t)T * (size_t)pW * 3);
+                e = hipGetLastError();
+            }
+        }
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     (void)hipFree(d_raw);
     (void)hipFree(d_loc);
+    if (d_src) (void)hipFree(d_src);
     if (e != hipSuccess) {
         free_data(ctx);
         return fail(ctx, TQ_ERR_HIP, "tq_set_data: %s", hipGetErrorString(e));
     }
     ctx->have_data = true;
+    if (pSp) {
+        ctx->pk_Sp = pSp;
+        ctx->pk_W = pW;
+        ctx->pk_gen = ctx->data_gen;
+    }
+    return TQ_OK;
+}
+
+int tq_pack_sites(const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *locus, int64_t locus_stride, uint32_t *src,
+                  int64_t cap, int64_t *packed_sites, int32_t *pays, double *estimate)
+{
+    if (!locus || S < 1 || S >= 0xFFFFFFFFll || locus_stride < 1 || cap < 0 || (cap > 0 && !src) || (tmparr && T < 1))
+        return TQ_ERR_INVALID_ARG;
+    try {
+        std::vector<uint32_t> loc((size_t)S);
+        std::unordered_set<uint32_t> seen;
+        for (int64_t i = 0; i < S; ++i) {
+            loc[(size_t)i] = locus[i * locus_stride];
+            if (loc[(size_t)i] == 0xFFFFFFFFu) return TQ_ERR_LOCUS_ORDER;
+            if ((!i || loc[(size_t)i] != loc[(size_t)i - 1]) && !seen.insert(loc[(size_t)i]).second) return TQ_ERR_LOCUS_ORDER;
+        }
+        std::vector<LocusRun> runs;
+        std::vector<uint32_t> map;
+        locus_runs(loc.data(), S, runs);
+        pack_sites(runs, map);
+        if (packed_sites) *packed_sites = (int64_t)map.size();
+        if (tmparr) {
+            double cost[2], trips[2];
+            const double gain_low = pack_estimate(tmparr, T, S, runs, map, cost, trips);
+            if (pays) *pays = pack_pays(gain_low) ? 1 : 0;
+            if (estimate) {
+                estimate[0] = cost[0];
+                estimate[1] = cost[1];
+                estimate[2] = trips[0];
+                estimate[3] = trips[1];
+                estimate[4] = gain_low;
+            }
+        }
+        if ((int64_t)map.size() <= cap) memcpy(src, map.data(), map.size() * sizeof(uint32_t));
+    } catch (const std::bad_alloc &) {
+        return TQ_ERR_OOM;
+    }
     return TQ_OK;
 }
 
@@ -2039,6 +2170,11 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
         ctx->scan_f4 = (int)value;
         return TQ_OK;
     }
+    if (!strcmp(name, "site_pack")) {
+        if (value < -1 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "site_pack must be -1 (automatic), 0 or 1");
+        ctx->site_pack = (int)value;
+        return TQ_OK;
+    }
     if (!strcmp(name, "scan_dp")) {
         if (value != 0 && value != 1) return fail(ctx, TQ_ERR_INVALID_ARG, "scan_dp must be 0 or 1");
         ctx->scan_dp = (int)value;
@@ -2345,6 +2481,12 @@ int tq_data_shape(tq_ctx *ctx, int64_t *T, int64_t *S)
 int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes)
 {
     if (!ctx || !dst || bytes < 0) return TQ_ERR_INVALID_ARG;
+    if (which == 4) {                       // the packed layout set: {its sites (0: none), 1 if the subsample scans read it now}
+        const int64_t st[2] = {ctx->pk_rows ? ctx->pk_Sp : 0, scan_data(ctx, 1).rows == ctx->pk_rows && ctx->pk_rows ? 1 : 0};
+        if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=4 takes 16 bytes");
+        memcpy(dst, st, sizeof st);
+        return TQ_OK;
+    }
     const void *src = which == 0 ? (const void *)ctx->d_cm : which == 1 ? (const void *)ctx->d_de
                       : which == 2 ? (const void *)ctx->d_sv : which == 3 ? (const void *)ctx->d_bdsqr_stats : nullptr;
     if (!src) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: nothing to fetch (which=%d)", which);

@@ -54,6 +54,44 @@ def pinned_empty(shape, dtype) -> np.ndarray:
     return raw[:n].view(dtype).reshape(shape)
 
 
+PACK_PAD = 0xFFFFFFFF
+
+
+def pack_sites(tmpmap: np.ndarray, tmparr: np.ndarray | None = None):
+    """The site order of the packed layout (option ``site_pack``, csrc/pack.hpp; host code, no GPU needed):
+    ``src`` u32[S'] with ``src[p]`` = the site packed position p holds or PACK_PAD, S' a multiple of 2048.  With
+    ``tmparr`` also what the automatic rule of ``set_data`` decides: returns (src, pays, estimate) with estimate =
+    (predicted instructions per quartet natural, packed, walk trips per quartet natural, packed, relative gain in
+    instructions lowered by two standard errors of the sample -- the rule takes the packed layout from 0.03 on)."""
+    lib = _lib.load()
+    tm = np.asarray(tmpmap)
+    stride = tm.shape[1] if tm.ndim == 2 else 1
+    tm = np.ascontiguousarray(tm, dtype=np.uint32)
+    S = tm.shape[0]
+    arr = None
+    if tmparr is not None:
+        arr = np.ascontiguousarray(tmparr, dtype=np.uint8)
+        if arr.ndim != 2 or arr.shape[1] != S:
+            raise ValueError("tmparr must be [ntaxa, nsites] with one column per tmpmap row")
+    T = arr.shape[0] if arr is not None else 0
+    n = ctypes.c_int64()
+    pays = ctypes.c_int32(-1)
+    est = np.zeros(5, np.float64)
+
+    def call(src, cap):
+        rc = lib.tq_pack_sites(_ptr(arr), T, S, _ptr(tm), stride, _ptr(src), cap, ctypes.byref(n), ctypes.byref(pays),
+                               _ptr(est))
+        if rc != 0:
+            raise TetradHipError(rc, "tq_pack_sites failed")
+
+    call(None, 0)
+    src = np.empty(n.value, np.uint32)
+    call(src, src.shape[0])
+    if arr is None:
+        return src
+    return src, bool(pays.value), tuple(est.tolist())
+
+
 class QuartetEngine:
     def __init__(self, device_id: int = 0):
         self._lib = _lib.load()
@@ -288,6 +326,12 @@ class QuartetEngine:
         out = np.zeros(shape, dt)
         self._check(self._lib.tq_debug_fetch(self._h, code, _ptr(out), out.nbytes))
         return out
+
+    def site_pack_state(self):
+        """Test hook: (padded site count of the packed layout set or 0, whether the subsample scans read it now)."""
+        out = np.zeros(2, np.int64)
+        self._check(self._lib.tq_debug_fetch(self._h, 4, _ptr(out), out.nbytes))
+        return int(out[0]), bool(out[1])
 
     def debug_bdsqr(self, de: np.ndarray, reps: int = 5):
         """Test hook: the bidiagonal-QR kernel alone on `de` f64[nmat,32] in the given order ->
