@@ -3,7 +3,11 @@
 RNG-stream parity with the reference is unpinned (numba's stream), so the device
 replicate is checked against the structural definition (oracle/resample.check_replicate), for
 determinism, for the distribution of the random choices, and end to end: resolving quartets on the
-device-built replicate must equal the oracle run on the exported (tmparr, tmpmap)."""
+device-built replicate must equal the oracle run on the exported (tmparr, tmpmap).
+
+The resident layout of a replicate under every scan kernel, the life cycle of its buffers and the device's random stream
+bit for bit against a NumPy model: tests/test_gpu_bootstrap_layout.py (model: tests/bootstrap_stream_model.py, its
+statistics: tests/test_bootstrap_stream_cpu.py)."""
 import numpy as np
 import pytest
 

@@ -112,6 +112,18 @@ def test_replicate_runner_equals_step_by_step(oracle, sampler):
     """Four replicates through the pipelined runner == the same draws applied step by step with a second
     engine (synchronous bootstrap + resolve), and == the oracle on the exported replicate for a sample; the
     Generator ends where the reference's would."""
+    _runner_against_step_by_step(oracle, sampler, True, {})
+
+
+@pytest.mark.parametrize("sub", [True, False])
+def test_replicate_runner_equals_step_by_step_on_the_cooperative_kernels(oracle, sub):
+    """The same above the cooperative thresholds (wg_min_quartets 64, dp_min_quartets 2), in both modes: the scans of
+    replicate k then run on the workgroup kernels -- plane records in subsample mode, the joint histogram on nib5 in full
+    mode -- while replicate k+1 is being built over the same buffers."""
+    _runner_against_step_by_step(oracle, "host", sub, {"wg_min_quartets": 64, "dp_min_quartets": 2})
+
+
+def _runner_against_step_by_step(oracle, sampler, sub, options):
     import torch
     from math import comb
     from tetrad_amd import bootstrap, synth
@@ -121,14 +133,18 @@ def test_replicate_runner_equals_step_by_step(oracle, sampler):
     Q, nreps, seed = 700, 4, 99
     got = {}
     with QuartetEngine(0) as eng:
+        for name, value in options.items():
+            eng.set_option(name, value)
         runner = ReplicateRunner(eng, seqarr, spans, Q, seed=seed, sampler=sampler, ahead=2)
-        stats = runner.run(nreps, True, on_result=lambda k, S, a, b, c: got.__setitem__(k, (S, a.copy(), b.copy(), c.copy())))
+        stats = runner.run(nreps, sub, on_result=lambda k, S, a, b, c: got.__setitem__(k, (S, a.copy(), b.copy(), c.copy())))
         final_state = runner.rng.bit_generator.state
         runner.close()
     assert sorted(got) == list(range(nreps)) and len(stats["sites"]) == nreps
     rng = np.random.default_rng(seed)
     dev = torch.device("cuda:0")
     with QuartetEngine(0) as eng:
+        for name, value in options.items():
+            eng.set_option(name, value)
         eng.set_source(seqarr, spans)
         for k in range(nreps):
             lidxs, s1, s2 = bootstrap.draw_replicate(len(spans), rng)
@@ -143,14 +159,14 @@ def test_replicate_runner_equals_step_by_step(oracle, sampler):
                 torch.cuda.synchronize()
                 q = d_q.cpu().numpy().view(np.uint32)
                 assert len(np.unique(q, axis=0)) == Q
-            rstat, rscor, flags = eng.resolve(q, True)
+            rstat, rscor, flags = eng.resolve(q, sub)
             assert got[k][0] == S
             np.testing.assert_array_equal(got[k][1], rstat)
             np.testing.assert_array_equal(got[k][2], rscor)
             np.testing.assert_array_equal(got[k][3], flags)
             if k == nreps - 1:
                 tmparr, tmpmap = eng.get_data()
-                _, o_rstat, o_rscor, o = oracle.new_infer_resolved_quartets(tmparr, tmpmap, q[:200], True, debug=True)
+                _, o_rstat, o_rscor, o = oracle.new_infer_resolved_quartets(tmparr, tmpmap, q[:200], sub, debug=True)
                 np.testing.assert_array_equal(rstat[:200, 1], o_rstat[:, 1])
                 ok = ((flags[:200] | o["flags"]) & 3) == 0
                 np.testing.assert_array_equal(rstat[:200][ok, 0], o_rstat[ok, 0])
