@@ -237,15 +237,27 @@ int tq_timing_read_kernels(tq_ctx *ctx, double *ms, int n_ms, int64_t *calls);
  * rows, bit for bit.  -1: built when the predicted instruction count of the scan falls (dense matrices; not for sparse
  * RAD-like ones, where the walk is short anyway and only the extra steps would cost -- no second copy is made then);
  * 1: always built; 0: never built, and a copy already built is no longer used (-1 / 1 set after tq_set_data take effect
- * with the next one).  Full mode, species mode, tq_get_data and device-built bootstrap replicates use the natural layout.
- * NOTE: 0 is a value of its own for this option, the default is -1.                                                */
+ * with the next one).  Full mode, species mode and tq_get_data use the natural layout.
+ * NOTE: 0 is a value of its own for this option, the default is -1.
+ * boot_pack (0, default; read by tq_bootstrap / tq_bootstrap_async): whether a device-built bootstrap replicate gets a
+ * packed copy too.  0: the replicate keeps the natural layout only, and a packed copy left by tq_set_data goes stale;
+ * 1: every replicate is packed -- the host plans the packed order from the widths of the drawn loci (no work per site, no
+ * device round trip: the call stays asynchronous), the packed start of every draw goes to the device with the locus indices
+ * and two more kernels build the copy right behind the natural one on the same stream; the same rows, bit for bit;
+ * -1: packed when the automatic rule of site_pack = -1 took the packed layout for the SOURCE (decided once, in
+ * tq_set_source, on the loci of the source with a two-base IUPAC code counted as present: a replicate resamples those
+ * loci, so their statistics are the replicate's).  site_pack = 0 keeps its meaning: no packed copy is read, and none is
+ * built for replicates either.                                                                                      */
 int tq_set_option(tq_ctx *ctx, const char *name, int64_t value);
 
 /* Test hook: copy the scratch of the last resolve call to the host.  which = 0: count slab
  * u32[n][256] of the last scan batch; 1: bidiagonals f64[3m][32] (d[16], e[16]); 2: singular values
  * f64[3m][16] (unsorted, sign bit = not converged), m = quartets of the last singular-value chunk; 3: the 8 u64 counters
  * of option bdsqr_stats; 4: two i64 about the packed layout set of option site_pack: its padded site count (0 = none is
- * resident) and 1 if a subsample-mode scan issued now would read it.  No reference counterpart.                        */
+ * resident) and 1 if a subsample-mode scan issued now would read it; 5: the site order of the packed copy of the current
+ * device-built replicate (option boot_pack) as u32[that padded site count] -- entry p = the replicate's site at packed
+ * position p or 0xFFFFFFFF for a pad, what tq_pack_sites gives for the replicate's tmpmap -- TQ_ERR_INVALID_ARG when the
+ * current packed copy was not built by tq_bootstrap or is stale.  No reference counterpart.                           */
 int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes);
 
 /* Test hook: run the bidiagonal-QR kernel (tq_bdsqr_kernel) alone on nmat bidiagonals given on the host -- de f64[nmat][32]

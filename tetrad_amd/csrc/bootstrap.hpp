@@ -116,6 +116,69 @@ __global__ void tq_boot_build_kernel(const uint8_t *__restrict__ seqarr, int64_t
     reinterpret_cast<uint4 *>(nib5 + t * (Sp / 2))[w] = make_uint4(n5[0], n5[1], n5[2], n5[3]);
 }
 
+// ------------------------------------------------------------------------------------
+// Packed layout set of the replicate (option boot_pack; pack.hpp).  The host plans at locus level and hands over the
+// packed start of every resampled locus; the site-level map and the second copy are made here, behind the natural build.
+// ------------------------------------------------------------------------------------
+// one thread per natural site: pk_src[packed start of its locus + offset in the locus] = s (pk_src pre-filled with pads)
+__global__ void tq_boot_pack_map_kernel(const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ site_locus,
+                                        const uint32_t *__restrict__ pstart, int64_t S, int64_t n, int64_t pSp,
+                                        uint32_t *__restrict__ pk_src)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const uint32_t l = site_locus[s];
+    if ((int64_t)l >= n) return;
+    const int64_t p = (int64_t)pstart[l] + (s - (int64_t)offsets[l]);
+    if (p >= 0 && p < pSp) pk_src[p] = (uint32_t)s;
+}
+
+// one thread per 32-site word of one taxon row of the PACKED set, gathered from the natural arrays tq_boot_build_kernel
+// has just written (so the resolved bases are the same: no coin is drawn again): code and missing flag of site s from its
+// nib5 nibble, its run-begin bit from the natural run-begin words.  The rule of tq_prepare_rows for a source map: a pad
+// is missing in every taxon and carries no run-begin bit.  A word's 32 row bytes are two 16-byte pieces (row_offset).
+__global__ void tq_boot_pack_build_kernel(const uint32_t *__restrict__ pk_src, const uint8_t *__restrict__ nib5,
+                                          const uint32_t *__restrict__ runbeg_nat, int64_t S, int64_t Sp, int64_t pSp,
+                                          int64_t pW, int32_t T, uint8_t *__restrict__ rows, uint8_t *__restrict__ nib,
+                                          uint4 *__restrict__ planes, uint32_t *__restrict__ planes3,
+                                          uint32_t *__restrict__ runbeg)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)T * pW) return;
+    const int64_t t = gid / pW, w = gid - t * pW;
+    const uint8_t *src = nib5 + t * (Sp / 2);
+    const uint4 *map = reinterpret_cast<const uint4 *>(pk_src + w * 32);
+    uint32_t mm = 0, b0 = 0, b1 = 0, rb = 0;
+    uint32_t nw[4] = {0, 0, 0, 0}, rw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint4 m4 = map[j];
+        const uint32_t site[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = 4 * j + k;
+            const int64_t s = (int64_t)site[k];
+            uint32_t c = 4;
+            if (s < S) {                                           // a pad is 0xFFFFFFFF
+                c = (uint32_t)(src[nib_offset(s)] >> nib_shift(s)) & 15u;
+                rb |= ((runbeg_nat[s >> 5] >> (s & 31)) & 1u) << i;
+            }
+            const uint32_t missing = c > 3u, code = missing ? 0u : c;
+            rw[i >> 2] |= code << (8 * (i & 3));
+            nw[i >> 3] |= code << (8 * (i & 3) + 4 * ((i >> 2) & 1));
+            mm |= missing << i;
+            b0 |= (code & 1u) << i;
+            b1 |= ((code >> 1) & 1u) << i;
+        }
+    }
+    uint8_t *dst = rows + t * pSp + row_offset(w * 32);
+    reinterpret_cast<uint4 *>(dst)[0] = make_uint4(rw[0], rw[1], rw[2], rw[3]);
+    reinterpret_cast<uint4 *>(dst + 1024)[0] = make_uint4(rw[4], rw[5], rw[6], rw[7]);
+    planes[t * pW + w] = make_uint4(mm, b0, b1, rb);
+    store_planes3(planes3, runbeg, t, pW, w, mm, b0, b1, rb);
+    reinterpret_cast<uint4 *>(nib + t * (pSp / 2))[w] = make_uint4(nw[0], nw[1], nw[2], nw[3]);
+}
+
 // replicate currently on the device -> the reference's tmparr (0..3, 78) / tmpmap layout
 __global__ void tq_export_kernel(const uint8_t *__restrict__ rows, const uint4 *__restrict__ planes, int64_t S,
                                  int64_t Sp, int64_t W, int32_t T, uint8_t *__restrict__ tmparr,

@@ -47,73 +47,85 @@ inline void locus_runs(const uint32_t *loc, int64_t S, std::vector<LocusRun> &ru
     }
 }
 
-// src[p] = original site of packed position p, or PACK_PAD; src.size() is a multiple of TILE
-inline void pack_sites(const std::vector<LocusRun> &runs, std::vector<uint32_t> &src)
-{
-    const size_t n = runs.size();
-    // loci by falling length: the long ones (> 32 sites) first, then buckets 32 .. 1, each in the original order
-    std::vector<uint32_t> by_len;
-    by_len.reserve(n);
+// The packing plan at locus level: packed start of every run from the run lengths alone (no work per site).  The scratch
+// vectors live in the planner and keep their capacity, so a planner that is kept (one per bootstrap source) allocates
+// nothing once it has seen its number of loci.
+struct PackPlanner {
+    std::vector<uint64_t> start;                     // start[i] = packed position of the first site of run i
+    std::vector<uint32_t> by_len, bin_of, bin_count, first, fill, member, order;
+    std::vector<uint32_t> open[33];                  // open[r]: bins with r free sites
+    std::vector<uint32_t> bucket[33];
+
+    // len_of(i) = sites of run i (>= 1), runs in the order of the matrix; returns the padded length, a multiple of TILE
+    template <typename LenOf>
+    size_t plan(size_t n, LenOf len_of)
     {
-        std::vector<uint32_t> bucket[33];
+        // loci by falling length: the long ones (> 32 sites) first, then buckets 32 .. 1, each in the original order
+        by_len.clear();
+        for (auto &v : bucket) v.clear();
         for (size_t i = 0; i < n; ++i) {
-            if (runs[i].len > 32) by_len.push_back((uint32_t)i);
-            else bucket[runs[i].len].push_back((uint32_t)i);
+            const int64_t len = (int64_t)len_of(i);
+            if (len > 32) by_len.push_back((uint32_t)i);
+            else bucket[len].push_back((uint32_t)i);
         }
         for (int l = 32; l >= 1; --l) by_len.insert(by_len.end(), bucket[l].begin(), bucket[l].end());
-    }
-    // a bin = one word, preceded by the full words of a long first locus; `count` = loci that may be counted in its word
-    struct Bin {
-        uint32_t count;
-    };
-    std::vector<Bin> bins;
-    std::vector<uint32_t> bin_of(n);
-    std::vector<uint32_t> open[33];                  // open[r]: bins with r free sites
-    for (uint32_t i : by_len) {
-        const int64_t len = runs[i].len;
-        const int need = (int)(len > 32 ? (len - 1) % 32 + 1 : len);       // sites in the bin's own word
-        int r = 33;
-        if (len <= 32)
-            for (r = need; r <= 32 && open[r].empty(); ++r) {}
-        uint32_t b;
-        if (r <= 32) {
-            b = open[r].back();
-            open[r].pop_back();
-        } else {
-            b = (uint32_t)bins.size();
-            bins.push_back({0});
-            r = 32;
+        // a bin = one word, preceded by the full words of a long first locus; its count = loci that may be counted in its word
+        bin_count.clear();
+        bin_of.resize(n);
+        for (auto &v : open) v.clear();
+        for (uint32_t i : by_len) {
+            const int64_t len = (int64_t)len_of(i);
+            const int need = (int)(len > 32 ? (len - 1) % 32 + 1 : len);       // sites in the bin's own word
+            int r = 33;
+            if (len <= 32)
+                for (r = need; r <= 32 && open[r].empty(); ++r) {}
+            uint32_t b;
+            if (r <= 32) {
+                b = open[r].back();
+                open[r].pop_back();
+            } else {
+                b = (uint32_t)bin_count.size();
+                bin_count.push_back(0);
+                r = 32;
+            }
+            bin_of[i] = b;
+            bin_count[b]++;
+            if (r - need > 0) open[r - need].push_back(b);
         }
-        bin_of[i] = b;
-        bins[b].count++;
-        if (r - need > 0) open[r - need].push_back(b);
-    }
-    // the loci of each bin, in placement order (a long locus is the first of its bin)
-    const size_t nb = bins.size();
-    std::vector<uint32_t> first(nb + 1, 0), member(n);
-    for (size_t i = 0; i < n; ++i) first[bin_of[i] + 1]++;
-    for (size_t b = 0; b < nb; ++b) first[b + 1] += first[b];
-    {
-        std::vector<uint32_t> fill(first.begin(), first.end() - 1);
+        // the loci of each bin, in placement order (a long locus is the first of its bin)
+        const size_t nb = bin_count.size();
+        first.assign(nb + 1, 0);
+        member.resize(n);
+        for (size_t i = 0; i < n; ++i) first[bin_of[i] + 1]++;
+        for (size_t b = 0; b < nb; ++b) first[b + 1] += first[b];
+        fill.assign(first.begin(), first.end() - 1);
         for (uint32_t i : by_len) member[fill[bin_of[i]]++] = i;
-    }
-    // bins by falling count (stable)
-    std::vector<uint32_t> order;
-    order.reserve(nb);
-    {
-        std::vector<uint32_t> bucket[33];
-        for (size_t b = 0; b < nb; ++b) bucket[bins[b].count].push_back((uint32_t)b);
+        // bins by falling count (stable)
+        order.clear();
+        for (auto &v : bucket) v.clear();
+        for (size_t b = 0; b < nb; ++b) bucket[bin_count[b]].push_back((uint32_t)b);
         for (int c = 32; c >= 1; --c) order.insert(order.end(), bucket[c].begin(), bucket[c].end());
-    }
-    src.clear();
-    for (uint32_t b : order) {
-        for (uint32_t k = first[b]; k < first[b + 1]; ++k) {
-            const LocusRun &run = runs[member[k]];
-            for (int64_t s = 0; s < run.len; ++s) src.push_back((uint32_t)(run.start + s));
+        start.resize(n);
+        size_t pos = 0;
+        for (uint32_t b : order) {
+            for (uint32_t k = first[b]; k < first[b + 1]; ++k) {
+                start[member[k]] = pos;
+                pos += (size_t)len_of(member[k]);
+            }
+            pos = pack_round_up(pos, 32);
         }
-        src.resize(pack_round_up(src.size(), 32), PACK_PAD);
+        return pack_round_up(pos ? pos : 1, TILE);
     }
-    src.resize(pack_round_up(src.size() ? src.size() : 1, TILE), PACK_PAD);
+};
+
+// src[p] = original site of packed position p, or PACK_PAD; src.size() is a multiple of TILE: the plan, site by site
+inline void pack_sites(const std::vector<LocusRun> &runs, std::vector<uint32_t> &src)
+{
+    PackPlanner pl;
+    const size_t total = pl.plan(runs.size(), [&runs](size_t i) { return runs[i].len; });
+    src.assign(total, PACK_PAD);
+    for (size_t i = 0; i < runs.size(); ++i)
+        for (int64_t s = 0; s < runs[i].len; ++s) src[pl.start[i] + (size_t)s] = (uint32_t)(runs[i].start + s);
 }
 
 // Walk trips and predicted cost per quartet of the natural and of the packed layout, from PACK_SAMPLE pseudo-random

@@ -181,8 +181,9 @@ struct tq_ctx {
     uint64_t data_gen = 0;          // bumped by tq_set_data / tq_bootstrap(_async)
     uint64_t sp_tab_gen = ~0ull;    // data_gen the species table was built from (~0: none)
     // packed layout set (pack.hpp): a second copy of rows / nib / planes / planes3 + runbeg with whole loci per lane word,
-    // read by the subsample-mode scans while it is current (pk_gen == data_gen; a device-built bootstrap replicate
-    // keeps the natural layout only and leaves this set stale).  Everything else reads the natural set.
+    // read by the subsample-mode scans while it is current (pk_gen == data_gen).  tq_set_data builds it under site_pack,
+    // tq_bootstrap_async under boot_pack (a replicate built without it leaves the set stale).  Everything else reads the
+    // natural set.
     int site_pack = -1;             // -1: tq_set_data builds the set when the predicted scan cost falls (pack.hpp), 1: always
                                     // (while subsample mode is possible), 0: never, and a built set is not used
     uint8_t *pk_rows = nullptr, *pk_nib = nullptr;
@@ -190,6 +191,17 @@ struct tq_ctx {
     uint32_t *pk_planes3 = nullptr; // [T][pk_W][3], then runbeg [pk_W]
     int64_t pk_Sp = 0, pk_W = 0;
     uint64_t pk_gen = ~0ull;        // data_gen the set was built from (~0: none)
+    int64_t pk_cap = 0;             // sites per row the pk_* arrays were allocated for (they grow only while T stays)
+    // packed set of a device-built replicate (bootstrap.hpp: tq_boot_pack_*): planned on the host at locus level
+    int boot_pack = 0;              // 1: every replicate is packed, -1: when the rule said so for the source (boot_pack_auto),
+                                    // 0: never (the replicate keeps the natural layout only); site_pack = 0 overrides
+    bool boot_pack_auto = false;    // pack_pays for the source matrix (tq_set_source): a replicate resamples its loci
+    bool pk_from_boot = false;      // the packed set was built by tq_bootstrap_async (d_pk_src is its map)
+    PackPlanner boot_plan;
+    uint32_t *d_pstart = nullptr;   // [nloci] packed start of every resampled locus
+    uint32_t *h_pstart_stage[2] = {nullptr, nullptr};    // page-locked staging, in turn with h_lidx_stage
+    uint32_t *d_pk_src = nullptr;   // [pk_src_cap] packed position -> natural site of the replicate, 0xFFFFFFFF = pad
+    int64_t pk_src_cap = 0;
     // host-buffer API: own compute and copy streams, events for the D2H pipeline
     hipStream_t sK = nullptr, sC = nullptr;
     std::vector<hipEvent_t> pipe_events;
@@ -343,8 +355,20 @@ void free_packed(tq_ctx *ctx)
     ctx->pk_nib = nullptr;
     ctx->pk_planes = nullptr;
     ctx->pk_planes3 = nullptr;
-    ctx->pk_Sp = ctx->pk_W = 0;
+    ctx->pk_Sp = ctx->pk_W = ctx->pk_cap = 0;
     ctx->pk_gen = ~0ull;
+    ctx->pk_from_boot = false;
+}
+
+int alloc_packed(tq_ctx *ctx, int64_t T, int64_t capSp)
+{
+    const int64_t capW = capSp / 32;
+    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_rows, (size_t)(T * capSp)));
+    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_nib, (size_t)(T * capSp / 2)));
+    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_planes, (size_t)(T * capW) * sizeof(uint4)));
+    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_planes3, (size_t)(T * capW * 3 + capW) * sizeof(uint32_t)));
+    ctx->pk_cap = capSp;
+    return TQ_OK;
 }
 
 void free_data(tq_ctx *ctx)
@@ -372,6 +396,13 @@ void free_source(tq_ctx *ctx)
     if (ctx->d_lidxs) (void)hipFree(ctx->d_lidxs);
     if (ctx->d_boot) (void)hipFree(ctx->d_boot);
     if (ctx->d_boot_tmp) (void)hipFree(ctx->d_boot_tmp);
+    if (ctx->d_pstart) (void)hipFree(ctx->d_pstart);
+    if (ctx->d_pk_src) (void)hipFree(ctx->d_pk_src);
+    ctx->d_pstart = nullptr;
+    ctx->d_pk_src = nullptr;
+    ctx->pk_src_cap = 0;
+    ctx->pk_from_boot = false;
+    ctx->boot_pack_auto = false;
     ctx->d_seqarr = nullptr;
     ctx->d_spans = nullptr;
     ctx->d_lidxs = nullptr;
@@ -381,6 +412,8 @@ void free_source(tq_ctx *ctx)
     ctx->nloci = 0;
     for (int i = 0; i < 2; ++i) {
         if (ctx->h_lidx_stage[i]) (void)pool().release(ctx->h_lidx_stage[i]);
+        if (ctx->h_pstart_stage[i]) (void)pool().release(ctx->h_pstart_stage[i]);
+        ctx->h_pstart_stage[i] = nullptr;
         if (ctx->ev_lidx[i]) (void)hipEventDestroy(ctx->ev_lidx[i]);
         ctx->h_lidx_stage[i] = nullptr;
         ctx->ev_lidx[i] = nullptr;
@@ -1781,6 +1814,7 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
     if (pSp) {
         ctx->pk_Sp = pSp;
         ctx->pk_W = pW;
+        ctx->pk_cap = pSp;
         ctx->pk_gen = ctx->data_gen;
     }
     return TQ_OK;
@@ -2175,6 +2209,11 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
         ctx->site_pack = (int)value;
         return TQ_OK;
     }
+    if (!strcmp(name, "boot_pack")) {
+        if (value < -1 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "boot_pack must be -1 (automatic), 0 or 1");
+        ctx->boot_pack = (int)value;
+        return TQ_OK;
+    }
     if (!strcmp(name, "scan_dp")) {
         if (value != 0 && value != 1) return fail(ctx, TQ_ERR_INVALID_ARG, "scan_dp must be 0 or 1");
         ctx->scan_dp = (int)value;
@@ -2308,9 +2347,43 @@ int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, con
         return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of host memory");
     }
     for (int i = 0; i < 2; ++i) {
-        if (pool().alloc((size_t)nloci * 8, (void **)&ctx->h_lidx_stage[i]) != TQ_OK)
+        if (pool().alloc((size_t)nloci * 8, (void **)&ctx->h_lidx_stage[i]) != TQ_OK ||
+            pool().alloc((size_t)nloci * 4, (void **)&ctx->h_pstart_stage[i]) != TQ_OK)
             return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of page-locked host memory");
         TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_lidx[i], hipEventDisableTiming));
+    }
+    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_pstart, (size_t)nloci * sizeof(uint32_t)));
+    // the automatic rule of boot_pack = -1, once, on the source: its loci (the spans, in their order) with the bases recoded
+    // as tq_set_data takes them -- a two-base IUPAC code counts as present (its first base) -- under the rule and the
+    // 32-bit-offset condition of tq_set_data.  A replicate resamples these loci, so their statistics are the replicate's.
+    try {
+        std::vector<LocusRun> runs((size_t)nloci);
+        int64_t Ssrc = 0;
+        for (int64_t i = 0; i < nloci; ++i) {
+            runs[(size_t)i] = {Ssrc, spans[2 * i + 1] - spans[2 * i]};
+            Ssrc += runs[(size_t)i].len;
+        }
+        if (Ssrc < 0xFFFFFFFFll) {
+            uint8_t code[256];
+            memset(code, 78, sizeof code);
+            for (int v = 0; v < 4; ++v) code[v] = (uint8_t)v;
+            code[65] = 0; code[67] = 1; code[71] = 2; code[84] = 3;
+            code[82] = 0; code[75] = 3; code[83] = 1; code[89] = 1; code[87] = 0; code[77] = 0;     // R K S Y W M
+            std::vector<uint8_t> arr((size_t)(T * Ssrc));
+            for (int64_t t = 0; t < T; ++t)
+                for (int64_t i = 0; i < nloci; ++i)
+                    for (int64_t s = 0; s < runs[(size_t)i].len; ++s)
+                        arr[(size_t)(t * Ssrc + runs[(size_t)i].start + s)] = code[seqarr[t * S0 + spans[2 * i] + s]];
+            std::vector<uint32_t> src;
+            pack_sites(runs, src);
+            double cost[2], trips[2];
+            const double gain_low = pack_estimate(arr.data(), T, Ssrc, runs, src, cost, trips);
+            const bool fits = (uint64_t)T * (uint64_t)src.size() < 0xFFFF0000ull ||
+                              (uint64_t)T * (uint64_t)align_up((size_t)Ssrc, TILE) >= 0xFFFF0000ull;
+            ctx->boot_pack_auto = pack_pays(gain_low) && fits;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of host memory");
     }
     ctx->src_T = T;
     ctx->src_S0 = S0;
@@ -2334,6 +2407,20 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: locus index %lld out of range", (long long)lidxs[i]);
         S += ctx->h_spans[2 * lidxs[i] + 1] - ctx->h_spans[2 * lidxs[i]];
     }
+    // the packed layout of the replicate, planned here at locus level (pack.hpp): the packed length is a launch argument,
+    // so it has to be known at enqueue time; only the packed start of every draw goes to the device
+    const bool pack = ctx->site_pack != 0 && (ctx->boot_pack > 0 || (ctx->boot_pack < 0 && ctx->boot_pack_auto));
+    int64_t pSp = 0;
+    if (pack) {
+        const int64_t *sp = ctx->h_spans.data();
+        try {
+            pSp = (int64_t)ctx->boot_plan.plan((size_t)n, [sp, lidxs](size_t i) { return sp[2 * lidxs[i] + 1] - sp[2 * lidxs[i]]; });
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, TQ_ERR_OOM, "tq_bootstrap: out of host memory");
+        }
+        if (pSp >= 0xFFFFFFFFll) pSp = 0;              // the map holds positions as u32: such a replicate keeps the natural layout
+    }
+    const int64_t pW = pSp / 32;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc0 = enter_dev_api(ctx, stream)) return rc0;      // a resolve still scanning the previous replicate on another stream
     const int64_t T = ctx->src_T;
@@ -2372,6 +2459,22 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
         ctx->plane_cap_W = capSp / 32;
         ctx->data_capacity = capSp;
     }
+    // the packed set grows only, with the same head-room; a set tq_set_data allocated serves while it is large enough
+    if (pSp > ctx->pk_cap || pSp > ctx->pk_src_cap) {
+        TQ_HIP(ctx, hipDeviceSynchronize());
+        const int64_t capSp = (int64_t)align_up((size_t)(pSp + pSp / 8), TILE);
+        if (pSp > ctx->pk_cap) {
+            free_packed(ctx);
+            if (int rc1 = alloc_packed(ctx, T, capSp)) return rc1;
+        }
+        if (pSp > ctx->pk_src_cap) {
+            if (ctx->d_pk_src) (void)hipFree(ctx->d_pk_src);
+            ctx->d_pk_src = nullptr;
+            ctx->pk_src_cap = 0;
+            TQ_HIP(ctx, hipMalloc((void **)&ctx->d_pk_src, (size_t)capSp * sizeof(uint32_t)));
+            ctx->pk_src_cap = capSp;
+        }
+    }
     uint32_t *widths = ctx->d_boot, *offsets = widths + (n + 1);
     uint32_t *src_col = offsets + (n + 1), *site_locus = src_col + ctx->boot_cap;
     // locus indices through a page-locked staging piece (two in turn, so that the draws of the next replicate
@@ -2380,6 +2483,11 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
     TQ_HIP(ctx, hipEventSynchronize(ctx->ev_lidx[turn]));
     memcpy(ctx->h_lidx_stage[turn], lidxs, (size_t)n * 8);
     TQ_HIP(ctx, hipMemcpyAsync(ctx->d_lidxs, ctx->h_lidx_stage[turn], (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    if (pSp) {
+        uint32_t *stage = ctx->h_pstart_stage[turn];
+        for (int64_t i = 0; i < n; ++i) stage[i] = (uint32_t)ctx->boot_plan.start[(size_t)i];
+        TQ_HIP(ctx, hipMemcpyAsync(ctx->d_pstart, stage, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    }
     TQ_HIP(ctx, hipEventRecord(ctx->ev_lidx[turn], stream));
     TQ_HIP(ctx, hipMemsetAsync(widths + n, 0, sizeof(uint32_t), stream));
     hipLaunchKernelGGL(tq_boot_width_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->d_spans,
@@ -2393,6 +2501,19 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
                        ctx->src_S0, src_col, site_locus, S, Sp, W, (int32_t)T, seed_ambig, ctx->d_rows, ctx->d_nib, ctx->d_nib5,
                        ctx->d_planes, ctx->d_planes3, ctx->d_planes3 + (size_t)T * (size_t)ctx->plane_cap_W * 3);
     TQ_HIP(ctx, hipGetLastError());
+    if (pSp) {
+        uint32_t *nat_runbeg = ctx->d_planes3 + (size_t)T * (size_t)ctx->plane_cap_W * 3;
+        TQ_HIP(ctx, hipMemsetAsync(ctx->d_pk_src, 0xFF, (size_t)pSp * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(tq_boot_pack_map_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream,
+                           (const uint32_t *)offsets, (const uint32_t *)site_locus, (const uint32_t *)ctx->d_pstart, S, n, pSp,
+                           ctx->d_pk_src);
+        const int64_t np = T * pW;
+        hipLaunchKernelGGL(tq_boot_pack_build_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream,
+                           (const uint32_t *)ctx->d_pk_src, (const uint8_t *)ctx->d_nib5, (const uint32_t *)nat_runbeg, S, Sp,
+                           pSp, pW, (int32_t)T, ctx->pk_rows, ctx->pk_nib, ctx->pk_planes, ctx->pk_planes3,
+                           ctx->pk_planes3 + (size_t)T * (size_t)pW * 3);
+        TQ_HIP(ctx, hipGetLastError());
+    }
     ctx->T = T;
     ctx->S = S;
     ctx->Sp = Sp;
@@ -2401,6 +2522,12 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
     ctx->locus_runs_ok = true;          // locus ids are the ordinals 0..n-1, one run each
     ctx->scanned_Q = 0;
     ctx->data_gen++;                    // the species table is rebuilt by the next species call
+    if (pSp) {
+        ctx->pk_Sp = pSp;
+        ctx->pk_W = pW;
+        ctx->pk_gen = ctx->data_gen;
+        ctx->pk_from_boot = true;
+    }
     if (out_S) *out_S = S;
     return note_dev_api(ctx, stream, TQ_OK);       // the host API must not scan a half-built replicate
 }
@@ -2485,6 +2612,16 @@ int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes)
         const int64_t st[2] = {ctx->pk_rows ? ctx->pk_Sp : 0, scan_data(ctx, 1).rows == ctx->pk_rows && ctx->pk_rows ? 1 : 0};
         if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=4 takes 16 bytes");
         memcpy(dst, st, sizeof st);
+        return TQ_OK;
+    }
+    if (which == 5) {                       // the map of the current replicate's packed set (option boot_pack)
+        if (!ctx->pk_from_boot || !ctx->pk_rows || ctx->pk_gen != ctx->data_gen)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 needs a current packed set built by tq_bootstrap");
+        if (bytes != ctx->pk_Sp * (int64_t)sizeof(uint32_t))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 takes %lld bytes", (long long)(ctx->pk_Sp * 4));
+        TQ_HIP(ctx, hipSetDevice(ctx->device));
+        TQ_HIP(ctx, hipDeviceSynchronize());
+        TQ_HIP(ctx, hipMemcpy(dst, ctx->d_pk_src, (size_t)bytes, hipMemcpyDeviceToHost));
         return TQ_OK;
     }
     const void *src = which == 0 ? (const void *)ctx->d_cm : which == 1 ? (const void *)ctx->d_de

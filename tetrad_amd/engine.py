@@ -333,6 +333,13 @@ class QuartetEngine:
         self._check(self._lib.tq_debug_fetch(self._h, 4, _ptr(out), out.nbytes))
         return int(out[0]), bool(out[1])
 
+    def boot_pack_map(self) -> np.ndarray:
+        """Test hook: the site order of the packed set the current device-built replicate carries (option ``boot_pack``):
+        u32[S'] as `pack_sites` returns it for the replicate's tmpmap.  Refused when the replicate was not packed."""
+        out = np.zeros(self.site_pack_state()[0], np.uint32)
+        self._check(self._lib.tq_debug_fetch(self._h, 5, _ptr(out), out.nbytes))
+        return out
+
     def debug_bdsqr(self, de: np.ndarray, reps: int = 5):
         """Test hook: the bidiagonal-QR kernel alone on `de` f64[nmat,32] in the given order ->
         (sv f64[nmat,16], rotation steps u32[nmat], sweeps u32[nmat], ms per launch)."""
