@@ -399,6 +399,51 @@ int tq_stree_rows(tq_stree *acc, uint32_t *splits, uint64_t *k, int64_t *n);
 int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_t cap, int64_t *written, int64_t *levels);
 int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out);
 
+/* Majority-rule consensus: how many trees of a set contain each split, counted exactly, the
+ * consensus tree built from the counts, and the counts written onto the edges of a given tree (the computation behind
+ * the reference's `tetrad consensus`, cli_consensus.py:87-132).  The host and the device execution return identical
+ * arrays and strings.
+ *   Trees are parent arrays as tq_conc_create takes them (tips 0..T-1 = the taxa, parent[root] = -1; a root of degree 2
+ *   is dissolved, unary nodes are suppressed; multifurcations allowed), 4 <= T <= 4096.  A split is an internal edge
+ *   with at least 2 taxa on both sides; its mask is the side without taxon 0, bit x of word x / 64 of W = ceil(T / 64)
+ *   u64 words.  Table order: count descending, then the mask ascending as one integer (word W - 1 most significant).
+ *   tq_cons_create  max_splits = distinct splits the table may hold (1..2^26).  `ctx` NULL: host back end.  With a
+ *                   context all device and page-locked memory is allocated here: the table (max_splits x (W + 3) x 8
+ *                   bytes) and one chunk of trees within the option "cons_scratch_bytes".  The context must outlive the
+ *                   accumulator; messages go to tq_last_error(ctx).
+ *   tq_cons_add     parents i32[R][stride], n_nodes i64[R] (each <= stride).  Every tree is validated first: one bad
+ *                   tree is TQ_ERR_INVALID_ARG naming its index, and nothing is added.  Device back end: the kernels
+ *                   run on `stream` (hipStream_t, NULL = default stream) chunk by chunk; the call returns with the last
+ *                   chunk in flight.  Adds on different streams are ordered in call order.
+ *   tq_cons_shape   T, W, trees added, distinct splits (any may be NULL; asking for the splits waits for device work).
+ *   tq_cons_read    masks u64[nsplits][W], counts i64[nsplits] in table order (either may be NULL); waits for device work.
+ *   tq_cons_tree    the consensus as newick: walking the table, a split is accepted when count >= min_count (>= 1) and
+ *                   it is compatible with every accepted split (disjoint, or one side inside the other).  The root holds
+ *                   the maximal sides and the uncovered tips (taxon 0 among them), children are ordered by their
+ *                   smallest taxon, tips are taxon numbers, an accepted side carries the integer percent
+ *                   (200 count + ntrees) / (2 ntrees) as its label, no branch lengths.  *written = the length
+ *                   (TQ_ERR_OOM with the needed size when cap is too small).
+ *   tq_cons_support the splits of one given tree, masks ascending: counts_out i64[E] = the split's count in the table
+ *                   (0 when absent), masks_out u64[E][W] (either may be NULL, room for T - 3 splits), *n_edges = E.
+ *   tq_cons_stats   out i64[6] = {trees per chunk, chunks launched, entries of the device table, entries of the host
+ *                   map, splits that lost a hash collision and were counted on the host, hash bits}; since create / reset.
+ *   More distinct splits than max_splits: TQ_ERR_INVALID_ARG from the add or the read that notices, and from every call
+ *   after it until tq_cons_reset; nothing is ever written out of bounds.
+ * Options (tq_set_option): "cons_hash_bits" 1..64 (default 64; read at create / reset) cuts the table key, so that the
+ * collision path can be exercised: results never depend on it.  "cons_scratch_bytes" (default 256 MiB; read at create)
+ * bounds the device and page-locked memory of one chunk of trees.                                                       */
+typedef struct tq_cons tq_cons;
+int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx);
+void tq_cons_destroy(tq_cons *acc);
+int tq_cons_reset(tq_cons *acc);
+int tq_cons_add(tq_cons *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream);
+int tq_cons_shape(tq_cons *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits);
+int tq_cons_read(tq_cons *acc, uint64_t *masks, int64_t *counts);
+int tq_cons_tree(tq_cons *acc, int64_t min_count, char *out, int64_t cap, int64_t *written);
+int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_t *counts_out, uint64_t *masks_out,
+                    int64_t *n_edges);
+int tq_cons_stats(tq_cons *acc, int64_t *out);
+
 /* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
  * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
  * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.

@@ -37,6 +37,8 @@ SYMBOLS = [
     "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
     "tq_stree_create", "tq_stree_destroy", "tq_stree_reset", "tq_stree_add", "tq_stree_add_dev", "tq_stree_graph",
     "tq_stree_rows", "tq_stree_build", "tq_stree_level_stats",
+    "tq_cons_create", "tq_cons_destroy", "tq_cons_reset", "tq_cons_add", "tq_cons_shape", "tq_cons_read", "tq_cons_tree",
+    "tq_cons_support", "tq_cons_stats",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
     "tq_pack_sites",
 ]
@@ -207,6 +209,24 @@ def load() -> ctypes.CDLL:
     lib.tq_stree_build.restype = i32
     lib.tq_stree_level_stats.argtypes = [vp, c.POINTER(i64), vp]
     lib.tq_stree_level_stats.restype = i32
+    lib.tq_cons_create.argtypes = [c.POINTER(vp), i64, i64, vp]
+    lib.tq_cons_create.restype = i32
+    lib.tq_cons_destroy.argtypes = [vp]
+    lib.tq_cons_destroy.restype = None
+    lib.tq_cons_reset.argtypes = [vp]
+    lib.tq_cons_reset.restype = i32
+    lib.tq_cons_add.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.tq_cons_add.restype = i32
+    lib.tq_cons_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.tq_cons_shape.restype = i32
+    lib.tq_cons_read.argtypes = [vp, vp, vp]
+    lib.tq_cons_read.restype = i32
+    lib.tq_cons_tree.argtypes = [vp, i64, vp, i64, c.POINTER(i64)]
+    lib.tq_cons_tree.restype = i32
+    lib.tq_cons_support.argtypes = [vp, vp, i64, vp, vp, c.POINTER(i64)]
+    lib.tq_cons_support.restype = i32
+    lib.tq_cons_stats.argtypes = [vp, vp]
+    lib.tq_cons_stats.restype = i32
     lib.tq_set_species.argtypes = [vp, vp, i64, i64]
     lib.tq_set_species.restype = i32
     lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]

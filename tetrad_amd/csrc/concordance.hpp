@@ -39,9 +39,12 @@ struct ConcTree {
     std::vector<uint64_t> nqrts;                // [E] quartets the edge induces
 };
 
-// Tree from a parent array: tips 0..T-1 = taxa (no children), nodes >= T internal (at least one child),
-// parent[root] = -1.  Returns an empty string or what is wrong.
-inline std::string conc_build_tree(const int32_t *parent, int64_t n, int64_t T, ConcTree &t)
+// The preparation every tree goes through (shared with consensus.hpp): a parent array whose tips 0..T-1 are the taxa
+// (no children), nodes >= T internal (at least one child), parent[root] = -1, is validated, its unary nodes are
+// suppressed and a root of degree 2 is dissolved.  Out: `par` / `nch` of the prepared tree, root = node T, internal
+// nodes T..N-1 in BFS order.  Returns an empty string or what is wrong.
+inline std::string conc_prepare_tree(const int32_t *parent, int64_t n, int64_t T, std::vector<int32_t> &par,
+                                     std::vector<std::vector<int32_t>> &nch)
 {
     if (T < 4) return "a tree needs at least 4 taxa";
     if (T > CONC_T_MAX) return "T exceeds the LCA table limit of 4096 taxa";
@@ -104,11 +107,23 @@ inline std::string conc_build_tree(const int32_t *parent, int64_t n, int64_t T, 
     int32_t next = (int32_t)T;
     for (int32_t v : bfs) newid[v] = v < T ? v : next++;
     const int32_t N = next;
-    std::vector<int32_t> par(N, -1);
-    std::vector<std::vector<int32_t>> nch(N);
+    par.assign(N, -1);
+    nch.assign(N, std::vector<int32_t>());
     for (int32_t v : bfs)
         if (v >= T)
             for (int32_t c : ch[v - T]) { par[newid[c]] = newid[v]; nch[newid[v]].push_back(newid[c]); }
+    return std::string();
+}
+
+// Tree from a parent array (`conc_prepare_tree`) with the tables of the concordance kernel.  Returns an empty string
+// or what is wrong.
+inline std::string conc_build_tree(const int32_t *parent, int64_t n, int64_t T, ConcTree &t)
+{
+    std::vector<int32_t> par;
+    std::vector<std::vector<int32_t>> nch;
+    const std::string err = conc_prepare_tree(parent, n, T, par, nch);
+    if (!err.empty()) return err;
+    const int32_t N = (int32_t)par.size();
     t.T = (int32_t)T; t.N = N; t.W = (int32_t)((T + 63) / 64);
     t.dep.assign(N, 0);
     std::vector<int32_t> pre{(int32_t)T}, stack{(int32_t)T};   // preorder: the tips of a subtree are contiguous

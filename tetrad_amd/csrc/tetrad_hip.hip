@@ -32,6 +32,7 @@
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
 //   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
+//   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
 //   species.hpp   tq_species_table_kernel + tq_species_mfma_kernel / tq_species_pool_kernel: pooled count matrices of
 //                 species quartets (species mode; MFMA form, VALU form)
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
@@ -78,6 +79,7 @@ namespace {
 #include "concordance.hpp"
 #include "species.hpp"
 #include "supertree.hpp"
+#include "consensus.hpp"
 
 }  // namespace
 
@@ -162,6 +164,8 @@ struct tq_ctx {
     int share_c = 0;                // 1: scan kernel variant that also shares row c inside a workgroup (scan.hpp: SHC;
                                     // measured slower everywhere -- the kernel is LDS/VALU-bound, not byte-bound -- kept as an A/B option)
     int svd_wpc = 0;                // blocks per CU of the bidiag / bdsqr grids (0 = one pass per block)
+    int cons_hash_bits = 64;        // consensus: the table key is the 64-bit mask hash cut to this many bits (results never depend on it)
+    int64_t cons_scratch_bytes = int64_t(256) << 20;   // consensus: device + page-locked bytes of one chunk of trees
     int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
     const uint32_t *scanned_q = nullptr;
@@ -1446,6 +1450,159 @@ int conc_wait(tq_conc *acc)
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
+// Consensus accumulator (consensus.hpp).  Host back end: one exact map mask -> count.  Device back end: the hash table
+// on the device plus the same map for the splits that lost a hash collision; `cons_table` merges both by mask.
+// ---------------------------------------------------------------------------------------------
+struct tq_cons {
+    tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
+    int32_t T = 0, W = 0, G = 1;
+    uint64_t tail = 0;
+    int64_t max_splits = 0, ntrees = 0;
+    ConsMap host;                   // host adds; with a context the unresolved splits of the device adds
+    bool overflow = false;          // more distinct splits than max_splits were offered: unusable until a reset
+    bool table_ok = false;          // tmasks / tcounts hold the canonical table of everything added
+    std::vector<uint64_t> tmasks;
+    std::vector<int64_t> tcounts;
+    // device back end
+    int hash_bits = 64;
+    int64_t chunk_trees = 0, slots = 0, gather_cap = 0;
+    int32_t *p_trees = nullptr, *d_trees = nullptr, *d_slot_idx = nullptr;
+    uint64_t *d_masks = nullptr, *d_keys = nullptr, *d_rep = nullptr, *d_gather = nullptr, *p_gather = nullptr;
+    unsigned long long *d_slot_key = nullptr, *d_count = nullptr;
+    unsigned int *d_ctr = nullptr, *p_ctr = nullptr;
+    uint32_t *d_unres = nullptr;
+    hipEvent_t ev = nullptr;        // recorded behind the last chunk
+    bool pending = false;
+    hipStream_t last = nullptr;
+    int64_t dev_entries = 0;        // entries of the device table after the last finished chunk
+    int64_t chunks = 0, unresolved = 0;
+};
+
+namespace {
+
+void cons_free_dev(tq_cons *a)
+{
+    void *dev[] = {a->d_trees, a->d_slot_idx, a->d_masks, a->d_keys, a->d_rep, a->d_gather, a->d_slot_key, a->d_count,
+                   a->d_ctr, a->d_unres};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    void *pin[] = {a->p_trees, a->p_gather, a->p_ctr};
+    for (void *p : pin)
+        if (p) (void)hipHostFree(p);
+    if (a->ev) (void)hipEventDestroy(a->ev);
+}
+
+int cons_overflow(tq_cons *a, const char *who)
+{
+    a->overflow = true;
+    return fail(a->ctx, TQ_ERR_INVALID_ARG, "%s: more than max_splits = %lld distinct splits; reset the accumulator", who,
+                (long long)a->max_splits);
+}
+
+ConsArgs cons_args(const tq_cons *a, int64_t ntrees)
+{
+    ConsArgs p{};
+    p.trees = a->d_trees; p.masks = a->d_masks; p.keys = a->d_keys;
+    p.items = ntrees * (a->T - 2);
+    p.T = a->T; p.W = a->W; p.G = a->G; p.hash_bits = a->hash_bits; p.tail = a->tail;
+    p.slot_key = a->d_slot_key; p.slot_idx = a->d_slot_idx; p.rep = a->d_rep; p.count = a->d_count; p.ctr = a->d_ctr;
+    p.unres = a->d_unres; p.slot_mask = a->slots - 1; p.max_splits = a->max_splits;
+    return p;
+}
+
+// empty table (also the reset): keys CONS_EMPTY (all bits set), slot entries -1, counts and counters 0
+int cons_clear_dev(tq_cons *a)
+{
+    tq_ctx *ctx = a->ctx;
+    TQ_HIP(ctx, hipMemset(a->d_slot_key, 0xFF, (size_t)a->slots * 8));
+    TQ_HIP(ctx, hipMemset(a->d_slot_idx, 0xFF, (size_t)a->slots * 4));
+    TQ_HIP(ctx, hipMemset(a->d_count, 0, (size_t)a->max_splits * 8));
+    TQ_HIP(ctx, hipMemset(a->d_ctr, 0, CONS_CTR_WORDS * 4));
+    TQ_HIP(ctx, hipDeviceSynchronize());
+    return TQ_OK;
+}
+
+// Waits for the last chunk, reads its counters and counts its unresolved splits in the host map.
+int cons_drain(tq_cons *a)
+{
+    if (!a->pending) return TQ_OK;
+    tq_ctx *ctx = a->ctx;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    TQ_HIP(ctx, hipEventSynchronize(a->ev));
+    a->pending = false;
+    a->dev_entries = std::min<int64_t>((int64_t)a->p_ctr[CONS_CTR_CLAIMS], a->max_splits);
+    if (a->p_ctr[CONS_CTR_OVERFLOW]) return cons_overflow(a, "tq_cons");
+    const int64_t nun = (int64_t)a->p_ctr[CONS_CTR_UNRES];
+    std::vector<uint64_t> m((size_t)a->W);
+    for (int64_t first = 0; first < nun; first += a->gather_cap) {
+        const int64_t n = std::min<int64_t>(a->gather_cap, nun - first);
+        hipLaunchKernelGGL(tq_cons_gather_kernel, dim3((unsigned)((n * a->W + CONS_THREADS - 1) / CONS_THREADS)),
+                           dim3(CONS_THREADS), 0, a->last, (const uint32_t *)a->d_unres, first, n,
+                           (const uint64_t *)a->d_masks, a->W, a->d_gather);
+        TQ_HIP(ctx, hipGetLastError());
+        TQ_HIP(ctx, hipMemcpyAsync(a->p_gather, a->d_gather, (size_t)n * a->W * 8, hipMemcpyDeviceToHost, a->last));
+        TQ_HIP(ctx, hipStreamSynchronize(a->last));
+        for (int64_t e = 0; e < n; ++e) {
+            m.assign(a->p_gather + e * a->W, a->p_gather + (e + 1) * a->W);
+            ++a->host[m];
+        }
+    }
+    a->unresolved += nun;
+    if (a->dev_entries + (int64_t)a->host.size() > a->max_splits) return cons_overflow(a, "tq_cons");
+    return TQ_OK;
+}
+
+// One chunk of prepared records (already in the page-locked buffer) through the three kernels on `st`.
+int cons_launch(tq_cons *a, int64_t ntrees, hipStream_t st)
+{
+    tq_ctx *ctx = a->ctx;
+    const ConsArgs p = cons_args(a, ntrees);
+    TQ_HIP(ctx, hipMemcpyAsync(a->d_trees, a->p_trees, (size_t)ntrees * cons_stride(a->T) * 4, hipMemcpyHostToDevice, st));
+    TQ_HIP(ctx, hipMemsetAsync(a->d_ctr + CONS_CTR_UNRES, 0, 4, st));
+    const unsigned blocks = (unsigned)((p.items * a->G + CONS_THREADS - 1) / CONS_THREADS);
+    hipLaunchKernelGGL(tq_cons_mask_kernel, dim3((unsigned)ntrees), dim3(CONS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(tq_cons_insert_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(tq_cons_count_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_cons_add: launch failed: %s", hipGetErrorString(e));
+    TQ_HIP(ctx, hipMemcpyAsync(a->p_ctr, a->d_ctr, CONS_CTR_WORDS * 4, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, hipEventRecord(a->ev, st));
+    a->pending = true;
+    a->last = st;
+    ++a->chunks;
+    return TQ_OK;
+}
+
+// The canonical table of everything added (cached until the next add / reset).
+int cons_table(tq_cons *a, const char *who)
+{
+    if (a->overflow) return cons_overflow(a, who);
+    if (a->ctx)
+        if (int rc = cons_drain(a)) return rc;
+    if (a->table_ok) return TQ_OK;
+    if (!a->ctx || a->dev_entries == 0) {
+        cons_sorted_table(a->host, a->W, a->tmasks, a->tcounts);
+    } else {
+        const int64_t n = a->dev_entries;
+        std::vector<uint64_t> rep((size_t)n * a->W), cnt((size_t)n);
+        TQ_HIP(a->ctx, hipSetDevice(a->ctx->device));
+        TQ_HIP(a->ctx, hipMemcpy(rep.data(), a->d_rep, rep.size() * 8, hipMemcpyDeviceToHost));
+        TQ_HIP(a->ctx, hipMemcpy(cnt.data(), a->d_count, cnt.size() * 8, hipMemcpyDeviceToHost));
+        ConsMap all = a->host;
+        std::vector<uint64_t> m((size_t)a->W);
+        for (int64_t e = 0; e < n; ++e) {
+            m.assign(rep.begin() + e * a->W, rep.begin() + (e + 1) * a->W);
+            all[m] += (int64_t)cnt[e];
+        }
+        cons_sorted_table(all, a->W, a->tmasks, a->tcounts);
+    }
+    a->table_ok = true;
+    return TQ_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
 // Exact supertree accumulator (supertree.hpp).  Host adds keep the weighted splits in host vectors; device adds append
 // them to the root store on the device.  A build never modifies either, so it may be repeated with any seed.
 // ---------------------------------------------------------------------------------------------
@@ -2240,6 +2397,16 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
     }
     if (!strcmp(name, "share_c")) {
         ctx->share_c = value != 0;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "cons_hash_bits")) {              // read by tq_cons_create / tq_cons_reset
+        if (value < 0 || value > 64) return fail(ctx, TQ_ERR_INVALID_ARG, "cons_hash_bits must be 1..64 (0 = default 64)");
+        ctx->cons_hash_bits = value ? (int)value : 64;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "cons_scratch_bytes")) {          // read by tq_cons_create
+        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "cons_scratch_bytes must be >= 0 (0 = default 256 MiB)");
+        ctx->cons_scratch_bytes = value ? value : int64_t(256) << 20;
         return TQ_OK;
     }
     if (!strcmp(name, "stree_lds")) {
@@ -3172,6 +3339,241 @@ int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out)
             o[0] = (double)s.nodes; o[1] = (double)s.live; o[2] = (double)s.cells;
             o[3] = s.graph_ms; o[4] = s.search_ms; o[5] = s.part_ms;
         }
+    return TQ_OK;
+}
+
+int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: out is NULL");
+    *out = nullptr;
+    if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: T must be 4..%d", CONS_T_MAX);
+    if (max_splits < 1 || max_splits > (int64_t(1) << 26))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: max_splits must be 1..2^26");
+    tq_cons *a = new (std::nothrow) tq_cons();
+    if (!a) return fail(ctx, TQ_ERR_OOM, "tq_cons_create: out of host memory");
+    a->ctx = ctx;
+    a->T = (int32_t)T;
+    a->W = (int32_t)((T + 63) / 64);
+    a->tail = (T & 63) ? (uint64_t(1) << (T & 63)) - 1 : ~uint64_t(0);
+    a->max_splits = max_splits;
+    while (a->G < a->W) a->G *= 2;
+    if (ctx) {
+        const int64_t W = a->W, nodes = T - 2, stride = cons_stride(T);
+        a->hash_bits = ctx->cons_hash_bits;
+        const int64_t per_tree = nodes * W * 8 + nodes * 8 + nodes * 4 + stride * 4;       // masks, keys, unresolved, record
+        a->chunk_trees = std::max<int64_t>(1, std::min<int64_t>(CONS_CHUNK_MAX, ctx->cons_scratch_bytes / per_tree));
+        a->slots = 64;
+        while (a->slots < 2 * max_splits) a->slots *= 2;
+        a->gather_cap = std::max<int64_t>(1, CONS_GATHER_BYTES / (W * 8));
+        const int64_t C = a->chunk_trees;
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_trees, (size_t)C * stride * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_masks, (size_t)C * nodes * W * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_keys, (size_t)C * nodes * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_unres, (size_t)C * nodes * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_slot_key, (size_t)a->slots * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_slot_idx, (size_t)a->slots * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_rep, (size_t)max_splits * W * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_count, (size_t)max_splits * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_ctr, CONS_CTR_WORDS * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&a->d_gather, (size_t)a->gather_cap * W * 8);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_trees, (size_t)C * stride * 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_gather, (size_t)a->gather_cap * W * 8, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_ctr, CONS_CTR_WORDS * 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            cons_free_dev(a);
+            delete a;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_cons_create: %s", hipGetErrorString(e));
+        }
+        if (int rc = cons_clear_dev(a)) {
+            cons_free_dev(a);
+            delete a;
+            return rc;
+        }
+    }
+    *out = a;
+    return TQ_OK;
+}
+
+void tq_cons_destroy(tq_cons *acc)
+{
+    if (!acc) return;
+    if (acc->ctx) {
+        (void)hipSetDevice(acc->ctx->device);
+        if (acc->pending) (void)hipEventSynchronize(acc->ev);
+        cons_free_dev(acc);
+    }
+    delete acc;
+}
+
+int tq_cons_reset(tq_cons *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (acc->ctx) {
+        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+        if (acc->pending) TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
+        acc->pending = false;
+        if (int rc = cons_clear_dev(acc)) return rc;
+        acc->hash_bits = acc->ctx->cons_hash_bits;
+    }
+    acc->host.clear();
+    acc->ntrees = 0;
+    acc->dev_entries = 0;
+    acc->chunks = 0;
+    acc->unresolved = 0;
+    acc->overflow = false;
+    acc->table_ok = false;
+    return TQ_OK;
+}
+
+int tq_cons_add(tq_cons *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_add: NULL pointer or negative size");
+    if (acc->overflow) return cons_overflow(acc, "tq_cons_add");
+    if (R == 0) return TQ_OK;
+    try {
+        const int64_t S = cons_stride(acc->T);
+        std::vector<int32_t> recs((size_t)R * S);       // every tree is validated before the first one is counted
+        for (int64_t r = 0; r < R; ++r) {
+            if (n_nodes[r] > stride)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_add: tree %lld: n_nodes exceeds the stride", (long long)r);
+            const std::string err = cons_prepare(parents + r * stride, n_nodes[r], acc->T, &recs[(size_t)r * S]);
+            if (!err.empty())
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_add: tree %lld: %s", (long long)r, err.c_str());
+        }
+        acc->table_ok = false;
+        acc->ntrees += R;
+        if (!ctx) {
+            std::vector<uint64_t> tmp, sides, m((size_t)acc->W);
+            for (int64_t r = 0; r < R; ++r) {
+                sides.clear();
+                cons_host_splits(&recs[(size_t)r * S], acc->T, acc->W, tmp, sides);
+                for (size_t e = 0; e < sides.size(); e += acc->W) {
+                    m.assign(sides.begin() + e, sides.begin() + e + acc->W);
+                    auto it = acc->host.find(m);
+                    if (it != acc->host.end()) { ++it->second; continue; }
+                    if ((int64_t)acc->host.size() >= acc->max_splits) return cons_overflow(acc, "tq_cons_add");
+                    acc->host.emplace(m, 1);
+                }
+            }
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, hipSetDevice(ctx->device));
+        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk_trees) {
+            const int64_t n = std::min<int64_t>(acc->chunk_trees, R - r0);
+            if (int rc = cons_drain(acc)) return rc;        // the staging buffer and the mask scratch are free again
+            memcpy(acc->p_trees, &recs[(size_t)r0 * S], (size_t)n * S * 4);
+            if (int rc = cons_launch(acc, n, (hipStream_t)stream)) return rc;
+        }
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_cons_add: out of host memory");
+    }
+}
+
+int tq_cons_shape(tq_cons *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->T;
+    if (W) *W = acc->W;
+    if (ntrees) *ntrees = acc->ntrees;
+    if (nsplits) {
+        try {
+            if (int rc = cons_table(acc, "tq_cons_shape")) return rc;
+        } catch (const std::bad_alloc &) {
+            return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_shape: out of host memory");
+        }
+        *nsplits = (int64_t)acc->tcounts.size();
+    }
+    return TQ_OK;
+}
+
+int tq_cons_read(tq_cons *acc, uint64_t *masks, int64_t *counts)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    try {
+        if (int rc = cons_table(acc, "tq_cons_read")) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_read: out of host memory");
+    }
+    if (masks && !acc->tmasks.empty()) memcpy(masks, acc->tmasks.data(), acc->tmasks.size() * 8);
+    if (counts && !acc->tcounts.empty()) memcpy(counts, acc->tcounts.data(), acc->tcounts.size() * 8);
+    return TQ_OK;
+}
+
+int tq_cons_tree(tq_cons *acc, int64_t min_count, char *out, int64_t cap, int64_t *written)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (cap < 0 || !written || (cap > 0 && !out))
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: NULL pointer or negative cap");
+    *written = 0;
+    if (min_count < 1) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: min_count must be at least 1");
+    try {
+        if (int rc = cons_table(acc, "tq_cons_tree")) return rc;
+        const std::string nwk = cons_newick(acc->tmasks, acc->tcounts, acc->T, acc->W, acc->ntrees, min_count);
+        *written = (int64_t)nwk.size();
+        if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
+        memcpy(out, nwk.data(), nwk.size());
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_tree: out of host memory");
+    }
+}
+
+int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_t *counts_out, uint64_t *masks_out,
+                    int64_t *n_edges)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (!parent || !n_edges) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: NULL pointer");
+    *n_edges = 0;
+    try {
+        std::vector<int32_t> rec((size_t)cons_stride(acc->T));
+        const std::string err = cons_prepare(parent, n_nodes, acc->T, rec.data());
+        if (!err.empty()) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: %s", err.c_str());
+        if (int rc = cons_table(acc, "tq_cons_support")) return rc;
+        const int32_t W = acc->W;
+        std::vector<uint64_t> tmp, sides;
+        cons_host_splits(rec.data(), acc->T, W, tmp, sides);
+        const int64_t E = (int64_t)(sides.size() / W);
+        std::vector<int64_t> order(E);
+        for (int64_t e = 0; e < E; ++e) order[e] = e;
+        std::sort(order.begin(), order.end(),
+                  [&](int64_t x, int64_t y) { return cons_mask_less(&sides[x * W], &sides[y * W], W); });
+        ConsMap seen;                               // the table by mask
+        std::vector<uint64_t> m((size_t)W);
+        for (size_t i = 0; i < acc->tcounts.size(); ++i) {
+            m.assign(acc->tmasks.begin() + i * W, acc->tmasks.begin() + (i + 1) * W);
+            seen.emplace(m, acc->tcounts[i]);
+        }
+        for (int64_t e = 0; e < E; ++e) {
+            const uint64_t *src = &sides[order[e] * W];
+            m.assign(src, src + W);
+            const auto it = seen.find(m);
+            if (counts_out) counts_out[e] = it == seen.end() ? 0 : it->second;
+            if (masks_out) memcpy(masks_out + e * W, src, (size_t)W * 8);
+        }
+        *n_edges = E;
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_support: out of host memory");
+    }
+}
+
+int tq_cons_stats(tq_cons *acc, int64_t *out)
+{
+    if (!acc || !out) return TQ_ERR_INVALID_ARG;
+    if (acc->ctx && !acc->overflow)
+        if (int rc = cons_drain(acc)) return rc;
+    out[0] = acc->chunk_trees;
+    out[1] = acc->chunks;
+    out[2] = acc->dev_entries;
+    out[3] = (int64_t)acc->host.size();
+    out[4] = acc->unresolved;
+    out[5] = acc->hash_bits;
     return TQ_OK;
 }
 

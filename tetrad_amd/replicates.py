@@ -230,7 +230,7 @@ class ReplicateRunner:
 def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, nboots: int, *,
                     subsample_snps: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
                     rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
-                    concordance=None, supertree: str = "host") -> list:
+                    concordance=None, supertree: str = "host", consensus=None) -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
@@ -239,7 +239,18 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
     `concordance` (a `concordance.Concordance` made with `engine`) receives every replicate's rows on the device.
     `supertree="device"`: the exact supertree (`qmc.Supertree`) instead -- no row leaves the
     device; each replicate's rows are added to one of a small ring of accumulators on the loop's stream and a worker
-    thread builds the tree on a stream of its own, beside the resolve kernels of the next replicates.  One rank only."""
+    thread builds the tree on a stream of its own, beside the resolve kernels of the next replicates.  One rank only.
+    `consensus` (a `consensus.Consensus`) receives the replicate trees in replicate order once they are all in
+    (`consensus.tree()` is then the majority-rule tree with bootstrap supports)."""
+    trees = _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
+                             rng, sampler, group, workers, concordance, supertree)
+    if consensus is not None and trees:
+        consensus.add_newick(trees)
+    return trees
+
+
+def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed, rng,
+                     sampler, group, workers, concordance, supertree) -> list:
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
     if supertree not in ("host", "device"):
