@@ -221,7 +221,8 @@ int tq_timing_read_kernels(tq_ctx *ctx, double *ms, int n_ms, int64_t *calls);
  * are equal are counted too -- what the reference's count kernels do when their caller's mask leaves such a site open,
  * resolve_quartets.py:59-64; one-wave kernel), bdsqr_maxit (QR sweeps per singular value before TQ_FLAG_NO_CONVERGENCE,
  * default 60), bdsqr_stats (1: count rotation steps / issued lane-slots, read with tq_debug_fetch which = 3), phases
- * (timing diagnostics), species_method (-1 auto, 0 VALU, 1 MFMA form of the species-mode pooled counts).  scan_method 2..5 and phases 1 / 2 are timing diagnostics whose rows are wrong: every row of a
+ * (timing diagnostics), species_method (-1 auto, 0 VALU, 1 MFMA form of the species-mode pooled counts), species_alleles
+ * (0 / 1: species mode reads both alleles of the IUPAC source, see the species section below).  scan_method 2..5 and phases 1 / 2 are timing diagnostics whose rows are wrong: every row of a
  * call made under them carries TQ_FLAG_INVALID_DIAGNOSTIC and a call without a flags array fails.  scan_method 6 = the
  * bank-private counter kernel (scan_pb.hpp; an A/B form, slower).  batch is clamped to 2^31 - 1.
  * scan_dp (1, default: full-mode batches -- subsample = 0 -- of at least dp_min_quartets go to the joint-histogram scan,
@@ -470,7 +471,24 @@ int tq_cons_stats(tq_cons *acc, int64_t *out);
  *                   TQ_FLAG_BAD_INDEX (zero data).
  *   tq_resolve_species_debug  also the pooled cmats u32[Q,3,16,16], svds f64[Q,3,16], ranks i32[Q,3] (any may be NULL).
  * Species calls fail with TQ_ERR_NO_DATA without data or without a map, TQ_ERR_INVALID_ARG when the map's T differs from
- * the resident replicate's.                                                                                          */
+ * the resident replicate's.
+ *
+ * Both alleles (option "species_alleles" = 1; 0, the default, is everything above): every sample
+ * of the SOURCE matrix (tq_set_source: seqarr u8[T,S0]) is two haplotype lineages, and the per-species base counts are
+ * built straight from it through the site map of the resident replicate instead of from the coin-resolved rows:
+ *   a cell A / C / G / T (or an already recoded 0..3) adds 2 to its base; a two-base code adds 1 to each of its bases
+ *   (R = G,A  K = G,T  S = G,C  Y = T,C  W = T,A  M = C,A: the table tq_bootstrap resolves by coin); every other byte
+ *   (N, gap, three-base codes) adds nothing.  The pooled matrix, with the same formula as above, is then the sum over
+ *   haplotype quartets = 16 x the expectation of the coin-resolved lineage-quartet matrix; seed_ambig has no influence.
+ *   Which sites: those of the resident replicate, which must have been built by tq_bootstrap(_async) from the current
+ *   source (the original matrix is the replicate of lidxs = 0..nloci-1).  Resident data from tq_set_data, or a
+ *   tq_set_source newer than the replicate, make every species call fail with TQ_ERR_NO_DATA, as does no source at all.
+ *   Sizes count in lineages = 2 x samples wherever a size rule applies: the call is refused when S x (product of the
+ *   four largest 2n) >= 2^32; a species holds at most 127 samples (2n <= 255, one byte per base); the MFMA form
+ *   (automatic choice and species_method 1) takes 2n <= 11, i.e. at most 5 samples per species; a row's own product
+ *   is taken over its 2n (host call: refused, device call: zero counts and TQ_FLAG_ZERO_DATA).  All of it is checked
+ *   by the species call, since the option can be set after the map.  Setting the option to another value makes the
+ *   next species call rebuild the counts on its stream; any value other than 0 / 1 is refused.                        */
 int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K);
 int tq_resolve_species(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor,
                        uint8_t *flags);

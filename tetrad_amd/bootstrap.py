@@ -44,3 +44,10 @@ def resample_tmp_database(engine: QuartetEngine, rng) -> int:
     (use `engine.get_data()` to inspect it or to write it to a database)."""
     rng = np.random.default_rng(rng)                               # :105 (pass-through for a Generator)
     return engine.bootstrap(*draw_replicate(engine.nloci, rng))
+
+
+def identity_replicate(engine: QuartetEngine) -> int:
+    """The original matrix as a device-built replicate: every locus once, in order (`lidxs = 0..nloci-1`).  The sites
+    of a locus are still shuffled inside it, which full-mode counts -- species mode included -- do not depend on.
+    What `species_alleles` needs to read the source matrix itself."""
+    return engine.bootstrap(np.arange(engine.nloci), 0, 0)

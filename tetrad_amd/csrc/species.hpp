@@ -34,6 +34,52 @@ tq_species_table_kernel(const uint8_t *__restrict__ nib5, int64_t Sp, int64_t S,
     for (int x = 0; x < 4; ++x) tab8[(k * 4 + x) * Sp + s] = (uint8_t)((c >> (8 * x)) & 0xFFu);
 }
 
+// Allele mode (option species_alleles): the same table, both layouts, built from the IUPAC source
+// matrix seqarr u8[T][S0] instead of the resident rows, with every sample as two haplotype lineages.  A cell adds 2 to
+// its base when it is A / C / G / T (or an already recoded 0..3), 1 to each of its two bases when it is a two-base code
+// (the table of tq_boot_build_kernel: R = G/A, K = G/T, S = G/C, Y = T/C, W = T/A, M = C/A) and nothing otherwise (N,
+// gap, three-base codes).  No coin is drawn: the pooled matrix of these counts is the sum over haplotype quartets.
+// {n_A, n_C, n_G, n_T} packed as in tab; the host admits at most 127 samples per species, so a byte holds 2n.
+__device__ __forceinline__ uint32_t species_allele_counts(uint8_t v)
+{
+    constexpr uint32_t A = 1u, C = 1u << 8, G = 1u << 16, T = 1u << 24;
+    switch (v) {
+    case 0: case 65: return 2 * A;
+    case 1: case 67: return 2 * C;
+    case 2: case 71: return 2 * G;
+    case 3: case 84: return 2 * T;
+    case 82: return G + A;
+    case 75: return G + T;
+    case 83: return G + C;
+    case 89: return T + C;
+    case 87: return T + A;
+    case 77: return C + A;
+    default: return 0;
+    }
+}
+
+// One thread per (species, padded site), as tq_species_table_kernel.  src_col[s] = the source column of replicate site
+// s, the map tq_boot_perm_kernel left for the resident replicate (s < S <= its capacity, src_col[s] < S0).  Plain
+// vector stores; no atomics, no LDS.
+__global__ void __launch_bounds__(256)
+tq_species_allele_table_kernel(const uint8_t *__restrict__ seqarr, int64_t S0, const uint32_t *__restrict__ src_col,
+                               int64_t S, int64_t Sp, const int32_t *__restrict__ members,
+                               const int32_t *__restrict__ offsets, int32_t K, uint32_t *__restrict__ tab,
+                               uint8_t *__restrict__ tab8)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)K * Sp) return;
+    const int64_t k = gid / Sp, s = gid - k * Sp;
+    uint32_t c = 0;
+    if (s < S) {
+        const uint8_t *col = seqarr + src_col[s];
+        for (int32_t m = offsets[k]; m < offsets[k + 1]; ++m) c += species_allele_counts(col[(int64_t)members[m] * S0]);
+    }
+    tab[gid] = c;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) tab8[(k * 4 + x) * Sp + s] = (uint8_t)((c >> (8 * x)) & 0xFFu);
+}
+
 // The row's own range rule: S x n_A n_B n_C n_D < 2^32.  The host refuses a call whose four largest species break it;
 // a row that repeats a species can still break it, and such a row gets zero counts (TQ_FLAG_ZERO_DATA) instead of
 // counts wrapped modulo 2^32.

@@ -33,8 +33,9 @@
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
 //   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
-//   species.hpp   tq_species_table_kernel + tq_species_mfma_kernel / tq_species_pool_kernel: pooled count matrices of
-//                 species quartets (species mode; MFMA form, VALU form)
+//   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
+//                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
+//                 count matrices of species quartets (species mode; MFMA form, VALU form)
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -177,13 +178,21 @@ struct tq_ctx {
     std::vector<int32_t> sp_size;   // lineages per species
     uint64_t sp_bound = 0;          // product of the four largest species sizes (range rule: S * sp_bound < 2^32)
     int32_t sp_max = 0;             // largest species size
-    int32_t *d_sp_members = nullptr;    // offsets [K+1], then the member samples grouped by species
+    int32_t *d_sp_members = nullptr;    // offsets [K+1], then the member samples grouped by species [T], then 2 x offsets [K+1]
     uint32_t *d_sp_tab = nullptr;   // u32 [K][Sp]: {n_A, n_C, n_G, n_T} per species and site, then u8 [K][4][Sp] (MFMA form)
     int64_t sp_tab_cap = 0;         // (species, site) entries allocated (8 bytes each)
     int species_method = -1;        // -1: MFMA form when every species holds <= SPECIES_MFMA_MAX lineages, else VALU;
                                     // 0: VALU form (tq_species_pool_kernel); 1: MFMA form (tq_species_mfma_kernel)
     uint64_t data_gen = 0;          // bumped by tq_set_data / tq_bootstrap(_async)
     uint64_t sp_tab_gen = ~0ull;    // data_gen the species table was built from (~0: none)
+    // allele mode (option species_alleles): the table is built from the IUPAC source through the
+    // resident replicate's site map (src_col in d_boot), every sample two lineages.  The map is the resident replicate's
+    // exactly while boot_gen == data_gen (tq_bootstrap_async built what is resident) and boot_src_gen == src_gen (from
+    // the source that is still the current one).
+    int species_alleles = 0;
+    uint64_t src_gen = 0;           // bumped by tq_set_source
+    uint64_t boot_gen = ~0ull;      // data_gen of the last replicate tq_bootstrap_async built (~0: none)
+    uint64_t boot_src_gen = ~0ull;  // src_gen it was built from
     // packed layout set (pack.hpp): a second copy of rows / nib / planes / planes3 + runbeg with whole loci per lane word,
     // read by the subsample-mode scans while it is current (pk_gen == data_gen).  tq_set_data builds it under site_pack,
     // tq_bootstrap_async under boot_pack (a replicate built without it leaves the set stale).  Everything else reads the
@@ -930,21 +939,39 @@ int stage_scan(tq_ctx *ctx, const uint32_t *dq, int64_t n, int subsample, bool i
     return TQ_OK;
 }
 
+// lineages per sample of the species map: 2 in allele mode (one per allele of a diploid genotype)
+inline int species_lineages(const tq_ctx *ctx) { return ctx->species_alleles ? 2 : 1; }
+
 // Species mode: the map is set, matches the resident replicate and the pooled counts fit u32
+// (allele mode: sizes in lineages = 2 x samples, and the resident data must be a device-built replicate of the current
+// source -- the option can be set after the map, so everything is checked here, at call time)
 int species_ready(tq_ctx *ctx, const char *who)
 {
+    if (ctx->species_alleles) {
+        if (!ctx->d_seqarr)
+            return fail(ctx, TQ_ERR_NO_DATA, "%s: species_alleles needs the IUPAC source (call tq_set_source, then tq_bootstrap)", who);
+        if (!ctx->have_data || ctx->boot_gen != ctx->data_gen || ctx->boot_src_gen != ctx->src_gen)
+            return fail(ctx, TQ_ERR_NO_DATA, "%s: species_alleles needs the resident data to be a replicate built by "
+                        "tq_bootstrap from the current source (tq_set_data and a new tq_set_source do not give one)", who);
+    }
     if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "%s: tq_set_data has not been called", who);
     if (!ctx->sp_K) return fail(ctx, TQ_ERR_NO_DATA, "%s: no species map (call tq_set_species first)", who);
     if (ctx->sp_T != ctx->T)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: the species map covers T=%lld samples, the resident replicate has T=%lld",
                     who, (long long)ctx->sp_T, (long long)ctx->T);
-    if ((unsigned __int128)ctx->S * ctx->sp_bound >= ((unsigned __int128)1 << 32))
+    const int lin = species_lineages(ctx);
+    if (lin == 2 && ctx->sp_max > 127)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: species_alleles takes species of at most 127 samples (254 lineages, one "
+                    "byte per base), the map has one of %d", who, (int)ctx->sp_max);
+    const uint64_t bound = ctx->sp_bound * (uint64_t)(lin * lin * lin * lin);      // <= 255^4 x 16 < 2^36
+    if ((unsigned __int128)ctx->S * bound >= ((unsigned __int128)1 << 32))
         return fail(ctx, TQ_ERR_INVALID_ARG,
-                    "%s: pooled counts may exceed u32: S=%lld x product of the four largest species sizes %llu >= 2^32",
-                    who, (long long)ctx->S, (unsigned long long)ctx->sp_bound);
-    if (ctx->species_method == 1 && ctx->sp_max > SPECIES_MFMA_MAX)
+                    "%s: pooled counts may exceed u32: S=%lld x product of the four largest species sizes %llu >= 2^32%s",
+                    who, (long long)ctx->S, (unsigned long long)bound, lin == 2 ? " (sizes in lineages: 2 per sample)" : "");
+    if (ctx->species_method == 1 && lin * ctx->sp_max > SPECIES_MFMA_MAX)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: species_method 1 (MFMA, i8 operands) takes species of at most %d lineages, "
-                    "the map has one of %d", who, SPECIES_MFMA_MAX, (int)ctx->sp_max);
+                    "the map has one of %d%s", who, SPECIES_MFMA_MAX, lin * (int)ctx->sp_max,
+                    lin == 2 ? " (species_alleles: 2 per sample, i.e. at most 5 samples)" : "");
     return TQ_OK;
 }
 
@@ -968,16 +995,25 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
             TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sp_tab, (size_t)entries * 8));
             ctx->sp_tab_cap = entries;
         }
-        hipLaunchKernelGGL(tq_species_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
-                           (const uint8_t *)ctx->d_nib5, ctx->Sp, ctx->S, (const int32_t *)(ctx->d_sp_members + ctx->sp_K + 1),
-                           (const int32_t *)ctx->d_sp_members, (int32_t)ctx->sp_K, ctx->d_sp_tab,
-                           (uint8_t *)(ctx->d_sp_tab + entries));
+        const int32_t *members = ctx->d_sp_members + ctx->sp_K + 1;
+        if (ctx->species_alleles)       // species_ready: d_boot holds the site map of the resident replicate
+            hipLaunchKernelGGL(tq_species_allele_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
+                               (const uint8_t *)ctx->d_seqarr, ctx->src_S0,
+                               (const uint32_t *)(ctx->d_boot + 2 * (ctx->nloci + 1)), ctx->S, ctx->Sp, members,
+                               (const int32_t *)ctx->d_sp_members, (int32_t)ctx->sp_K, ctx->d_sp_tab,
+                               (uint8_t *)(ctx->d_sp_tab + entries));
+        else
+            hipLaunchKernelGGL(tq_species_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
+                               (const uint8_t *)ctx->d_nib5, ctx->Sp, ctx->S, members, (const int32_t *)ctx->d_sp_members,
+                               (int32_t)ctx->sp_K, ctx->d_sp_tab, (uint8_t *)(ctx->d_sp_tab + entries));
         TQ_HIP(ctx, hipGetLastError());
         ctx->sp_tab_gen = ctx->data_gen;
     }
     if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
-    const bool mfma = ctx->species_method == 1 || (ctx->species_method < 0 && ctx->sp_max <= SPECIES_MFMA_MAX);
-    const int32_t *offsets = ctx->d_sp_members;
+    const int lin = species_lineages(ctx);
+    const bool mfma = ctx->species_method == 1 || (ctx->species_method < 0 && lin * ctx->sp_max <= SPECIES_MFMA_MAX);
+    // the pooled kernels read offsets for the per-row range rule only: in allele mode the copy whose differences are 2n
+    const int32_t *offsets = lin == 2 ? ctx->d_sp_members + ctx->sp_K + 1 + ctx->sp_T : ctx->d_sp_members;
     if (mfma)
         hipLaunchKernelGGL(tq_species_mfma_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
                            (const uint8_t *)(ctx->d_sp_tab + ctx->sp_K * ctx->Sp), ctx->Sp, ctx->S, dsq, n,
@@ -2203,9 +2239,13 @@ int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
             if (k >= 0 && ++size[(size_t)k] > 255)
                 return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: species %d has more than 255 lineages", k);
         }
-        // offsets [K+1] then the members grouped by species (ascending sample index inside a species)
-        members.assign((size_t)(K + 1 + T), 0);
-        for (int64_t k = 0; k < K; ++k) members[(size_t)k + 1] = members[(size_t)k] + size[(size_t)k];
+        // offsets [K+1], then the members grouped by species (ascending sample index inside a species), then the
+        // offsets in lineages of allele mode [K+1] (differences 2n: the per-row range rule of the pooled kernels)
+        members.assign((size_t)(K + 1 + T + K + 1), 0);
+        for (int64_t k = 0; k < K; ++k) {
+            members[(size_t)k + 1] = members[(size_t)k] + size[(size_t)k];
+            members[(size_t)(K + 1 + T + k + 1)] = 2 * members[(size_t)k + 1];
+        }
         std::vector<int32_t> fill(members.begin(), members.begin() + K);
         for (int64_t i = 0; i < T; ++i)
             if (species_of[i] >= 0) members[(size_t)(K + 1 + fill[(size_t)species_of[i]]++)] = (int32_t)i;
@@ -2259,14 +2299,15 @@ int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, 
     // ids on the host (the kernels re-check them and flag the row); a row that repeats a species can exceed the
     // call's range bound, so its own product is checked when the bound leaves room for that
     const uint32_t K = (uint32_t)ctx->sp_K;
-    const bool per_row = (unsigned __int128)ctx->S * ((uint64_t)ctx->sp_max * ctx->sp_max * ctx->sp_max * ctx->sp_max) >=
+    const uint64_t lin4 = ctx->species_alleles ? 16 : 1;      // lineages per sample, to the fourth
+    const bool per_row = (unsigned __int128)ctx->S * ((uint64_t)ctx->sp_max * ctx->sp_max * ctx->sp_max * ctx->sp_max * lin4) >=
                          ((unsigned __int128)1 << 32);
     for (int64_t i = 0; i < Q; ++i) {
         const uint32_t *q = squartets + 4 * i;
         if ((q[0] >= K) | (q[1] >= K) | (q[2] >= K) | (q[3] >= K))
             return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld has a species id >= K=%u", (long long)i, K);
         if (per_row) {
-            const uint64_t p = (uint64_t)ctx->sp_size[q[0]] * ctx->sp_size[q[1]] * ctx->sp_size[q[2]] * ctx->sp_size[q[3]];
+            const uint64_t p = (uint64_t)ctx->sp_size[q[0]] * ctx->sp_size[q[1]] * ctx->sp_size[q[2]] * ctx->sp_size[q[3]] * lin4;
             if ((unsigned __int128)ctx->S * p >= ((unsigned __int128)1 << 32))
                 return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld: S=%lld x its lineage product %llu >= 2^32",
                             (long long)i, (long long)ctx->S, (unsigned long long)p);
@@ -2477,6 +2518,13 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
         ctx->species_method = (int)value;
         return TQ_OK;
     }
+    if (!strcmp(name, "species_alleles")) {
+        if (value != 0 && value != 1)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "species_alleles must be 0 (one lineage per sample) or 1 (two: both alleles)");
+        if (ctx->species_alleles != (int)value) ctx->sp_tab_gen = ~0ull;      // the next species call rebuilds the table
+        ctx->species_alleles = (int)value;
+        return TQ_OK;
+    }
     if (!strcmp(name, "phases")) {
         if (value != 0 && value != 1 && value != 2 && value != 3)
             return fail(ctx, TQ_ERR_INVALID_ARG, "phases must be 1, 2 or 3");
@@ -2503,6 +2551,7 @@ int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, con
     }
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     free_source(ctx);
+    ctx->src_gen++;                     // a replicate of the earlier source is no replicate of this one
     TQ_HIP(ctx, hipMalloc((void **)&ctx->d_seqarr, (size_t)(T * S0)));
     TQ_HIP(ctx, hipMalloc((void **)&ctx->d_spans, (size_t)nloci * 16));
     TQ_HIP(ctx, hipMalloc((void **)&ctx->d_lidxs, (size_t)nloci * 8));
@@ -2689,6 +2738,8 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
     ctx->locus_runs_ok = true;          // locus ids are the ordinals 0..n-1, one run each
     ctx->scanned_Q = 0;
     ctx->data_gen++;                    // the species table is rebuilt by the next species call
+    ctx->boot_gen = ctx->data_gen;
+    ctx->boot_src_gen = ctx->src_gen;
     if (pSp) {
         ctx->pk_Sp = pSp;
         ctx->pk_W = pW;
