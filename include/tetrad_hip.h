@@ -384,8 +384,15 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
  *   tq_stree_level_stats  of the last build: *n_levels (at most 64 are kept), out f64[n_levels][6] = {open nodes, live
  *                    quartets, cells of one matrix, graph pass ms, host search ms, partition pass ms} (wall clock of the
  *                    calling thread, synchronisation included).
+ *   tq_stree_set_search  the rule of the cut search of the following builds: 0 (default) = the multi-start search on
+ *                    the cells as doubles, run on the host; 1 = "exact", the all-integer rule of DESIGN.md section 16,
+ *                    which device rows run in a kernel (only side bytes and a cut byte per node come back, still two
+ *                    synchronisations per level) and host rows on the host, with the same newick string from both.
+ *                    Anything else: TQ_ERR_INVALID_ARG, the rule stays.  May be called between builds.
  * Option "stree_lds" (tq_set_option): 1 (default) = the graph pass sums in private LDS counters where a level's cells fit
- * (at most 8128 per matrix), 0 = global integer atomics only.  Both are exact.                                        */
+ * (at most 8128 per matrix), 0 = global integer atomics only.  Both are exact.
+ * Option "stree_search_dev": 1 (default) = device rows run the rule "exact" in tq_stree_search_kernel, 0 = the matrices
+ * are copied out and the same rule runs on the host (A/B; the same string).                                            */
 typedef struct tq_stree tq_stree;
 int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int weights, int64_t min_snps, double min_ratio,
                     tq_ctx *ctx);
@@ -399,6 +406,16 @@ int tq_stree_graph(tq_stree *acc, uint64_t *G, uint64_t *B, int64_t *kept, int64
 int tq_stree_rows(tq_stree *acc, uint32_t *splits, uint64_t *k, int64_t *n);
 int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_t cap, int64_t *written, int64_t *levels);
 int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out);
+int tq_stree_set_search(tq_stree *acc, int search);
+
+/* Test hook: the exact cut search alone on a batch of nodes.  sizes i32[n_nodes] (4..65535 on the host, 4..1024 on the
+ * device), G and B the nodes' upper triangles one after the other (node of n taxa: n (n - 1) / 2 cells, cell (u < v) at
+ * u n - u (u + 1) / 2 + v - u - 1; 6 x the sum of a node's B cells / 2 must stay below 2^53), node_seeds u64[n_nodes].
+ * Out: side u8[sum of sizes] (zero for a node without a cut), cut u8[n_nodes], rounds i32[n_nodes] (may be NULL) = the
+ * Dinkelbach rounds run, 0 for n = 4 and for a node without B.  ctx NULL: the host execution; otherwise the batch is
+ * uploaded and tq_stree_search_kernel runs it in one launch.  No reference counterpart.                                */
+int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const uint64_t *G, const uint64_t *B,
+                    const uint64_t *node_seeds, uint8_t *side, uint8_t *cut, int32_t *rounds);
 
 /* Majority-rule consensus: how many trees of a set contain each split, counted exactly, the
  * consensus tree built from the counts, and the counts written onto the edges of a given tree (the computation behind

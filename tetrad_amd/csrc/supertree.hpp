@@ -8,13 +8,15 @@
 //   * For every open node of a level the graph G (good edges a-c, a-d, b-c, b-d) and B (bad edges a-b, c-d) are sums
 //     of k in u64 over the node's live quartets, upper triangle only: order-independent, so any launch shape, any row
 //     order and any split of the rows over several adds give the same cells.
-//   * The host searches each node's cut (qmc_search of qmc.hpp on cell / 10^5 as doubles, one generator per node keyed
-//     by (seed, level, index of the node in its level)).
+//   * Each node's cut is searched by one of two rules.  "f64" (default): the host runs qmc_search of qmc.hpp on cell /
+//     10^5 as doubles, one generator per node keyed by (seed, level, index of the node in its level).  "exact"
+//     (tq_stree_set_search): stree_search_exact, all-integer, which the device back end runs in
+//     tq_stree_search_kernel with the matrices where the graph pass left them.
 //   * One pass partitions the live quartets: four taxa on a side -> that child; three -> that child with the odd taxon
 //     replaced by the child's artificial taxon; 2 | 2 -> dropped.
 //   The level loop, the search, the forest and the newick writer are one piece of host code (`stree_build`) that talks
-//   to a back end with two operations, `graphs` and `partition`: StreeHostBackend on host arrays, StreeDevBackend on
-//   the device.  Both operations are exact, so the two give the same newick string.
+//   to a back end with three operations, `graphs`, `search` (rule "exact" only) and `partition`: StreeHostBackend on
+//   host arrays, StreeDevBackend on the device.  All three are exact, so the two give the same newick string.
 //
 // Device layout: a live quartet is {four node-local taxon indices u16 packed in a u64, k u64, node id u32}.  The rows
 // kept by the add kernel sit in the accumulator's root store (node 0 implied) and are never modified; the partition
@@ -293,6 +295,435 @@ __global__ __launch_bounds__(STREE_THREADS) void tq_stree_partition_kernel(Stree
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// the exact cut search: a second search rule beside qmc_search, on the integer cells alone.
+// One definition -- `stree_search_exact` on the host, `tq_stree_search_kernel` on the device -- whose every value is an
+// integer, so the two executions are equal bit for bit whatever the launch shape or the order of a reduction.
+//
+// Range: with S = sum of k < STREE_SUM_LIMIT (6 S < 2^53) a node's G cells sum to at most 4 S and its B cells to at most
+// 2 S, so p = good <= 4 S and q = bad <= 2 S.  A gain or an objective is a signed sum of terms q G[u][v] and p B[u][v]
+// whose absolute values total at most q 4 S + p 2 S <= 16 S^2 < 2^105 (twice that inside a gain update: < 2^106), and a
+// cross product good_X bad_Y is at most 8 S^2 < 2^104.  Signed 128-bit arithmetic never wraps.
+// ------------------------------------------------------------------------------------------------------------------
+typedef __int128 stree_i128;
+typedef unsigned __int128 stree_u128;
+
+constexpr int STREE_SEARCH_THREADS = 512;       // eight waves: the starts of a round are dealt over them
+constexpr int STREE_SEARCH_LDS_CELLS = 3072;    // a node of up to 78 taxa keeps its two triangles in LDS (48 KiB)
+constexpr int STREE_SEARCH_ROUNDS = 6;
+
+__host__ __device__ __forceinline__ uint64_t stree_mix(uint64_t z)         // QmcRng{s}.next() == stree_mix(s + gamma)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+constexpr uint64_t STREE_GAMMA = 0x9E3779B97F4A7C15ull;
+
+__host__ __device__ __forceinline__ uint64_t stree_node_seed(uint64_t seed, uint64_t level, uint64_t idx)
+{
+    return stree_mix((seed ^ (level * 0x9E3779B97F4A7C15ull) ^ (idx * 0xD1B54A32D192ED03ull)) + STREE_GAMMA);
+}
+
+// state of the generator of start s of round r; its draw v (the (v + 1)-th next()) is stree_start_bit's argument
+__host__ __device__ __forceinline__ uint64_t stree_start_seed(uint64_t node_seed, uint32_t round, uint32_t s)
+{
+    return stree_mix((node_seed ^ ((uint64_t)(32u * round + s + 1u) * 0xD6E8FEB86659FD93ull)) + STREE_GAMMA);
+}
+__host__ __device__ __forceinline__ uint32_t stree_start_bit(uint64_t state0, uint32_t v)
+{
+    return (uint32_t)(stree_mix(state0 + (uint64_t)(v + 1u) * STREE_GAMMA) & 1u);
+}
+
+// cut X = (gx, bx) beats cut Y: larger good / bad without a division, then larger good
+__host__ __device__ __forceinline__ bool stree_better(uint64_t gx, uint64_t bx, uint64_t gy, uint64_t by)
+{
+    const stree_u128 l = (stree_u128)gx * by, r = (stree_u128)gy * bx;
+    return l != r ? l > r : gx > gy;
+}
+__host__ __device__ __forceinline__ stree_i128 stree_edge(uint64_t p, uint64_t q, uint64_t g, uint64_t b)
+{
+    return (stree_i128)((stree_u128)q * g) - (stree_i128)((stree_u128)p * b);
+}
+__host__ __device__ __forceinline__ int stree_starts(int n) { return n <= 8 ? 24 : 12; }
+
+// n = 4: the three 2|2 splits {0, k} | rest, k = 1, 2, 3 in that order; the first best valid one
+__host__ __device__ __forceinline__ bool stree_search4(const uint64_t *G, const uint64_t *B, uint32_t &bits)
+{
+    bool have = false;
+    uint64_t bg = 0, bb = 0;
+    for (uint32_t k = 1; k < 4; ++k) {
+        const uint32_t sb = 0xEu & ~(1u << k);                 // bit v = side of v: 0 and k on side 0
+        uint64_t good = 0, bad = 0;
+        for (uint32_t u = 0; u < 4; ++u)
+            for (uint32_t v = u + 1; v < 4; ++v)
+                if (((sb >> u) ^ (sb >> v)) & 1u) {
+                    good += G[stree_tri(u, v, 4)];
+                    bad += B[stree_tri(u, v, 4)];
+                }
+        if (good > 0 && (!have || stree_better(good, bad, bg, bb))) {
+            have = true;
+            bg = good;
+            bb = bad;
+            bits = sb;
+        }
+    }
+    return have;
+}
+
+// the rule on the host.  G, B: the node's triangles, n >= 4; side u8[n]; rounds = Dinkelbach rounds run (0: n = 4 or no B)
+inline bool stree_search_exact(const uint64_t *G, const uint64_t *B, int n, uint64_t node_seed, uint8_t *side, int &rounds)
+{
+    rounds = 0;
+    const size_t tri = (size_t)n * (n - 1) / 2;
+    uint64_t bsum = 0;
+    for (size_t c = 0; c < tri; ++c) bsum |= B[c];
+    if (!bsum) return false;
+    if (n == 4) {
+        uint32_t bits = 0;
+        if (!stree_search4(G, B, bits)) return false;
+        for (int v = 0; v < 4; ++v) side[v] = (uint8_t)((bits >> v) & 1u);
+        return true;
+    }
+    std::vector<uint64_t> Gf((size_t)n * n, 0), Bf((size_t)n * n, 0);
+    {
+        size_t c = 0;
+        for (int u = 0; u < n; ++u)
+            for (int v = u + 1; v < n; ++v, ++c) {
+                Gf[(size_t)u * n + v] = Gf[(size_t)v * n + u] = G[c];
+                Bf[(size_t)u * n + v] = Bf[(size_t)v * n + u] = B[c];
+            }
+    }
+    std::vector<uint8_t> cur((size_t)n), inc((size_t)n), rbest((size_t)n);
+    std::vector<stree_i128> gain((size_t)n);
+    uint64_t p = 1, q = 1, ig = 0, ib = 0;
+    bool have = false;
+    const int starts = stree_starts(n);
+    for (int round = 0; round < STREE_SEARCH_ROUNDS; ++round) {
+        ++rounds;
+        bool rhave = false;
+        uint64_t rg = 0, rb = 0;
+        for (int s = 0; s <= starts; ++s) {
+            if (s == 0 && have) {
+                cur = inc;
+            } else {
+                const uint64_t st0 = stree_start_seed(node_seed, (uint32_t)round, (uint32_t)s);
+                int c1 = 0;
+                for (int v = 0; v < n; ++v) c1 += (cur[(size_t)v] = (uint8_t)stree_start_bit(st0, (uint32_t)v));
+                if (c1 < 2 || n - c1 < 2)
+                    for (int v = 0; v < n; ++v) cur[(size_t)v] = (uint8_t)(v & 1);
+            }
+            int cnt[2] = {0, 0};
+            for (int v = 0; v < n; ++v) cnt[cur[(size_t)v]]++;
+            for (int v = 0; v < n; ++v) {
+                stree_i128 g = 0;
+                const uint64_t *gr = &Gf[(size_t)v * n], *br = &Bf[(size_t)v * n];
+                for (int u = 0; u < n; ++u) {
+                    if (u == v) continue;
+                    const stree_i128 w = stree_edge(p, q, gr[u], br[u]);
+                    g += cur[(size_t)u] == cur[(size_t)v] ? w : -w;
+                }
+                gain[(size_t)v] = g;
+            }
+            for (int64_t pass = 0; pass < 50 * (int64_t)n; ++pass) {
+                int best = -1;
+                stree_i128 bg = 0;
+                for (int v = 0; v < n; ++v)
+                    if (gain[(size_t)v] > bg && cnt[cur[(size_t)v]] > 2) {
+                        bg = gain[(size_t)v];
+                        best = v;
+                    }
+                if (best < 0) break;
+                const int v = best;
+                cnt[cur[(size_t)v]]--;
+                cur[(size_t)v] ^= 1;
+                cnt[cur[(size_t)v]]++;
+                gain[(size_t)v] = -gain[(size_t)v];
+                const uint64_t *gr = &Gf[(size_t)v * n], *br = &Bf[(size_t)v * n];
+                for (int u = 0; u < n; ++u) {
+                    if (u == v) continue;
+                    const stree_i128 w2 = 2 * stree_edge(p, q, gr[u], br[u]);
+                    gain[(size_t)u] += cur[(size_t)u] == cur[(size_t)v] ? w2 : -w2;
+                }
+            }
+            uint64_t good = 0, bad = 0;
+            for (int u = 0; u < n; ++u)
+                for (int v = u + 1; v < n; ++v)
+                    if (cur[(size_t)u] != cur[(size_t)v]) {
+                        good += Gf[(size_t)u * n + v];
+                        bad += Bf[(size_t)u * n + v];
+                    }
+            if (!(good > 0 && cnt[0] >= 2 && cnt[1] >= 2)) continue;
+            if (!rhave || stree_better(good, bad, rg, rb)) {               // strictly: the lowest s keeps a tie
+                rhave = true;
+                rg = good;
+                rb = bad;
+                rbest = cur;
+            }
+        }
+        bool improved = false;
+        if (rhave && (!have || stree_better(rg, rb, ig, ib))) {
+            have = improved = true;
+            ig = rg;
+            ib = rb;
+            inc = rbest;
+        }
+        if (!have) return false;
+        if (!improved && round > 0) break;
+        if (ib == 0) break;
+        p = ig;
+        q = ib;
+    }
+    memcpy(side, inc.data(), (size_t)n);
+    return true;
+}
+
+struct StreeSearchArgs {
+    const StreeNode *nodes;
+    int32_t n_nodes;
+    int64_t cells;                      // of one matrix of this level
+    const unsigned long long *mat;      // [2][cells]: G then B, where the graph pass left them
+    const uint64_t *seeds;              // a node seed per node, or null: stree_node_seed(seed, level, node)
+    uint64_t seed;
+    uint32_t level;
+    uint8_t *side;                      // side of taxon v of node i at [nodes[i].moff + v], written when the node is cut
+    uint8_t *cut;                       // [n_nodes]
+    uint8_t *rounds;                    // [n_nodes] or null
+};
+
+__device__ __forceinline__ uint64_t stree_wave_sum(uint64_t x)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, m);
+    return x;
+}
+
+// one local search by one wave.  Lane l owns vertices l + 64 j, j < SLOTS: their sides in bit j of `bits`, their gains
+// in registers.  The cut's good and bad are kept as they change with every flip (mod 2^64; the true values fit).
+template <int SLOTS>
+__device__ __forceinline__ void stree_wave_search(const unsigned long long *G, const unsigned long long *B, const uint32_t n,
+                                                  const uint64_t p, const uint64_t q, uint32_t &bits, uint64_t &good,
+                                                  uint64_t &bad, uint32_t &ones)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    stree_i128 gain[SLOTS];
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) gain[j] = 0;
+    uint64_t pg = 0, pb = 0;
+    for (uint32_t u = 0; u < n; ++u) {
+        const uint32_t su = ((uint32_t)__shfl((int)bits, (int)(u & 63u)) >> (u >> 6)) & 1u;
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+            const uint32_t v = lane + 64u * (uint32_t)j;
+            if (v < n && v != u) {
+                const uint32_t c = stree_tri(u, v, n);
+                const uint64_t g = G[c], b = B[c];
+                const stree_i128 w = stree_edge(p, q, g, b);
+                if ((((bits >> j) & 1u) == su)) {
+                    gain[j] += w;
+                } else {
+                    gain[j] -= w;
+                    pg += g;
+                    pb += b;
+                }
+            }
+        }
+    }
+    const uint64_t good0 = stree_wave_sum(pg) >> 1, bad0 = stree_wave_sum(pb) >> 1;    // every pair was met twice
+    pg = lane == 0 ? good0 : 0;
+    pb = lane == 0 ? bad0 : 0;
+    uint32_t cnt1 = 0;
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) cnt1 += (uint32_t)__popcll(__ballot(lane + 64u * (uint32_t)j < n && ((bits >> j) & 1u)));
+    uint32_t cnt0 = n - cnt1;
+    const uint32_t flips = 50u * n;
+    for (uint32_t pass = 0; pass < flips; ++pass) {
+        stree_i128 bg = 0;
+        uint32_t bv = 0xFFFFFFFFu;
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+            const uint32_t v = lane + 64u * (uint32_t)j;
+            if (v < n && gain[j] > bg && (((bits >> j) & 1u) ? cnt1 : cnt0) > 2u) {
+                bg = gain[j];
+                bv = v;
+            }
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const unsigned long long olo = __shfl_xor((unsigned long long)(stree_u128)bg, m);
+            const unsigned long long ohi = __shfl_xor((unsigned long long)((stree_u128)bg >> 64), m);
+            const uint32_t ov = (uint32_t)__shfl_xor((int)bv, m);
+            const stree_i128 og = (stree_i128)(((stree_u128)ohi << 64) | olo);
+            if (og > bg || (og == bg && ov < bv)) {
+                bg = og;
+                bv = ov;
+            }
+        }
+        if (bv == 0xFFFFFFFFu) break;                                       // the same in every lane
+        const uint32_t v = bv, slot = v >> 6;
+        const uint32_t sv = ((uint32_t)__shfl((int)bits, (int)(v & 63u)) >> slot) & 1u, nv = sv ^ 1u;
+        cnt1 += nv ? 1u : 0xFFFFFFFFu;
+        cnt0 += nv ? 0xFFFFFFFFu : 1u;
+        if (lane == (v & 63u)) bits ^= 1u << slot;
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+            const uint32_t u = lane + 64u * (uint32_t)j;
+            if (u == v) {
+                gain[j] = -gain[j];
+            } else if (u < n) {
+                const uint32_t c = stree_tri(u, v, n);
+                const uint64_t g = G[c], b = B[c];
+                const stree_i128 w2 = 2 * stree_edge(p, q, g, b);
+                if (((bits >> j) & 1u) == nv) {                             // u is now on v's side: the pair is no longer cut
+                    gain[j] += w2;
+                    pg -= g;
+                    pb -= b;
+                } else {
+                    gain[j] -= w2;
+                    pg += g;
+                    pb += b;
+                }
+            }
+        }
+    }
+    good = stree_wave_sum(pg);
+    bad = stree_wave_sum(pb);
+    ones = cnt1;
+}
+
+// the rounds of one node by one workgroup: wave w runs starts w, w + waves, ...; two barriers per round
+template <int SLOTS>
+__device__ void stree_block_search(const unsigned long long *G, const unsigned long long *B, const uint32_t n,
+                                   const uint64_t node_seed, unsigned long long *s_good, unsigned long long *s_bad, int *s_s,
+                                   uint32_t *s_inc, uint32_t &out_bits, bool &out_cut, uint32_t &out_rounds)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const uint32_t starts = (uint32_t)stree_starts((int)n);
+    uint64_t p = 1, q = 1, ig = 0, ib = 0;
+    bool have = false;
+    uint32_t ibits = 0, rounds = 0;
+    for (uint32_t round = 0; round < (uint32_t)STREE_SEARCH_ROUNDS; ++round) {
+        ++rounds;
+        uint64_t wg = 0, wb = 0;
+        int ws = -1;
+        uint32_t wbits = 0;
+        for (uint32_t s = wave; s <= starts; s += waves) {
+            uint32_t bits = 0;
+            if (s == 0 && have) {
+                bits = ibits;
+            } else {
+                const uint64_t st0 = stree_start_seed(node_seed, round, s);
+                uint32_t c1 = 0;
+#pragma unroll
+                for (int j = 0; j < SLOTS; ++j) {
+                    const uint32_t v = lane + 64u * (uint32_t)j;
+                    const uint32_t bit = v < n ? stree_start_bit(st0, v) : 0u;
+                    bits |= bit << j;
+                    c1 += (uint32_t)__popcll(__ballot(bit != 0u));
+                }
+                if (c1 < 2u || n - c1 < 2u) {
+                    bits = 0;
+#pragma unroll
+                    for (int j = 0; j < SLOTS; ++j)
+                        if (lane + 64u * (uint32_t)j < n) bits |= (lane & 1u) << j;
+                }
+            }
+            uint64_t good, bad;
+            uint32_t ones;
+            stree_wave_search<SLOTS>(G, B, n, p, q, bits, good, bad, ones);
+            if (good > 0 && ones >= 2u && n - ones >= 2u && (ws < 0 || stree_better(good, bad, wg, wb))) {
+                wg = good;
+                wb = bad;
+                ws = (int)s;
+                wbits = bits;
+            }
+        }
+        if (lane == 0) {
+            s_good[wave] = wg;
+            s_bad[wave] = wb;
+            s_s[wave] = ws;
+        }
+        __syncthreads();
+        int win = -1;
+        for (uint32_t w = 0; w < waves; ++w) {
+            if (s_s[w] < 0) continue;
+            if (win < 0 || stree_better(s_good[w], s_bad[w], s_good[win], s_bad[win]) ||
+                (s_good[w] == s_good[win] && s_bad[w] == s_bad[win] && s_s[w] < s_s[win]))
+                win = (int)w;
+        }
+        const bool improved = win >= 0 && (!have || stree_better(s_good[win], s_bad[win], ig, ib));
+        if (improved) {
+            have = true;
+            ig = s_good[win];
+            ib = s_bad[win];
+            if ((int)wave == win) s_inc[lane] = wbits;
+        }
+        __syncthreads();                                                    // every value above is the same in all threads
+        if (improved) ibits = s_inc[lane];
+        if (!have) break;
+        if (!improved && round > 0) break;
+        if (ib == 0) break;
+        p = ig;
+        q = ib;
+    }
+    out_bits = ibits;
+    out_cut = have;
+    out_rounds = rounds;
+}
+
+// the cut search of a level: one workgroup per open node.  No loop waits on another lane, wave or workgroup; every
+// loop has a fixed bound (6 rounds, starts + 1 searches, n vertices, 50 n flips).
+__global__ __launch_bounds__(STREE_SEARCH_THREADS) void tq_stree_search_kernel(StreeSearchArgs a)
+{
+    __shared__ unsigned long long s_mat[2 * STREE_SEARCH_LDS_CELLS];
+    __shared__ unsigned long long s_good[16], s_bad[16];
+    __shared__ int s_s[16];
+    __shared__ uint32_t s_inc[64];
+    const uint32_t node = blockIdx.x;
+    if (node >= (uint32_t)a.n_nodes) return;
+    const StreeNode nd = a.nodes[node];
+    const uint32_t lane = threadIdx.x & 63u;
+    bool cut = false;
+    uint32_t bits = 0, rounds = 0;
+    if (nd.n >= 4 && nd.n <= STREE_T_MAX) {                                 // the same for every thread of the workgroup
+        const uint32_t n = (uint32_t)nd.n, tri = n * (n - 1) / 2;
+        const unsigned long long *G = a.mat + nd.toff, *B = a.mat + a.cells + nd.toff;
+        int any = 0;
+        for (uint32_t c = threadIdx.x; c < tri; c += blockDim.x) any |= B[c] != 0;
+        any = __syncthreads_or(any);
+        if (any && n == 4) {
+            cut = stree_search4((const uint64_t *)G, (const uint64_t *)B, bits);
+        } else if (any) {
+            if (tri <= (uint32_t)STREE_SEARCH_LDS_CELLS) {
+                for (uint32_t c = threadIdx.x; c < tri; c += blockDim.x) {
+                    s_mat[c] = G[c];
+                    s_mat[tri + c] = B[c];
+                }
+                __syncthreads();
+                G = s_mat;
+                B = s_mat + tri;
+            }
+            const uint64_t ns = a.seeds ? a.seeds[node] : stree_node_seed(a.seed, a.level, node);
+            if (n <= 64) stree_block_search<1>(G, B, n, ns, s_good, s_bad, s_s, s_inc, bits, cut, rounds);
+            else if (n <= 128) stree_block_search<2>(G, B, n, ns, s_good, s_bad, s_s, s_inc, bits, cut, rounds);
+            else if (n <= 256) stree_block_search<4>(G, B, n, ns, s_good, s_bad, s_s, s_inc, bits, cut, rounds);
+            else if (n <= 512) stree_block_search<8>(G, B, n, ns, s_good, s_bad, s_s, s_inc, bits, cut, rounds);
+            else stree_block_search<16>(G, B, n, ns, s_good, s_bad, s_s, s_inc, bits, cut, rounds);
+        }
+        if (cut && threadIdx.x < 64u) {
+            if (n == 4) {
+                if (lane < 4u) a.side[nd.moff + lane] = (uint8_t)((bits >> lane) & 1u);
+            } else {
+                for (uint32_t j = 0; lane + 64u * j < n; ++j) a.side[nd.moff + lane + 64u * j] = (uint8_t)((bits >> j) & 1u);
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        a.cut[node] = cut ? 1 : 0;
+        if (a.rounds) a.rounds[node] = (uint8_t)rounds;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // the driver (host): level loop, search, forest, newick -- once, for both back ends
 // ------------------------------------------------------------------------------------------------------------------
 struct StreeLevelStat {
@@ -307,20 +738,34 @@ struct StreeBackend {
     // the level's matrices u64 [2][cells] (G then B), valid until the next call
     virtual int graphs(const std::vector<StreeNode> &nodes, int64_t cells, int level, const uint64_t *&mat,
                        std::string &err) = 0;
+    // rule "exact" only: the cut search of the level whose matrices `graphs` just made.  sides[nodes[i].moff + v] = side
+    // of taxon v of node i where cuts[i] != 0.  With `exact` set, `graphs` may leave the matrices where this reads them
+    // and hand out no host pointer.
+    virtual int search(const std::vector<StreeNode> &nodes, int64_t cells, int level, uint64_t seed,
+                       std::vector<uint8_t> &sides, std::vector<uint8_t> &cuts, std::string &err) = 0;
+    bool exact = false;
     // routes the live quartets through the cuts (children, nA, nB in `nodes`; side and new index in `map`)
     virtual int partition(const std::vector<StreeNode> &nodes, const std::vector<uint32_t> &map, int level, int64_t &live,
                           std::string &err) = 0;
 };
 
-inline uint64_t stree_node_seed(uint64_t seed, uint64_t level, uint64_t idx)
-{
-    QmcRng r{seed ^ (level * 0x9E3779B97F4A7C15ull) ^ (idx * 0xD1B54A32D192ED03ull)};
-    return r.next();
-}
-
 inline double stree_ms_since(const std::chrono::steady_clock::time_point &t0)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the exact search of a level on host matrices (StreeHostBackend, and the device back end's A/B leg)
+inline void stree_search_level_host(const std::vector<StreeNode> &nodes, const uint64_t *mat, int64_t cells, int level,
+                                    uint64_t seed, std::vector<uint8_t> &sides, std::vector<uint8_t> &cuts)
+{
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const int n = nodes[i].n;
+        cuts[i] = 0;
+        if (n < 4) continue;
+        int rounds;
+        cuts[i] = stree_search_exact(mat + nodes[i].toff, mat + cells + nodes[i].toff, n,
+                                     stree_node_seed(seed, (uint64_t)level, (uint64_t)i), &sides[nodes[i].moff], rounds);
+    }
 }
 
 inline int stree_build(StreeBackend &be, int64_t ntaxa, uint64_t seed, std::string &newick, int64_t &levels,
@@ -344,7 +789,7 @@ inline int stree_build(StreeBackend &be, int64_t ntaxa, uint64_t seed, std::stri
     std::vector<StreeNode> nodes;
     std::vector<uint32_t> map;
     std::vector<double> Gd, Bd;
-    std::vector<uint8_t> side;
+    std::vector<uint8_t> side, sides, cuts;
     int level = 0;
     while (!open.empty()) {
         const size_t nn = open.size();
@@ -365,7 +810,8 @@ inline int stree_build(StreeBackend &be, int64_t ntaxa, uint64_t seed, std::stri
         st.live = live;
         st.cells = (int64_t)cells;
         const uint64_t *mat = nullptr;
-        if (live > 0 && cells > 0) {
+        const bool have_graph = live > 0 && cells > 0;
+        if (have_graph) {
             const auto t0 = std::chrono::steady_clock::now();
             if (int rc = be.graphs(nodes, (int64_t)cells, level, mat, err)) return rc;
             st.graph_ms = stree_ms_since(t0);
@@ -374,10 +820,20 @@ inline int stree_build(StreeBackend &be, int64_t ntaxa, uint64_t seed, std::stri
         map.assign((size_t)moff, 0);
         next.clear();
         bool any_cut = false;
+        if (be.exact && have_graph) {
+            sides.assign((size_t)moff, 0);
+            cuts.assign(nn, 0);
+            if (int rc = be.search(nodes, (int64_t)cells, level, seed, sides, cuts, err)) return rc;
+        }
         for (size_t i = 0; i < nn; ++i) {
             const int n = nodes[i].n;
             bool cut = false;
-            if (n > 3 && mat) {
+            if (be.exact) {
+                if (n > 3 && have_graph && cuts[i]) {
+                    cut = true;
+                    side.assign(sides.begin() + nodes[i].moff, sides.begin() + nodes[i].moff + n);
+                }
+            } else if (n > 3 && mat) {
                 const uint64_t *G = mat + nodes[i].toff, *B = mat + cells + nodes[i].toff;
                 const size_t tri = (size_t)n * (n - 1) / 2;
                 uint64_t bsum = 0;
@@ -476,6 +932,12 @@ struct StreeHostBackend : StreeBackend {
             for (int j = 0; j < 4; ++j) G[good[j]] += K[i];
         }
         out = mat.data();
+        return TQ_OK;
+    }
+    int search(const std::vector<StreeNode> &nodes, int64_t cells, int level, uint64_t seed, std::vector<uint8_t> &sides,
+               std::vector<uint8_t> &cuts, std::string &) override
+    {
+        stree_search_level_host(nodes, mat.data(), cells, level, seed, sides, cuts);
         return TQ_OK;
     }
     int partition(const std::vector<StreeNode> &nodes, const std::vector<uint32_t> &map, int, int64_t &live,

@@ -168,6 +168,7 @@ struct tq_ctx {
     int cons_hash_bits = 64;        // consensus: the table key is the 64-bit mask hash cut to this many bits (results never depend on it)
     int64_t cons_scratch_bytes = int64_t(256) << 20;   // consensus: device + page-locked bytes of one chunk of trees
     int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
+    int stree_search_dev = 1;       // supertree rule "exact" on device rows: 1 = the search kernel, 0 = the same rule on the host (A/B)
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
     const uint32_t *scanned_q = nullptr;
     int64_t scanned_Q = 0;
@@ -1649,6 +1650,7 @@ struct tq_stree {
     uint32_t min_snps = 1;
     double min_ratio = 1.0;
     int mode = 0;                   // 0: nothing added yet, 1: host rows, 2: device rows (they do not mix)
+    int search = 0;                 // cut search rule: 0 = qmc_search on doubles, 1 = stree_search_exact (tq_stree_set_search)
     int64_t rows_in = 0;            // rows offered since create / reset (capacity counts these)
     // host rows
     std::vector<uint64_t> h_t, h_k;
@@ -1661,6 +1663,8 @@ struct tq_stree {
     unsigned long long *d_cnt = nullptr, *d_mat = nullptr;
     StreeNode *d_nodes = nullptr;
     uint32_t *d_map = nullptr;
+    uint8_t *d_side = nullptr, *d_cut = nullptr;    // the search kernel's answer: side bytes as the map is laid out, a cut byte per node
+    uint8_t *p_side = nullptr, *p_cut = nullptr;
     uint64_t *p_mat = nullptr;      // page-locked: a level's matrices, its nodes and side map, the counters
     StreeNode *p_nodes = nullptr;
     uint32_t *p_map = nullptr;
@@ -1679,10 +1683,10 @@ namespace {
 void stree_free_dev(tq_stree *a)
 {
     void *dev[] = {a->d_root_t, a->d_root_k, a->d_wt[0], a->d_wt[1], a->d_wk[0], a->d_wk[1], a->d_wn[0], a->d_wn[1],
-                   a->d_cnt, a->d_mat, a->d_nodes, a->d_map};
+                   a->d_cnt, a->d_mat, a->d_nodes, a->d_map, a->d_side, a->d_cut};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt};
+    void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt, a->p_side, a->p_cut};
     for (void *p : pin)
         if (p) (void)hipHostFree(p);
     if (a->ev) (void)hipEventDestroy(a->ev);
@@ -1744,9 +1748,42 @@ struct StreeDevBackend : StreeBackend {
             hipLaunchKernelGGL(tq_stree_graph_kernel, dim3(G), dim3(STREE_THREADS), 0, st, p);
         }
         STREE_HIP(hipGetLastError());
+        if (exact && a->ctx->stree_search_dev) {                   // the search kernel reads d_mat behind this on `st`
+            mat = nullptr;
+            return TQ_OK;
+        }
         STREE_HIP(hipMemcpyAsync(a->p_mat, a->d_mat, (size_t)(2 * cells) * 8, hipMemcpyDeviceToHost, st));
         STREE_HIP(hipStreamSynchronize(st));
         mat = a->p_mat;
+        return TQ_OK;
+    }
+    int search(const std::vector<StreeNode> &nodes, int64_t cells, int level, uint64_t seed, std::vector<uint8_t> &sides,
+               std::vector<uint8_t> &cuts, std::string &err) override
+    {
+        if (!a->ctx->stree_search_dev) {                            // the matrices are in p_mat
+            stree_search_level_host(nodes, a->p_mat, cells, level, seed, sides, cuts);
+            return TQ_OK;
+        }
+        if ((int64_t)nodes.size() > a->max_nodes || (int64_t)sides.size() > 3 * a->max_nodes) {
+            err = "a level exceeds the nodes the accumulator was created for";
+            return TQ_ERR_INVALID_ARG;
+        }
+        StreeSearchArgs p{};
+        p.nodes = a->d_nodes;                                       // uploaded by `graphs`
+        p.n_nodes = (int32_t)nodes.size();
+        p.cells = cells;
+        p.mat = a->d_mat;
+        p.seed = seed;
+        p.level = (uint32_t)level;
+        p.side = a->d_side;
+        p.cut = a->d_cut;
+        hipLaunchKernelGGL(tq_stree_search_kernel, dim3((unsigned)nodes.size()), dim3(STREE_SEARCH_THREADS), 0, st, p);
+        STREE_HIP(hipGetLastError());
+        STREE_HIP(hipMemcpyAsync(a->p_side, a->d_side, sides.size(), hipMemcpyDeviceToHost, st));
+        STREE_HIP(hipMemcpyAsync(a->p_cut, a->d_cut, nodes.size(), hipMemcpyDeviceToHost, st));
+        STREE_HIP(hipStreamSynchronize(st));
+        memcpy(sides.data(), a->p_side, sides.size());
+        memcpy(cuts.data(), a->p_cut, nodes.size());
         return TQ_OK;
     }
     int partition(const std::vector<StreeNode> &nodes, const std::vector<uint32_t> &map, int, int64_t &live,
@@ -2448,6 +2485,11 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "cons_scratch_bytes")) {          // read by tq_cons_create
         if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "cons_scratch_bytes must be >= 0 (0 = default 256 MiB)");
         ctx->cons_scratch_bytes = value ? value : int64_t(256) << 20;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "stree_search_dev")) {
+        if (value < 0 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "stree_search_dev must be 0 or 1");
+        ctx->stree_search_dev = (int)value;
         return TQ_OK;
     }
     if (!strcmp(name, "stree_lds")) {
@@ -3153,6 +3195,10 @@ int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int we
             e = hipHostMalloc((void **)&acc->p_nodes, (size_t)acc->max_nodes * sizeof(StreeNode), hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_map, (size_t)acc->max_nodes * 3 * 4, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_cnt, SC_WORDS * 8, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_side, (size_t)acc->max_nodes * 3);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_cut, (size_t)acc->max_nodes);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_side, (size_t)acc->max_nodes * 3, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_cut, (size_t)acc->max_nodes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMemset(acc->d_cnt, 0, SC_WORDS * 8);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking);
@@ -3361,11 +3407,13 @@ int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_
             StreeDevBackend db;
             db.a = acc;
             db.st = (hipStream_t)stream;
+            db.exact = acc->search == 1;
             rc = stree_build(db, acc->ntaxa, seed, nwk, lv, acc->stats, err);
         } else {
             StreeHostBackend hb;
             hb.root_t = &acc->h_t;
             hb.root_k = &acc->h_k;
+            hb.exact = acc->search == 1;
             rc = stree_build(hb, acc->ntaxa, seed, nwk, lv, acc->stats, err);
         }
         if (rc) return fail(acc->ctx, rc, "tq_stree_build: %s", err.c_str());
@@ -3376,6 +3424,97 @@ int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_
         return TQ_OK;
     } catch (const std::bad_alloc &) {
         return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_build: out of host memory");
+    }
+}
+
+int tq_stree_set_search(tq_stree *acc, int search)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (search != 0 && search != 1)
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_set_search: no search rule %d (0 = f64, 1 = exact)", search);
+    acc->search = search;
+    return TQ_OK;
+}
+
+int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const uint64_t *G, const uint64_t *B,
+                    const uint64_t *node_seeds, uint8_t *side, uint8_t *cut, int32_t *rounds)
+{
+    if (n_nodes < 1 || n_nodes > (int64_t(1) << 20) || !sizes || !G || !B || !node_seeds || !side || !cut)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_search: NULL pointer or n_nodes not in 1..2^20");
+    try {
+        std::vector<StreeNode> nodes((size_t)n_nodes);
+        uint64_t cells = 0, moff = 0;
+        for (int64_t i = 0; i < n_nodes; ++i) {
+            const int64_t n = sizes[i];
+            if (n < 4 || n > (ctx ? STREE_T_MAX : 65535))
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_search: node %lld has %lld taxa, outside 4..%d", (long long)i,
+                            (long long)n, ctx ? STREE_T_MAX : 65535);
+            nodes[(size_t)i].toff = (uint32_t)cells;
+            nodes[(size_t)i].moff = (uint32_t)moff;
+            nodes[(size_t)i].n = (int32_t)n;
+            nodes[(size_t)i].childA = nodes[(size_t)i].childB = -1;
+            cells += (uint64_t)n * (uint64_t)(n - 1) / 2;
+            moff += (uint64_t)n;
+            if (cells > 0xFFFFFFFFull) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_search: more than 2^32 cells");
+        }
+        if (!ctx) {
+            for (int64_t i = 0; i < n_nodes; ++i) {
+                const StreeNode &nd = nodes[(size_t)i];
+                int r = 0;
+                cut[i] = stree_search_exact(G + nd.toff, B + nd.toff, nd.n, node_seeds[i], side + nd.moff, r) ? 1 : 0;
+                if (!cut[i]) memset(side + nd.moff, 0, (size_t)nd.n);
+                if (rounds) rounds[i] = r;
+            }
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, hipSetDevice(ctx->device));
+        unsigned long long *d_mat = nullptr;
+        StreeNode *d_nodes = nullptr;
+        uint64_t *d_seeds = nullptr;
+        uint8_t *d_out = nullptr;                                   // side bytes, cut bytes, round bytes
+        std::vector<uint8_t> out((size_t)moff + 2 * (size_t)n_nodes);
+        int rc = TQ_OK;
+        auto step = [&](hipError_t e, const char *what) {
+            if (!rc && e != hipSuccess)
+                rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_stree_search: %s: %s", what,
+                          hipGetErrorString(e));
+        };
+        step(hipMalloc((void **)&d_mat, (size_t)cells * 16), "hipMalloc");
+        if (!rc) step(hipMalloc((void **)&d_nodes, (size_t)n_nodes * sizeof(StreeNode)), "hipMalloc");
+        if (!rc) step(hipMalloc((void **)&d_seeds, (size_t)n_nodes * 8), "hipMalloc");
+        if (!rc) step(hipMalloc((void **)&d_out, out.size()), "hipMalloc");
+        if (!rc) step(hipMemcpy(d_mat, G, (size_t)cells * 8, hipMemcpyHostToDevice), "H2D");
+        if (!rc) step(hipMemcpy(d_mat + cells, B, (size_t)cells * 8, hipMemcpyHostToDevice), "H2D");
+        if (!rc) step(hipMemcpy(d_nodes, nodes.data(), (size_t)n_nodes * sizeof(StreeNode), hipMemcpyHostToDevice), "H2D");
+        if (!rc) step(hipMemcpy(d_seeds, node_seeds, (size_t)n_nodes * 8, hipMemcpyHostToDevice), "H2D");
+        if (!rc) step(hipMemset(d_out, 0, out.size()), "hipMemset");
+        if (!rc) {
+            StreeSearchArgs p{};
+            p.nodes = d_nodes;
+            p.n_nodes = (int32_t)n_nodes;
+            p.cells = (int64_t)cells;
+            p.mat = d_mat;
+            p.seeds = d_seeds;
+            p.side = d_out;
+            p.cut = d_out + moff;
+            p.rounds = d_out + moff + n_nodes;
+            hipLaunchKernelGGL(tq_stree_search_kernel, dim3((unsigned)n_nodes), dim3(STREE_SEARCH_THREADS), 0, 0, p);
+            step(hipGetLastError(), "launch");
+        }
+        if (!rc) step(hipDeviceSynchronize(), "sync");
+        if (!rc) step(hipMemcpy(out.data(), d_out, out.size(), hipMemcpyDeviceToHost), "D2H");
+        if (d_mat) (void)hipFree(d_mat);
+        if (d_nodes) (void)hipFree(d_nodes);
+        if (d_seeds) (void)hipFree(d_seeds);
+        if (d_out) (void)hipFree(d_out);
+        if (rc) return rc;
+        memcpy(side, out.data(), (size_t)moff);
+        memcpy(cut, out.data() + moff, (size_t)n_nodes);
+        if (rounds)
+            for (int64_t i = 0; i < n_nodes; ++i) rounds[i] = out[(size_t)moff + (size_t)n_nodes + (size_t)i];
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_stree_search: out of host memory");
     }
 }
 

@@ -100,13 +100,21 @@ class Supertree:
     ntaxa     taxa 0..ntaxa-1 (with an engine: 4..1024)
     capacity  rows that may be added between two resets
     weights, min_snps, min_ratio   as `qmc_splits`
+    search    rule of the cut search: "f64" (default) = the multi-start search on the cells as doubles, on the host;
+              "exact" = the all-integer rule of DESIGN.md section 16, which device rows run in a kernel.  Each rule
+              gives one string from both back ends; the two rules draw different starts and may differ from each other.
     """
 
-    def __init__(self, ntaxa: int, capacity: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, engine=None):
+    SEARCH = {"f64": 0, "exact": 1}
+
+    def __init__(self, ntaxa: int, capacity: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, engine=None,
+                 search: str = "f64"):
         from . import _lib
         self._lib = _lib.load()
         if weights not in (0, 1, 2, 3):
             raise ValueError(f"no weight strategy {weights}")
+        if search not in self.SEARCH:
+            raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
         self.ntaxa, self.capacity, self.engine = int(ntaxa), int(capacity), engine
         self.levels = 0
         self._h = None
@@ -114,6 +122,16 @@ class Supertree:
         self._check(self._lib.tq_stree_create(ctypes.byref(h), self.ntaxa, self.capacity, int(weights), int(min_snps),
                                               float(min_ratio), engine._h if engine is not None else None))
         self._h = h
+        self.search = "f64"
+        if search != "f64":
+            self.set_search(search)
+
+    def set_search(self, search: str):
+        """The rule of the following `tree` calls: "f64" or "exact"."""
+        if search not in self.SEARCH:
+            raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
+        self._check(self._lib.tq_stree_set_search(self._h, self.SEARCH[search]))
+        self.search = search
 
     def _check(self, rc: int):
         if rc != 0:
@@ -213,10 +231,11 @@ class Supertree:
 
 
 def infer_supertree_exact(rqrts, rscor, rstat, ntaxa: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0,
-                          seed: int = 0, flags=None) -> str:
-    """`infer_supertree_from_arrays` on the exact path (host back end): the tree does not depend on the row order."""
+                          seed: int = 0, flags=None, search: str = "f64") -> str:
+    """`infer_supertree_from_arrays` on the exact path (host back end): the tree does not depend on the row order.
+    `search`: the rule of the cut search, as `Supertree`."""
     n = np.asarray(rqrts).reshape(-1, 4).shape[0]
-    with Supertree(ntaxa, n, weights, min_snps, min_ratio) as st:
+    with Supertree(ntaxa, n, weights, min_snps, min_ratio, search=search) as st:
         st.add(rqrts, rscor, rstat, flags)
         return st.tree(seed)
 

@@ -230,7 +230,7 @@ class ReplicateRunner:
 def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, nboots: int, *,
                     subsample_snps: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
                     rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
-                    concordance=None, supertree: str = "host", consensus=None) -> list:
+                    concordance=None, supertree: str = "host", consensus=None, search: str = "f64") -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
@@ -240,24 +240,30 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
     `supertree="device"`: the exact supertree (`qmc.Supertree`) instead -- no row leaves the
     device; each replicate's rows are added to one of a small ring of accumulators on the loop's stream and a worker
     thread builds the tree on a stream of its own, beside the resolve kernels of the next replicates.  One rank only.
+    `search="exact"` (with `supertree="device"` only; `tq_qmc_tree` has one rule) runs the cut search of those trees by
+    the all-integer rule in a kernel.
     `consensus` (a `consensus.Consensus`) receives the replicate trees in replicate order once they are all in
     (`consensus.tree()` is then the majority-rule tree with bootstrap supports)."""
     trees = _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
-                             rng, sampler, group, workers, concordance, supertree)
+                             rng, sampler, group, workers, concordance, supertree, search)
     if consensus is not None and trees:
         consensus.add_newick(trees)
     return trees
 
 
 def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed, rng,
-                     sampler, group, workers, concordance, supertree) -> list:
+                     sampler, group, workers, concordance, supertree, search="f64") -> list:
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
     if supertree not in ("host", "device"):
         raise ValueError("supertree must be 'host' or 'device'")
+    if search not in ("f64", "exact"):
+        raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
+    if search == "exact" and supertree == "host":
+        raise ValueError("search='exact' needs supertree='device': supertree='host' is tq_qmc_tree, which has one rule")
     if supertree == "device":
         return _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps,
-                                       min_ratio, seed, rng, sampler, group, workers, concordance)
+                                       min_ratio, seed, rng, sampler, group, workers, concordance, search)
     runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
                              quartets_to_host=True, concordance=concordance)
     ntaxa = int(seqarr.shape[0])
@@ -274,7 +280,7 @@ def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, w
 
 
 def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
-                            rng, sampler, group, workers, concordance) -> list:
+                            rng, sampler, group, workers, concordance, search="f64") -> list:
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
@@ -286,7 +292,8 @@ def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_
             raise NotImplementedError("supertree='device' runs on one rank (the graphs of several ranks are not summed)")
         workers = max(1, int(workers))
         ntaxa = int(seqarr.shape[0])
-        ring = [qmc.Supertree(ntaxa, int(nquartets), weights, min_snps, min_ratio, engine=engine) for _ in range(workers + 1)]
+        ring = [qmc.Supertree(ntaxa, int(nquartets), weights, min_snps, min_ratio, engine=engine, search=search)
+                for _ in range(workers + 1)]
         free: queue.Queue = queue.Queue()
         for slot in range(len(ring)):
             free.put(slot)

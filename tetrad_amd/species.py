@@ -120,7 +120,8 @@ def infer_species_tree(engine, species_map: SpeciesMap, nquartets: int = 0, weig
 
 def bootstrap_species_trees(engine, seqarr, spans, species_map: SpeciesMap, nboots: int, *, nquartets: int = 0,
                             alleles: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
-                            rng=None, supertree: str = "device", consensus=None, include_original: bool = False) -> list[str]:
+                            rng=None, supertree: str = "device", consensus=None, include_original: bool = False,
+                            search: str = "f64") -> list[str]:
     """Bootstrap species trees: `nboots` replicates of the loci of `seqarr` u8[T,S0] (ASCII, IUPAC codes) / `spans`
     i64[nloci,2], each built on the device, resolved in species mode and turned into a tree by the exact supertree
     (DESIGN.md sections 13 and 15).  Returns the newick strings in replicate order with the species numbers as tips
@@ -136,6 +137,7 @@ def bootstrap_species_trees(engine, seqarr, spans, species_map: SpeciesMap, nboo
 
     `alleles` (default) runs the species calls under option ``species_alleles``: both alleles of every genotype
     count, and `seed_ambig` has no influence.  With `alleles=False` the replicate's coin-resolved rows are pooled.
+    `search` ("f64" or "exact") is the rule of the supertree's cut search, as `qmc.Supertree`; both back ends take it.
     `consensus` (a `consensus.Consensus(K)`) receives all trees through `add_newick` once they are in.  One rank,
     one plain loop: a species replicate is a few milliseconds.
 
@@ -145,6 +147,8 @@ def bootstrap_species_trees(engine, seqarr, spans, species_map: SpeciesMap, nboo
     from .bootstrap import draw_replicate, identity_replicate
     if supertree not in ("device", "host"):
         raise ValueError(f"supertree must be 'device' or 'host', got {supertree!r}")
+    if search not in ("f64", "exact"):
+        raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
     rng = np.random.default_rng(seed) if rng is None else np.random.default_rng(rng)
     K = species_map.K
     sampled = 0 < nquartets < comb(K, 4)
@@ -162,7 +166,7 @@ def bootstrap_species_trees(engine, seqarr, spans, species_map: SpeciesMap, nboo
         drs = torch.empty((Q, 2), dtype=torch.int32, device=dev)
         dsc = torch.empty((Q, 3), dtype=torch.float64, device=dev)
         dfl = torch.empty(Q, dtype=torch.uint8, device=dev)
-    acc = qmc.Supertree(K, Q, weights, min_snps, min_ratio, engine=engine) if supertree == "device" else None
+    acc = qmc.Supertree(K, Q, weights, min_snps, min_ratio, engine=engine, search=search) if supertree == "device" else None
     trees = []
     engine.set_option("species_alleles", int(bool(alleles)))
     try:
@@ -189,7 +193,7 @@ def bootstrap_species_trees(engine, seqarr, spans, species_map: SpeciesMap, nboo
                 else:
                     rstat, rscor, flags = drs.cpu().numpy().view(np.uint32), dsc.cpu().numpy(), dfl.cpu().numpy()
                     trees.append(qmc.infer_supertree_exact(sq, rscor, rstat, K, weights, min_snps, min_ratio, seed=k,
-                                                           flags=flags))
+                                                           flags=flags, search=search))
     finally:
         stream.synchronize()
         engine.set_option("species_alleles", 0)

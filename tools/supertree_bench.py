@@ -9,6 +9,12 @@
   --loop            `bootstrap_trees` at the c5 shape (1e6 quartets per replicate): replicates/s for supertree="host"
                     and "device" in alternating rounds, workers 2 and 8, and the replicate loop without trees.
 
+  --search          the cut search rules on device rows, in alternating rounds in one run: the f64
+                    rule with its host search, the exact rule on the host (option stree_search_dev = 0) and the exact
+                    rule in the search kernel; rows -> tree and per level graph / search / partition ms at the c5
+                    shape (T = 128) and at T = 512.  With --loop: replicates/s of `bootstrap_trees(supertree="device")`
+                    for the same three legs.
+
 Prints one JSON document; --out FILE also writes it."""
 import argparse
 import json
@@ -124,9 +130,85 @@ def loop(args):
     return out
 
 
+SEARCH_LEGS = (("f64", "f64", 1), ("exact_host", "exact", 0), ("exact_device", "exact", 1))
+
+
+def search_stages(args):
+    import torch
+    from supertree_model import bipartitions, newick_bipartitions, rows_from_tree
+    from tetrad_amd import qmc
+    from tetrad_amd.engine import QuartetEngine
+    out = {"reps": args.reps, "rows": args.rows, "weights": 1}
+    with QuartetEngine(0) as eng:
+        cur = torch.cuda.current_stream()
+        for T in (128, 512):
+            children, root, q, sc, st = rows_from_tree(T, args.rows, "random", 0.1, seed=5)
+            truth = bipartitions(children, root, T)
+            n = len(q)
+            dq = torch.from_numpy(q.view(np.int32)).cuda()
+            dst = torch.from_numpy(st.view(np.int32)).cuda()
+            dsc = torch.from_numpy(sc).cuda()
+            total = {leg: [] for leg, _, _ in SEARCH_LEGS}
+            levels = {leg: [] for leg, _, _ in SEARCH_LEGS}
+            found = {}
+            with qmc.Supertree(T, n, 1, engine=eng) as acc:
+                acc.add_dev_ptrs(dq.data_ptr(), dst.data_ptr(), dsc.data_ptr(), 0, n, cur.cuda_stream)
+                try:
+                    for r in range(args.reps + 1):                             # round 0 warms up
+                        for leg, rule, on_dev in SEARCH_LEGS:
+                            acc.set_search(rule)
+                            eng.set_option("stree_search_dev", on_dev)
+                            t0 = time.perf_counter()
+                            nwk = acc.tree(seed=r, stream=cur.cuda_stream)
+                            if r:
+                                total[leg].append((time.perf_counter() - t0) * 1e3)
+                                levels[leg].append(acc.level_stats())
+                            found[leg] = [len(newick_bipartitions(nwk, T) & truth), len(truth)]
+                finally:
+                    eng.set_option("stree_search_dev", 1)
+            res = {}
+            for leg, _, _ in SEARCH_LEGS:
+                L = min(len(x) for x in levels[leg])
+                per = np.median(np.stack([x[:L] for x in levels[leg]]), axis=0)
+                res[leg] = {
+                    "tree_ms": med(total[leg]), "tree_ms_min_max": [round(min(total[leg]), 3), round(max(total[leg]), 3)],
+                    "graph_ms": round(float(per[:, 3].sum()), 3), "search_ms": round(float(per[:, 4].sum()), 3),
+                    "partition_ms": round(float(per[:, 5].sum()), 3), "true_bipartitions": found[leg],
+                    "levels": [dict(level=i, nodes=int(p[0]), live=int(p[1]), cells=int(p[2]), graph_ms=round(p[3], 4),
+                                    search_ms=round(p[4], 4), partition_ms=round(p[5], 4)) for i, p in enumerate(per)]}
+            out[f"T{T}"] = res
+    return out
+
+
+def search_loop(args):
+    from tetrad_amd import synth
+    from tetrad_amd.engine import QuartetEngine
+    from tetrad_amd.replicates import bootstrap_trees
+    seqarr, maparr, spans = synth.make_c5_source()
+    Q, nb = 1_000_000, args.nboots
+    out = {"quartets": Q, "replicates": nb, "rounds": args.rounds, "sampler": args.sampler, "workers": 8}
+    with QuartetEngine(0) as eng:
+        rates = {leg: [] for leg, _, _ in SEARCH_LEGS}
+        try:
+            for r in range(args.rounds + 1):                                   # round 0 warms up
+                for leg, rule, on_dev in SEARCH_LEGS:
+                    eng.set_option("stree_search_dev", on_dev)
+                    t0 = time.perf_counter()
+                    trees = bootstrap_trees(eng, seqarr, spans, Q, nb if r else 3, weights=1, seed=2 + r,
+                                            sampler=args.sampler, workers=8, supertree="device", search=rule)
+                    if r:
+                        rates[leg].append(len(trees) / (time.perf_counter() - t0))
+        finally:
+            eng.set_option("stree_search_dev", 1)
+        for leg, v in rates.items():
+            out[leg] = {"replicates_per_s": med(v), "rounds": [round(x, 2) for x in v]}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--loop", action="store_true")
+    ap.add_argument("--search", action="store_true")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--nboots", type=int, default=30)
@@ -137,7 +219,10 @@ def main():
     from tetrad_amd import _lib
     res = {"commit": (REPO / ".build_commit").read_text().strip() if (REPO / ".build_commit").exists() else None,
            "library": str(_lib.LIB_PATH.name)}
-    res["loop" if args.loop else "stages"] = loop(args) if args.loop else stages(args)
+    if args.search:
+        res["search_loop" if args.loop else "search_stages"] = search_loop(args) if args.loop else search_stages(args)
+    else:
+        res["loop" if args.loop else "stages"] = loop(args) if args.loop else stages(args)
     text = json.dumps(res, indent=1)
     print(text)
     if args.out:
