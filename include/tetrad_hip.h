@@ -258,7 +258,11 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value);
  * resident) and 1 if a subsample-mode scan issued now would read it; 5: the site order of the packed copy of the current
  * device-built replicate (option boot_pack) as u32[that padded site count] -- entry p = the replicate's site at packed
  * position p or 0xFFFFFFFF for a pad, what tq_pack_sites gives for the replicate's tmpmap -- TQ_ERR_INVALID_ARG when the
- * current packed copy was not built by tq_bootstrap or is stale.  No reference counterpart.                           */
+ * current packed copy was not built by tq_bootstrap or is stale; 6: three i64 about the most recent scan launch of the
+ * context, recorded where the launch is decided: the kernel form (0 none yet, 1 tq_scan_kernel, 2 tq_scan_wg_kernel,
+ * 3 tq_scan_wg2_kernel, 4 tq_scan_f4_kernel, 5 tq_scan_pb_kernel, 6 tq_scan_dp_kernel), T * pitch of the layout set it
+ * read (the cooperative forms 2-6 address that set with 32-bit byte offsets and are chosen only below 0xFFFF0000) and 1
+ * if that set was the packed one, else 0.  No reference counterpart.                                                */
 int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes);
 
 /* Test hook: run the bidiagonal-QR kernel (tq_bdsqr_kernel) alone on nmat bidiagonals given on the host -- de f64[nmat][32]

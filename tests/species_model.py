@@ -62,8 +62,18 @@ def pooled_factored(tmparr, species_of, K, squartets, counts=None) -> np.ndarray
     cnt = species_counts(tmparr, species_of, K) if counts is None else counts
     sq = np.asarray(squartets)
     out = np.zeros((len(sq), 4, 4, 4, 4), np.int64)
+    S = cnt.shape[1]
+    per_site = cnt.sum(axis=2)                      # lineages with a base, per species and site
     for r, (a, b, c, d) in enumerate(sq):
-        t = np.einsum("sx,sy,sz,sw->xyzw", cnt[a], cnt[b], cnt[c], cnt[d], optimize=True)
+        # every bin, and every partial sum of it, is a non-negative integer <= this total: below 2^53 the float64
+        # product (AB)^T (CD) of the two S x 16 outer-product panels is exact in any summation order (and runs in BLAS;
+        # the int64 einsum takes seconds per row at a million sites)
+        if int((per_site[a] * per_site[b] * per_site[c] * per_site[d]).sum()) < 2**53:
+            ab = (cnt[a][:, :, None] * cnt[b][:, None, :]).reshape(S, 16).astype(np.float64)
+            cd = (cnt[c][:, :, None] * cnt[d][:, None, :]).reshape(S, 16).astype(np.float64)
+            t = (ab.T @ cd).astype(np.int64).reshape(4, 4, 4, 4)
+        else:
+            t = np.einsum("sx,sy,sz,sw->xyzw", cnt[a], cnt[b], cnt[c], cnt[d], optimize=True)
         for x in range(4):
             t[x, x, x, x] = 0
         out[r] = t

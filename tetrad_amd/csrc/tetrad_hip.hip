@@ -206,6 +206,11 @@ struct tq_ctx {
     int64_t pk_Sp = 0, pk_W = 0;
     uint64_t pk_gen = ~0ull;        // data_gen the set was built from (~0: none)
     int64_t pk_cap = 0;             // sites per row the pk_* arrays were allocated for (they grow only while T stays)
+    // the most recent scan launch (tq_debug_fetch which = 6): its kernel form (SCAN_FORM_*, 0 = none yet), T * pitch of
+    // the layout set it read and whether that was the packed set
+    int last_scan_form = 0;
+    int64_t last_scan_tpitch = 0;
+    int last_scan_packed = 0;
     // packed set of a device-built replicate (bootstrap.hpp: tq_boot_pack_*): planned on the host at locus level
     int boot_pack = 0;              // 1: every replicate is packed, -1: when the rule said so for the source (boot_pack_auto),
                                     // 0: never (the replicate keeps the natural layout only); site_pack = 0 overrides
@@ -618,6 +623,18 @@ DevData scan_data(const tq_ctx *ctx, int subsample)
     return d;
 }
 
+// kernel forms of a scan launch as tq_debug_fetch(which = 6) reports them
+enum { SCAN_FORM_NONE = 0, SCAN_FORM_ONE_WAVE = 1, SCAN_FORM_WG = 2, SCAN_FORM_WG2 = 3, SCAN_FORM_F4 = 4, SCAN_FORM_PB = 5,
+       SCAN_FORM_DP = 6 };
+
+// remembers which kernel form takes the batch and the layout set it reads (a test hook; decides nothing)
+void note_scan(tq_ctx *ctx, int form, const DevData &d)
+{
+    ctx->last_scan_form = form;
+    ctx->last_scan_tpitch = ctx->T * d.pitch;
+    ctx->last_scan_packed = ctx->pk_rows && d.rows == ctx->pk_rows ? 1 : 0;
+}
+
 template <typename K>
 int grid_for(tq_ctx *ctx, K kern, int64_t items, int64_t *grid, int wpc_kernel = 0)
 {
@@ -734,7 +751,9 @@ int launch_scan_dp(tq_ctx *ctx, const uint32_t *dq, int64_t Q, hipStream_t strea
 {
     const int64_t least = ((Q + 1) / 2 + DP_NW - 1) / DP_NW;
     const int64_t grid = (least + 7) / 8 * 8;
-    hipLaunchKernelGGL(tq_scan_dp_kernel<DP_NW>, dim3((unsigned)grid), dim3(DP_NW * WAVE), 0, stream, dev_data(ctx), dq,
+    const DevData d = dev_data(ctx);
+    note_scan(ctx, SCAN_FORM_DP, d);
+    hipLaunchKernelGGL(tq_scan_dp_kernel<DP_NW>, dim3((unsigned)grid), dim3(DP_NW * WAVE), 0, stream, d, dq,
                        (const uint2 *)ctx->d_units, reinterpret_cast<const uint32_t *>(ctx->d_units + ctx->cm_quartets),
                        ctx->d_cm);
     TQ_HIP(ctx, hipGetLastError());
@@ -748,6 +767,7 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
     if (ctx->scan_pair && ctx->scan_wg == 4 && Q >= 64 && !ctx->count_invariant && !ctx->share_c && ctx->waves_per_cu == 0 &&
         ctx->scan_method < 2 && (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
         const int m = ctx->scan_method < 0 ? (subsample ? 1 : 0) : ctx->scan_method;
+        note_scan(ctx, SCAN_FORM_WG2, d);
         if (subsample)
             return m ? launch_scan_wg2<true, 1, 4>(ctx, d, dq, order, Q, stream) : launch_scan_wg2<true, 0, 4>(ctx, d, dq, order, Q, stream);
         return m ? launch_scan_wg2<false, 1, 4>(ctx, d, dq, order, Q, stream) : launch_scan_wg2<false, 0, 4>(ctx, d, dq, order, Q, stream);
@@ -759,6 +779,7 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
         (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
         const int nw = ctx->scan_wg;
         const int64_t nblk = (Q + nw - 1) / nw;
+        note_scan(ctx, SCAN_FORM_F4, d);
         int64_t grid = nblk, xcd_chunk = 0;
         if (ctx->xcd_remap && nblk >= 64) {
             xcd_chunk = (nblk + 7) / 8;
@@ -779,12 +800,15 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
     const bool pb_fits = ctx->pb_ok == 1 && ctx->scan_wg == 4 && Q >= 64 && !ctx->count_invariant && !ctx->share_c &&
                          !ctx->scan_pair && ctx->waves_per_cu == 0 && d.pitch / TILE <= PB_MAX_TILES &&
                          (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull;
-    if (pb_fits && ctx->scan_method == 6)
+    if (pb_fits && ctx->scan_method == 6) {
+        note_scan(ctx, SCAN_FORM_PB, d);
         return subsample ? launch_scan_pb<true>(ctx, d, dq, order, Q, stream) : launch_scan_pb<false>(ctx, d, dq, order, Q, stream);
+    }
     if (ctx->scan_wg >= 2 && Q >= ctx->wg_min_quartets && !ctx->count_invariant &&
         (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
         int m = ctx->scan_method < 0 ? (subsample ? 1 : 0) : ctx->scan_method;
         if (m == 6) m = subsample ? 1 : 0;
+        note_scan(ctx, SCAN_FORM_WG, d);
 #define TQ_WG_CASE(NW)                                                                                   \
     if (ctx->scan_wg == NW) {                                                                            \
         if (m == 2) return launch_scan_wg<true, 2, NW>(ctx, d, dq, order, Q, stream);                       \
@@ -826,6 +850,7 @@ int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_
         return subsample ? launch_scan<N, true, 1>(ctx, d, dq, order, Q, stream)                        \
                          : launch_scan<N, false, 1>(ctx, d, dq, order, Q, stream)
     const int method = (ctx->scan_method < 0 || ctx->scan_method == 6) ? (subsample ? 1 : 0) : ctx->scan_method;
+    note_scan(ctx, SCAN_FORM_ONE_WAVE, d);
     switch (ctx->nrep) {
         TQ_SCAN_CASE(2);
         TQ_SCAN_CASE(4);
@@ -2871,6 +2896,12 @@ int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes)
     if (which == 4) {                       // the packed layout set: {its sites (0: none), 1 if the subsample scans read it now}
         const int64_t st[2] = {ctx->pk_rows ? ctx->pk_Sp : 0, scan_data(ctx, 1).rows == ctx->pk_rows && ctx->pk_rows ? 1 : 0};
         if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=4 takes 16 bytes");
+        memcpy(dst, st, sizeof st);
+        return TQ_OK;
+    }
+    if (which == 6) {                       // the most recent scan launch: {kernel form, T * pitch of the set it read, packed}
+        const int64_t st[3] = {ctx->last_scan_form, ctx->last_scan_tpitch, ctx->last_scan_packed};
+        if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=6 takes 24 bytes");
         memcpy(dst, st, sizeof st);
         return TQ_OK;
     }

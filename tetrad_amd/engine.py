@@ -333,6 +333,16 @@ class QuartetEngine:
         self._check(self._lib.tq_debug_fetch(self._h, 4, _ptr(out), out.nbytes))
         return int(out[0]), bool(out[1])
 
+    SCAN_FORMS = ("none", "one_wave", "wg", "wg2", "f4", "pb", "dp")
+
+    def last_scan(self):
+        """Test hook: (kernel form, T * pitch of the layout set it read, whether that was the packed set) of the most
+        recent scan launch; the form is one of SCAN_FORMS ('one_wave' = tq_scan_kernel, the others the cooperative
+        kernels tq_scan_<form>_kernel; 'none' before the first scan)."""
+        out = np.zeros(3, np.int64)
+        self._check(self._lib.tq_debug_fetch(self._h, 6, _ptr(out), out.nbytes))
+        return self.SCAN_FORMS[int(out[0])], int(out[1]), bool(out[2])
+
     def boot_pack_map(self) -> np.ndarray:
         """Test hook: the site order of the packed set the current device-built replicate carries (option ``boot_pack``):
         u32[S'] as `pack_sites` returns it for the replicate's tmpmap.  Refused when the replicate was not packed."""
