@@ -393,6 +393,27 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
  *                    which device rows run in a kernel (only side bytes and a cut byte per node come back, still two
  *                    synchronisations per level) and host rows on the host, with the same newick string from both.
  *                    Anything else: TQ_ERR_INVALID_ARG, the rule stays.  May be called between builds.
+ *   tq_stree_fit     quartet fit of R trees against the kept rows.  Trees as tq_cons_add takes
+ *                    them: parents i32[R][stride], n_nodes i64[R] (each <= stride), tips 0..ntaxa-1 = the taxa, every
+ *                    taxon of the accumulator in every tree.  Every tree is validated first: one bad tree gives
+ *                    TQ_ERR_INVALID_ARG with its index in the message and nothing is written.  With D(x, y) = the depth
+ *                    of the lowest common ancestor of tips x and y, a kept row a,b|c,d is satisfied when D(a,b) + D(c,d)
+ *                    is strictly the largest of the three pair sums, violated when one of the two others is, unresolved
+ *                    when the largest is not unique (a polytomy); the class does not depend on the rooting, on a root of
+ *                    degree 2 or on unary nodes.  out u64[R][6] = {k_satisfied, k_violated, k_unresolved, n_satisfied,
+ *                    n_violated, n_unresolved}: the k sum to the accumulator's sum of k, the n to its kept rows, and the
+ *                    host and the device execution agree bit for bit.  Host rows (or none, or no context) run on the
+ *                    host.  Device rows run tq_fit_table_kernel and tq_fit_kernel on `stream`, ordered behind the adds,
+ *                    with one synchronisation before returning.  Unlike the adds this call MAY ALLOCATE: the first fit
+ *                    of an accumulator allocates the table region (device) and staging for the parent arrays and the
+ *                    results (device and page-locked, 16 x ntaxa + 48 bytes per tree); both only grow and are freed
+ *                    with the accumulator.  The rows stay: fits and builds may alternate in any order.  Refused
+ *                    (TQ_ERR_INVALID_ARG) when the sum of k does not fit in 64 bits (tq_stree_graph then reports
+ *                    2^64 - 1); the 2^53 limit of tq_stree_build does not apply.  R = 0 and no kept rows (all zeros) are
+ *                    valid.
+ * Option "fit_scratch_bytes" (tq_set_option, default 64 MiB, read at an accumulator's first fit): bound of the table
+ * region.  Trees per chunk = max(1, bytes / (2 ntaxa^2)); chunks run one after the other on the call's stream.  Results
+ * never depend on it.
  * Option "stree_lds" (tq_set_option): 1 (default) = the graph pass sums in private LDS counters where a level's cells fit
  * (at most 8128 per matrix), 0 = global integer atomics only.  Both are exact.
  * Option "stree_search_dev": 1 (default) = device rows run the rule "exact" in tq_stree_search_kernel, 0 = the matrices
@@ -411,6 +432,8 @@ int tq_stree_rows(tq_stree *acc, uint32_t *splits, uint64_t *k, int64_t *n);
 int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_t cap, int64_t *written, int64_t *levels);
 int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out);
 int tq_stree_set_search(tq_stree *acc, int search);
+int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream,
+                 uint64_t *out);
 
 /* Test hook: the exact cut search alone on a batch of nodes.  sizes i32[n_nodes] (4..65535 on the host, 4..1024 on the
  * device), G and B the nodes' upper triangles one after the other (node of n taxa: n (n - 1) / 2 cells, cell (u < v) at

@@ -32,6 +32,7 @@
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
 //   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
+//   fit.hpp       tq_fit_*_kernel: LCA-depth tables of candidate trees, quartet fit of the supertree's kept rows against them
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
@@ -81,6 +82,7 @@ namespace {
 #include "species.hpp"
 #include "supertree.hpp"
 #include "consensus.hpp"
+#include "fit.hpp"
 
 }  // namespace
 
@@ -167,6 +169,7 @@ struct tq_ctx {
     int svd_wpc = 0;                // blocks per CU of the bidiag / bdsqr grids (0 = one pass per block)
     int cons_hash_bits = 64;        // consensus: the table key is the 64-bit mask hash cut to this many bits (results never depend on it)
     int64_t cons_scratch_bytes = int64_t(256) << 20;   // consensus: device + page-locked bytes of one chunk of trees
+    int64_t fit_scratch_bytes = int64_t(64) << 20;     // quartet fit: device bytes of the tables of one chunk of trees (results never depend on it)
     int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
     int stree_search_dev = 1;       // supertree rule "exact" on device rows: 1 = the search kernel, 0 = the same rule on the host (A/B)
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
@@ -1701,6 +1704,13 @@ struct tq_stree {
     hipStream_t last = nullptr;
     hipStream_t own = nullptr;      // stream of tq_stree_graph / tq_stree_rows, which take none
     std::vector<StreeLevelStat> stats;   // of the last build
+    // quartet fit (fit.hpp): allocated at the first fit, grow-only, freed with the accumulator
+    int64_t fit_bytes = 0;          // bound of the table region, the option "fit_scratch_bytes" as the first fit read it
+    uint16_t *d_fit_tab = nullptr;  // [chunk trees][T][T]
+    int64_t fit_tab_trees = 0;
+    int32_t *d_fit_rec = nullptr, *p_fit_rec = nullptr;             // [trees][2 T] prepared parent arrays
+    unsigned long long *d_fit_out = nullptr, *p_fit_out = nullptr;  // [trees][6], then the accumulator's counters
+    int64_t fit_trees = 0;          // trees the record and result buffers hold
 };
 
 namespace {
@@ -1708,10 +1718,10 @@ namespace {
 void stree_free_dev(tq_stree *a)
 {
     void *dev[] = {a->d_root_t, a->d_root_k, a->d_wt[0], a->d_wt[1], a->d_wk[0], a->d_wk[1], a->d_wn[0], a->d_wn[1],
-                   a->d_cnt, a->d_mat, a->d_nodes, a->d_map, a->d_side, a->d_cut};
+                   a->d_cnt, a->d_mat, a->d_nodes, a->d_map, a->d_side, a->d_cut, a->d_fit_tab, a->d_fit_rec, a->d_fit_out};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt, a->p_side, a->p_cut};
+    void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt, a->p_side, a->p_cut, a->p_fit_rec, a->p_fit_out};
     for (void *p : pin)
         if (p) (void)hipHostFree(p);
     if (a->ev) (void)hipEventDestroy(a->ev);
@@ -2515,6 +2525,11 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "stree_search_dev")) {
         if (value < 0 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "stree_search_dev must be 0 or 1");
         ctx->stree_search_dev = (int)value;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "fit_scratch_bytes")) {
+        if (value < 1) return fail(ctx, TQ_ERR_INVALID_ARG, "fit_scratch_bytes must be at least 1");
+        ctx->fit_scratch_bytes = value;
         return TQ_OK;
     }
     if (!strcmp(name, "stree_lds")) {
@@ -3465,6 +3480,108 @@ int tq_stree_set_search(tq_stree *acc, int search)
         return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_set_search: no search rule %d (0 = f64, 1 = exact)", search);
     acc->search = search;
     return TQ_OK;
+}
+
+int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream,
+                 uint64_t *out)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes || !out)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: NULL pointer or negative size");
+    if (R == 0) return TQ_OK;
+    const int64_t T = acc->ntaxa;
+    try {
+        std::vector<std::vector<int32_t>> pars((size_t)R);          // every tree is validated before anything is written
+        std::vector<std::vector<int32_t>> nch;
+        for (int64_t r = 0; r < R; ++r) {
+            if (n_nodes[r] > stride)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: tree %lld: n_nodes exceeds the stride", (long long)r);
+            const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
+            if (!err.empty())
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: tree %lld: %s", (long long)r, err.c_str());
+            if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: tree %lld: internal error: a prepared tree of T taxa has "
+                            "at most 2 T - 2 nodes", (long long)r);
+        }
+        const char *wide = "tq_stree_fit: the sum of k does not fit in 64 bits";
+        if (acc->mode != 2) {                                       // host rows, or none yet
+            if (acc->h_sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s", wide);
+            std::vector<uint16_t> D((size_t)T * T);
+            std::vector<uint32_t> dep;
+            std::vector<uint64_t> res((size_t)R * FIT_WORDS);
+            for (int64_t r = 0; r < R; ++r) {
+                fit_host_table(pars[(size_t)r], (uint32_t)T, dep, D.data());
+                fit_host_rows(D.data(), (uint32_t)T, acc->h_t.data(), acc->h_k.data(), (int64_t)acc->h_t.size(),
+                              &res[(size_t)r * FIT_WORDS]);
+            }
+            memcpy(out, res.data(), res.size() * 8);
+            return TQ_OK;
+        }
+        hipStream_t st = (hipStream_t)stream;
+        if (int rc = stree_join(acc, st)) return rc;                // behind the adds made on other streams
+        const int64_t S = 2 * T;
+        if (!acc->fit_bytes) acc->fit_bytes = ctx->fit_scratch_bytes;
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(acc->fit_bytes / (2 * T * T), FIT_MAX_CHUNK_TREES));
+        const int64_t tab_trees = std::min(R, chunk);
+        if (R > acc->fit_trees) {                                   // no fit is in flight: each one ends with a synchronisation
+            if (acc->d_fit_rec) (void)hipFree(acc->d_fit_rec);
+            if (acc->d_fit_out) (void)hipFree(acc->d_fit_out);
+            if (acc->p_fit_rec) (void)hipHostFree(acc->p_fit_rec);
+            if (acc->p_fit_out) (void)hipHostFree(acc->p_fit_out);
+            acc->d_fit_rec = acc->p_fit_rec = nullptr;
+            acc->d_fit_out = acc->p_fit_out = nullptr;
+            acc->fit_trees = 0;
+            const size_t rec_bytes = (size_t)R * S * 4, out_bytes = ((size_t)R * FIT_WORDS + SC_WORDS) * 8;
+            TQ_HIP(ctx, hipMalloc((void **)&acc->d_fit_rec, rec_bytes));
+            TQ_HIP(ctx, hipMalloc((void **)&acc->d_fit_out, out_bytes));
+            TQ_HIP(ctx, hipHostMalloc((void **)&acc->p_fit_rec, rec_bytes, hipHostMallocDefault));
+            TQ_HIP(ctx, hipHostMalloc((void **)&acc->p_fit_out, out_bytes, hipHostMallocDefault));
+            acc->fit_trees = R;
+        }
+        if (tab_trees > acc->fit_tab_trees) {
+            if (acc->d_fit_tab) (void)hipFree(acc->d_fit_tab);
+            acc->d_fit_tab = nullptr;
+            acc->fit_tab_trees = 0;
+            TQ_HIP(ctx, hipMalloc((void **)&acc->d_fit_tab, (size_t)tab_trees * T * T * 2));
+            acc->fit_tab_trees = tab_trees;
+        }
+        memset(acc->p_fit_rec, 0, (size_t)R * S * 4);
+        for (int64_t r = 0; r < R; ++r) {
+            int32_t *rec = acc->p_fit_rec + r * S;
+            memcpy(rec, pars[(size_t)r].data(), pars[(size_t)r].size() * 4);
+            rec[S - 1] = (int32_t)pars[(size_t)r].size();
+        }
+        TQ_HIP(ctx, hipMemcpyAsync(acc->d_fit_rec, acc->p_fit_rec, (size_t)R * S * 4, hipMemcpyHostToDevice, st));
+        TQ_HIP(ctx, hipMemsetAsync(acc->d_fit_out, 0, (size_t)R * FIT_WORDS * 8, st));
+        const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
+        const unsigned table_blocks = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
+        const unsigned slices = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((acc->rows_in + FIT_ROWS_PER_BLOCK - 1) / FIT_ROWS_PER_BLOCK, FIT_MAX_SLICES));
+        for (int64_t r0 = 0; r0 < R; r0 += chunk) {                 // the next chunk's tables follow this chunk's fit on `st`
+            const unsigned n = (unsigned)std::min<int64_t>(chunk, R - r0);
+            FitTableArgs ta{acc->d_fit_rec + r0 * S, acc->d_fit_tab, (uint32_t)T};
+            hipLaunchKernelGGL(tq_fit_table_kernel, dim3(table_blocks, n), dim3(FIT_THREADS), 0, st, ta);
+            TQ_HIP(ctx, hipGetLastError());
+            if (acc->rows_in == 0) continue;
+            FitArgs fa{acc->d_root_t, acc->d_root_k, &acc->d_cnt[SC_KEPT], acc->d_fit_tab, acc->d_fit_out + r0 * FIT_WORDS,
+                       (uint32_t)T};
+            if (T <= FIT_T_LDS) hipLaunchKernelGGL(tq_fit_kernel<true>, dim3(slices, n), dim3(FIT_THREADS), 0, st, fa);
+            else hipLaunchKernelGGL(tq_fit_kernel<false>, dim3(slices, n), dim3(FIT_THREADS), 0, st, fa);
+            TQ_HIP(ctx, hipGetLastError());
+        }
+        unsigned long long *cnt = acc->p_fit_out + R * FIT_WORDS;
+        TQ_HIP(ctx, hipMemcpyAsync(acc->p_fit_out, acc->d_fit_out, (size_t)R * FIT_WORDS * 8, hipMemcpyDeviceToHost, st));
+        TQ_HIP(ctx, hipMemcpyAsync(cnt, acc->d_cnt, SC_WORDS * 8, hipMemcpyDeviceToHost, st));
+        TQ_HIP(ctx, hipStreamSynchronize(st));
+        const unsigned __int128 sum = (unsigned __int128)cnt[SC_SUM_LO] + ((unsigned __int128)cnt[SC_SUM_HI] << 32);
+        if (sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s", wide);
+        memcpy(out, acc->p_fit_out, (size_t)R * FIT_WORDS * 8);
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_stree_fit: out of host memory");
+    }
 }
 
 int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const uint64_t *G, const uint64_t *B,

@@ -8,6 +8,7 @@ Tip labels are the taxon numbers, as in the file the reference's `relabel_tree` 
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from pathlib import Path
 
@@ -91,6 +92,13 @@ def infer_supertree_from_arrays(rqrts, rscor, rstat, ntaxa: int, weights: int = 
     return qmc_tree(splits, w if weights else None, ntaxa, seed)
 
 
+#: one record of `Supertree.fit` per tree: the six integers of `tq_stree_fit`, and k_satisfied / (k_satisfied + k_violated)
+FIT_DTYPE = np.dtype([("k_satisfied", np.uint64), ("k_violated", np.uint64), ("k_unresolved", np.uint64),
+                      ("n_satisfied", np.uint64), ("n_violated", np.uint64), ("n_unresolved", np.uint64),
+                      ("fraction", np.float64)])
+LastFit = collections.namedtuple("LastFit", "results chosen seeds")
+
+
 class Supertree:
     """Exact quartet supertree accumulator (`tq_stree_*`): Quartet MaxCut level by level on
     integer graph weights.  Rows are added on the host (`add`) or where the engine wrote them (`add_dev_ptrs`, needs
@@ -117,6 +125,8 @@ class Supertree:
             raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
         self.ntaxa, self.capacity, self.engine = int(ntaxa), int(capacity), engine
         self.levels = 0
+        self.last_fit = None
+        self._chosen_stats = None
         self._h = None
         h = ctypes.c_void_p()
         self._check(self._lib.tq_stree_create(ctypes.byref(h), self.ntaxa, self.capacity, int(weights), int(min_snps),
@@ -205,9 +215,7 @@ class Supertree:
         self._check(self._lib.tq_stree_rows(self._h, sp.ctypes.data, k.ctypes.data, ctypes.byref(n)))
         return sp, k
 
-    def tree(self, seed: int = 0, stream: int = 0) -> str:
-        """Newick of the rows added so far (numeric tips); `self.levels` = levels of the recursion.  Device rows: the
-        passes run on `stream`."""
+    def _build(self, seed: int, stream: int) -> str:
         cap = 16 * self.ntaxa + 64
         written, levels = ctypes.c_int64(), ctypes.c_int64()
         for _ in range(2):
@@ -222,8 +230,78 @@ class Supertree:
             cap = written.value
         self._check(rc)
 
+    def tree(self, seed: int = 0, stream: int = 0, restarts: int = 1) -> str:
+        """Newick of the rows added so far (numeric tips); `self.levels` = levels of the recursion.  Device rows: the
+        passes run on `stream`.
+        `restarts=N` > 1: builds with the seeds seed, seed + 1, ..., seed + N - 1, fits the N trees to the rows in one
+        `tq_stree_fit` and returns the tree with the largest k_satisfied (ties: the smaller k_violated, then the lowest
+        seed).  `self.last_fit` then holds `LastFit(results, chosen, seeds)`; `levels` and `level_stats()` describe the
+        chosen seed's build."""
+        restarts = int(restarts)
+        if restarts < 1:
+            raise ValueError("restarts must be at least 1")
+        self._chosen_stats = None
+        if restarts == 1:
+            return self._build(seed, stream)
+        if self.ntaxa < 4:
+            raise ValueError("restarts need a tree of at least 4 taxa to score")
+        seeds = [int(seed) + i for i in range(restarts)]
+        builds = []
+        for s in seeds:
+            nwk = self._build(s, stream)
+            builds.append((nwk, self.levels, self.level_stats()))
+        res = self.fit([b[0] for b in builds], stream=stream)
+        chosen = min(range(restarts), key=lambda i: (-int(res["k_satisfied"][i]), int(res["k_violated"][i]), i))
+        self.last_fit = LastFit(res, chosen, seeds)
+        nwk, self.levels, self._chosen_stats = builds[chosen]
+        return nwk
+
+    def fit(self, trees, samples=None, stream: int = 0) -> np.ndarray:
+        """Quartet fit of `trees` against the kept rows (`tq_stree_fit`).  `trees`: a newick string,
+        a list of newick strings, or parent arrays (one int32 array with tips 0..ntaxa-1 = the taxa and parent[root] =
+        -1, or a list of them).  Tips are taxon numbers, or names through `samples` (as `concordance.newick_to_parent`).
+        Returns one record per tree (`FIT_DTYPE`; a single newick string or parent array gives a single record): the
+        weight k and the number n of the kept rows the tree displays (satisfied), contradicts (violated) and leaves in
+        a polytomy (unresolved), and fraction = k_satisfied / (k_satisfied + k_violated), NaN when that is 0 / 0.
+        Device rows: the kernels run on `stream`."""
+        from .concordance import newick_to_parent
+        single = isinstance(trees, str) or (isinstance(trees, np.ndarray) and trees.ndim == 1) or (
+            isinstance(trees, (list, tuple)) and len(trees) > 0 and np.isscalar(trees[0]) and not isinstance(trees[0], str))
+        items = [trees] if single else list(trees)
+        pars = []
+        for i, t in enumerate(items):
+            if isinstance(t, str):
+                try:
+                    par, T, _ = newick_to_parent(t, samples)
+                except ValueError as e:
+                    raise ValueError(f"tree {i}: {e}") from None
+                if T != self.ntaxa:
+                    raise ValueError(f"tree {i}: {T} taxa, the accumulator has {self.ntaxa}")
+            else:
+                par = np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
+            pars.append(par)
+        R = len(pars)
+        stride = max([len(p) for p in pars], default=0)
+        parents = np.full((R, max(stride, 1)), -1, np.int32)
+        for i, p in enumerate(pars):
+            parents[i, :len(p)] = p
+        n_nodes = np.array([len(p) for p in pars], np.int64)
+        raw = np.zeros((R, 6), np.uint64)
+        self._check(self._lib.tq_stree_fit(self._h, parents.ctypes.data, n_nodes.ctypes.data, R, parents.shape[1],
+                                           stream or None, raw.ctypes.data))
+        out = np.zeros(R, FIT_DTYPE)
+        for j, name in enumerate(FIT_DTYPE.names[:6]):
+            out[name] = raw[:, j]
+        den = out["k_satisfied"].astype(np.float64) + out["k_violated"].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["fraction"] = np.where(den > 0, out["k_satisfied"].astype(np.float64) / den, np.nan)
+        return out[0] if single else out
+
     def level_stats(self) -> np.ndarray:
-        """Of the last `tree`: f64[levels,6] = {open nodes, live quartets, cells, graph ms, search ms, partition ms}."""
+        """Of the last `tree` (with restarts: of the chosen seed's build): f64[levels,6] = {open nodes, live quartets,
+        cells, graph ms, search ms, partition ms}."""
+        if getattr(self, "_chosen_stats", None) is not None:
+            return self._chosen_stats
         n = ctypes.c_int64()
         out = np.zeros((64, 6), np.float64)
         self._check(self._lib.tq_stree_level_stats(self._h, ctypes.byref(n), out.ctypes.data))
@@ -231,13 +309,13 @@ class Supertree:
 
 
 def infer_supertree_exact(rqrts, rscor, rstat, ntaxa: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0,
-                          seed: int = 0, flags=None, search: str = "f64") -> str:
+                          seed: int = 0, flags=None, search: str = "f64", restarts: int = 1) -> str:
     """`infer_supertree_from_arrays` on the exact path (host back end): the tree does not depend on the row order.
-    `search`: the rule of the cut search, as `Supertree`."""
+    `search`: the rule of the cut search, as `Supertree`; `restarts`: as `Supertree.tree`."""
     n = np.asarray(rqrts).reshape(-1, 4).shape[0]
     with Supertree(ntaxa, n, weights, min_snps, min_ratio, search=search) as st:
         st.add(rqrts, rscor, rstat, flags)
-        return st.tree(seed)
+        return st.tree(seed, restarts=restarts)
 
 
 def relabel_tree(newick: str, samples) -> str:

@@ -230,7 +230,8 @@ class ReplicateRunner:
 def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray, nquartets: int, nboots: int, *,
                     subsample_snps: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
                     rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
-                    concordance=None, supertree: str = "host", consensus=None, search: str = "f64") -> list:
+                    concordance=None, supertree: str = "host", consensus=None, search: str = "f64", restarts: int = 1,
+                    fit_out=None) -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
@@ -242,17 +243,20 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
     thread builds the tree on a stream of its own, beside the resolve kernels of the next replicates.  One rank only.
     `search="exact"` (with `supertree="device"` only; `tq_qmc_tree` has one rule) runs the cut search of those trees by
     the all-integer rule in a kernel.
+    `restarts=N` (with `supertree="device"` only: the host path keeps no rows to score against) builds every
+    replicate's tree from N seeds and keeps the one that satisfies the most quartet weight (`Supertree.tree`, DESIGN.md
+    section 17); with `fit_out` a list, the chosen tree's fit record is appended per replicate, in replicate order.
     `consensus` (a `consensus.Consensus`) receives the replicate trees in replicate order once they are all in
     (`consensus.tree()` is then the majority-rule tree with bootstrap supports)."""
     trees = _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
-                             rng, sampler, group, workers, concordance, supertree, search)
+                             rng, sampler, group, workers, concordance, supertree, search, restarts, fit_out)
     if consensus is not None and trees:
         consensus.add_newick(trees)
     return trees
 
 
 def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed, rng,
-                     sampler, group, workers, concordance, supertree, search="f64") -> list:
+                     sampler, group, workers, concordance, supertree, search="f64", restarts=1, fit_out=None) -> list:
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
     if supertree not in ("host", "device"):
@@ -261,9 +265,19 @@ def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, w
         raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
     if search == "exact" and supertree == "host":
         raise ValueError("search='exact' needs supertree='device': supertree='host' is tq_qmc_tree, which has one rule")
+    restarts = int(restarts)
+    if restarts < 1:
+        raise ValueError("restarts must be at least 1")
+    if restarts != 1 and supertree == "host":
+        raise ValueError("restarts != 1 needs supertree='device': supertree='host' keeps no rows to score a tree against")
+    if fit_out is not None and not isinstance(fit_out, list):
+        raise ValueError("fit_out must be a list or None")
+    if fit_out is not None and supertree == "host":
+        raise ValueError("fit_out needs supertree='device': supertree='host' keeps no rows to score a tree against")
     if supertree == "device":
         return _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps,
-                                       min_ratio, seed, rng, sampler, group, workers, concordance, search)
+                                       min_ratio, seed, rng, sampler, group, workers, concordance, search, restarts,
+                                       fit_out)
     runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
                              quartets_to_host=True, concordance=concordance)
     ntaxa = int(seqarr.shape[0])
@@ -280,13 +294,13 @@ def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, w
 
 
 def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
-                            rng, sampler, group, workers, concordance, search="f64") -> list:
+                            rng, sampler, group, workers, concordance, search="f64", restarts=1, fit_out=None) -> list:
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
     runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
                              concordance=concordance)
-    ring, futures = [], {}
+    ring, futures, fits = [], {}, {}
     try:
         if runner.res.world > 1:
             raise NotImplementedError("supertree='device' runs on one rank (the graphs of several ranks are not summed)")
@@ -306,8 +320,11 @@ def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_
                 if getattr(local, "stream", None) is None:
                     torch.cuda.set_device(runner.dev)
                     local.stream = torch.cuda.Stream(runner.dev)
-                nwk = ring[slot].tree(seed=k, stream=local.stream.cuda_stream)
-                ring[slot].reset()
+                acc, cs = ring[slot], local.stream.cuda_stream
+                nwk = acc.tree(seed=k, stream=cs, restarts=restarts)
+                if fit_out is not None:
+                    fits[k] = acc.last_fit.results[acc.last_fit.chosen] if restarts > 1 else acc.fit(nwk, stream=cs)
+                acc.reset()
                 return nwk
             finally:
                 free.put(slot)
@@ -319,7 +336,10 @@ def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_
                 futures[k] = pool.submit(work, slot, k)
             runner.row_sink = sink
             runner.run(nboots, subsample_snps)
-            return [futures[k].result() for k in sorted(futures)]
+            trees = [futures[k].result() for k in sorted(futures)]
+            if fit_out is not None:
+                fit_out.extend(fits[k] for k in sorted(futures))
+            return trees
     finally:
         for f in futures.values():
             f.exception()                                   # every worker has let go of its accumulator
