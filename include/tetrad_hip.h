@@ -541,6 +541,51 @@ int tq_resolve_species_dev(tq_ctx *ctx, const uint32_t *d_squartets, int64_t Q, 
 int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor,
                              uint8_t *flags, uint32_t *cmats, double *svds, int32_t *ranks);
 
+/* Site-pattern classes and ABBA-BABA D tests.  No reference counterpart in tetrad itself: the
+ * class counts are what ipyrad's `baba` tool made of tetrad's count matrices.
+ *   Rule: a pattern is four bases (x0, x1, x2, x3) in the order of the quartet's four taxa; its class is its
+ *   restricted-growth string (position 0 gets label 0, every base not seen before the next label) and the 15 strings in
+ *   lexicographic order number the classes: 0000 0001 0010 0011 0012 0100 0101 0102 0110 0111 0112 0120 0121 0122 0123.
+ *   A class row is u32[16]: slots 0..14 the class counts, slot 15 their sum = the number of counted sites (rstat[:,1]
+ *   of the same quartet).  Class 0 is zero unless option "count_invariant" is set.  With roles (P1, P2, P3, O) in
+ *   positions 0..3, BBAA is class 3, BABA class 6 and ABBA class 8.  Permuting the four positions permutes the classes,
+ *   so every role assignment of a taxon set is read off the row of its ASCENDING quartet.
+ *   tq_pattern_class_table  out u8[256]: the class of pattern 64 x0 + 16 x1 + 4 x2 + x3 (host code, no context).
+ *   tq_patterns        sets u32[Q,4], host buffers, synchronous; validated as tq_resolve validates its quartets, and a
+ *                      row that is not strictly ascending is refused (TQ_ERR_INVALID_ARG naming the row) before anything
+ *                      is launched.  classes u32[Q,16].  Q = 0 is valid.
+ *   tq_patterns_dev    device pointers, enqueued on `stream` (the stream rule above): scan batches of at most option
+ *                      "batch", each followed by the class kernel at the batch's offset.  The rows are the caller's
+ *                      responsibility, as in tq_resolve_dev (an index >= T gives a row of zeros).
+ *                      d_sets and d_classes must be 16-byte aligned (rows are read and written as 16-byte words):
+ *                      a misaligned pointer is refused with TQ_ERR_INVALID_ARG before anything is launched.
+ *   tq_patterns_species / tq_patterns_species_dev  the same on species quartets (ascending species ids) after
+ *                      tq_set_species: the class counts of the pooled lineage combinations.  Refused when a species
+ *                      resolve call would be.
+ *   All four are refused (TQ_ERR_INVALID_ARG) while a timing-diagnostic mode is set (scan_method 2..5, phases 1 / 2):
+ *   there is no flags array to mark the rows with.
+ *   Timing (tq_timing_enable): a pattern call counts as one call of tq_timing_read* and records the marks of its scan
+ *   (ordering, site scan; species: table, pooled counts); the class kernel runs behind the last mark, so its time is in
+ *   none of the figures and the timing indices stay as they are.  Time it with events of your own around the call.
+ *   tq_dstat_accumulate_dev  one replicate of N tests added on `stream`: test t reads a = classes[set_of[t]][ia[t]] and
+ *                      b = classes[set_of[t]][ib[t]] (set_of u32[N], ia / ib u8[N] in 0..14: the classes that play ABBA
+ *                      and BABA for the test) and, unless a + b = 0, adds d = (a - b) / (a + b) to its row of
+ *                      acc f64[N][4] = {n, sum of d, sum of d * d, d of the last replicate added}.  Every operation is
+ *                      rounded once (no fused multiply-add), replicates are added one after another by the same thread:
+ *                      the result depends on the replicate order only and equals the host execution bit for bit.  A test
+ *                      whose set_of >= n_sets or whose class index is above 14 is skipped without touching memory.
+ *   tq_dstat_accumulate  the host execution (no context; messages go to tq_last_error(NULL)); such a test is refused
+ *                      (TQ_ERR_INVALID_ARG) and nothing is added.                                                     */
+int tq_pattern_class_table(uint8_t *out);
+int tq_patterns(tq_ctx *ctx, const uint32_t *sets, int64_t Q, int subsample, uint32_t *classes);
+int tq_patterns_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, int subsample, uint32_t *d_classes, void *stream);
+int tq_patterns_species(tq_ctx *ctx, const uint32_t *ssets, int64_t Q, uint32_t *classes);
+int tq_patterns_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, uint32_t *d_classes, void *stream);
+int tq_dstat_accumulate(const uint32_t *classes, int64_t n_sets, const uint32_t *set_of, const uint8_t *ia,
+                        const uint8_t *ib, int64_t N, double *acc);
+int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_sets, const uint32_t *d_set_of,
+                            const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream);
+
 /* Device facts used by bench.py: writes CU count, wave slots used by the resolve
  * kernel per CU and the padded row pitch in bytes.                                 */
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch);

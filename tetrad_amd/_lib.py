@@ -41,6 +41,8 @@ SYMBOLS = [
     "tq_cons_support", "tq_cons_stats",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
     "tq_pack_sites",
+    "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
+    "tq_dstat_accumulate", "tq_dstat_accumulate_dev",
 ]
 
 
@@ -243,6 +245,20 @@ def load() -> ctypes.CDLL:
     lib.tq_resolve_species_debug.restype = i32
     lib.tq_pack_sites.argtypes = [vp, i64, i64, vp, i64, vp, i64, c.POINTER(i64), c.POINTER(c.c_int32), vp]
     lib.tq_pack_sites.restype = i32
+    lib.tq_pattern_class_table.argtypes = [vp]
+    lib.tq_pattern_class_table.restype = i32
+    lib.tq_patterns.argtypes = [vp, vp, i64, i32, vp]
+    lib.tq_patterns.restype = i32
+    lib.tq_patterns_dev.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.tq_patterns_dev.restype = i32
+    lib.tq_patterns_species.argtypes = [vp, vp, i64, vp]
+    lib.tq_patterns_species.restype = i32
+    lib.tq_patterns_species_dev.argtypes = [vp, vp, i64, vp, vp]
+    lib.tq_patterns_species_dev.restype = i32
+    lib.tq_dstat_accumulate.argtypes = [vp, i64, vp, vp, vp, i64, vp]
+    lib.tq_dstat_accumulate.restype = i32
+    lib.tq_dstat_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp]
+    lib.tq_dstat_accumulate_dev.restype = i32
     lib.tq_device_info.argtypes = [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(i64)]
     lib.tq_device_info.restype = i32
     _lib = lib

@@ -83,6 +83,7 @@ namespace {
 #include "supertree.hpp"
 #include "consensus.hpp"
 #include "fit.hpp"
+#include "patterns.hpp"
 
 }  // namespace
 
@@ -1436,6 +1437,88 @@ int debug_to_host(tq_ctx *ctx, const HostScratch &h, int64_t Q, int subsample, b
     return TQ_OK;
 }
 
+// Class rows of quartets dq[0..Q) (species quartets with `species`): scan batches of <= ctx->batch quartets into the
+// count slab, each followed on the same stream by the class kernel, which writes at the batch's offset of d_classes.
+// The caller has checked that the data are ready and that no diagnostic mode is set.
+int launch_patterns(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool species, uint32_t *d_classes,
+                    hipStream_t stream)
+{
+    if (ctx->timing) ctx->timed_calls++;
+    const int64_t batch = Q < ctx->batch ? Q : ctx->batch;
+    for (int64_t q0 = 0; q0 < Q; q0 += batch) {
+        const int64_t n = (Q - q0) < batch ? (Q - q0) : batch;
+        int rc = species ? stage_species(ctx, dq + q0 * 4, n, stream) : stage_scan(ctx, dq + q0 * 4, n, subsample, false, stream);
+        if (rc) return rc;
+        constexpr int per_block = PAT_THREADS / 16;
+        hipLaunchKernelGGL(tq_pattern_class_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(PAT_THREADS), 0,
+                           stream, (const uint32_t *)ctx->d_cm, n, d_classes + (size_t)q0 * PAT_ROW);
+        TQ_HIP(ctx, hipGetLastError());
+    }
+    ctx->scanned_Q = 0;          // the slab belongs to this call only
+    return TQ_OK;
+}
+
+// what every pattern call checks before anything is launched
+int patterns_ready(tq_ctx *ctx, const char *who, int subsample, bool species)
+{
+    int rc = species ? species_ready(ctx, who) : check_ready(ctx, subsample);
+    if (rc) return rc;
+    if (diagnostic_mode(ctx))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: a timing-diagnostic mode is set (scan_method 2..5 or phases 1 / 2): its rows "
+                    "are not results and class rows have no flags array to mark them with", who);
+    return TQ_OK;
+}
+
+// host sets -> host class rows (synchronous): rows must be strictly ascending indices below `bound`
+int patterns_to_host(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t Q, int subsample, bool species,
+                     uint32_t *classes)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || (Q > 0 && (!sets || !classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+    int rc = patterns_ready(ctx, who, subsample, species);
+    if (rc) return rc;
+    if (Q == 0) return TQ_OK;
+    const uint32_t bound = (uint32_t)(species ? ctx->sp_K : ctx->T);
+    for (int64_t i = 0; i < Q; ++i) {
+        const uint32_t *q = sets + 4 * i;
+        if ((q[0] >= bound) | (q[1] >= bound) | (q[2] >= bound) | (q[3] >= bound))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= %s=%u", who, (long long)i, species ? "K" : "T", bound);
+        if (!((q[0] < q[1]) & (q[1] < q[2]) & (q[2] < q[3])))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
+                        q[0], q[1], q[2], q[3]);
+    }
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t o_cls = align_up((size_t)Q * 16, 256);
+    if ((rc = ensure_scratch(ctx, o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    char *base = (char *)ctx->d_scratch;
+    uint32_t *d_classes = (uint32_t *)(base + o_cls);
+    TQ_HIP(ctx, hipMemcpyAsync(base, sets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
+    rc = launch_patterns(ctx, (const uint32_t *)base, Q, subsample, species, d_classes, ctx->sK);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->sK);
+        return rc;
+    }
+    TQ_HIP(ctx, hipMemcpyAsync(classes, d_classes, (size_t)Q * PAT_ROW * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->sK));
+    TQ_HIP(ctx, hipStreamSynchronize(ctx->sK));
+    return TQ_OK;
+}
+
+// device sets -> device class rows, enqueued on `stream`
+int patterns_dev(tq_ctx *ctx, const char *who, const uint32_t *d_sets, int64_t Q, int subsample, bool species,
+                 uint32_t *d_classes, hipStream_t stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || (Q > 0 && (!d_sets || !d_classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+    if (int rc = patterns_ready(ctx, who, subsample, species)) return rc;
+    if (Q == 0) return TQ_OK;
+    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = enter_dev_api(ctx, stream)) return rc;      // before any shared scratch is touched
+    return note_dev_api(ctx, stream, launch_patterns(ctx, d_sets, Q, subsample, species, d_classes, stream));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Concordance accumulator (concordance.hpp): device totals u64 [words] = per edge {conc, disc1, disc2, nu, nsnps sum,
 // weight sum (f64 bits), score sum (f64 bits)}, per taxon {QFc, QFd}, skipped rows; host totals of tq_conc_add beside.
@@ -2395,6 +2478,66 @@ int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, 
 int tq_resolve_species(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor, uint8_t *flags)
 {
     return tq_resolve_species_debug(ctx, squartets, Q, rstat, rscor, flags, nullptr, nullptr, nullptr);
+}
+
+int tq_pattern_class_table(uint8_t *out)
+{
+    if (!out) return TQ_ERR_INVALID_ARG;
+    for (int p = 0; p < 256; ++p) out[p] = (uint8_t)pattern_class(p >> 6, (p >> 4) & 3, (p >> 2) & 3, p & 3);
+    return TQ_OK;
+}
+
+int tq_patterns(tq_ctx *ctx, const uint32_t *sets, int64_t Q, int subsample, uint32_t *classes)
+{
+    return patterns_to_host(ctx, "tq_patterns", sets, Q, subsample, false, classes);
+}
+
+int tq_patterns_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, int subsample, uint32_t *d_classes, void *stream)
+{
+    return patterns_dev(ctx, "tq_patterns_dev", d_sets, Q, subsample, false, d_classes, (hipStream_t)stream);
+}
+
+int tq_patterns_species(tq_ctx *ctx, const uint32_t *ssets, int64_t Q, uint32_t *classes)
+{
+    return patterns_to_host(ctx, "tq_patterns_species", ssets, Q, 0, true, classes);
+}
+
+int tq_patterns_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, uint32_t *d_classes, void *stream)
+{
+    return patterns_dev(ctx, "tq_patterns_species_dev", d_ssets, Q, 0, true, d_classes, (hipStream_t)stream);
+}
+
+int tq_dstat_accumulate(const uint32_t *classes, int64_t n_sets, const uint32_t *set_of, const uint8_t *ia, const uint8_t *ib,
+                        int64_t N, double *acc)
+{
+    if (N < 0 || n_sets < 0 || (N > 0 && (!classes || !set_of || !ia || !ib || !acc)))
+        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate: NULL pointer or negative size");
+    for (int64_t t = 0; t < N; ++t) {
+        if ((int64_t)set_of[t] >= n_sets)
+            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate: test %lld has set_of=%u >= n_sets=%lld", (long long)t,
+                        set_of[t], (long long)n_sets);
+        if (ia[t] >= PAT_CLASSES || ib[t] >= PAT_CLASSES)
+            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate: test %lld has a class index above 14 (%u, %u)",
+                        (long long)t, (unsigned)ia[t], (unsigned)ib[t]);
+    }
+    dstat_add_host(classes, set_of, ia, ib, N, acc);
+    return TQ_OK;
+}
+
+int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_sets, const uint32_t *d_set_of,
+                            const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (N < 0 || n_sets < 0 || (N > 0 && (!d_classes || !d_set_of || !d_ia || !d_ib || !d_acc)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate_dev: NULL pointer or negative size");
+    if (N == 0) return TQ_OK;
+    if (N > (int64_t)0x7FFFFFFF * DSTAT_THREADS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate_dev: N=%lld tests exceed one launch", (long long)N);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(tq_dstat_kernel, dim3((unsigned)((N + DSTAT_THREADS - 1) / DSTAT_THREADS)), dim3(DSTAT_THREADS), 0,
+                       (hipStream_t)stream, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc);
+    TQ_HIP(ctx, hipGetLastError());
+    return TQ_OK;
 }
 
 int tq_timing_enable(tq_ctx *ctx, int on)

@@ -263,6 +263,44 @@ class QuartetEngine:
         self._check(self._lib.tq_resolve_species_dev(self._h, d_squartets, Q, d_rstat, d_rscor, d_flags or None,
                                                      stream or None))
 
+    # -- site-pattern classes and D tests (tetrad_amd/patterns.py) ----
+    @staticmethod
+    def _sets(sets) -> np.ndarray:
+        s = np.asarray(sets)
+        if s.size and (s.min() < 0 or s.max() > 0xFFFFFFFF):
+            raise ValueError("set indices must fit an unsigned 32-bit integer")
+        return np.ascontiguousarray(s, dtype=np.uint32).reshape(-1, 4)
+
+    def patterns(self, sets, subsample_snps: bool = True) -> np.ndarray:
+        """Class rows u32[Q,16] of strictly ascending quartets `sets` [Q,4]: the 15 site-pattern class counts
+        (patterns.CLASS_STRINGS) and their sum, the number of counted sites."""
+        s = self._sets(sets)
+        classes = np.zeros((s.shape[0], 16), np.uint32)
+        self._check(self._lib.tq_patterns(self._h, _ptr(s), s.shape[0], int(bool(subsample_snps)), _ptr(classes)))
+        return classes
+
+    def patterns_dev(self, d_sets: int, Q: int, subsample_snps: bool, d_classes: int, stream: int = 0):
+        """The same with device pointers (u32[Q,4] in, u32[Q,16] out), enqueued on `stream`; the rows are the
+        caller's responsibility."""
+        self._check(self._lib.tq_patterns_dev(self._h, d_sets, Q, int(bool(subsample_snps)), d_classes, stream or None))
+
+    def patterns_species(self, ssets) -> np.ndarray:
+        """Class rows u32[Q,16] of strictly ascending SPECIES quartets: the counts of the pooled lineage combinations."""
+        s = self._sets(ssets)
+        classes = np.zeros((s.shape[0], 16), np.uint32)
+        self._check(self._lib.tq_patterns_species(self._h, _ptr(s), s.shape[0], _ptr(classes)))
+        return classes
+
+    def patterns_species_dev(self, d_ssets: int, Q: int, d_classes: int, stream: int = 0):
+        self._check(self._lib.tq_patterns_species_dev(self._h, d_ssets, Q, d_classes, stream or None))
+
+    def dstat_accumulate_dev(self, d_classes: int, n_sets: int, d_set_of: int, d_ia: int, d_ib: int, N: int, d_acc: int,
+                             stream: int = 0):
+        """One replicate of N D tests added to d_acc f64[N,4] = {n, sum, sum of squares, last} on `stream`: test t reads
+        ABBA at d_classes[d_set_of[t]][d_ia[t]] and BABA at [d_ib[t]] (u32 / u8 / u8 arrays on the device)."""
+        self._check(self._lib.tq_dstat_accumulate_dev(self._h, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc,
+                                                      stream or None))
+
     # -- device-pointer API (addresses as ints, e.g. torch.Tensor.data_ptr()) -------
     def resolve_dev(self, d_quartets: int, Q: int, subsample_snps: bool, d_rstat: int,
                     d_rscor: int, d_flags: int = 0, stream: int = 0):

@@ -1,0 +1,209 @@
+"""Site-pattern classes of quartets and ABBA-BABA D tests with bootstrap Z.
+
+A site pattern of a quartet is four bases in the order of its taxa.  Its class is its restricted-growth string:
+position 0 gets label 0 and every base not seen before gets the next label.  The 15 strings in lexicographic order
+(`CLASS_STRINGS`) number the classes; `QuartetEngine.patterns` returns u32[Q,16] rows with the 15 class counts and
+their sum.  With roles (P1, P2, P3, O) in positions 0..3, BBAA is class 3, BABA class 6 and ABBA class 8.
+
+Permuting the four positions only permutes the classes (`permute_classes`), so the engine scans every taxon set once,
+as its ascending quartet, and every role assignment is read off that row: `dstat_tests` turns tests in role order
+into the unique ascending sets and, per test, the row and the two class indices that play ABBA and BABA.
+
+`run_dstat` is the whole test: observed counts from the given matrix, then locus-bootstrap replicates built on the
+device, each followed on the same stream by the class rows of the unique sets and one accumulation kernel.  Nothing
+returns to the host before the end.
+"""
+from __future__ import annotations
+
+from itertools import combinations
+from typing import Optional
+
+import numpy as np
+
+from . import _lib, bootstrap
+from ._lib import TetradHipError
+from .engine import QuartetEngine, _ptr
+
+CLASS_STRINGS = ("0000", "0001", "0010", "0011", "0012", "0100", "0101", "0102", "0110", "0111", "0112", "0120",
+                 "0121", "0122", "0123")
+NCLASS = 15
+BBAA, BABA, ABBA = 3, 6, 8
+
+DSTAT_DTYPE = np.dtype([("abba", np.uint32), ("baba", np.uint32), ("bbaa", np.uint32), ("nsites", np.uint32),
+                        ("D", np.float64), ("boot_n", np.int64), ("boot_mean", np.float64), ("boot_std", np.float64),
+                        ("Z", np.float64)])
+
+
+def class_table() -> np.ndarray:
+    """u8[256]: the class of the pattern with slab index 64 x0 + 16 x1 + 4 x2 + x3, from the library's rule."""
+    out = np.zeros(256, np.uint8)
+    rc = _lib.load().tq_pattern_class_table(_ptr(out))
+    if rc != 0:
+        raise TetradHipError(rc, "tq_pattern_class_table failed")
+    return out
+
+
+def _class_of_labels(labels) -> int:
+    """The class of four symbols (any hashables) in position order."""
+    seen: dict = {}
+    s = "".join(str(seen.setdefault(x, len(seen))) for x in labels)
+    return CLASS_STRINGS.index(s)
+
+
+def class_permutation(perm) -> np.ndarray:
+    """i64[15]: new class of each class when the positions are reordered so that new position i holds what position
+    perm[i] held."""
+    perm = [int(p) for p in perm]
+    if sorted(perm) != [0, 1, 2, 3]:
+        raise ValueError("perm must be a permutation of 0..3")
+    return np.array([_class_of_labels([s[p] for p in perm]) for s in CLASS_STRINGS], np.int64)
+
+
+def permute_classes(classes: np.ndarray, perm) -> np.ndarray:
+    """Class rows [..., 16] (or [..., 15]) of quartets (t0, t1, t2, t3) -> the rows of (t[perm[0]], .., t[perm[3]]).
+    The sum slot stays."""
+    classes = np.asarray(classes)
+    out = classes.copy()
+    out[..., class_permutation(perm)] = classes[..., :NCLASS]
+    return out
+
+
+def dstat_tests(tests):
+    """tests int[N,4] in the order (P1, P2, P3, O), distinct taxa in any order ->
+    (sets u32[M,4] unique and ascending, set_of u32[N], ia u8[N], ib u8[N]): test t reads ABBA at
+    classes[set_of[t], ia[t]] and BABA at classes[set_of[t], ib[t]] of the class rows of `sets`.  The three D tests of
+    one taxon set share one row."""
+    sets, set_of, idx = _role_classes(tests, (ABBA, BABA))
+    return sets, set_of, idx[:, 0].copy(), idx[:, 1].copy()
+
+
+def _role_classes(tests, role_classes):
+    tests = np.asarray(tests)
+    if tests.ndim != 2 or tests.shape[1] != 4:
+        raise ValueError("tests must be [N, 4] in the order (P1, P2, P3, O)")
+    if tests.size and tests.min() < 0:
+        raise ValueError("taxon indices must not be negative")
+    tests = tests.astype(np.int64)
+    order = np.argsort(tests, axis=1, kind="stable")
+    asc = np.take_along_axis(tests, order, axis=1)
+    if tests.shape[0] and (asc[:, 1:] == asc[:, :-1]).any():
+        raise ValueError("the four taxa of a test must be distinct")
+    # role position i holds ascending position rank[i]
+    rank = np.argsort(order, axis=1, kind="stable")
+    idx = np.zeros((tests.shape[0], len(role_classes)), np.uint8)
+    cache: dict = {}
+    for t, p in enumerate(map(tuple, rank.tolist())):
+        if p not in cache:
+            inv = np.argsort(class_permutation(p))          # inv[role class] = class of the ascending row
+            cache[p] = [int(inv[c]) for c in role_classes]
+        idx[t] = cache[p]
+    if tests.shape[0]:
+        sets, set_of = np.unique(asc, axis=0, return_inverse=True)
+    else:
+        sets, set_of = asc, np.zeros(0, np.int64)
+    return (np.ascontiguousarray(sets, dtype=np.uint32), np.ascontiguousarray(set_of.reshape(-1), dtype=np.uint32), idx)
+
+
+def tests_with_outgroup(ntaxa: int, outgroup: int) -> np.ndarray:
+    """i64[3 C(ntaxa - 1, 3), 4]: every test (P1, P2, P3, O) with O = outgroup -- for each three other taxa a < b < c
+    the three choices of P3: (a, b, c), (a, c, b), (b, c, a)."""
+    if not 0 <= outgroup < ntaxa:
+        raise ValueError("outgroup must be a taxon index")
+    rows = []
+    for a, b, c in combinations([t for t in range(ntaxa) if t != outgroup], 3):
+        rows += [(a, b, c, outgroup), (a, c, b, outgroup), (b, c, a, outgroup)]
+    return np.array(rows, np.int64).reshape(-1, 4)
+
+
+def dstat_moments(D: np.ndarray, acc: np.ndarray):
+    """(boot_n, boot_mean, boot_std, Z) from the observed D and the accumulator f64[N,4] = {n, s1, s2, last}:
+    boot_mean = s1 / n, boot_std = sqrt(max(0, s2 / n - (s1 / n)^2)), Z = D / boot_std; NaN where a denominator is 0."""
+    acc = np.asarray(acc, np.float64).reshape(-1, 4)
+    n, s1, s2 = acc[:, 0], acc[:, 1], acc[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(n > 0, s1 / n, np.nan)
+        std = np.where(n > 0, np.sqrt(np.maximum(0.0, s2 / n - mean * mean)), np.nan)
+        Z = np.where(std > 0, np.asarray(D, np.float64) / std, np.nan)
+    return n.astype(np.int64), mean, std, Z
+
+
+def observed_dstat(classes: np.ndarray, set_of, ia, ib, ibbaa) -> np.ndarray:
+    """The observed columns of the result from the class rows of the unique sets (the bootstrap columns empty)."""
+    rows = np.asarray(classes)[np.asarray(set_of, np.int64)]
+    take = lambda col: rows[np.arange(rows.shape[0]), np.asarray(col, np.int64)]
+    out = np.zeros(rows.shape[0], DSTAT_DTYPE)
+    out["abba"], out["baba"], out["bbaa"], out["nsites"] = take(ia), take(ib), take(ibbaa), rows[:, NCLASS]
+    a, b = out["abba"].astype(np.int64), out["baba"].astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["D"] = np.where(a + b > 0, (a - b) / (a + b), np.nan)
+    out["boot_mean"] = out["boot_std"] = out["Z"] = np.nan
+    return out
+
+
+def run_dstat(engine: QuartetEngine, tmparr, tmpmap, seqarr, spans, tests, nboots: int, *, subsample_snps: bool = False,
+              seed=None, rng: Optional[np.random.Generator] = None, species_of=None) -> np.ndarray:
+    """D tests with a locus bootstrap.  The observed counts are those of the resident matrix after
+    `set_data(tmparr, tmpmap)`; then `nboots` replicates of (seqarr, spans) are built on the device
+    (`bootstrap.draw_replicate` on one Generator, `engine.bootstrap` on the current stream), each followed on that
+    stream by the class rows of the unique sets and the accumulation of every test's D.  One device-to-host copy at
+    the end.  `tests` int[N,4] = (P1, P2, P3, O).  With `species_of` (i32[T], see `QuartetEngine.set_species`) the
+    tests name species and the counts are those of the pooled lineages (full mode only).
+    Returns a structured array per test: abba, baba, bbaa, nsites, D, boot_n, boot_mean, boot_std, Z."""
+    import torch
+    species = species_of is not None
+    if species and subsample_snps:
+        raise ValueError("species mode counts every site: subsample_snps must be False")
+    rng = rng if rng is not None else np.random.default_rng(seed)
+    sets, set_of, idx = _role_classes(tests, (ABBA, BABA, BBAA))
+    ia, ib = idx[:, 0].copy(), idx[:, 1].copy()
+    engine.set_data(tmparr, tmpmap)
+    if species:
+        engine.set_species(species_of)
+        obs = engine.patterns_species(sets)
+    else:
+        obs = engine.patterns(sets, subsample_snps)
+    out = observed_dstat(obs, set_of, ia, ib, idx[:, 2])
+    N, M = len(set_of), len(sets)
+    if nboots <= 0 or N == 0:
+        return out
+    engine.set_source(seqarr, spans)
+    nloci = int(np.asarray(spans).reshape(-1, 2).shape[0])
+    dev = torch.device("cuda", engine.device_id)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        d_sets = torch.from_numpy(sets.view(np.int32)).to(dev)
+        d_set_of = torch.from_numpy(set_of.view(np.int32)).to(dev)
+        d_ia, d_ib = torch.from_numpy(ia).to(dev), torch.from_numpy(ib).to(dev)
+        d_classes = torch.empty((M, 16), dtype=torch.int32, device=dev)
+        d_acc = torch.zeros((N, 4), dtype=torch.float64, device=dev)
+        for _ in range(int(nboots)):
+            lidxs, s1, s2 = bootstrap.draw_replicate(nloci, rng)
+            engine.bootstrap(lidxs, s1, s2, stream=cur.cuda_stream)
+            if species:
+                engine.patterns_species_dev(d_sets.data_ptr(), M, d_classes.data_ptr(), cur.cuda_stream)
+            else:
+                engine.patterns_dev(d_sets.data_ptr(), M, subsample_snps, d_classes.data_ptr(), cur.cuda_stream)
+            engine.dstat_accumulate_dev(d_classes.data_ptr(), M, d_set_of.data_ptr(), d_ia.data_ptr(), d_ib.data_ptr(), N,
+                                        d_acc.data_ptr(), cur.cuda_stream)
+        acc = d_acc.cpu().numpy()
+    out["boot_n"], out["boot_mean"], out["boot_std"], out["Z"] = dstat_moments(out["D"], acc)
+    return out
+
+
+def dstat_accumulate(classes, set_of, ia, ib, acc) -> np.ndarray:
+    """The host execution of the accumulation kernel (`tq_dstat_accumulate`, no GPU): one replicate's class rows
+    u32[M,16] added to acc f64[N,4] in place."""
+    classes = np.ascontiguousarray(classes, dtype=np.uint32).reshape(-1, 16)
+    set_of = np.ascontiguousarray(set_of, dtype=np.uint32)
+    ia, ib = np.ascontiguousarray(ia, dtype=np.uint8), np.ascontiguousarray(ib, dtype=np.uint8)
+    if not (isinstance(acc, np.ndarray) and acc.dtype == np.float64 and acc.flags.c_contiguous
+            and acc.size == 4 * set_of.shape[0]):
+        raise ValueError("acc must be a C-contiguous float64 array [N, 4]")
+    if not (ia.shape == ib.shape == set_of.shape):
+        raise ValueError("set_of, ia and ib must have one entry per test")
+    lib = _lib.load()
+    rc = lib.tq_dstat_accumulate(_ptr(classes), classes.shape[0], _ptr(set_of), _ptr(ia), _ptr(ib), set_of.shape[0],
+                                 _ptr(acc))
+    if rc != 0:
+        raise TetradHipError(rc, lib.tq_last_error(None).decode())
+    return acc
