@@ -586,6 +586,35 @@ int tq_dstat_accumulate(const uint32_t *classes, int64_t n_sets, const uint32_t 
 int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_sets, const uint32_t *d_set_of,
                             const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream);
 
+/* Site concordance factors per branch of a fixed tree: sCF / sDF1 / sDF2 / sN of Minh, Hahn &
+ * Lanfear 2020 from the class rows above.  No reference counterpart in tetrad itself.
+ *   Rule: a row is a set (a, b, c, d) with its class row u32[16] as the pattern calls write it.  The tree gives the
+ *   row's edge and its resolution r there exactly as the concordance accumulator does (a row induced on no edge counts
+ *   nowhere; a taxon >= T or a repeated taxon sends it to `skipped`).  n0, n1, n2 = classes 3, 6, 8: the sites that
+ *   support resolution 0, 1, 2 of the row as given; inf = n0 + n1 + n2.  conc = n_r, d1 = n of the lower of the two
+ *   other indices, d2 = n of the remaining one.  inf = 0: the edge's nq_zero += 1 and nothing else.  Otherwise nq += 1,
+ *   sum_x += x and fx_x += floor(x * 2^32 / inf) for x = conc, d1, d2.  Every sum is an unsigned 64-bit integer, so
+ *   host adds, device adds and any order of addition agree bit for bit.  sCF = 100 fx_conc / (nq 2^32).
+ *   tq_scf_create   tree as tq_conc_create takes it (4 <= T <= 4096, same unrooting, edges and edge order).  `ctx` may
+ *                   be NULL: then only tq_scf_add works.  The context must outlive the accumulator; messages go to
+ *                   tq_last_error(ctx) (tq_last_error(NULL) without one).
+ *   tq_scf_add      host rows, synchronous: sets u32[n,4], classes u32[n,16] (slot 15 is not read).  n = 0 is valid.
+ *   tq_scf_add_dev  the same rows as device pointers, enqueued on `stream` (hipStream_t, NULL = default stream),
+ *                   allocation-free; calls on different streams are ordered in call order.  d_sets and d_classes must be
+ *                   16-byte aligned: a misaligned pointer is refused with TQ_ERR_INVALID_ARG before anything is launched.
+ *   tq_scf_read     waits for the device adds and returns the sums of every add since create / reset, any output may be
+ *                   NULL: edge_counts i64[E][8] = {nq, nq_zero, sum_conc, sum_d1, sum_d2, fx_conc, fx_d1, fx_d2} (the
+ *                   u64 sums as their bit patterns), masks u64[E][W] and the edge order as tq_conc_read gives them for
+ *                   the same tree, *skipped.  E, W: tq_scf_shape.                                                     */
+typedef struct tq_scf tq_scf;
+int tq_scf_create(tq_scf **out, const int32_t *parent, int64_t n_nodes, int64_t T, tq_ctx *ctx);
+void tq_scf_destroy(tq_scf *acc);
+int tq_scf_reset(tq_scf *acc);
+int tq_scf_add(tq_scf *acc, const uint32_t *sets, const uint32_t *classes, int64_t n);
+int tq_scf_add_dev(tq_scf *acc, const uint32_t *d_sets, const uint32_t *d_classes, int64_t n, void *stream);
+int tq_scf_shape(const tq_scf *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words);
+int tq_scf_read(tq_scf *acc, int64_t *edge_counts, uint64_t *masks, int64_t *skipped);
+
 /* Device facts used by bench.py: writes CU count, wave slots used by the resolve
  * kernel per CU and the padded row pitch in bytes.                                 */
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch);

@@ -5,7 +5,19 @@ Only the per-quartet hot path of eaton-lab/tetrad and the callers / consumers ei
 mirrors of the reference's interfaces -- ``resolve_quartets`` (worker), ``distributor`` (dispatch + result gather
 over the GPUs of a node), ``replicates`` (bootstrap-replicate loop), ``bootstrap`` (resampler draws),
 ``combinations`` (quartet producers), ``qmc_format`` / ``qmc`` (wQMC text and the quartet supertree), ``concordance``
-(quartet concordance on a fixed tree), ``consensus`` (split counts over many trees, majority-rule consensus).
+(quartet concordance on a fixed tree), ``consensus`` (split counts over many trees, majority-rule consensus),
+``scf`` (site concordance factors per branch of a fixed tree).
 Importing the package does not load the HIP library; the first compute call does, and fails loudly if it is missing.
 """
 __version__ = "0.2.0"
+
+_SCF_EXPORTS = ("SiteConcordance", "sample_edge_quartets", "run_scf")
+__all__ = list(_SCF_EXPORTS)
+
+
+def __getattr__(name):
+    # resolved on first use, so that importing the package stays free of NumPy and of the binding
+    if name in _SCF_EXPORTS:
+        from . import scf
+        return getattr(scf, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -43,6 +43,7 @@ SYMBOLS = [
     "tq_pack_sites",
     "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
     "tq_dstat_accumulate", "tq_dstat_accumulate_dev",
+    "tq_scf_create", "tq_scf_destroy", "tq_scf_reset", "tq_scf_add", "tq_scf_add_dev", "tq_scf_shape", "tq_scf_read",
 ]
 
 
@@ -259,6 +260,20 @@ def load() -> ctypes.CDLL:
     lib.tq_dstat_accumulate.restype = i32
     lib.tq_dstat_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp]
     lib.tq_dstat_accumulate_dev.restype = i32
+    lib.tq_scf_create.argtypes = [c.POINTER(vp), vp, i64, i64, vp]
+    lib.tq_scf_create.restype = i32
+    lib.tq_scf_destroy.argtypes = [vp]
+    lib.tq_scf_destroy.restype = None
+    lib.tq_scf_reset.argtypes = [vp]
+    lib.tq_scf_reset.restype = i32
+    lib.tq_scf_add.argtypes = [vp, vp, vp, i64]
+    lib.tq_scf_add.restype = i32
+    lib.tq_scf_add_dev.argtypes = [vp, vp, vp, i64, vp]
+    lib.tq_scf_add_dev.restype = i32
+    lib.tq_scf_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.tq_scf_shape.restype = i32
+    lib.tq_scf_read.argtypes = [vp, vp, vp, c.POINTER(i64)]
+    lib.tq_scf_read.restype = i32
     lib.tq_device_info.argtypes = [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(i64)]
     lib.tq_device_info.restype = i32
     _lib = lib

@@ -31,6 +31,7 @@
 //   jacobi.hpp    tq_svd_kernel: one-sided Jacobi singular values in registers (alternative)
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
+//   scf.hpp         tq_scf_kernel + tq_scf_fold_kernel: site concordance sums of class rows on a fixed tree
 //   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
 //   fit.hpp       tq_fit_*_kernel: LCA-depth tables of candidate trees, quartet fit of the supertree's kept rows against them
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
@@ -84,6 +85,7 @@ namespace {
 #include "consensus.hpp"
 #include "fit.hpp"
 #include "patterns.hpp"
+#include "scf.hpp"
 
 }  // namespace
 
@@ -1587,6 +1589,77 @@ int conc_launch(tq_conc *acc, const uint32_t *dq, const uint32_t *drs, const dou
 }
 
 int conc_wait(tq_conc *acc)
+{
+    if (!acc->pending) return TQ_OK;
+    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+    TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
+    acc->pending = false;
+    return TQ_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// Site concordance accumulator (scf.hpp): device totals u64 [8 E + 1] = per edge {nq, nq_zero, sum conc / d1 / d2,
+// fx conc / d1 / d2}, skipped rows; host totals of tq_scf_add beside.
+// ---------------------------------------------------------------------------------------------
+struct tq_scf {
+    tq_ctx *ctx = nullptr;          // device adds need one; messages go to tq_last_error(ctx)
+    ConcTree t;
+    int64_t words = 0;
+    std::vector<uint64_t> hi;       // host adds
+    uint16_t *d_lca = nullptr, *d_dep = nullptr;
+    int32_t *d_eid = nullptr;
+    uint64_t *d_slab = nullptr, *d_tot = nullptr;
+    int gmax = 0;                   // workgroups the slab holds
+    int num_cu = 0;
+    hipEvent_t ev = nullptr;        // recorded behind the last device add
+    bool pending = false;
+    hipStream_t last = nullptr;
+};
+
+namespace {
+
+void scf_free_dev(tq_scf *a)
+{
+    if (a->d_lca) (void)hipFree(a->d_lca);
+    if (a->d_dep) (void)hipFree(a->d_dep);
+    if (a->d_eid) (void)hipFree(a->d_eid);
+    if (a->d_slab) (void)hipFree(a->d_slab);
+    if (a->d_tot) (void)hipFree(a->d_tot);
+    if (a->ev) (void)hipEventDestroy(a->ev);
+}
+
+int scf_launch(tq_scf *acc, const uint32_t *dsets, const uint32_t *dcls, int64_t n, hipStream_t stream)
+{
+    tq_ctx *ctx = acc->ctx;
+    const ConcTree &t = acc->t;
+    for (int64_t r0 = 0; r0 < n; r0 += SCF_ROWS_PER_LAUNCH) {
+        const int64_t m = std::min<int64_t>(SCF_ROWS_PER_LAUNCH, n - r0);
+        const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(m + 4095) / 4096, (int64_t)acc->num_cu, (int64_t)acc->gmax}));
+        ScfArgs a{dsets + 4 * r0, dcls + 16 * r0, m, acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, 0, t.E, 1, acc->d_slab,
+                  acc->words};
+        if (t.T <= SCF_T_LDS_A) {
+            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_A, SCF_T_LDS_A>), dim3(G), dim3(SCF_THREADS), 0, stream, a);
+        } else if (t.T <= SCF_T_LDS_B) {
+            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_B, SCF_T_LDS_B>), dim3(G), dim3(SCF_THREADS), 0, stream, a);
+        } else {
+            for (int32_t e0 = 0; e0 < t.E || e0 == 0; e0 += SCF_EDGE_TILE) {       // a pass per tile of edges
+                a.e_lo = e0;
+                a.e_n = std::min<int32_t>(SCF_EDGE_TILE, t.E - e0);
+                a.first = e0 == 0;
+                hipLaunchKernelGGL((tq_scf_kernel<false, CONC_T_MAX, SCF_EDGE_TILE>), dim3(G), dim3(SCF_THREADS), 0, stream, a);
+            }
+        }
+        hipLaunchKernelGGL(tq_scf_fold_kernel, dim3((unsigned)((acc->words + SCF_THREADS - 1) / SCF_THREADS)),
+                           dim3(SCF_THREADS), 0, stream, (const uint64_t *)acc->d_slab, G, acc->words, acc->d_tot);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_scf_add_dev: launch failed: %s", hipGetErrorString(e));
+    }
+    return TQ_OK;
+}
+
+int scf_wait(tq_scf *acc)
 {
     if (!acc->pending) return TQ_OK;
     TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
@@ -3339,6 +3412,133 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
     if (tip_counts)
         for (int64_t i = 0; i < 2 * (int64_t)t.T; ++i) tip_counts[i] = (int64_t)(dv[tb + i] + acc->hi[tb + i]);
     if (skipped) *skipped = (int64_t)(dv[tb + 2 * t.T] + acc->hi[tb + 2 * t.T]);
+    return TQ_OK;
+}
+
+int tq_scf_create(tq_scf **out, const int32_t *parent, int64_t n_nodes, int64_t T, tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: out is NULL");
+    *out = nullptr;
+    if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: parent is NULL");
+    tq_scf *acc = new (std::nothrow) tq_scf();
+    if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
+    try {
+        const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
+        if (!err.empty()) {
+            delete acc;
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: %s", err.c_str());
+        }
+        acc->ctx = ctx;
+        acc->words = (int64_t)acc->t.E * SCF_EDGE_WORDS + 1;
+        acc->hi.assign(acc->words, 0);
+    } catch (const std::bad_alloc &) {
+        delete acc;
+        return fail(ctx, TQ_ERR_OOM, "tq_scf_create: out of host memory");
+    }
+    if (ctx) {
+        const ConcTree &t = acc->t;
+        acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+        acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_lca, (size_t)T * T * 2);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_dep, (size_t)t.N * 2);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_eid, (size_t)t.N * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_slab, (size_t)acc->gmax * acc->words * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_tot, (size_t)acc->words * 8);
+        if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            scf_free_dev(acc);
+            delete acc;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_scf_create: %s", hipGetErrorString(e));
+        }
+    }
+    *out = acc;
+    return TQ_OK;
+}
+
+void tq_scf_destroy(tq_scf *acc)
+{
+    if (!acc) return;
+    if (acc->ctx) {
+        (void)hipSetDevice(acc->ctx->device);
+        if (acc->pending) (void)hipEventSynchronize(acc->ev);
+        scf_free_dev(acc);
+    }
+    delete acc;
+}
+
+int tq_scf_reset(tq_scf *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    std::fill(acc->hi.begin(), acc->hi.end(), 0);
+    if (acc->ctx) {
+        if (int rc = scf_wait(acc)) return rc;
+        TQ_HIP(acc->ctx, hipMemset(acc->d_tot, 0, (size_t)acc->words * 8));
+    }
+    return TQ_OK;
+}
+
+int tq_scf_add(tq_scf *acc, const uint32_t *sets, const uint32_t *classes, int64_t n)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (n < 0 || (n > 0 && (!sets || !classes)))
+        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_scf_add: NULL pointer or negative n");
+    scf_add_host(acc->t, sets, classes, n, acc->hi);
+    return TQ_OK;
+}
+
+int tq_scf_add_dev(tq_scf *acc, const uint32_t *d_sets, const uint32_t *d_classes, int64_t n, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: the accumulator was created without a context");
+    if (n < 0 || (n > 0 && (!d_sets || !d_classes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: NULL pointer or negative n");
+    if (n == 0) return TQ_OK;
+    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // sets are read as 16-byte words
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: d_sets and d_classes must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    if (acc->pending && st != acc->last) TQ_HIP(ctx, hipStreamWaitEvent(st, acc->ev, 0));   // slab / totals in call order
+    if (int rc = scf_launch(acc, d_sets, d_classes, n, st)) return rc;
+    TQ_HIP(ctx, hipEventRecord(acc->ev, st));
+    acc->pending = true;
+    acc->last = st;
+    return TQ_OK;
+}
+
+int tq_scf_shape(const tq_scf *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->t.T;
+    if (n_edges) *n_edges = acc->t.E;
+    if (mask_words) *mask_words = acc->t.W;
+    return TQ_OK;
+}
+
+int tq_scf_read(tq_scf *acc, int64_t *edge_counts, uint64_t *masks, int64_t *skipped)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    const ConcTree &t = acc->t;
+    std::vector<uint64_t> dv;
+    try {
+        dv.assign(acc->words, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_scf_read: out of host memory");
+    }
+    if (acc->ctx) {
+        if (int rc = scf_wait(acc)) return rc;
+        TQ_HIP(acc->ctx, hipMemcpy(dv.data(), acc->d_tot, (size_t)acc->words * 8, hipMemcpyDeviceToHost));
+    }
+    const int64_t eb = (int64_t)t.E * SCF_EDGE_WORDS;
+    if (edge_counts)
+        for (int64_t i = 0; i < eb; ++i) edge_counts[i] = (int64_t)(dv[i] + acc->hi[i]);
+    if (masks) memcpy(masks, t.masks.data(), t.masks.size() * 8);
+    if (skipped) *skipped = (int64_t)(dv[eb] + acc->hi[eb]);
     return TQ_OK;
 }
 

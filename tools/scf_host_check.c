@@ -1,0 +1,177 @@
+/* scf_host_check.c -- the host paths of the site concordance accumulator (tq_scf_create / tq_scf_add / tq_scf_read
+ * with a NULL context) driven from a plain C program, meant to be built with the host sanitizers:
+ *
+ *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
+ *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
+ *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/scf_host_check.c -o /tmp/scf_host_check.o
+ *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/scf_host_check.o -o /tmp/scf_host_check
+ *   /tmp/scf_host_check
+ *
+ * No device is needed or touched: every accumulator is created without a context.  Prints "scf_host_check: ok" and
+ * returns 0 when every check held; a sanitizer report or a failed check ends it with a non-zero status. */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "tetrad_hip.h"
+
+static uint64_t state = 0x9E3779B97F4A7C15ull;
+static uint32_t rnd(uint32_t n)
+{
+    state = state * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)((state >> 33) % n);
+}
+
+#define CHECK(cond)                                                                  \
+    do {                                                                             \
+        if (!(cond)) {                                                               \
+            fprintf(stderr, "scf_host_check: line %d: %s\n", __LINE__, #cond);       \
+            exit(1);                                                                 \
+        }                                                                            \
+    } while (0)
+
+/* random joins of two or three subtrees, a unary node now and then; returns the node count */
+static int64_t random_tree(int32_t T, int32_t *parent)
+{
+    int32_t *roots = (int32_t *)malloc(sizeof(int32_t) * (size_t)T);
+    int32_t nroots = T, n = T;
+    CHECK(roots);
+    for (int32_t t = 0; t < T; ++t) { roots[t] = t; parent[t] = -1; }
+    while (nroots > 1) {
+        const int32_t k = (nroots >= 3 && rnd(5) == 0) ? 3 : 2;
+        int32_t v = n++;
+        parent[v] = -1;
+        for (int32_t j = 0; j < k; ++j) {
+            const uint32_t p = rnd((uint32_t)nroots);
+            parent[roots[p]] = v;
+            roots[p] = roots[--nroots];
+        }
+        if (rnd(10) == 0) { parent[v] = n; v = n++; parent[v] = -1; }
+        roots[nroots++] = v;
+    }
+    free(roots);
+    return n;
+}
+
+static void run(int32_t T, int caterpillar, int64_t nrows)
+{
+    int32_t *parent = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)T);
+    int64_t n_nodes;
+    CHECK(parent);
+    if (caterpillar) {
+        int32_t prev = 0;
+        n_nodes = T;
+        for (int32_t t = 0; t < T; ++t) parent[t] = -1;
+        for (int32_t t = 1; t < T; ++t) {
+            const int32_t v = (int32_t)n_nodes++;
+            parent[v] = -1;
+            parent[prev] = v;
+            parent[t] = v;
+            prev = v;
+        }
+    } else {
+        n_nodes = random_tree(T, parent);
+    }
+    tq_scf *acc = NULL;
+    CHECK(tq_scf_create(&acc, parent, n_nodes, T, NULL) == TQ_OK && acc);
+    int64_t t = 0, E = 0, W = 0;
+    CHECK(tq_scf_shape(acc, &t, &E, &W) == TQ_OK && t == T && W == (T + 63) / 64);
+    if (caterpillar) CHECK(E == T - 3);
+
+    uint32_t *sets = (uint32_t *)malloc(sizeof(uint32_t) * 4 * (size_t)nrows);
+    uint32_t *classes = (uint32_t *)malloc(sizeof(uint32_t) * 16 * (size_t)nrows);
+    CHECK(sets && classes);
+    int64_t bad = 0;
+    for (int64_t i = 0; i < nrows; ++i) {
+        uint32_t *q = sets + 4 * i, *c = classes + 16 * i;
+        const int window = caterpillar && T > 8;          /* four taxa drawn from the whole caterpillar are hardly ever one edge apart */
+        const uint32_t base = window ? rnd((uint32_t)T - 7) : 0, span = window ? 8 : (uint32_t)T;
+        for (int k = 0; k < 4; ++k) q[k] = base + rnd(span);
+        const uint32_t kind = rnd(40);
+        if (kind == 0) q[1] = (uint32_t)T;
+        if (kind == 1) q[3] = 0xFFFFFFFFu;
+        if (kind == 2) q[2] = q[0];
+        for (int k = 0; k < 16; ++k) c[k] = rnd(3000);
+        const uint32_t v = rnd(8);
+        if (v == 0) c[3] = c[6] = c[8] = 0xFFFFFFFFu;
+        if (v == 1) c[3] = c[6] = c[8] = 0;
+        if (v == 2) { c[3] = 0xFFFFFFFFu; c[6] = 0; c[8] = 1; }
+        int rowbad = 0;
+        for (int a = 0; a < 4; ++a) {
+            if (q[a] >= (uint32_t)T) rowbad = 1;
+            for (int b = a + 1; b < 4; ++b)
+                if (q[a] == q[b]) rowbad = 1;
+        }
+        bad += rowbad;
+    }
+    const int64_t half = nrows / 2;
+    CHECK(tq_scf_add(acc, sets, classes, half) == TQ_OK);
+    CHECK(tq_scf_add(acc, sets + 4 * half, classes + 16 * half, nrows - half) == TQ_OK);
+    CHECK(tq_scf_add(acc, NULL, NULL, 0) == TQ_OK);
+    CHECK(tq_scf_add(acc, NULL, classes, 3) == TQ_ERR_INVALID_ARG);
+    CHECK(tq_scf_add(acc, sets, classes, -1) == TQ_ERR_INVALID_ARG);
+    CHECK(tq_scf_add_dev(acc, sets, classes, 1, NULL) == TQ_ERR_INVALID_ARG);
+    CHECK(strstr(tq_last_error(NULL), "without a context"));
+
+    int64_t *counts = (int64_t *)malloc(sizeof(int64_t) * 8 * (size_t)(E ? E : 1));
+    uint64_t *masks = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)((E ? E : 1) * W));
+    int64_t skipped = -1, induced = 0;
+    CHECK(counts && masks);
+    CHECK(tq_scf_read(acc, counts, masks, &skipped) == TQ_OK);
+    CHECK(tq_scf_read(acc, NULL, NULL, NULL) == TQ_OK);
+    CHECK(skipped == bad);
+    for (int64_t e = 0; e < E; ++e) {
+        const uint64_t *w = (const uint64_t *)counts + 8 * e;
+        induced += (int64_t)(w[0] + w[1]);
+        /* the three shares of a row add up to 2^32 less at most two truncations */
+        CHECK(w[5] + w[6] + w[7] <= (w[0] << 32) && w[5] + w[6] + w[7] + 2 * w[0] >= (w[0] << 32));
+        if (!w[0]) CHECK(!w[2] && !w[3] && !w[4]);
+        int64_t side = 0;
+        for (int64_t k = 0; k < W; ++k) side += __builtin_popcountll(masks[e * W + k]);
+        CHECK(side >= 2 && side <= T - 2);
+    }
+    CHECK(induced + skipped <= nrows);
+    if (E) CHECK(induced > 0);
+    CHECK(tq_scf_reset(acc) == TQ_OK);
+    CHECK(tq_scf_read(acc, counts, NULL, &skipped) == TQ_OK && skipped == 0);
+    for (int64_t i = 0; i < 8 * E; ++i) CHECK(counts[i] == 0);
+    tq_scf_destroy(acc);
+    free(masks); free(counts); free(classes); free(sets); free(parent);
+}
+
+int main(void)
+{
+    tq_scf *acc = (tq_scf *)1;
+    int32_t three[5] = {3, 3, 3, -1, 0};
+    CHECK(tq_scf_create(&acc, three, 4, 3, NULL) == TQ_ERR_INVALID_ARG && acc == NULL);
+    CHECK(tq_scf_create(&acc, NULL, 4, 4, NULL) == TQ_ERR_INVALID_ARG);
+    CHECK(tq_scf_create(NULL, three, 4, 3, NULL) == TQ_ERR_INVALID_ARG);
+    {
+        int32_t *big = (int32_t *)malloc(sizeof(int32_t) * 4098);
+        CHECK(big);
+        for (int i = 0; i < 4097; ++i) big[i] = 4097;
+        big[4097] = -1;
+        CHECK(tq_scf_create(&acc, big, 4098, 4097, NULL) == TQ_ERR_INVALID_ARG && acc == NULL);
+        CHECK(strstr(tq_last_error(NULL), "4096"));
+        /* a star of 4096 taxa: no edge, every row of distinct taxa is induced on none */
+        for (int i = 0; i < 4096; ++i) big[i] = 4096;
+        big[4096] = -1;
+        int64_t E = -1;
+        CHECK(tq_scf_create(&acc, big, 4097, 4096, NULL) == TQ_OK && tq_scf_shape(acc, NULL, &E, NULL) == TQ_OK && E == 0);
+        uint32_t q[4] = {0, 4095, 7, 9}, c[16] = {0};
+        int64_t skipped = -1;
+        CHECK(tq_scf_add(acc, q, c, 1) == TQ_OK && tq_scf_read(acc, NULL, NULL, &skipped) == TQ_OK && skipped == 0);
+        tq_scf_destroy(acc);
+        free(big);
+    }
+    tq_scf_destroy(NULL);
+    run(4, 1, 200);
+    run(5, 0, 2000);
+    run(40, 0, 200000);
+    run(257, 0, 200000);
+    run(4096, 0, 200000);
+    run(4096, 1, 200000);
+    printf("scf_host_check: ok\n");
+    return 0;
+}
