@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from concordance_model import ConcordanceModel, qc, qd, random_tree, row_values, row_values_reference, side_of
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 from tetrad_amd import _lib
 from tetrad_amd import concordance as C
 
@@ -258,6 +258,43 @@ def test_tsv_files_sum_like_one_accumulator(tmp_path):
     np.testing.assert_array_equal(a["QFc"], b["QFc"])
     assert_matches_model(got, model)
     assert "[&QC=" in got.to_newick() and "s0[&QF=" in got.to_newick()
+
+
+def test_to_newick_is_the_recorded_text():
+    """The annotated newick of the tree and rows of `test_tsv_files_sum_like_one_accumulator`, one name quoted, byte for
+    byte as tests/golden/concordance_newick_T14.txt records it (written by the recursive writer this one replaced)."""
+    rng = np.random.default_rng(11)
+    T = 14
+    parent = random_tree(T, rng, multifurcate=0.2)
+    acc = C.Concordance(parent, ntaxa=T, min_snps=2, min_ratio=1.05)
+    for _ in range(3):
+        q, sc, st, _ = random_rows(T, 700, rng, bad=False)
+        q.sort(axis=1)
+        acc.add(q, sc, st)
+    acc.names = [f"s{t}" for t in range(T)]
+    acc.names[3] = "s 3'x"
+    assert acc.to_newick() + "\n" == (GOLDEN / "concordance_newick_T14.txt").read_text()
+
+
+def test_to_newick_on_a_caterpillar_at_the_taxon_limit():
+    """4 096 taxa in a caterpillar are 4 095 levels deep, past Python's recursion limit: the text is written without
+    recursion, holds a comment for each of the T - 3 edges and each tip, and reads back as the same splits."""
+    from concordance_split_model import caterpillar
+    T = 4096
+    acc = C.Concordance(caterpillar(T), ntaxa=T)
+    q = np.array([[i, i + 1, i + 2, i + 3] for i in (0, 7, 2000, T - 4)], np.uint32)
+    acc.add(q, np.tile([1.0, 2.0, 4.0], (4, 1)), np.tile(np.array([0, 9], np.uint32), (4, 1)))
+    assert acc.raw()["edge_counts"][:, 1:5].sum() == 4
+    text = acc.to_newick()
+    assert text.count("[&QC=") == T - 3 and text.count("[&QF=") == T
+    par, T2, _ = C.newick_to_parent(text)
+    back = C.Concordance(par, ntaxa=T2)
+
+    def sides(a):
+        m = a.split_masks()
+        return {np.packbits(r).tobytes() for r in np.where(m[:, :1], ~m, m)}
+
+    assert T2 == T and back.n_edges == T - 3 and sides(back) == sides(acc)
 
 
 def test_supertree_newick_goes_back_in():

@@ -2,7 +2,7 @@
 bit-exact, the weight / score sums within 1e-12 relative -- on the LDS-table path (T = 128) and the global-table path
 (T = 600); the replicate loop feeds it every replicate's rows; two ranks reduce to one.
 
-At the sizes where `conc_launch` changes form (T = 129, 255, 256: the 256-taxon LDS form; 257: the global-table form),
+At the sizes where `tree_acc_add_dev` changes form (T = 129, 255, 256: the 256-taxon LDS form; 257: the global-table form),
 where that form starts a second edge pass (2 051 taxa = 2 048 edges = one full pass, 2 052 = a second pass of one
 edge) and at the table limit (4 096: two passes, fewer slabs than CUs) the device is compared with the split-mask
 model of tests/concordance_split_model.py, which shares nothing with the library's tree tables, on rows aimed at

@@ -1,5 +1,5 @@
 """GPU: the site concordance kernel (`tq_scf_add_dev`) equals the host execution and the
-Python-integer model of tests/scf_model.py, every word bit for bit, at the sizes where `scf_launch` changes form: the
+Python-integer model of tests/scf_model.py, every word bit for bit, at the sizes where `tree_acc_add_dev` changes form: the
 last T of each LDS form and the first past it, the T whose binary tree fills exactly one tile of edges and one edge more,
 and the table limit; at the row counts around the launcher's workgroup and grid boundaries; under every pattern of
 adds; and end to end through `run_scf` against class rows counted from the raw matrix by tests/patterns_model.py."""
@@ -182,6 +182,48 @@ def test_edge_order_is_that_of_the_concordance_accumulator(engine):
             np.testing.assert_array_equal(s.split_masks(), c.split_masks())
             assert (s.n_edges, s.mask_words) == (c.n_edges, c.mask_words)
             c.close()
+
+
+def test_both_accumulators_on_one_engine_across_streams(engine):
+    """A `Concordance` and a `SiteConcordance` on one engine and one tree of T = 129 (the smallest on the 256-taxon LDS
+    form), each with two device adds on two different streams, crosswise, equal their host adds word for word.  The
+    concordance scores are integers whose smallest is 1, 2 or 4, so every weight is a multiple of 1/2, every score a
+    multiple of 1/8, both at most 64: their f64 sums are exact in any order of addition, and the comparison is bitwise
+    for those words too."""
+    import torch
+    from tetrad_amd.concordance import Concordance
+    from tetrad_amd.scf import SiteConcordance
+    T = SCF_T_LDS_A + 1
+    rng = np.random.default_rng([T, 23])
+    parent = random_tree(T, rng)
+    sets, classes = scf_rows(ScfModel(parent, T), 2, 128, rng)        # 2 rows aimed at every edge, 128 mixed rows
+    n = len(sets)
+    h = n // 3
+    sc = np.stack([2.0 ** rng.integers(0, 3, n), rng.integers(4, 65, n), rng.integers(4, 65, n)], axis=1)
+    sc = rng.permuted(sc.astype(np.float64), axis=1)
+    st = np.stack([rng.integers(0, 3, n), rng.integers(0, 40, n)], axis=1).astype(np.uint32)
+    d_sets, d_classes = to_dev(sets, classes)
+    d_st, d_sc = torch.from_numpy(st.view(np.int32)).cuda(), torch.from_numpy(sc).cuda()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    s1.wait_stream(torch.cuda.current_stream())
+    s2.wait_stream(torch.cuda.current_stream())
+    with Concordance(parent, ntaxa=T, min_snps=3, min_ratio=1.25, engine=engine) as cd, \
+            Concordance(parent, ntaxa=T, min_snps=3, min_ratio=1.25) as ch, \
+            SiteConcordance(parent, ntaxa=T, engine=engine) as sd, SiteConcordance(parent, ntaxa=T) as sh:
+        cd.add_dev(d_sets[:h], d_st[:h], d_sc[:h], None, stream=s1)
+        sd.add_dev(d_sets[:h], d_classes[:h], stream=s2)
+        cd.add_dev(d_sets[h:], d_st[h:], d_sc[h:], None, stream=s2)
+        sd.add_dev(d_sets[h:], d_classes[h:], stream=s1)
+        ch.add(sets, sc, st)
+        sh.add(sets, classes)
+        assert_same(sd, sh)
+        got, want = cd.raw(), ch.raw()
+        for k in ("edge_counts", "edge_sums", "masks", "tip_counts"):
+            np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+        assert got["skipped"] == want["skipped"] == sh.raw()["skipped"] > 0
+        assert (want["edge_counts"][:, 1:5].sum(axis=1) >= 2).all() and (want["edge_sums"] > 0).all()
+        assert (sh.raw()["edge_counts"][:, NQ] >= 2).all()
+        torch.cuda.synchronize()
 
 
 # -- end to end ------------------------------------------------------------------------------------------------------

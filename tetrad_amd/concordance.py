@@ -183,15 +183,14 @@ def _div(a, b):
     return out
 
 
-class Concordance:
-    """Concordance counters of resolved quartet rows on one fixed tree.
+class _TreeAccumulator:
+    """What the accumulators of the library on one fixed tree share (`Concordance`, `scf.SiteConcordance`): the tree,
+    the handle and its lifecycle, the checks of device rows, the split masks and the annotated newick.  A subclass
+    names its family of library functions in `_prefix` and passes `tq_*_create` its own arguments."""
 
-    tree      newick text (tips = taxon numbers, or names through `samples`), or a parent array with `ntaxa`
-    engine    a `QuartetEngine` for device adds (`add_dev`); None: host adds only
-    """
+    _prefix = ""
 
-    def __init__(self, tree, *, samples=None, ntaxa: int | None = None, min_snps: int = 0, min_ratio: float = 1.0,
-                 engine=None):
+    def __init__(self, tree, samples, ntaxa, engine, *create_args):
         from . import _lib
         self._lib = _lib.load()
         if isinstance(tree, str):
@@ -203,18 +202,19 @@ class Concordance:
             self.newick = None
             par, T, names = np.ascontiguousarray(tree, dtype=np.int32), int(ntaxa), [str(t) for t in range(int(ntaxa))]
         self.parent, self.T, self.names = par, T, names
-        self.min_snps, self.min_ratio = int(min_snps), float(min_ratio)
         self.engine = engine                       # kept alive: the accumulator reports through its context
         ctx = engine._h if engine is not None else None
         h = ctypes.c_void_p()
-        rc = self._lib.tq_conc_create(ctypes.byref(h), par.ctypes.data, par.shape[0], T, self.min_snps, self.min_ratio, ctx)
+        rc = self._fn("create")(ctypes.byref(h), par.ctypes.data, par.shape[0], T, *create_args, ctx)
         if rc != 0:
             raise _lib.TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
         self._h = h
         t, e, w = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        self._check(self._lib.tq_conc_shape(h, ctypes.byref(t), ctypes.byref(e), ctypes.byref(w)))
+        self._check(self._fn("shape")(h, ctypes.byref(t), ctypes.byref(e), ctypes.byref(w)))
         self.n_edges, self.mask_words = e.value, w.value
-        self._carry = None                         # totals merged from other ranks (`reduce`)
+
+    def _fn(self, name):
+        return getattr(self._lib, f"{self._prefix}_{name}")
 
     # -- lifecycle ------------------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -225,7 +225,7 @@ class Concordance:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.tq_conc_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -241,7 +241,96 @@ class Concordance:
             pass
 
     def reset(self):
-        self._check(self._lib.tq_conc_reset(self._h))
+        self._check(self._fn("reset")(self._h))
+
+    # -- helpers of the subclasses ------------------------------------------------------------------------------
+    def _need_engine(self):
+        if self.engine is None:
+            raise ValueError("add_dev needs an accumulator created with an engine")
+
+    def _dev_stream(self, rows, n: int, stream) -> int:
+        """Checks device rows -- (tensor, elements per row, bytes per element) each, n rows -- and returns the handle
+        of `stream` (default: the current stream of their device)."""
+        import torch
+        for t, width, size in rows:
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size or t.numel() != n * width:
+                raise ValueError("device rows must be contiguous GPU tensors of matching shape and dtype")
+        if stream is None:
+            stream = torch.cuda.current_stream(rows[0][0].device)
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+
+    def _mask_bits(self, masks) -> np.ndarray:
+        """Mask words u64[E,W] -> bool [E,T]."""
+        bits = np.unpackbits(masks.view(np.uint8).reshape(self.n_edges, -1), axis=1, bitorder="little")
+        return bits[:, :self.T].astype(bool)
+
+    def _annotated_newick(self, split, edge_comment, tip_comment) -> str:
+        """The input tree (as given: rooted or not) with `edge_comment(e)` after the node of each edge (the first
+        node, in preorder, whose clade is one side of the edge; `split` bool [E,T]) and `tip_comment(t)`, which may be
+        empty, after each tip; tips carry their names."""
+        T, par = self.T, self.parent
+        n = par.shape[0]
+        kids = [[] for _ in range(n)]
+        root = -1
+        for v in range(n):
+            if par[v] < 0:
+                root = v
+            else:
+                kids[par[v]].append(v)
+        clade = [0] * n
+        order = [root]
+        for v in order:
+            order.extend(kids[v])
+        for v in reversed(order):
+            clade[v] = (1 << v) if v < T else 0
+            for k in kids[v]:
+                clade[v] |= clade[k]
+        full = (1 << T) - 1
+        where = {}
+        for e in range(self.n_edges):
+            m = int(sum(1 << int(t) for t in np.flatnonzero(split[e])))
+            where[m] = where[full ^ m] = e
+        placed, used = {}, set()
+        for v in order:
+            e = where.get(clade[v])
+            if v >= T and e is not None and e not in used:
+                placed[v] = e
+                used.add(e)
+
+        def name(t):
+            s = str(self.names[t])
+            return "'" + s.replace("'", "''") + "'" if any(ch in s for ch in " (),:;[]'") else s
+
+        # children before parents, without recursion (a caterpillar of 4096 taxa is 4095 levels deep)
+        text = {}
+        for v in reversed(order):
+            if v < T:
+                text[v] = name(v) + tip_comment(v)
+                continue
+            s = "(" + ",".join(text.pop(k) for k in kids[v]) + ")"
+            if v in placed:
+                s += edge_comment(placed[v])
+            text[v] = s
+        return text[root] + ";"
+
+
+class Concordance(_TreeAccumulator):
+    """Concordance counters of resolved quartet rows on one fixed tree.
+
+    tree      newick text (tips = taxon numbers, or names through `samples`), or a parent array with `ntaxa`
+    engine    a `QuartetEngine` for device adds (`add_dev`); None: host adds only
+    """
+
+    _prefix = "tq_conc"
+
+    def __init__(self, tree, *, samples=None, ntaxa: int | None = None, min_snps: int = 0, min_ratio: float = 1.0,
+                 engine=None):
+        self.min_snps, self.min_ratio = int(min_snps), float(min_ratio)
+        super().__init__(tree, samples, ntaxa, engine, self.min_snps, self.min_ratio)
+        self._carry = None                         # totals merged from other ranks (`reduce`)
+
+    def reset(self):
+        super().reset()
         self._carry = None
 
     # -- adding rows ------------------------------------------------------------------------------------------
@@ -267,17 +356,10 @@ class Concordance:
     def add_dev(self, quartets, rstat, rscor, flags=None, stream=None):
         """Device rows as torch tensors on the engine's device: quartets int32/uint32 [n,4], rstat int32 [n,2],
         rscor float64 [n,3], flags uint8 [n] or None; enqueued on `stream` (default: the current stream)."""
-        import torch
-        if self.engine is None:
-            raise ValueError("add_dev needs an accumulator created with an engine")
+        self._need_engine()
         n = int(quartets.shape[0]) if quartets.dim() == 2 else int(quartets.numel()) // 4
-        checks = [(quartets, 4, 4), (rstat, 2, 4), (rscor, 3, 8)] + ([(flags, 1, 1)] if flags is not None else [])
-        for t, width, size in checks:
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size or t.numel() != n * width:
-                raise ValueError("device rows must be contiguous GPU tensors of matching shape and dtype")
-        if stream is None:
-            stream = torch.cuda.current_stream(quartets.device)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        rows = [(quartets, 4, 4), (rstat, 2, 4), (rscor, 3, 8)] + ([(flags, 1, 1)] if flags is not None else [])
+        handle = self._dev_stream(rows, n, stream)
         self.add_dev_ptrs(quartets.data_ptr(), rstat.data_ptr(), rscor.data_ptr(),
                           flags.data_ptr() if flags is not None else 0, n, handle)
 
@@ -335,9 +417,7 @@ class Concordance:
 
     def split_masks(self) -> np.ndarray:
         """bool [E, T]: the taxa on one side of each edge."""
-        m = self.raw()["masks"]
-        bits = np.unpackbits(m.view(np.uint8).reshape(self.n_edges, -1), axis=1, bitorder="little")
-        return bits[:, :self.T].astype(bool)
+        return self._mask_bits(self.raw()["masks"])
 
     def stats(self) -> dict:
         """Per edge: split (bool [E,T]), nqrts, conc, disc1, disc2, nu, QC, QD, QI and the means nsnps, weights,
@@ -347,9 +427,8 @@ class Concordance:
         nq, conc, d1, d2, nu, nsn = (c[:, k] for k in range(6))
         induced = conc + d1 + d2 + nu
         qfc, qfd = r["tip_counts"][:, 0], r["tip_counts"][:, 1]
-        bits = np.unpackbits(r["masks"].view(np.uint8).reshape(self.n_edges, -1), axis=1, bitorder="little")
         return dict(
-            split=bits[:, :self.T].astype(bool), nqrts=nq, conc=conc, disc1=d1, disc2=d2, nu=nu,
+            split=self._mask_bits(r["masks"]), nqrts=nq, conc=conc, disc1=d1, disc2=d2, nu=nu,
             QC=np.array([qc(int(a), int(b), int(d)) for a, b, d in zip(conc, d1, d2)], np.float64),
             QD=np.array([qd(int(a), int(b)) for a, b in zip(d1, d2)], np.float64),
             QI=1.0 - _div(nu, induced),
@@ -361,53 +440,12 @@ class Concordance:
         node of each edge (the first node, in preorder, whose clade is one side of the edge), "[&QF=..]" after each
         tip; tips carry their names.  The byte format of toytree's write(features=...) is not reproduced."""
         st = self.stats()
-        T, par = self.T, self.parent
-        n = par.shape[0]
-        kids = [[] for _ in range(n)]
-        root = -1
-        for v in range(n):
-            if par[v] < 0:
-                root = v
-            else:
-                kids[par[v]].append(v)
-        clade = [0] * n
-        order = [root]
-        for v in order:
-            order.extend(kids[v])
-        for v in reversed(order):
-            clade[v] = (1 << v) if v < T else 0
-            for k in kids[v]:
-                clade[v] |= clade[k]
-        full = (1 << T) - 1
-        where = {}
-        for e in range(self.n_edges):
-            m = int(sum(int(b) << t for t, b in enumerate(st["split"][e]) if b))
-            where[m] = where[full ^ m] = e
-        placed, used = {}, set()
-        for v in order:
-            e = where.get(clade[v])
-            if v >= T and e is not None and e not in used:
-                placed[v] = e
-                used.add(e)
 
-        def fmt(x):
-            return ("%.6g" % x) if isinstance(x, float) else str(x)
+        def fmt(k, e):
+            return "%.6g" % float(st[k][e]) if k in ("QC", "QD", "QI", "nsnps", "weights", "scores") else str(int(st[k][e]))
 
-        def name(t):
-            s = str(self.names[t])
-            return "'" + s.replace("'", "''") + "'" if any(ch in s for ch in " (),:;[]'") else s
-
-        def write(v):
-            if v < T:
-                return name(v) + "[&QF=%s]" % fmt(float(st["QF"][v]))
-            s = "(" + ",".join(write(k) for k in kids[v]) + ")"
-            if v in placed:
-                e = placed[v]
-                s += "[&" + ",".join(f"{k}={fmt(float(st[k][e]) if k in ('QC', 'QD', 'QI', 'nsnps', 'weights', 'scores') else int(st[k][e]))}"
-                                     for k in STATS) + "]"
-            return s
-
-        return write(root) + ";"
+        return self._annotated_newick(st["split"], lambda e: "[&" + ",".join(f"{k}={fmt(k, e)}" for k in STATS) + "]",
+                                      lambda t: "[&QF=%.6g]" % float(st["QF"][t]))
 
 
 def run_quartet_concordance(newick_file, qrt_files, min_snps: int = 0, min_ratio: float = 1.0, samples=None,

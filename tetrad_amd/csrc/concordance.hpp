@@ -10,22 +10,27 @@
 //   dep  u16 [N]      edges from the root,
 //   eid  i32 [N]      edge id of an internal non-root node, -1 elsewhere.
 //
-// Row (one function, `conc_row`, on the host and on the device): the three pair sums
+// Geometry (`conc_geometry`, on the host and on the device; the row function of scf.hpp calls it): the three pair sums
 //   s_r = d(pairing r) with d(x, y) = dep[x] + dep[y] - 2 dep[lca(x, y)]
-// give the tree's resolution r of the row (four-point condition: the smallest sum; the two others are equal).
-// The row is induced on an edge iff its internal path is one edge long, (s_other - s_min) / 2 == 1; the edge is
-// the deeper of the two LCAs of the winning pairing.  On a polytomy (all three sums equal) it is induced on none.
-// Scores are rounded to 6 decimals exactly as the TSV reads back (`conc_reread6`, bit-equal to format.hpp's
-// reread6), sorted numerically; weight = (s1 + s2) / 2, score = weight / s0 (0 when s0 == 0).
+// give the tree's resolution r of four taxa (four-point condition: the smallest sum; the two others are equal).
+// They are induced on an edge iff their internal path is one edge long, (s_other - s_min) / 2 == 1; the edge is
+// the deeper of the two LCAs of the winning pairing.  On a polytomy (all three sums equal) they are induced on none.
+// Row (one function, `conc_row`, on the host and on the device): the same geometry, written out in place because
+// the call measured 1-2 % slower per device add (profiles/concordance/README.md), then the scores.  They are rounded
+// to 6 decimals exactly as the TSV reads back (`conc_reread6`, bit-equal to format.hpp's reread6) and sorted
+// numerically; weight = (s1 + s2) / 2, score = weight / s0 (0 when s0 == 0).
 //
 // Device layout: `tq_conc_kernel` strides over the rows with per-workgroup counters in LDS (u32 class counts,
 // u64 nsnps sum, f64 weight / score sums, u32 QFc / QFd per taxon), the LCA table in LDS up to T = 256 and read
-// through L2 above.  Each workgroup writes its counters to its own slab; `tq_conc_fold_kernel` adds the slabs in
-// fixed workgroup order to the u64 / f64 totals.  No float atomic touches global memory.
+// through L2 above (`ConcTables`, shared with scf.hpp).  Each workgroup writes its counters to its own slab;
+// `tq_conc_fold_kernel` (also the fold of scf.hpp) adds the slabs in fixed workgroup order to the u64 / f64 totals.
+// No float atomic touches global memory.
 #pragma once
 
 constexpr int CONC_T_MAX = 4096;            // u16 LCA table of T * T entries: 32 MiB at the limit
-constexpr int CONC_THREADS = 256;
+constexpr int CONC_THREADS = 256;           // of every kernel here and in scf.hpp
+constexpr int CONC_T_LDS_A = 128;           // LCA table in LDS, small form:  32 KiB table
+constexpr int CONC_T_LDS_B = 256;           // LCA table in LDS, large form: 128 KiB table
 constexpr int CONC_EDGE_WORDS = 7;          // per edge: conc, disc1, disc2, nu, nsnps sum (u64), weight sum, score sum (f64)
 constexpr int CONC_EDGE_TILE = 2048;        // edges per pass of the global-table kernel (LDS counters of one pass)
 constexpr int64_t CONC_ROWS_PER_LAUNCH = int64_t(1) << 31;   // keeps every u32 LDS counter of a workgroup below 2^32
@@ -195,6 +200,31 @@ __host__ __device__ __forceinline__ double conc_reread6(double x)
     return x < 0 ? -v : v;
 }
 
+// Four taxa against the tree.  Returns -1 (a taxon >= T or a repeated taxon), 0 (induced on no edge) or 1: the tree
+// resolves them as pairing `r` (0 = ab|cd, 1 = ac|bd, 2 = ad|bc) and they are induced on edge `edge`.  What a new
+// statistic on a fixed tree calls; `conc_row` below holds the same lines in place (see the head of this file).
+template <class LCA, class DEP, class EID>
+__host__ __device__ __forceinline__ int conc_geometry(const LCA *lca, const DEP *dep, const EID *eid, uint32_t T, uint32_t a,
+                                                      uint32_t b, uint32_t c, uint32_t d, int &r, int &edge)
+{
+    if (a >= T || b >= T || c >= T || d >= T) return -1;
+    if (a == b || a == c || a == d || b == c || b == d || c == d) return -1;
+    const uint32_t lab = lca[a * T + b], lcd = lca[c * T + d], lac = lca[a * T + c], lbd = lca[b * T + d],
+                   lad = lca[a * T + d], lbc = lca[b * T + c];
+    const int dsum = (int)dep[a] + (int)dep[b] + (int)dep[c] + (int)dep[d];
+    const int s0 = dsum - 2 * ((int)dep[lab] + (int)dep[lcd]);
+    const int s1 = dsum - 2 * ((int)dep[lac] + (int)dep[lbd]);
+    const int s2 = dsum - 2 * ((int)dep[lad] + (int)dep[lbc]);
+    int l1, l2, smin, sother;
+    if (s0 < s1 && s0 < s2) { r = 0; l1 = lab; l2 = lcd; smin = s0; sother = s1; }
+    else if (s1 < s0 && s1 < s2) { r = 1; l1 = lac; l2 = lbd; smin = s1; sother = s0; }
+    else if (s2 < s0 && s2 < s1) { r = 2; l1 = lad; l2 = lbc; smin = s2; sother = s0; }
+    else return 0;                               // star: the four taxa meet at one node
+    if (sother - smin != 2) return 0;            // internal path longer than one edge
+    edge = (int)eid[dep[l1] > dep[l2] ? l1 : l2];
+    return 1;
+}
+
 // One row against the tree.  Returns -1 (not counted: taxon >= T, repeated taxon, topology > 2, or flags
 // TQ_FLAG_BAD_INDEX / TQ_FLAG_INVALID_DIAGNOSTIC), 0 (induced on no edge) or 1: induced on edge `edge`, counted
 // in class `cls` (CW_CONC / CW_DISC1 / CW_DISC2 / CW_NU) with its weight and score.  `min_snps` >= 1.
@@ -250,14 +280,30 @@ struct ConcArgs {
     int64_t words;              // 7 E + 2 T + 1
 };
 
-// LDS_TABLE: lca / dep / eid copied to LDS (T <= TMAX); otherwise read from global memory through L2.
+// The tree tables of a workgroup: with LDS_TABLE, lca / dep / eid copied to LDS (T <= TMAX); otherwise nothing, and
+// the kernel reads them from global memory through L2.  Declared `__shared__` by tq_conc_kernel and tq_scf_kernel.
+template <bool LDS_TABLE, int TMAX>
+struct ConcTables {
+    uint16_t lca[LDS_TABLE ? TMAX * TMAX : 1];
+    uint16_t dep[LDS_TABLE ? 2 * TMAX : 1];
+    int16_t eid[LDS_TABLE ? 2 * TMAX : 1];
+    // every thread of the workgroup calls it; the caller's __syncthreads() follows
+    __device__ __forceinline__ void load(const uint16_t *g_lca, const uint16_t *g_dep, const int32_t *g_eid, int T, int N)
+    {
+        const int tid = threadIdx.x;
+        const uint32_t *src = (const uint32_t *)g_lca;           // T * T is even (T >= 4)
+        uint32_t *dst = (uint32_t *)lca;
+        for (int i = tid; i < T * T / 2; i += CONC_THREADS) dst[i] = src[i];
+        for (int i = tid; i < N; i += CONC_THREADS) { dep[i] = g_dep[i]; eid[i] = (int16_t)g_eid[i]; }
+    }
+};
+
+// LDS_TABLE, TMAX: see ConcTables.
 // EMAX: edges per pass; QF counters for TMAX taxa.
 template <bool LDS_TABLE, int TMAX, int EMAX>
 __global__ __launch_bounds__(CONC_THREADS) void tq_conc_kernel(ConcArgs a)
 {
-    __shared__ uint16_t s_lca[LDS_TABLE ? TMAX * TMAX : 1];
-    __shared__ uint16_t s_dep[LDS_TABLE ? 2 * TMAX : 1];
-    __shared__ int16_t s_eid[LDS_TABLE ? 2 * TMAX : 1];
+    __shared__ ConcTables<LDS_TABLE, TMAX> s_tab;
     __shared__ uint32_t s_cnt[EMAX * 4];
     __shared__ unsigned long long s_nsn[EMAX];
     __shared__ double s_ws[EMAX * 2];
@@ -265,12 +311,7 @@ __global__ __launch_bounds__(CONC_THREADS) void tq_conc_kernel(ConcArgs a)
     __shared__ uint32_t s_skip;
     const int tid = threadIdx.x;
     const int T = a.T;
-    if (LDS_TABLE) {
-        const uint32_t *src = (const uint32_t *)a.lca;           // T * T is even (T >= 4)
-        uint32_t *dst = (uint32_t *)s_lca;
-        for (int i = tid; i < T * T / 2; i += CONC_THREADS) dst[i] = src[i];
-        for (int i = tid; i < a.N; i += CONC_THREADS) { s_dep[i] = a.dep[i]; s_eid[i] = (int16_t)a.eid[i]; }
-    }
+    if (LDS_TABLE) s_tab.load(a.lca, a.dep, a.eid, T, a.N);
     for (int i = tid; i < a.e_n * 4; i += CONC_THREADS) s_cnt[i] = 0;
     for (int i = tid; i < a.e_n; i += CONC_THREADS) { s_nsn[i] = 0; s_ws[2 * i] = 0.0; s_ws[2 * i + 1] = 0.0; }
     for (int i = tid; i < 2 * T; i += CONC_THREADS) s_qf[i] = 0;
@@ -287,8 +328,8 @@ __global__ __launch_bounds__(CONC_THREADS) void tq_conc_kernel(ConcArgs a)
         int edge = -1, cls = 0;
         double w = 0.0, s = 0.0;
         const int res = LDS_TABLE
-            ? conc_row(s_lca, s_dep, s_eid, (uint32_t)T, a.min_snps, a.min_ratio, q.x, q.y, q.z, q.w, st.x, st.y, x0, x1,
-                       x2, fl, edge, cls, w, s)
+            ? conc_row(s_tab.lca, s_tab.dep, s_tab.eid, (uint32_t)T, a.min_snps, a.min_ratio, q.x, q.y, q.z, q.w, st.x, st.y,
+                       x0, x1, x2, fl, edge, cls, w, s)
             : conc_row(a.lca, a.dep, a.eid, (uint32_t)T, a.min_snps, a.min_ratio, q.x, q.y, q.z, q.w, st.x, st.y, x0, x1,
                        x2, fl, edge, cls, w, s);
         if (res < 0) {
@@ -330,13 +371,14 @@ __global__ __launch_bounds__(CONC_THREADS) void tq_conc_kernel(ConcArgs a)
     }
 }
 
-// totals[i] += slab[0][i] + slab[1][i] + ... in workgroup order (f64 for the weight / score words, u64 otherwise)
-__global__ __launch_bounds__(CONC_THREADS) void tq_conc_fold_kernel(const uint64_t *slab, int nslab, int64_t words, int32_t E,
-                                                                    uint64_t *totals)
+// totals[i] += slab[0][i] + slab[1][i] + ... in workgroup order: f64 for the weight / score words of the first
+// `f64_edges` records of CONC_EDGE_WORDS words (the concordance edges; scf.hpp passes 0), u64 otherwise
+__global__ __launch_bounds__(CONC_THREADS) void tq_conc_fold_kernel(const uint64_t *slab, int nslab, int64_t words,
+                                                                    int32_t f64_edges, uint64_t *totals)
 {
     const int64_t i = (int64_t)blockIdx.x * CONC_THREADS + threadIdx.x;
     if (i >= words) return;
-    const bool is_f64 = i < (int64_t)E * CONC_EDGE_WORDS && (i % CONC_EDGE_WORDS) >= CW_WEIGHT;
+    const bool is_f64 = i < (int64_t)f64_edges * CONC_EDGE_WORDS && (i % CONC_EDGE_WORDS) >= CW_WEIGHT;
     if (is_f64) {
         double s = __longlong_as_double((long long)totals[i]);
         for (int w = 0; w < nslab; ++w) s += __longlong_as_double((long long)slab[(int64_t)w * words + i]);

@@ -31,7 +31,7 @@
 //   jacobi.hpp    tq_svd_kernel: one-sided Jacobi singular values in registers (alternative)
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
 //   concordance.hpp tq_conc_kernel + tq_conc_fold_kernel: quartet concordance counters of resolved rows on a fixed tree
-//   scf.hpp         tq_scf_kernel + tq_scf_fold_kernel: site concordance sums of class rows on a fixed tree
+//   scf.hpp         tq_scf_kernel (tables, geometry and fold of concordance.hpp): site concordance sums of class rows
 //   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
 //   fit.hpp       tq_fit_*_kernel: LCA-depth tables of candidate trees, quartet fit of the supertree's kept rows against them
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
@@ -1522,149 +1522,176 @@ int patterns_dev(tq_ctx *ctx, const char *who, const uint32_t *d_sets, int64_t Q
 }
 
 // ---------------------------------------------------------------------------------------------
-// Concordance accumulator (concordance.hpp): device totals u64 [words] = per edge {conc, disc1, disc2, nu, nsnps sum,
-// weight sum (f64 bits), score sum (f64 bits)}, per taxon {QFc, QFd}, skipped rows; host totals of tq_conc_add beside.
+// Accumulators on a fixed tree: concordance (concordance.hpp; device totals u64 [7 E + 2 T + 1] = per edge {conc,
+// disc1, disc2, nu, nsnps sum, weight sum (f64 bits), score sum (f64 bits)}, per taxon {QFc, QFd}, skipped rows) and
+// site concordance (scf.hpp; u64 [8 E + 1] = per edge {nq, nq_zero, sum conc / d1 / d2, fx conc / d1 / d2}, skipped
+// rows).  `TreeAcc` is what they share: tree, host totals of tq_*_add, device tables, slabs and totals, every
+// operation but the row kernel and the layout of a read.
 // ---------------------------------------------------------------------------------------------
-}  // namespace
 
-struct tq_conc {
+// The event behind the last device work of an accumulator (its owner creates and destroys `ev`): an enqueue on
+// another stream first waits for it, a read or reset synchronises on it.
+struct StreamOrder {
+    hipEvent_t ev = nullptr;        // recorded behind the last device work
+    bool pending = false;
+    hipStream_t last = nullptr;
+    hipError_t join(hipStream_t st) { return pending && st != last ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
+    hipError_t mark(hipStream_t st)
+    {
+        const hipError_t e = hipEventRecord(ev, st);
+        if (e == hipSuccess) { pending = true; last = st; }
+        return e;
+    }
+    hipError_t sync()
+    {
+        const hipError_t e = pending ? hipEventSynchronize(ev) : hipSuccess;
+        if (e == hipSuccess) pending = false;
+        return e;
+    }
+};
+
+struct TreeAcc {
     tq_ctx *ctx = nullptr;          // device adds need one; messages go to tq_last_error(ctx)
     ConcTree t;
-    uint32_t min_snps = 1;
-    double min_ratio = 1.0;
     int64_t words = 0;
     std::vector<uint64_t> hi;       // host adds: integer words
-    std::vector<double> hf;         // host adds: weight / score sums
     uint16_t *d_lca = nullptr, *d_dep = nullptr;
     int32_t *d_eid = nullptr;
     uint64_t *d_slab = nullptr, *d_tot = nullptr;
     int gmax = 0;                   // workgroups the slab holds
     int num_cu = 0;
-    hipEvent_t ev = nullptr;        // recorded behind the last device add
-    bool pending = false;
-    hipStream_t last = nullptr;
+    StreamOrder order;              // of the device adds
+    TreeAcc() = default;
+    TreeAcc(const TreeAcc &) = delete;
+    ~TreeAcc()
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)order.sync();
+        void *dev[] = {d_lca, d_dep, d_eid, d_slab, d_tot};
+        for (void *p : dev)
+            if (p) (void)hipFree(p);
+        if (order.ev) (void)hipEventDestroy(order.ev);
+    }
 };
+
+}  // namespace
+
+struct tq_conc : TreeAcc {
+    uint32_t min_snps = 1;
+    double min_ratio = 1.0;
+    std::vector<double> hf;         // host adds: weight / score sums
+};
+
+struct tq_scf : TreeAcc {};
 
 namespace {
 
-void conc_free_dev(tq_conc *a)
+// The tree, host totals of edge_words * E + tail_words words and, with a context, the device side.  `who` names the
+// calling function in the messages.  After a failure the caller deletes the accumulator.
+int tree_acc_init(TreeAcc *acc, const char *who, const int32_t *parent, int64_t n_nodes, int64_t T, int edge_words,
+                  int64_t tail_words, tq_ctx *ctx)
 {
-    if (a->d_lca) (void)hipFree(a->d_lca);
-    if (a->d_dep) (void)hipFree(a->d_dep);
-    if (a->d_eid) (void)hipFree(a->d_eid);
-    if (a->d_slab) (void)hipFree(a->d_slab);
-    if (a->d_tot) (void)hipFree(a->d_tot);
-    if (a->ev) (void)hipEventDestroy(a->ev);
+    try {
+        const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
+        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: %s", who, err.c_str());
+        acc->words = (int64_t)acc->t.E * edge_words + tail_words;
+        acc->hi.assign(acc->words, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "%s: out of host memory", who);
+    }
+    if (!ctx) return TQ_OK;
+    const ConcTree &t = acc->t;
+    acc->ctx = ctx;
+    acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+    acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_lca, (size_t)T * T * 2);
+    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_dep, (size_t)t.N * 2);
+    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_eid, (size_t)t.N * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_slab, (size_t)acc->gmax * acc->words * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_tot, (size_t)acc->words * 8);
+    if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->order.ev, hipEventDisableTiming);
+    if (e != hipSuccess)
+        return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return TQ_OK;
 }
 
-int conc_launch(tq_conc *acc, const uint32_t *dq, const uint32_t *drs, const double *dsc, const uint8_t *dfl, int64_t n,
-                hipStream_t stream)
+int tree_acc_wait(TreeAcc *acc)
+{
+    if (!acc->order.pending) return TQ_OK;
+    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+    TQ_HIP(acc->ctx, acc->order.sync());
+    return TQ_OK;
+}
+
+int tree_acc_reset(TreeAcc *acc)
+{
+    std::fill(acc->hi.begin(), acc->hi.end(), 0);
+    if (acc->ctx) {
+        if (int rc = tree_acc_wait(acc)) return rc;
+        TQ_HIP(acc->ctx, hipMemset(acc->d_tot, 0, (size_t)acc->words * 8));
+    }
+    return TQ_OK;
+}
+
+int tree_acc_shape(const TreeAcc *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->t.T;
+    if (n_edges) *n_edges = acc->t.E;
+    if (mask_words) *mask_words = acc->t.W;
+    return TQ_OK;
+}
+
+// waits for the device adds and copies their totals to `dv` (zeros without a context)
+int tree_acc_read(TreeAcc *acc, const char *who, std::vector<uint64_t> &dv)
+{
+    try {
+        dv.assign(acc->words, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "%s: out of host memory", who);
+    }
+    if (acc->ctx) {
+        if (int rc = tree_acc_wait(acc)) return rc;
+        TQ_HIP(acc->ctx, hipMemcpy(dv.data(), acc->d_tot, (size_t)acc->words * 8, hipMemcpyDeviceToHost));
+    }
+    return TQ_OK;
+}
+
+// One device add of n > 0 rows on `st`, behind the adds made on other streams.  At most CONC_ROWS_PER_LAUNCH rows go
+// into a launch; `launch(form, G, r0, m, e_lo, e_n, first)` enqueues the caller's row kernel on G workgroups for the m
+// rows from r0 and the edges e_lo .. e_lo + e_n - 1 -- form 0 / 1: tables in LDS for T <= CONC_T_LDS_A / CONC_T_LDS_B
+// and every edge; form 2: tables through L2, a pass per CONC_EDGE_TILE edges, `first` on the first one -- and the fold
+// adds the G slabs to the totals, the first `f64_edges` concordance records with their f64 words.
+template <class Launch>
+int tree_acc_add_dev(TreeAcc *acc, const char *who, int64_t n, int32_t f64_edges, hipStream_t st, Launch launch)
 {
     tq_ctx *ctx = acc->ctx;
     const ConcTree &t = acc->t;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    TQ_HIP(ctx, acc->order.join(st));            // slab / totals in call order
     for (int64_t r0 = 0; r0 < n; r0 += CONC_ROWS_PER_LAUNCH) {
         const int64_t m = std::min<int64_t>(CONC_ROWS_PER_LAUNCH, n - r0);
         const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(m + 4095) / 4096, (int64_t)acc->num_cu, (int64_t)acc->gmax}));
-        ConcArgs a{dq + 4 * r0, drs + 2 * r0, dsc + 3 * r0, dfl ? dfl + r0 : nullptr, m, acc->d_lca, acc->d_dep, acc->d_eid,
-                   t.T, t.N, t.E, acc->min_snps, acc->min_ratio, 0, t.E, 1, acc->d_slab, acc->words};
-        if (t.T <= 128) {
-            hipLaunchKernelGGL((tq_conc_kernel<true, 128, 128>), dim3(G), dim3(CONC_THREADS), 0, stream, a);
-        } else if (t.T <= 256) {
-            hipLaunchKernelGGL((tq_conc_kernel<true, 256, 256>), dim3(G), dim3(CONC_THREADS), 0, stream, a);
+        if (t.T <= CONC_T_LDS_A) {
+            launch(0, G, r0, m, 0, t.E, 1);
+        } else if (t.T <= CONC_T_LDS_B) {
+            launch(1, G, r0, m, 0, t.E, 1);
         } else {
-            for (int32_t e0 = 0; e0 < t.E || e0 == 0; e0 += CONC_EDGE_TILE) {      // a pass per tile of edges
-                a.e_lo = e0;
-                a.e_n = std::min<int32_t>(CONC_EDGE_TILE, t.E - e0);
-                a.tips = e0 == 0;
-                hipLaunchKernelGGL((tq_conc_kernel<false, CONC_T_MAX, CONC_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0,
-                                   stream, a);
-            }
+            for (int32_t e0 = 0; e0 < t.E || e0 == 0; e0 += CONC_EDGE_TILE)       // a pass per tile of edges
+                launch(2, G, r0, m, e0, std::min<int32_t>(CONC_EDGE_TILE, t.E - e0), e0 == 0);
         }
         hipLaunchKernelGGL(tq_conc_fold_kernel, dim3((unsigned)((acc->words + CONC_THREADS - 1) / CONC_THREADS)),
-                           dim3(CONC_THREADS), 0, stream, (const uint64_t *)acc->d_slab, G, acc->words, t.E, acc->d_tot);
+                           dim3(CONC_THREADS), 0, st, (const uint64_t *)acc->d_slab, G, acc->words, f64_edges, acc->d_tot);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_conc_add_dev: launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
     }
-    return TQ_OK;
-}
-
-int conc_wait(tq_conc *acc)
-{
-    if (!acc->pending) return TQ_OK;
-    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-    TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
-    acc->pending = false;
-    return TQ_OK;
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------------------------
-// Site concordance accumulator (scf.hpp): device totals u64 [8 E + 1] = per edge {nq, nq_zero, sum conc / d1 / d2,
-// fx conc / d1 / d2}, skipped rows; host totals of tq_scf_add beside.
-// ---------------------------------------------------------------------------------------------
-struct tq_scf {
-    tq_ctx *ctx = nullptr;          // device adds need one; messages go to tq_last_error(ctx)
-    ConcTree t;
-    int64_t words = 0;
-    std::vector<uint64_t> hi;       // host adds
-    uint16_t *d_lca = nullptr, *d_dep = nullptr;
-    int32_t *d_eid = nullptr;
-    uint64_t *d_slab = nullptr, *d_tot = nullptr;
-    int gmax = 0;                   // workgroups the slab holds
-    int num_cu = 0;
-    hipEvent_t ev = nullptr;        // recorded behind the last device add
-    bool pending = false;
-    hipStream_t last = nullptr;
-};
-
-namespace {
-
-void scf_free_dev(tq_scf *a)
-{
-    if (a->d_lca) (void)hipFree(a->d_lca);
-    if (a->d_dep) (void)hipFree(a->d_dep);
-    if (a->d_eid) (void)hipFree(a->d_eid);
-    if (a->d_slab) (void)hipFree(a->d_slab);
-    if (a->d_tot) (void)hipFree(a->d_tot);
-    if (a->ev) (void)hipEventDestroy(a->ev);
-}
-
-int scf_launch(tq_scf *acc, const uint32_t *dsets, const uint32_t *dcls, int64_t n, hipStream_t stream)
-{
-    tq_ctx *ctx = acc->ctx;
-    const ConcTree &t = acc->t;
-    for (int64_t r0 = 0; r0 < n; r0 += SCF_ROWS_PER_LAUNCH) {
-        const int64_t m = std::min<int64_t>(SCF_ROWS_PER_LAUNCH, n - r0);
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(m + 4095) / 4096, (int64_t)acc->num_cu, (int64_t)acc->gmax}));
-        ScfArgs a{dsets + 4 * r0, dcls + 16 * r0, m, acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, 0, t.E, 1, acc->d_slab,
-                  acc->words};
-        if (t.T <= SCF_T_LDS_A) {
-            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_A, SCF_T_LDS_A>), dim3(G), dim3(SCF_THREADS), 0, stream, a);
-        } else if (t.T <= SCF_T_LDS_B) {
-            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_B, SCF_T_LDS_B>), dim3(G), dim3(SCF_THREADS), 0, stream, a);
-        } else {
-            for (int32_t e0 = 0; e0 < t.E || e0 == 0; e0 += SCF_EDGE_TILE) {       // a pass per tile of edges
-                a.e_lo = e0;
-                a.e_n = std::min<int32_t>(SCF_EDGE_TILE, t.E - e0);
-                a.first = e0 == 0;
-                hipLaunchKernelGGL((tq_scf_kernel<false, CONC_T_MAX, SCF_EDGE_TILE>), dim3(G), dim3(SCF_THREADS), 0, stream, a);
-            }
-        }
-        hipLaunchKernelGGL(tq_scf_fold_kernel, dim3((unsigned)((acc->words + SCF_THREADS - 1) / SCF_THREADS)),
-                           dim3(SCF_THREADS), 0, stream, (const uint64_t *)acc->d_slab, G, acc->words, acc->d_tot);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_scf_add_dev: launch failed: %s", hipGetErrorString(e));
-    }
-    return TQ_OK;
-}
-
-int scf_wait(tq_scf *acc)
-{
-    if (!acc->pending) return TQ_OK;
-    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-    TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
-    acc->pending = false;
+    TQ_HIP(ctx, acc->order.mark(st));
     return TQ_OK;
 }
 
@@ -1692,9 +1719,7 @@ struct tq_cons {
     unsigned long long *d_slot_key = nullptr, *d_count = nullptr;
     unsigned int *d_ctr = nullptr, *p_ctr = nullptr;
     uint32_t *d_unres = nullptr;
-    hipEvent_t ev = nullptr;        // recorded behind the last chunk
-    bool pending = false;
-    hipStream_t last = nullptr;
+    StreamOrder order;              // behind the last chunk
     int64_t dev_entries = 0;        // entries of the device table after the last finished chunk
     int64_t chunks = 0, unresolved = 0;
 };
@@ -1710,7 +1735,7 @@ void cons_free_dev(tq_cons *a)
     void *pin[] = {a->p_trees, a->p_gather, a->p_ctr};
     for (void *p : pin)
         if (p) (void)hipHostFree(p);
-    if (a->ev) (void)hipEventDestroy(a->ev);
+    if (a->order.ev) (void)hipEventDestroy(a->order.ev);
 }
 
 int cons_overflow(tq_cons *a, const char *who)
@@ -1746,11 +1771,10 @@ int cons_clear_dev(tq_cons *a)
 // Waits for the last chunk, reads its counters and counts its unresolved splits in the host map.
 int cons_drain(tq_cons *a)
 {
-    if (!a->pending) return TQ_OK;
+    if (!a->order.pending) return TQ_OK;
     tq_ctx *ctx = a->ctx;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
-    TQ_HIP(ctx, hipEventSynchronize(a->ev));
-    a->pending = false;
+    TQ_HIP(ctx, a->order.sync());
     a->dev_entries = std::min<int64_t>((int64_t)a->p_ctr[CONS_CTR_CLAIMS], a->max_splits);
     if (a->p_ctr[CONS_CTR_OVERFLOW]) return cons_overflow(a, "tq_cons");
     const int64_t nun = (int64_t)a->p_ctr[CONS_CTR_UNRES];
@@ -1758,11 +1782,11 @@ int cons_drain(tq_cons *a)
     for (int64_t first = 0; first < nun; first += a->gather_cap) {
         const int64_t n = std::min<int64_t>(a->gather_cap, nun - first);
         hipLaunchKernelGGL(tq_cons_gather_kernel, dim3((unsigned)((n * a->W + CONS_THREADS - 1) / CONS_THREADS)),
-                           dim3(CONS_THREADS), 0, a->last, (const uint32_t *)a->d_unres, first, n,
+                           dim3(CONS_THREADS), 0, a->order.last, (const uint32_t *)a->d_unres, first, n,
                            (const uint64_t *)a->d_masks, a->W, a->d_gather);
         TQ_HIP(ctx, hipGetLastError());
-        TQ_HIP(ctx, hipMemcpyAsync(a->p_gather, a->d_gather, (size_t)n * a->W * 8, hipMemcpyDeviceToHost, a->last));
-        TQ_HIP(ctx, hipStreamSynchronize(a->last));
+        TQ_HIP(ctx, hipMemcpyAsync(a->p_gather, a->d_gather, (size_t)n * a->W * 8, hipMemcpyDeviceToHost, a->order.last));
+        TQ_HIP(ctx, hipStreamSynchronize(a->order.last));
         for (int64_t e = 0; e < n; ++e) {
             m.assign(a->p_gather + e * a->W, a->p_gather + (e + 1) * a->W);
             ++a->host[m];
@@ -1787,9 +1811,7 @@ int cons_launch(tq_cons *a, int64_t ntrees, hipStream_t st)
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_cons_add: launch failed: %s", hipGetErrorString(e));
     TQ_HIP(ctx, hipMemcpyAsync(a->p_ctr, a->d_ctr, CONS_CTR_WORDS * 4, hipMemcpyDeviceToHost, st));
-    TQ_HIP(ctx, hipEventRecord(a->ev, st));
-    a->pending = true;
-    a->last = st;
+    TQ_HIP(ctx, a->order.mark(st));
     ++a->chunks;
     return TQ_OK;
 }
@@ -1855,9 +1877,7 @@ struct tq_stree {
     unsigned long long *p_cnt = nullptr;
     int64_t max_cells = 0, max_nodes = 0;
     int num_cu = 1;
-    hipEvent_t ev = nullptr;        // recorded behind the last device add
-    bool pending = false;
-    hipStream_t last = nullptr;
+    StreamOrder order;              // behind the last device add
     hipStream_t own = nullptr;      // stream of tq_stree_graph / tq_stree_rows, which take none
     std::vector<StreeLevelStat> stats;   // of the last build
     // quartet fit (fit.hpp): allocated at the first fit, grow-only, freed with the accumulator
@@ -1880,7 +1900,7 @@ void stree_free_dev(tq_stree *a)
     void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt, a->p_side, a->p_cut, a->p_fit_rec, a->p_fit_out};
     for (void *p : pin)
         if (p) (void)hipHostFree(p);
-    if (a->ev) (void)hipEventDestroy(a->ev);
+    if (a->order.ev) (void)hipEventDestroy(a->order.ev);
     if (a->own) (void)hipStreamDestroy(a->own);
 }
 
@@ -2014,7 +2034,7 @@ struct StreeDevBackend : StreeBackend {
 int stree_join(tq_stree *acc, hipStream_t st)
 {
     TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-    if (acc->pending && st != acc->last) TQ_HIP(acc->ctx, hipStreamWaitEvent(st, acc->ev, 0));
+    TQ_HIP(acc->ctx, acc->order.join(st));
     return TQ_OK;
 }
 
@@ -3275,68 +3295,29 @@ int tq_conc_create(tq_conc **out, const int32_t *parent, int64_t n_nodes, int64_
     if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: min_ratio is NaN");
     tq_conc *acc = new (std::nothrow) tq_conc();
     if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
+    acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);   // deviation 2
+    acc->min_ratio = min_ratio;
+    int rc = tree_acc_init(acc, "tq_conc_create", parent, n_nodes, T, CONC_EDGE_WORDS, 2 * T + 1, ctx);
     try {
-        const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
-        if (!err.empty()) {
-            delete acc;
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: %s", err.c_str());
-        }
-        acc->ctx = ctx;
-        acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);   // deviation 2
-        acc->min_ratio = min_ratio;
-        acc->words = (int64_t)acc->t.E * CONC_EDGE_WORDS + 2 * T + 1;
-        acc->hi.assign(acc->words, 0);
-        acc->hf.assign(acc->words, 0.0);
+        if (!rc) acc->hf.assign(acc->words, 0.0);
     } catch (const std::bad_alloc &) {
-        delete acc;
-        return fail(ctx, TQ_ERR_OOM, "tq_conc_create: out of host memory");
+        rc = fail(ctx, TQ_ERR_OOM, "tq_conc_create: out of host memory");
     }
-    if (ctx) {
-        const ConcTree &t = acc->t;
-        acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
-        acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_lca, (size_t)T * T * 2);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_dep, (size_t)t.N * 2);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_eid, (size_t)t.N * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_slab, (size_t)acc->gmax * acc->words * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_tot, (size_t)acc->words * 8);
-        if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            conc_free_dev(acc);
-            delete acc;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_conc_create: %s", hipGetErrorString(e));
-        }
+    if (rc) {
+        delete acc;
+        return rc;
     }
     *out = acc;
     return TQ_OK;
 }
 
-void tq_conc_destroy(tq_conc *acc)
-{
-    if (!acc) return;
-    if (acc->ctx) {
-        (void)hipSetDevice(acc->ctx->device);
-        if (acc->pending) (void)hipEventSynchronize(acc->ev);
-        conc_free_dev(acc);
-    }
-    delete acc;
-}
+void tq_conc_destroy(tq_conc *acc) { delete acc; }
 
 int tq_conc_reset(tq_conc *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    std::fill(acc->hi.begin(), acc->hi.end(), 0);
     std::fill(acc->hf.begin(), acc->hf.end(), 0.0);
-    if (acc->ctx) {
-        if (int rc = conc_wait(acc)) return rc;
-        TQ_HIP(acc->ctx, hipMemset(acc->d_tot, 0, (size_t)acc->words * 8));
-    }
-    return TQ_OK;
+    return tree_acc_reset(acc);
 }
 
 int tq_conc_add(tq_conc *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
@@ -3359,22 +3340,24 @@ int tq_conc_add_dev(tq_conc *acc, const uint32_t *d_quartets, const uint32_t *d_
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: NULL pointer or negative n");
     if (n == 0) return TQ_OK;
     hipStream_t st = (hipStream_t)stream;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (acc->pending && st != acc->last) TQ_HIP(ctx, hipStreamWaitEvent(st, acc->ev, 0));   // slab / totals in call order
-    if (int rc = conc_launch(acc, d_quartets, d_rstat, d_rscor, d_flags, n, st)) return rc;
-    TQ_HIP(ctx, hipEventRecord(acc->ev, st));
-    acc->pending = true;
-    acc->last = st;
-    return TQ_OK;
+    return tree_acc_add_dev(acc, "tq_conc_add_dev", n, acc->t.E, st,
+                            [=](int form, int G, int64_t r0, int64_t m, int32_t e_lo, int32_t e_n, int first) {
+        const ConcTree &t = acc->t;
+        const ConcArgs a{d_quartets + 4 * r0, d_rstat + 2 * r0, d_rscor + 3 * r0, d_flags ? d_flags + r0 : nullptr, m,
+                         acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, acc->min_snps, acc->min_ratio, e_lo, e_n, first,
+                         acc->d_slab, acc->words};
+        if (form == 0)
+            hipLaunchKernelGGL((tq_conc_kernel<true, CONC_T_LDS_A, CONC_T_LDS_A>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+        else if (form == 1)
+            hipLaunchKernelGGL((tq_conc_kernel<true, CONC_T_LDS_B, CONC_T_LDS_B>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+        else
+            hipLaunchKernelGGL((tq_conc_kernel<false, CONC_T_MAX, CONC_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+    });
 }
 
 int tq_conc_shape(const tq_conc *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words)
 {
-    if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->t.T;
-    if (n_edges) *n_edges = acc->t.E;
-    if (mask_words) *mask_words = acc->t.W;
-    return TQ_OK;
+    return tree_acc_shape(acc, T, n_edges, mask_words);
 }
 
 int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t *masks, int64_t *tip_counts,
@@ -3383,15 +3366,7 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
     if (!acc) return TQ_ERR_INVALID_ARG;
     const ConcTree &t = acc->t;
     std::vector<uint64_t> dv;
-    try {
-        dv.assign(acc->words, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_conc_read: out of host memory");
-    }
-    if (acc->ctx) {
-        if (int rc = conc_wait(acc)) return rc;
-        TQ_HIP(acc->ctx, hipMemcpy(dv.data(), acc->d_tot, (size_t)acc->words * 8, hipMemcpyDeviceToHost));
-    }
+    if (int rc = tree_acc_read(acc, "tq_conc_read", dv)) return rc;
     for (int32_t e = 0; e < t.E; ++e) {
         const uint64_t *d = &dv[(size_t)e * CONC_EDGE_WORDS];
         const uint64_t *h = &acc->hi[(size_t)e * CONC_EDGE_WORDS];
@@ -3422,65 +3397,17 @@ int tq_scf_create(tq_scf **out, const int32_t *parent, int64_t n_nodes, int64_t 
     if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: parent is NULL");
     tq_scf *acc = new (std::nothrow) tq_scf();
     if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
-    try {
-        const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
-        if (!err.empty()) {
-            delete acc;
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: %s", err.c_str());
-        }
-        acc->ctx = ctx;
-        acc->words = (int64_t)acc->t.E * SCF_EDGE_WORDS + 1;
-        acc->hi.assign(acc->words, 0);
-    } catch (const std::bad_alloc &) {
+    if (int rc = tree_acc_init(acc, "tq_scf_create", parent, n_nodes, T, SCF_EDGE_WORDS, 1, ctx)) {
         delete acc;
-        return fail(ctx, TQ_ERR_OOM, "tq_scf_create: out of host memory");
-    }
-    if (ctx) {
-        const ConcTree &t = acc->t;
-        acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
-        acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_lca, (size_t)T * T * 2);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_dep, (size_t)t.N * 2);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_eid, (size_t)t.N * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_slab, (size_t)acc->gmax * acc->words * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_tot, (size_t)acc->words * 8);
-        if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            scf_free_dev(acc);
-            delete acc;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_scf_create: %s", hipGetErrorString(e));
-        }
+        return rc;
     }
     *out = acc;
     return TQ_OK;
 }
 
-void tq_scf_destroy(tq_scf *acc)
-{
-    if (!acc) return;
-    if (acc->ctx) {
-        (void)hipSetDevice(acc->ctx->device);
-        if (acc->pending) (void)hipEventSynchronize(acc->ev);
-        scf_free_dev(acc);
-    }
-    delete acc;
-}
+void tq_scf_destroy(tq_scf *acc) { delete acc; }
 
-int tq_scf_reset(tq_scf *acc)
-{
-    if (!acc) return TQ_ERR_INVALID_ARG;
-    std::fill(acc->hi.begin(), acc->hi.end(), 0);
-    if (acc->ctx) {
-        if (int rc = scf_wait(acc)) return rc;
-        TQ_HIP(acc->ctx, hipMemset(acc->d_tot, 0, (size_t)acc->words * 8));
-    }
-    return TQ_OK;
-}
+int tq_scf_reset(tq_scf *acc) { return acc ? tree_acc_reset(acc) : TQ_ERR_INVALID_ARG; }
 
 int tq_scf_add(tq_scf *acc, const uint32_t *sets, const uint32_t *classes, int64_t n)
 {
@@ -3502,22 +3429,23 @@ int tq_scf_add_dev(tq_scf *acc, const uint32_t *d_sets, const uint32_t *d_classe
     if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // sets are read as 16-byte words
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: d_sets and d_classes must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (acc->pending && st != acc->last) TQ_HIP(ctx, hipStreamWaitEvent(st, acc->ev, 0));   // slab / totals in call order
-    if (int rc = scf_launch(acc, d_sets, d_classes, n, st)) return rc;
-    TQ_HIP(ctx, hipEventRecord(acc->ev, st));
-    acc->pending = true;
-    acc->last = st;
-    return TQ_OK;
+    return tree_acc_add_dev(acc, "tq_scf_add_dev", n, 0, st,
+                            [=](int form, int G, int64_t r0, int64_t m, int32_t e_lo, int32_t e_n, int first) {
+        const ConcTree &t = acc->t;
+        const ScfArgs a{d_sets + 4 * r0, d_classes + 16 * r0, m, acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, e_lo, e_n,
+                        first, acc->d_slab, acc->words};
+        if (form == 0)
+            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_A, SCF_T_LDS_A>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+        else if (form == 1)
+            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_B, SCF_T_LDS_B>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+        else
+            hipLaunchKernelGGL((tq_scf_kernel<false, CONC_T_MAX, SCF_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+    });
 }
 
 int tq_scf_shape(const tq_scf *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words)
 {
-    if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->t.T;
-    if (n_edges) *n_edges = acc->t.E;
-    if (mask_words) *mask_words = acc->t.W;
-    return TQ_OK;
+    return tree_acc_shape(acc, T, n_edges, mask_words);
 }
 
 int tq_scf_read(tq_scf *acc, int64_t *edge_counts, uint64_t *masks, int64_t *skipped)
@@ -3525,15 +3453,7 @@ int tq_scf_read(tq_scf *acc, int64_t *edge_counts, uint64_t *masks, int64_t *ski
     if (!acc) return TQ_ERR_INVALID_ARG;
     const ConcTree &t = acc->t;
     std::vector<uint64_t> dv;
-    try {
-        dv.assign(acc->words, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_scf_read: out of host memory");
-    }
-    if (acc->ctx) {
-        if (int rc = scf_wait(acc)) return rc;
-        TQ_HIP(acc->ctx, hipMemcpy(dv.data(), acc->d_tot, (size_t)acc->words * 8, hipMemcpyDeviceToHost));
-    }
+    if (int rc = tree_acc_read(acc, "tq_scf_read", dv)) return rc;
     const int64_t eb = (int64_t)t.E * SCF_EDGE_WORDS;
     if (edge_counts)
         for (int64_t i = 0; i < eb; ++i) edge_counts[i] = (int64_t)(dv[i] + acc->hi[i]);
@@ -3589,7 +3509,7 @@ int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int we
         if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_side, (size_t)acc->max_nodes * 3, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_cut, (size_t)acc->max_nodes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMemset(acc->d_cnt, 0, SC_WORDS * 8);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->order.ev, hipEventDisableTiming);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking);
         if (e != hipSuccess) {
             stree_free_dev(acc);
@@ -3606,7 +3526,7 @@ void tq_stree_destroy(tq_stree *acc)
     if (!acc) return;
     if (acc->ctx) {
         (void)hipSetDevice(acc->ctx->device);
-        if (acc->pending) (void)hipEventSynchronize(acc->ev);
+        (void)acc->order.sync();
         stree_free_dev(acc);
     }
     delete acc;
@@ -3623,8 +3543,7 @@ int tq_stree_reset(tq_stree *acc)
     acc->mode = 0;
     if (acc->ctx) {
         TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        if (acc->pending) TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
-        acc->pending = false;
+        TQ_HIP(acc->ctx, acc->order.sync());
         TQ_HIP(acc->ctx, hipMemsetAsync(acc->d_cnt, 0, SC_WORDS * 8, acc->own));   // not the null stream: it would wait
         TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));                           // for every other stream's work
     }
@@ -3687,9 +3606,7 @@ int tq_stree_add_dev(tq_stree *acc, const uint32_t *d_quartets, const uint32_t *
                        st, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_stree_add_dev: launch failed: %s", hipGetErrorString(e));
-    TQ_HIP(ctx, hipEventRecord(acc->ev, st));
-    acc->pending = true;
-    acc->last = st;
+    TQ_HIP(ctx, acc->order.mark(st));
     acc->mode = 2;
     acc->rows_in += n;
     return TQ_OK;
@@ -4061,7 +3978,7 @@ int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx)
         if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_trees, (size_t)C * stride * 4, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_gather, (size_t)a->gather_cap * W * 8, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_ctr, CONS_CTR_WORDS * 4, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
         if (e != hipSuccess) {
             cons_free_dev(a);
             delete a;
@@ -4082,7 +3999,7 @@ void tq_cons_destroy(tq_cons *acc)
     if (!acc) return;
     if (acc->ctx) {
         (void)hipSetDevice(acc->ctx->device);
-        if (acc->pending) (void)hipEventSynchronize(acc->ev);
+        (void)acc->order.sync();
         cons_free_dev(acc);
     }
     delete acc;
@@ -4093,8 +4010,7 @@ int tq_cons_reset(tq_cons *acc)
     if (!acc) return TQ_ERR_INVALID_ARG;
     if (acc->ctx) {
         TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        if (acc->pending) TQ_HIP(acc->ctx, hipEventSynchronize(acc->ev));
-        acc->pending = false;
+        TQ_HIP(acc->ctx, acc->order.sync());
         if (int rc = cons_clear_dev(acc)) return rc;
         acc->hash_bits = acc->ctx->cons_hash_bits;
     }

@@ -30,69 +30,24 @@ from typing import Optional
 
 import numpy as np
 
-from .concordance import _div, newick_to_parent
+from .concordance import _TreeAccumulator, _div, newick_to_parent
 
 WORDS = ("nq", "nq_zero", "sum_conc", "sum_d1", "sum_d2", "fx_conc", "fx_d1", "fx_d2")
 FEATURES = ("sCF", "sDF1", "sDF2", "sN", "nq")
 _FX = float(1 << 32)
 
 
-class SiteConcordance:
+class SiteConcordance(_TreeAccumulator):
     """Site concordance sums of class rows on one fixed tree.
 
     tree      newick text (tips = taxon numbers, or names through `samples`), or a parent array with `ntaxa`
     engine    a `QuartetEngine` for device adds (`add_dev`); None: host adds only
     """
 
+    _prefix = "tq_scf"
+
     def __init__(self, tree, *, samples=None, ntaxa: int | None = None, engine=None):
-        from . import _lib
-        self._lib = _lib.load()
-        if isinstance(tree, str):
-            self.newick = tree
-            par, T, names = newick_to_parent(tree, samples)
-        else:
-            if ntaxa is None:
-                raise ValueError("a parent array needs `ntaxa`")
-            self.newick = None
-            par, T, names = np.ascontiguousarray(tree, dtype=np.int32), int(ntaxa), [str(t) for t in range(int(ntaxa))]
-        self.parent, self.T, self.names = par, T, names
-        self.engine = engine                       # kept alive: the accumulator reports through its context
-        ctx = engine._h if engine is not None else None
-        h = ctypes.c_void_p()
-        rc = self._lib.tq_scf_create(ctypes.byref(h), par.ctypes.data, par.shape[0], T, ctx)
-        if rc != 0:
-            raise _lib.TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-        self._h = h
-        t, e, w = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        self._check(self._lib.tq_scf_shape(h, ctypes.byref(t), ctypes.byref(e), ctypes.byref(w)))
-        self.n_edges, self.mask_words = e.value, w.value
-
-    # -- lifecycle ------------------------------------------------------------------------------------------
-    def _check(self, rc: int):
-        if rc != 0:
-            from ._lib import TetradHipError
-            ctx = self.engine._h if self.engine is not None else None
-            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tq_scf_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._check(self._lib.tq_scf_reset(self._h))
+        super().__init__(tree, samples, ntaxa, engine)
 
     # -- adding rows ------------------------------------------------------------------------------------------
     def add(self, sets, classes):
@@ -110,16 +65,9 @@ class SiteConcordance:
     def add_dev(self, sets, classes, stream=None):
         """Device rows as torch tensors on the engine's device: sets int32/uint32 [n,4], classes int32/uint32 [n,16];
         enqueued on `stream` (default: the current stream)."""
-        import torch
-        if self.engine is None:
-            raise ValueError("add_dev needs an accumulator created with an engine")
+        self._need_engine()
         n = int(sets.numel()) // 4
-        for t, width in ((sets, 4), (classes, 16)):
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n * width:
-                raise ValueError("device rows must be contiguous GPU tensors of matching shape and dtype")
-        if stream is None:
-            stream = torch.cuda.current_stream(sets.device)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        handle = self._dev_stream([(sets, 4, 4), (classes, 16, 4)], n, stream)
         self.add_dev_ptrs(sets.data_ptr(), classes.data_ptr(), n, handle)
 
     # -- reading -----------------------------------------------------------------------------------------------
@@ -137,8 +85,7 @@ class SiteConcordance:
         """bool [E, T]: the taxa on one side of each edge (edge order and sides as `Concordance.split_masks`)."""
         m = np.zeros((self.n_edges, self.mask_words), np.uint64)
         self._check(self._lib.tq_scf_read(self._h, None, m.ctypes.data, None))
-        bits = np.unpackbits(m.view(np.uint8).reshape(self.n_edges, -1), axis=1, bitorder="little")
-        return bits[:, :self.T].astype(bool)
+        return self._mask_bits(m)
 
     def stats(self) -> dict:
         """Per edge: split (bool [E,T]), nq, nq_zero, the six sums, sCF / sDF1 / sDF2 (means of the rows' shares, in
@@ -147,8 +94,7 @@ class SiteConcordance:
         r = self.raw()
         c = r["edge_counts"]
         out = {k: c[:, i].copy() for i, k in enumerate(WORDS)}
-        bits = np.unpackbits(r["masks"].view(np.uint8).reshape(self.n_edges, -1), axis=1, bitorder="little")
-        out["split"] = bits[:, :self.T].astype(bool)
+        out["split"] = self._mask_bits(r["masks"])
         nq = out["nq"].astype(np.float64)
         sums = [out[k].astype(np.float64) for k in ("sum_conc", "sum_d1", "sum_d2")]
         total = sums[0] + sums[1] + sums[2]
@@ -164,53 +110,12 @@ class SiteConcordance:
         `Concordance.to_newick`: "[&sCF=..,sDF1=..,sDF2=..,sN=..,nq=..]" after the node of each edge (the first node,
         in preorder, whose clade is one side of the edge); tips carry their names."""
         st = self.stats()
-        T, par = self.T, self.parent
-        n = par.shape[0]
-        kids = [[] for _ in range(n)]
-        root = -1
-        for v in range(n):
-            if par[v] < 0:
-                root = v
-            else:
-                kids[par[v]].append(v)
-        clade = [0] * n
-        order = [root]
-        for v in order:
-            order.extend(kids[v])
-        for v in reversed(order):
-            clade[v] = (1 << v) if v < T else 0
-            for k in kids[v]:
-                clade[v] |= clade[k]
-        full = (1 << T) - 1
-        where = {}
-        for e in range(self.n_edges):
-            m = int(sum(1 << int(t) for t in np.flatnonzero(st["split"][e])))
-            where[m] = where[full ^ m] = e
-        placed, used = {}, set()
-        for v in order:
-            e = where.get(clade[v])
-            if v >= T and e is not None and e not in used:
-                placed[v] = e
-                used.add(e)
-
-        def name(t):
-            s = str(self.names[t])
-            return "'" + s.replace("'", "''") + "'" if any(ch in s for ch in " (),:;[]'") else s
 
         def feature(k, e):
             return f"{k}={int(st[k][e])}" if k == "nq" else f"{k}={'%.6g' % float(st[k][e])}"
 
-        # children before parents, without recursion (a caterpillar of 4096 taxa is 4095 levels deep)
-        text = {}
-        for v in reversed(order):
-            if v < T:
-                text[v] = name(v)
-                continue
-            s = "(" + ",".join(text.pop(k) for k in kids[v]) + ")"
-            if v in placed:
-                s += "[&" + ",".join(feature(k, placed[v]) for k in FEATURES) + "]"
-            text[v] = s
-        return text[root] + ";"
+        return self._annotated_newick(st["split"], lambda e: "[&" + ",".join(feature(k, e) for k in FEATURES) + "]",
+                                      lambda t: "")
 
 
 # -- the quartets around every branch -----------------------------------------------------------------------------

@@ -1,5 +1,8 @@
-/* scf_host_check.c -- the host paths of the site concordance accumulator (tq_scf_create / tq_scf_add / tq_scf_read
- * with a NULL context) driven from a plain C program, meant to be built with the host sanitizers:
+/* scf_host_check.c -- the host paths of the two accumulators on a fixed tree, which share their host code: the site
+ * concordance accumulator (tq_scf_create / tq_scf_add / tq_scf_read with a NULL context) and the
+ * quartet concordance accumulator (tq_conc_create / tq_conc_add / tq_conc_read / tq_conc_reset, section 11, its counts
+ * against a recount from the split masks in this file), driven from a plain C program, meant to be built with the host
+ * sanitizers:
  *
  *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
  *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
@@ -52,6 +55,107 @@ static int64_t random_tree(int32_t T, int32_t *parent)
     }
     free(roots);
     return n;
+}
+
+/* The concordance accumulator on the same tree: `nrows` rows with whole-number scores (their 6-decimal rounding is the
+ * identity, and sums made in row order are bit-equal to the library's) against a recount that knows only the split masks
+ * the library reports: a row is induced on an edge iff that split alone separates its taxa two against two. */
+static void run_conc(int32_t T, int caterpillar, const int32_t *parent, int64_t n_nodes, int64_t nrows)
+{
+    const int64_t min_snps = 3;
+    const double min_ratio = 1.25;
+    tq_conc *acc = NULL;
+    CHECK(tq_conc_create(&acc, parent, n_nodes, T, min_snps, min_ratio, NULL) == TQ_OK && acc);
+    int64_t t = 0, E = 0, W = 0;
+    CHECK(tq_conc_shape(acc, &t, &E, &W) == TQ_OK && t == T && W == (T + 63) / 64);
+    const size_t e1 = (size_t)(E ? E : 1);
+    uint32_t *q = (uint32_t *)malloc(sizeof(uint32_t) * 4 * (size_t)nrows);
+    uint32_t *st = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)nrows);
+    double *sc = (double *)malloc(sizeof(double) * 3 * (size_t)nrows);
+    uint8_t *fl = (uint8_t *)malloc((size_t)nrows);
+    int64_t *counts = (int64_t *)malloc(sizeof(int64_t) * 6 * e1), *want = (int64_t *)calloc(6 * e1, sizeof(int64_t));
+    double *sums = (double *)malloc(sizeof(double) * 2 * e1), *wsum = (double *)calloc(2 * e1, sizeof(double));
+    uint64_t *masks = (uint64_t *)malloc(sizeof(uint64_t) * e1 * (size_t)W);
+    int64_t *tips = (int64_t *)malloc(sizeof(int64_t) * 2 * (size_t)T), *wtips = (int64_t *)calloc(2 * (size_t)T, sizeof(int64_t));
+    CHECK(q && st && sc && fl && counts && want && sums && wsum && masks && tips && wtips);
+    for (int64_t i = 0; i < nrows; ++i) {
+        const int window = caterpillar && T > 8;
+        const uint32_t base = window ? rnd((uint32_t)T - 7) : 0, span = window ? 8 : (uint32_t)T;
+        for (int k = 0; k < 4; ++k) q[4 * i + k] = base + rnd(span);
+        const uint32_t kind = rnd(40);
+        if (kind == 0) q[4 * i + 1] = (uint32_t)T;
+        if (kind == 1) q[4 * i + 2] = q[4 * i];
+        st[2 * i] = kind == 2 ? 3 : rnd(3);
+        st[2 * i + 1] = rnd(12);
+        for (int k = 0; k < 3; ++k) sc[3 * i + k] = rnd(8) ? (double)rnd(400) : 0.0;
+        fl[i] = kind == 3 ? (uint8_t)(1u << rnd(5)) : 0;
+    }
+    const int64_t half = nrows / 2;
+    CHECK(tq_conc_add(acc, q, st, sc, fl, half) == TQ_OK);
+    CHECK(tq_conc_add(acc, q + 4 * half, st + 2 * half, sc + 3 * half, fl + half, nrows - half) == TQ_OK);
+    CHECK(tq_conc_add(acc, NULL, NULL, NULL, NULL, 0) == TQ_OK);
+    CHECK(tq_conc_add(acc, q, NULL, sc, fl, 3) == TQ_ERR_INVALID_ARG);
+    CHECK(tq_conc_add(acc, q, st, sc, fl, -1) == TQ_ERR_INVALID_ARG);
+    CHECK(tq_conc_add_dev(acc, q, st, sc, fl, 1, NULL) == TQ_ERR_INVALID_ARG);
+    CHECK(strstr(tq_last_error(NULL), "tq_conc_add_dev: the accumulator was created without a context"));
+    int64_t skipped = -1, wskipped = 0;
+    CHECK(tq_conc_read(acc, counts, sums, masks, tips, &skipped) == TQ_OK);
+    CHECK(tq_conc_read(acc, NULL, NULL, NULL, NULL, NULL) == TQ_OK);
+    for (int64_t i = 0; i < nrows; ++i) {
+        const uint32_t *r = q + 4 * i;
+        int bad = (fl[i] & (4 | 16)) || st[2 * i] > 2;
+        for (int a = 0; a < 4; ++a) {
+            if (r[a] >= (uint32_t)T) bad = 1;
+            for (int b = a + 1; b < 4; ++b)
+                if (r[a] == r[b]) bad = 1;
+        }
+        if (bad) { ++wskipped; continue; }
+        int64_t edge = -1;
+        int nsep = 0, res = 0;
+        for (int64_t e = 0; e < E; ++e) {
+            int in[4];
+            for (int k = 0; k < 4; ++k) in[k] = (int)(masks[e * W + (r[k] >> 6)] >> (r[k] & 63)) & 1;
+            if (in[0] + in[1] + in[2] + in[3] != 2) continue;
+            ++nsep;
+            edge = e;
+            res = in[0] == in[1] ? 0 : in[0] == in[2] ? 1 : 2;
+        }
+        if (nsep != 1) continue;
+        double y[3] = {sc[3 * i], sc[3 * i + 1], sc[3 * i + 2]}, tmp;
+        if (y[0] > y[1]) { tmp = y[0]; y[0] = y[1]; y[1] = tmp; }
+        if (y[1] > y[2]) { tmp = y[1]; y[1] = y[2]; y[2] = tmp; }
+        if (y[0] > y[1]) { tmp = y[0]; y[0] = y[1]; y[1] = tmp; }
+        const double weight = (y[1] + y[2]) / 2.0, score = y[0] == 0.0 ? 0.0 : weight / y[0];
+        const int topo = (int)st[2 * i], lower = res == 0 ? 1 : 0;
+        const int informative = !(score < min_ratio || (int64_t)st[2 * i + 1] < min_snps);
+        const int cls = !informative ? 4 : topo == res ? 1 : topo == lower ? 2 : 3;    /* conc, disc1, disc2, nu */
+        want[6 * edge + cls] += 1;
+        want[6 * edge + 5] += st[2 * i + 1];
+        wsum[2 * edge] += weight;
+        wsum[2 * edge + 1] += score;
+        if (informative)
+            for (int k = 0; k < 4; ++k) wtips[2 * r[k] + (cls == 1 ? 0 : 1)] += 1;
+    }
+    CHECK(skipped == wskipped);
+    int64_t induced = 0;
+    for (int64_t e = 0; e < E; ++e) {
+        CHECK(counts[6 * e] > 0);                                  /* nqrts: every edge induces some quartet */
+        for (int k = 1; k < 6; ++k) CHECK(counts[6 * e + k] == want[6 * e + k]);
+        CHECK(memcmp(&sums[2 * e], &wsum[2 * e], 2 * sizeof(double)) == 0);
+        induced += counts[6 * e + 1] + counts[6 * e + 2] + counts[6 * e + 3] + counts[6 * e + 4];
+    }
+    for (int64_t i = 0; i < 2 * (int64_t)T; ++i) CHECK(tips[i] == wtips[i]);
+    if (E) CHECK(induced > 0);
+    CHECK(tq_conc_reset(acc) == TQ_OK);
+    CHECK(tq_conc_read(acc, counts, sums, NULL, tips, &skipped) == TQ_OK && skipped == 0);
+    for (int64_t e = 0; e < E; ++e) {
+        for (int k = 1; k < 6; ++k) CHECK(counts[6 * e + k] == 0);
+        CHECK(sums[2 * e] == 0.0 && sums[2 * e + 1] == 0.0);
+    }
+    for (int64_t i = 0; i < 2 * (int64_t)T; ++i) CHECK(tips[i] == 0);
+    tq_conc_destroy(acc);
+    free(wtips); free(tips); free(masks); free(wsum); free(sums); free(want); free(counts);
+    free(fl); free(sc); free(st); free(q);
 }
 
 static void run(int32_t T, int caterpillar, int64_t nrows)
@@ -137,6 +241,7 @@ static void run(int32_t T, int caterpillar, int64_t nrows)
     CHECK(tq_scf_read(acc, counts, NULL, &skipped) == TQ_OK && skipped == 0);
     for (int64_t i = 0; i < 8 * E; ++i) CHECK(counts[i] == 0);
     tq_scf_destroy(acc);
+    run_conc(T, caterpillar, parent, n_nodes, nrows < 10000 ? nrows : 10000);
     free(masks); free(counts); free(classes); free(sets); free(parent);
 }
 
@@ -166,6 +271,14 @@ int main(void)
         free(big);
     }
     tq_scf_destroy(NULL);
+    {
+        tq_conc *c = (tq_conc *)1;
+        CHECK(tq_conc_create(&c, three, 4, 3, 0, 1.0, NULL) == TQ_ERR_INVALID_ARG && c == NULL);
+        CHECK(strstr(tq_last_error(NULL), "tq_conc_create: "));
+        CHECK(tq_conc_create(&c, three, 4, 4, 0, 0.0 / 0.0, NULL) == TQ_ERR_INVALID_ARG && c == NULL);
+        CHECK(tq_conc_reset(NULL) == TQ_ERR_INVALID_ARG && tq_conc_shape(NULL, NULL, NULL, NULL) == TQ_ERR_INVALID_ARG);
+        tq_conc_destroy(NULL);
+    }
     run(4, 1, 200);
     run(5, 0, 2000);
     run(40, 0, 200000);
