@@ -586,6 +586,53 @@ int tq_dstat_accumulate(const uint32_t *classes, int64_t n_sets, const uint32_t 
 int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_sets, const uint32_t *d_set_of,
                             const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream);
 
+/* Site-pattern classes per block of sites and the block-jackknife D test.  The error estimate of
+ * D that ADMIXTOOLS, Dsuite and ipyrad's `baba` use; no reference counterpart in tetrad itself.
+ *   Rule (full mode only): a site is counted for a set when none of its four bases is missing and, unless option
+ *   "count_invariant" is set, the four are not all equal; its class is the one of section 18.  block_starts i64[B + 1]
+ *   in HOST memory: block j = sites [block_starts[j], block_starts[j + 1]) of the resident replicate, with
+ *   0 <= block_starts[0], a strictly increasing sequence, block_starts[B] <= S and 1 <= B <= 4096.  Sites outside every
+ *   block count nowhere; blocks need not respect loci.  A block row is u32[16]: the class counts of the block's sites
+ *   and their sum.  When the blocks tile [0, S) the sum of a set's block rows equals the row tq_patterns(subsample = 0)
+ *   writes, bit for bit.  There is no subsample form (its one-SNP-per-locus choice is not a per-block function).
+ *   tq_patterns_blocks      sets u32[Q,4], host buffers, synchronous; classes u32[Q][B][16].  Validated as tq_patterns
+ *                      validates (NULL, negative Q, no data, an index >= T, a row not strictly ascending) plus the
+ *                      block rule, all before anything is launched.  Q = 0 is valid.  Works in chunks of whole sets of
+ *                      at most option "batch" items of Q * B.
+ *   tq_patterns_blocks_dev  d_sets / d_classes device pointers (16-byte aligned: a misaligned pointer is refused with
+ *                      TQ_ERR_INVALID_ARG before anything is launched), enqueued on `stream` under the stream rule
+ *                      above, so it is ordered behind a tq_bootstrap_async that rebuilds the layout.  The rows are the
+ *                      caller's responsibility (an index >= T gives rows of zeros).  block_starts is read before the call
+ *                      returns and reaches the device without a synchronisation of the caller's stream: it is copied
+ *                      into one of two page-locked staging pieces of the context (the host waits only for the copy that
+ *                      used that piece two calls earlier) and from there, asynchronously on `stream`, into a device array
+ *                      of the context.
+ *   Both read the natural layout always (never the packed set of site_pack / boot_pack) and no option but
+ *   "count_invariant" and, in the host form, "batch": not scan_method, not phases, no scan option.  Neither records a
+ *   timing mark or counts as a call of tq_timing_read*.
+ *   tq_dstat_jackknife_dev  one thread per test, enqueued on `stream`: test t reads the B block rows of set set_of[t],
+ *                      a_j = row_j[ia[t]], b_j = row_j[ib[t]], m_j = a_j + b_j, and OVERWRITES its row of
+ *                      out f64[N][4] = {g, theta, theta_J, var}: the delete-one-block jackknife with block weight m_j
+ *                      (Busing, Meijer & van der Leeden 1999).  A = sum a_j, Bs = sum b_j, n = A + Bs, g = blocks with
+ *                      m_j > 0 (integers).  n = 0: {0, NaN, NaN, NaN}.  theta = (A - Bs) / n.  g < 2: {g, theta, NaN,
+ *                      NaN}.  Over the blocks with m_j > 0 in block order: r = n - m_j, theta_-j = ((A - a_j) - (Bs - b_j))
+ *                      / r, sJ += (r / n) theta_-j; theta_J = g theta - sJ.  Then h = n / m_j, tau = h theta - (h - 1)
+ *                      theta_-j, e = tau - theta_J, sV += (e e) / (h - 1); var = sV / g.  Every floating operation is one
+ *                      correctly rounded double operation in that order (no fused multiply-add), so the result equals
+ *                      the host execution bit for bit.  Standard error = sqrt(var), Z = D / standard error: the
+ *                      caller's.  A test whose set_of >= n_sets or whose class index is above 14 is skipped without
+ *                      touching memory.  1 <= B <= 4096.
+ *   tq_dstat_jackknife  the host execution (no context; messages go to tq_last_error(NULL)); such a test, or B outside
+ *                      1..4096, is refused (TQ_ERR_INVALID_ARG) and nothing is written.                               */
+int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64_t *block_starts, int64_t B,
+                       uint32_t *classes);
+int tq_patterns_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts, int64_t B,
+                           uint32_t *d_classes, void *stream);
+int tq_dstat_jackknife(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint8_t *ia,
+                       const uint8_t *ib, int64_t N, double *out);
+int tq_dstat_jackknife_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
+                           const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_out, void *stream);
+
 /* Site concordance factors per branch of a fixed tree: sCF / sDF1 / sDF2 / sN of Minh, Hahn &
  * Lanfear 2020 from the class rows above.  No reference counterpart in tetrad itself.
  *   Rule: a row is a set (a, b, c, d) with its class row u32[16] as the pattern calls write it.  The tree gives the

@@ -1,0 +1,239 @@
+// pattern_blocks.hpp -- site-pattern class counts per (set, block of sites) from the bit planes, and the delete-one-block
+// jackknife of D on top of them.  Part of the single translation unit tetrad_hip.hip (included
+// inside its anonymous namespace, after patterns.hpp).
+//
+// Rule (full mode only): a site is counted for a set (a, b, c, d) when none of the four bases is missing and -- unless
+// option count_invariant is set -- the four are not all equal.  Its class is the restricted-growth string of
+// patterns.hpp.  Block j of `starts` i64[B + 1] is sites [starts[j], starts[j + 1]) of the resident replicate; a block
+// row is u32[16] = the 15 class counts of the block's sites and their sum.
+//
+// tq_pattern_blocks_kernel: a work item is a (set, block) pair, item = set * B + block.  16 lanes take one item, four
+// items per wavefront (the group shape of tq_pattern_class_kernel, whose DPP row sum is re-used).  Lane l takes the
+// words w0 + l, w0 + l + 16, ... of the block's word range: per word four 12-byte plane records {missing, bit 0, bit 1}
+// (prepare.hpp), valid = ~(OR of the missing words) & range mask, six equality words, the 15 class masks as products of
+// the equality words and their complements, 15 popcount-adds.  The range mask differs from all-ones only in the first
+// and the last word of the block (both cuts in one word when the block lies inside it); pad sites are missing in every
+// taxon.  No LDS, no atomics, no scratch; every address is 64-bit.  A taxon >= T gives a row of zeros; items past
+// Q * B store nothing.
+//
+// dstat_jackknife_row: Busing, Meijer & van der Leeden 1999, block weight m_j = a_j + b_j, every floating operation
+// rounded once and in one fixed order (see the function), so device, host and Python floats agree bit for bit.
+#pragma once
+
+constexpr int PBLK_THREADS = 256;           // 4 wavefronts = 16 items per workgroup
+constexpr int PBLK_ITEMS = PBLK_THREADS / 16;
+constexpr int JK_THREADS = 128;
+constexpr int64_t PBLK_MAX_BLOCKS = 4096;
+
+// The 15 class masks of 32 sites from the six equality words (e_xy: position x and y hold the same base).  `on` is
+// AND-ed into every mask.  One definition for the kernel and for the compile-time check below.
+struct PatternMasks {
+    uint32_t m[PAT_CLASSES];
+};
+
+constexpr __host__ __device__ PatternMasks pattern_masks(uint32_t e01, uint32_t e02, uint32_t e03, uint32_t e12, uint32_t e13,
+                                                         uint32_t e23, uint32_t on)
+{
+    PatternMasks r{};
+    const uint32_t s = on & e01, d = on & ~e01;        // x1 = x0 / x1 new
+    const uint32_t s2 = s & e02, n2 = s & ~e02;        // 000. / 001.
+    r.m[0] = s2 & e03;                                 // 0000
+    r.m[1] = s2 & ~e03;                                // 0001
+    r.m[2] = n2 & e03;                                 // 0010
+    const uint32_t n23 = n2 & ~e03;
+    r.m[3] = n23 & e23;                                // 0011
+    r.m[4] = n23 & ~e23;                               // 0012
+    const uint32_t d0 = d & e02;                       // 010.
+    r.m[5] = d0 & e03;                                 // 0100
+    const uint32_t d0n = d0 & ~e03;
+    r.m[6] = d0n & e13;                                // 0101
+    r.m[7] = d0n & ~e13;                               // 0102
+    const uint32_t dn = d & ~e02;
+    const uint32_t d1 = dn & e12;                      // 011.
+    r.m[8] = d1 & e03;                                 // 0110
+    const uint32_t d1n = d1 & ~e03;
+    r.m[9] = d1n & e13;                                // 0111
+    r.m[10] = d1n & ~e13;                              // 0112
+    const uint32_t d2 = dn & ~e12;                     // 012.
+    r.m[11] = d2 & e03;                                // 0120
+    const uint32_t d2n = d2 & ~e03;
+    r.m[12] = d2n & e13;                               // 0121
+    const uint32_t d2nn = d2n & ~e13;
+    r.m[13] = d2nn & e23;                              // 0122
+    r.m[14] = d2nn & ~e23;                             // 0123
+    return r;
+}
+
+// every one of the 256 patterns sets exactly the mask of its class (pattern_class, patterns.hpp)
+constexpr bool pattern_masks_ok()
+{
+    for (int p = 0; p < 256; ++p) {
+        const int x0 = p >> 6, x1 = (p >> 4) & 3, x2 = (p >> 2) & 3, x3 = p & 3;
+        const PatternMasks r = pattern_masks(x0 == x1, x0 == x2, x0 == x3, x1 == x2, x1 == x3, x2 == x3, 1u);
+        const int want = pattern_class(x0, x1, x2, x3);
+        for (int c = 0; c < PAT_CLASSES; ++c)
+            if (r.m[c] != (c == want ? 1u : 0u)) return false;
+    }
+    return true;
+}
+static_assert(pattern_masks_ok(), "the class masks must follow pattern_class");
+
+struct PlaneRec {
+    uint32_t miss, b0, b1;
+};
+
+__device__ __forceinline__ PlaneRec pblk_load(const uint32_t *row, int64_t w)
+{
+    typedef uint32_t v3 __attribute__((ext_vector_type(3)));
+    const v3 v = *reinterpret_cast<const v3 *>(row + w * 3);
+    return PlaneRec{v.x, v.y, v.z};
+}
+
+__device__ __forceinline__ uint32_t pblk_eq(const PlaneRec &x, const PlaneRec &y)
+{
+    return ~((x.b0 ^ y.b0) | (x.b1 ^ y.b1));
+}
+
+// planes3 u32[T][W][3]; sets u32[Q][4]; starts i64[B + 1] with 0 <= starts[0] < ... < starts[B] <= 32 W (checked on the
+// host), Q * B < 2^31; inv = 0xFFFFFFFF when invariant sites count, else 0; classes u32[Q][B][16]
+__global__ __launch_bounds__(PBLK_THREADS) void tq_pattern_blocks_kernel(const uint32_t *__restrict__ planes3, int64_t W,
+                                                                         uint32_t T, const uint32_t *__restrict__ sets,
+                                                                         int64_t Q, const int64_t *__restrict__ starts,
+                                                                         int64_t B, uint32_t inv,
+                                                                         uint32_t *__restrict__ classes)
+{
+    const int l = threadIdx.x & 15;
+    const int64_t item = (int64_t)blockIdx.x * PBLK_ITEMS + (threadIdx.x >> 4);
+    const bool live = item < Q * B;             // the same for the 16 lanes of a DPP row
+    // one launch holds fewer than 2^31 items (the host cuts longer calls): a 32-bit division
+    const uint32_t q32 = live ? (uint32_t)item / (uint32_t)B : 0u;
+    const int64_t q = q32, j = live ? item - q * B : 0;
+    const uint4 set = reinterpret_cast<const uint4 *>(sets)[q];
+    const bool inside = live && set.x < T && set.y < T && set.z < T && set.w < T;
+    uint32_t c[PAT_CLASSES];
+#pragma unroll
+    for (int i = 0; i < PAT_CLASSES; ++i) c[i] = 0;
+    if (inside) {
+        const int64_t s0 = starts[j], s1 = starts[j + 1];       // s0 < s1
+        const int64_t w0 = s0 >> 5, w1 = (s1 - 1) >> 5;
+        const uint32_t first = 0xFFFFFFFFu << (uint32_t)(s0 & 31);
+        const uint32_t last = 0xFFFFFFFFu >> (31u - (uint32_t)((s1 - 1) & 31));
+        const uint32_t *ra = planes3 + (int64_t)set.x * W * 3, *rb = planes3 + (int64_t)set.y * W * 3;
+        const uint32_t *rc = planes3 + (int64_t)set.z * W * 3, *rd = planes3 + (int64_t)set.w * W * 3;
+        for (int64_t w = w0 + l; w <= w1; w += 16) {
+            const PlaneRec a = pblk_load(ra, w), b = pblk_load(rb, w), cc = pblk_load(rc, w), d = pblk_load(rd, w);
+            uint32_t valid = ~(a.miss | b.miss | cc.miss | d.miss);
+            valid &= w == w0 ? first : 0xFFFFFFFFu;
+            valid &= w == w1 ? last : 0xFFFFFFFFu;
+            const PatternMasks k = pattern_masks(pblk_eq(a, b), pblk_eq(a, cc), pblk_eq(a, d), pblk_eq(b, cc), pblk_eq(b, d),
+                                                 pblk_eq(cc, d), valid);
+            c[0] += (uint32_t)__popc(k.m[0] & inv);
+#pragma unroll
+            for (int i = 1; i < PAT_CLASSES; ++i) c[i] += (uint32_t)__popc(k.m[i]);
+        }
+    }
+    // every lane of the wavefront is here: the DPP steps read lanes of the own row only, and a row is one item
+    uint32_t total = 0;
+#pragma unroll
+    for (int i = 0; i < PAT_CLASSES; ++i) {
+        c[i] = pattern_row_sum(c[i]);
+        total += c[i];
+    }
+    if (live && l == 0) {
+        uint4 *out = reinterpret_cast<uint4 *>(classes + item * PAT_ROW);
+        out[0] = make_uint4(c[0], c[1], c[2], c[3]);
+        out[1] = make_uint4(c[4], c[5], c[6], c[7]);
+        out[2] = make_uint4(c[8], c[9], c[10], c[11]);
+        out[3] = make_uint4(c[12], c[13], c[14], total);
+    }
+}
+
+// The delete-one-block jackknife of one test.  rows = the B block rows u32[B][16] of the test's set, ca / cb = the classes
+// that play ABBA and BABA.  Returns {g, theta, theta_J, var}: g = blocks with a_j + b_j > 0, theta = (A - Bs) / n over all
+// blocks, theta_J the jackknife estimate and var the jackknife variance with block weight m_j = a_j + b_j (Busing et
+// al. 1999).  n = 0: {0, NaN, NaN, NaN}; g < 2: {g, theta, NaN, NaN}.  The integers are exact (B <= 4096 counts below
+// 2^32: n < 2^45).  Every floating operation is one correctly rounded f64 operation in the order written: contraction
+// is off for this function (see dstat_add, patterns.hpp), so the products and sums stay apart on the device as well.
+struct JackknifeRow {
+    double g, theta, theta_j, var;
+};
+
+__host__ __device__ __forceinline__ JackknifeRow dstat_jackknife_row(const uint32_t *rows, int64_t B, uint32_t ca, uint32_t cb)
+{
+#pragma clang fp contract(off)
+    const double qnan = __builtin_bit_cast(double, (uint64_t)0x7FF8000000000000ull);
+    uint64_t A = 0, Bs = 0, g = 0;
+    for (int64_t j = 0; j < B; ++j) {
+        const uint64_t a = rows[j * PAT_ROW + ca], b = rows[j * PAT_ROW + cb];
+        A += a;
+        Bs += b;
+        g += (a + b) > 0 ? 1u : 0u;
+    }
+    const uint64_t n = A + Bs;
+    if (n == 0) return JackknifeRow{0.0, qnan, qnan, qnan};
+    const double nf = (double)n, gf = (double)g;
+    const double theta = (double)((int64_t)A - (int64_t)Bs) / nf;
+    if (g < 2) return JackknifeRow{gf, theta, qnan, qnan};
+    double sJ = 0.0;
+    for (int64_t j = 0; j < B; ++j) {
+        const uint64_t a = rows[j * PAT_ROW + ca], b = rows[j * PAT_ROW + cb], m = a + b;
+        if (m == 0) continue;
+        const double r = (double)(n - m);
+        const double tj = (double)((int64_t)(A - a) - (int64_t)(Bs - b)) / r;
+        const double wgt = r / nf;
+        const double p = wgt * tj;
+        sJ = sJ + p;
+    }
+    const double gt = gf * theta;
+    const double thetaJ = gt - sJ;
+    double sV = 0.0;
+    for (int64_t j = 0; j < B; ++j) {
+        const uint64_t a = rows[j * PAT_ROW + ca], b = rows[j * PAT_ROW + cb], m = a + b;
+        if (m == 0) continue;
+        const double r = (double)(n - m);
+        const double tj = (double)((int64_t)(A - a) - (int64_t)(Bs - b)) / r;
+        const double h = nf / (double)m;
+        const double h1 = h - 1.0;
+        const double ht = h * theta;
+        const double hj = h1 * tj;
+        const double tau = ht - hj;
+        const double e = tau - thetaJ;
+        const double ee = e * e;
+        const double q = ee / h1;
+        sV = sV + q;
+    }
+    return JackknifeRow{gf, theta, thetaJ, sV / gf};
+}
+
+// test t reads the block rows of set set_of[t]; one thread per test.  Indices out of range: the thread returns without
+// touching memory.  The output row is overwritten.
+__global__ __launch_bounds__(JK_THREADS) void tq_dstat_jackknife_kernel(const uint32_t *__restrict__ bclasses, int64_t n_sets,
+                                                                        int64_t B, const uint32_t *__restrict__ set_of,
+                                                                        const uint8_t *__restrict__ ia,
+                                                                        const uint8_t *__restrict__ ib, int64_t N,
+                                                                        double *__restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * JK_THREADS + threadIdx.x;
+    if (t >= N) return;
+    const uint32_t s = set_of[t];
+    const uint32_t ca = ia[t], cb = ib[t];
+    if ((int64_t)s >= n_sets || ca >= (uint32_t)PAT_CLASSES || cb >= (uint32_t)PAT_CLASSES) return;
+    const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)s * B * PAT_ROW, B, ca, cb);
+    out[4 * t + 0] = r.g;
+    out[4 * t + 1] = r.theta;
+    out[4 * t + 2] = r.theta_j;
+    out[4 * t + 3] = r.var;
+}
+
+// the host execution; the caller has checked the indices
+inline void dstat_jackknife_host(const uint32_t *bclasses, int64_t B, const uint32_t *set_of, const uint8_t *ia,
+                                 const uint8_t *ib, int64_t N, double *out)
+{
+    for (int64_t t = 0; t < N; ++t) {
+        const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)set_of[t] * B * PAT_ROW, B, ia[t], ib[t]);
+        out[4 * t + 0] = r.g;
+        out[4 * t + 1] = r.theta;
+        out[4 * t + 2] = r.theta_j;
+        out[4 * t + 3] = r.var;
+    }
+}

@@ -85,6 +85,7 @@ namespace {
 #include "consensus.hpp"
 #include "fit.hpp"
 #include "patterns.hpp"
+#include "pattern_blocks.hpp"
 #include "scf.hpp"
 
 }  // namespace
@@ -236,6 +237,12 @@ struct tq_ctx {
     hipEvent_t evDevApi = nullptr;
     bool dev_api_pending = false;
     hipStream_t last_dev_stream = nullptr;   // stream of the last device-API enqueue (enter_dev_api orders across streams)
+    // block boundaries of tq_patterns_blocks* (pattern_blocks.hpp): one device array, filled on the call's stream from
+    // page-locked staging (two pieces in turn, so the next call can hand its boundaries over while this copy is queued)
+    int64_t *d_bstarts = nullptr;   // [PBLK_MAX_BLOCKS + 1]
+    int64_t *h_bstarts_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_bstarts[2] = {nullptr, nullptr};   // the piece's H2D has been consumed
+    unsigned bstarts_turn = 0;
     // options
     int nrep = 1;
     int waves_per_cu = 0;           // 0 = from the occupancy query
@@ -1521,6 +1528,62 @@ int patterns_dev(tq_ctx *ctx, const char *who, const uint32_t *d_sets, int64_t Q
     return note_dev_api(ctx, stream, launch_patterns(ctx, d_sets, Q, subsample, species, d_classes, stream));
 }
 
+// Block rows (pattern_blocks.hpp).  What both forms check before anything is launched: the data and the block rule.
+int blocks_ready(tq_ctx *ctx, const char *who, const int64_t *block_starts, int64_t B)
+{
+    if (int rc = check_ready(ctx, 0)) return rc;
+    if (B < 1 || B > PBLK_MAX_BLOCKS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
+    if (block_starts[0] < 0)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[0]=%lld is negative", who, (long long)block_starts[0]);
+    for (int64_t j = 0; j < B; ++j)
+        if (block_starts[j + 1] <= block_starts[j])
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[%lld]=%lld is not above block_starts[%lld]=%lld", who,
+                        (long long)(j + 1), (long long)block_starts[j + 1], (long long)j, (long long)block_starts[j]);
+    if (block_starts[B] > ctx->S)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[%lld]=%lld is past the S=%lld sites of the resident replicate",
+                    who, (long long)B, (long long)block_starts[B], (long long)ctx->S);
+    return TQ_OK;
+}
+
+// The boundaries reach the device behind the work already on `stream`, without waiting for it: a copy into the next
+// staging piece (the host waits only for the copy that used this piece two calls ago), then an asynchronous H2D.
+// Calls of one context are ordered (enter_dev_api / ensure_streams), so one device array serves.
+int stage_block_starts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, hipStream_t stream)
+{
+    constexpr size_t bytes = (size_t)(PBLK_MAX_BLOCKS + 1) * sizeof(int64_t);
+    if (!ctx->d_bstarts) TQ_HIP(ctx, hipMalloc((void **)&ctx->d_bstarts, bytes));
+    for (int i = 0; i < 2; ++i) {
+        if (!ctx->h_bstarts_stage[i] && pool().alloc(bytes, (void **)&ctx->h_bstarts_stage[i]) != TQ_OK)
+            return fail(ctx, TQ_ERR_OOM, "out of page-locked host memory for the block boundaries");
+        if (!ctx->ev_bstarts[i]) TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_bstarts[i], hipEventDisableTiming));
+    }
+    const unsigned turn = ctx->bstarts_turn++ & 1u;
+    TQ_HIP(ctx, hipEventSynchronize(ctx->ev_bstarts[turn]));
+    memcpy(ctx->h_bstarts_stage[turn], block_starts, (size_t)(B + 1) * sizeof(int64_t));
+    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_bstarts, ctx->h_bstarts_stage[turn], (size_t)(B + 1) * sizeof(int64_t),
+                               hipMemcpyHostToDevice, stream));
+    TQ_HIP(ctx, hipEventRecord(ctx->ev_bstarts[turn], stream));
+    return TQ_OK;
+}
+
+// Block rows of sets dq[0..Q) into d_classes [Q][B][16]; the boundaries are in ctx->d_bstarts on this stream.  Always the
+// natural layout.  A launch holds fewer than 2^31 items.
+int launch_pattern_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
+{
+    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
+    const uint32_t inv = ctx->count_invariant ? 0xFFFFFFFFu : 0u;
+    for (int64_t q0 = 0; q0 < Q; q0 += per) {
+        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
+        const int64_t items = n * B;
+        hipLaunchKernelGGL(tq_pattern_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
+                           0, stream, (const uint32_t *)ctx->d_planes3, ctx->W, (uint32_t)ctx->T, dq + q0 * 4, n,
+                           (const int64_t *)ctx->d_bstarts, B, inv, d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
+        TQ_HIP(ctx, hipGetLastError());
+    }
+    return TQ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Accumulators on a fixed tree: concordance (concordance.hpp; device totals u64 [7 E + 2 T + 1] = per edge {conc,
 // disc1, disc2, nu, nsnps sum, weight sum (f64 bits), score sum (f64 bits)}, per taxon {QFc, QFd}, skipped rows) and
@@ -2114,6 +2177,14 @@ void tq_destroy(tq_ctx *ctx)
         (void)hipEventDestroy(ctx->evJoin);
     }
     if (ctx->evDevApi) (void)hipEventDestroy(ctx->evDevApi);
+    for (int i = 0; i < 2; ++i) {
+        if (ctx->ev_bstarts[i]) {
+            (void)hipEventSynchronize(ctx->ev_bstarts[i]);      // no copy may still read the staging piece
+            (void)hipEventDestroy(ctx->ev_bstarts[i]);
+        }
+        if (ctx->h_bstarts_stage[i]) (void)pool().release(ctx->h_bstarts_stage[i]);
+    }
+    if (ctx->d_bstarts) (void)hipFree(ctx->d_bstarts);
     for (auto e : ctx->pipe_events) (void)hipEventDestroy(e);
     for (auto &m : ctx->marks) (void)hipEventDestroy(m.ev);
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -2629,6 +2700,107 @@ int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_se
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(tq_dstat_kernel, dim3((unsigned)((N + DSTAT_THREADS - 1) / DSTAT_THREADS)), dim3(DSTAT_THREADS), 0,
                        (hipStream_t)stream, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc);
+    TQ_HIP(ctx, hipGetLastError());
+    return TQ_OK;
+}
+
+int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64_t *block_starts, int64_t B, uint32_t *classes)
+{
+    const char *who = "tq_patterns_blocks";
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || !block_starts || (Q > 0 && (!sets || !classes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+    int rc = blocks_ready(ctx, who, block_starts, B);
+    if (rc) return rc;
+    const uint32_t bound = (uint32_t)ctx->T;
+    for (int64_t i = 0; i < Q; ++i) {
+        const uint32_t *q = sets + 4 * i;
+        if ((q[0] >= bound) | (q[1] >= bound) | (q[2] >= bound) | (q[3] >= bound))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= T=%u", who, (long long)i, bound);
+        if (!((q[0] < q[1]) & (q[1] < q[2]) & (q[2] < q[3])))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
+                        q[0], q[1], q[2], q[3]);
+    }
+    if (Q == 0) return TQ_OK;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
+    int64_t chunk = ctx->batch / B;
+    if (chunk < 1) chunk = 1;
+    if (chunk > Q) chunk = Q;
+    const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
+    const size_t o_cls = align_up((size_t)chunk * 16, 256);
+    if ((rc = ensure_scratch(ctx, o_cls + (size_t)chunk * row_bytes))) return rc;
+    if ((rc = ensure_streams(ctx))) return rc;
+    char *base = (char *)ctx->d_scratch;
+    uint32_t *d_classes = (uint32_t *)(base + o_cls);
+    rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
+    for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
+        const int64_t n = (Q - q0) < chunk ? (Q - q0) : chunk;
+        if (hipMemcpyAsync(base, sets + q0 * 4, (size_t)n * 16, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
+            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the sets failed", who);
+        if (!rc) rc = launch_pattern_blocks(ctx, (const uint32_t *)base, n, B, d_classes, ctx->sK);
+        if (!rc && hipMemcpyAsync((char *)classes + (size_t)q0 * row_bytes, d_classes, (size_t)n * row_bytes, hipMemcpyDeviceToHost,
+                                  ctx->sK) != hipSuccess)
+            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the block rows failed", who);
+    }
+    if (hipStreamSynchronize(ctx->sK) != hipSuccess && !rc) rc = fail(ctx, TQ_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+    return rc;
+}
+
+int tq_patterns_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts, int64_t B,
+                           uint32_t *d_classes, void *stream_)
+{
+    const char *who = "tq_patterns_blocks_dev";
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || !block_starts || (Q > 0 && (!d_sets || !d_classes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+    if (int rc = blocks_ready(ctx, who, block_starts, B)) return rc;
+    if (Q == 0) return TQ_OK;
+    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
+    int rc = stage_block_starts(ctx, block_starts, B, stream);
+    if (!rc) rc = launch_pattern_blocks(ctx, d_sets, Q, B, d_classes, stream);
+    return note_dev_api(ctx, stream, rc);
+}
+
+int tq_dstat_jackknife(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint8_t *ia,
+                       const uint8_t *ib, int64_t N, double *out)
+{
+    if (N < 0 || n_sets < 0 || (N > 0 && (!bclasses || !set_of || !ia || !ib || !out)))
+        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: NULL pointer or negative size");
+    if (B < 1 || B > PBLK_MAX_BLOCKS)
+        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: B=%lld blocks, must be 1..%lld", (long long)B,
+                    (long long)PBLK_MAX_BLOCKS);
+    for (int64_t t = 0; t < N; ++t) {
+        if ((int64_t)set_of[t] >= n_sets)
+            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: test %lld has set_of=%u >= n_sets=%lld", (long long)t,
+                        set_of[t], (long long)n_sets);
+        if (ia[t] >= PAT_CLASSES || ib[t] >= PAT_CLASSES)
+            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: test %lld has a class index above 14 (%u, %u)",
+                        (long long)t, (unsigned)ia[t], (unsigned)ib[t]);
+    }
+    dstat_jackknife_host(bclasses, B, set_of, ia, ib, N, out);
+    return TQ_OK;
+}
+
+int tq_dstat_jackknife_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
+                           const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_out, void *stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (N < 0 || n_sets < 0 || (N > 0 && (!d_bclasses || !d_set_of || !d_ia || !d_ib || !d_out)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: NULL pointer or negative size");
+    if (B < 1 || B > PBLK_MAX_BLOCKS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: B=%lld blocks, must be 1..%lld", (long long)B,
+                    (long long)PBLK_MAX_BLOCKS);
+    if (N == 0) return TQ_OK;
+    if (N > (int64_t)0x7FFFFFFF * JK_THREADS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: N=%lld tests exceed one launch", (long long)N);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(tq_dstat_jackknife_kernel, dim3((unsigned)((N + JK_THREADS - 1) / JK_THREADS)), dim3(JK_THREADS), 0,
+                       (hipStream_t)stream, d_bclasses, n_sets, B, d_set_of, d_ia, d_ib, N, d_out);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
 }

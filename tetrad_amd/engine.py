@@ -301,6 +301,36 @@ class QuartetEngine:
         self._check(self._lib.tq_dstat_accumulate_dev(self._h, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc,
                                                       stream or None))
 
+    # -- class rows per block of sites and the block jackknife ----
+    @staticmethod
+    def _block_starts(block_starts) -> np.ndarray:
+        b = np.ascontiguousarray(block_starts, dtype=np.int64).reshape(-1)
+        if b.shape[0] < 2:
+            raise ValueError("block_starts must hold B + 1 >= 2 boundaries")
+        return b
+
+    def patterns_blocks(self, sets, block_starts) -> np.ndarray:
+        """Block rows u32[Q,B,16] of strictly ascending quartets `sets` [Q,4], full mode: block j holds the class
+        counts (and their sum) of sites [block_starts[j], block_starts[j+1]) of the resident replicate."""
+        s, b = self._sets(sets), self._block_starts(block_starts)
+        B = b.shape[0] - 1
+        classes = np.zeros((s.shape[0], B, 16), np.uint32)
+        self._check(self._lib.tq_patterns_blocks(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
+        return classes
+
+    def patterns_blocks_dev(self, d_sets: int, Q: int, block_starts, d_classes: int, stream: int = 0):
+        """The same with device pointers (u32[Q,4] in, u32[Q,B,16] out), enqueued on `stream`; `block_starts` is a host
+        array, read before the call returns.  The rows are the caller's responsibility."""
+        b = self._block_starts(block_starts)
+        self._check(self._lib.tq_patterns_blocks_dev(self._h, d_sets, Q, _ptr(b), b.shape[0] - 1, d_classes, stream or None))
+
+    def dstat_jackknife_dev(self, d_bclasses: int, n_sets: int, B: int, d_set_of: int, d_ia: int, d_ib: int, N: int,
+                            d_out: int, stream: int = 0):
+        """The delete-one-block jackknife of N D tests on `stream`: test t reads ABBA at d_bclasses[d_set_of[t]][j][d_ia[t]]
+        and BABA at [d_ib[t]] of every block j and overwrites d_out f64[N,4] = {blocks used, D, jackknife D, variance}."""
+        self._check(self._lib.tq_dstat_jackknife_dev(self._h, d_bclasses, n_sets, B, d_set_of, d_ia, d_ib, N, d_out,
+                                                     stream or None))
+
     # -- device-pointer API (addresses as ints, e.g. torch.Tensor.data_ptr()) -------
     def resolve_dev(self, d_quartets: int, Q: int, subsample_snps: bool, d_rstat: int,
                     d_rscor: int, d_flags: int = 0, stream: int = 0):

@@ -9,7 +9,12 @@ Permuting the four positions only permutes the classes (`permute_classes`), so t
 as its ascending quartet, and every role assignment is read off that row: `dstat_tests` turns tests in role order
 into the unique ascending sets and, per test, the row and the two class indices that play ABBA and BABA.
 
-`run_dstat` is the whole test: observed counts from the given matrix, then locus-bootstrap replicates built on the
+`run_dstat_jackknife` is the same test with the error estimate everyone else uses: the sites
+are cut into contiguous blocks (`locus_blocks`), one pass writes the class rows of every (set, block)
+(`QuartetEngine.patterns_blocks_dev`) and one kernel per chunk of sets runs the delete-one-block jackknife of every
+test (`dstat_jackknife_dev`) -- no replicate is built and nothing is rescanned.
+
+`run_dstat` is the whole bootstrap test: observed counts from the given matrix, then locus-bootstrap replicates built on the
 device, each followed on the same stream by the class rows of the unique sets and one accumulation kernel.  Nothing
 returns to the host before the end.
 """
@@ -28,6 +33,11 @@ CLASS_STRINGS = ("0000", "0001", "0010", "0011", "0012", "0100", "0101", "0102",
                  "0121", "0122", "0123")
 NCLASS = 15
 BBAA, BABA, ABBA = 3, 6, 8
+
+JACKKNIFE_DTYPE = np.dtype([("abba", np.uint32), ("baba", np.uint32), ("bbaa", np.uint32), ("nsites", np.uint32),
+                            ("D", np.float64), ("jk_blocks", np.int64), ("jk_mean", np.float64), ("jk_se", np.float64),
+                            ("Z", np.float64)])
+MAX_BLOCKS = 4096
 
 DSTAT_DTYPE = np.dtype([("abba", np.uint32), ("baba", np.uint32), ("bbaa", np.uint32), ("nsites", np.uint32),
                         ("D", np.float64), ("boot_n", np.int64), ("boot_mean", np.float64), ("boot_std", np.float64),
@@ -207,3 +217,123 @@ def dstat_accumulate(classes, set_of, ia, ib, acc) -> np.ndarray:
     if rc != 0:
         raise TetradHipError(rc, lib.tq_last_error(None).decode())
     return acc
+
+
+def locus_blocks(tmpmap, nblocks: int) -> np.ndarray:
+    """i64[B + 1] block starts that cut [0, S) at locus boundaries only, B = min(nblocks, number of loci).  Cut k sits
+    at the locus boundary nearest to k S / B (the lower one of two equally near) among those that leave a locus for
+    every block before and after it, so the blocks hold as equal site counts as the loci allow.  `tmpmap` is u32[S,2]
+    (column 0 used) or the 1-D locus column; a locus is a run of equal ids."""
+    tm = np.asarray(tmpmap)
+    locus = tm[:, 0] if tm.ndim == 2 else tm.reshape(-1)
+    S = int(locus.shape[0])
+    if S < 1:
+        raise ValueError("the matrix has no sites")
+    if not 1 <= int(nblocks) <= MAX_BLOCKS:
+        raise ValueError(f"nblocks must be 1..{MAX_BLOCKS}")
+    bnd = np.flatnonzero(locus[1:] != locus[:-1]).astype(np.int64) + 1       # interior locus boundaries, ascending
+    B = min(int(nblocks), bnd.shape[0] + 1)
+    starts = np.zeros(B + 1, np.int64)
+    starts[B] = S
+    lo = 0                                                                     # first boundary index still free
+    for k in range(1, B):
+        hi = bnd.shape[0] - (B - 1 - k)                                        # leave one boundary per later cut
+        num = k * S                                                            # target = num / B, compared exactly
+        i = int(np.searchsorted(bnd[lo:hi] * B, num, side="left")) + lo        # first boundary >= target
+        if i >= hi:
+            i = hi - 1
+        elif i > lo and num - int(bnd[i - 1]) * B <= int(bnd[i]) * B - num:
+            i -= 1
+        starts[k] = bnd[i]
+        lo = i + 1
+    return starts
+
+
+def jackknife_moments(out: np.ndarray):
+    """(jk_blocks, jk_mean, jk_se) from the rows f64[N,4] = {g, theta, theta_J, var} the jackknife calls write:
+    jk_mean = theta_J, jk_se = sqrt(var); both NaN where fewer than two blocks hold a count."""
+    out = np.asarray(out, np.float64).reshape(-1, 4)
+    with np.errstate(invalid="ignore"):
+        se = np.sqrt(out[:, 3])
+    return out[:, 0].astype(np.int64), out[:, 2].copy(), se
+
+
+def dstat_jackknife(bclasses, set_of, ia, ib) -> np.ndarray:
+    """The host execution of the jackknife kernel (`tq_dstat_jackknife`, no GPU): block rows u32[M,B,16] ->
+    f64[N,4] = {blocks with a count, D, jackknife D, jackknife variance} per test."""
+    bclasses = np.ascontiguousarray(bclasses, dtype=np.uint32)
+    if bclasses.ndim != 3 or bclasses.shape[2] != 16:
+        raise ValueError("bclasses must be [M, B, 16]")
+    set_of = np.ascontiguousarray(set_of, dtype=np.uint32)
+    ia, ib = np.ascontiguousarray(ia, dtype=np.uint8), np.ascontiguousarray(ib, dtype=np.uint8)
+    if not (ia.shape == ib.shape == set_of.shape):
+        raise ValueError("set_of, ia and ib must have one entry per test")
+    out = np.zeros((set_of.shape[0], 4), np.float64)
+    lib = _lib.load()
+    rc = lib.tq_dstat_jackknife(_ptr(bclasses), bclasses.shape[0], bclasses.shape[1], _ptr(set_of), _ptr(ia), _ptr(ib),
+                                set_of.shape[0], _ptr(out))
+    if rc != 0:
+        raise TetradHipError(rc, lib.tq_last_error(None).decode())
+    return out
+
+
+def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: int = 50, block_starts=None,
+                        chunk: int = 1 << 16, *, resident: bool = False) -> np.ndarray:
+    """D tests with a block jackknife, full mode.  `set_data(tmparr, tmpmap)`, then the unique sets of `tests`
+    int[N,4] = (P1, P2, P3, O) in chunks of `chunk`: the block rows of the chunk (`patterns_blocks_dev`, torch memory of
+    chunk x B x 64 bytes, re-used) and the jackknife of the chunk's tests (`dstat_jackknife_dev`), all on the current
+    stream; one device-to-host copy at the end.  The blocks are `block_starts` i64[B + 1] or, without it,
+    `locus_blocks(tmpmap, nblocks)`.  With `resident=True` nothing is loaded: the tests run on the replicate the engine
+    holds (after `engine.bootstrap`, say); `tmparr` is not read, and `tmpmap` may be None when `block_starts` is given
+    (else the resident locus column is fetched for the cuts).
+    Returns a structured array per test: abba, baba, bbaa, nsites (sums over the blocks), D, jk_blocks, jk_mean,
+    jk_se, Z = D / jk_se; NaN where undefined."""
+    import torch
+    if int(chunk) < 1:
+        raise ValueError("chunk must be positive")
+    sets, set_of, idx = _role_classes(tests, (ABBA, BABA, BBAA))
+    if not resident:
+        engine.set_data(tmparr, tmpmap)
+    if block_starts is None:
+        if tmpmap is None:
+            tmpmap = engine.get_data()[1]
+        block_starts = locus_blocks(tmpmap, nblocks)
+    starts = np.ascontiguousarray(block_starts, dtype=np.int64).reshape(-1)
+    B = starts.shape[0] - 1
+    N, M = len(set_of), len(sets)
+    res = np.zeros(N, JACKKNIFE_DTYPE)
+    if N == 0:
+        return res
+    chunk = min(int(chunk), M)
+    # the tests in the order of their sets: the tests of a chunk of sets are then one contiguous run
+    order = np.argsort(set_of, kind="stable")
+    s_sorted = set_of[order].astype(np.int64)
+    dev = torch.device("cuda", engine.device_id)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        d_sets = torch.from_numpy(sets.view(np.int32)).to(dev)
+        d_rel = torch.from_numpy((s_sorted % chunk).astype(np.uint32).view(np.int32)).to(dev)
+        d_ia = torch.from_numpy(np.ascontiguousarray(idx[order, 0])).to(dev)
+        d_ib = torch.from_numpy(np.ascontiguousarray(idx[order, 1])).to(dev)
+        d_rows = torch.empty((chunk, B, 16), dtype=torch.int32, device=dev)
+        d_sum = torch.empty((M, 16), dtype=torch.int32, device=dev)     # u32 sums: a set counts at most S < 2^32 sites
+        d_out = torch.empty((N, 4), dtype=torch.float64, device=dev)
+        for q0 in range(0, M, chunk):
+            n = min(chunk, M - q0)
+            engine.patterns_blocks_dev(d_sets.data_ptr() + 16 * q0, n, starts, d_rows.data_ptr(), cur.cuda_stream)
+            torch.sum(d_rows[:n], dim=1, dtype=torch.int32, out=d_sum[q0:q0 + n])
+            t0, t1 = (int(v) for v in np.searchsorted(s_sorted, [q0, q0 + n], side="left"))
+            if t1 > t0:
+                engine.dstat_jackknife_dev(d_rows.data_ptr(), n, B, d_rel.data_ptr() + 4 * t0, d_ia.data_ptr() + t0,
+                                           d_ib.data_ptr() + t0, t1 - t0, d_out.data_ptr() + 32 * t0, cur.cuda_stream)
+        sums = d_sum.cpu().numpy().view(np.uint32)
+        jk = np.empty((N, 4), np.float64)
+        jk[order] = d_out.cpu().numpy()
+    rows = sums[set_of.astype(np.int64)]
+    take = lambda col: rows[np.arange(N), np.asarray(col, np.int64)]
+    res["abba"], res["baba"], res["bbaa"], res["nsites"] = take(idx[:, 0]), take(idx[:, 1]), take(idx[:, 2]), rows[:, NCLASS]
+    res["D"] = jk[:, 1]
+    res["jk_blocks"], res["jk_mean"], res["jk_se"] = jackknife_moments(jk)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        res["Z"] = np.where(res["jk_se"] > 0, res["D"] / res["jk_se"], np.nan)
+    return res
