@@ -240,7 +240,7 @@ def test_round_trip_through_the_buffer_life_cycle(source10, oracle):
     with QuartetEngine(0) as A, QuartetEngine(0) as B:
         B.set_option("site_pack", 0)
         A.set_option("site_pack", 1)
-        # (a) tq_set_data sizes the buffers: capacity 5 steps, plane_cap_W = 320, and a packed set
+        # (a) tq_set_data sizes the buffers: capacity 5 steps (320 plane words per row), and a packed set
         big = synth.simulate_tmparr(10, 5 * TILE, seed=31, missing=0.15)
         A.set_data(*big)
         assert A.site_pack_state()[1]
@@ -254,11 +254,11 @@ def test_round_trip_through_the_buffer_life_cycle(source10, oracle):
                 cap = capacity_of_new_allocation(S)
             replicate_and_check(A, B, source10, draws(spans, first, S), (S, S + 1), S, q10, oracle, what)
 
-        # capacity 10 240 from tq_set_data: reused, W = 256 < plane_cap_W = 320, the packed set is stale
+        # capacity 10 240 from tq_set_data: reused, W = 256 < the 320 words of the allocation, the packed set is stale
         step([L[2100], L[2048], L[65]], 3 * TILE + 1, False, "a: after a packed tq_set_data")
         # (b) short after long: the long replicate's words lie behind Sp = 4 096
         step([L[100], L[65], L[33]], TILE + 1, False, "b: short after long")
-        # (c) capacity 10 240 still (tq_set_data leaves no head-room): filled to the last site, W = plane_cap_W again
+        # (c) capacity 10 240 still (tq_set_data leaves no head-room): filled to the last site, W = the allocation's 320 words again
         step([L[2100]] * 3 + [L[2048]], 5 * TILE, False, "c: fills the allocation of tq_set_data")
         # (d) one site more: Sp = 12 288 > 10 240 -> new allocation of align(12 288 + 1 536) = 14 336
         step([L[2100]] * 4, 5 * TILE + 1, True, "d: outgrows the allocation of tq_set_data")

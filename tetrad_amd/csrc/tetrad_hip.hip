@@ -19,6 +19,7 @@
 //   and, when it pays, a second rows / nib / planes / planes3 + runbeg set in the packed site order (pack.hpp)
 //
 // Kernels (each in its own header of this directory, all included below into one translation unit):
+//   device_mem.hpp (host) DevBuf / PinnedBuf, the owners of every device and page-locked block, and SiteSet, one layout set
 //   prepare.hpp   layout build, lexicographic unranking, sort keys
 //   pack.hpp      (host) packed site order for the subsample-mode scans: whole loci per lane word (option site_pack)
 //   scan.hpp      tq_scan_wg_kernel / tq_scan_kernel: site scan -> 256 pattern counts per quartet (nibble codes + plane
@@ -68,6 +69,7 @@
 namespace {
 
 #include "common.hpp"
+#include "device_mem.hpp"
 #include "prepare.hpp"
 #include "pack.hpp"
 #include "scan.hpp"
@@ -100,40 +102,33 @@ struct tq_ctx {
     std::string err;
     hipDeviceProp_t prop{};
     // replicate data
-    int64_t T = 0, S = 0, Sp = 0, W = 0;
-    uint8_t *d_rows = nullptr;
-    uint8_t *d_nib = nullptr;       // [T][Sp/2] nibble-packed copy of the rows (common.hpp: nib_offset)
-    uint8_t *d_nib5 = nullptr;      // [T][Sp/2] the same with 4 = missing (scan_dp.hpp)
-    uint4 *d_planes = nullptr;      // [T][W] {miss, p0, p1, runbeg}
-    uint32_t *d_planes3 = nullptr;  // [T][W][3] {miss, p0, p1}, then runbeg [W]
+    int64_t T = 0, S = 0;
+    SiteSet nat;                    // the natural layout set (device_mem.hpp); its arrays are re-used by bootstrap replicates
     bool have_data = false;
     bool locus_runs_ok = false;
-    int64_t plane_cap_W = 0;        // W the planes3 / runbeg allocation was sized for
-    int64_t data_capacity = 0;      // allocated Sp (rows/planes are re-used by bootstrap replicates)
     // bootstrap source (tq_set_source): ASCII seqarr [T][S0], spans i64 [nloci][2]
-    uint8_t *d_seqarr = nullptr;
-    int64_t *d_spans = nullptr;
+    DevBuf<uint8_t> d_seqarr;
+    DevBuf<int64_t> d_spans;
     int64_t src_T = 0, src_S0 = 0, nloci = 0, max_width = 0;
-    int64_t *d_lidxs = nullptr;     // [nloci]
+    DevBuf<int64_t> d_lidxs;        // [nloci]
     std::vector<int64_t> h_spans;   // host copy of the spans (replicate lengths are computed on the host)
     int64_t *h_lidx_stage[2] = {nullptr, nullptr};   // page-locked staging of the resampled locus indices
     hipEvent_t ev_lidx[2] = {nullptr, nullptr};      // its H2D has been consumed
     unsigned lidx_turn = 0;
-    uint32_t *d_boot = nullptr;     // widths/offsets [nloci+1] | src_col [cap] | site_locus [cap]
+    DevBuf<uint32_t> d_boot;        // widths/offsets [nloci+1] | src_col [cap] | site_locus [cap]
     int64_t boot_cap = 0;
-    void *d_boot_tmp = nullptr;
+    DevBuf<char> d_boot_tmp;
     size_t boot_tmp_bytes = 0;
-    // scratch for the host-buffer API
-    void *d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    // scratch for the host-buffer API (grow-only, in bytes)
+    DevBuf<char> d_scratch;
     // count slab between the scan and the singular-value stage: u32 [batch][256]; ordering scratch
-    uint32_t *d_cm = nullptr;
+    DevBuf<uint32_t> d_cm;
     int64_t cm_quartets = 0;
-    uint32_t *d_sort = nullptr;     // 4 arrays of cm_quartets u32: keys/idx in, keys/idx out
-    void *d_sort_tmp = nullptr;
+    DevBuf<uint32_t> d_sort;        // 4 arrays of cm_quartets u32: keys/idx in, keys/idx out
+    DevBuf<char> d_sort_tmp;
     size_t sort_tmp_bytes = 0;
     int order = 1;                  // 1 = process quartets in (a,b,c)-sorted order
-    uint2 *d_units = nullptr;       // cm_quartets + 2 entries: unit list of the joint-histogram scan (scan_dp.hpp), then its count
+    DevBuf<uint2> d_units;          // cm_quartets + 2 entries: unit list of the joint-histogram scan (scan_dp.hpp), then its count
     int scan_f4 = -1;               // the cooperative scan on 12-byte plane records only (SURVEY 8 row f4 as written; scan_f4.hpp):
                                     // -1 = in subsample mode (c3 scan 5.81 -> 5.58 ms), 1 = in both modes, 0 = never
     int scan_dp = 1;                // 1 = full-mode batches of >= dp_min_quartets go to tq_scan_dp_kernel (two quartets that share
@@ -142,8 +137,8 @@ struct tq_ctx {
     // singular-value stage scratch, sized for one chunk of `svd_chunk` quartets and re-used chunk after
     // chunk (so the bidiagonals / values of a chunk stay in the Infinity Cache between its three kernels):
     // de f64[3*chunk][32], sv f64[3*chunk][16], nsnps u32[chunk]
-    double *d_de = nullptr, *d_sv = nullptr;
-    uint32_t *d_nsnps = nullptr;
+    DevBuf<double> d_de, d_sv;
+    DevBuf<uint32_t> d_nsnps;
     int64_t svd_quartets = 0;
     int64_t svd_chunk = 1 << 18;    // quartets per pass of the singular-value stage (and per result D2H piece)
     int svd_streams = 2;            // chunks alternate between this many streams (1 or 2) so that the tail of one
@@ -153,7 +148,7 @@ struct tq_ctx {
     int svd_method = 1;             // 0 = one-sided Jacobi (tq_svd_kernel), 1 = Householder + bidiagonal QR
     int bidiag_layout = 1;          // 1 = matrix dealt 2 x 2 over the quad (tq_bidiag2_kernel), 0 = four column groups
     int bdsqr_maxit = 60;           // QR sweeps per singular value before a matrix is declared not converged
-    uint64_t *d_bdsqr_stats = nullptr;   // diagnostics (option "bdsqr_stats"): {matrices, rotation steps of all lanes,
+    DevBuf<uint64_t> d_bdsqr_stats;      // diagnostics (option "bdsqr_stats"): {matrices, rotation steps of all lanes,
                                          // lane-slots issued (64 x wave iterations), sweeps} summed over the launches
     int scan_wg = 4;                // waves per workgroup of the cooperative scan kernel (1 = one wave per quartet)
     int64_t wg_min_quartets = 4096; // smaller batches go to the one-wave-per-quartet kernel: a call of a few thousand quartets does not
@@ -186,9 +181,9 @@ struct tq_ctx {
     std::vector<int32_t> sp_size;   // lineages per species
     uint64_t sp_bound = 0;          // product of the four largest species sizes (range rule: S * sp_bound < 2^32)
     int32_t sp_max = 0;             // largest species size
-    int32_t *d_sp_members = nullptr;    // offsets [K+1], then the member samples grouped by species [T], then 2 x offsets [K+1]
-    uint32_t *d_sp_tab = nullptr;   // u32 [K][Sp]: {n_A, n_C, n_G, n_T} per species and site, then u8 [K][4][Sp] (MFMA form)
-    int64_t sp_tab_cap = 0;         // (species, site) entries allocated (8 bytes each)
+    DevBuf<int32_t> d_sp_members;   // offsets [K+1], then the member samples grouped by species [T], then 2 x offsets [K+1]
+    DevBuf<uint32_t> d_sp_tab;      // u32 [K][Sp]: {n_A, n_C, n_G, n_T} per species and site, then u8 [K][4][Sp] (MFMA form):
+                                    // two u32 per (species, site) entry, grow-only
     int species_method = -1;        // -1: MFMA form when every species holds <= SPECIES_MFMA_MAX lineages, else VALU;
                                     // 0: VALU form (tq_species_pool_kernel); 1: MFMA form (tq_species_mfma_kernel)
     uint64_t data_gen = 0;          // bumped by tq_set_data / tq_bootstrap(_async)
@@ -201,18 +196,14 @@ struct tq_ctx {
     uint64_t src_gen = 0;           // bumped by tq_set_source
     uint64_t boot_gen = ~0ull;      // data_gen of the last replicate tq_bootstrap_async built (~0: none)
     uint64_t boot_src_gen = ~0ull;  // src_gen it was built from
-    // packed layout set (pack.hpp): a second copy of rows / nib / planes / planes3 + runbeg with whole loci per lane word,
-    // read by the subsample-mode scans while it is current (pk_gen == data_gen).  tq_set_data builds it under site_pack,
+    // packed layout set `pk` (pack.hpp): a second copy of rows / nib / planes / planes3 + runbeg (no nib5) with whole loci per
+    // lane word, read by the subsample-mode scans while it is current (pk_gen == data_gen).  tq_set_data builds it under site_pack,
     // tq_bootstrap_async under boot_pack (a replicate built without it leaves the set stale).  Everything else reads the
     // natural set.
     int site_pack = -1;             // -1: tq_set_data builds the set when the predicted scan cost falls (pack.hpp), 1: always
                                     // (while subsample mode is possible), 0: never, and a built set is not used
-    uint8_t *pk_rows = nullptr, *pk_nib = nullptr;
-    uint4 *pk_planes = nullptr;
-    uint32_t *pk_planes3 = nullptr; // [T][pk_W][3], then runbeg [pk_W]
-    int64_t pk_Sp = 0, pk_W = 0;
+    SiteSet pk;                     // its arrays grow only while T stays
     uint64_t pk_gen = ~0ull;        // data_gen the set was built from (~0: none)
-    int64_t pk_cap = 0;             // sites per row the pk_* arrays were allocated for (they grow only while T stays)
     // the most recent scan launch (tq_debug_fetch which = 6): its kernel form (SCAN_FORM_*, 0 = none yet), T * pitch of
     // the layout set it read and whether that was the packed set
     int last_scan_form = 0;
@@ -224,10 +215,9 @@ struct tq_ctx {
     bool boot_pack_auto = false;    // pack_pays for the source matrix (tq_set_source): a replicate resamples its loci
     bool pk_from_boot = false;      // the packed set was built by tq_bootstrap_async (d_pk_src is its map)
     PackPlanner boot_plan;
-    uint32_t *d_pstart = nullptr;   // [nloci] packed start of every resampled locus
+    DevBuf<uint32_t> d_pstart;      // [nloci] packed start of every resampled locus
     uint32_t *h_pstart_stage[2] = {nullptr, nullptr};    // page-locked staging, in turn with h_lidx_stage
-    uint32_t *d_pk_src = nullptr;   // [pk_src_cap] packed position -> natural site of the replicate, 0xFFFFFFFF = pad
-    int64_t pk_src_cap = 0;
+    DevBuf<uint32_t> d_pk_src;      // packed position -> natural site of the replicate, 0xFFFFFFFF = pad (grow-only)
     // host-buffer API: own compute and copy streams, events for the D2H pipeline
     hipStream_t sK = nullptr, sC = nullptr;
     std::vector<hipEvent_t> pipe_events;
@@ -239,7 +229,7 @@ struct tq_ctx {
     hipStream_t last_dev_stream = nullptr;   // stream of the last device-API enqueue (enter_dev_api orders across streams)
     // block boundaries of tq_patterns_blocks* (pattern_blocks.hpp): one device array, filled on the call's stream from
     // page-locked staging (two pieces in turn, so the next call can hand its boundaries over while this copy is queued)
-    int64_t *d_bstarts = nullptr;   // [PBLK_MAX_BLOCKS + 1]
+    DevBuf<int64_t> d_bstarts;      // [PBLK_MAX_BLOCKS + 1]
     int64_t *h_bstarts_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_bstarts[2] = {nullptr, nullptr};   // the piece's H2D has been consumed
     unsigned bstarts_turn = 0;
@@ -377,69 +367,59 @@ bool is_pinned(const void *p, size_t bytes)
     return a.type == hipMemoryTypeHost;
 }
 
-void free_packed(tq_ctx *ctx)
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// C(T, 4), the number of quartets of T taxa (64 bits hold it up to T = 100 000)
+uint64_t choose4(uint64_t T) { return T < 4 ? 0 : T * (T - 1) / 2 * (T - 2) / 3 * (T - 3) / 4; }
+
+// The cooperative kernels address a set with 32-bit offsets: a packed set past that range while the natural one is inside
+// it would send the batch to the one-wave kernel, so such a set is not built automatically.
+bool pack_fits_offsets(int64_t T, size_t packedSp, size_t naturalSp)
 {
-    if (ctx->pk_rows) (void)hipFree(ctx->pk_rows);
-    if (ctx->pk_nib) (void)hipFree(ctx->pk_nib);
-    if (ctx->pk_planes) (void)hipFree(ctx->pk_planes);
-    if (ctx->pk_planes3) (void)hipFree(ctx->pk_planes3);
-    ctx->pk_rows = nullptr;
-    ctx->pk_nib = nullptr;
-    ctx->pk_planes = nullptr;
-    ctx->pk_planes3 = nullptr;
-    ctx->pk_Sp = ctx->pk_W = ctx->pk_cap = 0;
-    ctx->pk_gen = ~0ull;
-    ctx->pk_from_boot = false;
+    return (uint64_t)T * (uint64_t)packedSp < 0xFFFF0000ull || (uint64_t)T * (uint64_t)naturalSp >= 0xFFFF0000ull;
 }
 
-int alloc_packed(tq_ctx *ctx, int64_t T, int64_t capSp)
+// Contiguous copy of a strided locus column and the check subsample mode and the packed order rely on: no id 0xFFFFFFFF
+// and every id in one contiguous run of sites (a sorted column needs no set).  `loc` is filled either way.
+bool copy_locus_column(const uint32_t *locus, int64_t stride, int64_t S, std::vector<uint32_t> &loc)
 {
-    const int64_t capW = capSp / 32;
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_rows, (size_t)(T * capSp)));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_nib, (size_t)(T * capSp / 2)));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_planes, (size_t)(T * capW) * sizeof(uint4)));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->pk_planes3, (size_t)(T * capW * 3 + capW) * sizeof(uint32_t)));
-    ctx->pk_cap = capSp;
-    return TQ_OK;
+    bool ok = true, sorted = true;
+    loc.resize((size_t)S);
+    for (int64_t i = 0; i < S; ++i) {
+        loc[(size_t)i] = locus[i * stride];
+        if (loc[(size_t)i] == 0xFFFFFFFFu) ok = false;
+        if (i && loc[(size_t)i] < loc[(size_t)i - 1]) sorted = false;
+    }
+    if (ok && !sorted) {
+        std::unordered_set<uint32_t> seen;
+        seen.insert(loc[0]);
+        for (int64_t i = 1; i < S && ok; ++i)
+            if (loc[(size_t)i] != loc[(size_t)i - 1] && !seen.insert(loc[(size_t)i]).second) ok = false;
+    }
+    return ok;
 }
 
 void free_data(tq_ctx *ctx)
 {
-    if (ctx->d_rows) (void)hipFree(ctx->d_rows);
-    if (ctx->d_nib) (void)hipFree(ctx->d_nib);
-    if (ctx->d_nib5) (void)hipFree(ctx->d_nib5);
-    if (ctx->d_planes) (void)hipFree(ctx->d_planes);
-    if (ctx->d_planes3) (void)hipFree(ctx->d_planes3);
-    free_packed(ctx);
-    ctx->d_rows = nullptr;
-    ctx->d_nib = nullptr;
-    ctx->d_nib5 = nullptr;
-    ctx->d_planes = nullptr;
-    ctx->d_planes3 = nullptr;
+    ctx->nat.reset();
+    ctx->pk.reset();
+    ctx->pk_gen = ~0ull;
+    ctx->pk_from_boot = false;
     ctx->have_data = false;
-    ctx->data_capacity = 0;
     ctx->scanned_Q = 0;
 }
 
 void free_source(tq_ctx *ctx)
 {
-    if (ctx->d_seqarr) (void)hipFree(ctx->d_seqarr);
-    if (ctx->d_spans) (void)hipFree(ctx->d_spans);
-    if (ctx->d_lidxs) (void)hipFree(ctx->d_lidxs);
-    if (ctx->d_boot) (void)hipFree(ctx->d_boot);
-    if (ctx->d_boot_tmp) (void)hipFree(ctx->d_boot_tmp);
-    if (ctx->d_pstart) (void)hipFree(ctx->d_pstart);
-    if (ctx->d_pk_src) (void)hipFree(ctx->d_pk_src);
-    ctx->d_pstart = nullptr;
-    ctx->d_pk_src = nullptr;
-    ctx->pk_src_cap = 0;
+    ctx->d_seqarr.reset();
+    ctx->d_spans.reset();
+    ctx->d_lidxs.reset();
+    ctx->d_boot.reset();
+    ctx->d_boot_tmp.reset();
+    ctx->d_pstart.reset();
+    ctx->d_pk_src.reset();
     ctx->pk_from_boot = false;
     ctx->boot_pack_auto = false;
-    ctx->d_seqarr = nullptr;
-    ctx->d_spans = nullptr;
-    ctx->d_lidxs = nullptr;
-    ctx->d_boot = nullptr;
-    ctx->d_boot_tmp = nullptr;
     ctx->boot_cap = 0;
     ctx->nloci = 0;
     for (int i = 0; i < 2; ++i) {
@@ -452,41 +432,26 @@ void free_source(tq_ctx *ctx)
     }
 }
 
-int ensure_scratch(tq_ctx *ctx, size_t bytes)
-{
-    if (bytes <= ctx->scratch_bytes) return TQ_OK;
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    ctx->d_scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    TQ_HIP(ctx, hipMalloc(&ctx->d_scratch, bytes));
-    ctx->scratch_bytes = bytes;
-    return TQ_OK;
-}
-
 // count slab + ordering scratch for a scan batch of `quartets`
 int ensure_cm(tq_ctx *ctx, int64_t quartets)
 {
     if (quartets <= ctx->cm_quartets) return TQ_OK;
-    if (ctx->d_cm) (void)hipFree(ctx->d_cm);
-    if (ctx->d_sort) (void)hipFree(ctx->d_sort);
-    if (ctx->d_sort_tmp) (void)hipFree(ctx->d_sort_tmp);
-    if (ctx->d_units) (void)hipFree(ctx->d_units);
-    ctx->d_cm = nullptr;
-    ctx->d_sort = nullptr;
-    ctx->d_sort_tmp = nullptr;
-    ctx->d_units = nullptr;
+    ctx->d_cm.reset();
+    ctx->d_sort.reset();
+    ctx->d_sort_tmp.reset();
+    ctx->d_units.reset();
     ctx->cm_quartets = 0;
     ctx->scanned_Q = 0;
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_cm, (size_t)quartets * 1024));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sort, (size_t)quartets * 16));
+    TQ_HIP(ctx, ctx->d_cm.alloc((size_t)quartets * 256));
+    TQ_HIP(ctx, ctx->d_sort.alloc((size_t)quartets * 4));
     size_t tmp = 0;
     uint32_t *k = ctx->d_sort;
     TQ_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, k, k, k, k, (int)quartets));
     size_t tmp2 = 0;
     TQ_HIP(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, tmp2, k, k, (int)quartets));
     if (tmp2 > tmp) tmp = tmp2;
-    TQ_HIP(ctx, hipMalloc(&ctx->d_sort_tmp, tmp ? tmp : 16));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_units, ((size_t)quartets + 2) * sizeof(uint2)));
+    TQ_HIP(ctx, ctx->d_sort_tmp.alloc(tmp ? tmp : 16));
+    TQ_HIP(ctx, ctx->d_units.alloc((size_t)quartets + 2));
     ctx->sort_tmp_bytes = tmp;
     ctx->cm_quartets = quartets;
     return TQ_OK;
@@ -501,15 +466,13 @@ int ensure_svd(tq_ctx *ctx, int64_t quartets)
         TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->evJoin, hipEventDisableTiming));
     }
     if (quartets <= ctx->svd_quartets) return TQ_OK;
-    if (ctx->d_de) (void)hipFree(ctx->d_de);
-    if (ctx->d_sv) (void)hipFree(ctx->d_sv);
-    if (ctx->d_nsnps) (void)hipFree(ctx->d_nsnps);
-    ctx->d_de = ctx->d_sv = nullptr;
-    ctx->d_nsnps = nullptr;
+    ctx->d_de.reset();
+    ctx->d_sv.reset();
+    ctx->d_nsnps.reset();
     ctx->svd_quartets = 0;
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_de, 2 * (size_t)quartets * 3 * 32 * sizeof(double)));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sv, 2 * (size_t)quartets * 3 * 16 * sizeof(double)));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_nsnps, 2 * (size_t)quartets * sizeof(uint32_t)));
+    TQ_HIP(ctx, ctx->d_de.alloc(2 * (size_t)quartets * 3 * 32));
+    TQ_HIP(ctx, ctx->d_sv.alloc(2 * (size_t)quartets * 3 * 16));
+    TQ_HIP(ctx, ctx->d_nsnps.alloc(2 * (size_t)quartets));
     ctx->svd_quartets = quartets;
     return TQ_OK;
 }
@@ -567,7 +530,7 @@ bool use_dp(const tq_ctx *ctx, int64_t n, int subsample, bool input_sorted)
     return !subsample && ctx->scan_dp && ctx->scan_f4 <= 0 && ctx->scan_method < 0 && ctx->scan_wg == 4 && !ctx->count_invariant &&
            !ctx->share_c && !ctx->scan_pair && ctx->waves_per_cu == 0 && (ctx->order || input_sorted) &&
            n >= ctx->dp_min_quartets && n >= 2 && n <= 0x7FFFFFFF && T * T * T <= 0xFFFFFFFFull &&
-           T * (uint64_t)ctx->Sp < 0xFFFF0000ull;
+           T * (uint64_t)ctx->nat.Sp < 0xFFFF0000ull;
 }
 
 // ordering + unit list of the joint-histogram scan: d_units[0..count) = (first quartet, second quartet or DP_NONE) in
@@ -605,34 +568,18 @@ int make_units(tq_ctx *ctx, const uint32_t *dq, int64_t n, bool input_sorted, hi
 DevData dev_data(const tq_ctx *ctx)
 {
     DevData d;
-    d.rows = ctx->d_rows;
-    d.nib = ctx->d_nib;
-    d.nib5 = ctx->d_nib5;
-    d.planes = ctx->d_planes;
-    d.planes3 = ctx->d_planes3;
-    d.runbeg = ctx->d_planes3 + (size_t)ctx->T * (size_t)ctx->plane_cap_W * 3;
-    d.pitch = ctx->Sp;
-    d.W = ctx->W;
+    ctx->nat.fill(d, ctx->T);
     d.T = (int32_t)ctx->T;
-    d.ntiles = (int32_t)(ctx->Sp / TILE);
     d.inv = ctx->count_invariant ? 0xFFFFFFFFu : 0u;
     return d;
 }
 
-// the set a scan reads: in subsample mode the packed one while it is current (same counts, fewer walk trips per step)
+// the set a scan reads: in subsample mode the packed one while it is current (same counts, fewer walk trips per step);
+// its nib5 is NULL: full-mode kernels only (scan_dp.hpp, species.hpp)
 DevData scan_data(const tq_ctx *ctx, int subsample)
 {
     DevData d = dev_data(ctx);
-    if (!subsample || !ctx->site_pack || !ctx->pk_rows || ctx->pk_gen != ctx->data_gen) return d;
-    d.rows = ctx->pk_rows;
-    d.nib = ctx->pk_nib;
-    d.nib5 = nullptr;               // full-mode kernels only (scan_dp.hpp, species.hpp)
-    d.planes = ctx->pk_planes;
-    d.planes3 = ctx->pk_planes3;
-    d.runbeg = ctx->pk_planes3 + (size_t)ctx->T * (size_t)ctx->pk_W * 3;
-    d.pitch = ctx->pk_Sp;
-    d.W = ctx->pk_W;
-    d.ntiles = (int32_t)(ctx->pk_Sp / TILE);
+    if (subsample && ctx->site_pack && ctx->pk.rows && ctx->pk_gen == ctx->data_gen) ctx->pk.fill(d, ctx->T);
     return d;
 }
 
@@ -645,7 +592,7 @@ void note_scan(tq_ctx *ctx, int form, const DevData &d)
 {
     ctx->last_scan_form = form;
     ctx->last_scan_tpitch = ctx->T * d.pitch;
-    ctx->last_scan_packed = ctx->pk_rows && d.rows == ctx->pk_rows ? 1 : 0;
+    ctx->last_scan_packed = ctx->pk.rows && d.rows == ctx->pk.rows ? 1 : 0;
 }
 
 template <typename K>
@@ -723,19 +670,19 @@ int launch_scan_pb(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint
 // relies on: a launch with Q < 0 reports the offset and does nothing else.
 int probe_scan_pb(tq_ctx *ctx)
 {
-    uint32_t *d = nullptr, h[2] = {0, 0};
-    TQ_HIP(ctx, hipMalloc(&d, sizeof h));
+    DevBuf<uint32_t> d;
+    uint32_t h[2] = {0, 0};
+    TQ_HIP(ctx, d.alloc(2));
     hipError_t e = hipMemset(d, 0, sizeof h);
     if (e == hipSuccess) {
         DevData none{};
         hipLaunchKernelGGL(tq_scan_pb_kernel<false>, dim3(1), dim3(PB_NW * WAVE), 0, 0, none, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d);
+                           (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d.get());
         hipLaunchKernelGGL(tq_scan_pb_kernel<true>, dim3(1), dim3(PB_NW * WAVE), 0, 0, none, (const uint32_t *)nullptr,
                            (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d + 1);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "probe of tq_scan_pb_kernel failed: %s", hipGetErrorString(e));
     ctx->pb_ok = (h[0] == 0x80000000u && h[1] == 0x80000000u) ? 1 : -1;
     return TQ_OK;
@@ -914,7 +861,7 @@ int launch_hqr(tq_ctx *ctx, const uint32_t *cm, const uint32_t *dq, int64_t n, c
     rc = grid_for(ctx, tq_bdsqr_kernel, (nmat + WAVE - 1) / WAVE, &grid, svd_wpc);
     if (rc) return rc;
     hipLaunchKernelGGL(tq_bdsqr_kernel, dim3((unsigned)grid), dim3(WAVE), 0, stream, (const double *)de, nmat, sv,
-                       ctx->bdsqr_maxit, (unsigned long long *)ctx->d_bdsqr_stats);
+                       ctx->bdsqr_maxit, (unsigned long long *)ctx->d_bdsqr_stats.get());
     TQ_HIP(ctx, hipGetLastError());
     if ((rc = mark(ctx, TAG_BDSQR, stream, lane))) return rc;
     hipLaunchKernelGGL(tq_score_kernel<DEBUG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
@@ -1023,27 +970,21 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
     ctx->scanned_Q = 0;
     if ((rc = mark(ctx, TAG_ORIGIN, stream))) return rc;
     if (ctx->sp_tab_gen != ctx->data_gen) {
-        const int64_t entries = ctx->sp_K * ctx->Sp;
-        if (entries > ctx->sp_tab_cap) {
-            if (ctx->d_sp_tab) {
-                TQ_HIP(ctx, hipDeviceSynchronize());       // a species call on another stream may still read it
-                (void)hipFree(ctx->d_sp_tab);
-            }
-            ctx->d_sp_tab = nullptr;
-            ctx->sp_tab_cap = 0;
-            TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sp_tab, (size_t)entries * 8));
-            ctx->sp_tab_cap = entries;
+        const int64_t Sp = ctx->nat.Sp, entries = ctx->sp_K * Sp;
+        if ((size_t)entries * 2 > ctx->d_sp_tab.cap()) {
+            if (ctx->d_sp_tab) TQ_HIP(ctx, hipDeviceSynchronize());      // a species call on another stream may still read it
+            TQ_HIP(ctx, ctx->d_sp_tab.grow((size_t)entries * 2));
         }
         const int32_t *members = ctx->d_sp_members + ctx->sp_K + 1;
         if (ctx->species_alleles)       // species_ready: d_boot holds the site map of the resident replicate
             hipLaunchKernelGGL(tq_species_allele_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
                                (const uint8_t *)ctx->d_seqarr, ctx->src_S0,
-                               (const uint32_t *)(ctx->d_boot + 2 * (ctx->nloci + 1)), ctx->S, ctx->Sp, members,
+                               (const uint32_t *)(ctx->d_boot + 2 * (ctx->nloci + 1)), ctx->S, Sp, members,
                                (const int32_t *)ctx->d_sp_members, (int32_t)ctx->sp_K, ctx->d_sp_tab,
                                (uint8_t *)(ctx->d_sp_tab + entries));
         else
             hipLaunchKernelGGL(tq_species_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
-                               (const uint8_t *)ctx->d_nib5, ctx->Sp, ctx->S, members, (const int32_t *)ctx->d_sp_members,
+                               (const uint8_t *)ctx->nat.nib5, Sp, ctx->S, members, (const int32_t *)ctx->d_sp_members,
                                (int32_t)ctx->sp_K, ctx->d_sp_tab, (uint8_t *)(ctx->d_sp_tab + entries));
         TQ_HIP(ctx, hipGetLastError());
         ctx->sp_tab_gen = ctx->data_gen;
@@ -1055,11 +996,11 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
     const int32_t *offsets = lin == 2 ? ctx->d_sp_members + ctx->sp_K + 1 + ctx->sp_T : ctx->d_sp_members;
     if (mfma)
         hipLaunchKernelGGL(tq_species_mfma_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
-                           (const uint8_t *)(ctx->d_sp_tab + ctx->sp_K * ctx->Sp), ctx->Sp, ctx->S, dsq, n,
+                           (const uint8_t *)(ctx->d_sp_tab + ctx->sp_K * ctx->nat.Sp), ctx->nat.Sp, ctx->S, dsq, n,
                            (int32_t)ctx->sp_K, offsets, ctx->d_cm);
     else
         hipLaunchKernelGGL(tq_species_pool_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
-                           (const uint32_t *)ctx->d_sp_tab, ctx->Sp, ctx->S, dsq, n, (int32_t)ctx->sp_K, offsets, ctx->d_cm);
+                           (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S, dsq, n, (int32_t)ctx->sp_K, offsets, ctx->d_cm);
     TQ_HIP(ctx, hipGetLastError());
     if ((rc = mark(ctx, TAG_SCAN, stream))) return rc;
     ctx->scanned_q = dsq;
@@ -1163,8 +1104,6 @@ int launch(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool debug
     ctx->scanned_Q = 0;          // the slab belongs to this call only
     return TQ_OK;
 }
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 int ensure_streams(tq_ctx *ctx)
 {
@@ -1411,10 +1350,9 @@ int host_scratch(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, bool cmats, b
     h->o_sv = align_up(h->o_cm + (cmats ? (size_t)Q * 3072 : 0), 256);
     h->o_rk = align_up(h->o_sv + (svds ? (size_t)Q * 384 : 0), 256);
     const size_t total = align_up(h->o_rk + (ranks ? (size_t)Q * 12 : 0), 256);
-    int rc = ensure_scratch(ctx, total);
-    if (rc) return rc;
-    if ((rc = ensure_streams(ctx))) return rc;
-    h->base = (char *)ctx->d_scratch;
+    TQ_HIP(ctx, ctx->d_scratch.grow(total));
+    if (int rc = ensure_streams(ctx)) return rc;
+    h->base = ctx->d_scratch;
     // quartets H2D on the compute stream (asynchronous when the caller's array is page-locked)
     TQ_HIP(ctx, hipMemcpyAsync(h->base, quartets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
     return TQ_OK;
@@ -1498,9 +1436,9 @@ int patterns_to_host(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t
     }
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     const size_t o_cls = align_up((size_t)Q * 16, 256);
-    if ((rc = ensure_scratch(ctx, o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)))) return rc;
+    TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)));
     if ((rc = ensure_streams(ctx))) return rc;
-    char *base = (char *)ctx->d_scratch;
+    char *base = ctx->d_scratch;
     uint32_t *d_classes = (uint32_t *)(base + o_cls);
     TQ_HIP(ctx, hipMemcpyAsync(base, sets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
     rc = launch_patterns(ctx, (const uint32_t *)base, Q, subsample, species, d_classes, ctx->sK);
@@ -1528,6 +1466,27 @@ int patterns_dev(tq_ctx *ctx, const char *who, const uint32_t *d_sets, int64_t Q
     return note_dev_api(ctx, stream, launch_patterns(ctx, d_sets, Q, subsample, species, d_classes, stream));
 }
 
+// What the four D-test entry points check: sizes and pointers (`rows_and_out`: the class rows and the output are there),
+// the block count of the jackknife forms, and -- host forms only, `host_arrays` -- set_of and the class indices of every
+// test.  The device forms cannot read their arrays and check sizes only.
+int check_dstat_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n_sets, const int64_t *B, const uint32_t *set_of,
+                      const uint8_t *ia, const uint8_t *ib, int64_t N, bool host_arrays)
+{
+    if (N < 0 || n_sets < 0 || (N > 0 && (!rows_and_out || !set_of || !ia || !ib)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative size", who);
+    if (B && (*B < 1 || *B > PBLK_MAX_BLOCKS))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)*B, (long long)PBLK_MAX_BLOCKS);
+    for (int64_t t = 0; host_arrays && t < N; ++t) {
+        if ((int64_t)set_of[t] >= n_sets)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: test %lld has set_of=%u >= n_sets=%lld", who, (long long)t, set_of[t],
+                        (long long)n_sets);
+        if (ia[t] >= PAT_CLASSES || ib[t] >= PAT_CLASSES)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: test %lld has a class index above 14 (%u, %u)", who, (long long)t,
+                        (unsigned)ia[t], (unsigned)ib[t]);
+    }
+    return TQ_OK;
+}
+
 // Block rows (pattern_blocks.hpp).  What both forms check before anything is launched: the data and the block rule.
 int blocks_ready(tq_ctx *ctx, const char *who, const int64_t *block_starts, int64_t B)
 {
@@ -1552,7 +1511,7 @@ int blocks_ready(tq_ctx *ctx, const char *who, const int64_t *block_starts, int6
 int stage_block_starts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, hipStream_t stream)
 {
     constexpr size_t bytes = (size_t)(PBLK_MAX_BLOCKS + 1) * sizeof(int64_t);
-    if (!ctx->d_bstarts) TQ_HIP(ctx, hipMalloc((void **)&ctx->d_bstarts, bytes));
+    if (!ctx->d_bstarts) TQ_HIP(ctx, ctx->d_bstarts.alloc(PBLK_MAX_BLOCKS + 1));
     for (int i = 0; i < 2; ++i) {
         if (!ctx->h_bstarts_stage[i] && pool().alloc(bytes, (void **)&ctx->h_bstarts_stage[i]) != TQ_OK)
             return fail(ctx, TQ_ERR_OOM, "out of page-locked host memory for the block boundaries");
@@ -1577,7 +1536,7 @@ int launch_pattern_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B,
         const int64_t n = (Q - q0) < per ? (Q - q0) : per;
         const int64_t items = n * B;
         hipLaunchKernelGGL(tq_pattern_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
-                           0, stream, (const uint32_t *)ctx->d_planes3, ctx->W, (uint32_t)ctx->T, dq + q0 * 4, n,
+                           0, stream, (const uint32_t *)ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T, dq + q0 * 4, n,
                            (const int64_t *)ctx->d_bstarts, B, inv, d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
         TQ_HIP(ctx, hipGetLastError());
     }
@@ -1618,22 +1577,19 @@ struct TreeAcc {
     ConcTree t;
     int64_t words = 0;
     std::vector<uint64_t> hi;       // host adds: integer words
-    uint16_t *d_lca = nullptr, *d_dep = nullptr;
-    int32_t *d_eid = nullptr;
-    uint64_t *d_slab = nullptr, *d_tot = nullptr;
+    DevBuf<uint16_t> d_lca, d_dep;
+    DevBuf<int32_t> d_eid;
+    DevBuf<uint64_t> d_slab, d_tot;
     int gmax = 0;                   // workgroups the slab holds
     int num_cu = 0;
     StreamOrder order;              // of the device adds
     TreeAcc() = default;
     TreeAcc(const TreeAcc &) = delete;
-    ~TreeAcc()
+    ~TreeAcc()                      // the body runs before the buffers' destructors: device selected, adds finished
     {
         if (!ctx) return;
         (void)hipSetDevice(ctx->device);
         (void)order.sync();
-        void *dev[] = {d_lca, d_dep, d_eid, d_slab, d_tot};
-        for (void *p : dev)
-            if (p) (void)hipFree(p);
         if (order.ev) (void)hipEventDestroy(order.ev);
     }
 };
@@ -1669,11 +1625,11 @@ int tree_acc_init(TreeAcc *acc, const char *who, const int32_t *parent, int64_t 
     acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
     acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
     hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_lca, (size_t)T * T * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_dep, (size_t)t.N * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_eid, (size_t)t.N * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_slab, (size_t)acc->gmax * acc->words * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&acc->d_tot, (size_t)acc->words * 8);
+    if (e == hipSuccess) e = acc->d_lca.alloc((size_t)T * T);
+    if (e == hipSuccess) e = acc->d_dep.alloc((size_t)t.N);
+    if (e == hipSuccess) e = acc->d_eid.alloc((size_t)t.N);
+    if (e == hipSuccess) e = acc->d_slab.alloc((size_t)acc->gmax * acc->words);
+    if (e == hipSuccess) e = acc->d_tot.alloc((size_t)acc->words);
     if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
@@ -1777,29 +1733,29 @@ struct tq_cons {
     // device back end
     int hash_bits = 64;
     int64_t chunk_trees = 0, slots = 0, gather_cap = 0;
-    int32_t *p_trees = nullptr, *d_trees = nullptr, *d_slot_idx = nullptr;
-    uint64_t *d_masks = nullptr, *d_keys = nullptr, *d_rep = nullptr, *d_gather = nullptr, *p_gather = nullptr;
-    unsigned long long *d_slot_key = nullptr, *d_count = nullptr;
-    unsigned int *d_ctr = nullptr, *p_ctr = nullptr;
-    uint32_t *d_unres = nullptr;
+    PinnedBuf<int32_t> p_trees;
+    DevBuf<int32_t> d_trees, d_slot_idx;
+    DevBuf<uint64_t> d_masks, d_keys, d_rep, d_gather;
+    PinnedBuf<uint64_t> p_gather;
+    DevBuf<unsigned long long> d_slot_key, d_count;
+    DevBuf<unsigned int> d_ctr;
+    PinnedBuf<unsigned int> p_ctr;
+    DevBuf<uint32_t> d_unres;
     StreamOrder order;              // behind the last chunk
     int64_t dev_entries = 0;        // entries of the device table after the last finished chunk
     int64_t chunks = 0, unresolved = 0;
+    tq_cons() = default;
+    tq_cons(const tq_cons &) = delete;
+    ~tq_cons()                      // runs before the buffers' destructors: device selected, last chunk finished
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)order.sync();
+        if (order.ev) (void)hipEventDestroy(order.ev);
+    }
 };
 
 namespace {
-
-void cons_free_dev(tq_cons *a)
-{
-    void *dev[] = {a->d_trees, a->d_slot_idx, a->d_masks, a->d_keys, a->d_rep, a->d_gather, a->d_slot_key, a->d_count,
-                   a->d_ctr, a->d_unres};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *pin[] = {a->p_trees, a->p_gather, a->p_ctr};
-    for (void *p : pin)
-        if (p) (void)hipHostFree(p);
-    if (a->order.ev) (void)hipEventDestroy(a->order.ev);
-}
 
 int cons_overflow(tq_cons *a, const char *who)
 {
@@ -1926,18 +1882,18 @@ struct tq_stree {
     int64_t h_skipped = 0;
     unsigned __int128 h_sum = 0;
     // device rows and the working state of a build
-    uint64_t *d_root_t = nullptr, *d_root_k = nullptr;
-    uint64_t *d_wt[2] = {nullptr, nullptr}, *d_wk[2] = {nullptr, nullptr};
-    uint32_t *d_wn[2] = {nullptr, nullptr};
-    unsigned long long *d_cnt = nullptr, *d_mat = nullptr;
-    StreeNode *d_nodes = nullptr;
-    uint32_t *d_map = nullptr;
-    uint8_t *d_side = nullptr, *d_cut = nullptr;    // the search kernel's answer: side bytes as the map is laid out, a cut byte per node
-    uint8_t *p_side = nullptr, *p_cut = nullptr;
-    uint64_t *p_mat = nullptr;      // page-locked: a level's matrices, its nodes and side map, the counters
-    StreeNode *p_nodes = nullptr;
-    uint32_t *p_map = nullptr;
-    unsigned long long *p_cnt = nullptr;
+    DevBuf<uint64_t> d_root_t, d_root_k;
+    DevBuf<uint64_t> d_wt[2], d_wk[2];
+    DevBuf<uint32_t> d_wn[2];
+    DevBuf<unsigned long long> d_cnt, d_mat;
+    DevBuf<StreeNode> d_nodes;
+    DevBuf<uint32_t> d_map;
+    DevBuf<uint8_t> d_side, d_cut;  // the search kernel's answer: side bytes as the map is laid out, a cut byte per node
+    PinnedBuf<uint8_t> p_side, p_cut;
+    PinnedBuf<uint64_t> p_mat;      // page-locked: a level's matrices, its nodes and side map, the counters
+    PinnedBuf<StreeNode> p_nodes;
+    PinnedBuf<uint32_t> p_map;
+    PinnedBuf<unsigned long long> p_cnt;
     int64_t max_cells = 0, max_nodes = 0;
     int num_cu = 1;
     StreamOrder order;              // behind the last device add
@@ -1945,27 +1901,25 @@ struct tq_stree {
     std::vector<StreeLevelStat> stats;   // of the last build
     // quartet fit (fit.hpp): allocated at the first fit, grow-only, freed with the accumulator
     int64_t fit_bytes = 0;          // bound of the table region, the option "fit_scratch_bytes" as the first fit read it
-    uint16_t *d_fit_tab = nullptr;  // [chunk trees][T][T]
-    int64_t fit_tab_trees = 0;
-    int32_t *d_fit_rec = nullptr, *p_fit_rec = nullptr;             // [trees][2 T] prepared parent arrays
-    unsigned long long *d_fit_out = nullptr, *p_fit_out = nullptr;  // [trees][6], then the accumulator's counters
+    DevBuf<uint16_t> d_fit_tab;     // [chunk trees][T][T]
+    DevBuf<int32_t> d_fit_rec;      // [trees][2 T] prepared parent arrays
+    PinnedBuf<int32_t> p_fit_rec;
+    DevBuf<unsigned long long> d_fit_out;           // [trees][6], then the accumulator's counters
+    PinnedBuf<unsigned long long> p_fit_out;
     int64_t fit_trees = 0;          // trees the record and result buffers hold
+    tq_stree() = default;
+    tq_stree(const tq_stree &) = delete;
+    ~tq_stree()                     // runs before the buffers' destructors: device selected, device adds finished
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)order.sync();
+        if (order.ev) (void)hipEventDestroy(order.ev);
+        if (own) (void)hipStreamDestroy(own);
+    }
 };
 
 namespace {
-
-void stree_free_dev(tq_stree *a)
-{
-    void *dev[] = {a->d_root_t, a->d_root_k, a->d_wt[0], a->d_wt[1], a->d_wk[0], a->d_wk[1], a->d_wn[0], a->d_wn[1],
-                   a->d_cnt, a->d_mat, a->d_nodes, a->d_map, a->d_side, a->d_cut, a->d_fit_tab, a->d_fit_rec, a->d_fit_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *pin[] = {a->p_mat, a->p_nodes, a->p_map, a->p_cnt, a->p_side, a->p_cut, a->p_fit_rec, a->p_fit_out};
-    for (void *p : pin)
-        if (p) (void)hipHostFree(p);
-    if (a->order.ev) (void)hipEventDestroy(a->order.ev);
-    if (a->own) (void)hipStreamDestroy(a->own);
-}
 
 #define STREE_HIP(call)                                                                       \
     do {                                                                                      \
@@ -2155,20 +2109,8 @@ int tq_create(tq_ctx **out, int device_id)
 void tq_destroy(tq_ctx *ctx)
 {
     if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    free_data(ctx);
+    (void)hipSetDevice(ctx->device);     // for the buffers too: `delete ctx` below frees them
     free_source(ctx);
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->d_cm) (void)hipFree(ctx->d_cm);
-    if (ctx->d_sort) (void)hipFree(ctx->d_sort);
-    if (ctx->d_sort_tmp) (void)hipFree(ctx->d_sort_tmp);
-    if (ctx->d_units) (void)hipFree(ctx->d_units);
-    if (ctx->d_de) (void)hipFree(ctx->d_de);
-    if (ctx->d_sv) (void)hipFree(ctx->d_sv);
-    if (ctx->d_nsnps) (void)hipFree(ctx->d_nsnps);
-    if (ctx->d_bdsqr_stats) (void)hipFree(ctx->d_bdsqr_stats);
-    if (ctx->d_sp_members) (void)hipFree(ctx->d_sp_members);
-    if (ctx->d_sp_tab) (void)hipFree(ctx->d_sp_tab);
     if (ctx->sK) (void)hipStreamDestroy(ctx->sK);
     if (ctx->sC) (void)hipStreamDestroy(ctx->sC);
     if (ctx->sX) {
@@ -2184,7 +2126,6 @@ void tq_destroy(tq_ctx *ctx)
         }
         if (ctx->h_bstarts_stage[i]) (void)pool().release(ctx->h_bstarts_stage[i]);
     }
-    if (ctx->d_bstarts) (void)hipFree(ctx->d_bstarts);
     for (auto e : ctx->pipe_events) (void)hipEventDestroy(e);
     for (auto &m : ctx->marks) (void)hipEventDestroy(m.ev);
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -2218,27 +2159,17 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
     free_data(ctx);
     ctx->data_gen++;
 
-    // contiguous copy of the locus column + the run-contiguity check subsample mode relies on
+    // contiguous copy of the locus column + the run-contiguity check: not ok means no subsample mode
     std::vector<uint32_t> loc;
-    bool ok = true, sorted = true;
+    bool ok;
     try {
-        loc.resize((size_t)S);
-        for (int64_t i = 0; i < S; ++i) {
-            loc[(size_t)i] = locus[i * locus_stride];
-            if (loc[(size_t)i] == 0xFFFFFFFFu) ok = false;
-            if (i && loc[(size_t)i] < loc[(size_t)i - 1]) sorted = false;
-        }
-        if (ok && !sorted) {
-            std::unordered_set<uint32_t> seen;
-            seen.insert(loc[0]);
-            for (int64_t i = 1; i < S && ok; ++i)
-                if (loc[(size_t)i] != loc[(size_t)i - 1] && !seen.insert(loc[(size_t)i]).second) ok = false;
-        }
+        ok = copy_locus_column(locus, locus_stride, S, loc);
     } catch (const std::bad_alloc &) {
         return fail(ctx, TQ_ERR_OOM, "tq_set_data: out of host memory");
     }
     ctx->locus_runs_ok = ok;
 
+    const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
     // packed layout for the subsample-mode scans (pack.hpp): planned on the host, taken when forced or when it pays
     std::vector<uint32_t> pack_src;
     if (ok && ctx->site_pack != 0 && S < 0xFFFFFFFFll) {        // the map holds site indices as u32
@@ -2249,86 +2180,50 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
             if (ctx->site_pack < 0) {
                 double cost[2], trips[2];
                 const double gain_low = pack_estimate(tmparr, T, S, runs, pack_src, cost, trips);
-                // the cooperative kernels address a set with 32-bit offsets: a packed set past that range while the
-                // natural one is inside it would send the batch to the one-wave kernel
-                const bool fits = (uint64_t)T * (uint64_t)pack_src.size() < 0xFFFF0000ull ||
-                                  (uint64_t)T * (uint64_t)align_up((size_t)S, TILE) >= 0xFFFF0000ull;
-                if (!pack_pays(gain_low) || !fits) pack_src.clear();
+                if (!pack_pays(gain_low) || !pack_fits_offsets(T, pack_src.size(), (size_t)Sp)) pack_src.clear();
             }
         } catch (const std::bad_alloc &) {
             return fail(ctx, TQ_ERR_OOM, "tq_set_data: out of host memory");
         }
     }
 
-    const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
-    const int64_t W = Sp / 32;
-    ctx->T = T; ctx->S = S; ctx->Sp = Sp; ctx->W = W;
-    ctx->data_capacity = Sp;
-    uint8_t *d_raw = nullptr;
-    uint32_t *d_loc = nullptr;
-    // every allocation of this call is released on every failure path (the resident arrays by free_data,
-    // the two upload temporaries here)
-    hipError_t e = hipMalloc((void **)&ctx->d_rows, (size_t)(T * Sp));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_nib, (size_t)(T * Sp / 2));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_nib5, (size_t)(T * Sp / 2));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_planes, (size_t)(T * W) * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_planes3, (size_t)(T * W * 3 + W) * sizeof(uint32_t));
-    ctx->plane_cap_W = W;
-    if (e == hipSuccess) e = hipMalloc((void **)&d_raw, (size_t)(T * S));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_loc, (size_t)S * sizeof(uint32_t));
-    uint32_t *d_src = nullptr;
-    const int64_t pSp = (int64_t)pack_src.size(), pW = pSp / 32;
-    if (pSp) {
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_rows, (size_t)(T * pSp));
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_nib, (size_t)(T * pSp / 2));
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_planes, (size_t)(T * pW) * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->pk_planes3, (size_t)(T * pW * 3 + pW) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_src, (size_t)pSp * sizeof(uint32_t));
-    }
+    ctx->T = T; ctx->S = S;
+    // the resident sets leave no head-room (the packed one is built at exactly pSp); every failure path releases them
+    // through free_data and the three upload temporaries through their scope
+    const int64_t pSp = (int64_t)pack_src.size();
+    DevBuf<uint8_t> d_raw;
+    DevBuf<uint32_t> d_loc, d_src;
+    hipError_t e = ctx->nat.alloc(T, Sp, true);
+    if (e == hipSuccess) e = d_raw.alloc((size_t)(T * S));
+    if (e == hipSuccess) e = d_loc.alloc((size_t)S);
+    if (e == hipSuccess && pSp) e = ctx->pk.alloc(T, pSp, false);
+    if (e == hipSuccess && pSp) e = d_src.alloc((size_t)pSp);
     if (e != hipSuccess) {
-        if (d_raw) (void)hipFree(d_raw);
-        if (d_loc) (void)hipFree(d_loc);
-        if (d_src) (void)hipFree(d_src);
         free_data(ctx);
         return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_set_data: hipMalloc failed: %s",
                     hipGetErrorString(e));
     }
+    ctx->nat.set_sites(Sp);
+    ctx->pk.set_sites(pSp);
+    auto prepare = [&](const SiteSet &s, const uint32_t *src) {
+        const int64_t n = T * s.W;
+        hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_raw.get(), d_loc.get(), src, S,
+                           s.Sp, s.W, (int32_t)T, s.rows.get(), s.nib.get(), s.nib5.get(), s.planes.get(), s.planes3.get(),
+                           s.runbeg(T));
+        return hipGetLastError();
+    };
     e = hipMemcpy(d_raw, tmparr, (size_t)(T * S), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_loc, loc.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const int64_t n = T * W;
-        hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_raw, d_loc,
-                           (const uint32_t *)nullptr, S, Sp, W, (int32_t)T, ctx->d_rows, ctx->d_nib, ctx->d_nib5, ctx->d_planes,
-                           ctx->d_planes3,
-                           ctx->d_planes3 + (size_t)T * (size_t)W * 3);
-        e = hipGetLastError();
-        if (e == hipSuccess && pSp) {
-            e = hipMemcpy(d_src, pack_src.data(), (size_t)pSp * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e == hipSuccess) {
-                const int64_t np = T * pW;
-                hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, d_raw, d_loc,
-                                   (const uint32_t *)d_src, S, pSp, pW, (int32_t)T, ctx->pk_rows, ctx->pk_nib,
-                                   (uint8_t *)nullptr, ctx->pk_planes, ctx->pk_planes3,
-                                   ctx->pk_planes3 + (size_t)T * (size_t)pW * 3);
-                e = hipGetLastError();
-            }
-        }
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    (void)hipFree(d_raw);
-    (void)hipFree(d_loc);
-    if (d_src) (void)hipFree(d_src);
+    if (e == hipSuccess) e = prepare(ctx->nat, nullptr);
+    if (e == hipSuccess && pSp) e = hipMemcpy(d_src, pack_src.data(), (size_t)pSp * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && pSp) e = prepare(ctx->pk, d_src);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         free_data(ctx);
         return fail(ctx, TQ_ERR_HIP, "tq_set_data: %s", hipGetErrorString(e));
     }
     ctx->have_data = true;
-    if (pSp) {
-        ctx->pk_Sp = pSp;
-        ctx->pk_W = pW;
-        ctx->pk_cap = pSp;
-        ctx->pk_gen = ctx->data_gen;
-    }
+    if (pSp) ctx->pk_gen = ctx->data_gen;
     return TQ_OK;
 }
 
@@ -2338,13 +2233,8 @@ int tq_pack_sites(const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *l
     if (!locus || S < 1 || S >= 0xFFFFFFFFll || locus_stride < 1 || cap < 0 || (cap > 0 && !src) || (tmparr && T < 1))
         return TQ_ERR_INVALID_ARG;
     try {
-        std::vector<uint32_t> loc((size_t)S);
-        std::unordered_set<uint32_t> seen;
-        for (int64_t i = 0; i < S; ++i) {
-            loc[(size_t)i] = locus[i * locus_stride];
-            if (loc[(size_t)i] == 0xFFFFFFFFu) return TQ_ERR_LOCUS_ORDER;
-            if ((!i || loc[(size_t)i] != loc[(size_t)i - 1]) && !seen.insert(loc[(size_t)i]).second) return TQ_ERR_LOCUS_ORDER;
-        }
+        std::vector<uint32_t> loc;
+        if (!copy_locus_column(locus, locus_stride, S, loc)) return TQ_ERR_LOCUS_ORDER;
         std::vector<LocusRun> runs;
         std::vector<uint32_t> map;
         locus_runs(loc.data(), S, runs);
@@ -2432,17 +2322,15 @@ int tq_resolve_range_dev(tq_ctx *ctx, uint64_t first_rank, int64_t Q, int subsam
     if (Q < 0 || (Q > 0 && (!d_rstat || !d_rscor)))
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_range_dev: NULL pointer or negative Q");
     if (Q == 0) return TQ_OK;
-    const uint64_t T = (uint64_t)ctx->T;
-    const uint64_t total = T < 4 ? 0 : T * (T - 1) / 2 * (T - 2) / 3 * (T - 3) / 4;
+    const uint64_t total = choose4((uint64_t)ctx->T);
     if (first_rank + (uint64_t)Q > total)
         return fail(ctx, TQ_ERR_INVALID_ARG, "rank range [%llu,+%lld) exceeds C(%lld,4)=%llu",
                     (unsigned long long)first_rank, (long long)Q, (long long)ctx->T, (unsigned long long)total);
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     uint32_t *dq = d_quartets;
     if (!dq) {
-        int rc = ensure_scratch(ctx, (size_t)Q * 16);
-        if (rc) return rc;
-        dq = (uint32_t *)ctx->d_scratch;
+        TQ_HIP(ctx, ctx->d_scratch.grow((size_t)Q * 16));
+        dq = (uint32_t *)ctx->d_scratch.get();
     }
     hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint64_t *)nullptr, first_rank, Q, (int32_t)ctx->T, dq);
@@ -2468,8 +2356,8 @@ int tq_resolve_to_host(tq_ctx *ctx, const uint32_t *d_quartets, int64_t Q, int s
     const size_t o_rstat = 0;
     const size_t o_rscor = align_up(o_rstat + (size_t)Q * 8, 256);
     const size_t o_flags = align_up(o_rscor + (size_t)Q * 24, 256);
-    if ((rc = ensure_scratch(ctx, align_up(o_flags + (size_t)Q, 256)))) return rc;
-    char *base = (char *)ctx->d_scratch;
+    TQ_HIP(ctx, ctx->d_scratch.grow(align_up(o_flags + (size_t)Q, 256)));
+    char *base = ctx->d_scratch;
     return resolve_to_host(ctx, d_quartets, Q, subsample, false, rstat, rscor, flags, (uint32_t *)(base + o_rstat),
                            (double *)(base + o_rscor), (uint8_t *)(base + o_flags));
 }
@@ -2577,10 +2465,8 @@ int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
     for (int i = 0; i < 4; ++i) bound *= (uint64_t)top[(size_t)i];
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     TQ_HIP(ctx, hipDeviceSynchronize());         // a species call may still read the old map / table
-    if (ctx->d_sp_members) (void)hipFree(ctx->d_sp_members);
-    ctx->d_sp_members = nullptr;
     ctx->sp_K = 0;
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_sp_members, members.size() * sizeof(int32_t)));
+    TQ_HIP(ctx, ctx->d_sp_members.alloc(members.size()));
     TQ_HIP(ctx, hipMemcpy(ctx->d_sp_members, members.data(), members.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     ctx->sp_size.swap(size);
     ctx->sp_T = T;
@@ -2674,16 +2560,7 @@ int tq_patterns_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, uin
 int tq_dstat_accumulate(const uint32_t *classes, int64_t n_sets, const uint32_t *set_of, const uint8_t *ia, const uint8_t *ib,
                         int64_t N, double *acc)
 {
-    if (N < 0 || n_sets < 0 || (N > 0 && (!classes || !set_of || !ia || !ib || !acc)))
-        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate: NULL pointer or negative size");
-    for (int64_t t = 0; t < N; ++t) {
-        if ((int64_t)set_of[t] >= n_sets)
-            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate: test %lld has set_of=%u >= n_sets=%lld", (long long)t,
-                        set_of[t], (long long)n_sets);
-        if (ia[t] >= PAT_CLASSES || ib[t] >= PAT_CLASSES)
-            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate: test %lld has a class index above 14 (%u, %u)",
-                        (long long)t, (unsigned)ia[t], (unsigned)ib[t]);
-    }
+    if (int rc = check_dstat_tests(nullptr, "tq_dstat_accumulate", classes && acc, n_sets, nullptr, set_of, ia, ib, N, true)) return rc;
     dstat_add_host(classes, set_of, ia, ib, N, acc);
     return TQ_OK;
 }
@@ -2692,8 +2569,8 @@ int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_se
                             const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (N < 0 || n_sets < 0 || (N > 0 && (!d_classes || !d_set_of || !d_ia || !d_ib || !d_acc)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate_dev: NULL pointer or negative size");
+    if (int rc = check_dstat_tests(ctx, "tq_dstat_accumulate_dev", d_classes && d_acc, n_sets, nullptr, d_set_of, d_ia, d_ib, N, false))
+        return rc;
     if (N == 0) return TQ_OK;
     if (N > (int64_t)0x7FFFFFFF * DSTAT_THREADS)
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate_dev: N=%lld tests exceed one launch", (long long)N);
@@ -2729,9 +2606,9 @@ int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64
     if (chunk > Q) chunk = Q;
     const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
     const size_t o_cls = align_up((size_t)chunk * 16, 256);
-    if ((rc = ensure_scratch(ctx, o_cls + (size_t)chunk * row_bytes))) return rc;
+    TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
     if ((rc = ensure_streams(ctx))) return rc;
-    char *base = (char *)ctx->d_scratch;
+    char *base = ctx->d_scratch;
     uint32_t *d_classes = (uint32_t *)(base + o_cls);
     rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
     for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
@@ -2769,19 +2646,7 @@ int tq_patterns_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, const
 int tq_dstat_jackknife(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint8_t *ia,
                        const uint8_t *ib, int64_t N, double *out)
 {
-    if (N < 0 || n_sets < 0 || (N > 0 && (!bclasses || !set_of || !ia || !ib || !out)))
-        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: NULL pointer or negative size");
-    if (B < 1 || B > PBLK_MAX_BLOCKS)
-        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: B=%lld blocks, must be 1..%lld", (long long)B,
-                    (long long)PBLK_MAX_BLOCKS);
-    for (int64_t t = 0; t < N; ++t) {
-        if ((int64_t)set_of[t] >= n_sets)
-            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: test %lld has set_of=%u >= n_sets=%lld", (long long)t,
-                        set_of[t], (long long)n_sets);
-        if (ia[t] >= PAT_CLASSES || ib[t] >= PAT_CLASSES)
-            return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife: test %lld has a class index above 14 (%u, %u)",
-                        (long long)t, (unsigned)ia[t], (unsigned)ib[t]);
-    }
+    if (int rc = check_dstat_tests(nullptr, "tq_dstat_jackknife", bclasses && out, n_sets, &B, set_of, ia, ib, N, true)) return rc;
     dstat_jackknife_host(bclasses, B, set_of, ia, ib, N, out);
     return TQ_OK;
 }
@@ -2790,11 +2655,8 @@ int tq_dstat_jackknife_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_se
                            const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_out, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (N < 0 || n_sets < 0 || (N > 0 && (!d_bclasses || !d_set_of || !d_ia || !d_ib || !d_out)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: NULL pointer or negative size");
-    if (B < 1 || B > PBLK_MAX_BLOCKS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: B=%lld blocks, must be 1..%lld", (long long)B,
-                    (long long)PBLK_MAX_BLOCKS);
+    if (int rc = check_dstat_tests(ctx, "tq_dstat_jackknife_dev", d_bclasses && d_out, n_sets, &B, d_set_of, d_ia, d_ib, N, false))
+        return rc;
     if (N == 0) return TQ_OK;
     if (N > (int64_t)0x7FFFFFFF * JK_THREADS)
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: N=%lld tests exceed one launch", (long long)N);
@@ -2961,10 +2823,9 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
         return TQ_OK;
     }
     if (!strcmp(name, "bdsqr_stats")) {                  // 1: allocate + zero the counters, 0: free them
-        if (ctx->d_bdsqr_stats) (void)hipFree(ctx->d_bdsqr_stats);
-        ctx->d_bdsqr_stats = nullptr;
+        ctx->d_bdsqr_stats.reset();
         if (value) {
-            TQ_HIP(ctx, hipMalloc((void **)&ctx->d_bdsqr_stats, 8 * sizeof(uint64_t)));
+            TQ_HIP(ctx, ctx->d_bdsqr_stats.alloc(8));
             TQ_HIP(ctx, hipMemset(ctx->d_bdsqr_stats, 0, 8 * sizeof(uint64_t)));
         }
         return TQ_OK;
@@ -3024,27 +2885,12 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
     return fail(ctx, TQ_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
-int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, const int64_t *spans, int64_t nloci)
+// the uploads, staging pieces and the packing rule of tq_set_source, after free_source; the caller frees again on a failure
+static int build_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, const int64_t *spans, int64_t nloci, int64_t maxw)
 {
-    if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!seqarr || !spans) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: NULL pointer");
-    if (T < 1 || S0 < 1 || nloci < 1 || T > 0x7FFFFFFF)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: bad shape T=%lld S0=%lld nloci=%lld", (long long)T,
-                    (long long)S0, (long long)nloci);
-    int64_t maxw = 0;
-    for (int64_t i = 0; i < nloci; ++i) {
-        const int64_t a = spans[2 * i], b = spans[2 * i + 1];
-        if (a < 0 || b <= a || b > S0)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: span %lld = [%lld,%lld) outside [0,%lld)",
-                        (long long)i, (long long)a, (long long)b, (long long)S0);
-        if (b - a > maxw) maxw = b - a;
-    }
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    free_source(ctx);
-    ctx->src_gen++;                     // a replicate of the earlier source is no replicate of this one
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_seqarr, (size_t)(T * S0)));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_spans, (size_t)nloci * 16));
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_lidxs, (size_t)nloci * 8));
+    TQ_HIP(ctx, ctx->d_seqarr.alloc((size_t)(T * S0)));
+    TQ_HIP(ctx, ctx->d_spans.alloc((size_t)nloci * 2));
+    TQ_HIP(ctx, ctx->d_lidxs.alloc((size_t)nloci));
     TQ_HIP(ctx, hipMemcpy(ctx->d_seqarr, seqarr, (size_t)(T * S0), hipMemcpyHostToDevice));
     TQ_HIP(ctx, hipMemcpy(ctx->d_spans, spans, (size_t)nloci * 16, hipMemcpyHostToDevice));
     try {
@@ -3058,7 +2904,7 @@ int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, con
             return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of page-locked host memory");
         TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_lidx[i], hipEventDisableTiming));
     }
-    TQ_HIP(ctx, hipMalloc((void **)&ctx->d_pstart, (size_t)nloci * sizeof(uint32_t)));
+    TQ_HIP(ctx, ctx->d_pstart.alloc((size_t)nloci));
     // the automatic rule of boot_pack = -1, once, on the source: its loci (the spans, in their order) with the bases recoded
     // as tq_set_data takes them -- a two-base IUPAC code counts as present (its first base) -- under the rule and the
     // 32-bit-offset condition of tq_set_data.  A replicate resamples these loci, so their statistics are the replicate's.
@@ -3084,9 +2930,7 @@ int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, con
             pack_sites(runs, src);
             double cost[2], trips[2];
             const double gain_low = pack_estimate(arr.data(), T, Ssrc, runs, src, cost, trips);
-            const bool fits = (uint64_t)T * (uint64_t)src.size() < 0xFFFF0000ull ||
-                              (uint64_t)T * (uint64_t)align_up((size_t)Ssrc, TILE) >= 0xFFFF0000ull;
-            ctx->boot_pack_auto = pack_pays(gain_low) && fits;
+            ctx->boot_pack_auto = pack_pays(gain_low) && pack_fits_offsets(T, src.size(), align_up((size_t)Ssrc, TILE));
         }
     } catch (const std::bad_alloc &) {
         return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of host memory");
@@ -3096,6 +2940,29 @@ int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, con
     ctx->nloci = nloci;
     ctx->max_width = maxw;
     return TQ_OK;
+}
+
+int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, const int64_t *spans, int64_t nloci)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (!seqarr || !spans) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: NULL pointer");
+    if (T < 1 || S0 < 1 || nloci < 1 || T > 0x7FFFFFFF)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: bad shape T=%lld S0=%lld nloci=%lld", (long long)T,
+                    (long long)S0, (long long)nloci);
+    int64_t maxw = 0;
+    for (int64_t i = 0; i < nloci; ++i) {
+        const int64_t a = spans[2 * i], b = spans[2 * i + 1];
+        if (a < 0 || b <= a || b > S0)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: span %lld = [%lld,%lld) outside [0,%lld)",
+                        (long long)i, (long long)a, (long long)b, (long long)S0);
+        if (b - a > maxw) maxw = b - a;
+    }
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    free_source(ctx);
+    ctx->src_gen++;                     // a replicate of the earlier source is no replicate of this one
+    const int rc = build_source(ctx, seqarr, T, S0, spans, nloci, maxw);
+    if (rc) free_source(ctx);           // the context holds no half-built source
+    return rc;
 }
 
 int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t seed_shuffle, uint64_t seed_ambig,
@@ -3134,52 +3001,39 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
     const int64_t cap = n * ctx->max_width;
     if (cap > ctx->boot_cap) {
         TQ_HIP(ctx, hipDeviceSynchronize());
-        if (ctx->d_boot) (void)hipFree(ctx->d_boot);
-        if (ctx->d_boot_tmp) (void)hipFree(ctx->d_boot_tmp);
-        ctx->d_boot = nullptr;
-        ctx->d_boot_tmp = nullptr;
+        ctx->d_boot.reset();
+        ctx->d_boot_tmp.reset();
         ctx->boot_cap = 0;
-        TQ_HIP(ctx, hipMalloc((void **)&ctx->d_boot, (size_t)(2 * (n + 1) + 2 * cap) * sizeof(uint32_t)));
+        TQ_HIP(ctx, ctx->d_boot.alloc((size_t)(2 * (n + 1) + 2 * cap)));
         size_t tmp = 0;
         uint32_t *u = ctx->d_boot;
         TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, u, u, (int)(n + 1)));
         size_t tmp2 = 0;
         TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, u, u, (int)(cap / 32 + 2)));
         if (tmp2 > tmp) tmp = tmp2;
-        TQ_HIP(ctx, hipMalloc(&ctx->d_boot_tmp, tmp ? tmp : 16));
+        TQ_HIP(ctx, ctx->d_boot_tmp.alloc(tmp ? tmp : 16));
         ctx->boot_tmp_bytes = tmp;
         ctx->boot_cap = cap;
     }
     if (S < 1 || S > ctx->boot_cap) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: replicate length %lld", (long long)S);
     const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
     const int64_t W = Sp / 32;
-    if (Sp > ctx->data_capacity || T != ctx->T) {
+    SiteSet &nat = ctx->nat, &pk = ctx->pk;
+    if (Sp > nat.capSp || T != ctx->T) {
         TQ_HIP(ctx, hipDeviceSynchronize());           // kernels of the previous replicate may still read the old buffers
         free_data(ctx);
-        const int64_t capSp = (int64_t)align_up((size_t)(Sp + Sp / 8), TILE);   // head-room: replicate lengths vary
-        TQ_HIP(ctx, hipMalloc((void **)&ctx->d_rows, (size_t)(T * capSp)));
-        TQ_HIP(ctx, hipMalloc((void **)&ctx->d_nib, (size_t)(T * capSp / 2)));
-        TQ_HIP(ctx, hipMalloc((void **)&ctx->d_nib5, (size_t)(T * capSp / 2)));
-        TQ_HIP(ctx, hipMalloc((void **)&ctx->d_planes, (size_t)(T * (capSp / 32)) * sizeof(uint4)));
-        TQ_HIP(ctx, hipMalloc((void **)&ctx->d_planes3, (size_t)(T * (capSp / 32) * 3 + capSp / 32) * sizeof(uint32_t)));
-        ctx->plane_cap_W = capSp / 32;
-        ctx->data_capacity = capSp;
+        TQ_HIP(ctx, nat.alloc(T, (int64_t)align_up((size_t)(Sp + Sp / 8), TILE), true));   // head-room: replicate lengths vary
     }
     // the packed set grows only, with the same head-room; a set tq_set_data allocated serves while it is large enough
-    if (pSp > ctx->pk_cap || pSp > ctx->pk_src_cap) {
+    if (pSp > pk.capSp || (size_t)pSp > ctx->d_pk_src.cap()) {
         TQ_HIP(ctx, hipDeviceSynchronize());
         const int64_t capSp = (int64_t)align_up((size_t)(pSp + pSp / 8), TILE);
-        if (pSp > ctx->pk_cap) {
-            free_packed(ctx);
-            if (int rc1 = alloc_packed(ctx, T, capSp)) return rc1;
+        if (pSp > pk.capSp) {
+            ctx->pk_gen = ~0ull;
+            ctx->pk_from_boot = false;
+            TQ_HIP(ctx, pk.alloc(T, capSp, false));
         }
-        if (pSp > ctx->pk_src_cap) {
-            if (ctx->d_pk_src) (void)hipFree(ctx->d_pk_src);
-            ctx->d_pk_src = nullptr;
-            ctx->pk_src_cap = 0;
-            TQ_HIP(ctx, hipMalloc((void **)&ctx->d_pk_src, (size_t)capSp * sizeof(uint32_t)));
-            ctx->pk_src_cap = capSp;
-        }
+        TQ_HIP(ctx, ctx->d_pk_src.grow((size_t)capSp));
     }
     uint32_t *widths = ctx->d_boot, *offsets = widths + (n + 1);
     uint32_t *src_col = offsets + (n + 1), *site_locus = src_col + ctx->boot_cap;
@@ -3204,26 +3058,23 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
                        ctx->d_lidxs, offsets, n, ctx->nloci, seed_shuffle, src_col, site_locus);
     const int64_t nw = T * W;
     hipLaunchKernelGGL(tq_boot_build_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, ctx->d_seqarr,
-                       ctx->src_S0, src_col, site_locus, S, Sp, W, (int32_t)T, seed_ambig, ctx->d_rows, ctx->d_nib, ctx->d_nib5,
-                       ctx->d_planes, ctx->d_planes3, ctx->d_planes3 + (size_t)T * (size_t)ctx->plane_cap_W * 3);
+                       ctx->src_S0, src_col, site_locus, S, Sp, W, (int32_t)T, seed_ambig, nat.rows, nat.nib, nat.nib5,
+                       nat.planes, nat.planes3, nat.runbeg(T));
     TQ_HIP(ctx, hipGetLastError());
     if (pSp) {
-        uint32_t *nat_runbeg = ctx->d_planes3 + (size_t)T * (size_t)ctx->plane_cap_W * 3;
         TQ_HIP(ctx, hipMemsetAsync(ctx->d_pk_src, 0xFF, (size_t)pSp * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(tq_boot_pack_map_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream,
                            (const uint32_t *)offsets, (const uint32_t *)site_locus, (const uint32_t *)ctx->d_pstart, S, n, pSp,
                            ctx->d_pk_src);
         const int64_t np = T * pW;
         hipLaunchKernelGGL(tq_boot_pack_build_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream,
-                           (const uint32_t *)ctx->d_pk_src, (const uint8_t *)ctx->d_nib5, (const uint32_t *)nat_runbeg, S, Sp,
-                           pSp, pW, (int32_t)T, ctx->pk_rows, ctx->pk_nib, ctx->pk_planes, ctx->pk_planes3,
-                           ctx->pk_planes3 + (size_t)T * (size_t)pW * 3);
+                           (const uint32_t *)ctx->d_pk_src, (const uint8_t *)nat.nib5, (const uint32_t *)nat.runbeg(T), S, Sp,
+                           pSp, pW, (int32_t)T, pk.rows, pk.nib, pk.planes, pk.planes3, pk.runbeg(T));
         TQ_HIP(ctx, hipGetLastError());
     }
     ctx->T = T;
     ctx->S = S;
-    ctx->Sp = Sp;
-    ctx->W = W;
+    nat.set_sites(Sp);
     ctx->have_data = true;
     ctx->locus_runs_ok = true;          // locus ids are the ordinals 0..n-1, one run each
     ctx->scanned_Q = 0;
@@ -3231,8 +3082,7 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
     ctx->boot_gen = ctx->data_gen;
     ctx->boot_src_gen = ctx->src_gen;
     if (pSp) {
-        ctx->pk_Sp = pSp;
-        ctx->pk_W = pW;
+        pk.set_sites(pSp);
         ctx->pk_gen = ctx->data_gen;
         ctx->pk_from_boot = true;
     }
@@ -3255,7 +3105,7 @@ int tq_sample_quartets_dev(tq_ctx *ctx, uint64_t seed, int64_t Q, uint64_t *d_ra
     if (!ctx->have_data && !ctx->d_seqarr) return fail(ctx, TQ_ERR_NO_DATA, "no data on the device (T unknown)");
     if (Q < 0 || (Q > 0 && !d_quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_sample_quartets_dev: NULL pointer or negative Q");
     const uint64_t T = (uint64_t)(ctx->have_data ? ctx->T : ctx->src_T);
-    const uint64_t total = T < 4 ? 0 : T * (T - 1) / 2 * (T - 2) / 3 * (T - 3) / 4;
+    const uint64_t total = choose4(T);
     if ((uint64_t)Q > total)
         return fail(ctx, TQ_ERR_INVALID_ARG, "cannot draw %lld distinct quartets from C(%llu,4)=%llu", (long long)Q,
                     (unsigned long long)T, (unsigned long long)total);
@@ -3276,31 +3126,29 @@ int tq_get_data(tq_ctx *ctx, uint8_t *tmparr, uint32_t *tmpmap)
     if (!tmparr || !tmpmap) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_get_data: NULL pointer");
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     TQ_HIP(ctx, hipDeviceSynchronize());     // a replicate may still be queued (tq_bootstrap_async) on any stream
-    const int64_t T = ctx->T, S = ctx->S, W = ctx->W;
+    const SiteSet &nat = ctx->nat;
+    const int64_t T = ctx->T, S = ctx->S, W = nat.W;
     const size_t bytes = align_up((size_t)(T * S), 256) + align_up((size_t)S * 8, 256) + align_up((size_t)(W + 1) * 8, 256);
-    int rc = ensure_scratch(ctx, bytes);
-    if (rc) return rc;
-    uint8_t *d_arr = (uint8_t *)ctx->d_scratch;
-    uint32_t *d_map = (uint32_t *)((char *)ctx->d_scratch + align_up((size_t)(T * S), 256));
+    TQ_HIP(ctx, ctx->d_scratch.grow(bytes));
+    uint8_t *d_arr = (uint8_t *)ctx->d_scratch.get();
+    uint32_t *d_map = (uint32_t *)(ctx->d_scratch + align_up((size_t)(T * S), 256));
     uint32_t *d_cnt = (uint32_t *)((char *)d_map + align_up((size_t)S * 8, 256));
     uint32_t *d_base = d_cnt + (W + 1);
-    hipLaunchKernelGGL(tq_export_kernel, dim3((unsigned)((T * S + 255) / 256)), dim3(256), 0, 0, ctx->d_rows,
-                       ctx->d_planes, S, ctx->Sp, W, (int32_t)T, d_arr, d_map);
-    hipLaunchKernelGGL(tq_export_runcount_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, ctx->d_planes, W,
-                       d_cnt);
+    hipLaunchKernelGGL(tq_export_kernel, dim3((unsigned)((T * S + 255) / 256)), dim3(256), 0, 0, nat.rows, nat.planes, S,
+                       nat.Sp, W, (int32_t)T, d_arr, d_map);
+    hipLaunchKernelGGL(tq_export_runcount_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, nat.planes, W, d_cnt);
     size_t tmp = 0;
     TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_cnt, d_base, (int)W));
-    void *d_tmp = nullptr;
-    TQ_HIP(ctx, hipMalloc(&d_tmp, tmp ? tmp : 16));
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, d_cnt, d_base, (int)W);
+    DevBuf<char> d_tmp;
+    TQ_HIP(ctx, d_tmp.alloc(tmp ? tmp : 16));
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(d_tmp.get(), tmp, d_cnt, d_base, (int)W);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(tq_export_locus_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, ctx->d_planes,
+        hipLaunchKernelGGL(tq_export_locus_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, nat.planes,
                            (const uint32_t *)d_base, S, W, d_map);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(tmparr, d_arr, (size_t)(T * S), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(tmpmap, d_map, (size_t)S * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_tmp);
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_get_data: %s", hipGetErrorString(e));
     return TQ_OK;
 }
@@ -3317,7 +3165,7 @@ int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes)
 {
     if (!ctx || !dst || bytes < 0) return TQ_ERR_INVALID_ARG;
     if (which == 4) {                       // the packed layout set: {its sites (0: none), 1 if the subsample scans read it now}
-        const int64_t st[2] = {ctx->pk_rows ? ctx->pk_Sp : 0, scan_data(ctx, 1).rows == ctx->pk_rows && ctx->pk_rows ? 1 : 0};
+        const int64_t st[2] = {ctx->pk.Sp, ctx->pk.rows && scan_data(ctx, 1).rows == ctx->pk.rows ? 1 : 0};
         if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=4 takes 16 bytes");
         memcpy(dst, st, sizeof st);
         return TQ_OK;
@@ -3329,17 +3177,17 @@ int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes)
         return TQ_OK;
     }
     if (which == 5) {                       // the map of the current replicate's packed set (option boot_pack)
-        if (!ctx->pk_from_boot || !ctx->pk_rows || ctx->pk_gen != ctx->data_gen)
+        if (!ctx->pk_from_boot || !ctx->pk.rows || ctx->pk_gen != ctx->data_gen)
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 needs a current packed set built by tq_bootstrap");
-        if (bytes != ctx->pk_Sp * (int64_t)sizeof(uint32_t))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 takes %lld bytes", (long long)(ctx->pk_Sp * 4));
+        if (bytes != ctx->pk.Sp * (int64_t)sizeof(uint32_t))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 takes %lld bytes", (long long)(ctx->pk.Sp * 4));
         TQ_HIP(ctx, hipSetDevice(ctx->device));
         TQ_HIP(ctx, hipDeviceSynchronize());
         TQ_HIP(ctx, hipMemcpy(dst, ctx->d_pk_src, (size_t)bytes, hipMemcpyDeviceToHost));
         return TQ_OK;
     }
-    const void *src = which == 0 ? (const void *)ctx->d_cm : which == 1 ? (const void *)ctx->d_de
-                      : which == 2 ? (const void *)ctx->d_sv : which == 3 ? (const void *)ctx->d_bdsqr_stats : nullptr;
+    const void *src = which == 0 ? (const void *)ctx->d_cm.get() : which == 1 ? (const void *)ctx->d_de.get()
+                      : which == 2 ? (const void *)ctx->d_sv.get() : which == 3 ? (const void *)ctx->d_bdsqr_stats.get() : nullptr;
     if (!src) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: nothing to fetch (which=%d)", which);
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     TQ_HIP(ctx, hipDeviceSynchronize());
@@ -3351,28 +3199,28 @@ int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint
 {
     if (!ctx || !de || nmat < 1 || reps < 1) return TQ_ERR_INVALID_ARG;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
-    double *d_de = nullptr, *d_sv = nullptr;
-    uint32_t *d_work = nullptr;
+    DevBuf<double> d_de, d_sv;      // locals: every exit frees them
+    DevBuf<uint32_t> d_work;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = TQ_OK;
     auto step = [&](hipError_t e, const char *what) {
         if (!rc && e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_debug_bdsqr: %s: %s", what, hipGetErrorString(e));
     };
-    step(hipMalloc(&d_de, (size_t)nmat * 256), "hipMalloc");
-    if (!rc) step(hipMalloc(&d_sv, (size_t)nmat * 128), "hipMalloc");
-    if (!rc) step(hipMalloc(&d_work, (size_t)nmat * 4), "hipMalloc");
+    step(d_de.alloc((size_t)nmat * 32), "hipMalloc");
+    if (!rc) step(d_sv.alloc((size_t)nmat * 16), "hipMalloc");
+    if (!rc) step(d_work.alloc((size_t)nmat), "hipMalloc");
     if (!rc) step(hipMemcpy(d_de, de, (size_t)nmat * 256, hipMemcpyHostToDevice), "H2D");
     if (!rc) step(hipEventCreate(&e0), "event");
     if (!rc) step(hipEventCreate(&e1), "event");
     const unsigned grid = (unsigned)((nmat + WAVE - 1) / WAVE);
     if (!rc) {
         // once with the per-matrix counters (slower), then `reps` timed launches of the product form
-        hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv, ctx->bdsqr_maxit,
-                           (unsigned long long *)nullptr, d_work);
+        hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->bdsqr_maxit,
+                           (unsigned long long *)nullptr, d_work.get());
         step(hipGetLastError(), "launch");
         if (!rc) step(hipEventRecord(e0, 0), "record");
         for (int i = 0; i < reps && !rc; ++i)
-            hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv, ctx->bdsqr_maxit,
+            hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->bdsqr_maxit,
                                (unsigned long long *)nullptr, (uint32_t *)nullptr);
         if (!rc) step(hipEventRecord(e1, 0), "record");
         if (!rc) step(hipEventSynchronize(e1), "sync");
@@ -3384,9 +3232,6 @@ int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint
     if (!rc && work) step(hipMemcpy(work, d_work, (size_t)nmat * 4, hipMemcpyDeviceToHost), "D2H");
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (d_de) (void)hipFree(d_de);
-    if (d_sv) (void)hipFree(d_sv);
-    if (d_work) (void)hipFree(d_work);
     return rc;
 }
 
@@ -3428,7 +3273,7 @@ int tq_numpy_choice_tail(void *np_bitgen, uint64_t pop, int64_t size, int64_t *o
 int tq_unrank(const uint64_t *ranks, uint64_t first_rank, int64_t Q, int64_t T, uint32_t *quartets)
 {
     if (Q < 0 || T < 4 || T > 100000 || (Q > 0 && !quartets)) return TQ_ERR_INVALID_ARG;     // C(T,4) must fit 64 bits
-    const uint64_t t = (uint64_t)T, total = t * (t - 1) / 2 * (t - 2) / 3 * (t - 3) / 4;
+    const uint64_t total = choose4((uint64_t)T);
     if (ranks) {
         for (int64_t i = 0; i < Q; ++i)
             if (ranks[i] >= total) return TQ_ERR_INVALID_ARG;
@@ -3660,31 +3505,30 @@ int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int we
         acc->max_cells = 3 * ntaxa * ntaxa / 2 + 16;                 // sum of n (n - 1) / 2 with n <= ntaxa, sum of n < 3 ntaxa
         const size_t rows = (size_t)std::max<int64_t>(1, capacity_rows);
         hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_root_t, rows * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_root_k, rows * 8);
+        const size_t cells = (size_t)acc->max_cells, nodes = (size_t)acc->max_nodes;
+        if (e == hipSuccess) e = acc->d_root_t.alloc(rows);
+        if (e == hipSuccess) e = acc->d_root_k.alloc(rows);
         for (int b = 0; b < 2; ++b) {
-            if (e == hipSuccess) e = hipMalloc((void **)&acc->d_wt[b], rows * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&acc->d_wk[b], rows * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&acc->d_wn[b], rows * 4);
+            if (e == hipSuccess) e = acc->d_wt[b].alloc(rows);
+            if (e == hipSuccess) e = acc->d_wk[b].alloc(rows);
+            if (e == hipSuccess) e = acc->d_wn[b].alloc(rows);
         }
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_cnt, SC_WORDS * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_mat, (size_t)acc->max_cells * 16);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_nodes, (size_t)acc->max_nodes * sizeof(StreeNode));
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_map, (size_t)acc->max_nodes * 3 * 4);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_mat, (size_t)acc->max_cells * 16, hipHostMallocDefault);
-        if (e == hipSuccess)
-            e = hipHostMalloc((void **)&acc->p_nodes, (size_t)acc->max_nodes * sizeof(StreeNode), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_map, (size_t)acc->max_nodes * 3 * 4, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_cnt, SC_WORDS * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_side, (size_t)acc->max_nodes * 3);
-        if (e == hipSuccess) e = hipMalloc((void **)&acc->d_cut, (size_t)acc->max_nodes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_side, (size_t)acc->max_nodes * 3, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&acc->p_cut, (size_t)acc->max_nodes, hipHostMallocDefault);
+        if (e == hipSuccess) e = acc->d_cnt.alloc(SC_WORDS);
+        if (e == hipSuccess) e = acc->d_mat.alloc(cells * 2);
+        if (e == hipSuccess) e = acc->d_nodes.alloc(nodes);
+        if (e == hipSuccess) e = acc->d_map.alloc(nodes * 3);
+        if (e == hipSuccess) e = acc->p_mat.alloc(cells * 2);
+        if (e == hipSuccess) e = acc->p_nodes.alloc(nodes);
+        if (e == hipSuccess) e = acc->p_map.alloc(nodes * 3);
+        if (e == hipSuccess) e = acc->p_cnt.alloc(SC_WORDS);
+        if (e == hipSuccess) e = acc->d_side.alloc(nodes * 3);
+        if (e == hipSuccess) e = acc->d_cut.alloc(nodes);
+        if (e == hipSuccess) e = acc->p_side.alloc(nodes * 3);
+        if (e == hipSuccess) e = acc->p_cut.alloc(nodes);
         if (e == hipSuccess) e = hipMemset(acc->d_cnt, 0, SC_WORDS * 8);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->order.ev, hipEventDisableTiming);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking);
         if (e != hipSuccess) {
-            stree_free_dev(acc);
             delete acc;
             return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_stree_create: %s", hipGetErrorString(e));
         }
@@ -3693,16 +3537,7 @@ int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int we
     return TQ_OK;
 }
 
-void tq_stree_destroy(tq_stree *acc)
-{
-    if (!acc) return;
-    if (acc->ctx) {
-        (void)hipSetDevice(acc->ctx->device);
-        (void)acc->order.sync();
-        stree_free_dev(acc);
-    }
-    delete acc;
-}
+void tq_stree_destroy(tq_stree *acc) { delete acc; }
 
 int tq_stree_reset(tq_stree *acc)
 {
@@ -3957,27 +3792,15 @@ int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, 
         const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(acc->fit_bytes / (2 * T * T), FIT_MAX_CHUNK_TREES));
         const int64_t tab_trees = std::min(R, chunk);
         if (R > acc->fit_trees) {                                   // no fit is in flight: each one ends with a synchronisation
-            if (acc->d_fit_rec) (void)hipFree(acc->d_fit_rec);
-            if (acc->d_fit_out) (void)hipFree(acc->d_fit_out);
-            if (acc->p_fit_rec) (void)hipHostFree(acc->p_fit_rec);
-            if (acc->p_fit_out) (void)hipHostFree(acc->p_fit_out);
-            acc->d_fit_rec = acc->p_fit_rec = nullptr;
-            acc->d_fit_out = acc->p_fit_out = nullptr;
             acc->fit_trees = 0;
-            const size_t rec_bytes = (size_t)R * S * 4, out_bytes = ((size_t)R * FIT_WORDS + SC_WORDS) * 8;
-            TQ_HIP(ctx, hipMalloc((void **)&acc->d_fit_rec, rec_bytes));
-            TQ_HIP(ctx, hipMalloc((void **)&acc->d_fit_out, out_bytes));
-            TQ_HIP(ctx, hipHostMalloc((void **)&acc->p_fit_rec, rec_bytes, hipHostMallocDefault));
-            TQ_HIP(ctx, hipHostMalloc((void **)&acc->p_fit_out, out_bytes, hipHostMallocDefault));
+            const size_t rec = (size_t)R * S, res = (size_t)R * FIT_WORDS + SC_WORDS;
+            TQ_HIP(ctx, acc->d_fit_rec.alloc(rec));
+            TQ_HIP(ctx, acc->d_fit_out.alloc(res));
+            TQ_HIP(ctx, acc->p_fit_rec.alloc(rec));
+            TQ_HIP(ctx, acc->p_fit_out.alloc(res));
             acc->fit_trees = R;
         }
-        if (tab_trees > acc->fit_tab_trees) {
-            if (acc->d_fit_tab) (void)hipFree(acc->d_fit_tab);
-            acc->d_fit_tab = nullptr;
-            acc->fit_tab_trees = 0;
-            TQ_HIP(ctx, hipMalloc((void **)&acc->d_fit_tab, (size_t)tab_trees * T * T * 2));
-            acc->fit_tab_trees = tab_trees;
-        }
+        TQ_HIP(ctx, acc->d_fit_tab.grow((size_t)tab_trees * T * T));
         memset(acc->p_fit_rec, 0, (size_t)R * S * 4);
         for (int64_t r = 0; r < R; ++r) {
             int32_t *rec = acc->p_fit_rec + r * S;
@@ -4048,10 +3871,10 @@ int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const ui
             return TQ_OK;
         }
         TQ_HIP(ctx, hipSetDevice(ctx->device));
-        unsigned long long *d_mat = nullptr;
-        StreeNode *d_nodes = nullptr;
-        uint64_t *d_seeds = nullptr;
-        uint8_t *d_out = nullptr;                                   // side bytes, cut bytes, round bytes
+        DevBuf<unsigned long long> d_mat;                           // locals: every exit frees them
+        DevBuf<StreeNode> d_nodes;
+        DevBuf<uint64_t> d_seeds;
+        DevBuf<uint8_t> d_out;                                      // side bytes, cut bytes, round bytes
         std::vector<uint8_t> out((size_t)moff + 2 * (size_t)n_nodes);
         int rc = TQ_OK;
         auto step = [&](hipError_t e, const char *what) {
@@ -4059,10 +3882,10 @@ int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const ui
                 rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_stree_search: %s: %s", what,
                           hipGetErrorString(e));
         };
-        step(hipMalloc((void **)&d_mat, (size_t)cells * 16), "hipMalloc");
-        if (!rc) step(hipMalloc((void **)&d_nodes, (size_t)n_nodes * sizeof(StreeNode)), "hipMalloc");
-        if (!rc) step(hipMalloc((void **)&d_seeds, (size_t)n_nodes * 8), "hipMalloc");
-        if (!rc) step(hipMalloc((void **)&d_out, out.size()), "hipMalloc");
+        step(d_mat.alloc((size_t)cells * 2), "hipMalloc");
+        if (!rc) step(d_nodes.alloc((size_t)n_nodes), "hipMalloc");
+        if (!rc) step(d_seeds.alloc((size_t)n_nodes), "hipMalloc");
+        if (!rc) step(d_out.alloc(out.size()), "hipMalloc");
         if (!rc) step(hipMemcpy(d_mat, G, (size_t)cells * 8, hipMemcpyHostToDevice), "H2D");
         if (!rc) step(hipMemcpy(d_mat + cells, B, (size_t)cells * 8, hipMemcpyHostToDevice), "H2D");
         if (!rc) step(hipMemcpy(d_nodes, nodes.data(), (size_t)n_nodes * sizeof(StreeNode), hipMemcpyHostToDevice), "H2D");
@@ -4083,10 +3906,6 @@ int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const ui
         }
         if (!rc) step(hipDeviceSynchronize(), "sync");
         if (!rc) step(hipMemcpy(out.data(), d_out, out.size(), hipMemcpyDeviceToHost), "D2H");
-        if (d_mat) (void)hipFree(d_mat);
-        if (d_nodes) (void)hipFree(d_nodes);
-        if (d_seeds) (void)hipFree(d_seeds);
-        if (d_out) (void)hipFree(d_out);
         if (rc) return rc;
         memcpy(side, out.data(), (size_t)moff);
         memcpy(cut, out.data() + moff, (size_t)n_nodes);
@@ -4137,27 +3956,25 @@ int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx)
         a->gather_cap = std::max<int64_t>(1, CONS_GATHER_BYTES / (W * 8));
         const int64_t C = a->chunk_trees;
         hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_trees, (size_t)C * stride * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_masks, (size_t)C * nodes * W * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_keys, (size_t)C * nodes * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_unres, (size_t)C * nodes * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_slot_key, (size_t)a->slots * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_slot_idx, (size_t)a->slots * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_rep, (size_t)max_splits * W * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_count, (size_t)max_splits * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_ctr, CONS_CTR_WORDS * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&a->d_gather, (size_t)a->gather_cap * W * 8);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_trees, (size_t)C * stride * 4, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_gather, (size_t)a->gather_cap * W * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&a->p_ctr, CONS_CTR_WORDS * 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = a->d_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->d_masks.alloc((size_t)C * nodes * W);
+        if (e == hipSuccess) e = a->d_keys.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->d_unres.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->d_slot_key.alloc((size_t)a->slots);
+        if (e == hipSuccess) e = a->d_slot_idx.alloc((size_t)a->slots);
+        if (e == hipSuccess) e = a->d_rep.alloc((size_t)max_splits * W);
+        if (e == hipSuccess) e = a->d_count.alloc((size_t)max_splits);
+        if (e == hipSuccess) e = a->d_ctr.alloc(CONS_CTR_WORDS);
+        if (e == hipSuccess) e = a->d_gather.alloc((size_t)a->gather_cap * W);
+        if (e == hipSuccess) e = a->p_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->p_gather.alloc((size_t)a->gather_cap * W);
+        if (e == hipSuccess) e = a->p_ctr.alloc(CONS_CTR_WORDS);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
         if (e != hipSuccess) {
-            cons_free_dev(a);
             delete a;
             return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_cons_create: %s", hipGetErrorString(e));
         }
         if (int rc = cons_clear_dev(a)) {
-            cons_free_dev(a);
             delete a;
             return rc;
         }
@@ -4166,16 +3983,7 @@ int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx)
     return TQ_OK;
 }
 
-void tq_cons_destroy(tq_cons *acc)
-{
-    if (!acc) return;
-    if (acc->ctx) {
-        (void)hipSetDevice(acc->ctx->device);
-        (void)acc->order.sync();
-        cons_free_dev(acc);
-    }
-    delete acc;
-}
+void tq_cons_destroy(tq_cons *acc) { delete acc; }
 
 int tq_cons_reset(tq_cons *acc)
 {
@@ -4351,7 +4159,7 @@ int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t 
     if (!ctx) return TQ_ERR_INVALID_ARG;
     if (num_cu) *num_cu = ctx->prop.multiProcessorCount;
     if (waves_per_cu) *waves_per_cu = ctx->waves_per_cu;
-    if (row_pitch) *row_pitch = ctx->Sp;
+    if (row_pitch) *row_pitch = ctx->nat.Sp;
     return TQ_OK;
 }
 
