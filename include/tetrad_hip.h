@@ -633,6 +633,40 @@ int tq_dstat_jackknife(const uint32_t *bclasses, int64_t n_sets, int64_t B, cons
 int tq_dstat_jackknife_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
                            const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_out, void *stream);
 
+/* Pooled site-pattern classes of SPECIES sets per block of sites: the block rows of section 20
+ * for the species map of tq_set_species, so that tq_dstat_jackknife* give the block-jackknife D test between populations.
+ *   Rule: for a species set (A, B, C, D) and a site s let a[x], b[x], c[x], d[x] (x = 0..3) be the lineages of each
+ *   species with base x at s (a missing base counts nowhere; option "species_alleles": two lineages per sample).  The
+ *   pooled count of class k at s is the sum of a[x0] b[x1] c[x2] d[x3] over the patterns (x0, x1, x2, x3) of class k:
+ *   the number of lineage quartets (i in A, j in B, k in C, l in D) that show the class there.  Class 0 (xxxx) is always
+ *   0, under either value of "count_invariant", as the invariant bins of the pooled matrix are; slot 15 is the sum of
+ *   slots 1..14.  A block row is these counts summed over the block's sites; blocks and block_starts as above.  When
+ *   the blocks tile [0, S) the sum of a set's block rows equals the row tq_patterns_species writes, bit for bit.  The
+ *   counts are computed from the per-species base counts of the resident replicate (15 sums of products per site,
+ *   inverted once per row), not from 256 bins; u32, exact under the range rule of species mode.
+ *   tq_patterns_blocks_species      ssets u32[Q,4], host buffers, synchronous; classes u32[Q][B][16].  Refuses whatever
+ *                      the species calls refuse (no data, no map, a map for another T, the range rule S x product of the
+ *                      four largest species sizes >= 2^32, allele mode without a replicate built from the source), then
+ *                      NULL, negative Q, the block rule, an id >= K and a row not strictly ascending, all before
+ *                      anything is launched.  Q = 0 is valid.  Chunks by option "batch" as tq_patterns_blocks does.
+ *   tq_patterns_blocks_species_dev  d_ssets / d_classes device pointers (16-byte aligned or refused before anything is
+ *                      launched), enqueued on `stream` under the stream rule above: ordered behind a tq_bootstrap_async
+ *                      that rebuilds the layout, and the species table follows the replicate without a tq_set_species
+ *                      in between.  The rows are the caller's responsibility: an id >= K gives a row of zeros, and so
+ *                      does a row that repeats species so that S x its own lineage product reaches 2^32.  block_starts
+ *                      travels as in tq_patterns_blocks_dev.
+ *   Neither reads scan_method, phases, count_invariant or species_method (only a species_method the map's sizes do not
+ *   allow is refused, as by every species call); neither touches the count slab, records a timing mark or counts as a
+ *   call of tq_timing_read*.
+ *   tq_pooled_site_classes  host-only, no context: the rule for ONE site.  packed[4] = the four species' counts, each
+ *                      {n_A, n_C, n_G, n_T} as bytes 0..3 of a word; out[16] = the class row of that site, computed by
+ *                      the function the kernel runs (arithmetic modulo 2^32; counts up to 255^4 fit).               */
+int tq_patterns_blocks_species(tq_ctx *ctx, const uint32_t *ssets, int64_t Q, const int64_t *block_starts, int64_t B,
+                               uint32_t *classes);
+int tq_patterns_blocks_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, const int64_t *block_starts, int64_t B,
+                                   uint32_t *d_classes, void *stream);
+int tq_pooled_site_classes(const uint32_t packed[4], uint32_t out[16]);
+
 /* Site concordance factors per branch of a fixed tree: sCF / sDF1 / sDF2 / sN of Minh, Hahn &
  * Lanfear 2020 from the class rows above.  No reference counterpart in tetrad itself.
  *   Rule: a row is a set (a, b, c, d) with its class row u32[16] as the pattern calls write it.  The tree gives the

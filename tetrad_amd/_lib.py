@@ -44,6 +44,7 @@ SYMBOLS = [
     "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
     "tq_dstat_accumulate", "tq_dstat_accumulate_dev",
     "tq_patterns_blocks", "tq_patterns_blocks_dev", "tq_dstat_jackknife", "tq_dstat_jackknife_dev",
+    "tq_patterns_blocks_species", "tq_patterns_blocks_species_dev", "tq_pooled_site_classes",
     "tq_scf_create", "tq_scf_destroy", "tq_scf_reset", "tq_scf_add", "tq_scf_add_dev", "tq_scf_shape", "tq_scf_read",
 ]
 
@@ -269,6 +270,12 @@ def load() -> ctypes.CDLL:
     lib.tq_dstat_jackknife.restype = i32
     lib.tq_dstat_jackknife_dev.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, vp, vp]
     lib.tq_dstat_jackknife_dev.restype = i32
+    lib.tq_patterns_blocks_species.argtypes = [vp, vp, i64, vp, i64, vp]
+    lib.tq_patterns_blocks_species.restype = i32
+    lib.tq_patterns_blocks_species_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    lib.tq_patterns_blocks_species_dev.restype = i32
+    lib.tq_pooled_site_classes.argtypes = [vp, vp]
+    lib.tq_pooled_site_classes.restype = i32
     lib.tq_scf_create.argtypes = [c.POINTER(vp), vp, i64, i64, vp]
     lib.tq_scf_create.restype = i32
     lib.tq_scf_destroy.argtypes = [vp]

@@ -39,6 +39,7 @@
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
+//   species_blocks.hpp tq_species_blocks_kernel: pooled class rows of species sets per block of sites from the species table
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -88,6 +89,7 @@ namespace {
 #include "fit.hpp"
 #include "patterns.hpp"
 #include "pattern_blocks.hpp"
+#include "species_blocks.hpp"
 #include "scf.hpp"
 
 }  // namespace
@@ -961,14 +963,11 @@ int species_ready(tq_ctx *ctx, const char *who)
     return TQ_OK;
 }
 
-// Stage 1 of a species pass: (re)build the species table if the resident data changed, then the pooled counts of
-// species quartets dsq[0..n) into the count slab, where stage_svd finds them as it finds a scanned batch.
-int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t stream)
+// The species table of the resident replicate, both layouts: rebuilt on `stream` when the resident data (or the lineage
+// mode) changed since it was built, from the nibble rows or, in allele mode, from the IUPAC source.  The caller has
+// passed species_ready.  Touches nothing but the table: no slab, no timing mark.
+int ensure_species_table(tq_ctx *ctx, hipStream_t stream)
 {
-    int rc = ensure_cm(ctx, n);
-    if (rc) return rc;
-    ctx->scanned_Q = 0;
-    if ((rc = mark(ctx, TAG_ORIGIN, stream))) return rc;
     if (ctx->sp_tab_gen != ctx->data_gen) {
         const int64_t Sp = ctx->nat.Sp, entries = ctx->sp_K * Sp;
         if ((size_t)entries * 2 > ctx->d_sp_tab.cap()) {
@@ -989,11 +988,28 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
         TQ_HIP(ctx, hipGetLastError());
         ctx->sp_tab_gen = ctx->data_gen;
     }
+    return TQ_OK;
+}
+
+// the offsets the species kernels read for the per-row range rule: in allele mode the copy whose differences are 2n
+inline const int32_t *species_lineage_offsets(const tq_ctx *ctx)
+{
+    return species_lineages(ctx) == 2 ? ctx->d_sp_members + ctx->sp_K + 1 + ctx->sp_T : ctx->d_sp_members;
+}
+
+// Stage 1 of a species pass: (re)build the species table if the resident data changed, then the pooled counts of
+// species quartets dsq[0..n) into the count slab, where stage_svd finds them as it finds a scanned batch.
+int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t stream)
+{
+    int rc = ensure_cm(ctx, n);
+    if (rc) return rc;
+    ctx->scanned_Q = 0;
+    if ((rc = mark(ctx, TAG_ORIGIN, stream))) return rc;
+    if ((rc = ensure_species_table(ctx, stream))) return rc;
     if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
     const int lin = species_lineages(ctx);
     const bool mfma = ctx->species_method == 1 || (ctx->species_method < 0 && lin * ctx->sp_max <= SPECIES_MFMA_MAX);
-    // the pooled kernels read offsets for the per-row range rule only: in allele mode the copy whose differences are 2n
-    const int32_t *offsets = lin == 2 ? ctx->d_sp_members + ctx->sp_K + 1 + ctx->sp_T : ctx->d_sp_members;
+    const int32_t *offsets = species_lineage_offsets(ctx);      // read for the per-row range rule only
     if (mfma)
         hipLaunchKernelGGL(tq_species_mfma_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
                            (const uint8_t *)(ctx->d_sp_tab + ctx->sp_K * ctx->nat.Sp), ctx->nat.Sp, ctx->S, dsq, n,
@@ -1487,10 +1503,11 @@ int check_dstat_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n
     return TQ_OK;
 }
 
-// Block rows (pattern_blocks.hpp).  What both forms check before anything is launched: the data and the block rule.
-int blocks_ready(tq_ctx *ctx, const char *who, const int64_t *block_starts, int64_t B)
+// Block rows (pattern_blocks.hpp; of species sets with `species`, species_blocks.hpp).  What every form checks before
+// anything is launched: the data (and the species map) and the block rule.
+int blocks_ready(tq_ctx *ctx, const char *who, bool species, const int64_t *block_starts, int64_t B)
 {
-    if (int rc = check_ready(ctx, 0)) return rc;
+    if (int rc = species ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
     if (B < 1 || B > PBLK_MAX_BLOCKS)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
     if (block_starts[0] < 0)
@@ -1541,6 +1558,90 @@ int launch_pattern_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B,
         TQ_HIP(ctx, hipGetLastError());
     }
     return TQ_OK;
+}
+
+// Block rows of species sets dq[0..Q) from the species table (species_blocks.hpp), which is brought up to date on this
+// stream first; the boundaries are in ctx->d_bstarts on this stream.  Neither the count slab nor the timing marks are touched.
+int launch_species_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
+{
+    if (int rc = ensure_species_table(ctx, stream)) return rc;
+    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets: a launch holds fewer than 2^31 items
+    for (int64_t q0 = 0; q0 < Q; q0 += per) {
+        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
+        const int64_t items = n * B;
+        hipLaunchKernelGGL(tq_species_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
+                           0, stream, (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S, (uint32_t)ctx->sp_K,
+                           species_lineage_offsets(ctx), dq + q0 * 4, n, (const int64_t *)ctx->d_bstarts, B,
+                           d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
+        TQ_HIP(ctx, hipGetLastError());
+    }
+    return TQ_OK;
+}
+
+// host sets -> host block rows (synchronous): tq_patterns_blocks and, with `species`, tq_patterns_blocks_species
+int blocks_to_host(tq_ctx *ctx, const char *who, bool species, const uint32_t *sets, int64_t Q, const int64_t *block_starts,
+                   int64_t B, uint32_t *classes)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || !block_starts || (Q > 0 && (!sets || !classes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+    int rc = blocks_ready(ctx, who, species, block_starts, B);
+    if (rc) return rc;
+    const uint32_t bound = (uint32_t)(species ? ctx->sp_K : ctx->T);
+    for (int64_t i = 0; i < Q; ++i) {
+        const uint32_t *q = sets + 4 * i;
+        if ((q[0] >= bound) | (q[1] >= bound) | (q[2] >= bound) | (q[3] >= bound))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= %s=%u", who, (long long)i, species ? "K" : "T", bound);
+        if (!((q[0] < q[1]) & (q[1] < q[2]) & (q[2] < q[3])))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
+                        q[0], q[1], q[2], q[3]);
+    }
+    if (Q == 0) return TQ_OK;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
+    int64_t chunk = ctx->batch / B;
+    if (chunk < 1) chunk = 1;
+    if (chunk > Q) chunk = Q;
+    const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
+    const size_t o_cls = align_up((size_t)chunk * 16, 256);
+    TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
+    if ((rc = ensure_streams(ctx))) return rc;
+    char *base = ctx->d_scratch;
+    uint32_t *d_classes = (uint32_t *)(base + o_cls);
+    rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
+    for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
+        const int64_t n = (Q - q0) < chunk ? (Q - q0) : chunk;
+        if (hipMemcpyAsync(base, sets + q0 * 4, (size_t)n * 16, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
+            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the sets failed", who);
+        if (!rc)
+            rc = species ? launch_species_blocks(ctx, (const uint32_t *)base, n, B, d_classes, ctx->sK)
+                         : launch_pattern_blocks(ctx, (const uint32_t *)base, n, B, d_classes, ctx->sK);
+        if (!rc && hipMemcpyAsync((char *)classes + (size_t)q0 * row_bytes, d_classes, (size_t)n * row_bytes, hipMemcpyDeviceToHost,
+                                  ctx->sK) != hipSuccess)
+            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the block rows failed", who);
+    }
+    if (hipStreamSynchronize(ctx->sK) != hipSuccess && !rc) rc = fail(ctx, TQ_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+    return rc;
+}
+
+// device sets -> device block rows, enqueued on `stream`
+int blocks_dev(tq_ctx *ctx, const char *who, bool species, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts,
+               int64_t B, uint32_t *d_classes, hipStream_t stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (Q < 0 || !block_starts || (Q > 0 && (!d_sets || !d_classes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+    if (int rc = blocks_ready(ctx, who, species, block_starts, B)) return rc;
+    if (Q == 0) return TQ_OK;
+    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
+    int rc = stage_block_starts(ctx, block_starts, B, stream);
+    if (!rc)
+        rc = species ? launch_species_blocks(ctx, d_sets, Q, B, d_classes, stream)
+                     : launch_pattern_blocks(ctx, d_sets, Q, B, d_classes, stream);
+    return note_dev_api(ctx, stream, rc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2583,64 +2684,35 @@ int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_se
 
 int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64_t *block_starts, int64_t B, uint32_t *classes)
 {
-    const char *who = "tq_patterns_blocks";
-    if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || !block_starts || (Q > 0 && (!sets || !classes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    int rc = blocks_ready(ctx, who, block_starts, B);
-    if (rc) return rc;
-    const uint32_t bound = (uint32_t)ctx->T;
-    for (int64_t i = 0; i < Q; ++i) {
-        const uint32_t *q = sets + 4 * i;
-        if ((q[0] >= bound) | (q[1] >= bound) | (q[2] >= bound) | (q[3] >= bound))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= T=%u", who, (long long)i, bound);
-        if (!((q[0] < q[1]) & (q[1] < q[2]) & (q[2] < q[3])))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
-                        q[0], q[1], q[2], q[3]);
-    }
-    if (Q == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
-    int64_t chunk = ctx->batch / B;
-    if (chunk < 1) chunk = 1;
-    if (chunk > Q) chunk = Q;
-    const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
-    const size_t o_cls = align_up((size_t)chunk * 16, 256);
-    TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
-    if ((rc = ensure_streams(ctx))) return rc;
-    char *base = ctx->d_scratch;
-    uint32_t *d_classes = (uint32_t *)(base + o_cls);
-    rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
-    for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
-        const int64_t n = (Q - q0) < chunk ? (Q - q0) : chunk;
-        if (hipMemcpyAsync(base, sets + q0 * 4, (size_t)n * 16, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
-            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the sets failed", who);
-        if (!rc) rc = launch_pattern_blocks(ctx, (const uint32_t *)base, n, B, d_classes, ctx->sK);
-        if (!rc && hipMemcpyAsync((char *)classes + (size_t)q0 * row_bytes, d_classes, (size_t)n * row_bytes, hipMemcpyDeviceToHost,
-                                  ctx->sK) != hipSuccess)
-            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the block rows failed", who);
-    }
-    if (hipStreamSynchronize(ctx->sK) != hipSuccess && !rc) rc = fail(ctx, TQ_ERR_HIP, "%s: hipStreamSynchronize failed", who);
-    return rc;
+    return blocks_to_host(ctx, "tq_patterns_blocks", false, sets, Q, block_starts, B, classes);
 }
 
 int tq_patterns_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts, int64_t B,
-                           uint32_t *d_classes, void *stream_)
+                           uint32_t *d_classes, void *stream)
 {
-    const char *who = "tq_patterns_blocks_dev";
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || !block_starts || (Q > 0 && (!d_sets || !d_classes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    if (int rc = blocks_ready(ctx, who, block_starts, B)) return rc;
-    if (Q == 0) return TQ_OK;
-    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
-    int rc = stage_block_starts(ctx, block_starts, B, stream);
-    if (!rc) rc = launch_pattern_blocks(ctx, d_sets, Q, B, d_classes, stream);
-    return note_dev_api(ctx, stream, rc);
+    return blocks_dev(ctx, "tq_patterns_blocks_dev", false, d_sets, Q, block_starts, B, d_classes, (hipStream_t)stream);
+}
+
+int tq_patterns_blocks_species(tq_ctx *ctx, const uint32_t *ssets, int64_t Q, const int64_t *block_starts, int64_t B,
+                               uint32_t *classes)
+{
+    return blocks_to_host(ctx, "tq_patterns_blocks_species", true, ssets, Q, block_starts, B, classes);
+}
+
+int tq_patterns_blocks_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, const int64_t *block_starts, int64_t B,
+                                   uint32_t *d_classes, void *stream)
+{
+    return blocks_dev(ctx, "tq_patterns_blocks_species_dev", true, d_ssets, Q, block_starts, B, d_classes, (hipStream_t)stream);
+}
+
+int tq_pooled_site_classes(const uint32_t *packed, uint32_t *out)
+{
+    if (!packed || !out) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_pooled_site_classes: NULL pointer");
+    uint32_t f[PAT_CLASSES] = {}, row[PAT_ROW];
+    pooled_site_f(packed[0], packed[1], packed[2], packed[3], f);
+    pooled_invert(f, row);
+    memcpy(out, row, sizeof(row));
+    return TQ_OK;
 }
 
 int tq_dstat_jackknife(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint8_t *ia,

@@ -324,6 +324,22 @@ class QuartetEngine:
         b = self._block_starts(block_starts)
         self._check(self._lib.tq_patterns_blocks_dev(self._h, d_sets, Q, _ptr(b), b.shape[0] - 1, d_classes, stream or None))
 
+    def patterns_blocks_species(self, ssets, block_starts) -> np.ndarray:
+        """Block rows u32[Q,B,16] of strictly ascending SPECIES quartets: per block the pooled
+        class counts of the lineage combinations, class 0 always 0, slot 15 the sum.  Needs `set_species`."""
+        s, b = self._sets(ssets), self._block_starts(block_starts)
+        B = b.shape[0] - 1
+        classes = np.zeros((s.shape[0], B, 16), np.uint32)
+        self._check(self._lib.tq_patterns_blocks_species(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
+        return classes
+
+    def patterns_blocks_species_dev(self, d_ssets: int, Q: int, block_starts, d_classes: int, stream: int = 0):
+        """The same with device pointers (u32[Q,4] in, u32[Q,B,16] out), enqueued on `stream`; `block_starts` is a host
+        array, read before the call returns.  The rows are the caller's responsibility (an id >= K gives zeros)."""
+        b = self._block_starts(block_starts)
+        self._check(self._lib.tq_patterns_blocks_species_dev(self._h, d_ssets, Q, _ptr(b), b.shape[0] - 1, d_classes,
+                                                             stream or None))
+
     def dstat_jackknife_dev(self, d_bclasses: int, n_sets: int, B: int, d_set_of: int, d_ia: int, d_ib: int, N: int,
                             d_out: int, stream: int = 0):
         """The delete-one-block jackknife of N D tests on `stream`: test t reads ABBA at d_bclasses[d_set_of[t]][j][d_ia[t]]

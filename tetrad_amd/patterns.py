@@ -12,7 +12,8 @@ into the unique ascending sets and, per test, the row and the two class indices 
 `run_dstat_jackknife` is the same test with the error estimate everyone else uses: the sites
 are cut into contiguous blocks (`locus_blocks`), one pass writes the class rows of every (set, block)
 (`QuartetEngine.patterns_blocks_dev`) and one kernel per chunk of sets runs the delete-one-block jackknife of every
-test (`dstat_jackknife_dev`) -- no replicate is built and nothing is rescanned.
+test (`dstat_jackknife_dev`) -- no replicate is built and nothing is rescanned.  With `species_of` the tests name
+species and the block rows are the pooled ones of `patterns_blocks_species_dev`.
 
 `run_dstat` is the whole bootstrap test: observed counts from the given matrix, then locus-bootstrap replicates built on the
 device, each followed on the same stream by the class rows of the unique sets and one accumulation kernel.  Nothing
@@ -278,14 +279,17 @@ def dstat_jackknife(bclasses, set_of, ia, ib) -> np.ndarray:
 
 
 def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: int = 50, block_starts=None,
-                        chunk: int = 1 << 16, *, resident: bool = False) -> np.ndarray:
+                        chunk: int = 1 << 16, *, resident: bool = False, species_of=None) -> np.ndarray:
     """D tests with a block jackknife, full mode.  `set_data(tmparr, tmpmap)`, then the unique sets of `tests`
     int[N,4] = (P1, P2, P3, O) in chunks of `chunk`: the block rows of the chunk (`patterns_blocks_dev`, torch memory of
     chunk x B x 64 bytes, re-used) and the jackknife of the chunk's tests (`dstat_jackknife_dev`), all on the current
     stream; one device-to-host copy at the end.  The blocks are `block_starts` i64[B + 1] or, without it,
     `locus_blocks(tmpmap, nblocks)`.  With `resident=True` nothing is loaded: the tests run on the replicate the engine
     holds (after `engine.bootstrap`, say); `tmparr` is not read, and `tmpmap` may be None when `block_starts` is given
-    (else the resident locus column is fetched for the cuts).
+    (else the resident locus column is fetched for the cuts).  With `species_of` (i32[T], see
+    `QuartetEngine.set_species`) the tests name species and the block rows are those of the pooled lineages
+    (`patterns_blocks_species_dev`); the map is set after `set_data` or, with `resident=True`, on the resident replicate
+    (the way to allele mode: `set_source`, `bootstrap`, option "species_alleles", then `resident=True`).
     Returns a structured array per test: abba, baba, bbaa, nsites (sums over the blocks), D, jk_blocks, jk_mean,
     jk_se, Z = D / jk_se; NaN where undefined."""
     import torch
@@ -294,6 +298,9 @@ def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: i
     sets, set_of, idx = _role_classes(tests, (ABBA, BABA, BBAA))
     if not resident:
         engine.set_data(tmparr, tmpmap)
+    if species_of is not None:
+        engine.set_species(species_of)
+    block_rows_dev = engine.patterns_blocks_dev if species_of is None else engine.patterns_blocks_species_dev
     if block_starts is None:
         if tmpmap is None:
             tmpmap = engine.get_data()[1]
@@ -316,11 +323,12 @@ def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: i
         d_ia = torch.from_numpy(np.ascontiguousarray(idx[order, 0])).to(dev)
         d_ib = torch.from_numpy(np.ascontiguousarray(idx[order, 1])).to(dev)
         d_rows = torch.empty((chunk, B, 16), dtype=torch.int32, device=dev)
-        d_sum = torch.empty((M, 16), dtype=torch.int32, device=dev)     # u32 sums: a set counts at most S < 2^32 sites
+        # u32 sums: a set counts at most S < 2^32 sites (a species set: below 2^32 by the range rule of species mode)
+        d_sum = torch.empty((M, 16), dtype=torch.int32, device=dev)
         d_out = torch.empty((N, 4), dtype=torch.float64, device=dev)
         for q0 in range(0, M, chunk):
             n = min(chunk, M - q0)
-            engine.patterns_blocks_dev(d_sets.data_ptr() + 16 * q0, n, starts, d_rows.data_ptr(), cur.cuda_stream)
+            block_rows_dev(d_sets.data_ptr() + 16 * q0, n, starts, d_rows.data_ptr(), cur.cuda_stream)
             torch.sum(d_rows[:n], dim=1, dtype=torch.int32, out=d_sum[q0:q0 + n])
             t0, t1 = (int(v) for v in np.searchsorted(s_sorted, [q0, q0 + n], side="left"))
             if t1 > t0:
