@@ -667,6 +667,47 @@ int tq_patterns_blocks_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t
                                    uint32_t *d_classes, void *stream);
 int tq_pooled_site_classes(const uint32_t packed[4], uint32_t out[16]);
 
+/* Five-taxon site-pattern classes per block of sites and the block jackknife on sums of slots: what
+ * DFOIL (Pease & Hahn 2015) and partitioned D (Eaton & Ree 2013) are read from.  No reference counterpart in tetrad itself.
+ *   Rule (full mode only): a set is five taxa t0 < t1 < t2 < t3 < t4 with bases x0..x4 at a site.  The site is counted
+ *   when none of the five is missing and they take exactly two distinct values; its class is
+ *   k = sum over i = 1..4 of [x_i != x_0] 2^(i - 1), in 1..15 (unpolarised: every role assignment is a relabelling on the
+ *   host).  Invariant sites and sites with three or four bases count nowhere; "count_invariant" is not read.  A block
+ *   row is u32[16]: slot k = the count of class k for k = 1..15, slot 0 = the sum of slots 1..15.  block_starts and B as
+ *   in tq_patterns_blocks.
+ *   tq_quintet_class_table  host-only: out u8[1024], index 256 x0 + 64 x1 + 16 x2 + 4 x3 + x4; 0 = not counted, else the
+ *                      class 1..15, from the function the kernel's masks are checked against at compile time.
+ *   tq_patterns_quintet_blocks      sets5 u32[Q,5], host buffers, synchronous; classes u32[Q][B][16].  Validated as
+ *                      tq_patterns_blocks validates (NULL, negative Q, no data, an index >= T, a row not strictly
+ *                      ascending, the block rule), all before anything is launched.  Q = 0 is valid.  Chunks by option
+ *                      "batch" as tq_patterns_blocks does.
+ *   tq_patterns_quintet_blocks_dev  d_sets5 (4-byte aligned) / d_classes (16-byte aligned; either misaligned is refused
+ *                      before anything is launched) device pointers, enqueued on `stream` under the stream rule above, so
+ *                      ordered behind a tq_bootstrap_async that rebuilds the layout.  The rows are the caller's
+ *                      responsibility (an index >= T gives rows of zeros).  block_starts travels as in
+ *                      tq_patterns_blocks_dev.
+ *   Both read the natural layout always and no option but, in the host form, "batch"; neither records a timing mark or
+ *   counts as a call of tq_timing_read*.
+ *   tq_dstat_jackknife_masks_dev  one thread per test, one launch on `stream`: the jackknife of tq_dstat_jackknife_dev,
+ *                      operation for operation (one definition serves both), with a_j = the sum of the slots of block
+ *                      row j whose bit is set in lmask[t] and b_j the same for rmask[t] (u16 arrays; bit k = slot k).
+ *                      a_j + b_j <= 15 (2^32 - 1), n < 2^48: every integer is exact.  OVERWRITES out f64[N][4] =
+ *                      {g, theta, theta_J, var}.  A test is valid when bit 0 is clear in both masks, both are non-empty
+ *                      and they are disjoint; an invalid test, or one whose set_of >= n_sets, is skipped without
+ *                      touching memory.  1 <= B <= 4096.  Works on any u32[.][B][16] rows, the four-taxon ones included.
+ *   tq_dstat_jackknife_masks  the host execution (no context; messages go to tq_last_error(NULL)); an invalid test, or B
+ *                      outside 1..4096, is refused (TQ_ERR_INVALID_ARG) and nothing is written.                       */
+int tq_quintet_class_table(uint8_t out[1024]);
+int tq_patterns_quintet_blocks(tq_ctx *ctx, const uint32_t *sets5, int64_t Q, const int64_t *block_starts, int64_t B,
+                               uint32_t *classes);
+int tq_patterns_quintet_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets5, int64_t Q, const int64_t *block_starts, int64_t B,
+                                   uint32_t *d_classes, void *stream);
+int tq_dstat_jackknife_masks(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of,
+                             const uint16_t *lmask, const uint16_t *rmask, int64_t N, double *out);
+int tq_dstat_jackknife_masks_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B,
+                                 const uint32_t *d_set_of, const uint16_t *d_lmask, const uint16_t *d_rmask, int64_t N,
+                                 double *d_out, void *stream);
+
 /* Site concordance factors per branch of a fixed tree: sCF / sDF1 / sDF2 / sN of Minh, Hahn &
  * Lanfear 2020 from the class rows above.  No reference counterpart in tetrad itself.
  *   Rule: a row is a set (a, b, c, d) with its class row u32[16] as the pattern calls write it.  The tree gives the

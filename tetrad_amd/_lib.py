@@ -45,6 +45,8 @@ SYMBOLS = [
     "tq_dstat_accumulate", "tq_dstat_accumulate_dev",
     "tq_patterns_blocks", "tq_patterns_blocks_dev", "tq_dstat_jackknife", "tq_dstat_jackknife_dev",
     "tq_patterns_blocks_species", "tq_patterns_blocks_species_dev", "tq_pooled_site_classes",
+    "tq_quintet_class_table", "tq_patterns_quintet_blocks", "tq_patterns_quintet_blocks_dev",
+    "tq_dstat_jackknife_masks", "tq_dstat_jackknife_masks_dev",
     "tq_scf_create", "tq_scf_destroy", "tq_scf_reset", "tq_scf_add", "tq_scf_add_dev", "tq_scf_shape", "tq_scf_read",
 ]
 
@@ -276,6 +278,16 @@ def load() -> ctypes.CDLL:
     lib.tq_patterns_blocks_species_dev.restype = i32
     lib.tq_pooled_site_classes.argtypes = [vp, vp]
     lib.tq_pooled_site_classes.restype = i32
+    lib.tq_quintet_class_table.argtypes = [vp]
+    lib.tq_quintet_class_table.restype = i32
+    lib.tq_patterns_quintet_blocks.argtypes = [vp, vp, i64, vp, i64, vp]
+    lib.tq_patterns_quintet_blocks.restype = i32
+    lib.tq_patterns_quintet_blocks_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    lib.tq_patterns_quintet_blocks_dev.restype = i32
+    lib.tq_dstat_jackknife_masks.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
+    lib.tq_dstat_jackknife_masks.restype = i32
+    lib.tq_dstat_jackknife_masks_dev.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, vp, vp]
+    lib.tq_dstat_jackknife_masks_dev.restype = i32
     lib.tq_scf_create.argtypes = [c.POINTER(vp), vp, i64, i64, vp]
     lib.tq_scf_create.restype = i32
     lib.tq_scf_destroy.argtypes = [vp]

@@ -148,23 +148,36 @@ __global__ __launch_bounds__(PBLK_THREADS) void tq_pattern_blocks_kernel(const u
     }
 }
 
-// The delete-one-block jackknife of one test.  rows = the B block rows u32[B][16] of the test's set, ca / cb = the classes
-// that play ABBA and BABA.  Returns {g, theta, theta_J, var}: g = blocks with a_j + b_j > 0, theta = (A - Bs) / n over all
+// The delete-one-block jackknife of one test.  rows = the B block rows u32[B][16] of the test's set, fetch = how a row
+// gives (a_j, b_j): the classes that play ABBA and BABA (JackknifeClassPair) or two sums of slots (quintet_blocks.hpp).  Returns {g, theta, theta_J, var}: g = blocks with a_j + b_j > 0, theta = (A - Bs) / n over all
 // blocks, theta_J the jackknife estimate and var the jackknife variance with block weight m_j = a_j + b_j (Busing et
-// al. 1999).  n = 0: {0, NaN, NaN, NaN}; g < 2: {g, theta, NaN, NaN}.  The integers are exact (B <= 4096 counts below
-// 2^32: n < 2^45).  Every floating operation is one correctly rounded f64 operation in the order written: contraction
+// al. 1999).  n = 0: {0, NaN, NaN, NaN}; g < 2: {g, theta, NaN, NaN}.  The integers are exact (B <= 4096 blocks
+// of at most 15 slots below 2^32 a side: n < 2^48).  Every floating operation is one correctly rounded f64 operation in the order written: contraction
 // is off for this function (see dstat_add, patterns.hpp), so the products and sums stay apart on the device as well.
 struct JackknifeRow {
     double g, theta, theta_j, var;
 };
 
-__host__ __device__ __forceinline__ JackknifeRow dstat_jackknife_row(const uint32_t *rows, int64_t B, uint32_t ca, uint32_t cb)
+// How a block's (a_j, b_j) is fetched from its row: the class-index form of the four-taxon D test.  The mask form of
+// quintet_blocks.hpp (sums of slots) is the other instantiation; the rule below is stated once for both.
+struct JackknifeClassPair {
+    uint32_t ca, cb;
+    __host__ __device__ __forceinline__ void operator()(const uint32_t *row, uint64_t &a, uint64_t &b) const
+    {
+        a = row[ca];
+        b = row[cb];
+    }
+};
+
+template <class Fetch>
+__host__ __device__ __forceinline__ JackknifeRow dstat_jackknife_row(const uint32_t *rows, int64_t B, const Fetch fetch)
 {
 #pragma clang fp contract(off)
     const double qnan = __builtin_bit_cast(double, (uint64_t)0x7FF8000000000000ull);
     uint64_t A = 0, Bs = 0, g = 0;
     for (int64_t j = 0; j < B; ++j) {
-        const uint64_t a = rows[j * PAT_ROW + ca], b = rows[j * PAT_ROW + cb];
+        uint64_t a, b;
+        fetch(rows + j * PAT_ROW, a, b);
         A += a;
         Bs += b;
         g += (a + b) > 0 ? 1u : 0u;
@@ -176,7 +189,9 @@ __host__ __device__ __forceinline__ JackknifeRow dstat_jackknife_row(const uint3
     if (g < 2) return JackknifeRow{gf, theta, qnan, qnan};
     double sJ = 0.0;
     for (int64_t j = 0; j < B; ++j) {
-        const uint64_t a = rows[j * PAT_ROW + ca], b = rows[j * PAT_ROW + cb], m = a + b;
+        uint64_t a, b;
+        fetch(rows + j * PAT_ROW, a, b);
+        const uint64_t m = a + b;
         if (m == 0) continue;
         const double r = (double)(n - m);
         const double tj = (double)((int64_t)(A - a) - (int64_t)(Bs - b)) / r;
@@ -188,7 +203,9 @@ __host__ __device__ __forceinline__ JackknifeRow dstat_jackknife_row(const uint3
     const double thetaJ = gt - sJ;
     double sV = 0.0;
     for (int64_t j = 0; j < B; ++j) {
-        const uint64_t a = rows[j * PAT_ROW + ca], b = rows[j * PAT_ROW + cb], m = a + b;
+        uint64_t a, b;
+        fetch(rows + j * PAT_ROW, a, b);
+        const uint64_t m = a + b;
         if (m == 0) continue;
         const double r = (double)(n - m);
         const double tj = (double)((int64_t)(A - a) - (int64_t)(Bs - b)) / r;
@@ -218,7 +235,7 @@ __global__ __launch_bounds__(JK_THREADS) void tq_dstat_jackknife_kernel(const ui
     const uint32_t s = set_of[t];
     const uint32_t ca = ia[t], cb = ib[t];
     if ((int64_t)s >= n_sets || ca >= (uint32_t)PAT_CLASSES || cb >= (uint32_t)PAT_CLASSES) return;
-    const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)s * B * PAT_ROW, B, ca, cb);
+    const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)s * B * PAT_ROW, B, JackknifeClassPair{ca, cb});
     out[4 * t + 0] = r.g;
     out[4 * t + 1] = r.theta;
     out[4 * t + 2] = r.theta_j;
@@ -230,7 +247,7 @@ inline void dstat_jackknife_host(const uint32_t *bclasses, int64_t B, const uint
                                  const uint8_t *ib, int64_t N, double *out)
 {
     for (int64_t t = 0; t < N; ++t) {
-        const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)set_of[t] * B * PAT_ROW, B, ia[t], ib[t]);
+        const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)set_of[t] * B * PAT_ROW, B, JackknifeClassPair{ia[t], ib[t]});
         out[4 * t + 0] = r.g;
         out[4 * t + 1] = r.theta;
         out[4 * t + 2] = r.theta_j;

@@ -40,6 +40,8 @@
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
 //   species_blocks.hpp tq_species_blocks_kernel: pooled class rows of species sets per block of sites from the species table
+//   quintet_blocks.hpp tq_quintet_blocks_kernel: five-taxon class rows per block of sites + tq_dstat_jackknife_masks_kernel:
+//                 the block jackknife on sums of slots (DFOIL, partitioned D)
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -90,6 +92,7 @@ namespace {
 #include "patterns.hpp"
 #include "pattern_blocks.hpp"
 #include "species_blocks.hpp"
+#include "quintet_blocks.hpp"
 #include "scf.hpp"
 
 }  // namespace
@@ -1503,11 +1506,36 @@ int check_dstat_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n
     return TQ_OK;
 }
 
-// Block rows (pattern_blocks.hpp; of species sets with `species`, species_blocks.hpp).  What every form checks before
-// anything is launched: the data (and the species map) and the block rule.
-int blocks_ready(tq_ctx *ctx, const char *who, bool species, const int64_t *block_starts, int64_t B)
+// The same for the mask forms of the jackknife (quintet_blocks.hpp): a test is two u16 slot masks.
+int check_dstat_mask_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n_sets, int64_t B, const uint32_t *set_of,
+                           const uint16_t *lmask, const uint16_t *rmask, int64_t N, bool host_arrays)
 {
-    if (int rc = species ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
+    if (N < 0 || n_sets < 0 || (N > 0 && (!rows_and_out || !set_of || !lmask || !rmask)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative size", who);
+    if (B < 1 || B > PBLK_MAX_BLOCKS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
+    for (int64_t t = 0; host_arrays && t < N; ++t) {
+        if ((int64_t)set_of[t] >= n_sets)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: test %lld has set_of=%u >= n_sets=%lld", who, (long long)t, set_of[t],
+                        (long long)n_sets);
+        if (!jackknife_masks_valid(lmask[t], rmask[t]))
+            return fail(ctx, TQ_ERR_INVALID_ARG,
+                        "%s: test %lld has masks 0x%04x / 0x%04x: bit 0 must be clear, both non-empty, and disjoint", who,
+                        (long long)t, (unsigned)lmask[t], (unsigned)rmask[t]);
+    }
+    return TQ_OK;
+}
+
+// Block rows: of quartets (pattern_blocks.hpp), of species quartets (species_blocks.hpp) or of five-taxon sets
+// (quintet_blocks.hpp).
+enum BlockKind { BLK_QUARTET, BLK_SPECIES, BLK_QUINTET };
+
+constexpr int block_set_width(BlockKind kind) { return kind == BLK_QUINTET ? QNT_TAXA : 4; }
+
+// What every form checks before anything is launched: the data (and the species map) and the block rule.
+int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *block_starts, int64_t B)
+{
+    if (int rc = kind == BLK_SPECIES ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
     if (B < 1 || B > PBLK_MAX_BLOCKS)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
     if (block_starts[0] < 0)
@@ -1578,23 +1606,56 @@ int launch_species_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B,
     return TQ_OK;
 }
 
-// host sets -> host block rows (synchronous): tq_patterns_blocks and, with `species`, tq_patterns_blocks_species
-int blocks_to_host(tq_ctx *ctx, const char *who, bool species, const uint32_t *sets, int64_t Q, const int64_t *block_starts,
+// Block rows of five-taxon sets dq[0..Q) (u32[Q][5]) into d_classes [Q][B][16]; the boundaries are in ctx->d_bstarts on
+// this stream.  Always the natural layout.  A launch holds fewer than 2^31 items.
+int launch_quintet_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
+{
+    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
+    for (int64_t q0 = 0; q0 < Q; q0 += per) {
+        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
+        const int64_t items = n * B;
+        hipLaunchKernelGGL(tq_quintet_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
+                           0, stream, (const uint32_t *)ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T, dq + q0 * QNT_TAXA, n,
+                           (const int64_t *)ctx->d_bstarts, B, d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
+        TQ_HIP(ctx, hipGetLastError());
+    }
+    return TQ_OK;
+}
+
+int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
+{
+    switch (kind) {
+    case BLK_SPECIES: return launch_species_blocks(ctx, dq, Q, B, d_classes, stream);
+    case BLK_QUINTET: return launch_quintet_blocks(ctx, dq, Q, B, d_classes, stream);
+    default: return launch_pattern_blocks(ctx, dq, Q, B, d_classes, stream);
+    }
+}
+
+// host sets -> host block rows (synchronous): tq_patterns_blocks, tq_patterns_blocks_species and tq_patterns_quintet_blocks
+int blocks_to_host(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *sets, int64_t Q, const int64_t *block_starts,
                    int64_t B, uint32_t *classes)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
     if (Q < 0 || !block_starts || (Q > 0 && (!sets || !classes)))
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    int rc = blocks_ready(ctx, who, species, block_starts, B);
+    int rc = blocks_ready(ctx, who, kind, block_starts, B);
     if (rc) return rc;
+    const bool species = kind == BLK_SPECIES;
+    const int width = block_set_width(kind);
     const uint32_t bound = (uint32_t)(species ? ctx->sp_K : ctx->T);
     for (int64_t i = 0; i < Q; ++i) {
-        const uint32_t *q = sets + 4 * i;
-        if ((q[0] >= bound) | (q[1] >= bound) | (q[2] >= bound) | (q[3] >= bound))
+        const uint32_t *q = sets + width * i;
+        bool over = false, ascending = true;
+        for (int k = 0; k < width; ++k) over |= q[k] >= bound;
+        for (int k = 1; k < width; ++k) ascending &= q[k - 1] < q[k];
+        if (over)
             return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= %s=%u", who, (long long)i, species ? "K" : "T", bound);
-        if (!((q[0] < q[1]) & (q[1] < q[2]) & (q[2] < q[3])))
+        if (!ascending && width == 4)
             return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
                         q[0], q[1], q[2], q[3]);
+        if (!ascending)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u, %u) is not strictly ascending", who,
+                        (long long)i, q[0], q[1], q[2], q[3], q[4]);
     }
     if (Q == 0) return TQ_OK;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
@@ -1603,7 +1664,8 @@ int blocks_to_host(tq_ctx *ctx, const char *who, bool species, const uint32_t *s
     if (chunk < 1) chunk = 1;
     if (chunk > Q) chunk = Q;
     const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
-    const size_t o_cls = align_up((size_t)chunk * 16, 256);
+    const size_t set_bytes = (size_t)width * sizeof(uint32_t);
+    const size_t o_cls = align_up((size_t)chunk * set_bytes, 256);
     TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
     if ((rc = ensure_streams(ctx))) return rc;
     char *base = ctx->d_scratch;
@@ -1611,11 +1673,9 @@ int blocks_to_host(tq_ctx *ctx, const char *who, bool species, const uint32_t *s
     rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
     for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
         const int64_t n = (Q - q0) < chunk ? (Q - q0) : chunk;
-        if (hipMemcpyAsync(base, sets + q0 * 4, (size_t)n * 16, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
+        if (hipMemcpyAsync(base, sets + q0 * width, (size_t)n * set_bytes, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
             rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the sets failed", who);
-        if (!rc)
-            rc = species ? launch_species_blocks(ctx, (const uint32_t *)base, n, B, d_classes, ctx->sK)
-                         : launch_pattern_blocks(ctx, (const uint32_t *)base, n, B, d_classes, ctx->sK);
+        if (!rc) rc = launch_blocks(ctx, kind, (const uint32_t *)base, n, B, d_classes, ctx->sK);
         if (!rc && hipMemcpyAsync((char *)classes + (size_t)q0 * row_bytes, d_classes, (size_t)n * row_bytes, hipMemcpyDeviceToHost,
                                   ctx->sK) != hipSuccess)
             rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the block rows failed", who);
@@ -1625,22 +1685,23 @@ int blocks_to_host(tq_ctx *ctx, const char *who, bool species, const uint32_t *s
 }
 
 // device sets -> device block rows, enqueued on `stream`
-int blocks_dev(tq_ctx *ctx, const char *who, bool species, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts,
+int blocks_dev(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts,
                int64_t B, uint32_t *d_classes, hipStream_t stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
     if (Q < 0 || !block_starts || (Q > 0 && (!d_sets || !d_classes)))
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    if (int rc = blocks_ready(ctx, who, species, block_starts, B)) return rc;
+    if (int rc = blocks_ready(ctx, who, kind, block_starts, B)) return rc;
     if (Q == 0) return TQ_OK;
-    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
+    if (kind == BLK_QUINTET) {                                   // 20-byte set rows are read as dwords
+        if ((((uintptr_t)d_sets) & 3) | (((uintptr_t)d_classes) & 15))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets5 must be 4-byte and d_classes 16-byte aligned", who);
+    } else if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
     int rc = stage_block_starts(ctx, block_starts, B, stream);
-    if (!rc)
-        rc = species ? launch_species_blocks(ctx, d_sets, Q, B, d_classes, stream)
-                     : launch_pattern_blocks(ctx, d_sets, Q, B, d_classes, stream);
+    if (!rc) rc = launch_blocks(ctx, kind, d_sets, Q, B, d_classes, stream);
     return note_dev_api(ctx, stream, rc);
 }
 
@@ -2684,25 +2745,25 @@ int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_se
 
 int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64_t *block_starts, int64_t B, uint32_t *classes)
 {
-    return blocks_to_host(ctx, "tq_patterns_blocks", false, sets, Q, block_starts, B, classes);
+    return blocks_to_host(ctx, "tq_patterns_blocks", BLK_QUARTET, sets, Q, block_starts, B, classes);
 }
 
 int tq_patterns_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets, int64_t Q, const int64_t *block_starts, int64_t B,
                            uint32_t *d_classes, void *stream)
 {
-    return blocks_dev(ctx, "tq_patterns_blocks_dev", false, d_sets, Q, block_starts, B, d_classes, (hipStream_t)stream);
+    return blocks_dev(ctx, "tq_patterns_blocks_dev", BLK_QUARTET, d_sets, Q, block_starts, B, d_classes, (hipStream_t)stream);
 }
 
 int tq_patterns_blocks_species(tq_ctx *ctx, const uint32_t *ssets, int64_t Q, const int64_t *block_starts, int64_t B,
                                uint32_t *classes)
 {
-    return blocks_to_host(ctx, "tq_patterns_blocks_species", true, ssets, Q, block_starts, B, classes);
+    return blocks_to_host(ctx, "tq_patterns_blocks_species", BLK_SPECIES, ssets, Q, block_starts, B, classes);
 }
 
 int tq_patterns_blocks_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, const int64_t *block_starts, int64_t B,
                                    uint32_t *d_classes, void *stream)
 {
-    return blocks_dev(ctx, "tq_patterns_blocks_species_dev", true, d_ssets, Q, block_starts, B, d_classes, (hipStream_t)stream);
+    return blocks_dev(ctx, "tq_patterns_blocks_species_dev", BLK_SPECIES, d_ssets, Q, block_starts, B, d_classes, (hipStream_t)stream);
 }
 
 int tq_pooled_site_classes(const uint32_t *packed, uint32_t *out)
@@ -2735,6 +2796,56 @@ int tq_dstat_jackknife_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_se
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(tq_dstat_jackknife_kernel, dim3((unsigned)((N + JK_THREADS - 1) / JK_THREADS)), dim3(JK_THREADS), 0,
                        (hipStream_t)stream, d_bclasses, n_sets, B, d_set_of, d_ia, d_ib, N, d_out);
+    TQ_HIP(ctx, hipGetLastError());
+    return TQ_OK;
+}
+
+int tq_quintet_class_table(uint8_t *out)
+{
+    if (!out) return TQ_ERR_INVALID_ARG;
+    for (int p = 0; p < 1024; ++p) {
+        const int k = quintet_class(p >> 8, (p >> 6) & 3, (p >> 4) & 3, (p >> 2) & 3, p & 3);
+        out[p] = (uint8_t)(k < 0 ? 0 : k);
+    }
+    return TQ_OK;
+}
+
+int tq_patterns_quintet_blocks(tq_ctx *ctx, const uint32_t *sets5, int64_t Q, const int64_t *block_starts, int64_t B,
+                               uint32_t *classes)
+{
+    return blocks_to_host(ctx, "tq_patterns_quintet_blocks", BLK_QUINTET, sets5, Q, block_starts, B, classes);
+}
+
+int tq_patterns_quintet_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets5, int64_t Q, const int64_t *block_starts, int64_t B,
+                                   uint32_t *d_classes, void *stream)
+{
+    return blocks_dev(ctx, "tq_patterns_quintet_blocks_dev", BLK_QUINTET, d_sets5, Q, block_starts, B, d_classes,
+                      (hipStream_t)stream);
+}
+
+int tq_dstat_jackknife_masks(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint16_t *lmask,
+                             const uint16_t *rmask, int64_t N, double *out)
+{
+    if (int rc = check_dstat_mask_tests(nullptr, "tq_dstat_jackknife_masks", bclasses && out, n_sets, B, set_of, lmask, rmask, N,
+                                        true))
+        return rc;
+    dstat_jackknife_masks_host(bclasses, B, set_of, lmask, rmask, N, out);
+    return TQ_OK;
+}
+
+int tq_dstat_jackknife_masks_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
+                                 const uint16_t *d_lmask, const uint16_t *d_rmask, int64_t N, double *d_out, void *stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (int rc = check_dstat_mask_tests(ctx, "tq_dstat_jackknife_masks_dev", d_bclasses && d_out, n_sets, B, d_set_of, d_lmask,
+                                        d_rmask, N, false))
+        return rc;
+    if (N == 0) return TQ_OK;
+    if (N > (int64_t)0x7FFFFFFF * JK_THREADS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_masks_dev: N=%lld tests exceed one launch", (long long)N);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(tq_dstat_jackknife_masks_kernel, dim3((unsigned)((N + JK_THREADS - 1) / JK_THREADS)), dim3(JK_THREADS), 0,
+                       (hipStream_t)stream, d_bclasses, n_sets, B, d_set_of, d_lmask, d_rmask, N, d_out);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
 }

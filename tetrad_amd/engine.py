@@ -347,6 +347,40 @@ class QuartetEngine:
         self._check(self._lib.tq_dstat_jackknife_dev(self._h, d_bclasses, n_sets, B, d_set_of, d_ia, d_ib, N, d_out,
                                                      stream or None))
 
+    # -- five-taxon class rows per block and the jackknife on sums of slots ----
+    @staticmethod
+    def _sets5(sets5) -> np.ndarray:
+        s = np.ascontiguousarray(sets5, dtype=np.uint32)
+        if s.ndim != 2 or s.shape[1] != 5:
+            raise ValueError("sets5 must be [Q, 5]")
+        return s
+
+    def patterns_quintet_blocks(self, sets5, block_starts) -> np.ndarray:
+        """Block rows u32[Q,B,16] of strictly ascending five-taxon sets `sets5` [Q,5], full mode: slot k = 1..15 of
+        block j counts the sites of [block_starts[j], block_starts[j+1]) with no missing base, exactly two distinct
+        bases and class k = sum of [x_i != x_0] 2^(i-1); slot 0 is their sum."""
+        s, b = self._sets5(sets5), self._block_starts(block_starts)
+        B = b.shape[0] - 1
+        classes = np.zeros((s.shape[0], B, 16), np.uint32)
+        self._check(self._lib.tq_patterns_quintet_blocks(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
+        return classes
+
+    def patterns_quintet_blocks_dev(self, d_sets5: int, Q: int, block_starts, d_classes: int, stream: int = 0):
+        """The same with device pointers (u32[Q,5] in, 4-byte aligned; u32[Q,B,16] out, 16-byte aligned), enqueued on
+        `stream`; `block_starts` is a host array, read before the call returns.  The rows are the caller's
+        responsibility (an index >= T gives zeros)."""
+        b = self._block_starts(block_starts)
+        self._check(self._lib.tq_patterns_quintet_blocks_dev(self._h, d_sets5, Q, _ptr(b), b.shape[0] - 1, d_classes,
+                                                             stream or None))
+
+    def dstat_jackknife_masks_dev(self, d_bclasses: int, n_sets: int, B: int, d_set_of: int, d_lmask: int, d_rmask: int,
+                                  N: int, d_out: int, stream: int = 0):
+        """The delete-one-block jackknife of N tests on `stream`: test t reads, of every block row j of set d_set_of[t],
+        a_j = the sum of the slots set in d_lmask[t] and b_j = that of d_rmask[t] (u16 arrays) and overwrites d_out
+        f64[N,4] = {blocks used, D, jackknife D, variance}.  An invalid test is skipped."""
+        self._check(self._lib.tq_dstat_jackknife_masks_dev(self._h, d_bclasses, n_sets, B, d_set_of, d_lmask, d_rmask, N,
+                                                           d_out, stream or None))
+
     # -- device-pointer API (addresses as ints, e.g. torch.Tensor.data_ptr()) -------
     def resolve_dev(self, d_quartets: int, Q: int, subsample_snps: bool, d_rstat: int,
                     d_rscor: int, d_flags: int = 0, stream: int = 0):
