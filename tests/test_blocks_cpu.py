@@ -86,16 +86,17 @@ def test_refusals_leave_out_untouched(patterns):
     bad_ia[7] = 15
     bad_ib = ib.copy()
     bad_ib[0] = 200
-    for args, word in [((rows, rows.shape[0], 3, bad_set, ia, ib, 8), b"set_of"),
-                       ((rows, rows.shape[0], 3, set_of, bad_ia, ib, 8), b"class index"),
-                       ((rows, rows.shape[0], 3, set_of, ia, bad_ib, 8), b"class index"),
-                       ((rows, rows.shape[0], 0, set_of, ia, ib, 8), b"B=0"),
-                       ((rows, rows.shape[0], 4097, set_of, ia, ib, 8), b"B=4097"),
-                       ((rows, -1, 3, set_of, ia, ib, 8), b"negative"),
-                       ((rows, rows.shape[0], 3, set_of, ia, ib, -1), b"negative")]:
+    # the full texts, as the library gave them before the checks of the two test forms became one
+    for args, text in [((rows, rows.shape[0], 3, bad_set, ia, ib, 8), b"test 5 has set_of=5 >= n_sets=5"),
+                       ((rows, rows.shape[0], 3, set_of, bad_ia, ib, 8), b"test 7 has a class index above 14 (15, 8)"),
+                       ((rows, rows.shape[0], 3, set_of, ia, bad_ib, 8), b"test 0 has a class index above 14 (8, 200)"),
+                       ((rows, rows.shape[0], 0, set_of, ia, ib, 8), b"B=0 blocks, must be 1..4096"),
+                       ((rows, rows.shape[0], 4097, set_of, ia, ib, 8), b"B=4097 blocks, must be 1..4096"),
+                       ((rows, -1, 3, set_of, ia, ib, 8), b"NULL pointer or negative size"),
+                       ((rows, rows.shape[0], 3, set_of, ia, ib, -1), b"NULL pointer or negative size")]:
         rc, out = call(*args)
-        assert rc == -1 and (out == -7.0).all(), word
-        assert word in lib.tq_last_error(None)
+        assert rc == -1 and (out == -7.0).all(), text
+        assert lib.tq_last_error(None) == b"tq_dstat_jackknife: " + text
     out = np.full((8, 4), -7.0)
     assert lib.tq_dstat_jackknife(None, 5, 3, p(set_of), p(ia), p(ib), 8, p(out)) == -1 and (out == -7.0).all()
     assert lib.tq_dstat_jackknife(p(rows), 5, 3, p(set_of), p(ia), p(ib), 8, None) == -1

@@ -229,6 +229,9 @@ def test_refusals(engine):
                        ((sets, [-1, 50, 130]), b"negative"), ((sets, [0, 50, S + 1]), b"past the S=")]:
         rc, untouched, msg = host(*args)
         assert rc == -1 and untouched and word in msg, (word, msg)
+    # the row check is one function for every width and kind of set: its two texts in full
+    assert host(bad_t, good)[2] == b"tq_patterns_blocks: row 3 has an index >= T=7"
+    assert host(bad_order, good)[2] == b"tq_patterns_blocks: row 5 (0, 3, 1, 5) is not strictly ascending"
     assert lib.tq_patterns_blocks(h, None, 0, p(good), 2, None) == 0                     # Q = 0 is valid
     assert lib.tq_patterns_blocks(h, None, 0, None, 2, None) == -1
     assert lib.tq_patterns_blocks(h, None, -1, p(good), 2, None) == -1

@@ -399,6 +399,9 @@ def test_refusals(engine):
                        ((ssets, [-1, 50, S]), b"negative"), ((ssets, [0, 50, S + 1]), b"past the S=")]:
         rc, untouched, msg = host_call(engine, *args)
         assert rc == -1 and untouched and word in msg and b"tq_patterns_blocks_species" in msg, (word, msg)
+    # the row check is one function for every width and kind of set: its two texts in full
+    assert host_call(engine, bad_k, good)[2] == b"tq_patterns_blocks_species: row 3 has an index >= K=5"
+    assert host_call(engine, bad_order, good)[2] == b"tq_patterns_blocks_species: row 2 (0, 3, 1, 4) is not strictly ascending"
     lib, h = engine._lib, engine._h
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     assert lib.tq_patterns_blocks_species(h, None, 0, p(good), 2, None) == 0               # Q = 0 is valid

@@ -173,19 +173,22 @@ def test_refusals_leave_out_untouched(quintets):
         return b
 
     M = rows.shape[0]
-    for args, word in [((rows, M, 3, set_of, changed(lmask, 7, lmask[7] | 1), rmask, 8), b"bit 0"),
-                       ((rows, M, 3, set_of, lmask, changed(rmask, 0, rmask[0] | 1), 8), b"bit 0"),
-                       ((rows, M, 3, set_of, changed(lmask, 3, 0), rmask, 8), b"non-empty"),
-                       ((rows, M, 3, set_of, lmask, changed(rmask, 4, 0), 8), b"non-empty"),
-                       ((rows, M, 3, set_of, changed(lmask, 2, lmask[2] | rmask[2]), rmask, 8), b"disjoint"),
-                       ((rows, M, 3, changed(set_of, 5, M), lmask, rmask, 8), b"set_of"),
-                       ((rows, M, 0, set_of, lmask, rmask, 8), b"B=0"),
-                       ((rows, M, 4097, set_of, lmask, rmask, 8), b"B=4097"),
-                       ((rows, -1, 3, set_of, lmask, rmask, 8), b"negative"),
-                       ((rows, M, 3, set_of, lmask, rmask, -1), b"negative")]:
+    # the full texts, as the library gave them before the checks of the two test forms became one
+    rule = b": bit 0 must be clear, both non-empty, and disjoint"
+    for args, text in [((rows, M, 3, set_of, changed(lmask, 7, lmask[7] | 1), rmask, 8), b"test 7 has masks 0x8b63 / 0x7098" + rule),
+                       ((rows, M, 3, set_of, lmask, changed(rmask, 0, rmask[0] | 1), 8), b"test 0 has masks 0x4f20 / 0x90cf" + rule),
+                       ((rows, M, 3, set_of, changed(lmask, 3, 0), rmask, 8), b"test 3 has masks 0x0000 / 0xa4e0" + rule),
+                       ((rows, M, 3, set_of, lmask, changed(rmask, 4, 0), 8), b"test 4 has masks 0x4720 / 0x0000" + rule),
+                       ((rows, M, 3, set_of, changed(lmask, 2, lmask[2] | rmask[2]), rmask, 8),
+                        b"test 2 has masks 0x7bfa / 0x3910" + rule),
+                       ((rows, M, 3, changed(set_of, 5, M), lmask, rmask, 8), b"test 5 has set_of=4 >= n_sets=4"),
+                       ((rows, M, 0, set_of, lmask, rmask, 8), b"B=0 blocks, must be 1..4096"),
+                       ((rows, M, 4097, set_of, lmask, rmask, 8), b"B=4097 blocks, must be 1..4096"),
+                       ((rows, -1, 3, set_of, lmask, rmask, 8), b"NULL pointer or negative size"),
+                       ((rows, M, 3, set_of, lmask, rmask, -1), b"NULL pointer or negative size")]:
         rc, out = call(*args)
-        assert rc == -1 and (out == -7.0).all(), word
-        assert word in lib.tq_last_error(None)
+        assert rc == -1 and (out == -7.0).all(), text
+        assert lib.tq_last_error(None) == b"tq_dstat_jackknife_masks: " + text
     out = np.full((8, 4), -7.0)
     assert lib.tq_dstat_jackknife_masks(None, M, 3, p(set_of), p(lmask), p(rmask), 8, p(out)) == -1 and (out == -7.0).all()
     assert lib.tq_dstat_jackknife_masks(p(rows), M, 3, p(set_of), p(lmask), p(rmask), 8, None) == -1

@@ -222,35 +222,48 @@ __host__ __device__ __forceinline__ JackknifeRow dstat_jackknife_row(const uint3
     return JackknifeRow{gf, theta, thetaJ, sV / gf};
 }
 
-// test t reads the block rows of set set_of[t]; one thread per test.  Indices out of range: the thread returns without
-// touching memory.  The output row is overwritten.
-__global__ __launch_bounds__(JK_THREADS) void tq_dstat_jackknife_kernel(const uint32_t *__restrict__ bclasses, int64_t n_sets,
-                                                                        int64_t B, const uint32_t *__restrict__ set_of,
-                                                                        const uint8_t *__restrict__ ia,
-                                                                        const uint8_t *__restrict__ ib, int64_t N,
-                                                                        double *__restrict__ out)
+// The test forms of the jackknife: how test t names its (a_j, b_j).  A form holds the two per-test arrays a and b and
+// gives the Fetch of test t, whether that Fetch is a valid test, and the text of the host forms' refusal (arguments: who,
+// t, a[t], b[t]).  ClassPairTests: two u8 class indices below 15, the classes that play ABBA and BABA.
+// MaskPairTests is in quintet_blocks.hpp.
+struct ClassPairTests {
+    const uint8_t *a, *b;
+    static constexpr const char *refusal = "%s: test %lld has a class index above 14 (%u, %u)";
+    __host__ __device__ __forceinline__ JackknifeClassPair operator[](int64_t t) const { return JackknifeClassPair{a[t], b[t]}; }
+    static __host__ __device__ __forceinline__ bool valid(const JackknifeClassPair &p)
+    {
+        return p.ca < (uint32_t)PAT_CLASSES && p.cb < (uint32_t)PAT_CLASSES;
+    }
+};
+
+__host__ __device__ __forceinline__ void jackknife_store(double *out, int64_t t, const JackknifeRow &r)
 {
-    const int64_t t = (int64_t)blockIdx.x * JK_THREADS + threadIdx.x;
-    if (t >= N) return;
-    const uint32_t s = set_of[t];
-    const uint32_t ca = ia[t], cb = ib[t];
-    if ((int64_t)s >= n_sets || ca >= (uint32_t)PAT_CLASSES || cb >= (uint32_t)PAT_CLASSES) return;
-    const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)s * B * PAT_ROW, B, JackknifeClassPair{ca, cb});
     out[4 * t + 0] = r.g;
     out[4 * t + 1] = r.theta;
     out[4 * t + 2] = r.theta_j;
     out[4 * t + 3] = r.var;
 }
 
-// the host execution; the caller has checked the indices
-inline void dstat_jackknife_host(const uint32_t *bclasses, int64_t B, const uint32_t *set_of, const uint8_t *ia,
-                                 const uint8_t *ib, int64_t N, double *out)
+// test t reads the block rows of set set_of[t]; one thread per test.  An invalid test (set_of out of range, or not valid
+// by its form): the thread returns without touching memory.  The output row is overwritten.
+template <class Tests>
+__global__ __launch_bounds__(JK_THREADS) void tq_jackknife_kernel(const uint32_t *__restrict__ bclasses, int64_t n_sets, int64_t B,
+                                                                  const uint32_t *__restrict__ set_of, const Tests tests,
+                                                                  int64_t N, double *__restrict__ out)
 {
-    for (int64_t t = 0; t < N; ++t) {
-        const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)set_of[t] * B * PAT_ROW, B, JackknifeClassPair{ia[t], ib[t]});
-        out[4 * t + 0] = r.g;
-        out[4 * t + 1] = r.theta;
-        out[4 * t + 2] = r.theta_j;
-        out[4 * t + 3] = r.var;
-    }
+    const int64_t t = (int64_t)blockIdx.x * JK_THREADS + threadIdx.x;
+    if (t >= N) return;
+    const uint32_t s = set_of[t];
+    const auto fetch = tests[t];
+    const bool valid = Tests::valid(fetch);     // judged before the branch: the three loads go out together
+    if ((int64_t)s >= n_sets || !valid) return;
+    jackknife_store(out, t, dstat_jackknife_row(bclasses + (int64_t)s * B * PAT_ROW, B, fetch));
+}
+
+// the host execution; the caller has checked set_of and the tests
+template <class Tests>
+inline void jackknife_host(const uint32_t *bclasses, int64_t B, const uint32_t *set_of, const Tests tests, int64_t N, double *out)
+{
+    for (int64_t t = 0; t < N; ++t)
+        jackknife_store(out, t, dstat_jackknife_row(bclasses + (int64_t)set_of[t] * B * PAT_ROW, B, tests[t]));
 }

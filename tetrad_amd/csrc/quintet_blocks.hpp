@@ -17,8 +17,8 @@
 // 64-byte row.  No LDS, no atomics, no scratch; every address is 64-bit.  A taxon >= T gives a row of zeros; items past
 // Q * B store nothing.
 //
-// tq_dstat_jackknife_masks_kernel: dstat_jackknife_row with a_j / b_j = the sums of the row's slots named by two u16
-// masks (JackknifeMaskPair), one thread per test.
+// tq_jackknife_kernel<MaskPairTests>: dstat_jackknife_row with a_j / b_j = the sums of the row's slots named by two
+// u16 masks (JackknifeMaskPair), one thread per test.
 #pragma once
 
 constexpr int QNT_TAXA = 5;
@@ -175,37 +175,11 @@ constexpr __host__ __device__ bool jackknife_masks_valid(uint32_t lmask, uint32_
     return ((lmask | rmask) & 1u) == 0 && lmask != 0 && rmask != 0 && (lmask & rmask) == 0;
 }
 
-// test t reads the block rows of set set_of[t]; one thread per test.  An invalid test (set_of out of range, masks not
-// valid): the thread returns without touching memory.  The output row is overwritten.
-__global__ __launch_bounds__(JK_THREADS) void tq_dstat_jackknife_masks_kernel(const uint32_t *__restrict__ bclasses,
-                                                                              int64_t n_sets, int64_t B,
-                                                                              const uint32_t *__restrict__ set_of,
-                                                                              const uint16_t *__restrict__ lmask,
-                                                                              const uint16_t *__restrict__ rmask, int64_t N,
-                                                                              double *__restrict__ out)
-{
-    const int64_t t = (int64_t)blockIdx.x * JK_THREADS + threadIdx.x;
-    if (t >= N) return;
-    const uint32_t s = set_of[t];
-    const uint32_t lm = lmask[t], rm = rmask[t];
-    if ((int64_t)s >= n_sets || !jackknife_masks_valid(lm, rm)) return;
-    const JackknifeRow r = dstat_jackknife_row(bclasses + (int64_t)s * B * PAT_ROW, B, JackknifeMaskPair{lm, rm});
-    out[4 * t + 0] = r.g;
-    out[4 * t + 1] = r.theta;
-    out[4 * t + 2] = r.theta_j;
-    out[4 * t + 3] = r.var;
-}
-
-// the host execution; the caller has checked set_of and the masks
-inline void dstat_jackknife_masks_host(const uint32_t *bclasses, int64_t B, const uint32_t *set_of, const uint16_t *lmask,
-                                       const uint16_t *rmask, int64_t N, double *out)
-{
-    for (int64_t t = 0; t < N; ++t) {
-        const JackknifeRow r =
-            dstat_jackknife_row(bclasses + (int64_t)set_of[t] * B * PAT_ROW, B, JackknifeMaskPair{lmask[t], rmask[t]});
-        out[4 * t + 0] = r.g;
-        out[4 * t + 1] = r.theta;
-        out[4 * t + 2] = r.theta_j;
-        out[4 * t + 3] = r.var;
-    }
-}
+// the mask form of the jackknife tests (see ClassPairTests, pattern_blocks.hpp): two u16 slot masks per test
+struct MaskPairTests {
+    const uint16_t *a, *b;
+    static constexpr const char *refusal =
+        "%s: test %lld has masks 0x%04x / 0x%04x: bit 0 must be clear, both non-empty, and disjoint";
+    __host__ __device__ __forceinline__ JackknifeMaskPair operator[](int64_t t) const { return JackknifeMaskPair{a[t], b[t]}; }
+    static __host__ __device__ __forceinline__ bool valid(const JackknifeMaskPair &p) { return jackknife_masks_valid(p.lmask, p.rmask); }
+};

@@ -40,8 +40,8 @@
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
 //   species_blocks.hpp tq_species_blocks_kernel: pooled class rows of species sets per block of sites from the species table
-//   quintet_blocks.hpp tq_quintet_blocks_kernel: five-taxon class rows per block of sites + tq_dstat_jackknife_masks_kernel:
-//                 the block jackknife on sums of slots (DFOIL, partitioned D)
+//   quintet_blocks.hpp tq_quintet_blocks_kernel: five-taxon class rows per block of sites + the mask form of
+//                 tq_jackknife_kernel: the block jackknife on sums of slots (DFOIL, partitioned D)
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -1435,7 +1435,44 @@ int patterns_ready(tq_ctx *ctx, const char *who, int subsample, bool species)
     return TQ_OK;
 }
 
-// host sets -> host class rows (synchronous): rows must be strictly ascending indices below `bound`
+// Rows of `width` (4 or 5) indices: every index below `bound` and the row strictly ascending.  Per row the bound is
+// judged first.
+int check_set_rows(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t Q, int width, uint32_t bound, const char *bound_name)
+{
+    for (int64_t i = 0; i < Q; ++i) {
+        const uint32_t *q = sets + width * i;
+        bool over = false, ascending = true;
+        for (int k = 0; k < width; ++k) over |= q[k] >= bound;
+        for (int k = 1; k < width; ++k) ascending &= q[k - 1] < q[k];
+        if (over)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= %s=%u", who, (long long)i, bound_name, bound);
+        if (!ascending && width == 4)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
+                        q[0], q[1], q[2], q[3]);
+        if (!ascending)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u, %u) is not strictly ascending", who,
+                        (long long)i, q[0], q[1], q[2], q[3], q[4]);
+    }
+    return TQ_OK;
+}
+
+int check_set_rows(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t Q, int width, bool species)
+{
+    return check_set_rows(ctx, who, sets, Q, width, (uint32_t)(species ? ctx->sp_K : ctx->T), species ? "K" : "T");
+}
+
+// What the device forms ask of their pointers: set rows of width 4 are read, and class rows written, as 16-byte words;
+// 20-byte set rows are read as dwords.
+int check_dev_alignment(tq_ctx *ctx, const char *who, const void *d_sets, int width, const void *d_classes)
+{
+    if (width == 4 && ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
+    if (width != 4 && ((((uintptr_t)d_sets) & 3) | (((uintptr_t)d_classes) & 15)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets5 must be 4-byte and d_classes 16-byte aligned", who);
+    return TQ_OK;
+}
+
+// host sets -> host class rows (synchronous): rows must be strictly ascending indices below T (species: K)
 int patterns_to_host(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t Q, int subsample, bool species,
                      uint32_t *classes)
 {
@@ -1444,15 +1481,7 @@ int patterns_to_host(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t
     int rc = patterns_ready(ctx, who, subsample, species);
     if (rc) return rc;
     if (Q == 0) return TQ_OK;
-    const uint32_t bound = (uint32_t)(species ? ctx->sp_K : ctx->T);
-    for (int64_t i = 0; i < Q; ++i) {
-        const uint32_t *q = sets + 4 * i;
-        if ((q[0] >= bound) | (q[1] >= bound) | (q[2] >= bound) | (q[3] >= bound))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= %s=%u", who, (long long)i, species ? "K" : "T", bound);
-        if (!((q[0] < q[1]) & (q[1] < q[2]) & (q[2] < q[3])))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
-                        q[0], q[1], q[2], q[3]);
-    }
+    if ((rc = check_set_rows(ctx, who, sets, Q, 4, species))) return rc;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     const size_t o_cls = align_up((size_t)Q * 16, 256);
     TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)));
@@ -1478,52 +1507,71 @@ int patterns_dev(tq_ctx *ctx, const char *who, const uint32_t *d_sets, int64_t Q
     if (Q < 0 || (Q > 0 && (!d_sets || !d_classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
     if (int rc = patterns_ready(ctx, who, subsample, species)) return rc;
     if (Q == 0) return TQ_OK;
-    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
+    if (int rc = check_dev_alignment(ctx, who, d_sets, 4, d_classes)) return rc;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = enter_dev_api(ctx, stream)) return rc;      // before any shared scratch is touched
     return note_dev_api(ctx, stream, launch_patterns(ctx, d_sets, Q, subsample, species, d_classes, stream));
 }
 
-// What the four D-test entry points check: sizes and pointers (`rows_and_out`: the class rows and the output are there),
-// the block count of the jackknife forms, and -- host forms only, `host_arrays` -- set_of and the class indices of every
-// test.  The device forms cannot read their arrays and check sizes only.
-int check_dstat_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n_sets, const int64_t *B, const uint32_t *set_of,
-                      const uint8_t *ia, const uint8_t *ib, int64_t N, bool host_arrays)
+// the block count of every block-row and jackknife call
+int check_block_count(tq_ctx *ctx, const char *who, int64_t B)
 {
-    if (N < 0 || n_sets < 0 || (N > 0 && (!rows_and_out || !set_of || !ia || !ib)))
+    if (B < 1 || B > PBLK_MAX_BLOCKS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
+    return TQ_OK;
+}
+
+// What the D-test entry points check: sizes and pointers (`rows_and_out`: the class rows and the output are there), the
+// block count of the jackknife forms (`B`), and -- host forms only, `host_arrays` -- set_of and the validity of every test
+// by its form (ClassPairTests, MaskPairTests).  The device forms cannot read their arrays and check sizes only.
+template <class Tests>
+int check_dstat_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n_sets, const int64_t *B, const uint32_t *set_of,
+                      const Tests tests, int64_t N, bool host_arrays)
+{
+    if (N < 0 || n_sets < 0 || (N > 0 && (!rows_and_out || !set_of || !tests.a || !tests.b)))
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative size", who);
-    if (B && (*B < 1 || *B > PBLK_MAX_BLOCKS))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)*B, (long long)PBLK_MAX_BLOCKS);
+    if (B)
+        if (int rc = check_block_count(ctx, who, *B)) return rc;
     for (int64_t t = 0; host_arrays && t < N; ++t) {
         if ((int64_t)set_of[t] >= n_sets)
             return fail(ctx, TQ_ERR_INVALID_ARG, "%s: test %lld has set_of=%u >= n_sets=%lld", who, (long long)t, set_of[t],
                         (long long)n_sets);
-        if (ia[t] >= PAT_CLASSES || ib[t] >= PAT_CLASSES)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: test %lld has a class index above 14 (%u, %u)", who, (long long)t,
-                        (unsigned)ia[t], (unsigned)ib[t]);
+        if (!Tests::valid(tests[t]))
+            return fail(ctx, TQ_ERR_INVALID_ARG, Tests::refusal, who, (long long)t, (unsigned)tests.a[t], (unsigned)tests.b[t]);
     }
     return TQ_OK;
 }
 
-// The same for the mask forms of the jackknife (quintet_blocks.hpp): a test is two u16 slot masks.
-int check_dstat_mask_tests(tq_ctx *ctx, const char *who, bool rows_and_out, int64_t n_sets, int64_t B, const uint32_t *set_of,
-                           const uint16_t *lmask, const uint16_t *rmask, int64_t N, bool host_arrays)
+// The device forms of the per-test kernels: one launch of one thread per test, `threads` to a workgroup, on `stream`.
+template <class Kernel, class... Args>
+int launch_per_test(tq_ctx *ctx, const char *who, Kernel kernel, int threads, int64_t N, void *stream, Args... args)
 {
-    if (N < 0 || n_sets < 0 || (N > 0 && (!rows_and_out || !set_of || !lmask || !rmask)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative size", who);
-    if (B < 1 || B > PBLK_MAX_BLOCKS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
-    for (int64_t t = 0; host_arrays && t < N; ++t) {
-        if ((int64_t)set_of[t] >= n_sets)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: test %lld has set_of=%u >= n_sets=%lld", who, (long long)t, set_of[t],
-                        (long long)n_sets);
-        if (!jackknife_masks_valid(lmask[t], rmask[t]))
-            return fail(ctx, TQ_ERR_INVALID_ARG,
-                        "%s: test %lld has masks 0x%04x / 0x%04x: bit 0 must be clear, both non-empty, and disjoint", who,
-                        (long long)t, (unsigned)lmask[t], (unsigned)rmask[t]);
-    }
+    if (N == 0) return TQ_OK;
+    if (N > (int64_t)0x7FFFFFFF * threads) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: N=%lld tests exceed one launch", who, (long long)N);
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((N + threads - 1) / threads)), dim3(threads), 0, (hipStream_t)stream, args...);
+    TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
+}
+
+// The jackknife entry points, host and device form, for either form of the tests.
+template <class Tests>
+int jackknife_to_host(const char *who, const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of,
+                      const Tests tests, int64_t N, double *out)
+{
+    if (int rc = check_dstat_tests(nullptr, who, bclasses && out, n_sets, &B, set_of, tests, N, true)) return rc;
+    jackknife_host(bclasses, B, set_of, tests, N, out);
+    return TQ_OK;
+}
+
+template <class Tests>
+int jackknife_dev(tq_ctx *ctx, const char *who, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
+                  const Tests tests, int64_t N, double *d_out, void *stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    if (int rc = check_dstat_tests(ctx, who, d_bclasses && d_out, n_sets, &B, d_set_of, tests, N, false)) return rc;
+    return launch_per_test(ctx, who, tq_jackknife_kernel<Tests>, JK_THREADS, N, stream, d_bclasses, n_sets, B, d_set_of, tests, N,
+                           d_out);
 }
 
 // Block rows: of quartets (pattern_blocks.hpp), of species quartets (species_blocks.hpp) or of five-taxon sets
@@ -1536,8 +1584,7 @@ constexpr int block_set_width(BlockKind kind) { return kind == BLK_QUINTET ? QNT
 int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *block_starts, int64_t B)
 {
     if (int rc = kind == BLK_SPECIES ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
-    if (B < 1 || B > PBLK_MAX_BLOCKS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: B=%lld blocks, must be 1..%lld", who, (long long)B, (long long)PBLK_MAX_BLOCKS);
+    if (int rc = check_block_count(ctx, who, B)) return rc;
     if (block_starts[0] < 0)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[0]=%lld is negative", who, (long long)block_starts[0]);
     for (int64_t j = 0; j < B; ++j)
@@ -1571,64 +1618,38 @@ int stage_block_starts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, hipS
     return TQ_OK;
 }
 
-// Block rows of sets dq[0..Q) into d_classes [Q][B][16]; the boundaries are in ctx->d_bstarts on this stream.  Always the
-// natural layout.  A launch holds fewer than 2^31 items.
-int launch_pattern_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
-{
-    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
-    const uint32_t inv = ctx->count_invariant ? 0xFFFFFFFFu : 0u;
-    for (int64_t q0 = 0; q0 < Q; q0 += per) {
-        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
-        const int64_t items = n * B;
-        hipLaunchKernelGGL(tq_pattern_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
-                           0, stream, (const uint32_t *)ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T, dq + q0 * 4, n,
-                           (const int64_t *)ctx->d_bstarts, B, inv, d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
-        TQ_HIP(ctx, hipGetLastError());
-    }
-    return TQ_OK;
-}
-
-// Block rows of species sets dq[0..Q) from the species table (species_blocks.hpp), which is brought up to date on this
-// stream first; the boundaries are in ctx->d_bstarts on this stream.  Neither the count slab nor the timing marks are touched.
-int launch_species_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
-{
-    if (int rc = ensure_species_table(ctx, stream)) return rc;
-    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets: a launch holds fewer than 2^31 items
-    for (int64_t q0 = 0; q0 < Q; q0 += per) {
-        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
-        const int64_t items = n * B;
-        hipLaunchKernelGGL(tq_species_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
-                           0, stream, (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S, (uint32_t)ctx->sp_K,
-                           species_lineage_offsets(ctx), dq + q0 * 4, n, (const int64_t *)ctx->d_bstarts, B,
-                           d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
-        TQ_HIP(ctx, hipGetLastError());
-    }
-    return TQ_OK;
-}
-
-// Block rows of five-taxon sets dq[0..Q) (u32[Q][5]) into d_classes [Q][B][16]; the boundaries are in ctx->d_bstarts on
-// this stream.  Always the natural layout.  A launch holds fewer than 2^31 items.
-int launch_quintet_blocks(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
-{
-    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
-    for (int64_t q0 = 0; q0 < Q; q0 += per) {
-        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
-        const int64_t items = n * B;
-        hipLaunchKernelGGL(tq_quintet_blocks_kernel, dim3((unsigned)((items + PBLK_ITEMS - 1) / PBLK_ITEMS)), dim3(PBLK_THREADS),
-                           0, stream, (const uint32_t *)ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T, dq + q0 * QNT_TAXA, n,
-                           (const int64_t *)ctx->d_bstarts, B, d_classes + (size_t)q0 * (size_t)B * PAT_ROW);
-        TQ_HIP(ctx, hipGetLastError());
-    }
-    return TQ_OK;
-}
-
+// Block rows of sets dq[0..Q) (u32[Q][4], five-taxon sets u32[Q][5]) into d_classes [Q][B][16]; the boundaries are in
+// ctx->d_bstarts on this stream.  Always the natural layout; species sets read the species table (species_blocks.hpp),
+// which is brought up to date on this stream first.  Neither the count slab nor the timing marks are touched.  A launch
+// holds fewer than 2^31 items.
 int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
 {
-    switch (kind) {
-    case BLK_SPECIES: return launch_species_blocks(ctx, dq, Q, B, d_classes, stream);
-    case BLK_QUINTET: return launch_quintet_blocks(ctx, dq, Q, B, d_classes, stream);
-    default: return launch_pattern_blocks(ctx, dq, Q, B, d_classes, stream);
+    if (kind == BLK_SPECIES)
+        if (int rc = ensure_species_table(ctx, stream)) return rc;
+    const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
+    const uint32_t *planes3 = ctx->nat.planes3;
+    const int64_t *starts = ctx->d_bstarts;
+    for (int64_t q0 = 0; q0 < Q; q0 += per) {
+        const int64_t n = (Q - q0) < per ? (Q - q0) : per;
+        const dim3 grid((unsigned)((n * B + PBLK_ITEMS - 1) / PBLK_ITEMS)), block(PBLK_THREADS);
+        const uint32_t *sets = dq + q0 * block_set_width(kind);
+        uint32_t *rows = d_classes + (size_t)q0 * (size_t)B * PAT_ROW;
+        switch (kind) {
+        case BLK_SPECIES:
+            hipLaunchKernelGGL(tq_species_blocks_kernel, grid, block, 0, stream, (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S,
+                               (uint32_t)ctx->sp_K, species_lineage_offsets(ctx), sets, n, starts, B, rows);
+            break;
+        case BLK_QUINTET:
+            hipLaunchKernelGGL(tq_quintet_blocks_kernel, grid, block, 0, stream, planes3, ctx->nat.W, (uint32_t)ctx->T, sets, n,
+                               starts, B, rows);
+            break;
+        default:
+            hipLaunchKernelGGL(tq_pattern_blocks_kernel, grid, block, 0, stream, planes3, ctx->nat.W, (uint32_t)ctx->T, sets, n,
+                               starts, B, ctx->count_invariant ? 0xFFFFFFFFu : 0u, rows);
+        }
+        TQ_HIP(ctx, hipGetLastError());
     }
+    return TQ_OK;
 }
 
 // host sets -> host block rows (synchronous): tq_patterns_blocks, tq_patterns_blocks_species and tq_patterns_quintet_blocks
@@ -1640,23 +1661,8 @@ int blocks_to_host(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t 
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
     int rc = blocks_ready(ctx, who, kind, block_starts, B);
     if (rc) return rc;
-    const bool species = kind == BLK_SPECIES;
     const int width = block_set_width(kind);
-    const uint32_t bound = (uint32_t)(species ? ctx->sp_K : ctx->T);
-    for (int64_t i = 0; i < Q; ++i) {
-        const uint32_t *q = sets + width * i;
-        bool over = false, ascending = true;
-        for (int k = 0; k < width; ++k) over |= q[k] >= bound;
-        for (int k = 1; k < width; ++k) ascending &= q[k - 1] < q[k];
-        if (over)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld has an index >= %s=%u", who, (long long)i, species ? "K" : "T", bound);
-        if (!ascending && width == 4)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u) is not strictly ascending", who, (long long)i,
-                        q[0], q[1], q[2], q[3]);
-        if (!ascending)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: row %lld (%u, %u, %u, %u, %u) is not strictly ascending", who,
-                        (long long)i, q[0], q[1], q[2], q[3], q[4]);
-    }
+    if ((rc = check_set_rows(ctx, who, sets, Q, width, kind == BLK_SPECIES))) return rc;
     if (Q == 0) return TQ_OK;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
@@ -1693,11 +1699,7 @@ int blocks_dev(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *d_s
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
     if (int rc = blocks_ready(ctx, who, kind, block_starts, B)) return rc;
     if (Q == 0) return TQ_OK;
-    if (kind == BLK_QUINTET) {                                   // 20-byte set rows are read as dwords
-        if ((((uintptr_t)d_sets) & 3) | (((uintptr_t)d_classes) & 15))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets5 must be 4-byte and d_classes 16-byte aligned", who);
-    } else if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // rows are read and written as 16-byte words
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_sets and d_classes must be 16-byte aligned", who);
+    if (int rc = check_dev_alignment(ctx, who, d_sets, block_set_width(kind), d_classes)) return rc;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
     int rc = stage_block_starts(ctx, block_starts, B, stream);
@@ -2722,7 +2724,9 @@ int tq_patterns_species_dev(tq_ctx *ctx, const uint32_t *d_ssets, int64_t Q, uin
 int tq_dstat_accumulate(const uint32_t *classes, int64_t n_sets, const uint32_t *set_of, const uint8_t *ia, const uint8_t *ib,
                         int64_t N, double *acc)
 {
-    if (int rc = check_dstat_tests(nullptr, "tq_dstat_accumulate", classes && acc, n_sets, nullptr, set_of, ia, ib, N, true)) return rc;
+    if (int rc = check_dstat_tests(nullptr, "tq_dstat_accumulate", classes && acc, n_sets, nullptr, set_of,
+                                   ClassPairTests{ia, ib}, N, true))
+        return rc;
     dstat_add_host(classes, set_of, ia, ib, N, acc);
     return TQ_OK;
 }
@@ -2731,16 +2735,10 @@ int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_se
                             const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (int rc = check_dstat_tests(ctx, "tq_dstat_accumulate_dev", d_classes && d_acc, n_sets, nullptr, d_set_of, d_ia, d_ib, N, false))
+    const char *who = "tq_dstat_accumulate_dev";
+    if (int rc = check_dstat_tests(ctx, who, d_classes && d_acc, n_sets, nullptr, d_set_of, ClassPairTests{d_ia, d_ib}, N, false))
         return rc;
-    if (N == 0) return TQ_OK;
-    if (N > (int64_t)0x7FFFFFFF * DSTAT_THREADS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_accumulate_dev: N=%lld tests exceed one launch", (long long)N);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(tq_dstat_kernel, dim3((unsigned)((N + DSTAT_THREADS - 1) / DSTAT_THREADS)), dim3(DSTAT_THREADS), 0,
-                       (hipStream_t)stream, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    return launch_per_test(ctx, who, tq_dstat_kernel, DSTAT_THREADS, N, stream, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc);
 }
 
 int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64_t *block_starts, int64_t B, uint32_t *classes)
@@ -2779,25 +2777,14 @@ int tq_pooled_site_classes(const uint32_t *packed, uint32_t *out)
 int tq_dstat_jackknife(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint8_t *ia,
                        const uint8_t *ib, int64_t N, double *out)
 {
-    if (int rc = check_dstat_tests(nullptr, "tq_dstat_jackknife", bclasses && out, n_sets, &B, set_of, ia, ib, N, true)) return rc;
-    dstat_jackknife_host(bclasses, B, set_of, ia, ib, N, out);
-    return TQ_OK;
+    return jackknife_to_host("tq_dstat_jackknife", bclasses, n_sets, B, set_of, ClassPairTests{ia, ib}, N, out);
 }
 
 int tq_dstat_jackknife_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
                            const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_out, void *stream)
 {
-    if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (int rc = check_dstat_tests(ctx, "tq_dstat_jackknife_dev", d_bclasses && d_out, n_sets, &B, d_set_of, d_ia, d_ib, N, false))
-        return rc;
-    if (N == 0) return TQ_OK;
-    if (N > (int64_t)0x7FFFFFFF * JK_THREADS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_dev: N=%lld tests exceed one launch", (long long)N);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(tq_dstat_jackknife_kernel, dim3((unsigned)((N + JK_THREADS - 1) / JK_THREADS)), dim3(JK_THREADS), 0,
-                       (hipStream_t)stream, d_bclasses, n_sets, B, d_set_of, d_ia, d_ib, N, d_out);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    return jackknife_dev(ctx, "tq_dstat_jackknife_dev", d_bclasses, n_sets, B, d_set_of, ClassPairTests{d_ia, d_ib}, N, d_out,
+                         stream);
 }
 
 int tq_quintet_class_table(uint8_t *out)
@@ -2826,28 +2813,14 @@ int tq_patterns_quintet_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets5, int64_t
 int tq_dstat_jackknife_masks(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint16_t *lmask,
                              const uint16_t *rmask, int64_t N, double *out)
 {
-    if (int rc = check_dstat_mask_tests(nullptr, "tq_dstat_jackknife_masks", bclasses && out, n_sets, B, set_of, lmask, rmask, N,
-                                        true))
-        return rc;
-    dstat_jackknife_masks_host(bclasses, B, set_of, lmask, rmask, N, out);
-    return TQ_OK;
+    return jackknife_to_host("tq_dstat_jackknife_masks", bclasses, n_sets, B, set_of, MaskPairTests{lmask, rmask}, N, out);
 }
 
 int tq_dstat_jackknife_masks_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_t n_sets, int64_t B, const uint32_t *d_set_of,
                                  const uint16_t *d_lmask, const uint16_t *d_rmask, int64_t N, double *d_out, void *stream)
 {
-    if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (int rc = check_dstat_mask_tests(ctx, "tq_dstat_jackknife_masks_dev", d_bclasses && d_out, n_sets, B, d_set_of, d_lmask,
-                                        d_rmask, N, false))
-        return rc;
-    if (N == 0) return TQ_OK;
-    if (N > (int64_t)0x7FFFFFFF * JK_THREADS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_dstat_jackknife_masks_dev: N=%lld tests exceed one launch", (long long)N);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(tq_dstat_jackknife_masks_kernel, dim3((unsigned)((N + JK_THREADS - 1) / JK_THREADS)), dim3(JK_THREADS), 0,
-                       (hipStream_t)stream, d_bclasses, n_sets, B, d_set_of, d_lmask, d_rmask, N, d_out);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    return jackknife_dev(ctx, "tq_dstat_jackknife_masks_dev", d_bclasses, n_sets, B, d_set_of, MaskPairTests{d_lmask, d_rmask},
+                         N, d_out, stream);
 }
 
 int tq_timing_enable(tq_ctx *ctx, int on)

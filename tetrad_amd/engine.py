@@ -309,36 +309,36 @@ class QuartetEngine:
             raise ValueError("block_starts must hold B + 1 >= 2 boundaries")
         return b
 
+    def _blocks_host(self, entry, s: np.ndarray, block_starts) -> np.ndarray:
+        b = self._block_starts(block_starts)
+        B = b.shape[0] - 1
+        classes = np.zeros((s.shape[0], B, 16), np.uint32)
+        self._check(entry(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
+        return classes
+
+    def _blocks_dev(self, entry, d_sets: int, Q: int, block_starts, d_classes: int, stream: int):
+        b = self._block_starts(block_starts)
+        self._check(entry(self._h, d_sets, Q, _ptr(b), b.shape[0] - 1, d_classes, stream or None))
+
     def patterns_blocks(self, sets, block_starts) -> np.ndarray:
         """Block rows u32[Q,B,16] of strictly ascending quartets `sets` [Q,4], full mode: block j holds the class
         counts (and their sum) of sites [block_starts[j], block_starts[j+1]) of the resident replicate."""
-        s, b = self._sets(sets), self._block_starts(block_starts)
-        B = b.shape[0] - 1
-        classes = np.zeros((s.shape[0], B, 16), np.uint32)
-        self._check(self._lib.tq_patterns_blocks(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
-        return classes
+        return self._blocks_host(self._lib.tq_patterns_blocks, self._sets(sets), block_starts)
 
     def patterns_blocks_dev(self, d_sets: int, Q: int, block_starts, d_classes: int, stream: int = 0):
         """The same with device pointers (u32[Q,4] in, u32[Q,B,16] out), enqueued on `stream`; `block_starts` is a host
         array, read before the call returns.  The rows are the caller's responsibility."""
-        b = self._block_starts(block_starts)
-        self._check(self._lib.tq_patterns_blocks_dev(self._h, d_sets, Q, _ptr(b), b.shape[0] - 1, d_classes, stream or None))
+        self._blocks_dev(self._lib.tq_patterns_blocks_dev, d_sets, Q, block_starts, d_classes, stream)
 
     def patterns_blocks_species(self, ssets, block_starts) -> np.ndarray:
         """Block rows u32[Q,B,16] of strictly ascending SPECIES quartets: per block the pooled
         class counts of the lineage combinations, class 0 always 0, slot 15 the sum.  Needs `set_species`."""
-        s, b = self._sets(ssets), self._block_starts(block_starts)
-        B = b.shape[0] - 1
-        classes = np.zeros((s.shape[0], B, 16), np.uint32)
-        self._check(self._lib.tq_patterns_blocks_species(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
-        return classes
+        return self._blocks_host(self._lib.tq_patterns_blocks_species, self._sets(ssets), block_starts)
 
     def patterns_blocks_species_dev(self, d_ssets: int, Q: int, block_starts, d_classes: int, stream: int = 0):
         """The same with device pointers (u32[Q,4] in, u32[Q,B,16] out), enqueued on `stream`; `block_starts` is a host
         array, read before the call returns.  The rows are the caller's responsibility (an id >= K gives zeros)."""
-        b = self._block_starts(block_starts)
-        self._check(self._lib.tq_patterns_blocks_species_dev(self._h, d_ssets, Q, _ptr(b), b.shape[0] - 1, d_classes,
-                                                             stream or None))
+        self._blocks_dev(self._lib.tq_patterns_blocks_species_dev, d_ssets, Q, block_starts, d_classes, stream)
 
     def dstat_jackknife_dev(self, d_bclasses: int, n_sets: int, B: int, d_set_of: int, d_ia: int, d_ib: int, N: int,
                             d_out: int, stream: int = 0):
@@ -359,19 +359,13 @@ class QuartetEngine:
         """Block rows u32[Q,B,16] of strictly ascending five-taxon sets `sets5` [Q,5], full mode: slot k = 1..15 of
         block j counts the sites of [block_starts[j], block_starts[j+1]) with no missing base, exactly two distinct
         bases and class k = sum of [x_i != x_0] 2^(i-1); slot 0 is their sum."""
-        s, b = self._sets5(sets5), self._block_starts(block_starts)
-        B = b.shape[0] - 1
-        classes = np.zeros((s.shape[0], B, 16), np.uint32)
-        self._check(self._lib.tq_patterns_quintet_blocks(self._h, _ptr(s), s.shape[0], _ptr(b), B, _ptr(classes)))
-        return classes
+        return self._blocks_host(self._lib.tq_patterns_quintet_blocks, self._sets5(sets5), block_starts)
 
     def patterns_quintet_blocks_dev(self, d_sets5: int, Q: int, block_starts, d_classes: int, stream: int = 0):
         """The same with device pointers (u32[Q,5] in, 4-byte aligned; u32[Q,B,16] out, 16-byte aligned), enqueued on
         `stream`; `block_starts` is a host array, read before the call returns.  The rows are the caller's
         responsibility (an index >= T gives zeros)."""
-        b = self._block_starts(block_starts)
-        self._check(self._lib.tq_patterns_quintet_blocks_dev(self._h, d_sets5, Q, _ptr(b), b.shape[0] - 1, d_classes,
-                                                             stream or None))
+        self._blocks_dev(self._lib.tq_patterns_quintet_blocks_dev, d_sets5, Q, block_starts, d_classes, stream)
 
     def dstat_jackknife_masks_dev(self, d_bclasses: int, n_sets: int, B: int, d_set_of: int, d_lmask: int, d_rmask: int,
                                   N: int, d_out: int, stream: int = 0):

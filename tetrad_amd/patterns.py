@@ -88,31 +88,38 @@ def dstat_tests(tests):
     return sets, set_of, idx[:, 0].copy(), idx[:, 1].copy()
 
 
-def _role_classes(tests, role_classes):
+def _ascending_sets(tests, width: int, roles: str):
+    """tests int[N,width] in the order `roles`, distinct taxa in any order -> (sets u32[M,width] unique and ascending,
+    set_of u32[N], rank i64[N,width]): role position i of test t holds ascending position rank[t, i] of
+    sets[set_of[t]]."""
     tests = np.asarray(tests)
-    if tests.ndim != 2 or tests.shape[1] != 4:
-        raise ValueError("tests must be [N, 4] in the order (P1, P2, P3, O)")
+    if tests.ndim != 2 or tests.shape[1] != width:
+        raise ValueError(f"tests must be [N, {width}] in the order {roles}")
     if tests.size and tests.min() < 0:
         raise ValueError("taxon indices must not be negative")
     tests = tests.astype(np.int64)
     order = np.argsort(tests, axis=1, kind="stable")
     asc = np.take_along_axis(tests, order, axis=1)
     if tests.shape[0] and (asc[:, 1:] == asc[:, :-1]).any():
-        raise ValueError("the four taxa of a test must be distinct")
-    # role position i holds ascending position rank[i]
+        raise ValueError(f"the {('four', 'five')[width - 4]} taxa of a test must be distinct")
     rank = np.argsort(order, axis=1, kind="stable")
-    idx = np.zeros((tests.shape[0], len(role_classes)), np.uint8)
+    if tests.shape[0]:
+        sets, set_of = np.unique(asc, axis=0, return_inverse=True)
+    else:
+        sets, set_of = asc, np.zeros(0, np.int64)
+    return (np.ascontiguousarray(sets, dtype=np.uint32), np.ascontiguousarray(set_of.reshape(-1), dtype=np.uint32), rank)
+
+
+def _role_classes(tests, role_classes):
+    sets, set_of, rank = _ascending_sets(tests, 4, "(P1, P2, P3, O)")
+    idx = np.zeros((rank.shape[0], len(role_classes)), np.uint8)
     cache: dict = {}
     for t, p in enumerate(map(tuple, rank.tolist())):
         if p not in cache:
             inv = np.argsort(class_permutation(p))          # inv[role class] = class of the ascending row
             cache[p] = [int(inv[c]) for c in role_classes]
         idx[t] = cache[p]
-    if tests.shape[0]:
-        sets, set_of = np.unique(asc, axis=0, return_inverse=True)
-    else:
-        sets, set_of = asc, np.zeros(0, np.int64)
-    return (np.ascontiguousarray(sets, dtype=np.uint32), np.ascontiguousarray(set_of.reshape(-1), dtype=np.uint32), idx)
+    return sets, set_of, idx
 
 
 def tests_with_outgroup(ntaxa: int, outgroup: int) -> np.ndarray:
@@ -259,23 +266,84 @@ def jackknife_moments(out: np.ndarray):
     return out[:, 0].astype(np.int64), out[:, 2].copy(), se
 
 
-def dstat_jackknife(bclasses, set_of, ia, ib) -> np.ndarray:
-    """The host execution of the jackknife kernel (`tq_dstat_jackknife`, no GPU): block rows u32[M,B,16] ->
-    f64[N,4] = {blocks with a count, D, jackknife D, jackknife variance} per test."""
+def jackknife_z(D, se) -> np.ndarray:
+    """Z = D / jk_se; NaN where the standard error is 0 or undefined."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(se > 0, D / se, np.nan)
+
+
+def _jackknife_host(entry: str, dtype, names: str, bclasses, set_of, a, b) -> np.ndarray:
+    """The host execution of a jackknife kernel (library entry point `entry`, no GPU) on block rows u32[M,B,16] and the
+    per-test arrays a, b of `dtype`."""
     bclasses = np.ascontiguousarray(bclasses, dtype=np.uint32)
     if bclasses.ndim != 3 or bclasses.shape[2] != 16:
         raise ValueError("bclasses must be [M, B, 16]")
     set_of = np.ascontiguousarray(set_of, dtype=np.uint32)
-    ia, ib = np.ascontiguousarray(ia, dtype=np.uint8), np.ascontiguousarray(ib, dtype=np.uint8)
-    if not (ia.shape == ib.shape == set_of.shape):
-        raise ValueError("set_of, ia and ib must have one entry per test")
+    a, b = np.ascontiguousarray(a, dtype=dtype), np.ascontiguousarray(b, dtype=dtype)
+    if not (a.shape == b.shape == set_of.shape):
+        raise ValueError(f"set_of, {names} must have one entry per test")
     out = np.zeros((set_of.shape[0], 4), np.float64)
     lib = _lib.load()
-    rc = lib.tq_dstat_jackknife(_ptr(bclasses), bclasses.shape[0], bclasses.shape[1], _ptr(set_of), _ptr(ia), _ptr(ib),
-                                set_of.shape[0], _ptr(out))
+    rc = getattr(lib, entry)(_ptr(bclasses), bclasses.shape[0], bclasses.shape[1], _ptr(set_of), _ptr(a), _ptr(b),
+                             set_of.shape[0], _ptr(out))
     if rc != 0:
         raise TetradHipError(rc, lib.tq_last_error(None).decode())
     return out
+
+
+def dstat_jackknife(bclasses, set_of, ia, ib) -> np.ndarray:
+    """The host execution of the jackknife kernel (`tq_dstat_jackknife`, no GPU): block rows u32[M,B,16] ->
+    f64[N,4] = {blocks with a count, D, jackknife D, jackknife variance} per test."""
+    return _jackknife_host("tq_dstat_jackknife", np.uint8, "ia and ib", bclasses, set_of, ia, ib)
+
+
+def _jackknife_starts(engine: QuartetEngine, tmpmap, nblocks: int, block_starts) -> np.ndarray:
+    """i64[B + 1]: `block_starts`, or without it `locus_blocks` of `tmpmap` (None: the resident locus column)."""
+    if block_starts is None:
+        if tmpmap is None:
+            tmpmap = engine.get_data()[1]
+        block_starts = locus_blocks(tmpmap, nblocks)
+    return np.ascontiguousarray(block_starts, dtype=np.int64).reshape(-1)
+
+
+def _run_block_jackknife(engine: QuartetEngine, block_rows_dev, jackknife_dev, sets, set_of, per_test, starts, chunk: int):
+    """The chunked device loop of the block-jackknife drivers, all on the current stream.  `sets` u32[M,width] and
+    `set_of` u32[N] (N > 0) as `_ascending_sets` gives them; `per_test` [K,2,N] (u8 or u16, K > 0) holds the two
+    per-test arrays of each of K statistics.  Per chunk of `chunk` >= 1 sets: the block rows (`block_rows_dev`, torch memory
+    of chunk x B x 64 bytes, re-used), their sums over the blocks, and one `jackknife_dev` launch per statistic on the
+    chunk's tests.  One device-to-host copy at the end.
+    Returns (u32[M,16] block sums per set, f64[K,N,4] jackknife rows in test order)."""
+    import torch
+    B = starts.shape[0] - 1
+    (M, width), N, K = sets.shape, len(set_of), per_test.shape[0]
+    chunk = min(int(chunk), M)
+    # the tests in the order of their sets: the tests of a chunk of sets are then one contiguous run
+    order = np.argsort(set_of, kind="stable")
+    s_sorted = set_of[order].astype(np.int64)
+    item = per_test.dtype.itemsize
+    dev = torch.device("cuda", engine.device_id)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        d_sets = torch.from_numpy(sets.view(np.int32)).to(dev)
+        d_rel = torch.from_numpy((s_sorted % chunk).astype(np.uint32).view(np.int32)).to(dev)
+        d_per = torch.from_numpy(np.ascontiguousarray(per_test[:, :, order]).view(np.uint8)).to(dev)
+        d_rows = torch.empty((chunk, B, 16), dtype=torch.int32, device=dev)
+        # u32 sums: a set counts at most S < 2^32 sites (a species set: below 2^32 by the range rule of species mode)
+        d_sum = torch.empty((M, 16), dtype=torch.int32, device=dev)
+        d_out = torch.empty((K, N, 4), dtype=torch.float64, device=dev)
+        for q0 in range(0, M, chunk):
+            n = min(chunk, M - q0)
+            block_rows_dev(d_sets.data_ptr() + 4 * width * q0, n, starts, d_rows.data_ptr(), cur.cuda_stream)
+            torch.sum(d_rows[:n], dim=1, dtype=torch.int32, out=d_sum[q0:q0 + n])
+            t0, t1 = (int(v) for v in np.searchsorted(s_sorted, [q0, q0 + n], side="left"))
+            for s in range(K if t1 > t0 else 0):
+                jackknife_dev(d_rows.data_ptr(), n, B, d_rel.data_ptr() + 4 * t0, d_per.data_ptr() + item * (2 * s * N + t0),
+                              d_per.data_ptr() + item * ((2 * s + 1) * N + t0), t1 - t0, d_out.data_ptr() + 32 * (s * N + t0),
+                              cur.cuda_stream)
+        sums = d_sum.cpu().numpy().view(np.uint32)
+        jk = np.empty((K, N, 4), np.float64)
+        jk[:, order] = d_out.cpu().numpy()
+    return sums, jk
 
 
 def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: int = 50, block_starts=None,
@@ -292,7 +360,6 @@ def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: i
     (the way to allele mode: `set_source`, `bootstrap`, option "species_alleles", then `resident=True`).
     Returns a structured array per test: abba, baba, bbaa, nsites (sums over the blocks), D, jk_blocks, jk_mean,
     jk_se, Z = D / jk_se; NaN where undefined."""
-    import torch
     if int(chunk) < 1:
         raise ValueError("chunk must be positive")
     sets, set_of, idx = _role_classes(tests, (ABBA, BABA, BBAA))
@@ -301,47 +368,17 @@ def run_dstat_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, nblocks: i
     if species_of is not None:
         engine.set_species(species_of)
     block_rows_dev = engine.patterns_blocks_dev if species_of is None else engine.patterns_blocks_species_dev
-    if block_starts is None:
-        if tmpmap is None:
-            tmpmap = engine.get_data()[1]
-        block_starts = locus_blocks(tmpmap, nblocks)
-    starts = np.ascontiguousarray(block_starts, dtype=np.int64).reshape(-1)
-    B = starts.shape[0] - 1
-    N, M = len(set_of), len(sets)
+    starts = _jackknife_starts(engine, tmpmap, nblocks, block_starts)
+    N = len(set_of)
     res = np.zeros(N, JACKKNIFE_DTYPE)
     if N == 0:
         return res
-    chunk = min(int(chunk), M)
-    # the tests in the order of their sets: the tests of a chunk of sets are then one contiguous run
-    order = np.argsort(set_of, kind="stable")
-    s_sorted = set_of[order].astype(np.int64)
-    dev = torch.device("cuda", engine.device_id)
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        d_sets = torch.from_numpy(sets.view(np.int32)).to(dev)
-        d_rel = torch.from_numpy((s_sorted % chunk).astype(np.uint32).view(np.int32)).to(dev)
-        d_ia = torch.from_numpy(np.ascontiguousarray(idx[order, 0])).to(dev)
-        d_ib = torch.from_numpy(np.ascontiguousarray(idx[order, 1])).to(dev)
-        d_rows = torch.empty((chunk, B, 16), dtype=torch.int32, device=dev)
-        # u32 sums: a set counts at most S < 2^32 sites (a species set: below 2^32 by the range rule of species mode)
-        d_sum = torch.empty((M, 16), dtype=torch.int32, device=dev)
-        d_out = torch.empty((N, 4), dtype=torch.float64, device=dev)
-        for q0 in range(0, M, chunk):
-            n = min(chunk, M - q0)
-            block_rows_dev(d_sets.data_ptr() + 16 * q0, n, starts, d_rows.data_ptr(), cur.cuda_stream)
-            torch.sum(d_rows[:n], dim=1, dtype=torch.int32, out=d_sum[q0:q0 + n])
-            t0, t1 = (int(v) for v in np.searchsorted(s_sorted, [q0, q0 + n], side="left"))
-            if t1 > t0:
-                engine.dstat_jackknife_dev(d_rows.data_ptr(), n, B, d_rel.data_ptr() + 4 * t0, d_ia.data_ptr() + t0,
-                                           d_ib.data_ptr() + t0, t1 - t0, d_out.data_ptr() + 32 * t0, cur.cuda_stream)
-        sums = d_sum.cpu().numpy().view(np.uint32)
-        jk = np.empty((N, 4), np.float64)
-        jk[order] = d_out.cpu().numpy()
+    sums, jk = _run_block_jackknife(engine, block_rows_dev, engine.dstat_jackknife_dev, sets, set_of, idx[:, :2].T[None], starts,
+                                    chunk)
     rows = sums[set_of.astype(np.int64)]
     take = lambda col: rows[np.arange(N), np.asarray(col, np.int64)]
     res["abba"], res["baba"], res["bbaa"], res["nsites"] = take(idx[:, 0]), take(idx[:, 1]), take(idx[:, 2]), rows[:, NCLASS]
-    res["D"] = jk[:, 1]
-    res["jk_blocks"], res["jk_mean"], res["jk_se"] = jackknife_moments(jk)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        res["Z"] = np.where(res["jk_se"] > 0, res["D"] / res["jk_se"], np.nan)
+    res["D"] = jk[0, :, 1]
+    res["jk_blocks"], res["jk_mean"], res["jk_se"] = jackknife_moments(jk[0])
+    res["Z"] = jackknife_z(res["D"], res["jk_se"])
     return res

@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import TetradHipError
 from .engine import QuartetEngine, _ptr
-from .patterns import jackknife_moments, locus_blocks
+from .patterns import _ascending_sets, _jackknife_host, _jackknife_starts, _run_block_jackknife, jackknife_moments, jackknife_z
 
 
 class QuintetStats(tuple):
@@ -87,19 +87,9 @@ def quintet_tests(tests, stats=DFOIL):
     (left patterns, right patterns) ->
     (sets5 u32[M,5] unique and ascending, set_of u32[N], masks u16[N, len(stats), 2]): statistic s of test t reads
     L as the sum of the slots in masks[t, s, 0] and R as that in masks[t, s, 1] of the block rows of sets5[set_of[t]]."""
-    tests = np.asarray(tests)
-    if tests.ndim != 2 or tests.shape[1] != 5:
-        raise ValueError("tests must be [N, 5] in the order (P1, P2, P3, P4, O)")
-    if tests.size and tests.min() < 0:
-        raise ValueError("taxon indices must not be negative")
-    tests = tests.astype(np.int64)
-    order = np.argsort(tests, axis=1, kind="stable")
-    asc = np.take_along_axis(tests, order, axis=1)
-    if tests.shape[0] and (asc[:, 1:] == asc[:, :-1]).any():
-        raise ValueError("the five taxa of a test must be distinct")
-    rank = np.argsort(order, axis=1, kind="stable")          # role position i holds ascending position rank[i]
+    sets, set_of, rank = _ascending_sets(tests, 5, "(P1, P2, P3, P4, O)")
     stats = [(tuple(left), tuple(right)) for left, right in stats]
-    masks = np.zeros((tests.shape[0], len(stats), 2), np.uint16)
+    masks = np.zeros((rank.shape[0], len(stats), 2), np.uint16)
     cache: dict = {}
     for t, p in enumerate(map(tuple, rank.tolist())):
         if p not in cache:
@@ -112,31 +102,14 @@ def quintet_tests(tests, stats=DFOIL):
                     raise ValueError(f"statistic {s}: both sides need a pattern and they must not share one")
             cache[p] = row
         masks[t] = cache[p]
-    if tests.shape[0]:
-        sets, set_of = np.unique(asc, axis=0, return_inverse=True)
-    else:
-        sets, set_of = asc, np.zeros(0, np.int64)
-    return (np.ascontiguousarray(sets, dtype=np.uint32), np.ascontiguousarray(set_of.reshape(-1), dtype=np.uint32), masks)
+    return sets, set_of, masks
 
 
 def dstat_jackknife_masks(bclasses, set_of, lmask, rmask) -> np.ndarray:
     """The host execution of the mask jackknife (`tq_dstat_jackknife_masks`, no GPU): block rows u32[M,B,16] ->
     f64[N,4] = {blocks with a count, D, jackknife D, jackknife variance} per test, a_j / b_j the sums of the slots under
     lmask / rmask u16[N]."""
-    bclasses = np.ascontiguousarray(bclasses, dtype=np.uint32)
-    if bclasses.ndim != 3 or bclasses.shape[2] != 16:
-        raise ValueError("bclasses must be [M, B, 16]")
-    set_of = np.ascontiguousarray(set_of, dtype=np.uint32)
-    lmask, rmask = np.ascontiguousarray(lmask, dtype=np.uint16), np.ascontiguousarray(rmask, dtype=np.uint16)
-    if not (lmask.shape == rmask.shape == set_of.shape):
-        raise ValueError("set_of, lmask and rmask must have one entry per test")
-    out = np.zeros((set_of.shape[0], 4), np.float64)
-    lib = _lib.load()
-    rc = lib.tq_dstat_jackknife_masks(_ptr(bclasses), bclasses.shape[0], bclasses.shape[1], _ptr(set_of), _ptr(lmask),
-                                      _ptr(rmask), set_of.shape[0], _ptr(out))
-    if rc != 0:
-        raise TetradHipError(rc, lib.tq_last_error(None).decode())
-    return out
+    return _jackknife_host("tq_dstat_jackknife_masks", np.uint16, "lmask and rmask", bclasses, set_of, lmask, rmask)
 
 
 def result_dtype(stats) -> np.dtype:
@@ -159,50 +132,19 @@ def run_quintet_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, stats=DF
     and `tmpmap` as in `patterns.run_dstat_jackknife`.
     Returns a structured array per test (`result_dtype(stats)`): nsites (slot 0 summed over the blocks) and per
     statistic left, right (sums over the blocks), D, jk_blocks, jk_mean, jk_se, Z = D / jk_se; NaN where undefined."""
-    import torch
     if int(chunk) < 1:
         raise ValueError("chunk must be positive")
     names = _stat_names(stats)
     sets, set_of, masks = quintet_tests(tests, stats)
     if not resident:
         engine.set_data(tmparr, tmpmap)
-    if block_starts is None:
-        if tmpmap is None:
-            tmpmap = engine.get_data()[1]
-        block_starts = locus_blocks(tmpmap, nblocks)
-    starts = np.ascontiguousarray(block_starts, dtype=np.int64).reshape(-1)
-    B = starts.shape[0] - 1
-    N, M, K = len(set_of), len(sets), len(names)
+    starts = _jackknife_starts(engine, tmpmap, nblocks, block_starts)
+    N, K = len(set_of), len(names)
     res = np.zeros(N, result_dtype(stats))
     if N == 0 or K == 0:
         return res
-    chunk = min(int(chunk), M)
-    # the tests in the order of their sets: the tests of a chunk of sets are then one contiguous run
-    order = np.argsort(set_of, kind="stable")
-    s_sorted = set_of[order].astype(np.int64)
-    m_sorted = np.ascontiguousarray(masks[order].transpose(1, 2, 0))             # [K, 2, N]
-    dev = torch.device("cuda", engine.device_id)
-    with torch.cuda.device(dev):
-        cur = torch.cuda.current_stream(dev)
-        d_sets = torch.from_numpy(sets.view(np.int32)).to(dev)
-        d_rel = torch.from_numpy((s_sorted % chunk).astype(np.uint32).view(np.int32)).to(dev)
-        d_masks = torch.from_numpy(m_sorted.view(np.int16)).to(dev)
-        d_rows = torch.empty((chunk, B, 16), dtype=torch.int32, device=dev)
-        d_sum = torch.empty((M, 16), dtype=torch.int32, device=dev)             # u32 sums: a set counts at most S sites
-        d_out = torch.empty((K, N, 4), dtype=torch.float64, device=dev)
-        for q0 in range(0, M, chunk):
-            n = min(chunk, M - q0)
-            engine.patterns_quintet_blocks_dev(d_sets.data_ptr() + 20 * q0, n, starts, d_rows.data_ptr(), cur.cuda_stream)
-            torch.sum(d_rows[:n], dim=1, dtype=torch.int32, out=d_sum[q0:q0 + n])
-            t0, t1 = (int(v) for v in np.searchsorted(s_sorted, [q0, q0 + n], side="left"))
-            for s in range(K if t1 > t0 else 0):
-                engine.dstat_jackknife_masks_dev(d_rows.data_ptr(), n, B, d_rel.data_ptr() + 4 * t0,
-                                                 d_masks.data_ptr() + 2 * ((2 * s) * N + t0),
-                                                 d_masks.data_ptr() + 2 * ((2 * s + 1) * N + t0), t1 - t0,
-                                                 d_out.data_ptr() + 32 * (s * N + t0), cur.cuda_stream)
-        sums = d_sum.cpu().numpy().view(np.uint32)
-        jk = np.empty((K, N, 4), np.float64)
-        jk[:, order] = d_out.cpu().numpy()
+    sums, jk = _run_block_jackknife(engine, engine.patterns_quintet_blocks_dev, engine.dstat_jackknife_masks_dev, sets, set_of,
+                                    masks.transpose(1, 2, 0), starts, chunk)
     rows = sums[set_of.astype(np.int64)].astype(np.uint64)                       # [N, 16]
     slot = np.arange(16, dtype=np.uint16)
     res["nsites"] = rows[:, 0]
@@ -212,6 +154,5 @@ def run_quintet_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, stats=DF
             res[f"{name}_{field}"] = (rows * on).sum(axis=1, dtype=np.uint64)
         res[f"{name}_D"] = jk[s, :, 1]
         res[f"{name}_jk_blocks"], res[f"{name}_jk_mean"], res[f"{name}_jk_se"] = jackknife_moments(jk[s])
-        with np.errstate(divide="ignore", invalid="ignore"):
-            res[f"{name}_Z"] = np.where(res[f"{name}_jk_se"] > 0, res[f"{name}_D"] / res[f"{name}_jk_se"], np.nan)
+        res[f"{name}_Z"] = jackknife_z(res[f"{name}_D"], res[f"{name}_jk_se"])
     return res
