@@ -708,6 +708,42 @@ int tq_dstat_jackknife_masks_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_
                                  const uint32_t *d_set_of, const uint16_t *d_lmask, const uint16_t *d_rmask, int64_t N,
                                  double *d_out, void *stream);
 
+/* Pooled five-taxon site-pattern classes of SPECIES sets per block of sites: the block rows of
+ * section 22 for the species map of tq_set_species, so that tq_dstat_jackknife_masks* give DFOIL and partitioned D between
+ * populations.
+ *   Rule: a species set is five ids k0 < k1 < k2 < k3 < k4; n_i[x] (x = 0..3) is the number of lineages of species k_i
+ *   with base x at a site (a missing base counts nowhere; option "species_alleles": two lineages per sample).  The pooled
+ *   count of class k = 1..15 at the site is the number of lineage quintets, one lineage per species in position order,
+ *   whose five bases take exactly two values and whose class (tq_quintet_class_table) is k.  With M the positions i >= 1
+ *   whose bit i - 1 is set in k, Mc the other positions and d(T) = sum over x of the product over i in T of n_i[x], it
+ *   equals d(Mc) d(M) - d({0,1,2,3,4}).  Invariant sites and sites with three or four bases count nowhere;
+ *   "count_invariant" is not read.  A block row is u32[16]: slot k = the count of class k summed over the block's sites,
+ *   slot 0 = the sum of slots 1..15; blocks and block_starts as in tq_patterns_blocks.  u32, exact under the range rule
+ *   S x product of the five largest species sizes < 2^32 (sizes in lineages).
+ *   tq_patterns_quintet_blocks_species      ssets5 u32[Q,5], host buffers, synchronous; classes u32[Q][B][16].  Refuses
+ *                      NULL and negative Q, whatever the species calls refuse (no data, no map, a map for another T, the
+ *                      range rule of four species, allele mode without a replicate built from the source), the range rule
+ *                      of five species above, the block rule, an id >= K and a row not strictly ascending, all before
+ *                      anything is launched.  Q = 0 is valid.  Chunks by option "batch" as tq_patterns_blocks does.
+ *   tq_patterns_quintet_blocks_species_dev  d_ssets5 (4-byte aligned) / d_classes (16-byte aligned; either misaligned is
+ *                      refused before anything is launched) device pointers, enqueued on `stream` under the stream rule
+ *                      above: ordered behind a tq_bootstrap_async that rebuilds the layout, and the species table follows
+ *                      the replicate without a tq_set_species in between.  The rows are the caller's responsibility: an
+ *                      id >= K gives a row of zeros, and so does a row that repeats species so that S x its own lineage
+ *                      product reaches 2^32.  block_starts travels as in tq_patterns_blocks_dev.
+ *   Neither reads scan_method, phases, count_invariant or species_method (only a species_method the map's sizes do not
+ *   allow is refused, as by every species call); neither touches the count slab, records a timing mark or counts as a
+ *   call of tq_timing_read*.  tq_dstat_jackknife_masks* take the rows as they are: a_j + b_j <= 15 (2^32 - 1).
+ *   tq_pooled_quintet_site_classes  host-only, no context: the rule for ONE site.  packed[5] = the five species' counts
+ *                      in position order, each {n_A, n_C, n_G, n_T} as bytes 0..3 of a word; out[16] = the class row of
+ *                      that site, computed by the functions the kernel runs (arithmetic modulo 2^32; counts up to 255^4
+ *                      x 255 that fit u32 are exact).                                                                 */
+int tq_patterns_quintet_blocks_species(tq_ctx *ctx, const uint32_t *ssets5, int64_t Q, const int64_t *block_starts, int64_t B,
+                                       uint32_t *classes);
+int tq_patterns_quintet_blocks_species_dev(tq_ctx *ctx, const uint32_t *d_ssets5, int64_t Q, const int64_t *block_starts,
+                                           int64_t B, uint32_t *d_classes, void *stream);
+int tq_pooled_quintet_site_classes(const uint32_t packed[5], uint32_t out[16]);
+
 /* Site concordance factors per branch of a fixed tree: sCF / sDF1 / sDF2 / sN of Minh, Hahn &
  * Lanfear 2020 from the class rows above.  No reference counterpart in tetrad itself.
  *   Rule: a row is a set (a, b, c, d) with its class row u32[16] as the pattern calls write it.  The tree gives the

@@ -47,6 +47,7 @@ SYMBOLS = [
     "tq_patterns_blocks_species", "tq_patterns_blocks_species_dev", "tq_pooled_site_classes",
     "tq_quintet_class_table", "tq_patterns_quintet_blocks", "tq_patterns_quintet_blocks_dev",
     "tq_dstat_jackknife_masks", "tq_dstat_jackknife_masks_dev",
+    "tq_patterns_quintet_blocks_species", "tq_patterns_quintet_blocks_species_dev", "tq_pooled_quintet_site_classes",
     "tq_scf_create", "tq_scf_destroy", "tq_scf_reset", "tq_scf_add", "tq_scf_add_dev", "tq_scf_shape", "tq_scf_read",
 ]
 
@@ -288,6 +289,12 @@ def load() -> ctypes.CDLL:
     lib.tq_dstat_jackknife_masks.restype = i32
     lib.tq_dstat_jackknife_masks_dev.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, vp, vp]
     lib.tq_dstat_jackknife_masks_dev.restype = i32
+    lib.tq_patterns_quintet_blocks_species.argtypes = [vp, vp, i64, vp, i64, vp]
+    lib.tq_patterns_quintet_blocks_species.restype = i32
+    lib.tq_patterns_quintet_blocks_species_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    lib.tq_patterns_quintet_blocks_species_dev.restype = i32
+    lib.tq_pooled_quintet_site_classes.argtypes = [vp, vp]
+    lib.tq_pooled_quintet_site_classes.restype = i32
     lib.tq_scf_create.argtypes = [c.POINTER(vp), vp, i64, i64, vp]
     lib.tq_scf_create.restype = i32
     lib.tq_scf_destroy.argtypes = [vp]

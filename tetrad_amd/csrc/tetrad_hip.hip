@@ -42,6 +42,8 @@
 //   species_blocks.hpp tq_species_blocks_kernel: pooled class rows of species sets per block of sites from the species table
 //   quintet_blocks.hpp tq_quintet_blocks_kernel: five-taxon class rows per block of sites + the mask form of
 //                 tq_jackknife_kernel: the block jackknife on sums of slots (DFOIL, partitioned D)
+//   species_quintet_blocks.hpp tq_species_quintet_blocks_kernel: pooled five-taxon class rows of species sets per block of
+//                 sites from the species table
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -93,6 +95,7 @@ namespace {
 #include "pattern_blocks.hpp"
 #include "species_blocks.hpp"
 #include "quintet_blocks.hpp"
+#include "species_quintet_blocks.hpp"
 #include "scf.hpp"
 
 }  // namespace
@@ -185,6 +188,7 @@ struct tq_ctx {
     int64_t sp_T = 0, sp_K = 0;     // sp_K = 0: no map set
     std::vector<int32_t> sp_size;   // lineages per species
     uint64_t sp_bound = 0;          // product of the four largest species sizes (range rule: S * sp_bound < 2^32)
+    uint64_t sp_bound5 = 0;         // product of the five largest (of all four where K = 4): the rule of five-species rows
     int32_t sp_max = 0;             // largest species size
     DevBuf<int32_t> d_sp_members;   // offsets [K+1], then the member samples grouped by species [T], then 2 x offsets [K+1]
     DevBuf<uint32_t> d_sp_tab;      // u32 [K][Sp]: {n_A, n_C, n_G, n_T} per species and site, then u8 [K][4][Sp] (MFMA form):
@@ -1574,16 +1578,32 @@ int jackknife_dev(tq_ctx *ctx, const char *who, const uint32_t *d_bclasses, int6
                            d_out);
 }
 
-// Block rows: of quartets (pattern_blocks.hpp), of species quartets (species_blocks.hpp) or of five-taxon sets
-// (quintet_blocks.hpp).
-enum BlockKind { BLK_QUARTET, BLK_SPECIES, BLK_QUINTET };
+// Block rows: of quartets (pattern_blocks.hpp), of species quartets (species_blocks.hpp), of five-taxon sets
+// (quintet_blocks.hpp) or of five-species sets (species_quintet_blocks.hpp).
+enum BlockKind { BLK_QUARTET, BLK_SPECIES, BLK_QUINTET, BLK_SPECIES_QUINTET };
 
-constexpr int block_set_width(BlockKind kind) { return kind == BLK_QUINTET ? QNT_TAXA : 4; }
+constexpr int block_set_width(BlockKind kind) { return kind == BLK_QUINTET || kind == BLK_SPECIES_QUINTET ? QNT_TAXA : 4; }
+constexpr bool block_set_species(BlockKind kind) { return kind == BLK_SPECIES || kind == BLK_SPECIES_QUINTET; }
+
+// The range rule of five-species rows, behind species_ready (which holds the rule of four): every sum of a site is at most
+// the product of the five totals, so S x product of the five largest species sizes < 2^32 keeps every slot in u32.
+int species_quintet_ready(tq_ctx *ctx, const char *who)
+{
+    const int lin = species_lineages(ctx);
+    const uint64_t bound = ctx->sp_bound5 * (uint64_t)(lin * lin * lin * lin * lin);        // <= 255^5 x 32 < 2^45
+    if ((unsigned __int128)ctx->S * bound >= ((unsigned __int128)1 << 32))
+        return fail(ctx, TQ_ERR_INVALID_ARG,
+                    "%s: pooled counts may exceed u32: S=%lld x product of the five largest species sizes %llu >= 2^32%s",
+                    who, (long long)ctx->S, (unsigned long long)bound, lin == 2 ? " (sizes in lineages: 2 per sample)" : "");
+    return TQ_OK;
+}
 
 // What every form checks before anything is launched: the data (and the species map) and the block rule.
 int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *block_starts, int64_t B)
 {
-    if (int rc = kind == BLK_SPECIES ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
+    if (int rc = block_set_species(kind) ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
+    if (kind == BLK_SPECIES_QUINTET)
+        if (int rc = species_quintet_ready(ctx, who)) return rc;
     if (int rc = check_block_count(ctx, who, B)) return rc;
     if (block_starts[0] < 0)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[0]=%lld is negative", who, (long long)block_starts[0]);
@@ -1618,13 +1638,14 @@ int stage_block_starts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, hipS
     return TQ_OK;
 }
 
-// Block rows of sets dq[0..Q) (u32[Q][4], five-taxon sets u32[Q][5]) into d_classes [Q][B][16]; the boundaries are in
-// ctx->d_bstarts on this stream.  Always the natural layout; species sets read the species table (species_blocks.hpp),
+// Block rows of sets dq[0..Q) (u32[Q][4], five-taxon and five-species sets u32[Q][5]) into d_classes [Q][B][16]; the
+// boundaries are in ctx->d_bstarts on this stream.  Always the natural layout; species sets read the species table
+// (species_blocks.hpp, species_quintet_blocks.hpp),
 // which is brought up to date on this stream first.  Neither the count slab nor the timing marks are touched.  A launch
 // holds fewer than 2^31 items.
 int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, int64_t B, uint32_t *d_classes, hipStream_t stream)
 {
-    if (kind == BLK_SPECIES)
+    if (block_set_species(kind))
         if (int rc = ensure_species_table(ctx, stream)) return rc;
     const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
     const uint32_t *planes3 = ctx->nat.planes3;
@@ -1639,6 +1660,10 @@ int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, in
             hipLaunchKernelGGL(tq_species_blocks_kernel, grid, block, 0, stream, (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S,
                                (uint32_t)ctx->sp_K, species_lineage_offsets(ctx), sets, n, starts, B, rows);
             break;
+        case BLK_SPECIES_QUINTET:
+            hipLaunchKernelGGL(tq_species_quintet_blocks_kernel, grid, block, 0, stream, (const uint32_t *)ctx->d_sp_tab,
+                               ctx->nat.Sp, ctx->S, (uint32_t)ctx->sp_K, species_lineage_offsets(ctx), sets, n, starts, B, rows);
+            break;
         case BLK_QUINTET:
             hipLaunchKernelGGL(tq_quintet_blocks_kernel, grid, block, 0, stream, planes3, ctx->nat.W, (uint32_t)ctx->T, sets, n,
                                starts, B, rows);
@@ -1652,7 +1677,8 @@ int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, in
     return TQ_OK;
 }
 
-// host sets -> host block rows (synchronous): tq_patterns_blocks, tq_patterns_blocks_species and tq_patterns_quintet_blocks
+// host sets -> host block rows (synchronous): tq_patterns_blocks, tq_patterns_blocks_species, tq_patterns_quintet_blocks
+// and tq_patterns_quintet_blocks_species
 int blocks_to_host(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *sets, int64_t Q, const int64_t *block_starts,
                    int64_t B, uint32_t *classes)
 {
@@ -1662,7 +1688,7 @@ int blocks_to_host(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t 
     int rc = blocks_ready(ctx, who, kind, block_starts, B);
     if (rc) return rc;
     const int width = block_set_width(kind);
-    if ((rc = check_set_rows(ctx, who, sets, Q, width, kind == BLK_SPECIES))) return rc;
+    if ((rc = check_set_rows(ctx, who, sets, Q, width, block_set_species(kind)))) return rc;
     if (Q == 0) return TQ_OK;
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
@@ -2627,6 +2653,7 @@ int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
     std::sort(top.begin(), top.end(), [](int32_t a, int32_t b) { return a > b; });
     uint64_t bound = 1;
     for (int i = 0; i < 4; ++i) bound *= (uint64_t)top[(size_t)i];
+    const uint64_t bound5 = bound * (uint64_t)(K > 4 ? top[4] : 1);     // <= 255^5 < 2^40
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     TQ_HIP(ctx, hipDeviceSynchronize());         // a species call may still read the old map / table
     ctx->sp_K = 0;
@@ -2636,6 +2663,7 @@ int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
     ctx->sp_T = T;
     ctx->sp_K = K;
     ctx->sp_bound = bound;
+    ctx->sp_bound5 = bound5;
     ctx->sp_max = top[0];
     ctx->sp_tab_gen = ~0ull;
     return TQ_OK;
@@ -2808,6 +2836,29 @@ int tq_patterns_quintet_blocks_dev(tq_ctx *ctx, const uint32_t *d_sets5, int64_t
 {
     return blocks_dev(ctx, "tq_patterns_quintet_blocks_dev", BLK_QUINTET, d_sets5, Q, block_starts, B, d_classes,
                       (hipStream_t)stream);
+}
+
+int tq_patterns_quintet_blocks_species(tq_ctx *ctx, const uint32_t *ssets5, int64_t Q, const int64_t *block_starts, int64_t B,
+                                       uint32_t *classes)
+{
+    return blocks_to_host(ctx, "tq_patterns_quintet_blocks_species", BLK_SPECIES_QUINTET, ssets5, Q, block_starts, B, classes);
+}
+
+int tq_patterns_quintet_blocks_species_dev(tq_ctx *ctx, const uint32_t *d_ssets5, int64_t Q, const int64_t *block_starts,
+                                           int64_t B, uint32_t *d_classes, void *stream)
+{
+    return blocks_dev(ctx, "tq_patterns_quintet_blocks_species_dev", BLK_SPECIES_QUINTET, d_ssets5, Q, block_starts, B, d_classes,
+                      (hipStream_t)stream);
+}
+
+int tq_pooled_quintet_site_classes(const uint32_t *packed, uint32_t *out)
+{
+    if (!packed || !out) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_pooled_quintet_site_classes: NULL pointer");
+    uint32_t f[PAT_ROW] = {}, row[PAT_ROW];
+    pooled5_site_f(packed[0], packed[1], packed[2], packed[3], packed[4], f);
+    pooled5_finish(f, row);
+    memcpy(out, row, sizeof(row));
+    return TQ_OK;
 }
 
 int tq_dstat_jackknife_masks(const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of, const uint16_t *lmask,

@@ -375,6 +375,19 @@ class QuartetEngine:
         self._check(self._lib.tq_dstat_jackknife_masks_dev(self._h, d_bclasses, n_sets, B, d_set_of, d_lmask, d_rmask, N,
                                                            d_out, stream or None))
 
+    # -- pooled five-taxon class rows of species sets per block ----
+    def patterns_quintet_blocks_species(self, ssets5, block_starts) -> np.ndarray:
+        """Block rows u32[Q,B,16] of strictly ascending five-SPECIES sets `ssets5` [Q,5]: slot k = 1..15 of block j counts
+        the lineage quintets (one lineage per species) that show class k at a site of [block_starts[j], block_starts[j+1]),
+        summed over its sites; slot 0 is their sum.  Needs `set_species`."""
+        return self._blocks_host(self._lib.tq_patterns_quintet_blocks_species, self._sets5(ssets5), block_starts)
+
+    def patterns_quintet_blocks_species_dev(self, d_ssets5: int, Q: int, block_starts, d_classes: int, stream: int = 0):
+        """The same with device pointers (u32[Q,5] in, 4-byte aligned; u32[Q,B,16] out, 16-byte aligned), enqueued on
+        `stream`; `block_starts` is a host array, read before the call returns.  The rows are the caller's
+        responsibility (an id >= K gives zeros)."""
+        self._blocks_dev(self._lib.tq_patterns_quintet_blocks_species_dev, d_ssets5, Q, block_starts, d_classes, stream)
+
     # -- device-pointer API (addresses as ints, e.g. torch.Tensor.data_ptr()) -------
     def resolve_dev(self, d_quartets: int, Q: int, subsample_snps: bool, d_rstat: int,
                     d_rscor: int, d_flags: int = 0, stream: int = 0):

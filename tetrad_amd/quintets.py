@@ -11,6 +11,10 @@ order, and a role assignment is a relabelling: `quintet_tests` turns tests in ro
 and, per test and statistic, two u16 slot masks.  The jackknife is the one of the four-taxon D test
 (`patterns.run_dstat_jackknife`), with a block's a_j and b_j the sums of the row's slots under the two masks.
 
+With a species map the same rows exist for five species, pooled over one lineage per species
+(`QuartetEngine.patterns_quintet_blocks_species`), and `run_quintet_jackknife(species_of=...)` runs
+the tests between populations.
+
 `DFOIL` (Pease & Hahn 2015) is defined on the tree ((P1,P2),(P3,P4)),O; `PARTITIONED_D` (Eaton & Ree 2013) reads the
 roles as (P1, P2, P3_1, P3_2, O).
 """
@@ -124,12 +128,15 @@ def result_dtype(stats) -> np.dtype:
 
 
 def run_quintet_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, stats=DFOIL, nblocks: int = 50, block_starts=None,
-                          chunk: int = 1 << 16, *, resident: bool = False) -> np.ndarray:
+                          chunk: int = 1 << 16, *, resident: bool = False, species_of=None) -> np.ndarray:
     """Five-taxon tests with a block jackknife, full mode.  `set_data(tmparr, tmpmap)`, then the unique sets of `tests`
     int[N,5] = (P1, P2, P3, P4, O) in chunks of `chunk`: the block rows of the chunk (`patterns_quintet_blocks_dev`, torch
     memory of chunk x B x 64 bytes, re-used) and one jackknife launch per statistic on the chunk's tests
     (`dstat_jackknife_masks_dev`), all on the current stream; one device-to-host copy at the end.  Blocks, `resident`
-    and `tmpmap` as in `patterns.run_dstat_jackknife`.
+    and `tmpmap` as in `patterns.run_dstat_jackknife`.  With `species_of` (i32[T], see `QuartetEngine.set_species`) the
+    tests name species and the block rows are those of the pooled lineages (`patterns_quintet_blocks_species_dev`,
+    DESIGN.md section 23); the map is set after `set_data` or, with `resident=True`, on the resident replicate (the way to
+    allele mode, as in `patterns.run_dstat_jackknife`).
     Returns a structured array per test (`result_dtype(stats)`): nsites (slot 0 summed over the blocks) and per
     statistic left, right (sums over the blocks), D, jk_blocks, jk_mean, jk_se, Z = D / jk_se; NaN where undefined."""
     if int(chunk) < 1:
@@ -138,13 +145,16 @@ def run_quintet_jackknife(engine: QuartetEngine, tmparr, tmpmap, tests, stats=DF
     sets, set_of, masks = quintet_tests(tests, stats)
     if not resident:
         engine.set_data(tmparr, tmpmap)
+    if species_of is not None:
+        engine.set_species(species_of)
+    block_rows_dev = engine.patterns_quintet_blocks_dev if species_of is None else engine.patterns_quintet_blocks_species_dev
     starts = _jackknife_starts(engine, tmpmap, nblocks, block_starts)
     N, K = len(set_of), len(names)
     res = np.zeros(N, result_dtype(stats))
     if N == 0 or K == 0:
         return res
-    sums, jk = _run_block_jackknife(engine, engine.patterns_quintet_blocks_dev, engine.dstat_jackknife_masks_dev, sets, set_of,
-                                    masks.transpose(1, 2, 0), starts, chunk)
+    sums, jk = _run_block_jackknife(engine, block_rows_dev, engine.dstat_jackknife_masks_dev, sets, set_of, masks.transpose(1, 2, 0),
+                                    starts, chunk)
     rows = sums[set_of.astype(np.int64)].astype(np.uint64)                       # [N, 16]
     slot = np.arange(16, dtype=np.uint16)
     res["nsites"] = rows[:, 0]
