@@ -265,6 +265,20 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value);
  * if that set was the packed one, else 0.  No reference counterpart.                                                */
 int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes);
 
+/* Test hook: the scan kernel the library would launch, for n rows of options and batch shape (host code: no context, no
+ * device).  rows i64[n][22]: the options scan_pair, scan_wg, scan_method, scan_f4, scan_dp, park_t, share_c,
+ * count_invariant, waves_per_cu, nrep, order, wg_min_quartets, dp_min_quartets as the context holds them (defaults
+ * resolved: tq_set_option's 0 = default is not applied here), pb_ok (1: the start-up probe of tq_scan_pb_kernel passed, as
+ * on every device so far; -1: it failed), xcd_remap, the CU count; then T, the padded sites per row of the layout set
+ * the scan reads, the same of the natural set, Q, subsample, and 1 if the quartets arrive in sorted order.
+ * plans i64[n][12]: the kernel form (as tq_debug_fetch which = 6), the kernel's template arguments SUB, METHOD, NW, SHC,
+ * PARK_T, NREP (0 where the form's kernel has no such argument), quartets per workgroup, threads per workgroup, grid
+ * (0: the one-wave form sizes it by the occupancy query at launch), xcd_chunk, and the row of the library's table of
+ * scan instantiations that holds this kernel (-1: none is built -- a launch would fail).  *n_kernels (may be NULL)
+ * gets the number of rows of that table.  It is the function the launch itself calls.
+ * No reference counterpart.                                                                                          */
+int tq_scan_plan(const int64_t *rows, int64_t n, int64_t *plans, int64_t *n_kernels);
+
 /* Test hook: run the bidiagonal-QR kernel (tq_bdsqr_kernel) alone on nmat bidiagonals given on the host -- de f64[nmat][32]
  * as tq_debug_fetch(which = 1) hands them out, in ANY order: lane i of wave w gets matrix 64 w + i -- and return the singular
  * values sv f64[nmat][16] (unsorted; may be NULL), per matrix its rotation steps | sweeps << 16 (work u32[nmat]; may be NULL)

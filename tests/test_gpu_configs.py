@@ -259,6 +259,46 @@ def test_scan_kernel_variants_agree_on_sorted_batches(cfg, nq):
                     np.testing.assert_array_equal(a, b, err_msg=f"{opts} sub={sub}")
 
 
+def test_scan_plan_names_the_form_that_is_launched():
+    """tq_scan_plan is host code; this ties it to the launch.  16 taxa x 5000 sites (two whole 2048-site steps and a partial
+    one), all 1820 quartets, both thresholds at 64: for one option set per kernel form and mode, the form `last_scan`
+    reports after the call is the form of the plan for the same options and shape (shape from last_scan and device_info),
+    the plan has a kernel, and the rows are bitwise those of the defaults (count_invariant apart: it counts other sites)."""
+    from scan_plan_model import DEFAULT_KNOBS, KNOB_FIELDS
+    from tetrad_amd import synth
+    from tetrad_amd.engine import QuartetEngine, scan_plan
+    T = 16
+    tmparr, tmpmap = synth.simulate_tmparr(T, 5000, 21)
+    q = synth.all_quartets(T)
+    cases = [(1, {}, "f4"), (0, {}, "dp"), (1, {"scan_f4": 0}, "wg"), (0, {"scan_dp": 0}, "wg"), (1, {"scan_pair": 1}, "wg2"),
+             (0, {"scan_pair": 1}, "wg2"), (0, {"scan_f4": 1}, "f4"), (1, {"scan_wg": 1}, "one_wave"),
+             (0, {"count_invariant": 1}, "one_wave")]
+    with QuartetEngine(0) as eng:
+        eng.set_option("wg_min_quartets", 64)
+        eng.set_option("dp_min_quartets", 64)
+        eng.set_data(tmparr, tmpmap)
+        base = {sub: eng.resolve(q, bool(sub)) for sub in (0, 1)}
+        seen = set()
+        for sub, opts, expected in cases:
+            for name, value in opts.items():
+                eng.set_option(name, value)
+            got = eng.resolve(q, bool(sub))
+            form, tpitch, _ = eng.last_scan()
+            info = eng.device_info()
+            for name in opts:
+                eng.set_option(name, DEFAULT_KNOBS[name])
+            knobs = dict(DEFAULT_KNOBS, wg_min_quartets=64, dp_min_quartets=64, num_cu=info["num_cu"], **opts)
+            row = [knobs[f] for f in KNOB_FIELDS] + [T, tpitch // T, info["row_pitch"], len(q), sub, 0]
+            plan = scan_plan([row])[0][0]
+            assert QuartetEngine.SCAN_FORMS[plan[0]] == form == expected, (sub, opts)
+            assert plan[11] >= 0
+            seen.add(form)
+            if "count_invariant" not in opts:
+                for a, b in zip(base[sub], got):
+                    np.testing.assert_array_equal(a, b, err_msg=f"{opts} sub={sub}")
+        assert seen == {"one_wave", "wg", "wg2", "f4", "dp"}
+
+
 @pytest.mark.parametrize("case", ["dense_T8_S400", "tree_T12_S2000", "sparse_T10_S257", "edge_T7_S130", "carry_T6_S2500",
                                   "minrank_T14_S600"])
 def test_row_f4_kernel_on_golden_cases(case):

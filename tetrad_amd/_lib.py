@@ -32,7 +32,7 @@ SYMBOLS = [
     "tq_host_alloc", "tq_host_free", "tq_resolve_to_host", "tq_scan_dev", "tq_svd_dev",
     "tq_resolve_dev", "tq_resolve_range_dev", "tq_unrank_dev", "tq_resolve_debug",
     "tq_timing_enable", "tq_timing_read", "tq_timing_read_split", "tq_timing_read_kernels",
-    "tq_set_option", "tq_device_info", "tq_debug_fetch", "tq_debug_bdsqr",
+    "tq_set_option", "tq_device_info", "tq_debug_fetch", "tq_scan_plan", "tq_debug_bdsqr",
     "tq_format_tsv", "tq_format_qmc", "tq_qmc_tree", "tq_qmc_splits", "tq_unrank", "tq_numpy_choice_tail",
     "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
     "tq_stree_create", "tq_stree_destroy", "tq_stree_reset", "tq_stree_add", "tq_stree_add_dev", "tq_stree_graph",
@@ -169,6 +169,8 @@ def load() -> ctypes.CDLL:
     lib.tq_timing_read_split.restype = i32
     lib.tq_debug_fetch.argtypes = [vp, i32, vp, i64]
     lib.tq_debug_fetch.restype = i32
+    lib.tq_scan_plan.argtypes = [vp, i64, vp, c.POINTER(i64)]
+    lib.tq_scan_plan.restype = i32
     lib.tq_debug_bdsqr.argtypes = [vp, vp, i64, vp, vp, i32, c.POINTER(c.c_double)]
     lib.tq_debug_bdsqr.restype = i32
     lib.tq_set_option.argtypes = [vp, c.c_char_p, i64]

@@ -28,6 +28,7 @@
 //   scan_dp.hpp   tq_scan_dp_kernel: two quartets that share three taxa per wave, one joint histogram (default of full mode
 //                 from 32 768 quartets on); unit list from the sorted order
 //   scan_pb.hpp   tq_scan_pb_kernel: bank-private counters (A/B form)
+//   scan_plan.hpp (host) choose_scan: which of the scan kernels takes a batch, and its grid
 //   hqr.hpp       tq_bidiag_kernel + tq_bdsqr_kernel + tq_score_kernel: singular values (default)
 //   jacobi.hpp    tq_svd_kernel: one-sided Jacobi singular values in registers (alternative)
 //   bootstrap.hpp tq_boot_*: bootstrap replicate built on the device
@@ -81,6 +82,7 @@ namespace {
 #include "scan_pb.hpp"
 #include "scan_dp.hpp"
 #include "scan_f4.hpp"
+#include "scan_plan.hpp"
 #include "jacobi.hpp"
 #include "hqr.hpp"
 #include "bootstrap.hpp"
@@ -385,7 +387,7 @@ uint64_t choose4(uint64_t T) { return T < 4 ? 0 : T * (T - 1) / 2 * (T - 2) / 3 
 // it would send the batch to the one-wave kernel, so such a set is not built automatically.
 bool pack_fits_offsets(int64_t T, size_t packedSp, size_t naturalSp)
 {
-    return (uint64_t)T * (uint64_t)packedSp < 0xFFFF0000ull || (uint64_t)T * (uint64_t)naturalSp >= 0xFFFF0000ull;
+    return (uint64_t)T * (uint64_t)packedSp < SCAN_OFFSET_LIMIT || (uint64_t)T * (uint64_t)naturalSp >= SCAN_OFFSET_LIMIT;
 }
 
 // Contiguous copy of a strided locus column and the check subsample mode and the packed order rely on: no id 0xFFFFFFFF
@@ -531,17 +533,6 @@ int make_order(tq_ctx *ctx, const uint32_t *dq, int64_t n, bool input_sorted, hi
     return TQ_OK;
 }
 
-// Joint-histogram scan (scan_dp.hpp) for this batch?  Full mode, automatic kernel choice, the default workgroup shape,
-// keys that hold (a,b,c), and an order the pairing can rely on (sorted here, or sorted on arrival).
-bool use_dp(const tq_ctx *ctx, int64_t n, int subsample, bool input_sorted)
-{
-    const uint64_t T = (uint64_t)ctx->T;
-    return !subsample && ctx->scan_dp && ctx->scan_f4 <= 0 && ctx->scan_method < 0 && ctx->scan_wg == 4 && !ctx->count_invariant &&
-           !ctx->share_c && !ctx->scan_pair && ctx->waves_per_cu == 0 && (ctx->order || input_sorted) &&
-           n >= ctx->dp_min_quartets && n >= 2 && n <= 0x7FFFFFFF && T * T * T <= 0xFFFFFFFFull &&
-           T * (uint64_t)ctx->nat.Sp < 0xFFFF0000ull;
-}
-
 // ordering + unit list of the joint-histogram scan: d_units[0..count) = (first quartet, second quartet or DP_NONE) in
 // (a,b,c)-sorted order, count in d_units[cm_quartets] (read by the kernel: nothing comes back to the host)
 int make_units(tq_ctx *ctx, const uint32_t *dq, int64_t n, bool input_sorted, hipStream_t stream)
@@ -592,9 +583,16 @@ DevData scan_data(const tq_ctx *ctx, int subsample)
     return d;
 }
 
-// kernel forms of a scan launch as tq_debug_fetch(which = 6) reports them
-enum { SCAN_FORM_NONE = 0, SCAN_FORM_ONE_WAVE = 1, SCAN_FORM_WG = 2, SCAN_FORM_WG2 = 3, SCAN_FORM_F4 = 4, SCAN_FORM_PB = 5,
-       SCAN_FORM_DP = 6 };
+static_assert(SCAN_WAVE == WAVE && SCAN_TILE == TILE && SCAN_PB_NW == PB_NW && SCAN_PB_MAX_TILES == PB_MAX_TILES &&
+              SCAN_DP_NW == DP_NW, "scan_plan.hpp and the kernel headers disagree");
+
+// the options choose_scan reads
+ScanKnobs scan_knobs(const tq_ctx *ctx)
+{
+    return {ctx->scan_pair, ctx->scan_wg, ctx->scan_method, ctx->scan_f4, ctx->scan_dp, ctx->park_t, ctx->share_c,
+            ctx->count_invariant, ctx->waves_per_cu, ctx->nrep, ctx->order, ctx->wg_min_quartets, ctx->dp_min_quartets,
+            ctx->pb_ok, ctx->xcd_remap, ctx->prop.multiProcessorCount};
+}
 
 // remembers which kernel form takes the batch and the layout set it reads (a test hook; decides nothing)
 void note_scan(tq_ctx *ctx, int form, const DevData &d)
@@ -620,57 +618,114 @@ int grid_for(tq_ctx *ctx, K kern, int64_t items, int64_t *grid, int wpc_kernel =
     return TQ_OK;
 }
 
-template <int NREP, bool SUB, int METHOD>
-int launch_scan(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+// ---- the scan launch: choose_scan (scan_plan.hpp) names an instantiation, this table holds every one that is built --------
+using ScanWaveFn = void (*)(DevData, const uint32_t *, const uint32_t *, int64_t, uint32_t *);
+using ScanWgFn = void (*)(DevData, const uint32_t *, const uint32_t *, int64_t, uint32_t *, int64_t);            // WG, WG2, F4
+using ScanPbFn = void (*)(DevData, const uint32_t *, const uint32_t *, int64_t, uint32_t *, int64_t, uint32_t *);
+using ScanDpFn = void (*)(DevData, const uint32_t *, const uint2 *, const uint32_t *, uint32_t *);
+
+struct ScanKernel {
+    int form, sub, method, nw, shc, park, nrep;    // as in ScanPlan
+    ScanWaveFn wave;                               // exactly one of the four is set: the form's signature
+    ScanWgFn wg;
+    ScanPbFn pb;
+    ScanDpFn dp;
+};
+
+template <int NREP>
+void add_wave_rows(std::vector<ScanKernel> &t)
 {
-    auto kern = tq_scan_kernel<NREP, SUB, METHOD>;
-    int64_t grid;
-    int rc = grid_for(ctx, kern, Q, &grid);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVE), 0, stream, d, dq, order, Q, ctx->d_cm);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    t.push_back({SCAN_FORM_ONE_WAVE, 0, 0, 1, 0, 0, NREP, tq_scan_kernel<NREP, false, 0>});
+    t.push_back({SCAN_FORM_ONE_WAVE, 0, 1, 1, 0, 0, NREP, tq_scan_kernel<NREP, false, 1>});
+    t.push_back({SCAN_FORM_ONE_WAVE, 1, 0, 1, 0, 0, NREP, tq_scan_kernel<NREP, true, 0>});
+    t.push_back({SCAN_FORM_ONE_WAVE, 1, 1, 1, 0, 0, NREP, tq_scan_kernel<NREP, true, 1>});
 }
 
 template <bool SUB, int METHOD, int NW, bool SHC = false, bool PARK_T = false>
-int launch_scan_wg(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+ScanKernel wg_row()
 {
-    auto kern = tq_scan_wg_kernel<SUB, METHOD, NW, SHC, PARK_T>;
-    const int wgs = ctx->waves_per_cu > 0 ? (ctx->waves_per_cu + NW - 1) / NW : 0;
-    // default: one block of NW quartets per workgroup, dispatched in sorted order.  Workgroups that
-    // run at the same time are then neighbours of the (a,b) order (their shared rows are L2 hits) and
-    // the dispatcher balances the load; a persistent grid-stride loop was 13 % slower.
-    const int64_t nblk = (Q + NW - 1) / NW;
-    int64_t grid = wgs > 0 ? (int64_t)ctx->prop.multiProcessorCount * wgs : nblk;
-    int64_t xcd_chunk = 0;
-    if (grid >= nblk) {
-        grid = nblk;
-        if (ctx->xcd_remap && nblk >= 64) {                  // one block per workgroup, XCD-contiguous
-            xcd_chunk = (nblk + 7) / 8;
-            grid = xcd_chunk * 8;
-        }
-    }
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), 0, stream, d, dq, order, Q,
-                       ctx->d_cm, xcd_chunk);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    return {SCAN_FORM_WG, SUB, METHOD, NW, SHC, PARK_T, 0, nullptr, tq_scan_wg_kernel<SUB, METHOD, NW, SHC, PARK_T>};
 }
 
-// bank-private counters (scan_pb.hpp): one block of 4 quartets per workgroup, as launch_scan_wg
-template <bool SUB>
-int launch_scan_pb(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
+template <int NW>
+void add_wg_rows(std::vector<ScanKernel> &t)       // what every width has: methods 0 and 1 per mode, diagnostics 2 and 3
 {
-    auto kern = tq_scan_pb_kernel<SUB>;
-    const int64_t nblk = (Q + PB_NW - 1) / PB_NW;
-    int64_t grid = nblk, xcd_chunk = 0;
-    if (ctx->xcd_remap && nblk >= 64) {                      // one block per workgroup, XCD-contiguous
-        xcd_chunk = (nblk + 7) / 8;
-        grid = xcd_chunk * 8;
+    t.push_back(wg_row<false, 0, NW>());
+    t.push_back(wg_row<false, 1, NW>());
+    t.push_back(wg_row<true, 0, NW>());
+    t.push_back(wg_row<true, 1, NW>());
+    t.push_back(wg_row<true, 2, NW>());
+    t.push_back(wg_row<true, 3, NW>());
+}
+
+template <bool SUB, int NW>
+ScanKernel f4_row() { return {SCAN_FORM_F4, SUB, 0, NW, 0, 0, 0, nullptr, tq_scan_f4_kernel<SUB, NW>}; }
+
+template <bool SUB, int METHOD>
+ScanKernel wg2_row() { return {SCAN_FORM_WG2, SUB, METHOD, 4, 0, 0, 0, nullptr, tq_scan_wg2_kernel<SUB, METHOD, 4>}; }
+
+std::vector<ScanKernel> build_scan_table()
+{
+    std::vector<ScanKernel> t;
+    add_wave_rows<1>(t), add_wave_rows<2>(t), add_wave_rows<4>(t), add_wave_rows<8>(t), add_wave_rows<16>(t), add_wave_rows<32>(t);
+    add_wg_rows<2>(t), add_wg_rows<3>(t), add_wg_rows<4>(t), add_wg_rows<6>(t), add_wg_rows<8>(t), add_wg_rows<16>(t);
+    t.push_back(wg_row<true, 4, 4>());
+    t.push_back(wg_row<true, 5, 4>());
+    t.push_back(wg_row<false, 1, 4, false, true>());                        // PARK_T
+    t.push_back(wg_row<true, 1, 4, false, true>());
+    t.push_back(wg_row<true, 1, 6, false, true>());
+    t.push_back(wg_row<true, 1, 8, false, true>());
+    t.push_back(wg_row<false, 0, 4, true>());                               // SHC
+    t.push_back(wg_row<false, 1, 4, true>());
+    t.push_back(wg_row<true, 0, 4, true>());
+    t.push_back(wg_row<true, 1, 4, true>());
+    t.push_back(wg2_row<false, 0>());
+    t.push_back(wg2_row<false, 1>());
+    t.push_back(wg2_row<true, 0>());
+    t.push_back(wg2_row<true, 1>());
+    t.push_back(f4_row<false, 2>());
+    t.push_back(f4_row<true, 2>());
+    t.push_back(f4_row<false, 4>());
+    t.push_back(f4_row<true, 4>());
+    t.push_back(f4_row<false, 8>());
+    t.push_back(f4_row<true, 8>());
+    t.push_back({SCAN_FORM_PB, 0, 0, PB_NW, 0, 0, 0, nullptr, nullptr, tq_scan_pb_kernel<false>});
+    t.push_back({SCAN_FORM_PB, 1, 0, PB_NW, 0, 0, 0, nullptr, nullptr, tq_scan_pb_kernel<true>});
+    t.push_back({SCAN_FORM_DP, 0, 0, DP_NW, 0, 0, 0, nullptr, nullptr, nullptr, tq_scan_dp_kernel<DP_NW>});
+    return t;
+}
+
+const std::vector<ScanKernel> SCAN_TABLE = build_scan_table();
+
+// the table row of a plan, or nullptr: the plan names an instantiation that is not built
+const ScanKernel *find_scan_kernel(const ScanPlan &p)
+{
+    for (const ScanKernel &k : SCAN_TABLE)
+        if (k.form == p.form && k.sub == p.sub && k.method == p.method && k.nw == p.nw && k.shc == p.shc && k.park == p.park &&
+            k.nrep == p.nrep)
+            return &k;
+    return nullptr;
+}
+
+// launches the plan of any form but DP (launch_scan_dp: another argument list)
+int launch_scan(tq_ctx *ctx, const ScanPlan &p, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q,
+                hipStream_t stream)
+{
+    const ScanKernel *k = find_scan_kernel(p);
+    if (!k || k->dp)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "no scan kernel is built for form %d sub %d method %d nw %d shc %d park %d nrep %d",
+                    p.form, p.sub, p.method, p.nw, p.shc, p.park, p.nrep);
+    if (k->wave) {
+        int64_t grid;
+        int rc = grid_for(ctx, k->wave, Q, &grid);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k->wave, dim3((unsigned)grid), dim3(p.threads), 0, stream, d, dq, order, Q, ctx->d_cm);
+    } else if (k->pb) {
+        hipLaunchKernelGGL(k->pb, dim3((unsigned)p.grid), dim3(p.threads), 0, stream, d, dq, order, Q, ctx->d_cm, p.xcd_chunk,
+                           (uint32_t *)nullptr);
+    } else {
+        hipLaunchKernelGGL(k->wg, dim3((unsigned)p.grid), dim3(p.threads), 0, stream, d, dq, order, Q, ctx->d_cm, p.xcd_chunk);
     }
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PB_NW * WAVE), 0, stream, d, dq, order, Q, ctx->d_cm,
-                       xcd_chunk, (uint32_t *)nullptr);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
 }
@@ -697,139 +752,15 @@ int probe_scan_pb(tq_ctx *ctx)
     return TQ_OK;
 }
 
-template <bool SUB, int METHOD, int NW>
-int launch_scan_wg2(tq_ctx *ctx, const DevData &d, const uint32_t *dq, const uint32_t *order, int64_t Q, hipStream_t stream)
-{
-    auto kern = tq_scan_wg2_kernel<SUB, METHOD, NW>;
-    const int64_t nblk = (Q + 2 * NW - 1) / (2 * NW);
-    int64_t grid = nblk, xcd_chunk = 0;
-    if (ctx->xcd_remap && nblk >= 64) {                      // one block per workgroup, XCD-contiguous
-        xcd_chunk = (nblk + 7) / 8;
-        grid = xcd_chunk * 8;
-    }
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * WAVE), 0, stream, d, dq, order, Q, ctx->d_cm,
-                       xcd_chunk);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
-}
-
-// joint-histogram scan over the unit list make_units left: at least ceil(Q / 2) units, at most Q -- the grid covers the
-// least (rounded to the 8 XCDs) and a workgroup whose id + grid is still a block takes that one as well
+// joint-histogram scan over the unit list make_units left (grid: scan_dp_grid)
 int launch_scan_dp(tq_ctx *ctx, const uint32_t *dq, int64_t Q, hipStream_t stream)
 {
-    const int64_t least = ((Q + 1) / 2 + DP_NW - 1) / DP_NW;
-    const int64_t grid = (least + 7) / 8 * 8;
     const DevData d = dev_data(ctx);
-    note_scan(ctx, SCAN_FORM_DP, d);
-    hipLaunchKernelGGL(tq_scan_dp_kernel<DP_NW>, dim3((unsigned)grid), dim3(DP_NW * WAVE), 0, stream, d, dq,
+    hipLaunchKernelGGL(tq_scan_dp_kernel<DP_NW>, dim3((unsigned)scan_dp_grid(Q)), dim3(DP_NW * WAVE), 0, stream, d, dq,
                        (const uint2 *)ctx->d_units, reinterpret_cast<const uint32_t *>(ctx->d_units + ctx->cm_quartets),
                        ctx->d_cm);
     TQ_HIP(ctx, hipGetLastError());
     return TQ_OK;
-}
-
-int launch_scan_n(tq_ctx *ctx, const uint32_t *dq, const uint32_t *order, int64_t Q, int subsample,
-                  hipStream_t stream)
-{
-    const DevData d = scan_data(ctx, subsample);
-    if (ctx->scan_pair && ctx->scan_wg == 4 && Q >= 64 && !ctx->count_invariant && !ctx->share_c && ctx->waves_per_cu == 0 &&
-        ctx->scan_method < 2 && (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
-        const int m = ctx->scan_method < 0 ? (subsample ? 1 : 0) : ctx->scan_method;
-        note_scan(ctx, SCAN_FORM_WG2, d);
-        if (subsample)
-            return m ? launch_scan_wg2<true, 1, 4>(ctx, d, dq, order, Q, stream) : launch_scan_wg2<true, 0, 4>(ctx, d, dq, order, Q, stream);
-        return m ? launch_scan_wg2<false, 1, 4>(ctx, d, dq, order, Q, stream) : launch_scan_wg2<false, 0, 4>(ctx, d, dq, order, Q, stream);
-    }
-    // row f4 as written (option scan_f4): own rows as 12-byte plane records only, pattern bits pulled out in the walk
-    const bool f4 = ctx->scan_f4 < 0 ? (subsample != 0 && ctx->scan_method < 0 && ctx->park_t) : ctx->scan_f4 != 0;
-    if (f4 && (ctx->scan_wg == 4 || ctx->scan_wg == 8 || ctx->scan_wg == 2) && Q >= ctx->wg_min_quartets && !ctx->count_invariant &&
-        !ctx->share_c && !ctx->scan_pair && ctx->waves_per_cu == 0 && (ctx->scan_method < 0 || ctx->scan_method == 1) &&
-        (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
-        const int nw = ctx->scan_wg;
-        const int64_t nblk = (Q + nw - 1) / nw;
-        note_scan(ctx, SCAN_FORM_F4, d);
-        int64_t grid = nblk, xcd_chunk = 0;
-        if (ctx->xcd_remap && nblk >= 64) {
-            xcd_chunk = (nblk + 7) / 8;
-            grid = xcd_chunk * 8;
-        }
-#define TQ_F4_CASE(SUBF, NWF)                                                                                         \
-        if ((subsample != 0) == SUBF && nw == NWF)                                                                    \
-            hipLaunchKernelGGL((tq_scan_f4_kernel<SUBF, NWF>), dim3((unsigned)grid), dim3(NWF * WAVE), 0, stream,      \
-                               d, dq, order, Q, ctx->d_cm, xcd_chunk);
-        TQ_F4_CASE(true, 4) TQ_F4_CASE(false, 4) TQ_F4_CASE(true, 8) TQ_F4_CASE(false, 8) TQ_F4_CASE(true, 2) TQ_F4_CASE(false, 2)
-#undef TQ_F4_CASE
-        TQ_HIP(ctx, hipGetLastError());
-        return TQ_OK;
-    }
-    // bank-private counters (option scan_method = 6, an A/B form: conflict-free atomics, but an LDS atomic costs its 4
-    // cycles of operand transfer either way and the 64 KiB of counters leave two workgroups per CU -- measured slower,
-    // scan_pb.hpp); 16-bit counters, so only while a quartet has at most PB_MAX_TILES steps
-    const bool pb_fits = ctx->pb_ok == 1 && ctx->scan_wg == 4 && Q >= 64 && !ctx->count_invariant && !ctx->share_c &&
-                         !ctx->scan_pair && ctx->waves_per_cu == 0 && d.pitch / TILE <= PB_MAX_TILES &&
-                         (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull;
-    if (pb_fits && ctx->scan_method == 6) {
-        note_scan(ctx, SCAN_FORM_PB, d);
-        return subsample ? launch_scan_pb<true>(ctx, d, dq, order, Q, stream) : launch_scan_pb<false>(ctx, d, dq, order, Q, stream);
-    }
-    if (ctx->scan_wg >= 2 && Q >= ctx->wg_min_quartets && !ctx->count_invariant &&
-        (uint64_t)ctx->T * (uint64_t)d.pitch < 0xFFFF0000ull) {
-        int m = ctx->scan_method < 0 ? (subsample ? 1 : 0) : ctx->scan_method;
-        if (m == 6) m = subsample ? 1 : 0;
-        note_scan(ctx, SCAN_FORM_WG, d);
-#define TQ_WG_CASE(NW)                                                                                   \
-    if (ctx->scan_wg == NW) {                                                                            \
-        if (m == 2) return launch_scan_wg<true, 2, NW>(ctx, d, dq, order, Q, stream);                       \
-        if (m == 3) return launch_scan_wg<true, 3, NW>(ctx, d, dq, order, Q, stream);                       \
-        if (NW == 4 && m == 4) return launch_scan_wg<true, 4, 4>(ctx, d, dq, order, Q, stream);             \
-        if (NW == 4 && m == 5) return launch_scan_wg<true, 5, 4>(ctx, d, dq, order, Q, stream);             \
-        if (subsample)                                                                                   \
-            return m ? launch_scan_wg<true, 1, NW>(ctx, d, dq, order, Q, stream)                            \
-                     : launch_scan_wg<true, 0, NW>(ctx, d, dq, order, Q, stream);                           \
-        return m ? launch_scan_wg<false, 1, NW>(ctx, d, dq, order, Q, stream)                               \
-                 : launch_scan_wg<false, 0, NW>(ctx, d, dq, order, Q, stream);                              \
-    }
-        TQ_WG_CASE(2)
-        if (ctx->scan_wg == 4 && ctx->park_t && m == 1 && !ctx->share_c)
-            return subsample ? launch_scan_wg<true, 1, 4, false, true>(ctx, d, dq, order, Q, stream)
-                             : launch_scan_wg<false, 1, 4, false, true>(ctx, d, dq, order, Q, stream);
-        if ((ctx->scan_wg == 8 || ctx->scan_wg == 6) && ctx->park_t && m == 1 && subsample && !ctx->share_c)
-            return ctx->scan_wg == 8 ? launch_scan_wg<true, 1, 8, false, true>(ctx, d, dq, order, Q, stream)
-                                     : launch_scan_wg<true, 1, 6, false, true>(ctx, d, dq, order, Q, stream);
-        if (ctx->scan_wg == 4 && ctx->share_c && m <= 1) {
-            if (subsample)
-                return m ? launch_scan_wg<true, 1, 4, true>(ctx, d, dq, order, Q, stream)
-                         : launch_scan_wg<true, 0, 4, true>(ctx, d, dq, order, Q, stream);
-            return m ? launch_scan_wg<false, 1, 4, true>(ctx, d, dq, order, Q, stream)
-                     : launch_scan_wg<false, 0, 4, true>(ctx, d, dq, order, Q, stream);
-        }
-        TQ_WG_CASE(4)
-        TQ_WG_CASE(3)
-        TQ_WG_CASE(6)
-        TQ_WG_CASE(16)
-        TQ_WG_CASE(8)
-#undef TQ_WG_CASE
-    }
-#define TQ_SCAN_CASE(N)                                                                              \
-    case N:                                                                                          \
-        if (method == 0)                                                                             \
-            return subsample ? launch_scan<N, true, 0>(ctx, d, dq, order, Q, stream)                    \
-                             : launch_scan<N, false, 0>(ctx, d, dq, order, Q, stream);                  \
-        return subsample ? launch_scan<N, true, 1>(ctx, d, dq, order, Q, stream)                        \
-                         : launch_scan<N, false, 1>(ctx, d, dq, order, Q, stream)
-    const int method = (ctx->scan_method < 0 || ctx->scan_method == 6) ? (subsample ? 1 : 0) : ctx->scan_method;
-    note_scan(ctx, SCAN_FORM_ONE_WAVE, d);
-    switch (ctx->nrep) {
-        TQ_SCAN_CASE(2);
-        TQ_SCAN_CASE(4);
-        TQ_SCAN_CASE(8);
-        TQ_SCAN_CASE(16);
-        TQ_SCAN_CASE(32);
-    default:
-        TQ_SCAN_CASE(1);
-    }
-#undef TQ_SCAN_CASE
 }
 
 // Jacobi path: count slab rows [cm, cm + n) -> outputs of the same rows
@@ -913,18 +844,15 @@ int stage_scan(tq_ctx *ctx, const uint32_t *dq, int64_t n, int subsample, bool i
     ctx->scanned_Q = 0;
     if ((rc = mark(ctx, TAG_ORIGIN, stream))) return rc;
     if (ctx->phases & 1) {
-        if (use_dp(ctx, n, subsample, input_sorted)) {
-            rc = make_units(ctx, dq, n, input_sorted, stream);
-            if (rc) return rc;
-            if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
-            rc = launch_scan_dp(ctx, dq, n, stream);
-        } else {
-            const uint32_t *order = nullptr;
-            rc = make_order(ctx, dq, n, input_sorted, stream, &order);
-            if (rc) return rc;
-            if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
-            rc = launch_scan_n(ctx, dq, order, n, subsample, stream);
-        }
+        const DevData d = scan_data(ctx, subsample);
+        const ScanPlan plan = choose_scan(scan_knobs(ctx), {ctx->T, d.pitch, ctx->nat.Sp, n, subsample, input_sorted});
+        const uint32_t *order = nullptr;
+        rc = plan.form == SCAN_FORM_DP ? make_units(ctx, dq, n, input_sorted, stream)
+                                       : make_order(ctx, dq, n, input_sorted, stream, &order);
+        if (rc) return rc;
+        if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
+        note_scan(ctx, plan.form, d);
+        rc = plan.form == SCAN_FORM_DP ? launch_scan_dp(ctx, dq, n, stream) : launch_scan(ctx, plan, d, dq, order, n, stream);
         if (rc) return rc;
         if ((rc = mark(ctx, TAG_SCAN, stream))) return rc;
     }
@@ -2726,6 +2654,24 @@ int tq_pattern_class_table(uint8_t *out)
 {
     if (!out) return TQ_ERR_INVALID_ARG;
     for (int p = 0; p < 256; ++p) out[p] = (uint8_t)pattern_class(p >> 6, (p >> 4) & 3, (p >> 2) & 3, p & 3);
+    return TQ_OK;
+}
+
+int tq_scan_plan(const int64_t *rows, int64_t n, int64_t *plans, int64_t *n_kernels)
+{
+    if (n < 0 || (n && (!rows || !plans))) return TQ_ERR_INVALID_ARG;
+    if (n_kernels) *n_kernels = (int64_t)SCAN_TABLE.size();
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t *r = rows + i * 22;
+        const ScanKnobs k = {(int)r[0], (int)r[1], (int)r[2], (int)r[3], (int)r[4], (int)r[5], (int)r[6], (int)r[7], (int)r[8],
+                             (int)r[9], (int)r[10], r[11], r[12], (int)r[13], (int)r[14], (int)r[15]};
+        const ScanShape s = {r[16], r[17], r[18], r[19], (int)r[20], (int)r[21]};
+        const ScanPlan p = choose_scan(k, s);
+        const ScanKernel *kern = find_scan_kernel(p);
+        const int64_t out[12] = {p.form, p.sub, p.method, p.nw, p.shc, p.park, p.nrep, p.qpw, p.threads, p.grid, p.xcd_chunk,
+                                 kern ? (int64_t)(kern - SCAN_TABLE.data()) : -1};
+        memcpy(plans + i * 12, out, sizeof out);
+    }
     return TQ_OK;
 }
 

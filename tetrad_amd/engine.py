@@ -54,6 +54,19 @@ def pinned_empty(shape, dtype) -> np.ndarray:
     return raw[:n].view(dtype).reshape(shape)
 
 
+def scan_plan(rows) -> tuple[np.ndarray, int]:
+    """Test hook (tq_scan_plan; host code, no GPU needed): for rows i64[n, 22] of scan options and batch shape, the kernel
+    the library would launch as i64[n, 12], and the number of scan instantiations it is built with.  Columns:
+    include/tetrad_hip.h."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 22)
+    plans = np.zeros((len(rows), 12), np.int64)
+    n_kernels = ctypes.c_int64()
+    rc = _lib.load().tq_scan_plan(_ptr(rows), len(rows), _ptr(plans), ctypes.byref(n_kernels))
+    if rc != 0:
+        raise TetradHipError(rc, "tq_scan_plan failed")
+    return plans, n_kernels.value
+
+
 PACK_PAD = 0xFFFFFFFF
 
 
