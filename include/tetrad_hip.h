@@ -425,6 +425,33 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
  *                    (TQ_ERR_INVALID_ARG) when the sum of k does not fit in 64 bits (tq_stree_graph then reports
  *                    2^64 - 1); the 2^53 limit of tq_stree_build does not apply.  R = 0 and no kept rows (all zeros) are
  *                    valid.
+ *   tq_stree_nni_scan  the quartet-fit weights of every nearest-neighbour interchange of one tree, in one pass over the
+ *                    kept rows.  The tree is a parent array as tq_stree_fit takes one (validated
+ *                    first, the same messages, as "tree 0"; a bad tree writes nothing) and is held as prepared: root of
+ *                    degree >= 3, no unary nodes, children ordered by their smallest taxon, internal nodes in BFS order.
+ *                    Edge e is the edge above the e-th internal non-root node v; *n_edges <= ntaxa - 3 of them.  With u =
+ *                    parent(v) the edge is eligible when v has two children and u three neighbours (eligible u8[E]).  Its
+ *                    corners u64[E][4][W], W = ceil(ntaxa / 64), bit x of word x / 64: X1, X2 = the taxa below the
+ *                    children of v, Y1, Y2 = the two other subtrees at u, within a side the corner with the smaller
+ *                    smallest taxon first; zeros when not eligible.  w u64[E][3]: the sum of k over the kept rows with
+ *                    one taxon in each corner that display X1 X2 | Y1 Y2 (the tree's split), X1 Y1 | X2 Y2 (alternative
+ *                    1) and X1 Y2 | X2 Y1 (alternative 2); zeros when not eligible.  The neighbour tree of alternative j
+ *                    has k_satisfied - w[e][0] + w[e][j], k_violated + w[e][0] - w[e][j] and the same k_unresolved.  Any
+ *                    output may be NULL.  Host rows (or none, or no context) run on the host; device rows run
+ *                    tq_nni_table_kernel and tq_nni_kernel on `stream` behind the adds, with one synchronisation, and
+ *                    give the same numbers bit for bit.  The first scan on device rows ALLOCATES (2 ntaxa^2 + 44 ntaxa
+ *                    bytes on the device, 40 ntaxa page-locked), freed with the accumulator.  Refused when the sum of k
+ *                    does not fit in 64 bits.  No kept rows (all zeros) is valid.  The rows stay.
+ *   tq_stree_polish  local search from that tree: one round = one scan, then for every eligible edge the alternative with
+ *                    the larger weight (a tie: alternative 1), a candidate when that weight exceeds w[e][0]; candidates by
+ *                    gain descending, then edge ascending; an edge is accepted when neither of its two nodes belongs to an
+ *                    edge accepted before it in the round; all accepted interchanges are applied (the root stays) and
+ *                    k_satisfied rises by exactly the sum of their gains.  Stops when a scan finds no candidate
+ *                    (*converged = 1) or after max_rounds rounds (0..65536; 0 only rewrites the tree).  out / cap /
+ *                    *written as tq_stree_build: newick with numeric tips from the prepared rooting, children by smallest
+ *                    taxon.  trace u64[max_rounds][2] = {interchanges applied, sum of gains} per round that moved, *rounds
+ *                    = those rounds; trace, rounds and converged may be NULL.  The selection runs on the host for both
+ *                    back ends: the same string and trace from both.  One synchronisation of `stream` per round.
  * Option "fit_scratch_bytes" (tq_set_option, default 64 MiB, read at an accumulator's first fit): bound of the table
  * region.  Trees per chunk = max(1, bytes / (2 ntaxa^2)); chunks run one after the other on the call's stream.  Results
  * never depend on it.
@@ -448,6 +475,10 @@ int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out);
 int tq_stree_set_search(tq_stree *acc, int search);
 int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream,
                  uint64_t *out);
+int tq_stree_nni_scan(tq_stree *acc, const int32_t *parent, int64_t n_nodes, void *stream, int64_t *n_edges,
+                      uint8_t *eligible, uint64_t *corners, uint64_t *w);
+int tq_stree_polish(tq_stree *acc, const int32_t *parent, int64_t n_nodes, int64_t max_rounds, void *stream, char *out,
+                    int64_t cap, int64_t *written, uint64_t *trace, int64_t *rounds, int *converged);
 
 /* Test hook: the exact cut search alone on a batch of nodes.  sizes i32[n_nodes] (4..65535 on the host, 4..1024 on the
  * device), G and B the nodes' upper triangles one after the other (node of n taxa: n (n - 1) / 2 cells, cell (u < v) at

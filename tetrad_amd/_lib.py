@@ -37,6 +37,7 @@ SYMBOLS = [
     "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
     "tq_stree_create", "tq_stree_destroy", "tq_stree_reset", "tq_stree_add", "tq_stree_add_dev", "tq_stree_graph",
     "tq_stree_rows", "tq_stree_build", "tq_stree_level_stats", "tq_stree_set_search", "tq_stree_search", "tq_stree_fit",
+    "tq_stree_nni_scan", "tq_stree_polish",
     "tq_cons_create", "tq_cons_destroy", "tq_cons_reset", "tq_cons_add", "tq_cons_shape", "tq_cons_read", "tq_cons_tree",
     "tq_cons_support", "tq_cons_stats",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
@@ -225,6 +226,10 @@ def load() -> ctypes.CDLL:
     lib.tq_stree_search.restype = i32
     lib.tq_stree_fit.argtypes = [vp, vp, vp, i64, i64, vp, vp]
     lib.tq_stree_fit.restype = i32
+    lib.tq_stree_nni_scan.argtypes = [vp, vp, i64, vp, c.POINTER(i64), vp, vp, vp]
+    lib.tq_stree_nni_scan.restype = i32
+    lib.tq_stree_polish.argtypes = [vp, vp, i64, i64, vp, vp, i64, c.POINTER(i64), vp, c.POINTER(i64), c.POINTER(i32)]
+    lib.tq_stree_polish.restype = i32
     lib.tq_cons_create.argtypes = [c.POINTER(vp), i64, i64, vp]
     lib.tq_cons_create.restype = i32
     lib.tq_cons_destroy.argtypes = [vp]

@@ -36,6 +36,7 @@
 //   scf.hpp         tq_scf_kernel (tables, geometry and fold of concordance.hpp): site concordance sums of class rows
 //   supertree.hpp tq_stree_*_kernel: rows -> weighted splits, graph and partition passes of the exact quartet supertree
 //   fit.hpp       tq_fit_*_kernel: LCA-depth tables of candidate trees, quartet fit of the supertree's kept rows against them
+//   nni.hpp       tq_nni_*_kernel: the quartet-fit weights of every nearest-neighbour interchange of a tree in one row pass; the polish search
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
@@ -93,6 +94,7 @@ namespace {
 #include "supertree.hpp"
 #include "consensus.hpp"
 #include "fit.hpp"
+#include "nni.hpp"
 #include "patterns.hpp"
 #include "pattern_blocks.hpp"
 #include "species_blocks.hpp"
@@ -2025,6 +2027,12 @@ struct tq_stree {
     DevBuf<unsigned long long> d_fit_out;           // [trees][6], then the accumulator's counters
     PinnedBuf<unsigned long long> p_fit_out;
     int64_t fit_trees = 0;          // trees the record and result buffers hold
+    // NNI scan (nni.hpp): allocated at the first scan on device rows (sizes depend on ntaxa alone), freed with the accumulator
+    DevBuf<uint16_t> d_nni_tab;     // [T][T] LCA nodes, then [2 T] node depths
+    DevBuf<uint64_t> d_nni_rec;     // [T] words = the 2 T i32 of the parent record, then [T] edge records
+    PinnedBuf<uint64_t> p_nni_rec;
+    DevBuf<unsigned long long> d_nni_w;             // [T][3] sums, then the accumulator's counters
+    PinnedBuf<unsigned long long> p_nni_w;
     tq_stree() = default;
     tq_stree(const tq_stree &) = delete;
     ~tq_stree()                     // runs before the buffers' destructors: device selected, device adds finished
@@ -2188,6 +2196,59 @@ int stree_counts(tq_stree *acc, hipStream_t st, int64_t &kept, int64_t &skipped,
         skipped = acc->h_skipped;
         sum = acc->h_sum;
     }
+    return TQ_OK;
+}
+
+// One scan of the canonical tree `t` against the kept rows (nni.hpp): w[E][3].  Host rows, or none: the host execution.
+// Device rows: the parent record and the edge records go up, tq_nni_table_kernel and tq_nni_kernel run on `st` behind
+// the adds, the sums and the counters come back; one synchronisation.  `who` names the caller in messages.
+int nni_scan_once(tq_stree *acc, const NniTree &t, hipStream_t st, const char *who, std::vector<uint64_t> &w)
+{
+    tq_ctx *ctx = acc->ctx;
+    const int64_t T = acc->ntaxa, E = t.E;
+    if (acc->mode != 2) {
+        if (acc->h_sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: the sum of k does not fit in 64 bits", who);
+        nni_host_rows(t, acc->h_t.data(), acc->h_k.data(), (int64_t)acc->h_t.size(), w);
+        return TQ_OK;
+    }
+    if (int rc = stree_join(acc, st)) return rc;                    // behind the adds made on other streams
+    const size_t wn = (size_t)T * 3;
+    if (!acc->d_nni_tab.get()) {                                    // no scan is in flight: each one ends with a synchronisation
+        TQ_HIP(ctx, acc->d_nni_rec.grow((size_t)2 * T));
+        TQ_HIP(ctx, acc->p_nni_rec.grow((size_t)2 * T));
+        TQ_HIP(ctx, acc->d_nni_w.grow(wn + SC_WORDS));
+        TQ_HIP(ctx, acc->p_nni_w.grow(wn + SC_WORDS));
+        TQ_HIP(ctx, acc->d_nni_tab.grow((size_t)T * T + 2 * T));
+    }
+    memset(acc->p_nni_rec, 0, (size_t)2 * T * 8);
+    int32_t *prec = (int32_t *)acc->p_nni_rec.get();
+    memcpy(prec, t.par.data(), (size_t)t.N * 4);
+    prec[2 * T - 1] = t.N;
+    if (E) memcpy(acc->p_nni_rec + T, t.rec.data(), (size_t)E * 8);
+    TQ_HIP(ctx, hipMemcpyAsync(acc->d_nni_rec, acc->p_nni_rec, (size_t)2 * T * 8, hipMemcpyHostToDevice, st));
+    TQ_HIP(ctx, hipMemsetAsync(acc->d_nni_w, 0, wn * 8, st));
+    if (E > 0 && acc->rows_in > 0) {
+        const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
+        const unsigned table_blocks = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((span + 4 * NNI_THREADS - 1) / (4 * NNI_THREADS), NNI_TABLE_BLOCKS));
+        const unsigned slices = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((acc->rows_in + NNI_ROWS_PER_BLOCK - 1) / NNI_ROWS_PER_BLOCK, NNI_MAX_SLICES));
+        NniTableArgs ta{(const int32_t *)acc->d_nni_rec.get(), acc->d_nni_tab, (uint32_t)T};
+        hipLaunchKernelGGL(tq_nni_table_kernel, dim3(table_blocks), dim3(NNI_THREADS), 0, st, ta);
+        TQ_HIP(ctx, hipGetLastError());
+        NniArgs na{acc->d_root_t, acc->d_root_k, &acc->d_cnt[SC_KEPT], acc->d_nni_tab, acc->d_nni_rec + T, acc->d_nni_w,
+                   (uint32_t)T, (uint32_t)t.N, (uint32_t)E};
+        if (T <= NNI_T_LDS) hipLaunchKernelGGL(tq_nni_kernel<true>, dim3(slices), dim3(NNI_THREADS), 0, st, na);
+        else hipLaunchKernelGGL(tq_nni_kernel<false>, dim3(slices), dim3(NNI_THREADS), 0, st, na);
+        TQ_HIP(ctx, hipGetLastError());
+    }
+    unsigned long long *cnt = acc->p_nni_w + wn;
+    TQ_HIP(ctx, hipMemcpyAsync(acc->p_nni_w, acc->d_nni_w, wn * 8, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, hipMemcpyAsync(cnt, acc->d_cnt, SC_WORDS * 8, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, hipStreamSynchronize(st));
+    const unsigned __int128 sum = (unsigned __int128)cnt[SC_SUM_LO] + ((unsigned __int128)cnt[SC_SUM_HI] << 32);
+    if (sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: the sum of k does not fit in 64 bits", who);
+    w.assign(acc->p_nni_w.get(), acc->p_nni_w.get() + (size_t)E * 3);
     return TQ_OK;
 }
 
@@ -3989,6 +4050,67 @@ int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, 
         return TQ_OK;
     } catch (const std::bad_alloc &) {
         return fail(ctx, TQ_ERR_OOM, "tq_stree_fit: out of host memory");
+    }
+}
+
+int tq_stree_nni_scan(tq_stree *acc, const int32_t *parent, int64_t n_nodes, void *stream, int64_t *n_edges,
+                      uint8_t *eligible, uint64_t *corners, uint64_t *w)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (!parent || n_nodes < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_nni_scan: NULL pointer or negative size");
+    try {
+        NniTree t;
+        const std::string err = nni_prepare(parent, n_nodes, acc->ntaxa, t);    // validated before anything is written
+        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_nni_scan: tree 0: %s", err.c_str());
+        std::vector<uint64_t> sums;
+        if (int rc = nni_scan_once(acc, t, (hipStream_t)stream, "tq_stree_nni_scan", sums)) return rc;
+        if (n_edges) *n_edges = t.E;
+        if (eligible && t.E) memcpy(eligible, t.elig.data(), (size_t)t.E);
+        if (corners) nni_corner_masks(t, corners);
+        if (w && t.E) memcpy(w, sums.data(), (size_t)t.E * 3 * 8);
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_stree_nni_scan: out of host memory");
+    }
+}
+
+int tq_stree_polish(tq_stree *acc, const int32_t *parent, int64_t n_nodes, int64_t max_rounds, void *stream, char *out,
+                    int64_t cap, int64_t *written, uint64_t *trace, int64_t *rounds, int *converged)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (!parent || n_nodes < 0 || cap < 0 || !written || (cap > 0 && !out))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: NULL pointer or negative size");
+    if (max_rounds < 0 || max_rounds > NNI_MAX_ROUNDS)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: max_rounds must be 0..%lld", (long long)NNI_MAX_ROUNDS);
+    try {
+        NniTree t;
+        const std::string err = nni_prepare(parent, n_nodes, acc->ntaxa, t);    // validated before anything is written
+        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: tree 0: %s", err.c_str());
+        std::vector<uint64_t> sums, tr;
+        int conv = 0;
+        for (int64_t r = 0; r < max_rounds; ++r) {
+            if (int rc = nni_scan_once(acc, t, (hipStream_t)stream, "tq_stree_polish", sums)) return rc;
+            uint64_t gain = 0;
+            const int64_t moves = nni_round(t, sums, gain);
+            if (!moves) {
+                conv = 1;
+                break;
+            }
+            tr.push_back((uint64_t)moves);
+            tr.push_back(gain);
+        }
+        const std::string nwk = nni_newick(t);
+        *written = (int64_t)nwk.size();
+        if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
+        memcpy(out, nwk.data(), nwk.size());
+        if (trace && !tr.empty()) memcpy(trace, tr.data(), tr.size() * 8);
+        if (rounds) *rounds = (int64_t)(tr.size() / 2);
+        if (converged) *converged = conv;
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_stree_polish: out of host memory");
     }
 }
 

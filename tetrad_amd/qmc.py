@@ -97,6 +97,9 @@ FIT_DTYPE = np.dtype([("k_satisfied", np.uint64), ("k_violated", np.uint64), ("k
                       ("n_satisfied", np.uint64), ("n_violated", np.uint64), ("n_unresolved", np.uint64),
                       ("fraction", np.float64)])
 LastFit = collections.namedtuple("LastFit", "results chosen seeds")
+#: what `Supertree.polish` did: interchanges applied and sum of gains (Python ints) per round that moved, and whether the
+#: last scan found no candidate
+PolishTrace = collections.namedtuple("PolishTrace", "moves gains converged")
 
 
 class Supertree:
@@ -126,6 +129,7 @@ class Supertree:
         self.ntaxa, self.capacity, self.engine = int(ntaxa), int(capacity), engine
         self.levels = 0
         self.last_fit = None
+        self.last_polish = None
         self._chosen_stats = None
         self._h = None
         h = ctypes.c_void_p()
@@ -230,31 +234,109 @@ class Supertree:
             cap = written.value
         self._check(rc)
 
-    def tree(self, seed: int = 0, stream: int = 0, restarts: int = 1) -> str:
+    def tree(self, seed: int = 0, stream: int = 0, restarts: int = 1, polish: bool = False) -> str:
         """Newick of the rows added so far (numeric tips); `self.levels` = levels of the recursion.  Device rows: the
         passes run on `stream`.
         `restarts=N` > 1: builds with the seeds seed, seed + 1, ..., seed + N - 1, fits the N trees to the rows in one
         `tq_stree_fit` and returns the tree with the largest k_satisfied (ties: the smaller k_violated, then the lowest
         seed).  `self.last_fit` then holds `LastFit(results, chosen, seeds)`; `levels` and `level_stats()` describe the
-        chosen seed's build."""
+        chosen seed's build.
+        `polish=True`: every build goes through `polish` (its default rounds) before the fit that chooses among the
+        restarts; `self.last_polish` holds the returned tree's `PolishTrace` (None after a call without polish).  Off, the
+        calls are the ones above."""
         restarts = int(restarts)
         if restarts < 1:
             raise ValueError("restarts must be at least 1")
         self._chosen_stats = None
+        self.last_polish = None
+        if polish and self.ntaxa < 4:
+            raise ValueError("polish needs a tree of at least 4 taxa")
         if restarts == 1:
-            return self._build(seed, stream)
+            nwk = self._build(seed, stream)
+            if polish:
+                nwk, self.last_polish = self.polish(nwk, stream=stream)
+            return nwk
         if self.ntaxa < 4:
             raise ValueError("restarts need a tree of at least 4 taxa to score")
         seeds = [int(seed) + i for i in range(restarts)]
         builds = []
         for s in seeds:
-            nwk = self._build(s, stream)
-            builds.append((nwk, self.levels, self.level_stats()))
+            nwk, trace = self._build(s, stream), None
+            if polish:
+                nwk, trace = self.polish(nwk, stream=stream)
+            builds.append((nwk, self.levels, self.level_stats(), trace))
         res = self.fit([b[0] for b in builds], stream=stream)
         chosen = min(range(restarts), key=lambda i: (-int(res["k_satisfied"][i]), int(res["k_violated"][i]), i))
         self.last_fit = LastFit(res, chosen, seeds)
-        nwk, self.levels, self._chosen_stats = builds[chosen]
+        nwk, self.levels, self._chosen_stats, trace = builds[chosen]
+        if polish:
+            self.last_polish = trace
         return nwk
+
+    def _parent_of(self, tree, samples):
+        """One tree as `fit` takes it -> parent array i32."""
+        from .concordance import newick_to_parent
+        if isinstance(tree, str):
+            par, T, _ = newick_to_parent(tree, samples)
+            if T != self.ntaxa:
+                raise ValueError(f"the tree has {T} taxa, the accumulator has {self.ntaxa}")
+            return np.ascontiguousarray(par, dtype=np.int32)
+        return np.ascontiguousarray(tree, dtype=np.int32).reshape(-1)
+
+    def nni_scan(self, tree, samples=None, stream: int = 0) -> np.ndarray:
+        """The quartet-fit weights of every nearest-neighbour interchange of `tree` (a newick string or a parent array,
+        as `fit` takes one) in one pass over the kept rows (`tq_stree_nni_scan`).  One record
+        per internal edge of the prepared tree: `eligible`; `corners` u64[4, W] = the taxon masks X1, X2, Y1, Y2 (bit x
+        of word x // 64; `corner_ints` turns a record's into Python ints); `w0`, `w1`, `w2` = the weight of the kept
+        rows with a taxon in every corner that display the tree's split X1 X2 | Y1 Y2, X1 Y1 | X2 Y2 and X1 Y2 | X2 Y1.
+        The neighbour of alternative j scores k_satisfied - w0 + wj.  Device rows: the kernels run on `stream`."""
+        par = self._parent_of(tree, samples)
+        W = (self.ntaxa + 63) // 64
+        cap = max(self.ntaxa - 3, 1)
+        n = ctypes.c_int64()
+        elig = np.zeros(cap, np.uint8)
+        corners = np.zeros((cap, 4, W), np.uint64)
+        w = np.zeros((cap, 3), np.uint64)
+        self._check(self._lib.tq_stree_nni_scan(self._h, par.ctypes.data, len(par), stream or None, ctypes.byref(n),
+                                                elig.ctypes.data, corners.ctypes.data, w.ctypes.data))
+        E = n.value
+        out = np.zeros(E, np.dtype([("eligible", np.bool_), ("corners", np.uint64, (4, W)), ("w0", np.uint64),
+                                    ("w1", np.uint64), ("w2", np.uint64)]))
+        out["eligible"] = elig[:E] != 0
+        out["corners"] = corners[:E]
+        out["w0"], out["w1"], out["w2"] = w[:E, 0], w[:E, 1], w[:E, 2]
+        return out
+
+    @staticmethod
+    def corner_ints(record) -> list:
+        """The four corner masks of one `nni_scan` record as Python ints (bit x = taxon x)."""
+        return [sum(int(word) << (64 * i) for i, word in enumerate(m)) for m in record["corners"]]
+
+    def polish(self, tree, max_rounds: int = 1000, samples=None, stream: int = 0):
+        """Local search from `tree` on the quartet fit (`tq_stree_polish`): rounds of one
+        `nni_scan` each, after which every interchange that raises k_satisfied and shares no node with a better one is
+        applied, until none does or `max_rounds` rounds have moved.  Returns (newick with numeric tips,
+        `PolishTrace(moves, gains, converged)`).  The rows stay as they are."""
+        par = self._parent_of(tree, samples)
+        max_rounds = int(max_rounds)
+        if not 0 <= max_rounds <= 65536:
+            raise ValueError("max_rounds must be 0..65536")
+        cap = 16 * self.ntaxa + 64
+        written, rounds, conv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        trace = np.zeros((max(max_rounds, 1), 2), np.uint64)
+        for _ in range(2):
+            buf = np.empty(cap, dtype=np.uint8)
+            rc = self._lib.tq_stree_polish(self._h, par.ctypes.data, len(par), max_rounds, stream or None, buf.ctypes.data,
+                                           cap, ctypes.byref(written), trace.ctypes.data, ctypes.byref(rounds),
+                                           ctypes.byref(conv))
+            if rc == 0:
+                r = rounds.value
+                return (buf[:written.value].tobytes().decode("ascii"),
+                        PolishTrace([int(x) for x in trace[:r, 0]], [int(x) for x in trace[:r, 1]], bool(conv.value)))
+            if rc != -6 or written.value <= cap:
+                self._check(rc)
+            cap = written.value
+        self._check(rc)
 
     def fit(self, trees, samples=None, stream: int = 0) -> np.ndarray:
         """Quartet fit of `trees` against the kept rows (`tq_stree_fit`).  `trees`: a newick string,
@@ -309,13 +391,13 @@ class Supertree:
 
 
 def infer_supertree_exact(rqrts, rscor, rstat, ntaxa: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0,
-                          seed: int = 0, flags=None, search: str = "f64", restarts: int = 1) -> str:
+                          seed: int = 0, flags=None, search: str = "f64", restarts: int = 1, polish: bool = False) -> str:
     """`infer_supertree_from_arrays` on the exact path (host back end): the tree does not depend on the row order.
-    `search`: the rule of the cut search, as `Supertree`; `restarts`: as `Supertree.tree`."""
+    `search`: the rule of the cut search, as `Supertree`; `restarts`, `polish`: as `Supertree.tree`."""
     n = np.asarray(rqrts).reshape(-1, 4).shape[0]
     with Supertree(ntaxa, n, weights, min_snps, min_ratio, search=search) as st:
         st.add(rqrts, rscor, rstat, flags)
-        return st.tree(seed, restarts=restarts)
+        return st.tree(seed, restarts=restarts, polish=polish)
 
 
 def relabel_tree(newick: str, samples) -> str:

@@ -231,7 +231,7 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
                     subsample_snps: bool = True, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, seed=None,
                     rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
                     concordance=None, supertree: str = "host", consensus=None, search: str = "f64", restarts: int = 1,
-                    fit_out=None) -> list:
+                    fit_out=None, polish: bool = False) -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
@@ -246,17 +246,20 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
     `restarts=N` (with `supertree="device"` only: the host path keeps no rows to score against) builds every
     replicate's tree from N seeds and keeps the one that satisfies the most quartet weight (`Supertree.tree`, DESIGN.md
     section 17); with `fit_out` a list, the chosen tree's fit record is appended per replicate, in replicate order.
+    `polish=True` (with `supertree="device"` only, for the same reason) sends every build through `Supertree.polish`
+     before that choice; `fit_out` then receives the polished tree's record.
     `consensus` (a `consensus.Consensus`) receives the replicate trees in replicate order once they are all in
     (`consensus.tree()` is then the majority-rule tree with bootstrap supports)."""
     trees = _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
-                             rng, sampler, group, workers, concordance, supertree, search, restarts, fit_out)
+                             rng, sampler, group, workers, concordance, supertree, search, restarts, fit_out, polish)
     if consensus is not None and trees:
         consensus.add_newick(trees)
     return trees
 
 
 def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed, rng,
-                     sampler, group, workers, concordance, supertree, search="f64", restarts=1, fit_out=None) -> list:
+                     sampler, group, workers, concordance, supertree, search="f64", restarts=1, fit_out=None,
+                     polish=False) -> list:
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
     if supertree not in ("host", "device"):
@@ -270,6 +273,8 @@ def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, w
         raise ValueError("restarts must be at least 1")
     if restarts != 1 and supertree == "host":
         raise ValueError("restarts != 1 needs supertree='device': supertree='host' keeps no rows to score a tree against")
+    if polish and supertree == "host":
+        raise ValueError("polish=True needs supertree='device': supertree='host' keeps no rows to score a tree against")
     if fit_out is not None and not isinstance(fit_out, list):
         raise ValueError("fit_out must be a list or None")
     if fit_out is not None and supertree == "host":
@@ -277,7 +282,7 @@ def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, w
     if supertree == "device":
         return _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps,
                                        min_ratio, seed, rng, sampler, group, workers, concordance, search, restarts,
-                                       fit_out)
+                                       fit_out, polish)
     runner = ReplicateRunner(engine, seqarr, spans, nquartets, seed=seed, rng=rng, sampler=sampler, group=group,
                              quartets_to_host=True, concordance=concordance)
     ntaxa = int(seqarr.shape[0])
@@ -294,7 +299,8 @@ def _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, w
 
 
 def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
-                            rng, sampler, group, workers, concordance, search="f64", restarts=1, fit_out=None) -> list:
+                            rng, sampler, group, workers, concordance, search="f64", restarts=1, fit_out=None,
+                            polish=False) -> list:
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import qmc
@@ -321,7 +327,7 @@ def _bootstrap_trees_device(engine, seqarr, spans, nquartets, nboots, subsample_
                     torch.cuda.set_device(runner.dev)
                     local.stream = torch.cuda.Stream(runner.dev)
                 acc, cs = ring[slot], local.stream.cuda_stream
-                nwk = acc.tree(seed=k, stream=cs, restarts=restarts)
+                nwk = acc.tree(seed=k, stream=cs, restarts=restarts, polish=polish)
                 if fit_out is not None:
                     fits[k] = acc.last_fit.results[acc.last_fit.chosen] if restarts > 1 else acc.fit(nwk, stream=cs)
                 acc.reset()
