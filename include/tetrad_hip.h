@@ -534,6 +534,48 @@ int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_
                     int64_t *n_edges);
 int tq_cons_stats(tq_cons *acc, int64_t *out);
 
+/* Transfer bootstrap supports (TBE; Lemoine et al. 2018): for every branch of one reference tree
+ * and every replicate tree, the number of taxa that must be moved to turn the branch's bipartition into the closest
+ * bipartition of the replicate, summed over the replicates.  Integers only; the host and the device execution return
+ * identical arrays.  No reference counterpart.
+ *   Trees are parent arrays as tq_cons_add takes them (a root of degree 2 is dissolved, unary nodes are suppressed,
+ *   multifurcations allowed), 4 <= T <= 4096.
+ *   Branches: the splits of the reference tree (an internal edge with at least 2 taxa on both sides), mask = the side
+ *   without taxon 0 in W = ceil(T / 64) u64 words, ordered by the mask ascending as one integer (the order of
+ *   tq_cons_support), E <= T - 3 of them; p[b] = min(|mask|, T - |mask|) >= 2, the light side.
+ *   Distance of two bipartitions with masks x, y: d = popcount(x xor y) over the W words, delta = min(d, T - d); the
+ *   same whichever side either mask names.
+ *   Transfer index phi(b, t) = the minimum of delta over every edge of replicate t, the edges above tips included: a tip
+ *   of the light side gives p - 1, so phi = min(p[b] - 1, min over the internal splits of t of delta).  A star gives
+ *   p - 1 for every branch, a replicate that contains the branch gives 0.  No argmin is reported.
+ *   Accumulated: ntrees and phi_sum[b] = the sum of phi(b, t), u64; any chunking and order of adds gives the same sums.
+ *   Support: TBE(b) = 1 - phi_sum[b] / (ntrees (p[b] - 1)), taken by the caller; the integer percent, rounded half up,
+ *   is (200 (N q - s) + N q) / (2 N q) with q = p - 1, N = ntrees, s = phi_sum.
+ *   tq_tbe_create   the reference tree ref_parent i32[n_nodes]; a bad tree is TQ_ERR_INVALID_ARG, a star is valid with
+ *                   E = 0.  `ctx` NULL: host back end.  With a context all device and page-locked memory is allocated
+ *                   here: the branch masks, p and phi_sum, and one chunk of trees (records, masks, phi rows) within the
+ *                   option "cons_scratch_bytes", read here as tq_cons_create reads it.  The context must outlive the
+ *                   accumulator; messages go to tq_last_error(ctx).
+ *   tq_tbe_reset    keeps the reference tree, zeroes ntrees and phi_sum (waits for device work).
+ *   tq_tbe_add      parents i32[R][stride], n_nodes i64[R] (each <= stride).  Every tree is validated first: one bad
+ *                   tree is TQ_ERR_INVALID_ARG naming its index, and nothing is added.  R = 0 is a no-op.  Device back
+ *                   end: the kernels run on `stream` (hipStream_t, NULL = default stream) chunk by chunk.  phi_out
+ *                   NULL: the call returns with the last chunk in flight.  phi_out u16[R][E]: the call waits for its
+ *                   chunks and writes phi(b, t) of every replicate of the call.  Adds on different streams are ordered
+ *                   in call order.
+ *   tq_tbe_shape    T, W, E, trees added (any may be NULL).
+ *   tq_tbe_read     masks u64[E][W], p i64[E], phi_sum u64[E] (any may be NULL); waits for device work.
+ *   tq_tbe_stats    out i64[2] = {trees per chunk (0 on the host), chunks launched since create / reset}.           */
+typedef struct tq_tbe tq_tbe;
+int tq_tbe_create(tq_tbe **out, int64_t T, const int32_t *ref_parent, int64_t n_nodes, tq_ctx *ctx);
+void tq_tbe_destroy(tq_tbe *acc);
+int tq_tbe_reset(tq_tbe *acc);
+int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream,
+               uint16_t *phi_out);
+int tq_tbe_shape(tq_tbe *acc, int64_t *T, int64_t *W, int64_t *E, int64_t *ntrees);
+int tq_tbe_read(tq_tbe *acc, uint64_t *masks, int64_t *p, uint64_t *phi_sum);
+int tq_tbe_stats(tq_tbe *acc, int64_t *out);
+
 /* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
  * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
  * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.

@@ -6,13 +6,15 @@ mirrors of the reference's interfaces -- ``resolve_quartets`` (worker), ``distri
 over the GPUs of a node), ``replicates`` (bootstrap-replicate loop), ``bootstrap`` (resampler draws),
 ``combinations`` (quartet producers), ``qmc_format`` / ``qmc`` (wQMC text and the quartet supertree), ``concordance``
 (quartet concordance on a fixed tree), ``consensus`` (split counts over many trees, majority-rule consensus),
-``scf`` (site concordance factors per branch of a fixed tree).
+``scf`` (site concordance factors per branch of a fixed tree), ``tbe`` (transfer bootstrap supports of a tree's
+branches over replicate trees).
 Importing the package does not load the HIP library; the first compute call does, and fails loudly if it is missing.
 """
 __version__ = "0.2.0"
 
 _SCF_EXPORTS = ("SiteConcordance", "sample_edge_quartets", "run_scf")
-__all__ = list(_SCF_EXPORTS)
+_TBE_EXPORTS = ("TransferSupport", "transfer_supports")
+__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS)
 
 
 def __getattr__(name):
@@ -20,4 +22,7 @@ def __getattr__(name):
     if name in _SCF_EXPORTS:
         from . import scf
         return getattr(scf, name)
+    if name in _TBE_EXPORTS:
+        from . import tbe
+        return getattr(tbe, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -40,6 +40,7 @@ SYMBOLS = [
     "tq_stree_nni_scan", "tq_stree_polish",
     "tq_cons_create", "tq_cons_destroy", "tq_cons_reset", "tq_cons_add", "tq_cons_shape", "tq_cons_read", "tq_cons_tree",
     "tq_cons_support", "tq_cons_stats",
+    "tq_tbe_create", "tq_tbe_destroy", "tq_tbe_reset", "tq_tbe_add", "tq_tbe_shape", "tq_tbe_read", "tq_tbe_stats",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
     "tq_pack_sites",
     "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
@@ -248,6 +249,20 @@ def load() -> ctypes.CDLL:
     lib.tq_cons_support.restype = i32
     lib.tq_cons_stats.argtypes = [vp, vp]
     lib.tq_cons_stats.restype = i32
+    lib.tq_tbe_create.argtypes = [c.POINTER(vp), i64, vp, i64, vp]
+    lib.tq_tbe_create.restype = i32
+    lib.tq_tbe_destroy.argtypes = [vp]
+    lib.tq_tbe_destroy.restype = None
+    lib.tq_tbe_reset.argtypes = [vp]
+    lib.tq_tbe_reset.restype = i32
+    lib.tq_tbe_add.argtypes = [vp, vp, vp, i64, i64, vp, vp]
+    lib.tq_tbe_add.restype = i32
+    lib.tq_tbe_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.tq_tbe_shape.restype = i32
+    lib.tq_tbe_read.argtypes = [vp, vp, vp, vp]
+    lib.tq_tbe_read.restype = i32
+    lib.tq_tbe_stats.argtypes = [vp, vp]
+    lib.tq_tbe_stats.restype = i32
     lib.tq_set_species.argtypes = [vp, vp, i64, i64]
     lib.tq_set_species.restype = i32
     lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]

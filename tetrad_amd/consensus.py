@@ -200,56 +200,63 @@ class Consensus:
         """The given tree (its own shape, rooting, child order and tip labels) with the percent support of each of its
         splits as the label of the first node in preorder whose clade is one side of the edge (where
         `Concordance.to_newick` puts its comments).  Branch lengths and labels of internal nodes are dropped."""
-        _, T, names = newick_to_parent(newick, samples)            # validates; the writer below walks the text's own order
-        counts, masks = self.support_of(newick, samples)
+        counts, masks = self.support_of(newick, samples)           # validates; the writer walks the text's own order
         ntrees = self.ntrees
-        par, label, nkids = parse_newick(newick)                   # node 0 = the root, children in order of appearance
-        n = len(par)
-        taxon_of = {str(name): t for t, name in enumerate(names)}
-        kids = [[] for _ in range(n)]
-        for v in range(1, n):
-            kids[par[v]].append(v)
-        root = 0
-        clade = [0] * n
-        for v in range(n - 1, -1, -1):                             # a child always follows its parent
-            if not nkids[v]:
-                clade[v] = 1 << taxon_of[label[v]]
-            if v:
-                clade[par[v]] |= clade[v]
-        full = (1 << T) - 1
-        where = {}
-        for e in range(len(counts)):
-            m = sum(1 << int(t) for t in np.flatnonzero(masks[e]))
-            where[m] = where[full ^ m] = e
-        placed, used = {}, set()
-        for v in range(n):                                         # order of appearance = preorder
-            e = where.get(clade[v])
-            if nkids[v] and e is not None and e not in used:
-                placed[v] = e
-                used.add(e)
+        return write_split_labels(newick, samples, masks, [str(percent(c, ntrees)) for c in counts])
 
-        def name(v):
-            s = str(label[v])
-            return "'" + s.replace("'", "''") + "'" if any(ch in s for ch in " (),:;[]'") else s
 
-        out, stack = [], [(root, 0)]
-        while stack:
-            v, i = stack.pop()
-            if not nkids[v]:
-                out.append(name(v))
-                continue
-            if i == 0:
-                out.append("(")
-            if i == len(kids[v]):
-                out.append(")")
-                if v in placed:
-                    out.append(str(percent(counts[placed[v]], ntrees)))
-                continue
-            if i:
-                out.append(",")
-            stack.append((v, i + 1))
-            stack.append((kids[v][i], 0))
-        return "".join(out) + ";"
+def write_split_labels(newick: str, samples, masks, labels) -> str:
+    """`newick` (its own shape, rooting, child order and tip labels) with `labels[e]` written behind the first node in
+    preorder whose clade is one side of split `e` (`masks` bool[E, ntaxa]).  Branch lengths and labels of internal nodes
+    are dropped.  The writer of `Consensus.map_supports` and `tbe.TransferSupport.map_supports`."""
+    _, T, names = newick_to_parent(newick, samples)
+    par, label, nkids = parse_newick(newick)                       # node 0 = the root, children in order of appearance
+    n = len(par)
+    taxon_of = {str(name): t for t, name in enumerate(names)}
+    kids = [[] for _ in range(n)]
+    for v in range(1, n):
+        kids[par[v]].append(v)
+    root = 0
+    clade = [0] * n
+    for v in range(n - 1, -1, -1):                                 # a child always follows its parent
+        if not nkids[v]:
+            clade[v] = 1 << taxon_of[label[v]]
+        if v:
+            clade[par[v]] |= clade[v]
+    full = (1 << T) - 1
+    where = {}
+    for e in range(len(labels)):
+        m = sum(1 << int(t) for t in np.flatnonzero(masks[e]))
+        where[m] = where[full ^ m] = e
+    placed, used = {}, set()
+    for v in range(n):                                             # order of appearance = preorder
+        e = where.get(clade[v])
+        if nkids[v] and e is not None and e not in used:
+            placed[v] = e
+            used.add(e)
+
+    def name(v):
+        s = str(label[v])
+        return "'" + s.replace("'", "''") + "'" if any(ch in s for ch in " (),:;[]'") else s
+
+    out, stack = [], [(root, 0)]
+    while stack:
+        v, i = stack.pop()
+        if not nkids[v]:
+            out.append(name(v))
+            continue
+        if i == 0:
+            out.append("(")
+        if i == len(kids[v]):
+            out.append(")")
+            if v in placed:
+                out.append(labels[placed[v]])
+            continue
+        if i:
+            out.append(",")
+        stack.append((v, i + 1))
+        stack.append((kids[v][i], 0))
+    return "".join(out) + ";"
 
 
 def consensus_tree(newicks, min_freq: float = 0.5, samples=None, engine=None) -> str:

@@ -38,6 +38,7 @@
 //   fit.hpp       tq_fit_*_kernel: LCA-depth tables of candidate trees, quartet fit of the supertree's kept rows against them
 //   nni.hpp       tq_nni_*_kernel: the quartet-fit weights of every nearest-neighbour interchange of a tree in one row pass; the polish search
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
+//   tbe.hpp       tq_tbe_kernel: transfer distances of a reference tree's branches to every node of many trees (TBE)
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
@@ -93,6 +94,7 @@ namespace {
 #include "species.hpp"
 #include "supertree.hpp"
 #include "consensus.hpp"
+#include "tbe.hpp"
 #include "fit.hpp"
 #include "nni.hpp"
 #include "patterns.hpp"
@@ -1979,6 +1981,68 @@ int cons_table(tq_cons *a, const char *who)
         cons_sorted_table(all, a->W, a->tmasks, a->tcounts);
     }
     a->table_ok = true;
+    return TQ_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// Transfer bootstrap accumulator (tbe.hpp).  The reference branches are fixed at create; host back end: phi_sum in a
+// host vector; device back end: phi_sum on the device, one chunk of trees staged and scanned at a time.
+// ---------------------------------------------------------------------------------------------
+struct tq_tbe {
+    tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
+    int32_t T = 0, W = 0, G = 1;
+    uint64_t tail = 0;
+    int64_t E = 0, ntrees = 0;
+    std::vector<uint64_t> masks;    // [E][W] ascending
+    std::vector<int32_t> p;         // [E]
+    std::vector<uint64_t> phi_sum;  // host back end
+    // device back end
+    int64_t chunk_trees = 0, chunks = 0;
+    PinnedBuf<int32_t> p_trees;
+    PinnedBuf<uint16_t> p_phi;
+    DevBuf<int32_t> d_trees, d_p;
+    DevBuf<uint64_t> d_masks, d_keys, d_ref;
+    DevBuf<unsigned long long> d_phi_sum;
+    DevBuf<uint16_t> d_phi;
+    StreamOrder order;              // behind the last chunk
+    tq_tbe() = default;
+    tq_tbe(const tq_tbe &) = delete;
+    ~tq_tbe()                       // runs before the buffers' destructors: device selected, last chunk finished
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)order.sync();
+        if (order.ev) (void)hipEventDestroy(order.ev);
+    }
+};
+
+namespace {
+
+// One chunk of prepared records (already in the page-locked buffer): the masks by tq_cons_mask_kernel, then the
+// distances, on `st`.  With `want_phi` the chunk's phi rows follow into the page-locked buffer.
+int tbe_launch(tq_tbe *a, int64_t ntrees, hipStream_t st, bool want_phi)
+{
+    tq_ctx *ctx = a->ctx;
+    ConsArgs c{};
+    c.trees = a->d_trees; c.masks = a->d_masks; c.keys = a->d_keys;
+    c.items = ntrees * (a->T - 2);
+    c.T = a->T; c.W = a->W; c.G = a->G; c.hash_bits = 64; c.tail = a->tail;
+    TbeArgs t{};
+    t.trees = a->d_trees; t.masks = a->d_masks; t.ref = a->d_ref; t.p = a->d_p; t.phi_sum = a->d_phi_sum;
+    t.phi = want_phi ? a->d_phi.get() : nullptr;
+    t.T = a->T; t.W = a->W; t.E = (int32_t)a->E;
+    TQ_HIP(ctx, hipMemcpyAsync(a->d_trees, a->p_trees, (size_t)ntrees * cons_stride(a->T) * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(tq_cons_mask_kernel, dim3((unsigned)ntrees), dim3(CONS_THREADS), 0, st, c);
+    hipLaunchKernelGGL(tq_tbe_kernel, dim3((unsigned)ntrees, (unsigned)((a->E + TBE_BE - 1) / TBE_BE)), dim3(TBE_THREADS), 0,
+                       st, t);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_tbe_add: launch failed: %s", hipGetErrorString(e));
+    if (want_phi)
+        TQ_HIP(ctx, hipMemcpyAsync(a->p_phi, a->d_phi, (size_t)ntrees * a->E * 2, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, a->order.mark(st));
+    ++a->chunks;
     return TQ_OK;
 }
 
@@ -4426,6 +4490,160 @@ int tq_cons_stats(tq_cons *acc, int64_t *out)
     out[3] = (int64_t)acc->host.size();
     out[4] = acc->unresolved;
     out[5] = acc->hash_bits;
+    return TQ_OK;
+}
+
+int tq_tbe_create(tq_tbe **out, int64_t T, const int32_t *ref_parent, int64_t n_nodes, tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: out is NULL");
+    *out = nullptr;
+    if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: T must be 4..%d", CONS_T_MAX);
+    if (!ref_parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: ref_parent is NULL");
+    tq_tbe *a = nullptr;
+    try {
+        std::vector<int32_t> rec((size_t)cons_stride(T));
+        const std::string err = cons_prepare(ref_parent, n_nodes, T, rec.data());
+        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: %s", err.c_str());
+        a = new tq_tbe();
+        a->ctx = ctx;
+        a->T = (int32_t)T;
+        a->W = (int32_t)((T + 63) / 64);
+        a->tail = (T & 63) ? (uint64_t(1) << (T & 63)) - 1 : ~uint64_t(0);
+        while (a->G < a->W) a->G *= 2;
+        tbe_reference(rec.data(), a->T, a->W, a->masks, a->p);
+        a->E = (int64_t)a->p.size();
+        a->phi_sum.assign((size_t)a->E, 0);
+    } catch (const std::bad_alloc &) {
+        delete a;
+        return fail(ctx, TQ_ERR_OOM, "tq_tbe_create: out of host memory");
+    }
+    if (ctx) {
+        const int64_t W = a->W, nodes = T - 2, stride = cons_stride(T), E1 = std::max<int64_t>(1, a->E);
+        const int64_t per_tree = nodes * W * 8 + nodes * 8 + stride * 4 + E1 * 2;       // masks, keys, record, phi row
+        a->chunk_trees = std::max<int64_t>(1, std::min<int64_t>(CONS_CHUNK_MAX, ctx->cons_scratch_bytes / per_tree));
+        const int64_t C = a->chunk_trees;
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = a->d_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->d_masks.alloc((size_t)C * nodes * W);
+        if (e == hipSuccess) e = a->d_keys.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->d_phi.alloc((size_t)C * E1);
+        if (e == hipSuccess) e = a->d_ref.alloc((size_t)E1 * W);
+        if (e == hipSuccess) e = a->d_p.alloc((size_t)E1);
+        if (e == hipSuccess) e = a->d_phi_sum.alloc((size_t)E1);
+        if (e == hipSuccess) e = a->p_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->p_phi.alloc((size_t)C * E1);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
+        if (e == hipSuccess && a->E) e = hipMemcpy(a->d_ref, a->masks.data(), (size_t)a->E * W * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && a->E) e = hipMemcpy(a->d_p, a->p.data(), (size_t)a->E * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(a->d_phi_sum, 0, (size_t)E1 * 8);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            delete a;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_tbe_create: %s", hipGetErrorString(e));
+        }
+    }
+    *out = a;
+    return TQ_OK;
+}
+
+void tq_tbe_destroy(tq_tbe *acc) { delete acc; }
+
+int tq_tbe_reset(tq_tbe *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (acc->ctx) {
+        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+        TQ_HIP(acc->ctx, acc->order.sync());
+        TQ_HIP(acc->ctx, hipMemset(acc->d_phi_sum, 0, (size_t)std::max<int64_t>(1, acc->E) * 8));
+        TQ_HIP(acc->ctx, hipDeviceSynchronize());
+    }
+    std::fill(acc->phi_sum.begin(), acc->phi_sum.end(), uint64_t(0));
+    acc->ntrees = 0;
+    acc->chunks = 0;
+    return TQ_OK;
+}
+
+int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream,
+               uint16_t *phi_out)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_add: NULL pointer or negative size");
+    if (R == 0) return TQ_OK;
+    try {
+        const int64_t S = cons_stride(acc->T), E = acc->E;
+        std::vector<int32_t> recs((size_t)R * S);       // every tree is validated before the first one is added
+        for (int64_t r = 0; r < R; ++r) {
+            if (n_nodes[r] > stride)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_add: tree %lld: n_nodes exceeds the stride", (long long)r);
+            const std::string err = cons_prepare(parents + r * stride, n_nodes[r], acc->T, &recs[(size_t)r * S]);
+            if (!err.empty())
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_add: tree %lld: %s", (long long)r, err.c_str());
+        }
+        acc->ntrees += R;
+        if (E == 0) return TQ_OK;                       // a star reference: nothing to measure
+        if (!ctx) {
+            std::vector<uint64_t> tmp, sides;
+            std::vector<uint32_t> phi((size_t)E);
+            for (int64_t r = 0; r < R; ++r) {
+                tbe_host_tree(&recs[(size_t)r * S], acc->T, acc->W, acc->masks, acc->p, tmp, sides, phi.data());
+                for (int64_t e = 0; e < E; ++e) {
+                    acc->phi_sum[e] += phi[e];
+                    if (phi_out) phi_out[r * E + e] = (uint16_t)phi[e];
+                }
+            }
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, hipSetDevice(ctx->device));
+        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk_trees) {
+            const int64_t n = std::min<int64_t>(acc->chunk_trees, R - r0);
+            TQ_HIP(ctx, acc->order.sync());             // the staging buffer and the mask scratch are free again
+            memcpy(acc->p_trees, &recs[(size_t)r0 * S], (size_t)n * S * 4);
+            if (int rc = tbe_launch(acc, n, (hipStream_t)stream, phi_out != nullptr)) return rc;
+            if (phi_out) {
+                TQ_HIP(ctx, acc->order.sync());
+                memcpy(phi_out + r0 * E, acc->p_phi, (size_t)n * E * 2);
+            }
+        }
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_tbe_add: out of host memory");
+    }
+}
+
+int tq_tbe_shape(tq_tbe *acc, int64_t *T, int64_t *W, int64_t *E, int64_t *ntrees)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->T;
+    if (W) *W = acc->W;
+    if (E) *E = acc->E;
+    if (ntrees) *ntrees = acc->ntrees;
+    return TQ_OK;
+}
+
+int tq_tbe_read(tq_tbe *acc, uint64_t *masks, int64_t *p, uint64_t *phi_sum)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    const int64_t E = acc->E;
+    if (acc->ctx) {
+        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+        TQ_HIP(acc->ctx, acc->order.sync());
+        if (phi_sum && E) TQ_HIP(acc->ctx, hipMemcpy(phi_sum, acc->d_phi_sum, (size_t)E * 8, hipMemcpyDeviceToHost));
+    } else if (phi_sum && E) {
+        memcpy(phi_sum, acc->phi_sum.data(), (size_t)E * 8);
+    }
+    if (masks && E) memcpy(masks, acc->masks.data(), (size_t)E * acc->W * 8);
+    if (p)
+        for (int64_t e = 0; e < E; ++e) p[e] = acc->p[e];
+    return TQ_OK;
+}
+
+int tq_tbe_stats(tq_tbe *acc, int64_t *out)
+{
+    if (!acc || !out) return TQ_ERR_INVALID_ARG;
+    out[0] = acc->chunk_trees;
+    out[1] = acc->chunks;
     return TQ_OK;
 }
 
