@@ -576,6 +576,50 @@ int tq_tbe_shape(tq_tbe *acc, int64_t *T, int64_t *W, int64_t *E, int64_t *ntree
 int tq_tbe_read(tq_tbe *acc, uint64_t *masks, int64_t *p, uint64_t *phi_sum);
 int tq_tbe_stats(tq_tbe *acc, int64_t *out);
 
+/* All-pairs Robinson-Foulds distances of a set of trees: which trees of a bootstrap set, of N
+ * restarts or of two search rules agree, and by how much.  Integers only; the host and the device execution return
+ * identical arrays.  No reference counterpart.
+ *   Trees are parent arrays as tq_cons_add takes them (a root of degree 2 is dissolved, unary nodes are suppressed,
+ *   multifurcations allowed), 4 <= T <= 4096.  A split is an internal edge with at least 2 taxa on both sides, its mask
+ *   the side without taxon 0 in W = ceil(T / 64) u64 words; two splits are the same when all W words are.
+ *   nsplits[i]    the splits of tree i: 0 for a star, at most T - 3.
+ *   shared[i][j]  the splits both trees hold; shared[i][i] = nsplits[i].
+ *   rf[i][j]      nsplits[i] + nsplits[j] - 2 shared[i][j]: the size of the symmetric difference, the unnormalised
+ *                 Robinson-Foulds distance of unrooted trees (right for polytomies too).
+ *   The matrices are symmetric, N x N over the trees in the order they were added.  No result depends on the chunking
+ *   of trees or columns, the order of adds, streams or the option "cons_hash_bits".
+ *   tq_rf_create   max_trees 1..8192, max_splits 1..2^26 distinct splits.  `ctx` NULL: host back end (an exact map gives
+ *                  every tree an ascending id list; shared = a merge of two lists).  With a context all device and
+ *                  page-locked memory is allocated here: a split table of max_splits entries, ids u32[max_trees][T - 2],
+ *                  the two u32 matrices of max_trees^2 each, one chunk of trees and the bit rows of one chunk of columns,
+ *                  each within the option "cons_scratch_bytes"; "cons_hash_bits" is read here and at reset.  A failed
+ *                  allocation is TQ_ERR_OOM / TQ_ERR_HIP with a message and frees everything.  The context must outlive
+ *                  the accumulator; messages go to tq_last_error(ctx).
+ *   tq_rf_reset    forgets the trees and the splits (waits for device work).
+ *   tq_rf_add      parents i32[R][stride], n_nodes i64[R] (each <= stride).  Every tree is validated first: one bad tree
+ *                  is TQ_ERR_INVALID_ARG naming its index, more than max_trees trees in all is TQ_ERR_INVALID_ARG, and
+ *                  nothing is added.  R = 0 is a no-op.  Device back end: the kernels run on `stream` (hipStream_t, NULL
+ *                  = default stream) chunk by chunk and the call returns with the last chunk in flight; adds on different
+ *                  streams are ordered in call order.  More than max_splits distinct splits: TQ_ERR_INVALID_ARG, at the
+ *                  add or at the next call that waits, and the accumulator refuses everything until a reset.
+ *   tq_rf_shape    T, W, trees added, distinct splits seen (waits), columns of the last read (any may be NULL).
+ *   tq_rf_read     nsplits i32[N], shared u32[N][N], rf u32[N][N] (any may be NULL); waits.  May be called any number of
+ *                  times, between adds too.  Device back end: a column is a split of at least two trees; the bit rows
+ *                  B[N][columns] are built a chunk of columns at a time and shared += B B^T by tq_rf_gemm_kernel.
+ *   tq_rf_stats    out i64[8] = {trees per chunk, tree chunks launched since create / reset, columns of the last read,
+ *                  column words per chunk, column chunks of the last read, splits resolved on the host after a hash
+ *                  collision, hash bits in use, entries of the device table}; on the host only the columns count.
+ *   tq_rf_word_shared  the word rule of the product, popcount(x & y): the one definition tq_rf_gemm_kernel compiles.  */
+typedef struct tq_rf tq_rf;
+int tq_rf_create(tq_rf **out, int64_t T, int64_t max_trees, int64_t max_splits, tq_ctx *ctx);
+void tq_rf_destroy(tq_rf *acc);
+int tq_rf_reset(tq_rf *acc);
+int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream);
+int tq_rf_shape(tq_rf *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits, int64_t *columns);
+int tq_rf_read(tq_rf *acc, int32_t *nsplits, uint32_t *shared, uint32_t *rf);
+int tq_rf_stats(tq_rf *acc, int64_t *out);
+uint32_t tq_rf_word_shared(uint64_t x, uint64_t y);
+
 /* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
  * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
  * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.

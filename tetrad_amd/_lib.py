@@ -41,6 +41,8 @@ SYMBOLS = [
     "tq_cons_create", "tq_cons_destroy", "tq_cons_reset", "tq_cons_add", "tq_cons_shape", "tq_cons_read", "tq_cons_tree",
     "tq_cons_support", "tq_cons_stats",
     "tq_tbe_create", "tq_tbe_destroy", "tq_tbe_reset", "tq_tbe_add", "tq_tbe_shape", "tq_tbe_read", "tq_tbe_stats",
+    "tq_rf_create", "tq_rf_destroy", "tq_rf_reset", "tq_rf_add", "tq_rf_shape", "tq_rf_read", "tq_rf_stats",
+    "tq_rf_word_shared",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
     "tq_pack_sites",
     "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
@@ -263,6 +265,22 @@ def load() -> ctypes.CDLL:
     lib.tq_tbe_read.restype = i32
     lib.tq_tbe_stats.argtypes = [vp, vp]
     lib.tq_tbe_stats.restype = i32
+    lib.tq_rf_create.argtypes = [c.POINTER(vp), i64, i64, i64, vp]
+    lib.tq_rf_create.restype = i32
+    lib.tq_rf_destroy.argtypes = [vp]
+    lib.tq_rf_destroy.restype = None
+    lib.tq_rf_reset.argtypes = [vp]
+    lib.tq_rf_reset.restype = i32
+    lib.tq_rf_add.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.tq_rf_add.restype = i32
+    lib.tq_rf_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
+    lib.tq_rf_shape.restype = i32
+    lib.tq_rf_read.argtypes = [vp, vp, vp, vp]
+    lib.tq_rf_read.restype = i32
+    lib.tq_rf_stats.argtypes = [vp, vp]
+    lib.tq_rf_stats.restype = i32
+    lib.tq_rf_word_shared.argtypes = [c.c_uint64, c.c_uint64]
+    lib.tq_rf_word_shared.restype = c.c_uint32
     lib.tq_set_species.argtypes = [vp, vp, i64, i64]
     lib.tq_set_species.restype = i32
     lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]

@@ -39,6 +39,7 @@
 //   nni.hpp       tq_nni_*_kernel: the quartet-fit weights of every nearest-neighbour interchange of a tree in one row pass; the polish search
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
 //   tbe.hpp       tq_tbe_kernel: transfer distances of a reference tree's branches to every node of many trees (TBE)
+//   treedist.hpp  tq_rf_*_kernel: split ids, bit rows and their product: all-pairs Robinson-Foulds distances of a tree set
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
@@ -95,6 +96,7 @@ namespace {
 #include "supertree.hpp"
 #include "consensus.hpp"
 #include "tbe.hpp"
+#include "treedist.hpp"
 #include "fit.hpp"
 #include "nni.hpp"
 #include "patterns.hpp"
@@ -2043,6 +2045,242 @@ int tbe_launch(tq_tbe *a, int64_t ntrees, hipStream_t st, bool want_phi)
         TQ_HIP(ctx, hipMemcpyAsync(a->p_phi, a->d_phi, (size_t)ntrees * a->E * 2, hipMemcpyDeviceToHost, st));
     TQ_HIP(ctx, a->order.mark(st));
     ++a->chunks;
+    return TQ_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// Tree distance accumulator (treedist.hpp).  Host back end: an exact map mask -> id and one ascending id list per tree.
+// Device back end: a consensus table of its own gives the ids, the same map resolves the splits that lost a hash
+// collision; a read builds the bit rows and multiplies them.
+// ---------------------------------------------------------------------------------------------
+struct tq_rf {
+    tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
+    int32_t T = 0, W = 0, G = 1;
+    uint64_t tail = 0;
+    int64_t max_trees = 0, max_splits = 0, ntrees = 0;
+    ConsMap host;                   // mask -> id (host back end) or -> k, the id being max_splits - 1 - k (device)
+    std::vector<int64_t> host_count;        // [id or k] trees that hold it
+    std::vector<std::vector<uint32_t>> lists;       // host back end: the ascending ids of every tree
+    bool overflow = false;          // more distinct splits than max_splits were offered: unusable until a reset
+    bool final_ok = false;          // the matrices below / on the device are those of everything added
+    std::vector<int32_t> h_nsplits; // host back end results
+    std::vector<uint32_t> h_shared, h_rf;
+    int64_t columns = 0, col_chunks = 0;    // of the last read
+    // device back end
+    int hash_bits = 64;
+    int64_t chunk_trees = 0, slots = 0, gather_cap = 0, cw_chunk = 0;
+    int64_t chunk_base = 0;         // first tree of the chunk in flight
+    PinnedBuf<int32_t> p_trees;
+    DevBuf<int32_t> d_trees, d_slot_idx, d_nsplits;
+    DevBuf<uint64_t> d_masks, d_keys, d_rep, d_gather;
+    PinnedBuf<uint64_t> p_gather;
+    DevBuf<unsigned long long> d_slot_key, d_count, d_bits;
+    DevBuf<unsigned int> d_ctr;
+    PinnedBuf<unsigned int> p_ctr;
+    DevBuf<uint32_t> d_unres, d_newid, d_ids, d_colmap, d_shared, d_rf;
+    PinnedBuf<uint32_t> p_newid;
+    StreamOrder order;              // behind the last chunk
+    int64_t dev_entries = 0;        // entries of the device table after the last finished chunk
+    int64_t chunks = 0, unresolved = 0;
+    tq_rf() = default;
+    tq_rf(const tq_rf &) = delete;
+    ~tq_rf()                        // runs before the buffers' destructors: device selected, last chunk finished
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)order.sync();
+        if (order.ev) (void)hipEventDestroy(order.ev);
+    }
+};
+
+namespace {
+
+int rf_overflow(tq_rf *a, const char *who)
+{
+    a->overflow = true;
+    return fail(a->ctx, TQ_ERR_INVALID_ARG, "%s: more than max_splits = %lld distinct splits; reset the accumulator", who,
+                (long long)a->max_splits);
+}
+
+ConsArgs rf_cons_args(const tq_rf *a, int64_t ntrees)
+{
+    ConsArgs p{};
+    p.trees = a->d_trees; p.masks = a->d_masks; p.keys = a->d_keys;
+    p.items = ntrees * (a->T - 2);
+    p.T = a->T; p.W = a->W; p.G = a->G; p.hash_bits = a->hash_bits; p.tail = a->tail;
+    p.slot_key = a->d_slot_key; p.slot_idx = a->d_slot_idx; p.rep = a->d_rep; p.count = a->d_count; p.ctr = a->d_ctr;
+    p.unres = a->d_unres; p.slot_mask = a->slots - 1; p.max_splits = a->max_splits;
+    return p;
+}
+
+// empty table and no trees (also the reset).  ids, bit rows and matrices need no clearing: a read uses the rows of the
+// trees added since, all of which an add has written.
+int rf_clear_dev(tq_rf *a)
+{
+    tq_ctx *ctx = a->ctx;
+    TQ_HIP(ctx, hipMemset(a->d_slot_key, 0xFF, (size_t)a->slots * 8));
+    TQ_HIP(ctx, hipMemset(a->d_slot_idx, 0xFF, (size_t)a->slots * 4));
+    TQ_HIP(ctx, hipMemset(a->d_count, 0, (size_t)a->max_splits * 8));
+    TQ_HIP(ctx, hipMemset(a->d_nsplits, 0, (size_t)a->max_trees * 4));
+    TQ_HIP(ctx, hipMemset(a->d_ctr, 0, CONS_CTR_WORDS * 4));
+    TQ_HIP(ctx, hipDeviceSynchronize());
+    return TQ_OK;
+}
+
+// Waits for the last chunk, reads its counters, gives its unresolved splits their ids from the host map and stores them.
+int rf_drain(tq_rf *a)
+{
+    if (!a->order.pending) return TQ_OK;
+    tq_ctx *ctx = a->ctx;
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    TQ_HIP(ctx, a->order.sync());
+    a->dev_entries = std::min<int64_t>((int64_t)a->p_ctr[CONS_CTR_CLAIMS], a->max_splits);
+    if (a->p_ctr[CONS_CTR_OVERFLOW]) return rf_overflow(a, "tq_rf");
+    const int64_t nun = (int64_t)a->p_ctr[CONS_CTR_UNRES];
+    if (nun == 0) return TQ_OK;
+    hipStream_t st = a->order.last;
+    std::vector<uint64_t> m((size_t)a->W);
+    for (int64_t first = 0; first < nun; first += a->gather_cap) {
+        const int64_t n = std::min<int64_t>(a->gather_cap, nun - first);
+        hipLaunchKernelGGL(tq_cons_gather_kernel, dim3((unsigned)((n * a->W + CONS_THREADS - 1) / CONS_THREADS)),
+                           dim3(CONS_THREADS), 0, st, (const uint32_t *)a->d_unres, first, n, (const uint64_t *)a->d_masks,
+                           a->W, a->d_gather);
+        TQ_HIP(ctx, hipGetLastError());
+        TQ_HIP(ctx, hipMemcpyAsync(a->p_gather, a->d_gather, (size_t)n * a->W * 8, hipMemcpyDeviceToHost, st));
+        TQ_HIP(ctx, hipStreamSynchronize(st));
+        for (int64_t e = 0; e < n; ++e) {
+            m.assign(a->p_gather + e * a->W, a->p_gather + (e + 1) * a->W);
+            auto it = a->host.find(m);
+            if (it == a->host.end()) {
+                if (a->dev_entries + (int64_t)a->host.size() >= a->max_splits) return rf_overflow(a, "tq_rf");
+                it = a->host.emplace(m, (int64_t)a->host.size()).first;
+                a->host_count.push_back(0);
+            }
+            ++a->host_count[(size_t)it->second];
+            a->p_newid[first + e] = (uint32_t)(a->max_splits - 1 - it->second);
+        }
+    }
+    RfIdentArgs r{a->d_ids, a->d_nsplits, a->chunk_base};
+    TQ_HIP(ctx, hipMemcpyAsync(a->d_newid, a->p_newid, (size_t)nun * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(tq_rf_patch_kernel, dim3((unsigned)((nun + CONS_THREADS - 1) / CONS_THREADS)), dim3(CONS_THREADS), 0, st,
+                       (const uint32_t *)a->d_unres, (const uint32_t *)a->d_newid, nun, r, a->T - 2);
+    TQ_HIP(ctx, hipGetLastError());
+    TQ_HIP(ctx, hipStreamSynchronize(st));
+    a->unresolved += nun;
+    if (a->dev_entries + (int64_t)a->host.size() > a->max_splits) return rf_overflow(a, "tq_rf");
+    return TQ_OK;
+}
+
+// One chunk of prepared records (already in the page-locked buffer), trees first .. first + ntrees - 1, on `st`.
+int rf_launch(tq_rf *a, int64_t first, int64_t ntrees, hipStream_t st)
+{
+    tq_ctx *ctx = a->ctx;
+    const ConsArgs p = rf_cons_args(a, ntrees);
+    const RfIdentArgs r{a->d_ids, a->d_nsplits, first};
+    TQ_HIP(ctx, hipMemcpyAsync(a->d_trees, a->p_trees, (size_t)ntrees * cons_stride(a->T) * 4, hipMemcpyHostToDevice, st));
+    TQ_HIP(ctx, hipMemsetAsync(a->d_ctr + CONS_CTR_UNRES, 0, 4, st));
+    const unsigned blocks = (unsigned)((p.items * a->G + CONS_THREADS - 1) / CONS_THREADS);
+    hipLaunchKernelGGL(tq_cons_mask_kernel, dim3((unsigned)ntrees), dim3(CONS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(tq_cons_insert_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(tq_rf_ident_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p, r);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_rf_add: launch failed: %s", hipGetErrorString(e));
+    TQ_HIP(ctx, hipMemcpyAsync(a->p_ctr, a->d_ctr, CONS_CTR_WORDS * 4, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, a->order.mark(st));
+    a->chunk_base = first;
+    ++a->chunks;
+    return TQ_OK;
+}
+
+// Host back end: the three arrays of everything added.
+void rf_host_final(tq_rf *a)
+{
+    const int64_t N = a->ntrees;
+    a->h_nsplits.assign((size_t)N, 0);
+    a->h_shared.assign((size_t)(N * N), 0);
+    a->h_rf.assign((size_t)(N * N), 0);
+    for (int64_t i = 0; i < N; ++i) a->h_nsplits[i] = (int32_t)a->lists[i].size();
+    for (int64_t i = 0; i < N; ++i) {
+        a->h_shared[i * N + i] = (uint32_t)a->h_nsplits[i];
+        for (int64_t j = i + 1; j < N; ++j) {
+            const uint32_t s = rf_host_shared(a->lists[i], a->lists[j]);
+            const uint32_t d = rf_distance((uint32_t)a->h_nsplits[i], (uint32_t)a->h_nsplits[j], s);
+            a->h_shared[i * N + j] = a->h_shared[j * N + i] = s;
+            a->h_rf[i * N + j] = a->h_rf[j * N + i] = d;
+        }
+    }
+    a->columns = 0;
+    for (int64_t c : a->host_count) a->columns += c >= 2;
+    a->col_chunks = 0;
+}
+
+// Device back end: columns, bit rows, the product and the epilogue; the matrices stay on the device.
+int rf_dev_final(tq_rf *a)
+{
+    tq_ctx *ctx = a->ctx;
+    const int64_t N = a->ntrees, nd = a->dev_entries, nh = (int64_t)a->host_count.size();
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    // columns in entry order: the device entries, then the host's
+    std::vector<unsigned long long> cnt((size_t)nd);
+    if (nd) TQ_HIP(ctx, hipMemcpy(cnt.data(), a->d_count, (size_t)nd * 8, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> dev_col((size_t)nd), host_col((size_t)nh);       // host_col[i] belongs to id max_splits - nh + i
+    uint32_t C = 0;
+    for (int64_t e = 0; e < nd; ++e) dev_col[e] = cnt[e] >= 2 ? C++ : RF_NONE;
+    for (int64_t k = 0; k < nh; ++k) host_col[nh - 1 - k] = a->host_count[k] >= 2 ? C++ : RF_NONE;
+    hipStream_t st = a->order.last;
+    int64_t launched = 0;
+    TQ_HIP(ctx, hipMemsetAsync(a->d_shared, 0, (size_t)(N * N) * 4, st));
+    if (C) {
+        if (nd) TQ_HIP(ctx, hipMemcpyAsync(a->d_colmap, dev_col.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
+        if (nh)
+            TQ_HIP(ctx, hipMemcpyAsync(a->d_colmap + (a->max_splits - nh), host_col.data(), (size_t)nh * 4,
+                                       hipMemcpyHostToDevice, st));
+        const int64_t per = a->cw_chunk * 64, nt = (N + RF_BT - 1) / RF_BT;
+        RfBitArgs b{};
+        b.ids = a->d_ids; b.colmap = a->d_colmap; b.bits = a->d_bits;
+        b.items = N * (a->T - 2); b.nodes = a->T - 2;
+        RfGemmArgs g{};
+        g.bits = (const uint64_t *)a->d_bits.get(); g.shared = a->d_shared;
+        g.N = (int32_t)N; g.nt = (int32_t)nt;
+        for (int64_t c0 = 0; c0 < (int64_t)C; c0 += per) {
+            b.col0 = (uint32_t)c0;
+            b.ncol = (uint32_t)std::min<int64_t>(per, (int64_t)C - c0);
+            g.Cw = (int32_t)((b.ncol + 63) / 64);
+            b.pitch = g.pitch = g.Cw;           // rows packed to the chunk's words (at most cw_chunk)
+            TQ_HIP(ctx, hipMemsetAsync(a->d_bits, 0, (size_t)(N * g.Cw) * 8, st));
+            hipLaunchKernelGGL(tq_rf_scatter_kernel, dim3((unsigned)((b.items + RF_THREADS - 1) / RF_THREADS)), dim3(RF_THREADS),
+                               0, st, b);
+            hipLaunchKernelGGL(tq_rf_gemm_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(RF_THREADS), 0, st, g);
+            ++launched;
+        }
+    }
+    hipLaunchKernelGGL(tq_rf_final_kernel, dim3((unsigned)((N * N + RF_THREADS - 1) / RF_THREADS)), dim3(RF_THREADS), 0, st,
+                       a->d_shared.get(), a->d_rf.get(), (const int32_t *)a->d_nsplits.get(), (int32_t)N);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_rf_read: launch failed: %s", hipGetErrorString(e));
+    TQ_HIP(ctx, hipStreamSynchronize(st));      // dev_col / host_col live until here
+    a->columns = C;
+    a->col_chunks = launched;
+    return TQ_OK;
+}
+
+// The matrices of everything added (kept until the next add / reset).
+int rf_final(tq_rf *a, const char *who)
+{
+    if (a->overflow) return rf_overflow(a, who);
+    if (a->ctx)
+        if (int rc = rf_drain(a)) return rc;
+    if (a->final_ok) return TQ_OK;
+    if (a->ntrees == 0) {
+        a->columns = a->col_chunks = 0;
+    } else if (!a->ctx) {
+        rf_host_final(a);
+    } else if (int rc = rf_dev_final(a)) {
+        return rc;
+    }
+    a->final_ok = true;
     return TQ_OK;
 }
 
@@ -4646,6 +4884,226 @@ int tq_tbe_stats(tq_tbe *acc, int64_t *out)
     out[1] = acc->chunks;
     return TQ_OK;
 }
+
+int tq_rf_create(tq_rf **out, int64_t T, int64_t max_trees, int64_t max_splits, tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: out is NULL");
+    *out = nullptr;
+    if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: T must be 4..%d", CONS_T_MAX);
+    if (max_trees < 1 || max_trees > RF_MAX_TREES)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: max_trees must be 1..%lld", (long long)RF_MAX_TREES);
+    if (max_splits < 1 || max_splits > (int64_t(1) << 26))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: max_splits must be 1..2^26");
+    tq_rf *a = new (std::nothrow) tq_rf();
+    if (!a) return fail(ctx, TQ_ERR_OOM, "tq_rf_create: out of host memory");
+    a->ctx = ctx;
+    a->T = (int32_t)T;
+    a->W = (int32_t)((T + 63) / 64);
+    a->tail = (T & 63) ? (uint64_t(1) << (T & 63)) - 1 : ~uint64_t(0);
+    a->max_trees = max_trees;
+    a->max_splits = max_splits;
+    while (a->G < a->W) a->G *= 2;
+    if (ctx) {
+        const int64_t W = a->W, nodes = T - 2, stride = cons_stride(T);
+        a->hash_bits = ctx->cons_hash_bits;
+        // masks, keys, unresolved items and their ids (device and page-locked), record
+        const int64_t per_tree = nodes * W * 8 + nodes * 8 + nodes * 4 * 3 + stride * 4;
+        a->chunk_trees = std::max<int64_t>(1, std::min<int64_t>(CONS_CHUNK_MAX, ctx->cons_scratch_bytes / per_tree));
+        a->chunk_trees = std::min<int64_t>(a->chunk_trees, max_trees);
+        a->slots = 64;
+        while (a->slots < 2 * max_splits) a->slots *= 2;
+        a->gather_cap = std::max<int64_t>(1, CONS_GATHER_BYTES / (W * 8));
+        // a column is a split of at least two trees
+        const int64_t max_cols = std::max<int64_t>(1, std::min<int64_t>(max_splits, max_trees * (T - 3) / 2));
+        a->cw_chunk = std::max<int64_t>(1, std::min<int64_t>((max_cols + 63) / 64, ctx->cons_scratch_bytes / (max_trees * 8)));
+        const int64_t C = a->chunk_trees;
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = a->d_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->d_masks.alloc((size_t)C * nodes * W);
+        if (e == hipSuccess) e = a->d_keys.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->d_unres.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->d_newid.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->d_slot_key.alloc((size_t)a->slots);
+        if (e == hipSuccess) e = a->d_slot_idx.alloc((size_t)a->slots);
+        if (e == hipSuccess) e = a->d_rep.alloc((size_t)max_splits * W);
+        if (e == hipSuccess) e = a->d_count.alloc((size_t)max_splits);
+        if (e == hipSuccess) e = a->d_colmap.alloc((size_t)max_splits);
+        if (e == hipSuccess) e = a->d_ctr.alloc(CONS_CTR_WORDS);
+        if (e == hipSuccess) e = a->d_gather.alloc((size_t)a->gather_cap * W);
+        if (e == hipSuccess) e = a->d_ids.alloc((size_t)max_trees * nodes);
+        if (e == hipSuccess) e = a->d_nsplits.alloc((size_t)max_trees);
+        if (e == hipSuccess) e = a->d_bits.alloc((size_t)max_trees * a->cw_chunk);
+        if (e == hipSuccess) e = a->d_shared.alloc((size_t)max_trees * max_trees);
+        if (e == hipSuccess) e = a->d_rf.alloc((size_t)max_trees * max_trees);
+        if (e == hipSuccess) e = a->p_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->p_gather.alloc((size_t)a->gather_cap * W);
+        if (e == hipSuccess) e = a->p_newid.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->p_ctr.alloc(CONS_CTR_WORDS);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            delete a;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_rf_create: %s", hipGetErrorString(e));
+        }
+        if (int rc = rf_clear_dev(a)) {
+            delete a;
+            return rc;
+        }
+    }
+    *out = a;
+    return TQ_OK;
+}
+
+void tq_rf_destroy(tq_rf *acc) { delete acc; }
+
+int tq_rf_reset(tq_rf *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (acc->ctx) {
+        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+        TQ_HIP(acc->ctx, acc->order.sync());
+        if (int rc = rf_clear_dev(acc)) return rc;
+        acc->hash_bits = acc->ctx->cons_hash_bits;
+    }
+    acc->host.clear();
+    acc->host_count.clear();
+    acc->lists.clear();
+    acc->ntrees = 0;
+    acc->dev_entries = 0;
+    acc->chunks = 0;
+    acc->unresolved = 0;
+    acc->columns = acc->col_chunks = 0;
+    acc->overflow = false;
+    acc->final_ok = false;
+    return TQ_OK;
+}
+
+int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: NULL pointer or negative size");
+    if (acc->overflow) return rf_overflow(acc, "tq_rf_add");
+    if (R == 0) return TQ_OK;
+    if (acc->ntrees + R > acc->max_trees)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: %lld trees held and %lld offered exceed max_trees = %lld",
+                    (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
+    try {
+        const int64_t S = cons_stride(acc->T);
+        std::vector<int32_t> recs((size_t)R * S);       // every tree is validated before the first one is added
+        for (int64_t r = 0; r < R; ++r) {
+            if (n_nodes[r] > stride)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: tree %lld: n_nodes exceeds the stride", (long long)r);
+            const std::string err = cons_prepare(parents + r * stride, n_nodes[r], acc->T, &recs[(size_t)r * S]);
+            if (!err.empty())
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: tree %lld: %s", (long long)r, err.c_str());
+        }
+        if (!ctx) {
+            std::vector<uint64_t> tmp, sides, m((size_t)acc->W);
+            acc->lists.reserve((size_t)(acc->ntrees + R));
+            for (int64_t r = 0; r < R; ++r) {
+                sides.clear();
+                cons_host_splits(&recs[(size_t)r * S], acc->T, acc->W, tmp, sides);
+                std::vector<uint32_t> ids;
+                ids.reserve(sides.size() / acc->W);
+                for (size_t e = 0; e < sides.size(); e += acc->W) {
+                    m.assign(sides.begin() + e, sides.begin() + e + acc->W);
+                    auto it = acc->host.find(m);
+                    if (it == acc->host.end()) {
+                        if ((int64_t)acc->host.size() >= acc->max_splits) return rf_overflow(acc, "tq_rf_add");
+                        it = acc->host.emplace(m, (int64_t)acc->host.size()).first;
+                        acc->host_count.push_back(0);
+                    }
+                    ++acc->host_count[(size_t)it->second];
+                    ids.push_back((uint32_t)it->second);
+                }
+                std::sort(ids.begin(), ids.end());
+                acc->lists.push_back(std::move(ids));
+                acc->final_ok = false;
+                ++acc->ntrees;
+            }
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, hipSetDevice(ctx->device));
+        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk_trees) {
+            const int64_t n = std::min<int64_t>(acc->chunk_trees, R - r0);
+            if (int rc = rf_drain(acc)) return rc;          // the staging buffer and the mask scratch are free again
+            memcpy(acc->p_trees, &recs[(size_t)r0 * S], (size_t)n * S * 4);
+            acc->final_ok = false;
+            if (int rc = rf_launch(acc, acc->ntrees, n, (hipStream_t)stream)) return rc;
+            acc->ntrees += n;
+        }
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_rf_add: out of host memory");
+    }
+}
+
+int tq_rf_shape(tq_rf *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits, int64_t *columns)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->T;
+    if (W) *W = acc->W;
+    if (ntrees) *ntrees = acc->ntrees;
+    if (nsplits) {
+        if (acc->ctx && !acc->overflow) {
+            try {
+                if (int rc = rf_drain(acc)) return rc;
+            } catch (const std::bad_alloc &) {
+                return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_shape: out of host memory");
+            }
+        }
+        *nsplits = (acc->ctx ? acc->dev_entries : 0) + (int64_t)acc->host.size();
+    }
+    if (columns) *columns = acc->columns;
+    return TQ_OK;
+}
+
+int tq_rf_read(tq_rf *acc, int32_t *nsplits, uint32_t *shared, uint32_t *rf)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    try {
+        if (int rc = rf_final(acc, "tq_rf_read")) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_read: out of host memory");
+    }
+    const size_t N = (size_t)acc->ntrees;
+    if (N == 0) return TQ_OK;
+    if (acc->ctx) {
+        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
+        if (nsplits) TQ_HIP(acc->ctx, hipMemcpy(nsplits, acc->d_nsplits, N * 4, hipMemcpyDeviceToHost));
+        if (shared) TQ_HIP(acc->ctx, hipMemcpy(shared, acc->d_shared, N * N * 4, hipMemcpyDeviceToHost));
+        if (rf) TQ_HIP(acc->ctx, hipMemcpy(rf, acc->d_rf, N * N * 4, hipMemcpyDeviceToHost));
+    } else {
+        if (nsplits) memcpy(nsplits, acc->h_nsplits.data(), N * 4);
+        if (shared) memcpy(shared, acc->h_shared.data(), N * N * 4);
+        if (rf) memcpy(rf, acc->h_rf.data(), N * N * 4);
+    }
+    return TQ_OK;
+}
+
+int tq_rf_stats(tq_rf *acc, int64_t *out)
+{
+    if (!acc || !out) return TQ_ERR_INVALID_ARG;
+    if (acc->ctx && !acc->overflow) {
+        try {
+            if (int rc = rf_drain(acc)) return rc;
+        } catch (const std::bad_alloc &) {
+            return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_stats: out of host memory");
+        }
+    }
+    out[0] = acc->chunk_trees;
+    out[1] = acc->chunks;
+    out[2] = acc->columns;
+    out[3] = acc->cw_chunk;
+    out[4] = acc->col_chunks;
+    out[5] = acc->unresolved;
+    out[6] = acc->hash_bits;
+    out[7] = acc->dev_entries;
+    return TQ_OK;
+}
+
+uint32_t tq_rf_word_shared(uint64_t x, uint64_t y) { return rf_word_shared(x, y); }
 
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch)
 {
