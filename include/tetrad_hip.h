@@ -620,6 +620,65 @@ int tq_rf_read(tq_rf *acc, int32_t *nsplits, uint32_t *shared, uint32_t *rf);
 int tq_rf_stats(tq_rf *acc, int64_t *out);
 uint32_t tq_rf_word_shared(uint64_t x, uint64_t y);
 
+/* All-pairs quartet distances of a set of trees: for every pair of trees the number of quartets
+ * both resolve alike, both resolve differently, only one resolves, neither resolves -- the ruler of the quartet
+ * supertrees themselves, and one that a single misplaced taxon moves little.  Integers only; the host and the device
+ * execution return identical arrays.  No reference counterpart.
+ *   Trees are parent arrays as tq_stree_fit takes them (a root of degree 2 is dissolved, unary nodes are suppressed,
+ *   multifurcations allowed), 4 <= T <= 1024 on both back ends.  D(x, y) is the depth of the lowest common ancestor of
+ *   tips x and y.  The code of four distinct taxa (a, b, c, d), in any order, in a tree: with m0 = D(a,b) + D(c,d),
+ *   m1 = D(a,c) + D(b,d), m2 = D(a,d) + D(b,c) it is 0, 1 or 2 when m0, m1 or m2 is strictly the largest and 3
+ *   (unresolved) otherwise.
+ *   same[i][j]    quartets scored so far that trees i and j both resolve, with the same code.
+ *   both[i][j]    quartets scored so far that both resolve; both[i][i] = the quartets tree i resolves.
+ *   Both are exact u64 sums, symmetric, N x N over the trees in the order they were added.  No result depends on the
+ *   launch shape, the chunking of trees or quartets, the k split, streams, the order of score calls or the order of the
+ *   taxa inside a quartet.
+ *   tq_qd_create   max_trees 1..8192.  `ctx` NULL: host back end.  With a context all device and page-locked memory is
+ *                  allocated here: tables max_trees T^2 u16, the parent records max_trees 2 T i32 (device and
+ *                  page-locked), two u64 matrices of max_trees^2, and one chunk of quartets -- per quartet 16 bytes of
+ *                  taxa and 8 of rank on the device, 16 page-locked, and 3 bits of plane row for each of max_trees --
+ *                  within the option "qdist_scratch_bytes" (tq_set_option, default 256 MiB, 0 = default, read here).  A
+ *                  failed allocation is TQ_ERR_OOM / TQ_ERR_HIP with a message and frees everything.  The context must
+ *                  outlive the accumulator; messages go to tq_last_error(ctx).
+ *   tq_qd_add      parents i32[R][stride], n_nodes i64[R] (each <= stride).  Every tree is validated first, with the
+ *                  messages of tq_stree_fit: one bad tree is TQ_ERR_INVALID_ARG naming its index, more than max_trees
+ *                  trees in all is TQ_ERR_INVALID_ARG, and nothing of the call is added.  The tables of the new trees are
+ *                  built (tq_fit_table_kernel on `stream`) and kept.  Refused once anything has been scored, until a
+ *                  clear or reset.  R = 0 is a no-op.
+ *   tq_qd_score    quartets i32[Q][4]: the host checks every quartet (taxa distinct and < T); one bad quartet is
+ *                  TQ_ERR_INVALID_ARG naming its index and nothing is scored.  Device back end: chunk by chunk on
+ *                  `stream` (hipStream_t, NULL = default stream) tq_qd_encode_kernel writes three bit planes per tree and
+ *                  tq_qd_gemm_kernel adds their product; the call returns with the last chunk in flight.
+ *   tq_qd_score_ranks  ranks u64[Q], or NULL for the Q consecutive ranks from first_rank: lexicographic ranks of
+ *                  4-combinations as in tq_resolve_range_dev, unranked by tq_unrank_kernel.  A rank >= C(T,4) is
+ *                  TQ_ERR_INVALID_ARG naming its index and nothing is scored.  Q = 0 and an accumulator without trees are
+ *                  valid no-ops (of both score calls).
+ *   Calls on different streams are ordered in call order.  Option "qdist_kslices" (0 = auto, read at every score): the
+ *   number of slices the words of a chunk are split into across workgroups of the product; auto aims at about 4
+ *   workgroups per compute unit, never more slices than staged word chunks (of 8 words).
+ *   tq_qd_clear    zeroes the counts and keeps the trees.   tq_qd_reset  forgets everything.  Both wait.
+ *   tq_qd_shape    T, trees held, quartets scored since create / clear / reset (any may be NULL).
+ *   tq_qd_read     same u64[N][N], both u64[N][N] (either may be NULL); waits.  May be called between score calls.
+ *   tq_qd_stats    out i64[6] = {quartets per chunk, quartet chunks launched since create / reset, k slices of the last
+ *                  launch (0 on the host), tree tables built since create / reset, table form (0 host, 1 LDS, 2 through
+ *                  L2), plane words per chunk}.
+ *   tq_qd_word_counts  the word rule of the product: same = popc(x0 & y0) + popc(x1 & y1) + popc(x2 & y2), both =
+ *                  popc((x0 | x1 | x2) & (y0 | y1 | y2)); the one definition tq_qd_gemm_kernel compiles.  */
+typedef struct tq_qd tq_qd;
+int tq_qd_create(tq_qd **out, int64_t T, int64_t max_trees, tq_ctx *ctx);
+void tq_qd_destroy(tq_qd *acc);
+int tq_qd_reset(tq_qd *acc);
+int tq_qd_clear(tq_qd *acc);
+int tq_qd_add(tq_qd *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream);
+int tq_qd_score(tq_qd *acc, const int32_t *quartets, int64_t Q, void *stream);
+int tq_qd_score_ranks(tq_qd *acc, const uint64_t *ranks, uint64_t first_rank, int64_t Q, void *stream);
+int tq_qd_shape(tq_qd *acc, int64_t *T, int64_t *ntrees, uint64_t *q_total);
+int tq_qd_read(tq_qd *acc, uint64_t *same, uint64_t *both);
+int tq_qd_stats(tq_qd *acc, int64_t *out);
+void tq_qd_word_counts(uint64_t x0, uint64_t x1, uint64_t x2, uint64_t y0, uint64_t y1, uint64_t y2, uint32_t *same,
+                       uint32_t *both);
+
 /* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
  * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
  * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.

@@ -7,7 +7,8 @@ over the GPUs of a node), ``replicates`` (bootstrap-replicate loop), ``bootstrap
 ``combinations`` (quartet producers), ``qmc_format`` / ``qmc`` (wQMC text and the quartet supertree), ``concordance``
 (quartet concordance on a fixed tree), ``consensus`` (split counts over many trees, majority-rule consensus),
 ``scf`` (site concordance factors per branch of a fixed tree), ``tbe`` (transfer bootstrap supports of a tree's
-branches over replicate trees), ``treedist`` (all-pairs Robinson-Foulds distances of a set of trees).
+branches over replicate trees), ``treedist`` (all-pairs Robinson-Foulds distances of a set of trees),
+``qdist`` (all-pairs quartet distances of a set of trees).
 Importing the package does not load the HIP library; the first compute call does, and fails loudly if it is missing.
 """
 __version__ = "0.2.0"
@@ -15,7 +16,8 @@ __version__ = "0.2.0"
 _SCF_EXPORTS = ("SiteConcordance", "sample_edge_quartets", "run_scf")
 _TBE_EXPORTS = ("TransferSupport", "transfer_supports")
 _TREEDIST_EXPORTS = ("TreeDistances", "rf_matrix")
-__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS + _TREEDIST_EXPORTS)
+_QDIST_EXPORTS = ("QuartetDistances", "quartet_distance_matrix")
+__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS + _TREEDIST_EXPORTS + _QDIST_EXPORTS)
 
 
 def __getattr__(name):
@@ -29,4 +31,7 @@ def __getattr__(name):
     if name in _TREEDIST_EXPORTS:
         from . import treedist
         return getattr(treedist, name)
+    if name in _QDIST_EXPORTS:
+        from . import qdist
+        return getattr(qdist, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -43,6 +43,8 @@ SYMBOLS = [
     "tq_tbe_create", "tq_tbe_destroy", "tq_tbe_reset", "tq_tbe_add", "tq_tbe_shape", "tq_tbe_read", "tq_tbe_stats",
     "tq_rf_create", "tq_rf_destroy", "tq_rf_reset", "tq_rf_add", "tq_rf_shape", "tq_rf_read", "tq_rf_stats",
     "tq_rf_word_shared",
+    "tq_qd_create", "tq_qd_destroy", "tq_qd_reset", "tq_qd_clear", "tq_qd_add", "tq_qd_score", "tq_qd_score_ranks",
+    "tq_qd_shape", "tq_qd_read", "tq_qd_stats", "tq_qd_word_counts",
     "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
     "tq_pack_sites",
     "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
@@ -281,6 +283,28 @@ def load() -> ctypes.CDLL:
     lib.tq_rf_stats.restype = i32
     lib.tq_rf_word_shared.argtypes = [c.c_uint64, c.c_uint64]
     lib.tq_rf_word_shared.restype = c.c_uint32
+    lib.tq_qd_create.argtypes = [c.POINTER(vp), i64, i64, vp]
+    lib.tq_qd_create.restype = i32
+    lib.tq_qd_destroy.argtypes = [vp]
+    lib.tq_qd_destroy.restype = None
+    lib.tq_qd_reset.argtypes = [vp]
+    lib.tq_qd_reset.restype = i32
+    lib.tq_qd_clear.argtypes = [vp]
+    lib.tq_qd_clear.restype = i32
+    lib.tq_qd_add.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.tq_qd_add.restype = i32
+    lib.tq_qd_score.argtypes = [vp, vp, i64, vp]
+    lib.tq_qd_score.restype = i32
+    lib.tq_qd_score_ranks.argtypes = [vp, vp, c.c_uint64, i64, vp]
+    lib.tq_qd_score_ranks.restype = i32
+    lib.tq_qd_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_uint64)]
+    lib.tq_qd_shape.restype = i32
+    lib.tq_qd_read.argtypes = [vp, vp, vp]
+    lib.tq_qd_read.restype = i32
+    lib.tq_qd_stats.argtypes = [vp, vp]
+    lib.tq_qd_stats.restype = i32
+    lib.tq_qd_word_counts.argtypes = [c.c_uint64] * 6 + [c.POINTER(c.c_uint32), c.POINTER(c.c_uint32)]
+    lib.tq_qd_word_counts.restype = None
     lib.tq_set_species.argtypes = [vp, vp, i64, i64]
     lib.tq_set_species.restype = i32
     lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]

@@ -40,6 +40,7 @@
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
 //   tbe.hpp       tq_tbe_kernel: transfer distances of a reference tree's branches to every node of many trees (TBE)
 //   treedist.hpp  tq_rf_*_kernel: split ids, bit rows and their product: all-pairs Robinson-Foulds distances of a tree set
+//   qdist.hpp     tq_qd_*_kernel: quartet topology planes of every tree and their product: all-pairs quartet distances of a tree set
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
@@ -98,6 +99,7 @@ namespace {
 #include "tbe.hpp"
 #include "treedist.hpp"
 #include "fit.hpp"
+#include "qdist.hpp"
 #include "nni.hpp"
 #include "patterns.hpp"
 #include "pattern_blocks.hpp"
@@ -185,6 +187,8 @@ struct tq_ctx {
     int cons_hash_bits = 64;        // consensus: the table key is the 64-bit mask hash cut to this many bits (results never depend on it)
     int64_t cons_scratch_bytes = int64_t(256) << 20;   // consensus: device + page-locked bytes of one chunk of trees
     int64_t fit_scratch_bytes = int64_t(64) << 20;     // quartet fit: device bytes of the tables of one chunk of trees (results never depend on it)
+    int64_t qdist_scratch_bytes = int64_t(256) << 20;  // quartet distances: device + page-locked bytes of one chunk of quartets (read at create)
+    int qdist_kslices = 0;          // quartet distances: k slices of the product, 0 = chosen from the compute units (read at every score)
     int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
     int stree_search_dev = 1;       // supertree rule "exact" on device rows: 1 = the search kernel, 0 = the same rule on the host (A/B)
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
@@ -2287,6 +2291,192 @@ int rf_final(tq_rf *a, const char *who)
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
+// Quartet distance accumulator (qdist.hpp).  Both back ends keep the depth table of every tree added and two u64
+// matrices; a score call walks its quartets a chunk at a time: the planes of every tree, then their product.
+// ---------------------------------------------------------------------------------------------
+struct tq_qd {
+    tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
+    int32_t T = 0;
+    int64_t max_trees = 0, ntrees = 0;
+    uint64_t q_total = 0;           // quartets scored since create / clear / reset
+    bool scored = false;            // adds are refused until a clear or reset
+    int64_t chunk_words = 0;        // plane words (of 64 quartets) of one chunk
+    int64_t chunks = 0, kslices = 0, tables = 0;
+    // host back end
+    std::vector<uint16_t> h_tab;    // [ntrees][T][T]
+    std::vector<uint64_t> h_same, h_both;   // [ntrees][ntrees] once something has been scored
+    // device back end
+    int num_cu = 1;
+    DevBuf<uint16_t> d_tab;         // [max_trees][T][T]
+    DevBuf<int32_t> d_rec;          // [max_trees][2 T]: the prepared parents, as tq_fit_table_kernel reads them
+    PinnedBuf<int32_t> p_rec;
+    DevBuf<unsigned long long> d_same, d_both;      // [max_trees^2], row pitch = ntrees
+    DevBuf<uint32_t> d_quart;       // [64 chunk_words][4]
+    DevBuf<uint64_t> d_ranks, d_planes;     // [64 chunk_words], [max_trees][3][chunk_words]
+    PinnedBuf<uint64_t> p_stage;    // 16 bytes per quartet of a chunk: its taxa or its rank on the way to the device
+    hipEvent_t copy_ev = nullptr;   // behind the last copy out of p_stage
+    bool copy_pending = false;
+    StreamOrder order;              // behind the last add / score
+    tq_qd() = default;
+    tq_qd(const tq_qd &) = delete;
+    ~tq_qd()                        // runs before the buffers' destructors: device selected, last work finished
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)order.sync();
+        if (copy_ev) { if (copy_pending) (void)hipEventSynchronize(copy_ev); (void)hipEventDestroy(copy_ev); }
+        if (order.ev) (void)hipEventDestroy(order.ev);
+    }
+};
+
+namespace {
+
+// the k slices of one product launch: `want` 0 = about QD_GRID_PER_CU workgroups per compute unit; never more than the
+// staged word chunks, and no slice is empty.  Returns the words per slice.
+int64_t qd_kslices(int64_t cw, int64_t nt, int num_cu, int want, int64_t *slices)
+{
+    const int64_t nchunks = (cw + QD_KW - 1) / QD_KW, pairs = nt * (nt + 1) / 2;
+    int64_t ks = want > 0 ? want : ((int64_t)QD_GRID_PER_CU * num_cu + pairs - 1) / pairs;
+    ks = std::max<int64_t>(1, std::min<int64_t>({ks, nchunks, 65535}));
+    const int64_t per = (nchunks + ks - 1) / ks;
+    *slices = (nchunks + per - 1) / per;
+    return per * QD_KW;
+}
+
+// the staging buffer is free again
+int qd_stage_wait(tq_qd *a)
+{
+    if (a->copy_pending) {
+        TQ_HIP(a->ctx, hipEventSynchronize(a->copy_ev));
+        a->copy_pending = false;
+    }
+    return TQ_OK;
+}
+
+// planes and product of the nq quartets in d_quart, on `st`
+int qd_launch(tq_qd *a, int64_t nq, hipStream_t st, const char *who)
+{
+    tq_ctx *ctx = a->ctx;
+    const int64_t N = a->ntrees, cw = (nq + 63) / 64, nt = (N + QD_BT - 1) / QD_BT;
+    QdEncodeArgs e{(const uint4 *)a->d_quart.get(), a->d_tab, a->d_planes, nq, (int32_t)cw, (uint32_t)a->T};
+    const unsigned slices = (unsigned)std::max<int64_t>(
+        1, std::min<int64_t>((cw + QD_ENC_WORDS_PER_BLOCK - 1) / QD_ENC_WORDS_PER_BLOCK, 4096));
+    if (a->T <= FIT_T_LDS)
+        hipLaunchKernelGGL(tq_qd_encode_kernel<true>, dim3(slices, (unsigned)N), dim3(QD_THREADS), 0, st, e);
+    else
+        hipLaunchKernelGGL(tq_qd_encode_kernel<false>, dim3(slices, (unsigned)N), dim3(QD_THREADS), 0, st, e);
+    QdGemmArgs g{};
+    g.planes = a->d_planes; g.same = a->d_same; g.both = a->d_both;
+    g.N = (int32_t)N; g.cw = (int32_t)cw; g.nt = (int32_t)nt;
+    int64_t ks = 1;
+    g.slice_words = (int32_t)qd_kslices(cw, nt, a->num_cu, ctx->qdist_kslices, &ks);
+    g.atomic = ks > 1;
+    hipLaunchKernelGGL(tq_qd_gemm_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)ks), dim3(QD_THREADS), 0, st, g);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(ctx, TQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
+    a->kslices = ks;
+    ++a->chunks;
+    return TQ_OK;
+}
+
+// Host back end: the quartets q[Q][4] against every table
+void qd_host_score(tq_qd *a, const uint32_t *q, int64_t Q)
+{
+    const int64_t N = a->ntrees, T = a->T, per = QD_HOST_CHUNK_WORDS * 64;
+    if (!a->scored) {
+        a->h_same.assign((size_t)(N * N), 0);
+        a->h_both.assign((size_t)(N * N), 0);
+    }
+    std::vector<uint64_t> planes;
+    for (int64_t q0 = 0; q0 < Q; q0 += per) {
+        const int64_t nq = std::min(per, Q - q0), cw = (nq + 63) / 64;
+        planes.resize((size_t)(N * 3 * cw));
+        for (int64_t t = 0; t < N; ++t)
+            qd_host_encode(&a->h_tab[(size_t)(t * T * T)], (uint32_t)T, q + 4 * q0, nq, cw, &planes[(size_t)(t * 3 * cw)]);
+        qd_host_product(planes.data(), N, cw, a->h_same.data(), a->h_both.data());
+        ++a->chunks;
+    }
+}
+
+// One score call: explicit quartets (`quartets`), explicit ranks (`ranks`) or the range from first_rank (both NULL).
+// Everything has been validated.
+int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t first_rank, int64_t Q, hipStream_t st,
+             const char *who)
+{
+    tq_ctx *ctx = a->ctx;
+    if (Q == 0 || a->ntrees == 0) return TQ_OK;
+    if (!ctx) {
+        const int64_t per = QD_HOST_CHUNK_WORDS * 64 * 16;          // unranked a piece at a time
+        std::vector<uint32_t> q;
+        for (int64_t q0 = 0; q0 < Q; q0 += per) {
+            const int64_t n = std::min(per, Q - q0);
+            const uint32_t *src = quartets ? (const uint32_t *)quartets + 4 * q0 : nullptr;
+            if (!quartets) {
+                q.resize((size_t)n * 4);
+                unrank_host(ranks ? ranks + q0 : nullptr, first_rank + (uint64_t)q0, n, a->T, q.data());
+                src = q.data();
+            }
+            qd_host_score(a, src, n);
+            a->scored = true;
+        }
+        a->q_total += (uint64_t)Q;
+        return TQ_OK;
+    }
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    TQ_HIP(ctx, a->order.join(st));
+    const int64_t per = a->chunk_words * 64;
+    for (int64_t q0 = 0; q0 < Q; q0 += per) {
+        const int64_t n = std::min(per, Q - q0);
+        if (quartets || ranks) {
+            if (int rc = qd_stage_wait(a)) return rc;
+            if (quartets) {
+                memcpy(a->p_stage, quartets + 4 * q0, (size_t)n * 16);
+                TQ_HIP(ctx, hipMemcpyAsync(a->d_quart, a->p_stage, (size_t)n * 16, hipMemcpyHostToDevice, st));
+            } else {
+                memcpy(a->p_stage, ranks + q0, (size_t)n * 8);
+                TQ_HIP(ctx, hipMemcpyAsync(a->d_ranks, a->p_stage, (size_t)n * 8, hipMemcpyHostToDevice, st));
+            }
+            TQ_HIP(ctx, hipEventRecord(a->copy_ev, st));
+            a->copy_pending = true;
+        }
+        if (!quartets) {
+            hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                               ranks ? (const uint64_t *)a->d_ranks.get() : (const uint64_t *)nullptr,
+                               first_rank + (uint64_t)q0, n, a->T, a->d_quart.get());
+            TQ_HIP(ctx, hipGetLastError());
+        }
+        a->scored = true;                                           // from here on the matrices hold part of the call
+        if (int rc = qd_launch(a, n, st, who)) return rc;
+        TQ_HIP(ctx, a->order.mark(st));
+    }
+    a->q_total += (uint64_t)Q;
+    return TQ_OK;
+}
+
+// zero counts (device: the part of the matrices that N trees use; the rest has not been written since create)
+int qd_zero(tq_qd *a)
+{
+    if (a->ctx) {
+        TQ_HIP(a->ctx, hipSetDevice(a->ctx->device));
+        TQ_HIP(a->ctx, a->order.sync());
+        if (int rc = qd_stage_wait(a)) return rc;
+        const size_t n = (size_t)(a->ntrees * a->ntrees) * 8;
+        if (n && a->scored) {
+            TQ_HIP(a->ctx, hipMemset(a->d_same, 0, n));
+            TQ_HIP(a->ctx, hipMemset(a->d_both, 0, n));
+            TQ_HIP(a->ctx, hipDeviceSynchronize());
+        }
+    }
+    a->h_same.clear();
+    a->h_both.clear();
+    a->q_total = 0;
+    a->scored = false;
+    return TQ_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
 // Exact supertree accumulator (supertree.hpp).  Host adds keep the weighted splits in host vectors; device adds append
 // them to the root store on the device.  A build never modifies either, so it may be repeated with any seed.
 // ---------------------------------------------------------------------------------------------
@@ -3316,6 +3506,16 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
     if (!strcmp(name, "fit_scratch_bytes")) {
         if (value < 1) return fail(ctx, TQ_ERR_INVALID_ARG, "fit_scratch_bytes must be at least 1");
         ctx->fit_scratch_bytes = value;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "qdist_scratch_bytes")) {         // read by tq_qd_create
+        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "qdist_scratch_bytes must be >= 0 (0 = default 256 MiB)");
+        ctx->qdist_scratch_bytes = value ? value : int64_t(256) << 20;
+        return TQ_OK;
+    }
+    if (!strcmp(name, "qdist_kslices")) {               // read by every tq_qd_score*
+        if (value < 0 || value > 65535) return fail(ctx, TQ_ERR_INVALID_ARG, "qdist_kslices must be 0 (auto) .. 65535");
+        ctx->qdist_kslices = (int)value;
         return TQ_OK;
     }
     if (!strcmp(name, "stree_lds")) {
@@ -5104,6 +5304,233 @@ int tq_rf_stats(tq_rf *acc, int64_t *out)
 }
 
 uint32_t tq_rf_word_shared(uint64_t x, uint64_t y) { return rf_word_shared(x, y); }
+
+int tq_qd_create(tq_qd **out, int64_t T, int64_t max_trees, tq_ctx *ctx)
+{
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: out is NULL");
+    *out = nullptr;
+    if (T < 4 || T > STREE_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: T must be 4..%d", STREE_T_MAX);
+    if (max_trees < 1 || max_trees > QD_MAX_TREES)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: max_trees must be 1..%lld", (long long)QD_MAX_TREES);
+    tq_qd *a = new (std::nothrow) tq_qd();
+    if (!a) return fail(ctx, TQ_ERR_OOM, "tq_qd_create: out of host memory");
+    a->ctx = ctx;
+    a->T = (int32_t)T;
+    a->max_trees = max_trees;
+    a->chunk_words = QD_HOST_CHUNK_WORDS;
+    if (ctx) {
+        // per plane word of a chunk: 64 quartets as taxa and as ranks on the device, 16 page-locked bytes each, and
+        // three plane words of every tree
+        const int64_t per_word = 64 * (16 + 8 + 16) + max_trees * 3 * 8;
+        a->chunk_words = std::max<int64_t>(1, std::min<int64_t>(ctx->qdist_scratch_bytes / per_word, QD_MAX_CHUNK_WORDS));
+        a->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+        const size_t cq = (size_t)a->chunk_words * 64, mm = (size_t)(max_trees * max_trees);
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = a->d_tab.alloc((size_t)max_trees * T * T);
+        if (e == hipSuccess) e = a->d_rec.alloc((size_t)max_trees * 2 * T);
+        if (e == hipSuccess) e = a->p_rec.alloc((size_t)max_trees * 2 * T);
+        if (e == hipSuccess) e = a->d_same.alloc(mm);
+        if (e == hipSuccess) e = a->d_both.alloc(mm);
+        if (e == hipSuccess) e = a->d_quart.alloc(cq * 4);
+        if (e == hipSuccess) e = a->d_ranks.alloc(cq);
+        if (e == hipSuccess) e = a->d_planes.alloc((size_t)max_trees * 3 * a->chunk_words);
+        if (e == hipSuccess) e = a->p_stage.alloc(cq * 2);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->copy_ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipMemset(a->d_same, 0, mm * 8);
+        if (e == hipSuccess) e = hipMemset(a->d_both, 0, mm * 8);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            delete a;
+            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_qd_create: %s", hipGetErrorString(e));
+        }
+    }
+    *out = a;
+    return TQ_OK;
+}
+
+void tq_qd_destroy(tq_qd *acc) { delete acc; }
+
+int tq_qd_clear(tq_qd *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return qd_zero(acc);
+}
+
+int tq_qd_reset(tq_qd *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (int rc = qd_zero(acc)) return rc;
+    acc->h_tab.clear();
+    acc->ntrees = 0;
+    acc->chunks = acc->kslices = acc->tables = 0;
+    return TQ_OK;
+}
+
+int tq_qd_add(tq_qd *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: NULL pointer or negative size");
+    if (R == 0) return TQ_OK;
+    if (acc->scored)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: quartets have been scored; clear or reset the accumulator first");
+    if (acc->ntrees + R > acc->max_trees)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: %lld trees held and %lld offered exceed max_trees = %lld",
+                    (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
+    const int64_t T = acc->T;
+    try {
+        std::vector<std::vector<int32_t>> pars((size_t)R);          // every tree is validated before the first one is added
+        std::vector<std::vector<int32_t>> nch;
+        for (int64_t r = 0; r < R; ++r) {
+            if (n_nodes[r] > stride)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: tree %lld: n_nodes exceeds the stride", (long long)r);
+            const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
+            if (!err.empty())
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: tree %lld: %s", (long long)r, err.c_str());
+            if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: tree %lld: internal error: a prepared tree of T taxa has "
+                            "at most 2 T - 2 nodes", (long long)r);
+        }
+        if (!ctx) {
+            acc->h_tab.resize((size_t)((acc->ntrees + R) * T * T));
+            std::vector<uint32_t> dep;
+            for (int64_t r = 0; r < R; ++r)
+                fit_host_table(pars[(size_t)r], (uint32_t)T, dep, &acc->h_tab[(size_t)((acc->ntrees + r) * T * T)]);
+            acc->ntrees += R;
+            acc->tables += R;
+            return TQ_OK;
+        }
+        hipStream_t st = (hipStream_t)stream;
+        TQ_HIP(ctx, hipSetDevice(ctx->device));
+        TQ_HIP(ctx, acc->order.join(st));
+        const int64_t S = 2 * T, first = acc->ntrees;
+        int32_t *rec0 = acc->p_rec + first * S;                     // every tree has a record of its own: none is reused
+        memset(rec0, 0, (size_t)(R * S) * 4);
+        for (int64_t r = 0; r < R; ++r) {
+            memcpy(rec0 + r * S, pars[(size_t)r].data(), pars[(size_t)r].size() * 4);
+            rec0[r * S + S - 1] = (int32_t)pars[(size_t)r].size();
+        }
+        TQ_HIP(ctx, hipMemcpyAsync(acc->d_rec + first * S, rec0, (size_t)(R * S) * 4, hipMemcpyHostToDevice, st));
+        const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
+        const unsigned table_blocks = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
+        FitTableArgs ta{acc->d_rec + first * S, acc->d_tab + first * T * T, (uint32_t)T};
+        hipLaunchKernelGGL(tq_fit_table_kernel, dim3(table_blocks, (unsigned)R), dim3(FIT_THREADS), 0, st, ta);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_qd_add: launch failed: %s", hipGetErrorString(e));
+        TQ_HIP(ctx, acc->order.mark(st));
+        acc->ntrees += R;
+        acc->tables += R;
+        return TQ_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_qd_add: out of host memory");
+    }
+}
+
+int tq_qd_score(tq_qd *acc, const int32_t *quartets, int64_t Q, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (Q < 0 || (Q > 0 && !quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: NULL pointer or negative Q");
+    const int32_t T = acc->T;
+    for (int64_t i = 0; i < Q; ++i) {                               // every quartet is validated before anything is scored
+        const int32_t *q = quartets + 4 * i;
+        if (q[0] < 0 || q[0] >= T || q[1] < 0 || q[1] >= T || q[2] < 0 || q[2] >= T || q[3] < 0 || q[3] >= T)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: taxon out of range 0..%d", (long long)i, T - 1);
+        if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: repeated taxon", (long long)i);
+    }
+    try {
+        return qd_score(acc, quartets, nullptr, 0, Q, (hipStream_t)stream, "tq_qd_score");
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_qd_score: out of host memory");
+    }
+}
+
+int tq_qd_score_ranks(tq_qd *acc, const uint64_t *ranks, uint64_t first_rank, int64_t Q, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    if (Q < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: negative Q");
+    const uint64_t total = choose4((uint64_t)acc->T);
+    if (ranks) {
+        for (int64_t i = 0; i < Q; ++i)
+            if (ranks[i] >= total)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank %lld: %llu is not below C(%d,4) = %llu",
+                            (long long)i, (unsigned long long)ranks[i], acc->T, (unsigned long long)total);
+    } else if (Q > 0 && (first_rank > total || (uint64_t)Q > total - first_rank)) {
+        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank range [%llu,+%lld) exceeds C(%d,4) = %llu",
+                    (unsigned long long)first_rank, (long long)Q, acc->T, (unsigned long long)total);
+    }
+    try {
+        return qd_score(acc, nullptr, ranks, ranks ? 0 : first_rank, Q, (hipStream_t)stream, "tq_qd_score_ranks");
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "tq_qd_score_ranks: out of host memory");
+    }
+}
+
+int tq_qd_shape(tq_qd *acc, int64_t *T, int64_t *ntrees, uint64_t *q_total)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->T;
+    if (ntrees) *ntrees = acc->ntrees;
+    if (q_total) *q_total = acc->q_total;
+    return TQ_OK;
+}
+
+int tq_qd_read(tq_qd *acc, uint64_t *same, uint64_t *both)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->ctx;
+    const int64_t N = acc->ntrees;
+    const size_t bytes = (size_t)(N * N) * 8;
+    if (N == 0) return TQ_OK;
+    if (!ctx) {
+        if (!acc->scored) {
+            if (same) memset(same, 0, bytes);
+            if (both) memset(both, 0, bytes);
+            return TQ_OK;
+        }
+        if (same) memcpy(same, acc->h_same.data(), bytes);
+        if (both) memcpy(both, acc->h_both.data(), bytes);
+        return TQ_OK;
+    }
+    TQ_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = acc->order.last;
+    if (acc->scored && N > QD_BT) {                                 // the tiles below the diagonal, behind the last score
+        hipLaunchKernelGGL(tq_qd_final_kernel, dim3((unsigned)((N * N + QD_THREADS - 1) / QD_THREADS)), dim3(QD_THREADS), 0, st,
+                           acc->d_same.get(), acc->d_both.get(), (int32_t)N);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_qd_read: launch failed: %s", hipGetErrorString(e));
+        TQ_HIP(ctx, acc->order.mark(st));
+    }
+    TQ_HIP(ctx, acc->order.sync());
+    if (same) TQ_HIP(ctx, hipMemcpy(same, acc->d_same, bytes, hipMemcpyDeviceToHost));
+    if (both) TQ_HIP(ctx, hipMemcpy(both, acc->d_both, bytes, hipMemcpyDeviceToHost));
+    return TQ_OK;
+}
+
+int tq_qd_stats(tq_qd *acc, int64_t *out)
+{
+    if (!acc || !out) return TQ_ERR_INVALID_ARG;
+    out[0] = acc->chunk_words * 64;
+    out[1] = acc->chunks;
+    out[2] = acc->kslices;
+    out[3] = acc->tables;
+    out[4] = !acc->ctx ? 0 : acc->T <= FIT_T_LDS ? 1 : 2;
+    out[5] = acc->chunk_words;
+    return TQ_OK;
+}
+
+void tq_qd_word_counts(uint64_t x0, uint64_t x1, uint64_t x2, uint64_t y0, uint64_t y1, uint64_t y2, uint32_t *same,
+                       uint32_t *both)
+{
+    const QdCounts c = qd_word(x0, x1, x2, y0, y1, y2);
+    if (same) *same = c.same;
+    if (both) *both = c.both;
+}
 
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch)
 {
