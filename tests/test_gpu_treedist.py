@@ -223,6 +223,42 @@ def test_refusals_leave_the_device_state_unchanged(engine):
             TreeDistances(bad_T, 4, engine=engine)
 
 
+@pytest.mark.parametrize("bits", [64, 4])
+def test_more_distinct_splits_than_max_splits_is_refused_until_a_reset(engine, bits):
+    """As the host back end (tests/test_treedist_cpu.py): the add that crosses max_splits fails -- a device add when its
+    chunk is drained, here by the read behind it --, every later call fails, a reset makes the accumulator usable.  With
+    64 hash bits the device table itself runs full.  With 4 it holds at most 16 of the 59 splits, the others get
+    their ids from the host map, and that map runs full while the drain walks the chunk's unresolved masks."""
+    from tetrad_amd._lib import TetradHipError
+    T = 33
+    trees, nsplits, shared, rf, _ = dm.set_model(T, T)
+    two = np.ix_([0, 28], [0, 28])
+    distinct = len(dm.splits(trees[0], T) | dm.splits(trees[28], T))
+    assert distinct > 16 and dm.splits(trees[32], T) - dm.splits(trees[0], T) - dm.splits(trees[28], T)
+    engine.set_option("cons_hash_bits", bits)
+    try:
+        with TreeDistances(T, 8, max_splits=distinct, engine=engine) as dev:
+            dev.add_parents([trees[0], trees[28]])
+            dm.assert_matches(dev, nsplits[[0, 28]], shared[two], rf[two])
+            assert dev.ndistinct == distinct
+            with pytest.raises(TetradHipError, match="more than max_splits = %d distinct splits" % distinct) as info:
+                dev.add_parents([trees[32]])                        # brings new splits
+                dev.rf()
+            assert info.value.code == -1
+            with pytest.raises(TetradHipError, match="reset the accumulator"):
+                dev.rf()
+            with pytest.raises(TetradHipError, match="reset the accumulator"):
+                dev.add_parents([trees[0]])
+            st = dev.stats()
+            assert st["hash_bits"] == bits and (bits == 64 or st["dev_entries"] <= 16)
+            dev.reset()
+            dev.add_parents([trees[0], trees[28]])
+            dm.assert_matches(dev, nsplits[[0, 28]], shared[two], rf[two])
+            assert dev.stats()["hash_bits"] == bits
+    finally:
+        engine.set_option("cons_hash_bits", 0)
+
+
 def test_replicate_loop_feeds_both_accumulators(engine):
     """bootstrap_trees(supertree="device", distances=acc, consensus=acc2) on a source of the c1 shape (16 taxa, 5 000
     sites): both accumulators hold the returned trees, as adds made by hand do."""

@@ -23,25 +23,20 @@
 //                         Three wave ballots (code == k) are the three plane words; lanes 0..2 store one each with a
 //                         plain store.  Lanes past the chunk's end vote in no ballot.  Every word of the chunk belongs
 //                         to one wave: no atomics, nothing to clear.
-//   tq_qd_gemm_kernel     the tile structure of tq_rf_gemm_kernel -- 256 threads as 16 x 16, 64 trees x 64 trees, a thread
-//                         owns the 4 x 4 pairs of trees ty + 16 i and tx + 16 j, the words staged in LDS in chunks of
-//                         QD_KW at a pitch of QD_KW + 1 -- with three planes per side (R is made once per staged word in
-//                         registers), two u32 accumulators per pair, and a grid of (upper-triangle tile pairs, k slices):
-//                         a workgroup walks only its slice of the chunk's words.  With one slice a thread adds to same /
-//                         both with a plain read-modify-write (it alone owns the pair; launches follow each other on the
-//                         stream); with more it uses the integer atomicAdd on u64 and skips zeros.
+//   tq_qd_gemm_kernel     the tile product of bit_tile.hpp, 64 trees x 64 trees, with three planes per side, `qd_word`
+//                         as the word rule (R is made once per staged word in registers), two u32 accumulators per pair,
+//                         and a grid of (upper-triangle tile pairs as `bit_tile_pair` numbers them, k slices): a workgroup
+//                         walks only its slice of the chunk's words.  With one slice a thread adds to same / both with a
+//                         plain read-modify-write (it alone owns the pair; launches follow each other on the stream);
+//                         with more it uses the integer atomicAdd on u64 and skips zeros.
 //   tq_qd_final_kernel    at a read: the tiles below the diagonal mirrored from the ones above.
-// LDS of the product: 2 sides x 3 planes x 64 x 9 x 8 = 27 648 bytes.  A u32 accumulator holds at most 64 x the words of
-// one chunk, which create keeps below 2^24.
+// A u32 accumulator holds at most 64 x the words of one chunk, which create keeps below 2^24.
 // No float, no inline assembly, no loop that waits on another lane or workgroup; every loop is bounded by T, N, the
 // words of a chunk or a constant.
 #pragma once
 
-constexpr int QD_THREADS = 256;
-constexpr int QD_BT = 64;                   // trees per tile side
-constexpr int QD_KW = 8;                    // plane words per staged chunk
-constexpr int QD_PITCH = QD_KW + 1;         // words per LDS row
-constexpr int QD_PLANE = QD_BT * QD_PITCH;  // words of one staged plane
+constexpr int QD_THREADS = BT_THREADS;
+constexpr int QD_BT = BT_ROWS;              // trees per tile side
 constexpr int64_t QD_MAX_TREES = 8192;
 constexpr int64_t QD_MAX_CHUNK_WORDS = int64_t(1) << 24;
 constexpr int QD_ENC_WORDS_PER_BLOCK = 256; // plane words (of 64 quartets) an encode workgroup is sized for (unmeasured)
@@ -158,78 +153,37 @@ struct QdGemmArgs {
     const uint64_t *planes;     // [N][3][cw]
     unsigned long long *same, *both;    // [N][N]
     int32_t N, cw, nt;          // trees, words of the chunk, tiles per side
-    int32_t slice_words;        // words a k slice walks, a multiple of QD_KW
+    int32_t slice_words;        // words a k slice walks, a multiple of BT_KW
     int32_t atomic;             // more than one k slice
 };
-
-__device__ __forceinline__ void qd_step(uint32_t (&same)[4][4], uint32_t (&both)[4][4], const uint64_t *rowA, const uint64_t *rowB,
-                                        int k)
-{
-    uint64_t x[4][3], y[4][3], xr[4], yr[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) x[i][p] = rowA[p * QD_PLANE + 16 * i * QD_PITCH + k];
-        xr[i] = x[i][0] | x[i][1] | x[i][2];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) y[j][p] = rowB[p * QD_PLANE + 16 * j * QD_PITCH + k];
-        yr[j] = y[j][0] | y[j][1] | y[j][2];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const QdCounts c = qd_word_r(x[i][0], x[i][1], x[i][2], xr[i], y[j][0], y[j][1], y[j][2], yr[j]);
-            same[i][j] += c.same;
-            both[i][j] += c.both;
-        }
-}
 
 // grid (upper-triangle tile pairs, k slices)
 __global__ __launch_bounds__(QD_THREADS) void tq_qd_gemm_kernel(QdGemmArgs a)
 {
-    __shared__ uint64_t sA[3 * QD_PLANE], sB[3 * QD_PLANE];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int N = a.N;
-    int bi = 0, rest = (int)blockIdx.x;         // row bi of the triangle holds the pairs (bi, bi .. nt - 1)
-    for (int width = a.nt; bi < a.nt - 1 && rest >= width; --width) { rest -= width; ++bi; }
-    const int bj = bi + rest;
-    if (bj >= a.nt) return;                     // never with the grid of nt (nt + 1) / 2
+    int bi, bj;
+    if (!bit_tile_pair((int)blockIdx.x, a.nt, bi, bj)) return;
     const int wbeg = (int)blockIdx.y * a.slice_words;
     const int wend = min(a.cw, wbeg + a.slice_words);
     if (wbeg >= wend) return;                   // never with the slices the host counts
     const int r0 = bi * QD_BT, c0 = bj * QD_BT;
-    const int lr = tid >> 3, lk = tid & 7;      // staging: rows lr and lr + 32, word lk of the chunk, the three planes
-    const uint64_t *rowA = sA + ty * QD_PITCH, *rowB = sB + tx * QD_PITCH;
     uint32_t same[4][4], both[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) same[i][j] = both[i][j] = 0;
-    for (int w0 = wbeg; w0 < wend; w0 += QD_KW) {
-        __syncthreads();                        // the tiles of the step before have been read
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {           // rows past N and words past the slice are zero: they count nothing
-            const int row = lr + 32 * h, w = w0 + lk, r = r0 + row, c = c0 + row;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                sA[p * QD_PLANE + row * QD_PITCH + lk] =
-                    (r < N && w < wend) ? a.planes[((int64_t)r * 3 + p) * a.cw + w] : uint64_t(0);
-                sB[p * QD_PLANE + row * QD_PITCH + lk] =
-                    (c < N && w < wend) ? a.planes[((int64_t)c * 3 + p) * a.cw + w] : uint64_t(0);
-            }
-        }
-        __syncthreads();
-        if (wend - w0 >= QD_KW) {
-#pragma unroll 2                                // 167 VGPRs, 3 waves per SIMD; a full unroll holds 255 and leaves 2
-            for (int k = 0; k < QD_KW; ++k) qd_step(same, both, rowA, rowB, k);
-        } else {
-            for (int k = 0; k < wend - w0; ++k) qd_step(same, both, rowA, rowB, k);
-        }
-    }
+    // rows past N and words past the slice are zero: they count nothing.  The k loop is unrolled twice: 159 VGPRs, 3
+    // waves per SIMD; a full unroll held 255 and left 2 (profiles/qdist/)
+    bit_tile_product<3, 2>(
+        N - r0, N - c0, wbeg, wend,
+        [&](int row, int p, int w) { return a.planes[((int64_t)(r0 + row) * 3 + p) * a.cw + w]; },
+        [&](int row, int p, int w) { return a.planes[((int64_t)(c0 + row) * 3 + p) * a.cw + w]; },
+        [&](int i, int j, const uint64_t (&x)[3], const uint64_t (&y)[3]) {
+            const QdCounts c = qd_word(x[0], x[1], x[2], y[0], y[1], y[2]);
+            same[i][j] += c.same;
+            both[i][j] += c.both;
+        });
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = r0 + ty + 16 * i;

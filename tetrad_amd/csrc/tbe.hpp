@@ -15,27 +15,16 @@
 //
 // Device layout (all of it allocated at create): a chunk of prepared trees is staged through a page-locked buffer,
 // `tq_cons_mask_kernel` (consensus.hpp, unchanged) fills the chunk's [chunk][T - 2][W] masks, and behind it on the stream
-//   tq_tbe_kernel   grid (replicate of the chunk, tile of TBE_BE branches), 256 threads as 16 x 16.  A binary GEMM: the
-//                   workgroup walks the replicate's M nodes (M from the tree's record; rows v >= M of the scratch hold
-//                   an earlier chunk's masks and are never read) in tiles of TBE_BN, the words in chunks of TBE_KW.
-//                   Both operand tiles are staged in LDS row-major with a pitch of TBE_KW + 1 words; a thread owns
-//                   the 4 x 4 distances of branches ty + 16 i and nodes tx + 16 j.  After the last word chunk delta
-//                   is folded into 4 running minima, after the last node tile the minima are reduced over the 16
-//                   lanes that share the branches (shuffles), clamped to p - 1, added to phi_sum with one 64-bit
-//                   integer atomic per (branch, replicate) and, when asked for, stored as u16 phi[replicate][branch].
-// Tile sizes: 64 x 64 x 8 words makes 2 x 64 x 9 x 8 = 9 216 bytes of LDS (no limit on the workgroups of a CU) and 16
-// accumulators per thread; with the operand words of the unrolled chunk in flight the kernel takes 92 VGPRs, 5 waves
-// per SIMD.  Per word a thread issues 8 ds_read_b64 for 16 xor + popcount pairs (64 VALU operations), so the vector
-// ALU, not the LDS, sets the pace.  The pitch of 9 words puts the 16 rows tx + 16 j a half-wave reads (bytes 72 tx) on
-// 16 different even bank pairs; the rows ty + 16 i of a wave are 4 broadcasts.
+//   tq_tbe_kernel   grid (replicate of the chunk, tile of 64 branches): the tile product of bit_tile.hpp with the
+//                   branches as A, the replicate's M nodes as B (M from the tree's record; rows v >= M of the scratch
+//                   hold an earlier chunk's masks and are never read) and `tbe_word_distance` as the word rule.  The
+//                   workgroup walks the nodes in tiles of 64; after the last word of a tile delta is folded into 4
+//                   running minima, after the last node tile the minima are reduced over the 16 lanes that share the
+//                   branches (shuffles), clamped to p - 1, added to phi_sum with one 64-bit integer atomic per
+//                   (branch, replicate) and, when asked for, stored as u16 phi[replicate][branch].
+// With the operand words of the unrolled chunk in flight the kernel takes 92 VGPRs, 5 waves per SIMD.
 // No float, no loop that waits on another lane or workgroup, every loop bounded by T, W or a constant.
 #pragma once
-
-constexpr int TBE_THREADS = 256;
-constexpr int TBE_BE = 64;                  // reference branches per workgroup
-constexpr int TBE_BN = 64;                  // replicate nodes per tile
-constexpr int TBE_KW = 8;                   // mask words per staged chunk
-constexpr int TBE_PITCH = TBE_KW + 1;       // words per LDS row
 
 // d of one word; d of two masks is the sum over their W words
 __host__ __device__ __forceinline__ uint32_t tbe_word_distance(uint64_t x, uint64_t y)
@@ -102,54 +91,27 @@ struct TbeArgs {
     int32_t T, W, E;
 };
 
-__device__ __forceinline__ void tbe_step(uint32_t (&acc)[4][4], const uint64_t *rowA, const uint64_t *rowB, int k)
+__global__ __launch_bounds__(BT_THREADS) void tq_tbe_kernel(TbeArgs a)
 {
-    uint64_t x[4], y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x[i] = rowA[16 * i * TBE_PITCH + k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = rowB[16 * j * TBE_PITCH + k];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += tbe_word_distance(x[i], y[j]);
-}
-
-__global__ __launch_bounds__(TBE_THREADS) void tq_tbe_kernel(TbeArgs a)
-{
-    __shared__ uint64_t sA[TBE_BE * TBE_PITCH], sB[TBE_BN * TBE_PITCH];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int T = a.T, W = a.W, E = a.E;
-    const int e0 = blockIdx.y * TBE_BE;
+    const int e0 = blockIdx.y * BT_ROWS;
     const int M = min(a.trees[(int64_t)blockIdx.x * cons_stride(T)], T - 2);
     const uint64_t *nodes = a.masks + (int64_t)blockIdx.x * (T - 2) * W;
-    const int lr = tid >> 3, lk = tid & 7;      // staging: rows lr and lr + 32, word lk of the chunk
-    const uint64_t *rowA = sA + ty * TBE_PITCH, *rowB = sB + tx * TBE_PITCH;
     uint32_t best[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) best[i] = (uint32_t)T;
-    for (int v0 = 0; v0 < M; v0 += TBE_BN) {
+    for (int v0 = 0; v0 < M; v0 += BT_ROWS) {
         uint32_t acc[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-        for (int w0 = 0; w0 < W; w0 += TBE_KW) {
-            __syncthreads();                    // the tiles of the step before have been read
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {       // rows past E or M and words past W are zero: they add nothing to d
-                const int row = lr + 32 * h, w = w0 + lk, e = e0 + row, v = v0 + row;
-                sA[row * TBE_PITCH + lk] = (e < E && w < W) ? a.ref[(int64_t)e * W + w] : uint64_t(0);
-                sB[row * TBE_PITCH + lk] = (v < M && w < W) ? nodes[(int64_t)v * W + w] : uint64_t(0);
-            }
-            __syncthreads();
-            if (W - w0 >= TBE_KW) {
-#pragma unroll
-                for (int k = 0; k < TBE_KW; ++k) tbe_step(acc, rowA, rowB, k);
-            } else {
-                for (int k = 0; k < W - w0; ++k) tbe_step(acc, rowA, rowB, k);
-            }
-        }
+        bit_tile_product<1, BT_KW>(
+            E - e0, M - v0, 0, W,               // rows past E or M and words past W are zero: they add nothing to d
+            [&](int row, int, int w) { return a.ref[(int64_t)(e0 + row) * W + w]; },
+            [&](int row, int, int w) { return nodes[(int64_t)(v0 + row) * W + w]; },
+            [&](int i, int j, const uint64_t (&x)[1], const uint64_t (&y)[1]) { acc[i][j] += tbe_word_distance(x[0], y[0]); });
         // a zero row (v >= M) gives delta = p >= p - 1: it never lowers the clamped minimum
 #pragma unroll
         for (int i = 0; i < 4; ++i)

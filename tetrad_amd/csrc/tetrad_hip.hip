@@ -38,6 +38,9 @@
 //   fit.hpp       tq_fit_*_kernel: LCA-depth tables of candidate trees, quartet fit of the supertree's kept rows against them
 //   nni.hpp       tq_nni_*_kernel: the quartet-fit weights of every nearest-neighbour interchange of a tree in one row pass; the polish search
 //   consensus.hpp tq_cons_*_kernel: split masks of many trees, exact split counts in a hash table (majority-rule consensus)
+//   split_table.hpp (host) TreeChunk and SplitTable: the staged chunk of trees and the split table that the accumulators
+//                 of consensus.hpp, tbe.hpp and treedist.hpp share (included below StreamOrder, not with the kernels)
+//   bit_tile.hpp  bit_tile_product: the 64 x 64 tile product on bit rows inside the product kernels of the next three
 //   tbe.hpp       tq_tbe_kernel: transfer distances of a reference tree's branches to every node of many trees (TBE)
 //   treedist.hpp  tq_rf_*_kernel: split ids, bit rows and their product: all-pairs Robinson-Foulds distances of a tree set
 //   qdist.hpp     tq_qd_*_kernel: quartet topology planes of every tree and their product: all-pairs quartet distances of a tree set
@@ -96,6 +99,7 @@ namespace {
 #include "species.hpp"
 #include "supertree.hpp"
 #include "consensus.hpp"
+#include "bit_tile.hpp"
 #include "tbe.hpp"
 #include "treedist.hpp"
 #include "fit.hpp"
@@ -1679,12 +1683,24 @@ int blocks_dev(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *d_s
 // operation but the row kernel and the layout of a read.
 // ---------------------------------------------------------------------------------------------
 
-// The event behind the last device work of an accumulator (its owner creates and destroys `ev`): an enqueue on
-// another stream first waits for it, a read or reset synchronises on it.
+// The event behind the last device work of an accumulator: an enqueue on another stream first waits for it, a read or
+// reset synchronises on it.  The owner calls create() with its device selected and finish() in its destructor's body.
 struct StreamOrder {
     hipEvent_t ev = nullptr;        // recorded behind the last device work
     bool pending = false;
     hipStream_t last = nullptr;
+    hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+    // The end of an owner on `ctx` (NULL: a host back end, nothing to do): device selected, the work waited for, the
+    // event destroyed.  A destructor's body runs before its members' destructors, so the owner's buffers are freed
+    // behind this.
+    void finish(const tq_ctx *ctx)
+    {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)sync();
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
     hipError_t join(hipStream_t st) { return pending && st != last ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
     hipError_t mark(hipStream_t st)
     {
@@ -1713,13 +1729,7 @@ struct TreeAcc {
     StreamOrder order;              // of the device adds
     TreeAcc() = default;
     TreeAcc(const TreeAcc &) = delete;
-    ~TreeAcc()                      // the body runs before the buffers' destructors: device selected, adds finished
-    {
-        if (!ctx) return;
-        (void)hipSetDevice(ctx->device);
-        (void)order.sync();
-        if (order.ev) (void)hipEventDestroy(order.ev);
-    }
+    ~TreeAcc() { order.finish(ctx); }
 };
 
 }  // namespace
@@ -1762,7 +1772,7 @@ int tree_acc_init(TreeAcc *acc, const char *who, const int32_t *parent, int64_t 
     if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->order.ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = acc->order.create();
     if (e != hipSuccess)
         return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return TQ_OK;
@@ -1842,6 +1852,8 @@ int tree_acc_add_dev(TreeAcc *acc, const char *who, int64_t n, int32_t f64_edges
     return TQ_OK;
 }
 
+#include "split_table.hpp"     // TreeChunk and SplitTable of the accumulators over sets of trees below
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1850,141 +1862,74 @@ int tree_acc_add_dev(TreeAcc *acc, const char *who, int64_t n, int32_t f64_edges
 // ---------------------------------------------------------------------------------------------
 struct tq_cons {
     tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
-    int32_t T = 0, W = 0, G = 1;
-    uint64_t tail = 0;
-    int64_t max_splits = 0, ntrees = 0;
-    ConsMap host;                   // host adds; with a context the unresolved splits of the device adds
-    bool overflow = false;          // more distinct splits than max_splits were offered: unusable until a reset
+    TreeChunk chunk;                // T, W and the device back end's chunk of trees
+    SplitTable table;               // host adds; with a context the device table and the unresolved splits of its adds
+    int64_t ntrees = 0;
     bool table_ok = false;          // tmasks / tcounts hold the canonical table of everything added
     std::vector<uint64_t> tmasks;
     std::vector<int64_t> tcounts;
-    // device back end
-    int hash_bits = 64;
-    int64_t chunk_trees = 0, slots = 0, gather_cap = 0;
-    PinnedBuf<int32_t> p_trees;
-    DevBuf<int32_t> d_trees, d_slot_idx;
-    DevBuf<uint64_t> d_masks, d_keys, d_rep, d_gather;
-    PinnedBuf<uint64_t> p_gather;
-    DevBuf<unsigned long long> d_slot_key, d_count;
-    DevBuf<unsigned int> d_ctr;
-    PinnedBuf<unsigned int> p_ctr;
-    DevBuf<uint32_t> d_unres;
     StreamOrder order;              // behind the last chunk
-    int64_t dev_entries = 0;        // entries of the device table after the last finished chunk
-    int64_t chunks = 0, unresolved = 0;
     tq_cons() = default;
     tq_cons(const tq_cons &) = delete;
-    ~tq_cons()                      // runs before the buffers' destructors: device selected, last chunk finished
-    {
-        if (!ctx) return;
-        (void)hipSetDevice(ctx->device);
-        (void)order.sync();
-        if (order.ev) (void)hipEventDestroy(order.ev);
-    }
+    ~tq_cons() { order.finish(ctx); }
 };
 
 namespace {
 
-int cons_overflow(tq_cons *a, const char *who)
-{
-    a->overflow = true;
-    return fail(a->ctx, TQ_ERR_INVALID_ARG, "%s: more than max_splits = %lld distinct splits; reset the accumulator", who,
-                (long long)a->max_splits);
-}
-
-ConsArgs cons_args(const tq_cons *a, int64_t ntrees)
-{
-    ConsArgs p{};
-    p.trees = a->d_trees; p.masks = a->d_masks; p.keys = a->d_keys;
-    p.items = ntrees * (a->T - 2);
-    p.T = a->T; p.W = a->W; p.G = a->G; p.hash_bits = a->hash_bits; p.tail = a->tail;
-    p.slot_key = a->d_slot_key; p.slot_idx = a->d_slot_idx; p.rep = a->d_rep; p.count = a->d_count; p.ctr = a->d_ctr;
-    p.unres = a->d_unres; p.slot_mask = a->slots - 1; p.max_splits = a->max_splits;
-    return p;
-}
-
-// empty table (also the reset): keys CONS_EMPTY (all bits set), slot entries -1, counts and counters 0
-int cons_clear_dev(tq_cons *a)
-{
-    tq_ctx *ctx = a->ctx;
-    TQ_HIP(ctx, hipMemset(a->d_slot_key, 0xFF, (size_t)a->slots * 8));
-    TQ_HIP(ctx, hipMemset(a->d_slot_idx, 0xFF, (size_t)a->slots * 4));
-    TQ_HIP(ctx, hipMemset(a->d_count, 0, (size_t)a->max_splits * 8));
-    TQ_HIP(ctx, hipMemset(a->d_ctr, 0, CONS_CTR_WORDS * 4));
-    TQ_HIP(ctx, hipDeviceSynchronize());
-    return TQ_OK;
-}
-
-// Waits for the last chunk, reads its counters and counts its unresolved splits in the host map.
+// Waits for the last chunk and counts its unresolved splits in the host map.
 int cons_drain(tq_cons *a)
 {
-    if (!a->order.pending) return TQ_OK;
-    tq_ctx *ctx = a->ctx;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    TQ_HIP(ctx, a->order.sync());
-    a->dev_entries = std::min<int64_t>((int64_t)a->p_ctr[CONS_CTR_CLAIMS], a->max_splits);
-    if (a->p_ctr[CONS_CTR_OVERFLOW]) return cons_overflow(a, "tq_cons");
-    const int64_t nun = (int64_t)a->p_ctr[CONS_CTR_UNRES];
-    std::vector<uint64_t> m((size_t)a->W);
-    for (int64_t first = 0; first < nun; first += a->gather_cap) {
-        const int64_t n = std::min<int64_t>(a->gather_cap, nun - first);
-        hipLaunchKernelGGL(tq_cons_gather_kernel, dim3((unsigned)((n * a->W + CONS_THREADS - 1) / CONS_THREADS)),
-                           dim3(CONS_THREADS), 0, a->order.last, (const uint32_t *)a->d_unres, first, n,
-                           (const uint64_t *)a->d_masks, a->W, a->d_gather);
-        TQ_HIP(ctx, hipGetLastError());
-        TQ_HIP(ctx, hipMemcpyAsync(a->p_gather, a->d_gather, (size_t)n * a->W * 8, hipMemcpyDeviceToHost, a->order.last));
-        TQ_HIP(ctx, hipStreamSynchronize(a->order.last));
-        for (int64_t e = 0; e < n; ++e) {
-            m.assign(a->p_gather + e * a->W, a->p_gather + (e + 1) * a->W);
-            ++a->host[m];
-        }
-    }
-    a->unresolved += nun;
-    if (a->dev_entries + (int64_t)a->host.size() > a->max_splits) return cons_overflow(a, "tq_cons");
-    return TQ_OK;
+    int64_t nun;
+    return a->table.drain(a->ctx, "tq_cons", a->order, a->chunk.d_masks, nun, [a](int64_t, const std::vector<uint64_t> &m) {
+        ++a->table.host[m];
+        return true;
+    });
 }
 
-// One chunk of prepared records (already in the page-locked buffer) through the three kernels on `st`.
-int cons_launch(tq_cons *a, int64_t ntrees, hipStream_t st)
+// One chunk of n prepared records through the three kernels on `st`.
+int cons_launch(tq_cons *a, int64_t n, const int32_t *recs, hipStream_t st)
 {
     tq_ctx *ctx = a->ctx;
-    const ConsArgs p = cons_args(a, ntrees);
-    TQ_HIP(ctx, hipMemcpyAsync(a->d_trees, a->p_trees, (size_t)ntrees * cons_stride(a->T) * 4, hipMemcpyHostToDevice, st));
-    TQ_HIP(ctx, hipMemsetAsync(a->d_ctr + CONS_CTR_UNRES, 0, 4, st));
-    const unsigned blocks = (unsigned)((p.items * a->G + CONS_THREADS - 1) / CONS_THREADS);
-    hipLaunchKernelGGL(tq_cons_mask_kernel, dim3((unsigned)ntrees), dim3(CONS_THREADS), 0, st, p);
+    ConsArgs p{};
+    a->chunk.fill(p, n);
+    a->table.fill(p);
+    TQ_HIP(ctx, a->chunk.stage(n, recs, st, p));
+    TQ_HIP(ctx, a->table.begin_chunk(st));
+    const unsigned blocks = (unsigned)((p.items * p.G + CONS_THREADS - 1) / CONS_THREADS);
     hipLaunchKernelGGL(tq_cons_insert_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
     hipLaunchKernelGGL(tq_cons_count_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_cons_add: launch failed: %s", hipGetErrorString(e));
-    TQ_HIP(ctx, hipMemcpyAsync(a->p_ctr, a->d_ctr, CONS_CTR_WORDS * 4, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, a->table.end_chunk(st));
     TQ_HIP(ctx, a->order.mark(st));
-    ++a->chunks;
+    ++a->chunk.chunks;
     return TQ_OK;
 }
 
 // The canonical table of everything added (cached until the next add / reset).
 int cons_table(tq_cons *a, const char *who)
 {
-    if (a->overflow) return cons_overflow(a, who);
+    SplitTable &t = a->table;
+    const int32_t W = a->chunk.W;
+    if (t.overflow) return t.overflowed(a->ctx, who);
     if (a->ctx)
         if (int rc = cons_drain(a)) return rc;
     if (a->table_ok) return TQ_OK;
-    if (!a->ctx || a->dev_entries == 0) {
-        cons_sorted_table(a->host, a->W, a->tmasks, a->tcounts);
+    if (!a->ctx || t.dev_entries == 0) {
+        cons_sorted_table(t.host, W, a->tmasks, a->tcounts);
     } else {
-        const int64_t n = a->dev_entries;
-        std::vector<uint64_t> rep((size_t)n * a->W), cnt((size_t)n);
+        const int64_t n = t.dev_entries;
+        std::vector<uint64_t> rep((size_t)n * W), cnt((size_t)n);
         TQ_HIP(a->ctx, hipSetDevice(a->ctx->device));
-        TQ_HIP(a->ctx, hipMemcpy(rep.data(), a->d_rep, rep.size() * 8, hipMemcpyDeviceToHost));
-        TQ_HIP(a->ctx, hipMemcpy(cnt.data(), a->d_count, cnt.size() * 8, hipMemcpyDeviceToHost));
-        ConsMap all = a->host;
-        std::vector<uint64_t> m((size_t)a->W);
+        TQ_HIP(a->ctx, hipMemcpy(rep.data(), t.d_rep, rep.size() * 8, hipMemcpyDeviceToHost));
+        TQ_HIP(a->ctx, hipMemcpy(cnt.data(), t.d_count, cnt.size() * 8, hipMemcpyDeviceToHost));
+        ConsMap all = t.host;
+        std::vector<uint64_t> m((size_t)W);
         for (int64_t e = 0; e < n; ++e) {
-            m.assign(rep.begin() + e * a->W, rep.begin() + (e + 1) * a->W);
+            m.assign(rep.begin() + e * W, rep.begin() + (e + 1) * W);
             all[m] += (int64_t)cnt[e];
         }
-        cons_sorted_table(all, a->W, a->tmasks, a->tcounts);
+        cons_sorted_table(all, W, a->tmasks, a->tcounts);
     }
     a->table_ok = true;
     return TQ_OK;
@@ -1998,57 +1943,44 @@ int cons_table(tq_cons *a, const char *who)
 // ---------------------------------------------------------------------------------------------
 struct tq_tbe {
     tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
-    int32_t T = 0, W = 0, G = 1;
-    uint64_t tail = 0;
+    TreeChunk chunk;                // T, W and the device back end's chunk of trees
     int64_t E = 0, ntrees = 0;
     std::vector<uint64_t> masks;    // [E][W] ascending
     std::vector<int32_t> p;         // [E]
     std::vector<uint64_t> phi_sum;  // host back end
     // device back end
-    int64_t chunk_trees = 0, chunks = 0;
-    PinnedBuf<int32_t> p_trees;
     PinnedBuf<uint16_t> p_phi;
-    DevBuf<int32_t> d_trees, d_p;
-    DevBuf<uint64_t> d_masks, d_keys, d_ref;
+    DevBuf<int32_t> d_p;
+    DevBuf<uint64_t> d_ref;
     DevBuf<unsigned long long> d_phi_sum;
     DevBuf<uint16_t> d_phi;
     StreamOrder order;              // behind the last chunk
     tq_tbe() = default;
     tq_tbe(const tq_tbe &) = delete;
-    ~tq_tbe()                       // runs before the buffers' destructors: device selected, last chunk finished
-    {
-        if (!ctx) return;
-        (void)hipSetDevice(ctx->device);
-        (void)order.sync();
-        if (order.ev) (void)hipEventDestroy(order.ev);
-    }
+    ~tq_tbe() { order.finish(ctx); }
 };
 
 namespace {
 
-// One chunk of prepared records (already in the page-locked buffer): the masks by tq_cons_mask_kernel, then the
-// distances, on `st`.  With `want_phi` the chunk's phi rows follow into the page-locked buffer.
-int tbe_launch(tq_tbe *a, int64_t ntrees, hipStream_t st, bool want_phi)
+// One chunk of n prepared records: the masks, then the distances, on `st`.  With `want_phi` the chunk's phi rows
+// follow into the page-locked buffer.
+int tbe_launch(tq_tbe *a, int64_t n, const int32_t *recs, hipStream_t st, bool want_phi)
 {
     tq_ctx *ctx = a->ctx;
-    ConsArgs c{};
-    c.trees = a->d_trees; c.masks = a->d_masks; c.keys = a->d_keys;
-    c.items = ntrees * (a->T - 2);
-    c.T = a->T; c.W = a->W; c.G = a->G; c.hash_bits = 64; c.tail = a->tail;
+    const TreeChunk &c = a->chunk;
+    ConsArgs p{};
+    c.fill(p, n);
     TbeArgs t{};
-    t.trees = a->d_trees; t.masks = a->d_masks; t.ref = a->d_ref; t.p = a->d_p; t.phi_sum = a->d_phi_sum;
+    t.trees = c.d_trees; t.masks = c.d_masks; t.ref = a->d_ref; t.p = a->d_p; t.phi_sum = a->d_phi_sum;
     t.phi = want_phi ? a->d_phi.get() : nullptr;
-    t.T = a->T; t.W = a->W; t.E = (int32_t)a->E;
-    TQ_HIP(ctx, hipMemcpyAsync(a->d_trees, a->p_trees, (size_t)ntrees * cons_stride(a->T) * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(tq_cons_mask_kernel, dim3((unsigned)ntrees), dim3(CONS_THREADS), 0, st, c);
-    hipLaunchKernelGGL(tq_tbe_kernel, dim3((unsigned)ntrees, (unsigned)((a->E + TBE_BE - 1) / TBE_BE)), dim3(TBE_THREADS), 0,
-                       st, t);
+    t.T = c.T; t.W = c.W; t.E = (int32_t)a->E;
+    TQ_HIP(ctx, a->chunk.stage(n, recs, st, p));
+    hipLaunchKernelGGL(tq_tbe_kernel, dim3((unsigned)n, (unsigned)((a->E + BT_ROWS - 1) / BT_ROWS)), dim3(BT_THREADS), 0, st, t);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_tbe_add: launch failed: %s", hipGetErrorString(e));
-    if (want_phi)
-        TQ_HIP(ctx, hipMemcpyAsync(a->p_phi, a->d_phi, (size_t)ntrees * a->E * 2, hipMemcpyDeviceToHost, st));
+    if (want_phi) TQ_HIP(ctx, hipMemcpyAsync(a->p_phi, a->d_phi, (size_t)n * a->E * 2, hipMemcpyDeviceToHost, st));
     TQ_HIP(ctx, a->order.mark(st));
-    ++a->chunks;
+    ++a->chunk.chunks;
     return TQ_OK;
 }
 
@@ -2061,140 +1993,94 @@ int tbe_launch(tq_tbe *a, int64_t ntrees, hipStream_t st, bool want_phi)
 // ---------------------------------------------------------------------------------------------
 struct tq_rf {
     tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
-    int32_t T = 0, W = 0, G = 1;
-    uint64_t tail = 0;
-    int64_t max_trees = 0, max_splits = 0, ntrees = 0;
-    ConsMap host;                   // mask -> id (host back end) or -> k, the id being max_splits - 1 - k (device)
+    TreeChunk chunk;                // T, W and the device back end's chunk of trees
+    SplitTable table;               // host: mask -> id (host back end) or -> k, the id being max_splits - 1 - k (device)
+    int64_t max_trees = 0, ntrees = 0;
     std::vector<int64_t> host_count;        // [id or k] trees that hold it
     std::vector<std::vector<uint32_t>> lists;       // host back end: the ascending ids of every tree
-    bool overflow = false;          // more distinct splits than max_splits were offered: unusable until a reset
     bool final_ok = false;          // the matrices below / on the device are those of everything added
     std::vector<int32_t> h_nsplits; // host back end results
     std::vector<uint32_t> h_shared, h_rf;
     int64_t columns = 0, col_chunks = 0;    // of the last read
     // device back end
-    int hash_bits = 64;
-    int64_t chunk_trees = 0, slots = 0, gather_cap = 0, cw_chunk = 0;
+    int64_t cw_chunk = 0;
     int64_t chunk_base = 0;         // first tree of the chunk in flight
-    PinnedBuf<int32_t> p_trees;
-    DevBuf<int32_t> d_trees, d_slot_idx, d_nsplits;
-    DevBuf<uint64_t> d_masks, d_keys, d_rep, d_gather;
-    PinnedBuf<uint64_t> p_gather;
-    DevBuf<unsigned long long> d_slot_key, d_count, d_bits;
-    DevBuf<unsigned int> d_ctr;
-    PinnedBuf<unsigned int> p_ctr;
-    DevBuf<uint32_t> d_unres, d_newid, d_ids, d_colmap, d_shared, d_rf;
+    DevBuf<int32_t> d_nsplits;
+    DevBuf<unsigned long long> d_bits;
+    DevBuf<uint32_t> d_newid, d_ids, d_colmap, d_shared, d_rf;
     PinnedBuf<uint32_t> p_newid;
     StreamOrder order;              // behind the last chunk
-    int64_t dev_entries = 0;        // entries of the device table after the last finished chunk
-    int64_t chunks = 0, unresolved = 0;
     tq_rf() = default;
     tq_rf(const tq_rf &) = delete;
-    ~tq_rf()                        // runs before the buffers' destructors: device selected, last chunk finished
-    {
-        if (!ctx) return;
-        (void)hipSetDevice(ctx->device);
-        (void)order.sync();
-        if (order.ev) (void)hipEventDestroy(order.ev);
-    }
+    ~tq_rf() { order.finish(ctx); }
 };
 
 namespace {
 
-int rf_overflow(tq_rf *a, const char *who)
+// the id of a split in the host map, which has room for `room` of them: a new split takes the next number; one more
+// tree holds it.  NULL when the map is full.
+const int64_t *rf_host_id(tq_rf *a, const std::vector<uint64_t> &m, int64_t room)
 {
-    a->overflow = true;
-    return fail(a->ctx, TQ_ERR_INVALID_ARG, "%s: more than max_splits = %lld distinct splits; reset the accumulator", who,
-                (long long)a->max_splits);
-}
-
-ConsArgs rf_cons_args(const tq_rf *a, int64_t ntrees)
-{
-    ConsArgs p{};
-    p.trees = a->d_trees; p.masks = a->d_masks; p.keys = a->d_keys;
-    p.items = ntrees * (a->T - 2);
-    p.T = a->T; p.W = a->W; p.G = a->G; p.hash_bits = a->hash_bits; p.tail = a->tail;
-    p.slot_key = a->d_slot_key; p.slot_idx = a->d_slot_idx; p.rep = a->d_rep; p.count = a->d_count; p.ctr = a->d_ctr;
-    p.unres = a->d_unres; p.slot_mask = a->slots - 1; p.max_splits = a->max_splits;
-    return p;
+    auto it = a->table.host.find(m);
+    if (it == a->table.host.end()) {
+        if ((int64_t)a->table.host.size() >= room) return nullptr;
+        it = a->table.host.emplace(m, (int64_t)a->table.host.size()).first;
+        a->host_count.push_back(0);
+    }
+    ++a->host_count[(size_t)it->second];
+    return &it->second;
 }
 
 // empty table and no trees (also the reset).  ids, bit rows and matrices need no clearing: a read uses the rows of the
 // trees added since, all of which an add has written.
 int rf_clear_dev(tq_rf *a)
 {
-    tq_ctx *ctx = a->ctx;
-    TQ_HIP(ctx, hipMemset(a->d_slot_key, 0xFF, (size_t)a->slots * 8));
-    TQ_HIP(ctx, hipMemset(a->d_slot_idx, 0xFF, (size_t)a->slots * 4));
-    TQ_HIP(ctx, hipMemset(a->d_count, 0, (size_t)a->max_splits * 8));
-    TQ_HIP(ctx, hipMemset(a->d_nsplits, 0, (size_t)a->max_trees * 4));
-    TQ_HIP(ctx, hipMemset(a->d_ctr, 0, CONS_CTR_WORDS * 4));
-    TQ_HIP(ctx, hipDeviceSynchronize());
-    return TQ_OK;
+    TQ_HIP(a->ctx, hipMemset(a->d_nsplits, 0, (size_t)a->max_trees * 4));
+    return a->table.clear(a->ctx);
 }
 
-// Waits for the last chunk, reads its counters, gives its unresolved splits their ids from the host map and stores them.
+// Waits for the last chunk, gives its unresolved splits their ids from the host map and stores them.
 int rf_drain(tq_rf *a)
 {
-    if (!a->order.pending) return TQ_OK;
     tq_ctx *ctx = a->ctx;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    TQ_HIP(ctx, a->order.sync());
-    a->dev_entries = std::min<int64_t>((int64_t)a->p_ctr[CONS_CTR_CLAIMS], a->max_splits);
-    if (a->p_ctr[CONS_CTR_OVERFLOW]) return rf_overflow(a, "tq_rf");
-    const int64_t nun = (int64_t)a->p_ctr[CONS_CTR_UNRES];
+    SplitTable &t = a->table;
+    int64_t nun;
+    if (int rc = t.drain(ctx, "tq_rf", a->order, a->chunk.d_masks, nun, [a, &t](int64_t u, const std::vector<uint64_t> &m) {
+            const int64_t *k = rf_host_id(a, m, t.max_splits - t.dev_entries);
+            if (k) a->p_newid[u] = (uint32_t)(t.max_splits - 1 - *k);
+            return k != nullptr;
+        }))
+        return rc;
     if (nun == 0) return TQ_OK;
     hipStream_t st = a->order.last;
-    std::vector<uint64_t> m((size_t)a->W);
-    for (int64_t first = 0; first < nun; first += a->gather_cap) {
-        const int64_t n = std::min<int64_t>(a->gather_cap, nun - first);
-        hipLaunchKernelGGL(tq_cons_gather_kernel, dim3((unsigned)((n * a->W + CONS_THREADS - 1) / CONS_THREADS)),
-                           dim3(CONS_THREADS), 0, st, (const uint32_t *)a->d_unres, first, n, (const uint64_t *)a->d_masks,
-                           a->W, a->d_gather);
-        TQ_HIP(ctx, hipGetLastError());
-        TQ_HIP(ctx, hipMemcpyAsync(a->p_gather, a->d_gather, (size_t)n * a->W * 8, hipMemcpyDeviceToHost, st));
-        TQ_HIP(ctx, hipStreamSynchronize(st));
-        for (int64_t e = 0; e < n; ++e) {
-            m.assign(a->p_gather + e * a->W, a->p_gather + (e + 1) * a->W);
-            auto it = a->host.find(m);
-            if (it == a->host.end()) {
-                if (a->dev_entries + (int64_t)a->host.size() >= a->max_splits) return rf_overflow(a, "tq_rf");
-                it = a->host.emplace(m, (int64_t)a->host.size()).first;
-                a->host_count.push_back(0);
-            }
-            ++a->host_count[(size_t)it->second];
-            a->p_newid[first + e] = (uint32_t)(a->max_splits - 1 - it->second);
-        }
-    }
     RfIdentArgs r{a->d_ids, a->d_nsplits, a->chunk_base};
     TQ_HIP(ctx, hipMemcpyAsync(a->d_newid, a->p_newid, (size_t)nun * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(tq_rf_patch_kernel, dim3((unsigned)((nun + CONS_THREADS - 1) / CONS_THREADS)), dim3(CONS_THREADS), 0, st,
-                       (const uint32_t *)a->d_unres, (const uint32_t *)a->d_newid, nun, r, a->T - 2);
+                       (const uint32_t *)t.d_unres, (const uint32_t *)a->d_newid, nun, r, a->chunk.T - 2);
     TQ_HIP(ctx, hipGetLastError());
     TQ_HIP(ctx, hipStreamSynchronize(st));
-    a->unresolved += nun;
-    if (a->dev_entries + (int64_t)a->host.size() > a->max_splits) return rf_overflow(a, "tq_rf");
     return TQ_OK;
 }
 
-// One chunk of prepared records (already in the page-locked buffer), trees first .. first + ntrees - 1, on `st`.
-int rf_launch(tq_rf *a, int64_t first, int64_t ntrees, hipStream_t st)
+// One chunk of n prepared records, trees first .. first + n - 1, on `st`.
+int rf_launch(tq_rf *a, int64_t first, int64_t n, const int32_t *recs, hipStream_t st)
 {
     tq_ctx *ctx = a->ctx;
-    const ConsArgs p = rf_cons_args(a, ntrees);
+    ConsArgs p{};
+    a->chunk.fill(p, n);
+    a->table.fill(p);
     const RfIdentArgs r{a->d_ids, a->d_nsplits, first};
-    TQ_HIP(ctx, hipMemcpyAsync(a->d_trees, a->p_trees, (size_t)ntrees * cons_stride(a->T) * 4, hipMemcpyHostToDevice, st));
-    TQ_HIP(ctx, hipMemsetAsync(a->d_ctr + CONS_CTR_UNRES, 0, 4, st));
-    const unsigned blocks = (unsigned)((p.items * a->G + CONS_THREADS - 1) / CONS_THREADS);
-    hipLaunchKernelGGL(tq_cons_mask_kernel, dim3((unsigned)ntrees), dim3(CONS_THREADS), 0, st, p);
+    TQ_HIP(ctx, a->chunk.stage(n, recs, st, p));
+    TQ_HIP(ctx, a->table.begin_chunk(st));
+    const unsigned blocks = (unsigned)((p.items * p.G + CONS_THREADS - 1) / CONS_THREADS);
     hipLaunchKernelGGL(tq_cons_insert_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
     hipLaunchKernelGGL(tq_rf_ident_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p, r);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_rf_add: launch failed: %s", hipGetErrorString(e));
-    TQ_HIP(ctx, hipMemcpyAsync(a->p_ctr, a->d_ctr, CONS_CTR_WORDS * 4, hipMemcpyDeviceToHost, st));
+    TQ_HIP(ctx, a->table.end_chunk(st));
     TQ_HIP(ctx, a->order.mark(st));
     a->chunk_base = first;
-    ++a->chunks;
+    ++a->chunk.chunks;
     return TQ_OK;
 }
 
@@ -2224,11 +2110,12 @@ void rf_host_final(tq_rf *a)
 int rf_dev_final(tq_rf *a)
 {
     tq_ctx *ctx = a->ctx;
-    const int64_t N = a->ntrees, nd = a->dev_entries, nh = (int64_t)a->host_count.size();
+    const int64_t N = a->ntrees, nd = a->table.dev_entries, nh = (int64_t)a->host_count.size();
+    const int64_t max_splits = a->table.max_splits, nodes = a->chunk.nodes();
     TQ_HIP(ctx, hipSetDevice(ctx->device));
     // columns in entry order: the device entries, then the host's
     std::vector<unsigned long long> cnt((size_t)nd);
-    if (nd) TQ_HIP(ctx, hipMemcpy(cnt.data(), a->d_count, (size_t)nd * 8, hipMemcpyDeviceToHost));
+    if (nd) TQ_HIP(ctx, hipMemcpy(cnt.data(), a->table.d_count, (size_t)nd * 8, hipMemcpyDeviceToHost));
     std::vector<uint32_t> dev_col((size_t)nd), host_col((size_t)nh);       // host_col[i] belongs to id max_splits - nh + i
     uint32_t C = 0;
     for (int64_t e = 0; e < nd; ++e) dev_col[e] = cnt[e] >= 2 ? C++ : RF_NONE;
@@ -2239,12 +2126,12 @@ int rf_dev_final(tq_rf *a)
     if (C) {
         if (nd) TQ_HIP(ctx, hipMemcpyAsync(a->d_colmap, dev_col.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
         if (nh)
-            TQ_HIP(ctx, hipMemcpyAsync(a->d_colmap + (a->max_splits - nh), host_col.data(), (size_t)nh * 4,
+            TQ_HIP(ctx, hipMemcpyAsync(a->d_colmap + (max_splits - nh), host_col.data(), (size_t)nh * 4,
                                        hipMemcpyHostToDevice, st));
         const int64_t per = a->cw_chunk * 64, nt = (N + RF_BT - 1) / RF_BT;
         RfBitArgs b{};
         b.ids = a->d_ids; b.colmap = a->d_colmap; b.bits = a->d_bits;
-        b.items = N * (a->T - 2); b.nodes = a->T - 2;
+        b.items = N * nodes; b.nodes = (int32_t)nodes;
         RfGemmArgs g{};
         g.bits = (const uint64_t *)a->d_bits.get(); g.shared = a->d_shared;
         g.N = (int32_t)N; g.nt = (int32_t)nt;
@@ -2273,7 +2160,7 @@ int rf_dev_final(tq_rf *a)
 // The matrices of everything added (kept until the next add / reset).
 int rf_final(tq_rf *a, const char *who)
 {
-    if (a->overflow) return rf_overflow(a, who);
+    if (a->table.overflow) return a->table.overflowed(a->ctx, who);
     if (a->ctx)
         if (int rc = rf_drain(a)) return rc;
     if (a->final_ok) return TQ_OK;
@@ -2314,18 +2201,14 @@ struct tq_qd {
     DevBuf<uint32_t> d_quart;       // [64 chunk_words][4]
     DevBuf<uint64_t> d_ranks, d_planes;     // [64 chunk_words], [max_trees][3][chunk_words]
     PinnedBuf<uint64_t> p_stage;    // 16 bytes per quartet of a chunk: its taxa or its rank on the way to the device
-    hipEvent_t copy_ev = nullptr;   // behind the last copy out of p_stage
-    bool copy_pending = false;
+    StreamOrder copy;               // behind the last copy out of p_stage
     StreamOrder order;              // behind the last add / score
     tq_qd() = default;
     tq_qd(const tq_qd &) = delete;
-    ~tq_qd()                        // runs before the buffers' destructors: device selected, last work finished
+    ~tq_qd()
     {
-        if (!ctx) return;
-        (void)hipSetDevice(ctx->device);
-        (void)order.sync();
-        if (copy_ev) { if (copy_pending) (void)hipEventSynchronize(copy_ev); (void)hipEventDestroy(copy_ev); }
-        if (order.ev) (void)hipEventDestroy(order.ev);
+        order.finish(ctx);
+        copy.finish(ctx);
     }
 };
 
@@ -2335,22 +2218,12 @@ namespace {
 // staged word chunks, and no slice is empty.  Returns the words per slice.
 int64_t qd_kslices(int64_t cw, int64_t nt, int num_cu, int want, int64_t *slices)
 {
-    const int64_t nchunks = (cw + QD_KW - 1) / QD_KW, pairs = nt * (nt + 1) / 2;
+    const int64_t nchunks = (cw + BT_KW - 1) / BT_KW, pairs = nt * (nt + 1) / 2;
     int64_t ks = want > 0 ? want : ((int64_t)QD_GRID_PER_CU * num_cu + pairs - 1) / pairs;
     ks = std::max<int64_t>(1, std::min<int64_t>({ks, nchunks, 65535}));
     const int64_t per = (nchunks + ks - 1) / ks;
     *slices = (nchunks + per - 1) / per;
-    return per * QD_KW;
-}
-
-// the staging buffer is free again
-int qd_stage_wait(tq_qd *a)
-{
-    if (a->copy_pending) {
-        TQ_HIP(a->ctx, hipEventSynchronize(a->copy_ev));
-        a->copy_pending = false;
-    }
-    return TQ_OK;
+    return per * BT_KW;
 }
 
 // planes and product of the nq quartets in d_quart, on `st`
@@ -2428,7 +2301,7 @@ int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t 
     for (int64_t q0 = 0; q0 < Q; q0 += per) {
         const int64_t n = std::min(per, Q - q0);
         if (quartets || ranks) {
-            if (int rc = qd_stage_wait(a)) return rc;
+            TQ_HIP(ctx, a->copy.sync());                            // the staging buffer is free again
             if (quartets) {
                 memcpy(a->p_stage, quartets + 4 * q0, (size_t)n * 16);
                 TQ_HIP(ctx, hipMemcpyAsync(a->d_quart, a->p_stage, (size_t)n * 16, hipMemcpyHostToDevice, st));
@@ -2436,8 +2309,7 @@ int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t 
                 memcpy(a->p_stage, ranks + q0, (size_t)n * 8);
                 TQ_HIP(ctx, hipMemcpyAsync(a->d_ranks, a->p_stage, (size_t)n * 8, hipMemcpyHostToDevice, st));
             }
-            TQ_HIP(ctx, hipEventRecord(a->copy_ev, st));
-            a->copy_pending = true;
+            TQ_HIP(ctx, a->copy.mark(st));
         }
         if (!quartets) {
             hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
@@ -2459,7 +2331,7 @@ int qd_zero(tq_qd *a)
     if (a->ctx) {
         TQ_HIP(a->ctx, hipSetDevice(a->ctx->device));
         TQ_HIP(a->ctx, a->order.sync());
-        if (int rc = qd_stage_wait(a)) return rc;
+        TQ_HIP(a->ctx, a->copy.sync());
         const size_t n = (size_t)(a->ntrees * a->ntrees) * 8;
         if (n && a->scored) {
             TQ_HIP(a->ctx, hipMemset(a->d_same, 0, n));
@@ -2527,13 +2399,10 @@ struct tq_stree {
     PinnedBuf<unsigned long long> p_nni_w;
     tq_stree() = default;
     tq_stree(const tq_stree &) = delete;
-    ~tq_stree()                     // runs before the buffers' destructors: device selected, device adds finished
+    ~tq_stree()
     {
-        if (!ctx) return;
-        (void)hipSetDevice(ctx->device);
-        (void)order.sync();
-        if (order.ev) (void)hipEventDestroy(order.ev);
-        if (own) (void)hipStreamDestroy(own);
+        order.finish(ctx);
+        if (ctx && own) (void)hipStreamDestroy(own);
     }
 };
 
@@ -4242,7 +4111,7 @@ int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int we
         if (e == hipSuccess) e = acc->p_side.alloc(nodes * 3);
         if (e == hipSuccess) e = acc->p_cut.alloc(nodes);
         if (e == hipSuccess) e = hipMemset(acc->d_cnt, 0, SC_WORDS * 8);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&acc->order.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = acc->order.create();
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking);
         if (e != hipSuccess) {
             delete acc;
@@ -4718,40 +4587,21 @@ int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx)
     tq_cons *a = new (std::nothrow) tq_cons();
     if (!a) return fail(ctx, TQ_ERR_OOM, "tq_cons_create: out of host memory");
     a->ctx = ctx;
-    a->T = (int32_t)T;
-    a->W = (int32_t)((T + 63) / 64);
-    a->tail = (T & 63) ? (uint64_t(1) << (T & 63)) - 1 : ~uint64_t(0);
-    a->max_splits = max_splits;
-    while (a->G < a->W) a->G *= 2;
+    a->chunk.shape(T);
+    a->table.max_splits = max_splits;
     if (ctx) {
-        const int64_t W = a->W, nodes = T - 2, stride = cons_stride(T);
-        a->hash_bits = ctx->cons_hash_bits;
-        const int64_t per_tree = nodes * W * 8 + nodes * 8 + nodes * 4 + stride * 4;       // masks, keys, unresolved, record
-        a->chunk_trees = std::max<int64_t>(1, std::min<int64_t>(CONS_CHUNK_MAX, ctx->cons_scratch_bytes / per_tree));
-        a->slots = 64;
-        while (a->slots < 2 * max_splits) a->slots *= 2;
-        a->gather_cap = std::max<int64_t>(1, CONS_GATHER_BYTES / (W * 8));
-        const int64_t C = a->chunk_trees;
+        const int64_t nodes = a->chunk.nodes();
         hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = a->d_trees.alloc((size_t)C * stride);
-        if (e == hipSuccess) e = a->d_masks.alloc((size_t)C * nodes * W);
-        if (e == hipSuccess) e = a->d_keys.alloc((size_t)C * nodes);
-        if (e == hipSuccess) e = a->d_unres.alloc((size_t)C * nodes);
-        if (e == hipSuccess) e = a->d_slot_key.alloc((size_t)a->slots);
-        if (e == hipSuccess) e = a->d_slot_idx.alloc((size_t)a->slots);
-        if (e == hipSuccess) e = a->d_rep.alloc((size_t)max_splits * W);
-        if (e == hipSuccess) e = a->d_count.alloc((size_t)max_splits);
-        if (e == hipSuccess) e = a->d_ctr.alloc(CONS_CTR_WORDS);
-        if (e == hipSuccess) e = a->d_gather.alloc((size_t)a->gather_cap * W);
-        if (e == hipSuccess) e = a->p_trees.alloc((size_t)C * stride);
-        if (e == hipSuccess) e = a->p_gather.alloc((size_t)a->gather_cap * W);
-        if (e == hipSuccess) e = a->p_ctr.alloc(CONS_CTR_WORDS);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = a->chunk.alloc(ctx->cons_scratch_bytes, nodes * 4);        // the unresolved items
+        if (e == hipSuccess) e = a->table.alloc(ctx, a->chunk.W, a->chunk.chunk_trees * nodes);
+        if (e == hipSuccess) e = a->chunk.alloc_host();
+        if (e == hipSuccess) e = a->table.alloc_host();
+        if (e == hipSuccess) e = a->order.create();
         if (e != hipSuccess) {
             delete a;
             return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_cons_create: %s", hipGetErrorString(e));
         }
-        if (int rc = cons_clear_dev(a)) {
+        if (int rc = a->table.clear(ctx)) {
             delete a;
             return rc;
         }
@@ -4768,15 +4618,11 @@ int tq_cons_reset(tq_cons *acc)
     if (acc->ctx) {
         TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
         TQ_HIP(acc->ctx, acc->order.sync());
-        if (int rc = cons_clear_dev(acc)) return rc;
-        acc->hash_bits = acc->ctx->cons_hash_bits;
+        if (int rc = acc->table.clear(acc->ctx)) return rc;
     }
-    acc->host.clear();
+    acc->table.forget(acc->ctx);
     acc->ntrees = 0;
-    acc->dev_entries = 0;
-    acc->chunks = 0;
-    acc->unresolved = 0;
-    acc->overflow = false;
+    acc->chunk.chunks = 0;
     acc->table_ok = false;
     return TQ_OK;
 }
@@ -4785,43 +4631,37 @@ int tq_cons_add(tq_cons *acc, const int32_t *parents, const int64_t *n_nodes, in
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_add: NULL pointer or negative size");
-    if (acc->overflow) return cons_overflow(acc, "tq_cons_add");
+    SplitTable &t = acc->table;
+    const int32_t T = acc->chunk.T, W = acc->chunk.W;
+    if (int rc = tree_set_args(ctx, "tq_cons_add", parents, n_nodes, R, stride)) return rc;
+    if (t.overflow) return t.overflowed(ctx, "tq_cons_add");
     if (R == 0) return TQ_OK;
     try {
-        const int64_t S = cons_stride(acc->T);
-        std::vector<int32_t> recs((size_t)R * S);       // every tree is validated before the first one is counted
-        for (int64_t r = 0; r < R; ++r) {
-            if (n_nodes[r] > stride)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_add: tree %lld: n_nodes exceeds the stride", (long long)r);
-            const std::string err = cons_prepare(parents + r * stride, n_nodes[r], acc->T, &recs[(size_t)r * S]);
-            if (!err.empty())
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_add: tree %lld: %s", (long long)r, err.c_str());
-        }
+        const int64_t S = cons_stride(T);
+        std::vector<int32_t> recs;
+        if (int rc = prepare_trees(ctx, "tq_cons_add", parents, n_nodes, R, stride, T, recs)) return rc;
         acc->table_ok = false;
         acc->ntrees += R;
         if (!ctx) {
-            std::vector<uint64_t> tmp, sides, m((size_t)acc->W);
+            std::vector<uint64_t> tmp, sides, m((size_t)W);
             for (int64_t r = 0; r < R; ++r) {
                 sides.clear();
-                cons_host_splits(&recs[(size_t)r * S], acc->T, acc->W, tmp, sides);
-                for (size_t e = 0; e < sides.size(); e += acc->W) {
-                    m.assign(sides.begin() + e, sides.begin() + e + acc->W);
-                    auto it = acc->host.find(m);
-                    if (it != acc->host.end()) { ++it->second; continue; }
-                    if ((int64_t)acc->host.size() >= acc->max_splits) return cons_overflow(acc, "tq_cons_add");
-                    acc->host.emplace(m, 1);
+                cons_host_splits(&recs[(size_t)r * S], T, W, tmp, sides);
+                for (size_t e = 0; e < sides.size(); e += W) {
+                    m.assign(sides.begin() + e, sides.begin() + e + W);
+                    auto it = t.host.find(m);
+                    if (it != t.host.end()) { ++it->second; continue; }
+                    if ((int64_t)t.host.size() >= t.max_splits) return t.overflowed(ctx, "tq_cons_add");
+                    t.host.emplace(m, 1);
                 }
             }
             return TQ_OK;
         }
         TQ_HIP(ctx, hipSetDevice(ctx->device));
-        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk_trees) {
-            const int64_t n = std::min<int64_t>(acc->chunk_trees, R - r0);
+        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk.chunk_trees) {
+            const int64_t n = std::min<int64_t>(acc->chunk.chunk_trees, R - r0);
             if (int rc = cons_drain(acc)) return rc;        // the staging buffer and the mask scratch are free again
-            memcpy(acc->p_trees, &recs[(size_t)r0 * S], (size_t)n * S * 4);
-            if (int rc = cons_launch(acc, n, (hipStream_t)stream)) return rc;
+            if (int rc = cons_launch(acc, n, &recs[(size_t)r0 * S], (hipStream_t)stream)) return rc;
         }
         return TQ_OK;
     } catch (const std::bad_alloc &) {
@@ -4832,8 +4672,8 @@ int tq_cons_add(tq_cons *acc, const int32_t *parents, const int64_t *n_nodes, in
 int tq_cons_shape(tq_cons *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->T;
-    if (W) *W = acc->W;
+    if (T) *T = acc->chunk.T;
+    if (W) *W = acc->chunk.W;
     if (ntrees) *ntrees = acc->ntrees;
     if (nsplits) {
         try {
@@ -4868,7 +4708,7 @@ int tq_cons_tree(tq_cons *acc, int64_t min_count, char *out, int64_t cap, int64_
     if (min_count < 1) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: min_count must be at least 1");
     try {
         if (int rc = cons_table(acc, "tq_cons_tree")) return rc;
-        const std::string nwk = cons_newick(acc->tmasks, acc->tcounts, acc->T, acc->W, acc->ntrees, min_count);
+        const std::string nwk = cons_newick(acc->tmasks, acc->tcounts, acc->chunk.T, acc->chunk.W, acc->ntrees, min_count);
         *written = (int64_t)nwk.size();
         if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
         memcpy(out, nwk.data(), nwk.size());
@@ -4884,14 +4724,14 @@ int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_
     if (!acc) return TQ_ERR_INVALID_ARG;
     if (!parent || !n_edges) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: NULL pointer");
     *n_edges = 0;
+    const int32_t T = acc->chunk.T, W = acc->chunk.W;
     try {
-        std::vector<int32_t> rec((size_t)cons_stride(acc->T));
-        const std::string err = cons_prepare(parent, n_nodes, acc->T, rec.data());
+        std::vector<int32_t> rec((size_t)cons_stride(T));
+        const std::string err = cons_prepare(parent, n_nodes, T, rec.data());
         if (!err.empty()) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: %s", err.c_str());
         if (int rc = cons_table(acc, "tq_cons_support")) return rc;
-        const int32_t W = acc->W;
         std::vector<uint64_t> tmp, sides;
-        cons_host_splits(rec.data(), acc->T, W, tmp, sides);
+        cons_host_splits(rec.data(), T, W, tmp, sides);
         const int64_t E = (int64_t)(sides.size() / W);
         std::vector<int64_t> order(E);
         for (int64_t e = 0; e < E; ++e) order[e] = e;
@@ -4920,14 +4760,14 @@ int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_
 int tq_cons_stats(tq_cons *acc, int64_t *out)
 {
     if (!acc || !out) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx && !acc->overflow)
+    if (acc->ctx && !acc->table.overflow)
         if (int rc = cons_drain(acc)) return rc;
-    out[0] = acc->chunk_trees;
-    out[1] = acc->chunks;
-    out[2] = acc->dev_entries;
-    out[3] = (int64_t)acc->host.size();
-    out[4] = acc->unresolved;
-    out[5] = acc->hash_bits;
+    out[0] = acc->chunk.chunk_trees;
+    out[1] = acc->chunk.chunks;
+    out[2] = acc->table.dev_entries;
+    out[3] = (int64_t)acc->table.host.size();
+    out[4] = acc->table.unresolved;
+    out[5] = acc->table.hash_bits;
     return TQ_OK;
 }
 
@@ -4944,11 +4784,8 @@ int tq_tbe_create(tq_tbe **out, int64_t T, const int32_t *ref_parent, int64_t n_
         if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: %s", err.c_str());
         a = new tq_tbe();
         a->ctx = ctx;
-        a->T = (int32_t)T;
-        a->W = (int32_t)((T + 63) / 64);
-        a->tail = (T & 63) ? (uint64_t(1) << (T & 63)) - 1 : ~uint64_t(0);
-        while (a->G < a->W) a->G *= 2;
-        tbe_reference(rec.data(), a->T, a->W, a->masks, a->p);
+        a->chunk.shape(T);
+        tbe_reference(rec.data(), a->chunk.T, a->chunk.W, a->masks, a->p);
         a->E = (int64_t)a->p.size();
         a->phi_sum.assign((size_t)a->E, 0);
     } catch (const std::bad_alloc &) {
@@ -4956,21 +4793,17 @@ int tq_tbe_create(tq_tbe **out, int64_t T, const int32_t *ref_parent, int64_t n_
         return fail(ctx, TQ_ERR_OOM, "tq_tbe_create: out of host memory");
     }
     if (ctx) {
-        const int64_t W = a->W, nodes = T - 2, stride = cons_stride(T), E1 = std::max<int64_t>(1, a->E);
-        const int64_t per_tree = nodes * W * 8 + nodes * 8 + stride * 4 + E1 * 2;       // masks, keys, record, phi row
-        a->chunk_trees = std::max<int64_t>(1, std::min<int64_t>(CONS_CHUNK_MAX, ctx->cons_scratch_bytes / per_tree));
-        const int64_t C = a->chunk_trees;
+        const int64_t W = a->chunk.W, E1 = std::max<int64_t>(1, a->E);
         hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = a->d_trees.alloc((size_t)C * stride);
-        if (e == hipSuccess) e = a->d_masks.alloc((size_t)C * nodes * W);
-        if (e == hipSuccess) e = a->d_keys.alloc((size_t)C * nodes);
+        if (e == hipSuccess) e = a->chunk.alloc(ctx->cons_scratch_bytes, E1 * 2);       // the phi row
+        const int64_t C = a->chunk.chunk_trees;
         if (e == hipSuccess) e = a->d_phi.alloc((size_t)C * E1);
         if (e == hipSuccess) e = a->d_ref.alloc((size_t)E1 * W);
         if (e == hipSuccess) e = a->d_p.alloc((size_t)E1);
         if (e == hipSuccess) e = a->d_phi_sum.alloc((size_t)E1);
-        if (e == hipSuccess) e = a->p_trees.alloc((size_t)C * stride);
+        if (e == hipSuccess) e = a->chunk.alloc_host();
         if (e == hipSuccess) e = a->p_phi.alloc((size_t)C * E1);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = a->order.create();
         if (e == hipSuccess && a->E) e = hipMemcpy(a->d_ref, a->masks.data(), (size_t)a->E * W * 8, hipMemcpyHostToDevice);
         if (e == hipSuccess && a->E) e = hipMemcpy(a->d_p, a->p.data(), (size_t)a->E * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemset(a->d_phi_sum, 0, (size_t)E1 * 8);
@@ -4997,7 +4830,7 @@ int tq_tbe_reset(tq_tbe *acc)
     }
     std::fill(acc->phi_sum.begin(), acc->phi_sum.end(), uint64_t(0));
     acc->ntrees = 0;
-    acc->chunks = 0;
+    acc->chunk.chunks = 0;
     return TQ_OK;
 }
 
@@ -5006,26 +4839,20 @@ int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int6
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_add: NULL pointer or negative size");
+    const int32_t T = acc->chunk.T, W = acc->chunk.W;
+    if (int rc = tree_set_args(ctx, "tq_tbe_add", parents, n_nodes, R, stride)) return rc;
     if (R == 0) return TQ_OK;
     try {
-        const int64_t S = cons_stride(acc->T), E = acc->E;
-        std::vector<int32_t> recs((size_t)R * S);       // every tree is validated before the first one is added
-        for (int64_t r = 0; r < R; ++r) {
-            if (n_nodes[r] > stride)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_add: tree %lld: n_nodes exceeds the stride", (long long)r);
-            const std::string err = cons_prepare(parents + r * stride, n_nodes[r], acc->T, &recs[(size_t)r * S]);
-            if (!err.empty())
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_add: tree %lld: %s", (long long)r, err.c_str());
-        }
+        const int64_t S = cons_stride(T), E = acc->E;
+        std::vector<int32_t> recs;
+        if (int rc = prepare_trees(ctx, "tq_tbe_add", parents, n_nodes, R, stride, T, recs)) return rc;
         acc->ntrees += R;
         if (E == 0) return TQ_OK;                       // a star reference: nothing to measure
         if (!ctx) {
             std::vector<uint64_t> tmp, sides;
             std::vector<uint32_t> phi((size_t)E);
             for (int64_t r = 0; r < R; ++r) {
-                tbe_host_tree(&recs[(size_t)r * S], acc->T, acc->W, acc->masks, acc->p, tmp, sides, phi.data());
+                tbe_host_tree(&recs[(size_t)r * S], T, W, acc->masks, acc->p, tmp, sides, phi.data());
                 for (int64_t e = 0; e < E; ++e) {
                     acc->phi_sum[e] += phi[e];
                     if (phi_out) phi_out[r * E + e] = (uint16_t)phi[e];
@@ -5034,11 +4861,10 @@ int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int6
             return TQ_OK;
         }
         TQ_HIP(ctx, hipSetDevice(ctx->device));
-        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk_trees) {
-            const int64_t n = std::min<int64_t>(acc->chunk_trees, R - r0);
+        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk.chunk_trees) {
+            const int64_t n = std::min<int64_t>(acc->chunk.chunk_trees, R - r0);
             TQ_HIP(ctx, acc->order.sync());             // the staging buffer and the mask scratch are free again
-            memcpy(acc->p_trees, &recs[(size_t)r0 * S], (size_t)n * S * 4);
-            if (int rc = tbe_launch(acc, n, (hipStream_t)stream, phi_out != nullptr)) return rc;
+            if (int rc = tbe_launch(acc, n, &recs[(size_t)r0 * S], (hipStream_t)stream, phi_out != nullptr)) return rc;
             if (phi_out) {
                 TQ_HIP(ctx, acc->order.sync());
                 memcpy(phi_out + r0 * E, acc->p_phi, (size_t)n * E * 2);
@@ -5053,8 +4879,8 @@ int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int6
 int tq_tbe_shape(tq_tbe *acc, int64_t *T, int64_t *W, int64_t *E, int64_t *ntrees)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->T;
-    if (W) *W = acc->W;
+    if (T) *T = acc->chunk.T;
+    if (W) *W = acc->chunk.W;
     if (E) *E = acc->E;
     if (ntrees) *ntrees = acc->ntrees;
     return TQ_OK;
@@ -5071,7 +4897,7 @@ int tq_tbe_read(tq_tbe *acc, uint64_t *masks, int64_t *p, uint64_t *phi_sum)
     } else if (phi_sum && E) {
         memcpy(phi_sum, acc->phi_sum.data(), (size_t)E * 8);
     }
-    if (masks && E) memcpy(masks, acc->masks.data(), (size_t)E * acc->W * 8);
+    if (masks && E) memcpy(masks, acc->masks.data(), (size_t)E * acc->chunk.W * 8);
     if (p)
         for (int64_t e = 0; e < E; ++e) p[e] = acc->p[e];
     return TQ_OK;
@@ -5080,8 +4906,8 @@ int tq_tbe_read(tq_tbe *acc, uint64_t *masks, int64_t *p, uint64_t *phi_sum)
 int tq_tbe_stats(tq_tbe *acc, int64_t *out)
 {
     if (!acc || !out) return TQ_ERR_INVALID_ARG;
-    out[0] = acc->chunk_trees;
-    out[1] = acc->chunks;
+    out[0] = acc->chunk.chunk_trees;
+    out[1] = acc->chunk.chunks;
     return TQ_OK;
 }
 
@@ -5097,49 +4923,30 @@ int tq_rf_create(tq_rf **out, int64_t T, int64_t max_trees, int64_t max_splits, 
     tq_rf *a = new (std::nothrow) tq_rf();
     if (!a) return fail(ctx, TQ_ERR_OOM, "tq_rf_create: out of host memory");
     a->ctx = ctx;
-    a->T = (int32_t)T;
-    a->W = (int32_t)((T + 63) / 64);
-    a->tail = (T & 63) ? (uint64_t(1) << (T & 63)) - 1 : ~uint64_t(0);
+    a->chunk.shape(T);
     a->max_trees = max_trees;
-    a->max_splits = max_splits;
-    while (a->G < a->W) a->G *= 2;
+    a->table.max_splits = max_splits;
     if (ctx) {
-        const int64_t W = a->W, nodes = T - 2, stride = cons_stride(T);
-        a->hash_bits = ctx->cons_hash_bits;
-        // masks, keys, unresolved items and their ids (device and page-locked), record
-        const int64_t per_tree = nodes * W * 8 + nodes * 8 + nodes * 4 * 3 + stride * 4;
-        a->chunk_trees = std::max<int64_t>(1, std::min<int64_t>(CONS_CHUNK_MAX, ctx->cons_scratch_bytes / per_tree));
-        a->chunk_trees = std::min<int64_t>(a->chunk_trees, max_trees);
-        a->slots = 64;
-        while (a->slots < 2 * max_splits) a->slots *= 2;
-        a->gather_cap = std::max<int64_t>(1, CONS_GATHER_BYTES / (W * 8));
+        const int64_t nodes = a->chunk.nodes();
         // a column is a split of at least two trees
         const int64_t max_cols = std::max<int64_t>(1, std::min<int64_t>(max_splits, max_trees * (T - 3) / 2));
         a->cw_chunk = std::max<int64_t>(1, std::min<int64_t>((max_cols + 63) / 64, ctx->cons_scratch_bytes / (max_trees * 8)));
-        const int64_t C = a->chunk_trees;
         hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = a->d_trees.alloc((size_t)C * stride);
-        if (e == hipSuccess) e = a->d_masks.alloc((size_t)C * nodes * W);
-        if (e == hipSuccess) e = a->d_keys.alloc((size_t)C * nodes);
-        if (e == hipSuccess) e = a->d_unres.alloc((size_t)C * nodes);
-        if (e == hipSuccess) e = a->d_newid.alloc((size_t)C * nodes);
-        if (e == hipSuccess) e = a->d_slot_key.alloc((size_t)a->slots);
-        if (e == hipSuccess) e = a->d_slot_idx.alloc((size_t)a->slots);
-        if (e == hipSuccess) e = a->d_rep.alloc((size_t)max_splits * W);
-        if (e == hipSuccess) e = a->d_count.alloc((size_t)max_splits);
+        // beside a tree's masks: its unresolved items and their ids, device and page-locked
+        if (e == hipSuccess) e = a->chunk.alloc(ctx->cons_scratch_bytes, nodes * 4 * 3, max_trees);
+        const int64_t items = a->chunk.chunk_trees * nodes;
+        if (e == hipSuccess) e = a->table.alloc(ctx, a->chunk.W, items);
+        if (e == hipSuccess) e = a->d_newid.alloc((size_t)items);
         if (e == hipSuccess) e = a->d_colmap.alloc((size_t)max_splits);
-        if (e == hipSuccess) e = a->d_ctr.alloc(CONS_CTR_WORDS);
-        if (e == hipSuccess) e = a->d_gather.alloc((size_t)a->gather_cap * W);
         if (e == hipSuccess) e = a->d_ids.alloc((size_t)max_trees * nodes);
         if (e == hipSuccess) e = a->d_nsplits.alloc((size_t)max_trees);
         if (e == hipSuccess) e = a->d_bits.alloc((size_t)max_trees * a->cw_chunk);
         if (e == hipSuccess) e = a->d_shared.alloc((size_t)max_trees * max_trees);
         if (e == hipSuccess) e = a->d_rf.alloc((size_t)max_trees * max_trees);
-        if (e == hipSuccess) e = a->p_trees.alloc((size_t)C * stride);
-        if (e == hipSuccess) e = a->p_gather.alloc((size_t)a->gather_cap * W);
-        if (e == hipSuccess) e = a->p_newid.alloc((size_t)C * nodes);
-        if (e == hipSuccess) e = a->p_ctr.alloc(CONS_CTR_WORDS);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = a->chunk.alloc_host();
+        if (e == hipSuccess) e = a->table.alloc_host();
+        if (e == hipSuccess) e = a->p_newid.alloc((size_t)items);
+        if (e == hipSuccess) e = a->order.create();
         if (e != hipSuccess) {
             delete a;
             return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_rf_create: %s", hipGetErrorString(e));
@@ -5162,17 +4969,13 @@ int tq_rf_reset(tq_rf *acc)
         TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
         TQ_HIP(acc->ctx, acc->order.sync());
         if (int rc = rf_clear_dev(acc)) return rc;
-        acc->hash_bits = acc->ctx->cons_hash_bits;
     }
-    acc->host.clear();
+    acc->table.forget(acc->ctx);
     acc->host_count.clear();
     acc->lists.clear();
     acc->ntrees = 0;
-    acc->dev_entries = 0;
-    acc->chunks = 0;
-    acc->unresolved = 0;
+    acc->chunk.chunks = 0;
     acc->columns = acc->col_chunks = 0;
-    acc->overflow = false;
     acc->final_ok = false;
     return TQ_OK;
 }
@@ -5181,41 +4984,31 @@ int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: NULL pointer or negative size");
-    if (acc->overflow) return rf_overflow(acc, "tq_rf_add");
+    SplitTable &t = acc->table;
+    const int32_t T = acc->chunk.T, W = acc->chunk.W;
+    if (int rc = tree_set_args(ctx, "tq_rf_add", parents, n_nodes, R, stride)) return rc;
+    if (t.overflow) return t.overflowed(ctx, "tq_rf_add");
     if (R == 0) return TQ_OK;
     if (acc->ntrees + R > acc->max_trees)
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: %lld trees held and %lld offered exceed max_trees = %lld",
                     (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
     try {
-        const int64_t S = cons_stride(acc->T);
-        std::vector<int32_t> recs((size_t)R * S);       // every tree is validated before the first one is added
-        for (int64_t r = 0; r < R; ++r) {
-            if (n_nodes[r] > stride)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: tree %lld: n_nodes exceeds the stride", (long long)r);
-            const std::string err = cons_prepare(parents + r * stride, n_nodes[r], acc->T, &recs[(size_t)r * S]);
-            if (!err.empty())
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: tree %lld: %s", (long long)r, err.c_str());
-        }
+        const int64_t S = cons_stride(T);
+        std::vector<int32_t> recs;
+        if (int rc = prepare_trees(ctx, "tq_rf_add", parents, n_nodes, R, stride, T, recs)) return rc;
         if (!ctx) {
-            std::vector<uint64_t> tmp, sides, m((size_t)acc->W);
+            std::vector<uint64_t> tmp, sides, m((size_t)W);
             acc->lists.reserve((size_t)(acc->ntrees + R));
             for (int64_t r = 0; r < R; ++r) {
                 sides.clear();
-                cons_host_splits(&recs[(size_t)r * S], acc->T, acc->W, tmp, sides);
+                cons_host_splits(&recs[(size_t)r * S], T, W, tmp, sides);
                 std::vector<uint32_t> ids;
-                ids.reserve(sides.size() / acc->W);
-                for (size_t e = 0; e < sides.size(); e += acc->W) {
-                    m.assign(sides.begin() + e, sides.begin() + e + acc->W);
-                    auto it = acc->host.find(m);
-                    if (it == acc->host.end()) {
-                        if ((int64_t)acc->host.size() >= acc->max_splits) return rf_overflow(acc, "tq_rf_add");
-                        it = acc->host.emplace(m, (int64_t)acc->host.size()).first;
-                        acc->host_count.push_back(0);
-                    }
-                    ++acc->host_count[(size_t)it->second];
-                    ids.push_back((uint32_t)it->second);
+                ids.reserve(sides.size() / W);
+                for (size_t e = 0; e < sides.size(); e += W) {
+                    m.assign(sides.begin() + e, sides.begin() + e + W);
+                    const int64_t *id = rf_host_id(acc, m, t.max_splits);
+                    if (!id) return t.overflowed(ctx, "tq_rf_add");
+                    ids.push_back((uint32_t)*id);
                 }
                 std::sort(ids.begin(), ids.end());
                 acc->lists.push_back(std::move(ids));
@@ -5225,12 +5018,11 @@ int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_
             return TQ_OK;
         }
         TQ_HIP(ctx, hipSetDevice(ctx->device));
-        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk_trees) {
-            const int64_t n = std::min<int64_t>(acc->chunk_trees, R - r0);
+        for (int64_t r0 = 0; r0 < R; r0 += acc->chunk.chunk_trees) {
+            const int64_t n = std::min<int64_t>(acc->chunk.chunk_trees, R - r0);
             if (int rc = rf_drain(acc)) return rc;          // the staging buffer and the mask scratch are free again
-            memcpy(acc->p_trees, &recs[(size_t)r0 * S], (size_t)n * S * 4);
             acc->final_ok = false;
-            if (int rc = rf_launch(acc, acc->ntrees, n, (hipStream_t)stream)) return rc;
+            if (int rc = rf_launch(acc, acc->ntrees, n, &recs[(size_t)r0 * S], (hipStream_t)stream)) return rc;
             acc->ntrees += n;
         }
         return TQ_OK;
@@ -5242,18 +5034,18 @@ int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_
 int tq_rf_shape(tq_rf *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits, int64_t *columns)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->T;
-    if (W) *W = acc->W;
+    if (T) *T = acc->chunk.T;
+    if (W) *W = acc->chunk.W;
     if (ntrees) *ntrees = acc->ntrees;
     if (nsplits) {
-        if (acc->ctx && !acc->overflow) {
+        if (acc->ctx && !acc->table.overflow) {
             try {
                 if (int rc = rf_drain(acc)) return rc;
             } catch (const std::bad_alloc &) {
                 return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_shape: out of host memory");
             }
         }
-        *nsplits = (acc->ctx ? acc->dev_entries : 0) + (int64_t)acc->host.size();
+        *nsplits = (acc->ctx ? acc->table.dev_entries : 0) + (int64_t)acc->table.host.size();
     }
     if (columns) *columns = acc->columns;
     return TQ_OK;
@@ -5285,21 +5077,21 @@ int tq_rf_read(tq_rf *acc, int32_t *nsplits, uint32_t *shared, uint32_t *rf)
 int tq_rf_stats(tq_rf *acc, int64_t *out)
 {
     if (!acc || !out) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx && !acc->overflow) {
+    if (acc->ctx && !acc->table.overflow) {
         try {
             if (int rc = rf_drain(acc)) return rc;
         } catch (const std::bad_alloc &) {
             return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_stats: out of host memory");
         }
     }
-    out[0] = acc->chunk_trees;
-    out[1] = acc->chunks;
+    out[0] = acc->chunk.chunk_trees;
+    out[1] = acc->chunk.chunks;
     out[2] = acc->columns;
     out[3] = acc->cw_chunk;
     out[4] = acc->col_chunks;
-    out[5] = acc->unresolved;
-    out[6] = acc->hash_bits;
-    out[7] = acc->dev_entries;
+    out[5] = acc->table.unresolved;
+    out[6] = acc->table.hash_bits;
+    out[7] = acc->table.dev_entries;
     return TQ_OK;
 }
 
@@ -5335,8 +5127,8 @@ int tq_qd_create(tq_qd **out, int64_t T, int64_t max_trees, tq_ctx *ctx)
         if (e == hipSuccess) e = a->d_ranks.alloc(cq);
         if (e == hipSuccess) e = a->d_planes.alloc((size_t)max_trees * 3 * a->chunk_words);
         if (e == hipSuccess) e = a->p_stage.alloc(cq * 2);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->order.ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&a->copy_ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = a->order.create();
+        if (e == hipSuccess) e = a->copy.create();
         if (e == hipSuccess) e = hipMemset(a->d_same, 0, mm * 8);
         if (e == hipSuccess) e = hipMemset(a->d_both, 0, mm * 8);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -5371,8 +5163,7 @@ int tq_qd_add(tq_qd *acc, const int32_t *parents, const int64_t *n_nodes, int64_
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: NULL pointer or negative size");
+    if (int rc = tree_set_args(ctx, "tq_qd_add", parents, n_nodes, R, stride)) return rc;
     if (R == 0) return TQ_OK;
     if (acc->scored)
         return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: quartets have been scored; clear or reset the accumulator first");

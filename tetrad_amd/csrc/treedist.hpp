@@ -24,25 +24,18 @@
 // id -> column).  For as many columns at a time as the bit scratch holds:
 //   tq_rf_scatter_kernel  threads over (tree, node): sets bit (column - first) of row `tree` of B[N][pitch] with a 64-bit
 //                         integer atomic OR.
-//   tq_rf_gemm_kernel     shared += B B^T on bit rows with `rf_word_shared` = popcount(x & y): the tile structure of
-//                         tq_tbe_kernel -- 256 threads as 16 x 16, 64 trees x 64 trees, the words in chunks of RF_KW staged
-//                         in LDS at a pitch of RF_KW + 1; a thread owns the 4 x 4 counts of trees ty + 16 i and tx + 16 j.
-//                         The grid is the tile pairs bj >= bi only (row bi of the triangle holds nt - bi of them; the
-//                         workgroup finds its pair in a loop of at most nt steps).  Every (i, j) of those tiles belongs to
-//                         one thread, which adds its count with a plain read-modify-write; the column chunks follow each
-//                         other on the stream.  No atomics.
+//   tq_rf_gemm_kernel     shared += B B^T on bit rows: the tile product of bit_tile.hpp, 64 trees x 64 trees, with
+//                         `rf_word_shared` = popcount(x & y) as the word rule.  The grid is the tile pairs bj >= bi only
+//                         (`bit_tile_pair`).  Every (i, j) of those tiles belongs to one thread, which adds its count
+//                         with a plain read-modify-write; the column chunks follow each other on the stream.  No atomics.
 //   tq_rf_final_kernel    threads over (i, j): the diagonal from nsplits, the tiles below the diagonal mirrored from the
 //                         ones above, rf from both.  A thread below the diagonal tiles reads [j][i], which no thread of
 //                         this kernel writes.
-// Tile sizes as tbe.hpp: 2 x 64 x 9 x 8 = 9 216 bytes of LDS, 16 accumulators per thread; the pitch of 9 words puts the
-// 16 rows tx + 16 j of a half-wave on 16 different even bank pairs, the rows ty + 16 i of a wave are 4 broadcasts.
 // No float, no loop that waits on another lane or workgroup, every loop bounded by T, W, N, Cw or a constant.
 #pragma once
 
-constexpr int RF_THREADS = 256;
-constexpr int RF_BT = 64;                   // trees per tile side
-constexpr int RF_KW = 8;                    // column words per staged chunk
-constexpr int RF_PITCH = RF_KW + 1;         // words per LDS row
+constexpr int RF_THREADS = BT_THREADS;
+constexpr int RF_BT = BT_ROWS;              // trees per tile side
 constexpr uint32_t RF_NONE = ~uint32_t(0);  // id of a node that is no split; column of an id held by one tree
 constexpr int64_t RF_MAX_TREES = 8192;
 
@@ -153,52 +146,23 @@ struct RfGemmArgs {
     int32_t N, Cw, nt;          // trees, words of the chunk, tiles per side
 };
 
-__device__ __forceinline__ void rf_step(uint32_t (&acc)[4][4], const uint64_t *rowA, const uint64_t *rowB, int k)
-{
-    uint64_t x[4], y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x[i] = rowA[16 * i * RF_PITCH + k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = rowB[16 * j * RF_PITCH + k];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += rf_word_shared(x[i], y[j]);
-}
-
 __global__ __launch_bounds__(RF_THREADS) void tq_rf_gemm_kernel(RfGemmArgs a)
 {
-    __shared__ uint64_t sA[RF_BT * RF_PITCH], sB[RF_BT * RF_PITCH];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int N = a.N, Cw = a.Cw;
-    int bi = 0, rest = (int)blockIdx.x;         // row bi of the triangle holds the pairs (bi, bi .. nt - 1)
-    for (int width = a.nt; bi < a.nt - 1 && rest >= width; --width) { rest -= width; ++bi; }
-    const int bj = bi + rest;
-    if (bj >= a.nt) return;                     // never with the grid of nt (nt + 1) / 2
+    const int N = a.N;
+    int bi, bj;
+    if (!bit_tile_pair((int)blockIdx.x, a.nt, bi, bj)) return;
     const int r0 = bi * RF_BT, c0 = bj * RF_BT;
-    const int lr = tid >> 3, lk = tid & 7;      // staging: rows lr and lr + 32, word lk of the chunk
-    const uint64_t *rowA = sA + ty * RF_PITCH, *rowB = sB + tx * RF_PITCH;
     uint32_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-    for (int w0 = 0; w0 < Cw; w0 += RF_KW) {
-        __syncthreads();                        // the tiles of the step before have been read
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {           // rows past N and words past Cw are zero: they share nothing
-            const int row = lr + 32 * h, w = w0 + lk, r = r0 + row, c = c0 + row;
-            sA[row * RF_PITCH + lk] = (r < N && w < Cw) ? a.bits[(int64_t)r * a.pitch + w] : uint64_t(0);
-            sB[row * RF_PITCH + lk] = (c < N && w < Cw) ? a.bits[(int64_t)c * a.pitch + w] : uint64_t(0);
-        }
-        __syncthreads();
-        if (Cw - w0 >= RF_KW) {
-#pragma unroll
-            for (int k = 0; k < RF_KW; ++k) rf_step(acc, rowA, rowB, k);
-        } else {
-            for (int k = 0; k < Cw - w0; ++k) rf_step(acc, rowA, rowB, k);
-        }
-    }
+    bit_tile_product<1, BT_KW>(                 // rows past N and words past Cw are zero: they share nothing
+        N - r0, N - c0, 0, a.Cw,
+        [&](int row, int, int w) { return a.bits[(int64_t)(r0 + row) * a.pitch + w]; },
+        [&](int row, int, int w) { return a.bits[(int64_t)(c0 + row) * a.pitch + w]; },
+        [&](int i, int j, const uint64_t (&x)[1], const uint64_t (&y)[1]) { acc[i][j] += rf_word_shared(x[0], y[0]); });
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = r0 + ty + 16 * i;
