@@ -23,6 +23,36 @@ def test_header_and_binding_agree():
     assert header_symbols() == sorted(_lib.SYMBOLS)
 
 
+def header_declarations():
+    """{name: (result type text, number of parameters)} of every function the header declares.  The header has no
+    function-pointer parameters, so the parameter list splits at its commas."""
+    text = re.sub(r"/\*.*?\*/", "", _lib.HEADER.read_text(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    decls = {}
+    for result, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(tq_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        params = params.strip()
+        decls[name] = (" ".join(result.split()), 0 if params in ("", "void") else len(params.split(",")))
+    return decls
+
+
+def test_prototypes_match_the_header():
+    """Every declared function has one prototype with the header's number of parameters, and no result type exactly
+    where the header says void: a missing or short prototype would pass 64-bit values through ctypes' int default."""
+    decls = header_declarations()
+    assert sorted(decls) == header_symbols()
+    assert sorted(decls) == sorted(_lib.PROTOTYPES)
+    for name, (result, nparams) in decls.items():
+        argtypes, restype = _lib.PROTOTYPES[name]
+        assert len(argtypes) == nparams, f"{name}: {len(argtypes)} argument types, the header declares {nparams}"
+        assert (restype is None) == (result == "void"), f"{name}: result {restype}, the header says {result!r}"
+
+
+def test_load_declares_every_prototype(lib):
+    for name, (argtypes, restype) in _lib.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+
+
 def test_every_declared_symbol_is_exported(lib):
     for name in header_symbols():
         assert hasattr(lib, name), f"{name} not exported by {_lib.LIB_PATH}"

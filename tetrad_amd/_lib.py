@@ -2,7 +2,7 @@
 
 There is no CPU fallback: if the HIP library is missing or cannot be loaded the
 import-time helper raises, and every compute entry point raises TetradHipError
-on a non-zero return code (message from tq_last_error).
+on a non-zero return code (message from the library's last-error text).
 """
 from __future__ import annotations
 
@@ -25,37 +25,161 @@ ERR_NAMES = {
 }
 FLAG_ZERO_DATA, FLAG_DEGENERATE, FLAG_BAD_INDEX, FLAG_NO_CONVERGENCE, FLAG_INVALID_DIAGNOSTIC = 1, 2, 4, 8, 16
 
-#: every symbol include/tetrad_hip.h declares (checked by tests/test_cabi_symbols.py)
-SYMBOLS = [
-    "tq_create", "tq_destroy", "tq_last_error", "tq_set_data", "tq_resolve",
-    "tq_set_source", "tq_bootstrap", "tq_bootstrap_async", "tq_sample_quartets_dev", "tq_get_data", "tq_data_shape",
-    "tq_host_alloc", "tq_host_free", "tq_resolve_to_host", "tq_scan_dev", "tq_svd_dev",
-    "tq_resolve_dev", "tq_resolve_range_dev", "tq_unrank_dev", "tq_resolve_debug",
-    "tq_timing_enable", "tq_timing_read", "tq_timing_read_split", "tq_timing_read_kernels",
-    "tq_set_option", "tq_device_info", "tq_debug_fetch", "tq_scan_plan", "tq_debug_bdsqr",
-    "tq_format_tsv", "tq_format_qmc", "tq_qmc_tree", "tq_qmc_splits", "tq_unrank", "tq_numpy_choice_tail",
-    "tq_conc_create", "tq_conc_destroy", "tq_conc_reset", "tq_conc_add", "tq_conc_add_dev", "tq_conc_shape", "tq_conc_read",
-    "tq_stree_create", "tq_stree_destroy", "tq_stree_reset", "tq_stree_add", "tq_stree_add_dev", "tq_stree_graph",
-    "tq_stree_rows", "tq_stree_build", "tq_stree_level_stats", "tq_stree_set_search", "tq_stree_search", "tq_stree_fit",
-    "tq_stree_nni_scan", "tq_stree_polish",
-    "tq_cons_create", "tq_cons_destroy", "tq_cons_reset", "tq_cons_add", "tq_cons_shape", "tq_cons_read", "tq_cons_tree",
-    "tq_cons_support", "tq_cons_stats",
-    "tq_tbe_create", "tq_tbe_destroy", "tq_tbe_reset", "tq_tbe_add", "tq_tbe_shape", "tq_tbe_read", "tq_tbe_stats",
-    "tq_rf_create", "tq_rf_destroy", "tq_rf_reset", "tq_rf_add", "tq_rf_shape", "tq_rf_read", "tq_rf_stats",
-    "tq_rf_word_shared",
-    "tq_qd_create", "tq_qd_destroy", "tq_qd_reset", "tq_qd_clear", "tq_qd_add", "tq_qd_score", "tq_qd_score_ranks",
-    "tq_qd_shape", "tq_qd_read", "tq_qd_stats", "tq_qd_word_counts",
-    "tq_set_species", "tq_resolve_species", "tq_resolve_species_dev", "tq_resolve_species_debug",
-    "tq_pack_sites",
-    "tq_pattern_class_table", "tq_patterns", "tq_patterns_dev", "tq_patterns_species", "tq_patterns_species_dev",
-    "tq_dstat_accumulate", "tq_dstat_accumulate_dev",
-    "tq_patterns_blocks", "tq_patterns_blocks_dev", "tq_dstat_jackknife", "tq_dstat_jackknife_dev",
-    "tq_patterns_blocks_species", "tq_patterns_blocks_species_dev", "tq_pooled_site_classes",
-    "tq_quintet_class_table", "tq_patterns_quintet_blocks", "tq_patterns_quintet_blocks_dev",
-    "tq_dstat_jackknife_masks", "tq_dstat_jackknife_masks_dev",
-    "tq_patterns_quintet_blocks_species", "tq_patterns_quintet_blocks_species_dev", "tq_pooled_quintet_site_classes",
-    "tq_scf_create", "tq_scf_destroy", "tq_scf_reset", "tq_scf_add", "tq_scf_add_dev", "tq_scf_shape", "tq_scf_read",
-]
+vp, text, f64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double
+i32, i64, u32, u64 = ctypes.c_int, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
+P = ctypes.POINTER
+
+
+def _sig(*argtypes, ret=i32):
+    return list(argtypes), ret
+
+
+#: every function include/tetrad_hip.h declares, in its order: the argument types and, where it is not int, the result
+#: type (None = void).  `load()` declares exactly these; tests/test_cabi_symbols.py compares names, arity and void
+#: results with the header.  Array and handle arguments are plain addresses (vp); P(...) marks a by-reference scalar.
+PROTOTYPES = {
+    # -- context, resident data, bootstrap replicates
+    "tq_create": _sig(P(vp), i32),
+    "tq_destroy": _sig(vp, ret=None),
+    "tq_last_error": _sig(vp, ret=text),
+    "tq_set_data": _sig(vp, vp, i64, i64, vp, i64),
+    "tq_set_source": _sig(vp, vp, i64, i64, vp, i64),
+    "tq_bootstrap": _sig(vp, vp, i64, u64, u64, P(i64)),
+    "tq_bootstrap_async": _sig(vp, vp, i64, u64, u64, P(i64), vp),
+    "tq_get_data": _sig(vp, vp, vp),
+    "tq_data_shape": _sig(vp, P(i64), P(i64)),
+    # -- resolving quartets: host rows, the pinned pool, device rows, the two halves, ranks
+    "tq_resolve": _sig(vp, vp, i64, i32, vp, vp, vp),
+    "tq_host_alloc": _sig(i64, P(vp)),
+    "tq_host_free": _sig(vp),
+    "tq_resolve_to_host": _sig(vp, vp, i64, i32, vp, vp, vp),
+    "tq_resolve_dev": _sig(vp, vp, i64, i32, vp, vp, vp, vp),
+    "tq_resolve_range_dev": _sig(vp, u64, i64, i32, vp, vp, vp, vp, vp),
+    "tq_scan_dev": _sig(vp, vp, i64, i32, vp),
+    "tq_svd_dev": _sig(vp, i64, i64, vp, vp, vp, vp),
+    "tq_unrank_dev": _sig(vp, vp, i64, vp, vp),
+    "tq_sample_quartets_dev": _sig(vp, u64, i64, vp, vp, vp),
+    "tq_resolve_debug": _sig(vp, vp, i64, i32, vp, vp, vp, vp, vp, vp),
+    # -- timing, options, test hooks
+    "tq_timing_enable": _sig(vp, i32),
+    "tq_timing_read": _sig(vp, P(f64), P(i64)),
+    "tq_timing_read_split": _sig(vp, P(f64), P(f64), P(f64), P(i64)),
+    "tq_timing_read_kernels": _sig(vp, P(f64), i32, P(i64)),
+    "tq_set_option": _sig(vp, text, i64),
+    "tq_debug_fetch": _sig(vp, i32, vp, i64),
+    "tq_scan_plan": _sig(vp, i64, vp, P(i64)),
+    "tq_debug_bdsqr": _sig(vp, vp, i64, vp, vp, i32, P(f64)),
+    # -- host helpers without a context: formats, site packing, ranks, Quartet MaxCut
+    "tq_format_tsv": _sig(vp, vp, vp, i64, vp, i64, P(i64)),
+    "tq_format_qmc": _sig(vp, vp, vp, i64, i32, i64, f64, vp, i64, P(i64), P(i64)),
+    "tq_pack_sites": _sig(vp, i64, i64, vp, i64, vp, i64, P(i64), P(i32), vp),
+    "tq_numpy_choice_tail": _sig(vp, u64, i64, vp),
+    "tq_unrank": _sig(vp, u64, i64, i64, vp),
+    "tq_qmc_splits": _sig(vp, vp, vp, i64, i32, i64, f64, vp, vp, P(i64)),
+    "tq_qmc_tree": _sig(vp, vp, i64, i64, u64, vp, i64, P(i64)),
+    # -- quartet concordance on a fixed tree
+    "tq_conc_create": _sig(P(vp), vp, i64, i64, i64, f64, vp),
+    "tq_conc_destroy": _sig(vp, ret=None),
+    "tq_conc_reset": _sig(vp),
+    "tq_conc_add": _sig(vp, vp, vp, vp, vp, i64),
+    "tq_conc_add_dev": _sig(vp, vp, vp, vp, vp, i64, vp),
+    "tq_conc_shape": _sig(vp, P(i64), P(i64), P(i64)),
+    "tq_conc_read": _sig(vp, vp, vp, vp, vp, P(i64)),
+    # -- exact supertree
+    "tq_stree_create": _sig(P(vp), i64, i64, i32, i64, f64, vp),
+    "tq_stree_destroy": _sig(vp, ret=None),
+    "tq_stree_reset": _sig(vp),
+    "tq_stree_add": _sig(vp, vp, vp, vp, vp, i64),
+    "tq_stree_add_dev": _sig(vp, vp, vp, vp, vp, i64, vp),
+    "tq_stree_graph": _sig(vp, vp, vp, P(i64), P(i64), P(u64)),
+    "tq_stree_rows": _sig(vp, vp, vp, P(i64)),
+    "tq_stree_build": _sig(vp, u64, vp, vp, i64, P(i64), P(i64)),
+    "tq_stree_level_stats": _sig(vp, P(i64), vp),
+    "tq_stree_set_search": _sig(vp, i32),
+    "tq_stree_fit": _sig(vp, vp, vp, i64, i64, vp, vp),
+    "tq_stree_nni_scan": _sig(vp, vp, i64, vp, P(i64), vp, vp, vp),
+    "tq_stree_polish": _sig(vp, vp, i64, i64, vp, vp, i64, P(i64), vp, P(i64), P(i32)),
+    "tq_stree_search": _sig(vp, i64, vp, vp, vp, vp, vp, vp, vp),
+    # -- consensus: split counts of tree sets
+    "tq_cons_create": _sig(P(vp), i64, i64, vp),
+    "tq_cons_destroy": _sig(vp, ret=None),
+    "tq_cons_reset": _sig(vp),
+    "tq_cons_add": _sig(vp, vp, vp, i64, i64, vp),
+    "tq_cons_shape": _sig(vp, P(i64), P(i64), P(i64), P(i64)),
+    "tq_cons_read": _sig(vp, vp, vp),
+    "tq_cons_tree": _sig(vp, i64, vp, i64, P(i64)),
+    "tq_cons_support": _sig(vp, vp, i64, vp, vp, P(i64)),
+    "tq_cons_stats": _sig(vp, vp),
+    # -- transfer bootstrap supports
+    "tq_tbe_create": _sig(P(vp), i64, vp, i64, vp),
+    "tq_tbe_destroy": _sig(vp, ret=None),
+    "tq_tbe_reset": _sig(vp),
+    "tq_tbe_add": _sig(vp, vp, vp, i64, i64, vp, vp),
+    "tq_tbe_shape": _sig(vp, P(i64), P(i64), P(i64), P(i64)),
+    "tq_tbe_read": _sig(vp, vp, vp, vp),
+    "tq_tbe_stats": _sig(vp, vp),
+    # -- Robinson-Foulds distances
+    "tq_rf_create": _sig(P(vp), i64, i64, i64, vp),
+    "tq_rf_destroy": _sig(vp, ret=None),
+    "tq_rf_reset": _sig(vp),
+    "tq_rf_add": _sig(vp, vp, vp, i64, i64, vp),
+    "tq_rf_shape": _sig(vp, P(i64), P(i64), P(i64), P(i64), P(i64)),
+    "tq_rf_read": _sig(vp, vp, vp, vp),
+    "tq_rf_stats": _sig(vp, vp),
+    "tq_rf_word_shared": _sig(u64, u64, ret=u32),
+    # -- quartet distances
+    "tq_qd_create": _sig(P(vp), i64, i64, vp),
+    "tq_qd_destroy": _sig(vp, ret=None),
+    "tq_qd_reset": _sig(vp),
+    "tq_qd_clear": _sig(vp),
+    "tq_qd_add": _sig(vp, vp, vp, i64, i64, vp),
+    "tq_qd_score": _sig(vp, vp, i64, vp),
+    "tq_qd_score_ranks": _sig(vp, vp, u64, i64, vp),
+    "tq_qd_shape": _sig(vp, P(i64), P(i64), P(u64)),
+    "tq_qd_read": _sig(vp, vp, vp),
+    "tq_qd_stats": _sig(vp, vp),
+    "tq_qd_word_counts": _sig(u64, u64, u64, u64, u64, u64, P(u32), P(u32), ret=None),
+    # -- species mode
+    "tq_set_species": _sig(vp, vp, i64, i64),
+    "tq_resolve_species": _sig(vp, vp, i64, vp, vp, vp),
+    "tq_resolve_species_dev": _sig(vp, vp, i64, vp, vp, vp, vp),
+    "tq_resolve_species_debug": _sig(vp, vp, i64, vp, vp, vp, vp, vp, vp),
+    # -- site-pattern classes and D tests: whole rows, per block, pooled by species
+    "tq_pattern_class_table": _sig(vp),
+    "tq_patterns": _sig(vp, vp, i64, i32, vp),
+    "tq_patterns_dev": _sig(vp, vp, i64, i32, vp, vp),
+    "tq_patterns_species": _sig(vp, vp, i64, vp),
+    "tq_patterns_species_dev": _sig(vp, vp, i64, vp, vp),
+    "tq_dstat_accumulate": _sig(vp, i64, vp, vp, vp, i64, vp),
+    "tq_dstat_accumulate_dev": _sig(vp, vp, i64, vp, vp, vp, i64, vp, vp),
+    "tq_patterns_blocks": _sig(vp, vp, i64, vp, i64, vp),
+    "tq_patterns_blocks_dev": _sig(vp, vp, i64, vp, i64, vp, vp),
+    "tq_dstat_jackknife": _sig(vp, i64, i64, vp, vp, vp, i64, vp),
+    "tq_dstat_jackknife_dev": _sig(vp, vp, i64, i64, vp, vp, vp, i64, vp, vp),
+    "tq_patterns_blocks_species": _sig(vp, vp, i64, vp, i64, vp),
+    "tq_patterns_blocks_species_dev": _sig(vp, vp, i64, vp, i64, vp, vp),
+    "tq_pooled_site_classes": _sig(vp, vp),
+    # -- five-taxon patterns
+    "tq_quintet_class_table": _sig(vp),
+    "tq_patterns_quintet_blocks": _sig(vp, vp, i64, vp, i64, vp),
+    "tq_patterns_quintet_blocks_dev": _sig(vp, vp, i64, vp, i64, vp, vp),
+    "tq_dstat_jackknife_masks": _sig(vp, i64, i64, vp, vp, vp, i64, vp),
+    "tq_dstat_jackknife_masks_dev": _sig(vp, vp, i64, i64, vp, vp, vp, i64, vp, vp),
+    "tq_patterns_quintet_blocks_species": _sig(vp, vp, i64, vp, i64, vp),
+    "tq_patterns_quintet_blocks_species_dev": _sig(vp, vp, i64, vp, i64, vp, vp),
+    "tq_pooled_quintet_site_classes": _sig(vp, vp),
+    # -- site concordance on a fixed tree
+    "tq_scf_create": _sig(P(vp), vp, i64, i64, vp),
+    "tq_scf_destroy": _sig(vp, ret=None),
+    "tq_scf_reset": _sig(vp),
+    "tq_scf_add": _sig(vp, vp, vp, i64),
+    "tq_scf_add_dev": _sig(vp, vp, vp, i64, vp),
+    "tq_scf_shape": _sig(vp, P(i64), P(i64), P(i64)),
+    "tq_scf_read": _sig(vp, vp, vp, P(i64)),
+    "tq_device_info": _sig(vp, P(i32), P(i32), P(i64)),
+}
+#: the names alone
+SYMBOLS = list(PROTOTYPES)
 
 
 class TetradHipError(RuntimeError):
@@ -122,258 +246,8 @@ def load() -> ctypes.CDLL:
     global LOADED_PATH
     LOADED_PATH = alt if alt else str(LIB_PATH)
     lib = ctypes.CDLL(LOADED_PATH)
-    c = ctypes
-    vp, i64, i32 = c.c_void_p, c.c_int64, c.c_int
-    lib.tq_create.argtypes = [c.POINTER(vp), i32]
-    lib.tq_create.restype = i32
-    lib.tq_destroy.argtypes = [vp]
-    lib.tq_destroy.restype = None
-    lib.tq_last_error.argtypes = [vp]
-    lib.tq_last_error.restype = c.c_char_p
-    lib.tq_set_data.argtypes = [vp, vp, i64, i64, vp, i64]
-    lib.tq_set_data.restype = i32
-    lib.tq_set_source.argtypes = [vp, vp, i64, i64, vp, i64]
-    lib.tq_set_source.restype = i32
-    lib.tq_bootstrap.argtypes = [vp, vp, i64, c.c_uint64, c.c_uint64, c.POINTER(i64)]
-    lib.tq_bootstrap.restype = i32
-    lib.tq_bootstrap_async.argtypes = [vp, vp, i64, c.c_uint64, c.c_uint64, c.POINTER(i64), vp]
-    lib.tq_bootstrap_async.restype = i32
-    lib.tq_sample_quartets_dev.argtypes = [vp, c.c_uint64, i64, vp, vp, vp]
-    lib.tq_sample_quartets_dev.restype = i32
-    lib.tq_get_data.argtypes = [vp, vp, vp]
-    lib.tq_get_data.restype = i32
-    lib.tq_data_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_data_shape.restype = i32
-    lib.tq_resolve.argtypes = [vp, vp, i64, i32, vp, vp, vp]
-    lib.tq_resolve.restype = i32
-    lib.tq_host_alloc.argtypes = [i64, c.POINTER(vp)]
-    lib.tq_host_alloc.restype = i32
-    lib.tq_host_free.argtypes = [vp]
-    lib.tq_host_free.restype = i32
-    lib.tq_resolve_to_host.argtypes = [vp, vp, i64, i32, vp, vp, vp]
-    lib.tq_resolve_to_host.restype = i32
-    lib.tq_scan_dev.argtypes = [vp, vp, i64, i32, vp]
-    lib.tq_scan_dev.restype = i32
-    lib.tq_svd_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp]
-    lib.tq_svd_dev.restype = i32
-    lib.tq_timing_read_kernels.argtypes = [vp, c.POINTER(c.c_double), i32, c.POINTER(i64)]
-    lib.tq_timing_read_kernels.restype = i32
-    lib.tq_resolve_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-    lib.tq_resolve_dev.restype = i32
-    lib.tq_resolve_range_dev.argtypes = [vp, c.c_uint64, i64, i32, vp, vp, vp, vp, vp]
-    lib.tq_resolve_range_dev.restype = i32
-    lib.tq_unrank_dev.argtypes = [vp, vp, i64, vp, vp]
-    lib.tq_unrank_dev.restype = i32
-    lib.tq_resolve_debug.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-    lib.tq_resolve_debug.restype = i32
-    lib.tq_timing_enable.argtypes = [vp, i32]
-    lib.tq_timing_enable.restype = i32
-    lib.tq_timing_read.argtypes = [vp, c.POINTER(c.c_double), c.POINTER(i64)]
-    lib.tq_timing_read.restype = i32
-    lib.tq_timing_read_split.argtypes = [vp, c.POINTER(c.c_double), c.POINTER(c.c_double),
-                                         c.POINTER(c.c_double), c.POINTER(i64)]
-    lib.tq_timing_read_split.restype = i32
-    lib.tq_debug_fetch.argtypes = [vp, i32, vp, i64]
-    lib.tq_debug_fetch.restype = i32
-    lib.tq_scan_plan.argtypes = [vp, i64, vp, c.POINTER(i64)]
-    lib.tq_scan_plan.restype = i32
-    lib.tq_debug_bdsqr.argtypes = [vp, vp, i64, vp, vp, i32, c.POINTER(c.c_double)]
-    lib.tq_debug_bdsqr.restype = i32
-    lib.tq_set_option.argtypes = [vp, c.c_char_p, i64]
-    lib.tq_set_option.restype = i32
-    lib.tq_format_tsv.argtypes = [vp, vp, vp, i64, vp, i64, c.POINTER(i64)]
-    lib.tq_format_tsv.restype = i32
-    lib.tq_format_qmc.argtypes = [vp, vp, vp, i64, i32, i64, c.c_double, vp, i64, c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_format_qmc.restype = i32
-    lib.tq_qmc_splits.argtypes = [vp, vp, vp, i64, i32, i64, c.c_double, vp, vp, c.POINTER(i64)]
-    lib.tq_qmc_splits.restype = i32
-    lib.tq_numpy_choice_tail.argtypes = [vp, c.c_uint64, i64, vp]
-    lib.tq_numpy_choice_tail.restype = i32
-    lib.tq_unrank.argtypes = [vp, c.c_uint64, i64, i64, vp]
-    lib.tq_unrank.restype = i32
-    lib.tq_qmc_tree.argtypes = [vp, vp, i64, i64, c.c_uint64, vp, i64, c.POINTER(i64)]
-    lib.tq_qmc_tree.restype = i32
-    lib.tq_conc_create.argtypes = [c.POINTER(vp), vp, i64, i64, i64, c.c_double, vp]
-    lib.tq_conc_create.restype = i32
-    lib.tq_conc_destroy.argtypes = [vp]
-    lib.tq_conc_destroy.restype = None
-    lib.tq_conc_reset.argtypes = [vp]
-    lib.tq_conc_reset.restype = i32
-    lib.tq_conc_add.argtypes = [vp, vp, vp, vp, vp, i64]
-    lib.tq_conc_add.restype = i32
-    lib.tq_conc_add_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp]
-    lib.tq_conc_add_dev.restype = i32
-    lib.tq_conc_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_conc_shape.restype = i32
-    lib.tq_conc_read.argtypes = [vp, vp, vp, vp, vp, c.POINTER(i64)]
-    lib.tq_conc_read.restype = i32
-    lib.tq_stree_create.argtypes = [c.POINTER(vp), i64, i64, i32, i64, c.c_double, vp]
-    lib.tq_stree_create.restype = i32
-    lib.tq_stree_destroy.argtypes = [vp]
-    lib.tq_stree_destroy.restype = None
-    lib.tq_stree_reset.argtypes = [vp]
-    lib.tq_stree_reset.restype = i32
-    lib.tq_stree_add.argtypes = [vp, vp, vp, vp, vp, i64]
-    lib.tq_stree_add.restype = i32
-    lib.tq_stree_add_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp]
-    lib.tq_stree_add_dev.restype = i32
-    lib.tq_stree_graph.argtypes = [vp, vp, vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_uint64)]
-    lib.tq_stree_graph.restype = i32
-    lib.tq_stree_rows.argtypes = [vp, vp, vp, c.POINTER(i64)]
-    lib.tq_stree_rows.restype = i32
-    lib.tq_stree_build.argtypes = [vp, c.c_uint64, vp, vp, i64, c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_stree_build.restype = i32
-    lib.tq_stree_level_stats.argtypes = [vp, c.POINTER(i64), vp]
-    lib.tq_stree_level_stats.restype = i32
-    lib.tq_stree_set_search.argtypes = [vp, i32]
-    lib.tq_stree_set_search.restype = i32
-    lib.tq_stree_search.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    lib.tq_stree_search.restype = i32
-    lib.tq_stree_fit.argtypes = [vp, vp, vp, i64, i64, vp, vp]
-    lib.tq_stree_fit.restype = i32
-    lib.tq_stree_nni_scan.argtypes = [vp, vp, i64, vp, c.POINTER(i64), vp, vp, vp]
-    lib.tq_stree_nni_scan.restype = i32
-    lib.tq_stree_polish.argtypes = [vp, vp, i64, i64, vp, vp, i64, c.POINTER(i64), vp, c.POINTER(i64), c.POINTER(i32)]
-    lib.tq_stree_polish.restype = i32
-    lib.tq_cons_create.argtypes = [c.POINTER(vp), i64, i64, vp]
-    lib.tq_cons_create.restype = i32
-    lib.tq_cons_destroy.argtypes = [vp]
-    lib.tq_cons_destroy.restype = None
-    lib.tq_cons_reset.argtypes = [vp]
-    lib.tq_cons_reset.restype = i32
-    lib.tq_cons_add.argtypes = [vp, vp, vp, i64, i64, vp]
-    lib.tq_cons_add.restype = i32
-    lib.tq_cons_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_cons_shape.restype = i32
-    lib.tq_cons_read.argtypes = [vp, vp, vp]
-    lib.tq_cons_read.restype = i32
-    lib.tq_cons_tree.argtypes = [vp, i64, vp, i64, c.POINTER(i64)]
-    lib.tq_cons_tree.restype = i32
-    lib.tq_cons_support.argtypes = [vp, vp, i64, vp, vp, c.POINTER(i64)]
-    lib.tq_cons_support.restype = i32
-    lib.tq_cons_stats.argtypes = [vp, vp]
-    lib.tq_cons_stats.restype = i32
-    lib.tq_tbe_create.argtypes = [c.POINTER(vp), i64, vp, i64, vp]
-    lib.tq_tbe_create.restype = i32
-    lib.tq_tbe_destroy.argtypes = [vp]
-    lib.tq_tbe_destroy.restype = None
-    lib.tq_tbe_reset.argtypes = [vp]
-    lib.tq_tbe_reset.restype = i32
-    lib.tq_tbe_add.argtypes = [vp, vp, vp, i64, i64, vp, vp]
-    lib.tq_tbe_add.restype = i32
-    lib.tq_tbe_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_tbe_shape.restype = i32
-    lib.tq_tbe_read.argtypes = [vp, vp, vp, vp]
-    lib.tq_tbe_read.restype = i32
-    lib.tq_tbe_stats.argtypes = [vp, vp]
-    lib.tq_tbe_stats.restype = i32
-    lib.tq_rf_create.argtypes = [c.POINTER(vp), i64, i64, i64, vp]
-    lib.tq_rf_create.restype = i32
-    lib.tq_rf_destroy.argtypes = [vp]
-    lib.tq_rf_destroy.restype = None
-    lib.tq_rf_reset.argtypes = [vp]
-    lib.tq_rf_reset.restype = i32
-    lib.tq_rf_add.argtypes = [vp, vp, vp, i64, i64, vp]
-    lib.tq_rf_add.restype = i32
-    lib.tq_rf_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_rf_shape.restype = i32
-    lib.tq_rf_read.argtypes = [vp, vp, vp, vp]
-    lib.tq_rf_read.restype = i32
-    lib.tq_rf_stats.argtypes = [vp, vp]
-    lib.tq_rf_stats.restype = i32
-    lib.tq_rf_word_shared.argtypes = [c.c_uint64, c.c_uint64]
-    lib.tq_rf_word_shared.restype = c.c_uint32
-    lib.tq_qd_create.argtypes = [c.POINTER(vp), i64, i64, vp]
-    lib.tq_qd_create.restype = i32
-    lib.tq_qd_destroy.argtypes = [vp]
-    lib.tq_qd_destroy.restype = None
-    lib.tq_qd_reset.argtypes = [vp]
-    lib.tq_qd_reset.restype = i32
-    lib.tq_qd_clear.argtypes = [vp]
-    lib.tq_qd_clear.restype = i32
-    lib.tq_qd_add.argtypes = [vp, vp, vp, i64, i64, vp]
-    lib.tq_qd_add.restype = i32
-    lib.tq_qd_score.argtypes = [vp, vp, i64, vp]
-    lib.tq_qd_score.restype = i32
-    lib.tq_qd_score_ranks.argtypes = [vp, vp, c.c_uint64, i64, vp]
-    lib.tq_qd_score_ranks.restype = i32
-    lib.tq_qd_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(c.c_uint64)]
-    lib.tq_qd_shape.restype = i32
-    lib.tq_qd_read.argtypes = [vp, vp, vp]
-    lib.tq_qd_read.restype = i32
-    lib.tq_qd_stats.argtypes = [vp, vp]
-    lib.tq_qd_stats.restype = i32
-    lib.tq_qd_word_counts.argtypes = [c.c_uint64] * 6 + [c.POINTER(c.c_uint32), c.POINTER(c.c_uint32)]
-    lib.tq_qd_word_counts.restype = None
-    lib.tq_set_species.argtypes = [vp, vp, i64, i64]
-    lib.tq_set_species.restype = i32
-    lib.tq_resolve_species.argtypes = [vp, vp, i64, vp, vp, vp]
-    lib.tq_resolve_species.restype = i32
-    lib.tq_resolve_species_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp]
-    lib.tq_resolve_species_dev.restype = i32
-    lib.tq_resolve_species_debug.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.tq_resolve_species_debug.restype = i32
-    lib.tq_pack_sites.argtypes = [vp, i64, i64, vp, i64, vp, i64, c.POINTER(i64), c.POINTER(c.c_int32), vp]
-    lib.tq_pack_sites.restype = i32
-    lib.tq_pattern_class_table.argtypes = [vp]
-    lib.tq_pattern_class_table.restype = i32
-    lib.tq_patterns.argtypes = [vp, vp, i64, i32, vp]
-    lib.tq_patterns.restype = i32
-    lib.tq_patterns_dev.argtypes = [vp, vp, i64, i32, vp, vp]
-    lib.tq_patterns_dev.restype = i32
-    lib.tq_patterns_species.argtypes = [vp, vp, i64, vp]
-    lib.tq_patterns_species.restype = i32
-    lib.tq_patterns_species_dev.argtypes = [vp, vp, i64, vp, vp]
-    lib.tq_patterns_species_dev.restype = i32
-    lib.tq_dstat_accumulate.argtypes = [vp, i64, vp, vp, vp, i64, vp]
-    lib.tq_dstat_accumulate.restype = i32
-    lib.tq_dstat_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp]
-    lib.tq_dstat_accumulate_dev.restype = i32
-    lib.tq_patterns_blocks.argtypes = [vp, vp, i64, vp, i64, vp]
-    lib.tq_patterns_blocks.restype = i32
-    lib.tq_patterns_blocks_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    lib.tq_patterns_blocks_dev.restype = i32
-    lib.tq_dstat_jackknife.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
-    lib.tq_dstat_jackknife.restype = i32
-    lib.tq_dstat_jackknife_dev.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, vp, vp]
-    lib.tq_dstat_jackknife_dev.restype = i32
-    lib.tq_patterns_blocks_species.argtypes = [vp, vp, i64, vp, i64, vp]
-    lib.tq_patterns_blocks_species.restype = i32
-    lib.tq_patterns_blocks_species_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    lib.tq_patterns_blocks_species_dev.restype = i32
-    lib.tq_pooled_site_classes.argtypes = [vp, vp]
-    lib.tq_pooled_site_classes.restype = i32
-    lib.tq_quintet_class_table.argtypes = [vp]
-    lib.tq_quintet_class_table.restype = i32
-    lib.tq_patterns_quintet_blocks.argtypes = [vp, vp, i64, vp, i64, vp]
-    lib.tq_patterns_quintet_blocks.restype = i32
-    lib.tq_patterns_quintet_blocks_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    lib.tq_patterns_quintet_blocks_dev.restype = i32
-    lib.tq_dstat_jackknife_masks.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
-    lib.tq_dstat_jackknife_masks.restype = i32
-    lib.tq_dstat_jackknife_masks_dev.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, vp, vp]
-    lib.tq_dstat_jackknife_masks_dev.restype = i32
-    lib.tq_patterns_quintet_blocks_species.argtypes = [vp, vp, i64, vp, i64, vp]
-    lib.tq_patterns_quintet_blocks_species.restype = i32
-    lib.tq_patterns_quintet_blocks_species_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    lib.tq_patterns_quintet_blocks_species_dev.restype = i32
-    lib.tq_pooled_quintet_site_classes.argtypes = [vp, vp]
-    lib.tq_pooled_quintet_site_classes.restype = i32
-    lib.tq_scf_create.argtypes = [c.POINTER(vp), vp, i64, i64, vp]
-    lib.tq_scf_create.restype = i32
-    lib.tq_scf_destroy.argtypes = [vp]
-    lib.tq_scf_destroy.restype = None
-    lib.tq_scf_reset.argtypes = [vp]
-    lib.tq_scf_reset.restype = i32
-    lib.tq_scf_add.argtypes = [vp, vp, vp, i64]
-    lib.tq_scf_add.restype = i32
-    lib.tq_scf_add_dev.argtypes = [vp, vp, vp, i64, vp]
-    lib.tq_scf_add_dev.restype = i32
-    lib.tq_scf_shape.argtypes = [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64)]
-    lib.tq_scf_shape.restype = i32
-    lib.tq_scf_read.argtypes = [vp, vp, vp, c.POINTER(i64)]
-    lib.tq_scf_read.restype = i32
-    lib.tq_device_info.argtypes = [vp, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(i64)]
-    lib.tq_device_info.restype = i32
+    for name, (argtypes, restype) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib

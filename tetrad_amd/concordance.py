@@ -32,6 +32,8 @@ from pathlib import Path
 
 import numpy as np
 
+from ._handle import Handle, mask_bits
+
 STATS = ["QC", "QD", "QI", "nsnps", "weights", "scores", "conc", "disc1", "disc2", "nu", "nqrts"]
 
 
@@ -154,6 +156,66 @@ def newick_to_parent(text: str, samples=None):
     return par, T, names
 
 
+def tree_to_parent(tree, ntaxa=None, samples=None):
+    """One tree, newick text or a parent array -> (parent i32[n], T, tip names).  Text of another taxon count than
+    `ntaxa` is refused (None: the text decides); a parent array needs `ntaxa`."""
+    if isinstance(tree, str):
+        par, T, names = newick_to_parent(tree, samples)
+        if ntaxa is not None and T != ntaxa:
+            raise ValueError(f"{T} taxa, the accumulator has {ntaxa}")
+        return par, T, names
+    if ntaxa is None:
+        raise ValueError("a parent array needs `ntaxa`")
+    return np.ascontiguousarray(tree, dtype=np.int32).reshape(-1), int(ntaxa), [str(t) for t in range(int(ntaxa))]
+
+
+def trees_to_parents(trees, ntaxa: int, samples=None) -> list:
+    """Trees as `tree_to_parent` takes one (a single newick string stands for a list of one) -> their parent arrays;
+    what is wrong with tree i is reported as "tree {i}: ..."."""
+    parents = []
+    for i, t in enumerate([trees] if isinstance(trees, str) else trees):
+        try:
+            parents.append(tree_to_parent(t, ntaxa, samples)[0])
+        except ValueError as e:
+            raise ValueError(f"tree {i}: {e}") from None
+    return parents
+
+
+def parent_block(parents, min_stride: int = 0):
+    """Parent arrays of any lengths (a list or a generator) -> (block i32[R, stride] padded with -1, n_nodes i64[R],
+    stride): how the library takes a set of trees."""
+    arrs = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in parents]
+    n = np.array([a.shape[0] for a in arrs], np.int64)
+    stride = max(int(n.max(initial=0)), min_stride)
+    block = np.full((len(arrs), stride), -1, np.int32)
+    for i, a in enumerate(arrs):
+        block[i, :a.shape[0]] = a
+    return block, n, stride
+
+
+class TreeSetInput:
+    """`add_parents` / `add_newick` of the accumulators over sets of trees on the taxa 0..`ntaxa`-1.  A class supplies
+    `_add(block, n_nodes, stride, stream)`, the call of its tq_*_add on a block that is not empty, and may keep the
+    `samples` given at create as the default of `add_newick`."""
+
+    samples = None
+
+    def _add_trees(self, parents, stream, *extra):
+        block, n, stride = parent_block(parents)
+        if len(n):
+            self._add(block, n, stride, stream or None, *extra)
+
+    def add_parents(self, parents, stream: int = 0):
+        """Trees as parent arrays (nodes 0..ntaxa-1 the taxa, parent[root] = -1), each with its own node count.  All of
+        them are validated before any is added.  With an engine the kernels run on `stream` (a hipStream_t)."""
+        self._add_trees(parents, stream)
+
+    def add_newick(self, strings, samples=None, stream: int = 0):
+        """Trees as newick text: tips are taxon numbers, or names through `samples` (`newick_to_parent`; default: those
+        given at create, where the accumulator takes them there)."""
+        self.add_parents(trees_to_parents(strings, self.ntaxa, self.samples if samples is None else samples), stream)
+
+
 # -- statistics (concordance.py:37-71, :246-281) ---------------------------------------------------------------------
 def qc(conc, disc1, disc2) -> float:
     """QC as concordance.py:37-57: +-1 with one non-zero class, 1 + sum p log_z p for z = 2 or 3, 1.0 for none."""
@@ -183,65 +245,20 @@ def _div(a, b):
     return out
 
 
-class _TreeAccumulator:
+class _TreeAccumulator(Handle):
     """What the accumulators of the library on one fixed tree share (`Concordance`, `scf.SiteConcordance`): the tree,
-    the handle and its lifecycle, the checks of device rows, the split masks and the annotated newick.  A subclass
-    names its family of library functions in `_prefix` and passes `tq_*_create` its own arguments."""
-
-    _prefix = ""
+    the checks of device rows, the split masks and the annotated newick.  A subclass names its family of library
+    functions in `_prefix` and passes `tq_*_create` its own arguments."""
 
     def __init__(self, tree, samples, ntaxa, engine, *create_args):
-        from . import _lib
-        self._lib = _lib.load()
-        if isinstance(tree, str):
-            self.newick = tree
-            par, T, names = newick_to_parent(tree, samples)
-        else:
-            if ntaxa is None:
-                raise ValueError("a parent array needs `ntaxa`")
-            self.newick = None
-            par, T, names = np.ascontiguousarray(tree, dtype=np.int32), int(ntaxa), [str(t) for t in range(int(ntaxa))]
+        self.newick = tree if isinstance(tree, str) else None
+        par, T, names = tree_to_parent(tree, ntaxa if self.newick is None else None, samples)     # text decides its own T
         self.parent, self.T, self.names = par, T, names
-        self.engine = engine                       # kept alive: the accumulator reports through its context
-        ctx = engine._h if engine is not None else None
-        h = ctypes.c_void_p()
-        rc = self._fn("create")(ctypes.byref(h), par.ctypes.data, par.shape[0], T, *create_args, ctx)
-        if rc != 0:
-            raise _lib.TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-        self._h = h
+        self.engine = engine
+        self._create(par.ctypes.data, par.shape[0], T, *create_args, self._ctx())
         t, e, w = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        self._check(self._fn("shape")(h, ctypes.byref(t), ctypes.byref(e), ctypes.byref(w)))
+        self._check(self._fn("shape")(self._h, ctypes.byref(t), ctypes.byref(e), ctypes.byref(w)))
         self.n_edges, self.mask_words = e.value, w.value
-
-    def _fn(self, name):
-        return getattr(self._lib, f"{self._prefix}_{name}")
-
-    # -- lifecycle ------------------------------------------------------------------------------------------
-    def _check(self, rc: int):
-        if rc != 0:
-            from ._lib import TetradHipError
-            ctx = self.engine._h if self.engine is not None else None
-            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._fn("destroy")(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._check(self._fn("reset")(self._h))
 
     # -- helpers of the subclasses ------------------------------------------------------------------------------
     def _need_engine(self):
@@ -258,11 +275,6 @@ class _TreeAccumulator:
         if stream is None:
             stream = torch.cuda.current_stream(rows[0][0].device)
         return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-
-    def _mask_bits(self, masks) -> np.ndarray:
-        """Mask words u64[E,W] -> bool [E,T]."""
-        bits = np.unpackbits(masks.view(np.uint8).reshape(self.n_edges, -1), axis=1, bitorder="little")
-        return bits[:, :self.T].astype(bool)
 
     def _annotated_newick(self, split, edge_comment, tip_comment) -> str:
         """The input tree (as given: rooted or not) with `edge_comment(e)` after the node of each edge (the first
@@ -417,7 +429,7 @@ class Concordance(_TreeAccumulator):
 
     def split_masks(self) -> np.ndarray:
         """bool [E, T]: the taxa on one side of each edge."""
-        return self._mask_bits(self.raw()["masks"])
+        return mask_bits(self.raw()["masks"], self.T)
 
     def stats(self) -> dict:
         """Per edge: split (bool [E,T]), nqrts, conc, disc1, disc2, nu, QC, QD, QI and the means nsnps, weights,
@@ -428,7 +440,7 @@ class Concordance(_TreeAccumulator):
         induced = conc + d1 + d2 + nu
         qfc, qfd = r["tip_counts"][:, 0], r["tip_counts"][:, 1]
         return dict(
-            split=self._mask_bits(r["masks"]), nqrts=nq, conc=conc, disc1=d1, disc2=d2, nu=nu,
+            split=mask_bits(r["masks"], self.T), nqrts=nq, conc=conc, disc1=d1, disc2=d2, nu=nu,
             QC=np.array([qc(int(a), int(b), int(d)) for a, b, d in zip(conc, d1, d2)], np.float64),
             QD=np.array([qd(int(a), int(b)) for a, b in zip(d1, d2)], np.float64),
             QI=1.0 - _div(nu, induced),

@@ -26,7 +26,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .concordance import newick_to_parent, parse_newick
+from ._handle import Handle, grow_text, mask_bits
+from .concordance import TreeSetInput, newick_to_parent, parse_newick, tree_to_parent
 
 
 def min_count_for(min_freq: float, ntrees: int) -> int:
@@ -46,7 +47,7 @@ def percent(count: int, ntrees: int) -> int:
     return (200 * int(count) + int(ntrees)) // (2 * int(ntrees)) if ntrees else 0
 
 
-class Consensus:
+class Consensus(TreeSetInput, Handle):
     """Split counts over a set of trees on the taxa 0..ntaxa-1, and the consensus built from them.
 
     ntaxa       4..4096
@@ -54,73 +55,16 @@ class Consensus:
     engine      a `QuartetEngine`: the splits are counted on its device; None: on the host
     """
 
+    _prefix = "tq_cons"
+
     def __init__(self, ntaxa: int, max_splits: int | None = None, engine=None):
-        from . import _lib
-        self._lib = _lib.load()
         self.ntaxa, self.engine = int(ntaxa), engine
         self.max_splits = int(max_splits) if max_splits is not None else max(1024, 16 * self.ntaxa)
-        self._h = None
-        h = ctypes.c_void_p()
-        self._check(self._lib.tq_cons_create(ctypes.byref(h), self.ntaxa, self.max_splits,
-                                             engine._h if engine is not None else None))
-        self._h = h
+        self._create(self.ntaxa, self.max_splits, self._ctx())
         self.mask_words = (self.ntaxa + 63) // 64
 
-    # -- lifecycle ------------------------------------------------------------------------------------------
-    def _check(self, rc: int):
-        if rc != 0:
-            from ._lib import TetradHipError
-            ctx = self.engine._h if self.engine is not None else None
-            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tq_cons_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._check(self._lib.tq_cons_reset(self._h))
-
-    # -- adding trees ---------------------------------------------------------------------------------------
-    def add_parents(self, parents, stream: int = 0):
-        """Trees as parent arrays (nodes 0..ntaxa-1 the taxa, parent[root] = -1), each with its own node count.  All
-        of them are validated before any is counted.  With an engine the kernels run on `stream` (a hipStream_t)."""
-        arrs = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in parents]
-        if not arrs:
-            return
-        n = np.array([a.shape[0] for a in arrs], np.int64)
-        stride = int(n.max())
-        block = np.full((len(arrs), stride), -1, np.int32)
-        for i, a in enumerate(arrs):
-            block[i, :a.shape[0]] = a
-        self._check(self._lib.tq_cons_add(self._h, block.ctypes.data, n.ctypes.data, len(arrs), stride, stream or None))
-
-    def add_newick(self, strings, samples=None, stream: int = 0):
-        """Trees as newick text: tips are taxon numbers, or names through `samples` (`concordance.newick_to_parent`)."""
-        if isinstance(strings, str):
-            strings = [strings]
-        parents = []
-        for i, s in enumerate(strings):
-            try:
-                par, T, _ = newick_to_parent(s, samples)
-            except ValueError as e:
-                raise ValueError(f"tree {i}: {e}") from None
-            if T != self.ntaxa:
-                raise ValueError(f"tree {i}: {T} taxa, the accumulator counts trees of {self.ntaxa}")
-            parents.append(par)
-        self.add_parents(parents, stream)
+    def _add(self, block, n_nodes, stride, stream):
+        self._check(self._lib.tq_cons_add(self._h, block.ctypes.data, n_nodes.ctypes.data, len(n_nodes), stride, stream))
 
     # -- reading --------------------------------------------------------------------------------------------
     @property
@@ -128,10 +72,6 @@ class Consensus:
         n = ctypes.c_int64()
         self._check(self._lib.tq_cons_shape(self._h, None, None, ctypes.byref(n), None))
         return n.value
-
-    def _bits(self, masks: np.ndarray) -> np.ndarray:
-        bits = np.unpackbits(masks.view(np.uint8).reshape(masks.shape[0], 8 * self.mask_words), axis=1, bitorder="little")
-        return bits[:, :self.ntaxa].astype(bool)
 
     def raw(self):
         """(masks u64[n, W], counts i64[n], ntrees) in table order; waits for the device."""
@@ -145,7 +85,7 @@ class Consensus:
     def splits(self):
         """(masks bool[n, ntaxa] = the side without taxon 0, counts i64[n], ntrees) in table order."""
         masks, counts, ntrees = self.raw()
-        return self._bits(masks), counts, ntrees
+        return mask_bits(masks, self.ntaxa), counts, ntrees
 
     def frequencies(self) -> np.ndarray:
         """count / ntrees per split of the table (the only float of this module besides `min_freq`)."""
@@ -162,17 +102,8 @@ class Consensus:
 
     def tree_min_count(self, min_count: int) -> str:
         """The consensus newick for an integer threshold."""
-        cap = 16 * self.ntaxa + 64
-        written = ctypes.c_int64()
-        for _ in range(2):
-            buf = np.empty(cap, dtype=np.uint8)
-            rc = self._lib.tq_cons_tree(self._h, int(min_count), buf.ctypes.data, cap, ctypes.byref(written))
-            if rc == 0:
-                return buf[:written.value].tobytes().decode("ascii")
-            if rc != -6 or written.value <= cap:
-                self._check(rc)
-            cap = written.value
-        self._check(rc)
+        return grow_text(lambda out, cap, written: self._lib.tq_cons_tree(self._h, int(min_count), out, cap, written),
+                         16 * self.ntaxa + 64, self._check)
 
     def tree(self, min_freq: float = 0.5) -> str:
         """The consensus newick (numeric tips; `qmc.relabel_tree` gives names and leaves the supports alone):
@@ -182,19 +113,14 @@ class Consensus:
     def support_of(self, newick_or_parent, samples=None):
         """(counts i64[E], masks bool[E, ntaxa]) of the splits of one given tree (newick text or a parent array), masks
         ascending: in how many added trees each occurs, 0 for a split seen in none."""
-        if isinstance(newick_or_parent, str):
-            par, T, _ = newick_to_parent(newick_or_parent, samples)
-            if T != self.ntaxa:
-                raise ValueError(f"the tree has {T} taxa, the accumulator counts trees of {self.ntaxa}")
-        else:
-            par = np.ascontiguousarray(newick_or_parent, dtype=np.int32).reshape(-1)
+        par = tree_to_parent(newick_or_parent, self.ntaxa, samples)[0]
         cap = max(1, self.ntaxa - 3)
         counts = np.zeros(cap, np.int64)
         masks = np.zeros((cap, self.mask_words), np.uint64)
         e = ctypes.c_int64()
         self._check(self._lib.tq_cons_support(self._h, par.ctypes.data, par.shape[0], counts.ctypes.data,
                                               masks.ctypes.data, ctypes.byref(e)))
-        return counts[:e.value].copy(), self._bits(masks[:e.value])
+        return counts[:e.value].copy(), mask_bits(masks[:e.value], self.ntaxa)
 
     def map_supports(self, newick: str, samples=None) -> str:
         """The given tree (its own shape, rooting, child order and tip labels) with the percent support of each of its

@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._handle import Handle
 from ._lib import TetradHipError
 
 
@@ -105,41 +106,19 @@ def pack_sites(tmpmap: np.ndarray, tmparr: np.ndarray | None = None):
     return src, bool(pays.value), tuple(est.tolist())
 
 
-class QuartetEngine:
+class QuartetEngine(Handle):
+    _prefix = "tq"
+
     def __init__(self, device_id: int = 0):
-        self._lib = _lib.load()
-        h = ctypes.c_void_p()
-        rc = self._lib.tq_create(ctypes.byref(h), int(device_id))
-        if rc != 0:
-            raise TetradHipError(rc, self._lib.tq_last_error(None).decode())
-        self._h = h
+        self._create(int(device_id))
         self.device_id = int(device_id)
         self.T = self.S = 0
         #: bumped whenever the resident replicate is replaced (set_data / bootstrap); lets the API
         #: mirrors notice that what they uploaded is no longer what the device holds
         self.data_generation = 0
 
-    # -- lifecycle ---------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tq_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc != 0:
-            raise TetradHipError(rc, self._lib.tq_last_error(self._h).decode())
+    def _ctx(self):
+        return self._h                  # the engine's errors are in its own context (NULL while it is being created)
 
     # -- data --------------------------------------------------------------
     def set_data(self, tmparr: np.ndarray, tmpmap: np.ndarray):

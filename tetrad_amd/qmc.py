@@ -14,6 +14,9 @@ from pathlib import Path
 
 import numpy as np
 
+from ._handle import Handle, grow_text
+from .concordance import parent_block, tree_to_parent, trees_to_parents
+
 
 def qmc_tree(splits: np.ndarray, weights=None, ntaxa: int | None = None, seed: int = 0) -> str:
     """Newick of the supertree of quartets `splits` u32[n,4] ("a,b|c,d" per row) with optional weights."""
@@ -26,18 +29,13 @@ def qmc_tree(splits: np.ndarray, weights=None, ntaxa: int | None = None, seed: i
     w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
     if w is not None and w.shape[0] != n:
         raise ValueError("weights must have one entry per quartet")
-    cap = 16 * int(ntaxa) + 64
-    written = ctypes.c_int64()
-    for _ in range(2):
-        buf = np.empty(cap, dtype=np.uint8)
-        rc = lib.tq_qmc_tree(sp.ctypes.data, None if w is None else w.ctypes.data, n, int(ntaxa), int(seed) & (2**64 - 1),
-                             buf.ctypes.data, cap, ctypes.byref(written))
-        if rc == 0:
-            return buf[:written.value].tobytes().decode("ascii")
-        if rc != -6 or written.value <= cap:
-            raise _lib.TetradHipError(rc, "tq_qmc_tree")
-        cap = written.value
-    raise _lib.TetradHipError(rc, "tq_qmc_tree: buffer sizing failed")
+
+    def fail(rc):
+        raise _lib.TetradHipError(rc, "tq_qmc_tree")
+
+    return grow_text(lambda out, cap, written: lib.tq_qmc_tree(sp.ctypes.data, None if w is None else w.ctypes.data, n,
+                                                               int(ntaxa), int(seed) & (2**64 - 1), out, cap, written),
+                     16 * int(ntaxa) + 64, fail)
 
 
 def qmc_splits(rqrts, rscor, rstat, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0):
@@ -102,7 +100,7 @@ LastFit = collections.namedtuple("LastFit", "results chosen seeds")
 PolishTrace = collections.namedtuple("PolishTrace", "moves gains converged")
 
 
-class Supertree:
+class Supertree(Handle):
     """Exact quartet supertree accumulator (`tq_stree_*`): Quartet MaxCut level by level on
     integer graph weights.  Rows are added on the host (`add`) or where the engine wrote them (`add_dev_ptrs`, needs
     `engine`); `tree(seed)` gives the newick with numeric tips.  The host and the device execution give the same
@@ -117,11 +115,10 @@ class Supertree:
     """
 
     SEARCH = {"f64": 0, "exact": 1}
+    _prefix = "tq_stree"
 
     def __init__(self, ntaxa: int, capacity: int, weights: int = 0, min_snps: int = 0, min_ratio: float = 1.0, engine=None,
                  search: str = "f64"):
-        from . import _lib
-        self._lib = _lib.load()
         if weights not in (0, 1, 2, 3):
             raise ValueError(f"no weight strategy {weights}")
         if search not in self.SEARCH:
@@ -131,11 +128,7 @@ class Supertree:
         self.last_fit = None
         self.last_polish = None
         self._chosen_stats = None
-        self._h = None
-        h = ctypes.c_void_p()
-        self._check(self._lib.tq_stree_create(ctypes.byref(h), self.ntaxa, self.capacity, int(weights), int(min_snps),
-                                              float(min_ratio), engine._h if engine is not None else None))
-        self._h = h
+        self._create(self.ntaxa, self.capacity, int(weights), int(min_snps), float(min_ratio), self._ctx())
         self.search = "f64"
         if search != "f64":
             self.set_search(search)
@@ -146,32 +139,6 @@ class Supertree:
             raise ValueError(f"search must be 'f64' or 'exact', got {search!r}")
         self._check(self._lib.tq_stree_set_search(self._h, self.SEARCH[search]))
         self.search = search
-
-    def _check(self, rc: int):
-        if rc != 0:
-            from ._lib import TetradHipError
-            ctx = self.engine._h if self.engine is not None else None
-            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tq_stree_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._check(self._lib.tq_stree_reset(self._h))
 
     def add(self, rqrts, rscor, rstat, flags=None):
         """Host rows: quartets u32[n,4], scores f64[n,3], rstat u32[n,2] = {topology, nsnps}, flags u8[n] or None."""
@@ -220,19 +187,12 @@ class Supertree:
         return sp, k
 
     def _build(self, seed: int, stream: int) -> str:
-        cap = 16 * self.ntaxa + 64
-        written, levels = ctypes.c_int64(), ctypes.c_int64()
-        for _ in range(2):
-            buf = np.empty(cap, dtype=np.uint8)
-            rc = self._lib.tq_stree_build(self._h, int(seed) & (2**64 - 1), stream or None, buf.ctypes.data, cap,
-                                          ctypes.byref(written), ctypes.byref(levels))
-            if rc == 0:
-                self.levels = levels.value
-                return buf[:written.value].tobytes().decode("ascii")
-            if rc != -6 or written.value <= cap:
-                self._check(rc)
-            cap = written.value
-        self._check(rc)
+        levels = ctypes.c_int64()
+        nwk = grow_text(lambda out, cap, written: self._lib.tq_stree_build(self._h, int(seed) & (2**64 - 1), stream or None,
+                                                                           out, cap, written, ctypes.byref(levels)),
+                        16 * self.ntaxa + 64, self._check)
+        self.levels = levels.value
+        return nwk
 
     def tree(self, seed: int = 0, stream: int = 0, restarts: int = 1, polish: bool = False) -> str:
         """Newick of the rows added so far (numeric tips); `self.levels` = levels of the recursion.  Device rows: the
@@ -275,13 +235,7 @@ class Supertree:
 
     def _parent_of(self, tree, samples):
         """One tree as `fit` takes it -> parent array i32."""
-        from .concordance import newick_to_parent
-        if isinstance(tree, str):
-            par, T, _ = newick_to_parent(tree, samples)
-            if T != self.ntaxa:
-                raise ValueError(f"the tree has {T} taxa, the accumulator has {self.ntaxa}")
-            return np.ascontiguousarray(par, dtype=np.int32)
-        return np.ascontiguousarray(tree, dtype=np.int32).reshape(-1)
+        return tree_to_parent(tree, self.ntaxa, samples)[0]
 
     def nni_scan(self, tree, samples=None, stream: int = 0) -> np.ndarray:
         """The quartet-fit weights of every nearest-neighbour interchange of `tree` (a newick string or a parent array,
@@ -321,22 +275,13 @@ class Supertree:
         max_rounds = int(max_rounds)
         if not 0 <= max_rounds <= 65536:
             raise ValueError("max_rounds must be 0..65536")
-        cap = 16 * self.ntaxa + 64
-        written, rounds, conv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        rounds, conv = ctypes.c_int64(), ctypes.c_int()
         trace = np.zeros((max(max_rounds, 1), 2), np.uint64)
-        for _ in range(2):
-            buf = np.empty(cap, dtype=np.uint8)
-            rc = self._lib.tq_stree_polish(self._h, par.ctypes.data, len(par), max_rounds, stream or None, buf.ctypes.data,
-                                           cap, ctypes.byref(written), trace.ctypes.data, ctypes.byref(rounds),
-                                           ctypes.byref(conv))
-            if rc == 0:
-                r = rounds.value
-                return (buf[:written.value].tobytes().decode("ascii"),
-                        PolishTrace([int(x) for x in trace[:r, 0]], [int(x) for x in trace[:r, 1]], bool(conv.value)))
-            if rc != -6 or written.value <= cap:
-                self._check(rc)
-            cap = written.value
-        self._check(rc)
+        nwk = grow_text(lambda out, cap, written: self._lib.tq_stree_polish(
+            self._h, par.ctypes.data, len(par), max_rounds, stream or None, out, cap, written, trace.ctypes.data,
+            ctypes.byref(rounds), ctypes.byref(conv)), 16 * self.ntaxa + 64, self._check)
+        r = rounds.value
+        return nwk, PolishTrace([int(x) for x in trace[:r, 0]], [int(x) for x in trace[:r, 1]], bool(conv.value))
 
     def fit(self, trees, samples=None, stream: int = 0) -> np.ndarray:
         """Quartet fit of `trees` against the kept rows (`tq_stree_fit`).  `trees`: a newick string,
@@ -346,30 +291,12 @@ class Supertree:
         weight k and the number n of the kept rows the tree displays (satisfied), contradicts (violated) and leaves in
         a polytomy (unresolved), and fraction = k_satisfied / (k_satisfied + k_violated), NaN when that is 0 / 0.
         Device rows: the kernels run on `stream`."""
-        from .concordance import newick_to_parent
         single = isinstance(trees, str) or (isinstance(trees, np.ndarray) and trees.ndim == 1) or (
             isinstance(trees, (list, tuple)) and len(trees) > 0 and np.isscalar(trees[0]) and not isinstance(trees[0], str))
-        items = [trees] if single else list(trees)
-        pars = []
-        for i, t in enumerate(items):
-            if isinstance(t, str):
-                try:
-                    par, T, _ = newick_to_parent(t, samples)
-                except ValueError as e:
-                    raise ValueError(f"tree {i}: {e}") from None
-                if T != self.ntaxa:
-                    raise ValueError(f"tree {i}: {T} taxa, the accumulator has {self.ntaxa}")
-            else:
-                par = np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
-            pars.append(par)
-        R = len(pars)
-        stride = max([len(p) for p in pars], default=0)
-        parents = np.full((R, max(stride, 1)), -1, np.int32)
-        for i, p in enumerate(pars):
-            parents[i, :len(p)] = p
-        n_nodes = np.array([len(p) for p in pars], np.int64)
+        parents, n_nodes, stride = parent_block(trees_to_parents([trees] if single else trees, self.ntaxa, samples), 1)
+        R = len(n_nodes)
         raw = np.zeros((R, 6), np.uint64)
-        self._check(self._lib.tq_stree_fit(self._h, parents.ctypes.data, n_nodes.ctypes.data, R, parents.shape[1],
+        self._check(self._lib.tq_stree_fit(self._h, parents.ctypes.data, n_nodes.ctypes.data, R, stride,
                                            stream or None, raw.ctypes.data))
         out = np.zeros(R, FIT_DTYPE)
         for j, name in enumerate(FIT_DTYPE.names[:6]):

@@ -30,6 +30,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._handle import mask_bits
 from .concordance import _TreeAccumulator, _div, newick_to_parent
 
 WORDS = ("nq", "nq_zero", "sum_conc", "sum_d1", "sum_d2", "fx_conc", "fx_d1", "fx_d2")
@@ -85,7 +86,7 @@ class SiteConcordance(_TreeAccumulator):
         """bool [E, T]: the taxa on one side of each edge (edge order and sides as `Concordance.split_masks`)."""
         m = np.zeros((self.n_edges, self.mask_words), np.uint64)
         self._check(self._lib.tq_scf_read(self._h, None, m.ctypes.data, None))
-        return self._mask_bits(m)
+        return mask_bits(m, self.T)
 
     def stats(self) -> dict:
         """Per edge: split (bool [E,T]), nq, nq_zero, the six sums, sCF / sDF1 / sDF2 (means of the rows' shares, in
@@ -94,7 +95,7 @@ class SiteConcordance(_TreeAccumulator):
         r = self.raw()
         c = r["edge_counts"]
         out = {k: c[:, i].copy() for i, k in enumerate(WORDS)}
-        out["split"] = self._mask_bits(r["masks"])
+        out["split"] = mask_bits(r["masks"], self.T)
         nq = out["nq"].astype(np.float64)
         sums = [out[k].astype(np.float64) for k in ("sum_conc", "sum_d1", "sum_d2")]
         total = sums[0] + sums[1] + sums[2]

@@ -22,7 +22,8 @@ import ctypes
 
 import numpy as np
 
-from .concordance import newick_to_parent
+from ._handle import Handle, mask_bits
+from .concordance import TreeSetInput, newick_to_parent, tree_to_parent, trees_to_parents
 from .consensus import write_split_labels
 
 
@@ -51,7 +52,7 @@ def _parent_to_newick(parent, T: int) -> str:
     return text[root] + ";"
 
 
-class TransferSupport:
+class TransferSupport(TreeSetInput, Handle):
     """Transfer indices of the branches of `tree` summed over replicate trees on the taxa 0..ntaxa-1.
 
     ntaxa    4..4096
@@ -59,89 +60,39 @@ class TransferSupport:
     engine   a `QuartetEngine`: the distances are taken on its device; None: on the host
     """
 
+    _prefix = "tq_tbe"
+
     def __init__(self, ntaxa: int, tree, samples=None, engine=None):
-        from . import _lib
-        self._lib = _lib.load()
         self.ntaxa, self.engine, self.samples = int(ntaxa), engine, samples
-        self._h = None
-        if isinstance(tree, str):
-            par, T, _ = newick_to_parent(tree, samples)
-            if T != self.ntaxa:
-                raise ValueError(f"the tree has {T} taxa, the accumulator was asked for {self.ntaxa}")
-            self._newick = tree
-        else:
-            par = np.ascontiguousarray(tree, dtype=np.int32).reshape(-1)
-            self._newick = None
-        self._parent = par
-        h = ctypes.c_void_p()
-        self._check(self._lib.tq_tbe_create(ctypes.byref(h), self.ntaxa, par.ctypes.data, par.shape[0],
-                                            engine._h if engine is not None else None))
-        self._h = h
+        self._newick = tree if isinstance(tree, str) else None
+        self._parent = par = tree_to_parent(tree, self.ntaxa, samples)[0]
+        self._create(self.ntaxa, par.ctypes.data, par.shape[0], self._ctx())
         self.mask_words = (self.ntaxa + 63) // 64
         e = ctypes.c_int64()
         self._check(self._lib.tq_tbe_shape(self._h, None, None, ctypes.byref(e), None))
         self.nbranches = e.value
 
-    # -- lifecycle ------------------------------------------------------------------------------------------
-    def _check(self, rc: int):
-        if rc != 0:
-            from ._lib import TetradHipError
-            ctx = self.engine._h if self.engine is not None else None
-            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tq_tbe_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self):
         """Forgets the replicates, keeps the reference tree."""
-        self._check(self._lib.tq_tbe_reset(self._h))
+        super().reset()
 
     # -- adding trees ---------------------------------------------------------------------------------------
+    def _add(self, block, n_nodes, stride, stream, phi=None):
+        self._check(self._lib.tq_tbe_add(self._h, block.ctypes.data, n_nodes.ctypes.data, len(n_nodes), stride, stream,
+                                         None if phi is None else phi.ctypes.data))
+
     def add_parents(self, parents, stream: int = 0, per_tree: bool = False):
         """Replicates as parent arrays (nodes 0..ntaxa-1 the taxa, parent[root] = -1), each with its own node count.
         All of them are validated before any is added.  With an engine the kernels run on `stream` (a hipStream_t).
         `per_tree`: returns phi as u16 [R, E] (the call then waits for the device)."""
-        arrs = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in parents]
-        phi = np.zeros((len(arrs), self.nbranches), np.uint16) if per_tree else None
-        if not arrs:
-            return phi
-        n = np.array([a.shape[0] for a in arrs], np.int64)
-        stride = int(n.max())
-        block = np.full((len(arrs), stride), -1, np.int32)
-        for i, a in enumerate(arrs):
-            block[i, :a.shape[0]] = a
-        self._check(self._lib.tq_tbe_add(self._h, block.ctypes.data, n.ctypes.data, len(arrs), stride, stream or None,
-                                         phi.ctypes.data if per_tree else None))
+        parents = list(parents)
+        phi = np.zeros((len(parents), self.nbranches), np.uint16) if per_tree else None
+        self._add_trees(parents, stream, phi)
         return phi
 
     def add_newick(self, strings, samples=None, stream: int = 0, per_tree: bool = False):
         """Replicates as newick text: tips are taxon numbers, or names through `samples`."""
-        if isinstance(strings, str):
-            strings = [strings]
-        parents = []
-        for i, s in enumerate(strings):
-            try:
-                par, T, _ = newick_to_parent(s, samples)
-            except ValueError as e:
-                raise ValueError(f"tree {i}: {e}") from None
-            if T != self.ntaxa:
-                raise ValueError(f"tree {i}: {T} taxa, the accumulator measures trees of {self.ntaxa}")
-            parents.append(par)
-        return self.add_parents(parents, stream, per_tree)
+        return self.add_parents(trees_to_parents(strings, self.ntaxa, samples), stream, per_tree)
 
     # -- reading --------------------------------------------------------------------------------------------
     @property
@@ -158,8 +109,7 @@ class TransferSupport:
         p = np.zeros(E, np.int64)
         phi_sum = np.zeros(E, np.uint64)
         self._check(self._lib.tq_tbe_read(self._h, masks.ctypes.data, p.ctypes.data, phi_sum.ctypes.data))
-        bits = np.unpackbits(masks.view(np.uint8).reshape(E, 8 * self.mask_words), axis=1, bitorder="little")
-        return bits[:, :self.ntaxa].astype(bool), p, phi_sum
+        return mask_bits(masks, self.ntaxa), p, phi_sum
 
     def stats(self) -> dict:
         """Counters of the device path: trees per chunk, chunks launched since create / reset."""

@@ -20,10 +20,11 @@ import ctypes
 
 import numpy as np
 
-from .concordance import newick_to_parent
+from ._handle import Handle, mean_pairs, medoid
+from .concordance import TreeSetInput, newick_to_parent
 
 
-class TreeDistances:
+class TreeDistances(TreeSetInput, Handle):
     """Robinson-Foulds distances between all trees added, on the taxa 0..ntaxa-1.
 
     ntaxa       4..4096
@@ -33,78 +34,22 @@ class TreeDistances:
     engine      a `QuartetEngine`: the work is done on its device; None: on the host
     """
 
+    _prefix = "tq_rf"
+
     def __init__(self, ntaxa: int, max_trees: int, max_splits=None, samples=None, engine=None):
-        from . import _lib
-        self._lib = _lib.load()
         self.ntaxa, self.max_trees, self.engine, self.samples = int(ntaxa), int(max_trees), engine, samples
-        self._h = None
         if max_splits is None:
             max_splits = max(1, min(self.max_trees * (self.ntaxa - 3), 2 ** 26))
         self.max_splits = int(max_splits)
-        h = ctypes.c_void_p()
-        self._check(self._lib.tq_rf_create(ctypes.byref(h), self.ntaxa, self.max_trees, self.max_splits,
-                                           engine._h if engine is not None else None))
-        self._h = h
+        self._create(self.ntaxa, self.max_trees, self.max_splits, self._ctx())
         self.mask_words = (self.ntaxa + 63) // 64
-
-    # -- lifecycle ------------------------------------------------------------------------------------------
-    def _check(self, rc: int):
-        if rc != 0:
-            from ._lib import TetradHipError
-            ctx = self.engine._h if self.engine is not None else None
-            raise TetradHipError(rc, self._lib.tq_last_error(ctx).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.tq_rf_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         """Forgets the trees and their splits."""
-        self._check(self._lib.tq_rf_reset(self._h))
+        super().reset()
 
-    # -- adding trees ---------------------------------------------------------------------------------------
-    def add_parents(self, parents, stream: int = 0):
-        """Trees as parent arrays (nodes 0..ntaxa-1 the taxa, parent[root] = -1), each with its own node count.  All of
-        them are validated before any is added.  With an engine the kernels run on `stream` (a hipStream_t)."""
-        arrs = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in parents]
-        if not arrs:
-            return
-        n = np.array([a.shape[0] for a in arrs], np.int64)
-        stride = int(n.max())
-        block = np.full((len(arrs), stride), -1, np.int32)
-        for i, a in enumerate(arrs):
-            block[i, :a.shape[0]] = a
-        self._check(self._lib.tq_rf_add(self._h, block.ctypes.data, n.ctypes.data, len(arrs), stride, stream or None))
-
-    def add_newick(self, strings, samples=None, stream: int = 0):
-        """Trees as newick text: tips are taxon numbers, or names through `samples` (default: those given at create)."""
-        if isinstance(strings, str):
-            strings = [strings]
-        if samples is None:
-            samples = self.samples
-        parents = []
-        for i, s in enumerate(strings):
-            try:
-                par, T, _ = newick_to_parent(s, samples)
-            except ValueError as e:
-                raise ValueError(f"tree {i}: {e}") from None
-            if T != self.ntaxa:
-                raise ValueError(f"tree {i}: {T} taxa, the accumulator compares trees of {self.ntaxa}")
-            parents.append(par)
-        self.add_parents(parents, stream)
+    def _add(self, block, n_nodes, stride, stream):
+        self._check(self._lib.tq_rf_add(self._h, block.ctypes.data, n_nodes.ctypes.data, len(n_nodes), stride, stream))
 
     # -- reading --------------------------------------------------------------------------------------------
     def _shape(self, which: int) -> int:
@@ -159,21 +104,11 @@ class TreeDistances:
 
     def medoid(self):
         """(index, row sum) of the tree with the smallest sum of distances to all others; ties go to the lowest index."""
-        rf = self.rf()
-        if not len(rf):
-            raise ValueError("no trees")
-        sums = [sum(int(x) for x in row) for row in rf]
-        best = min(range(len(sums)), key=lambda i: (sums[i], i))
-        return best, sums[best]
+        return medoid(self.rf())
 
     def mean_rf(self) -> float:
         """The mean distance over the pairs i < j; 0.0 for fewer than 2 trees."""
-        rf = self.rf()
-        N = len(rf)
-        if N < 2:
-            return 0.0
-        total = sum(int(x) for x in rf[np.triu_indices(N, 1)])
-        return total / (N * (N - 1) // 2)
+        return mean_pairs(self.rf())
 
     def stats(self) -> dict:
         """Counters: trees per chunk, tree chunks launched since create / reset, and of the last read the columns
