@@ -48,14 +48,41 @@ __device__ __forceinline__ double quad_sum(double v)
     return v;
 }
 
-__device__ __forceinline__ double sqrt_nr(double x)     // x >= 0, full precision, sqrt(0) = 0
+__device__ __forceinline__ double sqrt_nr_pos(double x) // x > 0, full precision (x = 0 gives NaN)
 {
     // v_rsq_f64 (5e-8) + one Newton step (4e-15), then one Heron step on the root itself, which squares that
     // error: full precision without a second Newton step on the reciprocal root
     const double y = rsq_nr<1>(x);
     const double s = x * y;
-    const double r = fma(fma(-s, s, x), 0.5 * y, s);
-    return x > 0.0 ? r : 0.0;
+    return fma(fma(-s, s, x), 0.5 * y, s);
+}
+
+__device__ __forceinline__ double sqrt_nr(double x)     // x >= 0, full precision, sqrt(0) = 0
+{
+    return x > 0.0 ? sqrt_nr_pos(x) : 0.0;
+}
+
+// alpha and beta of the Householder reflector of a vector with squared norm n2 and leading value x0: the reflector maps
+// the vector to alpha e_1, and with v = x - alpha e_1 it is I - beta v v^T.  A vector whose squared norm is not above thr2
+// gets no reflector (alpha = beta = 0).  That case is rare, so the coefficients are computed without its selects, and one
+// wave-uniform test puts the zeros in afterwards when some lane of the wave needs them: a live vector has n2 > thr2 >= 0,
+// for which sqrt_nr_pos is sqrt_nr, so its alpha and beta are the same bits on either way through.
+__device__ __forceinline__ void reflector_coeffs(double n2, double thr2, double x0, double &alpha, double &beta)
+{
+    const double nrm = sqrt_nr_pos(n2);
+    double al = (x0 < 0.0) ? nrm : -nrm;
+    const double den = fma(-al, x0, n2);                 // = |v|^2 / 2 > 0 for a live vector
+    // one Newton step (2e-15) is enough: I - beta(1+d) v v^T is the exact reflector times a scaling
+    // of ONE direction by 1+2d -- invertible, so ranks and zero singular values are untouched and the
+    // others move by a relative 4e-15
+    double be = rcp_nr<1>(den);
+    if (__builtin_expect(__ballot(!(n2 > thr2)) != 0, 0)) {
+        const bool live = n2 > thr2;
+        al = live ? al : 0.0;
+        be = live ? be : 0.0;
+    }
+    alpha = al;
+    beta = be;
 }
 
 // de layout: f64 [3*Q][32]: d[0..15] then e[0..15] with e[0] = 0 (e[i] couples columns i-1, i)
@@ -166,16 +193,10 @@ tq_bidiag_kernel(const uint32_t *__restrict__ cm, int64_t Q, double *__restrict_
                     double n2 = 0.0;
 #pragma unroll
                     for (int r = K; r < 16; ++r) n2 = fma(v[r], v[r], n2);
-                    const bool live = n2 > thr2;
-                    const double nrm = sqrt_nr(n2);
                     const double x0 = v[K];
-                    const double alpha = live ? ((x0 < 0.0) ? nrm : -nrm) : 0.0;
+                    double alpha, beta;
+                    reflector_coeffs(n2, thr2, x0, alpha, beta);
                     v[K] = x0 - alpha;
-                    const double den = fma(-alpha, x0, n2);      // = |v|^2 / 2 > 0 for a live column
-                    // one Newton step (2e-15) is enough: I - beta(1+d) v v^T is the exact reflector times a scaling
-                    // of ONE direction by 1+2d -- invertible, so ranks and zero singular values are untouched and the
-                    // others move by a relative 4e-15
-                    const double beta = live ? rcp_nr<1>(den) : 0.0;
                     if (writer) dout[K] = alpha;
 #pragma unroll
                     for (int s = so; s < 4; ++s) {
@@ -199,12 +220,9 @@ tq_bidiag_kernel(const uint32_t *__restrict__ cm, int64_t Q, double *__restrict_
                         p = fma(y[s], y[s], p);
                     }
                     const double n2 = quad_sum(p);
-                    const bool live = n2 > thr2;
                     const double x0 = quad_bcast<c1>(y[s1]);
-                    const double nrm = sqrt_nr(n2);
-                    const double alpha = live ? ((x0 < 0.0) ? nrm : -nrm) : 0.0;
-                    const double den = fma(-alpha, x0, n2);
-                    const double beta = live ? rcp_nr<1>(den) : 0.0;
+                    double alpha, beta;
+                    reflector_coeffs(n2, thr2, x0, alpha, beta);
                     if (c == c1) y[s1] = x0 - alpha;
                     if (writer) dout[16 + K1] = alpha;
                     // -beta * y: one multiply per slot instead of one per row, and the sign goes in here so that the
@@ -352,13 +370,10 @@ tq_bidiag2_kernel(const uint32_t *__restrict__ cm, int64_t Q, double *__restrict
 #pragma unroll
                     for (int rs = S0; rs < 8; ++rs) n2 = fma(v[rs], v[rs], n2);
                     n2 += dpx<2>(n2);                                        // + the rows of the other parity
-                    const bool live = n2 > thr2;
-                    const double nrm = sqrt_nr(n2);
                     const double x0 = quad_from_ri<PK>(v[S0]);               // M[K][K]
-                    const double alpha = live ? ((x0 < 0.0) ? nrm : -nrm) : 0.0;
+                    double alpha, beta;
+                    reflector_coeffs(n2, thr2, x0, alpha, beta);
                     if (ri == PK) v[S0] = x0 - alpha;
-                    const double den = fma(-alpha, x0, n2);
-                    const double beta = live ? rcp_nr<1>(den) : 0.0;
                     if (writer) dout[K] = alpha;
                     // columns right of K: slot S0 holds column K + 1 for the lanes with ci = 1 when K is even
                     constexpr int CS0 = PK == 0 ? S0 : S0 + 1;
@@ -386,12 +401,9 @@ tq_bidiag2_kernel(const uint32_t *__restrict__ cm, int64_t Q, double *__restrict
 #pragma unroll
                     for (int cs = S1; cs < 8; ++cs) p = fma(y[cs], y[cs], p);
                     const double n2 = p + dpx<1>(p);
-                    const bool live = n2 > thr2;
                     const double x0 = quad_from_ci<P1>(y[S1]);               // M[K][K + 1]
-                    const double nrm = sqrt_nr(n2);
-                    const double alpha = live ? ((x0 < 0.0) ? nrm : -nrm) : 0.0;
-                    const double den = fma(-alpha, x0, n2);
-                    const double beta = live ? rcp_nr<1>(den) : 0.0;
+                    double alpha, beta;
+                    reflector_coeffs(n2, thr2, x0, alpha, beta);
                     if (ci == P1) y[S1] = x0 - alpha;
                     if (writer) dout[16 + K1] = alpha;
                     double yb[8];
@@ -425,6 +437,53 @@ tq_bidiag2_kernel(const uint32_t *__restrict__ cm, int64_t Q, double *__restrict
 #define E_(i) el[(i) * WAVE]
 __device__ __forceinline__ double hypot_nr(double a, double b) { return sqrt_nr(fma(a, a, b * b)); }
 constexpr int RSQ_NR = 1;      // Newton steps on v_rsq_f64 inside a rotation (1: 5e-15, 2: 1e-16 relative)
+
+// One step of a QR sweep: the rotation that chases the bulge out of e[jj] (new e[jj] = r.e), then the one that restores
+// the diagonal (new w[jj] = r.w).  Each hypot shares one rsq with the reciprocal its rotation needs.
+//   GUARD = true : a zero pivot (f = h = 0) is a clamp before the rsq and, in the second rotation, a select that keeps
+//                  the first rotation's c and s: right for every input.
+//   GUARD = false: the bare arithmetic.  fmax(zz, 1e-290) is zz itself and the selects take their first arm whenever
+//                  zz >= 1e-290, so for both squared pivots in that range the two forms give the same bits; below it the
+//                  bare form returns infinities and NaNs, which the caller must not use.  r.zhi is the smaller of the two
+//                  squared pivots' high words (both are >= +0, so their high words order like the values): the caller
+//                  takes the guarded form when r.zhi < BD_ZERO_HI, which holds for every zz < 1e-290 (and for the few
+//                  values that share its high word, where either form will do).  A NaN squared pivot has a large high
+//                  word and stays on the bare form, where the guarded form would clamp it to 1e-290: the two differ
+//                  there, but a NaN needs a non-finite d or e, which no count matrix gives.
+struct BdStep {
+    double f, x, cc, ss, e, w;
+    uint32_t zhi;
+};
+constexpr uint32_t BD_ZERO_HI = (uint32_t)(__builtin_bit_cast(unsigned long long, 1e-290) >> 32) + 1u;
+
+template <bool GUARD>
+__device__ __forceinline__ BdStep bdsqr_step(double f, double x, double g, double y, double cc, double ss)
+{
+    BdStep r;
+    double h = ss * g;
+    g = cc * g;
+    const double z1 = fma(f, f, h * h);
+    double rz = rsq_nr<RSQ_NR>(GUARD ? fmax(z1, 1e-290) : z1);
+    r.e = z1 * rz;
+    cc = f * rz;
+    ss = h * rz;
+    f = fma(x, cc, g * ss);
+    g = fma(g, cc, -(x * ss));
+    h = y * ss;
+    y *= cc;
+    const double z2 = fma(f, f, h * h);
+    rz = rsq_nr<RSQ_NR>(GUARD ? fmax(z2, 1e-290) : z2);
+    r.w = z2 * rz;
+    const bool nz = GUARD ? z2 > 0.0 : true;
+    cc = nz ? f * rz : cc;
+    ss = nz ? h * rz : ss;
+    r.f = fma(cc, g, ss * y);
+    r.x = fma(cc, y, -(ss * g));
+    r.cc = cc;
+    r.ss = ss;
+    r.zhi = min((uint32_t)__double2hiint(z1), (uint32_t)__double2hiint(z2));
+    return r;
+}
 
 __global__ void __launch_bounds__(WAVE)
 tq_bdsqr_kernel(const double *__restrict__ de, int64_t nmat, double *__restrict__ sv, int maxit,
@@ -537,8 +596,8 @@ tq_bdsqr_kernel(const double *__restrict__ de, int64_t nmat, double *__restrict_
             f = ((x - z) * (x + z) + h * (y * rcp_nr<1>(f + copysign(g, f)) - h)) * rcp_nr<1>(x);
             double cc = 1.0, ss = 1.0;
             // one QR sweep over the block [l,k]; the LDS reads of the next step are issued before the
-            // current step's arithmetic, each hypot shares one rsq with the reciprocal its rotation
-            // needs, and a zero pivot is a select, not a branch (f = h = 0 there, so c = s = 0 * rz)
+            // current step's arithmetic.  The step runs unguarded; a zero pivot (f = h = 0, rare) in any lane that is
+            // still sweeping sends the wave through the guarded copy of that step (bdsqr_step)
             double gn = E_(l + 1), yn = W_(l + 1);
             if (work_out) {
                 my_steps += (uint32_t)(nm - l + 1);
@@ -560,25 +619,22 @@ tq_bdsqr_kernel(const double *__restrict__ de, int64_t nmat, double *__restrict_
                 const int i2 = min(jj + 2, 15);
                 gn = E_(i2);
                 yn = W_(i2);
-                h = ss * g;
-                g = cc * g;
-                double zz = fma(f, f, h * h);
-                double rz = rsq_nr<RSQ_NR>(fmax(zz, 1e-290));
-                SET_E(jj, zz * rz);
-                cc = f * rz;
-                ss = h * rz;
-                f = fma(x, cc, g * ss);
-                g = fma(g, cc, -(x * ss));
-                h = y * ss;
-                y *= cc;
-                zz = fma(f, f, h * h);
-                rz = rsq_nr<RSQ_NR>(fmax(zz, 1e-290));
-                SET_W(jj, zz * rz);
-                const bool nz = zz > 0.0;
-                cc = nz ? f * rz : cc;
-                ss = nz ? h * rz : ss;
-                f = fma(cc, g, ss * y);
-                x = fma(cc, y, -(ss * g));
+                BdStep r = bdsqr_step<false>(f, x, g, y, cc, ss);
+                // the unguarded values are parked before the test, so that the whole step is issued ahead of the branch
+                // and the branch does not sit in the step's chain of dependent operations
+                SET_E(jj, r.e);
+                SET_W(jj, r.w);
+                // wave-uniform: only the lanes still in this loop vote, and a hit sends them all through the guarded copy
+                // for this one step (a lane without a zero pivot gets the same bits from either copy)
+                if (__builtin_expect(__ballot(r.zhi < BD_ZERO_HI) != 0, 0)) {
+                    r = bdsqr_step<true>(f, x, g, y, cc, ss);
+                    SET_E(jj, r.e);
+                    SET_W(jj, r.w);
+                }
+                f = r.f;
+                x = r.x;
+                cc = r.cc;
+                ss = r.ss;
             }
             SET_E(l, 0.0);
             SET_E(k, f);
