@@ -1,4 +1,4 @@
-"""GPU: pooled class rows of species sets per block of sites (`tq_species_blocks_kernel`) against
+"""GPU: pooled class rows of species sets per block of sites (`tq_block_rows_kernel<SpeciesRule>`) against
 the factored and the literal model, against `patterns_species` (summed over a tiling) and against the sample kernel under
 the identity map; table freshness behind device-built replicates; refusals; and `run_dstat_jackknife(species_of=...)`
 end to end.  Every comparison is bit-exact."""
@@ -130,7 +130,7 @@ def test_a_tiling_sums_to_patterns_species(engine, sizes, method, inv):
 
 
 def test_identity_map_equals_the_sample_kernel(engine):
-    """Every species one sample: the new kernel against tq_pattern_blocks_kernel on the same sets."""
+    """Every species one sample: the new kernel against tq_block_rows_kernel<QuartetRule> on the same sets."""
     g = load_golden("carry_T6_S2500")
     sets = all_sets(6)
     engine.set_data(g["tmparr"], g["tmpmap"])

@@ -1,4 +1,4 @@
-"""GPU: pooled five-taxon class rows of species sets per block of sites (`tq_species_quintet_blocks_kernel`, DESIGN.md
+"""GPU: pooled five-taxon class rows of species sets per block of sites (`tq_block_rows_kernel<SpeciesQuintetRule>`, DESIGN.md
 section 23) against the factored and the literal model, against the sample kernel under the identity map and against the
 pooled four-species rows; the range rule at its edges; table freshness behind device-built replicates; refusals; and
 `run_quintet_jackknife(species_of=...)` end to end.  Every comparison is bit-exact."""

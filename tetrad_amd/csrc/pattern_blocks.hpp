@@ -7,14 +7,9 @@
 // patterns.hpp.  Block j of `starts` i64[B + 1] is sites [starts[j], starts[j + 1]) of the resident replicate; a block
 // row is u32[16] = the 15 class counts of the block's sites and their sum.
 //
-// tq_pattern_blocks_kernel: a work item is a (set, block) pair, item = set * B + block.  16 lanes take one item, four
-// items per wavefront (the group shape of tq_pattern_class_kernel, whose DPP row sum is re-used).  Lane l takes the
-// words w0 + l, w0 + l + 16, ... of the block's word range: per word four 12-byte plane records {missing, bit 0, bit 1}
-// (prepare.hpp), valid = ~(OR of the missing words) & range mask, six equality words, the 15 class masks as products of
-// the equality words and their complements, 15 popcount-adds.  The range mask differs from all-ones only in the first
-// and the last word of the block (both cuts in one word when the block lies inside it); pad sites are missing in every
-// taxon.  No LDS, no atomics, no scratch; every address is 64-bit.  A taxon >= T gives a row of zeros; items past
-// Q * B store nothing.
+// The rows are written by tq_block_rows_kernel<QuartetRule> (block_rows.hpp has the kernel, the plane walk and the rule):
+// per word of the block four plane records, six equality words, the 15 class masks as products of the equality words and
+// their complements (pattern_masks), 15 popcount-adds.  A taxon >= T gives a row of zeros.
 //
 // dstat_jackknife_row: Busing, Meijer & van der Leeden 1999, block weight m_j = a_j + b_j, every floating operation
 // rounded once and in one fixed order (see the function), so device, host and Python floats agree bit for bit.
@@ -92,60 +87,6 @@ __device__ __forceinline__ PlaneRec pblk_load(const uint32_t *row, int64_t w)
 __device__ __forceinline__ uint32_t pblk_eq(const PlaneRec &x, const PlaneRec &y)
 {
     return ~((x.b0 ^ y.b0) | (x.b1 ^ y.b1));
-}
-
-// planes3 u32[T][W][3]; sets u32[Q][4]; starts i64[B + 1] with 0 <= starts[0] < ... < starts[B] <= 32 W (checked on the
-// host), Q * B < 2^31; inv = 0xFFFFFFFF when invariant sites count, else 0; classes u32[Q][B][16]
-__global__ __launch_bounds__(PBLK_THREADS) void tq_pattern_blocks_kernel(const uint32_t *__restrict__ planes3, int64_t W,
-                                                                         uint32_t T, const uint32_t *__restrict__ sets,
-                                                                         int64_t Q, const int64_t *__restrict__ starts,
-                                                                         int64_t B, uint32_t inv,
-                                                                         uint32_t *__restrict__ classes)
-{
-    const int l = threadIdx.x & 15;
-    const int64_t item = (int64_t)blockIdx.x * PBLK_ITEMS + (threadIdx.x >> 4);
-    const bool live = item < Q * B;             // the same for the 16 lanes of a DPP row
-    // one launch holds fewer than 2^31 items (the host cuts longer calls): a 32-bit division
-    const uint32_t q32 = live ? (uint32_t)item / (uint32_t)B : 0u;
-    const int64_t q = q32, j = live ? item - q * B : 0;
-    const uint4 set = reinterpret_cast<const uint4 *>(sets)[q];
-    const bool inside = live && set.x < T && set.y < T && set.z < T && set.w < T;
-    uint32_t c[PAT_CLASSES];
-#pragma unroll
-    for (int i = 0; i < PAT_CLASSES; ++i) c[i] = 0;
-    if (inside) {
-        const int64_t s0 = starts[j], s1 = starts[j + 1];       // s0 < s1
-        const int64_t w0 = s0 >> 5, w1 = (s1 - 1) >> 5;
-        const uint32_t first = 0xFFFFFFFFu << (uint32_t)(s0 & 31);
-        const uint32_t last = 0xFFFFFFFFu >> (31u - (uint32_t)((s1 - 1) & 31));
-        const uint32_t *ra = planes3 + (int64_t)set.x * W * 3, *rb = planes3 + (int64_t)set.y * W * 3;
-        const uint32_t *rc = planes3 + (int64_t)set.z * W * 3, *rd = planes3 + (int64_t)set.w * W * 3;
-        for (int64_t w = w0 + l; w <= w1; w += 16) {
-            const PlaneRec a = pblk_load(ra, w), b = pblk_load(rb, w), cc = pblk_load(rc, w), d = pblk_load(rd, w);
-            uint32_t valid = ~(a.miss | b.miss | cc.miss | d.miss);
-            valid &= w == w0 ? first : 0xFFFFFFFFu;
-            valid &= w == w1 ? last : 0xFFFFFFFFu;
-            const PatternMasks k = pattern_masks(pblk_eq(a, b), pblk_eq(a, cc), pblk_eq(a, d), pblk_eq(b, cc), pblk_eq(b, d),
-                                                 pblk_eq(cc, d), valid);
-            c[0] += (uint32_t)__popc(k.m[0] & inv);
-#pragma unroll
-            for (int i = 1; i < PAT_CLASSES; ++i) c[i] += (uint32_t)__popc(k.m[i]);
-        }
-    }
-    // every lane of the wavefront is here: the DPP steps read lanes of the own row only, and a row is one item
-    uint32_t total = 0;
-#pragma unroll
-    for (int i = 0; i < PAT_CLASSES; ++i) {
-        c[i] = pattern_row_sum(c[i]);
-        total += c[i];
-    }
-    if (live && l == 0) {
-        uint4 *out = reinterpret_cast<uint4 *>(classes + item * PAT_ROW);
-        out[0] = make_uint4(c[0], c[1], c[2], c[3]);
-        out[1] = make_uint4(c[4], c[5], c[6], c[7]);
-        out[2] = make_uint4(c[8], c[9], c[10], c[11]);
-        out[3] = make_uint4(c[12], c[13], c[14], total);
-    }
 }
 
 // The delete-one-block jackknife of one test.  rows = the B block rows u32[B][16] of the test's set, fetch = how a row

@@ -9,9 +9,10 @@
 // block row is u32[16]: slot k = the count of class k (k = 1..15), slot 0 = their sum.  Blocks are the `starts` of
 // pattern_blocks.hpp.
 //
-// tq_quintet_blocks_kernel: the shape of tq_pattern_blocks_kernel.  A work item is a (set, block) pair, item = set * B +
-// block; 16 lanes per item, four items per wavefront.  Lane l takes the words w0 + l, w0 + l + 16, ... of the block's
-// word range: per word five 12-byte plane records, valid = ~(OR of the missing words) & range mask, the four
+// tq_quintet_blocks_kernel: the shape of tq_block_rows_kernel (block_rows.hpp), written out on its own: as a rule of that
+// template the kernel measured 1 % slower at B = 50 (profiles/quintets/README.md).  A work item is a (set, block) pair,
+// item = set * B + block; 16 lanes per item, four items per wavefront.  Lane l takes the words w0 + l, w0 + l + 16, ...
+// of the block's word range: per word five 12-byte plane records, valid = ~(OR of the missing words) & range mask, the four
 // "differs from x0" words and the six pair-difference words among positions 1..4, the 15 class masks (quintet_masks),
 // 15 popcount-adds.  The 16 lanes are summed with the DPP steps of pattern_row_sum and the group's lane 0 writes the
 // 64-byte row.  No LDS, no atomics, no scratch; every address is 64-bit.  A taxon >= T gives a row of zeros; items past

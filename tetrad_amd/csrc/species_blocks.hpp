@@ -22,11 +22,9 @@
 // S x product of the four largest species sizes < 2^32) bounds the sum of that over the sites.  So no f sum and no class
 // count wraps; only the signed intermediate steps of the inversion rely on the wrap-around.
 //
-// tq_species_blocks_kernel: the shape of tq_pattern_blocks_kernel.  A work item is a (set, block) pair, item = set * B +
-// block; 16 lanes per item, four items per wavefront.  Lane l takes the sites s0 + l, s0 + l + 16, ... of the block: the
-// four species' packed entries (one dword each), the 15 products, 15 adds.  The 16 lanes are summed with the DPP steps of
-// pattern_row_sum, the group's lane 0 inverts and writes the 64-byte row.  No LDS, no atomics, no scratch; every address
-// is 64-bit.
+// The rows are written by tq_block_rows_kernel<SpeciesRule> (block_rows.hpp has the kernel, the table walk and the rule):
+// per site of the block the four species' packed entries, the 15 products, 15 adds; lane 0 inverts the summed f.  A
+// species id >= K, or a row that repeats species so that it breaks the range rule, gives a row of zeros.
 #pragma once
 
 // sum of the four byte products of two packed words: one v_dot4_u32_u8 on the device
@@ -172,44 +170,3 @@ constexpr bool pooled_rule_ok()
     return true;
 }
 static_assert(pooled_rule_ok(), "the inverted partition sums must follow pattern_class");
-
-// tab u32[K][Sp] (VALU form of the species table, current for the resident replicate); offsets i32[K + 1] in lineages;
-// ssets u32[Q][4]; starts i64[B + 1] with 0 <= starts[0] < ... < starts[B] <= S <= Sp (checked on the host), Q * B < 2^31;
-// classes u32[Q][B][16].  A species id >= K, or a row that repeats species so that S x its own lineage product breaks the
-// range rule (species_row_in_range, as the pooling kernels), gives a zero row; items past Q * B store nothing.
-__global__ __launch_bounds__(PBLK_THREADS) void tq_species_blocks_kernel(const uint32_t *__restrict__ tab, int64_t Sp, int64_t S,
-                                                                         uint32_t K, const int32_t *__restrict__ offsets,
-                                                                         const uint32_t *__restrict__ ssets, int64_t Q,
-                                                                         const int64_t *__restrict__ starts, int64_t B,
-                                                                         uint32_t *__restrict__ classes)
-{
-    const int l = threadIdx.x & 15;
-    const int64_t item = (int64_t)blockIdx.x * PBLK_ITEMS + (threadIdx.x >> 4);
-    const bool live = item < Q * B;             // the same for the 16 lanes of a DPP row
-    // one launch holds fewer than 2^31 items (the host cuts longer calls): a 32-bit division
-    const uint32_t q32 = live ? (uint32_t)item / (uint32_t)B : 0u;
-    const int64_t q = q32, j = live ? item - q * B : 0;
-    const uint4 set = reinterpret_cast<const uint4 *>(ssets)[q];
-    const bool inside = live && ((set.x < K) & (set.y < K) & (set.z < K) & (set.w < K)) && species_row_in_range(offsets, set, S);
-    uint32_t f[PAT_CLASSES];
-#pragma unroll
-    for (int i = 0; i < PAT_CLASSES; ++i) f[i] = 0;
-    if (inside) {
-        const int64_t s0 = starts[j], s1 = starts[j + 1];       // s0 < s1 <= S
-        const uint32_t *ta = tab + (int64_t)set.x * Sp, *tb = tab + (int64_t)set.y * Sp;
-        const uint32_t *tc = tab + (int64_t)set.z * Sp, *td = tab + (int64_t)set.w * Sp;
-        for (int64_t s = s0 + l; s < s1; s += 16) pooled_site_f(ta[s], tb[s], tc[s], td[s], f);
-    }
-    // every lane of the wavefront is here: the DPP steps read lanes of the own row only, and a row is one item
-#pragma unroll
-    for (int i = 0; i < PAT_CLASSES; ++i) f[i] = pattern_row_sum(f[i]);
-    if (live && l == 0) {
-        uint32_t c[PAT_ROW];
-        pooled_invert(f, c);
-        uint4 *out = reinterpret_cast<uint4 *>(classes + item * PAT_ROW);
-        out[0] = make_uint4(c[0], c[1], c[2], c[3]);
-        out[1] = make_uint4(c[4], c[5], c[6], c[7]);
-        out[2] = make_uint4(c[8], c[9], c[10], c[11]);
-        out[3] = make_uint4(c[12], c[13], c[14], c[15]);
-    }
-}

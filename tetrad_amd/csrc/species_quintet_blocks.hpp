@@ -24,10 +24,9 @@
 // total take the full multiply (pooled5_mul_full, v_mul_lo_u32), everything else -- the quadruple and quintuple byte
 // products included, whose factors are a triple product and a byte or a pair product -- the 24-bit one.
 //
-// tq_species_quintet_blocks_kernel: the shape of tq_species_blocks_kernel.  A work item is a (set, block) pair, item =
-// set * B + block; 16 lanes per item, four items per wavefront.  Lane l takes the sites s0 + l, s0 + l + 16, ... of the
-// block: one dword per species, the 16 sums.  The 16 lanes are summed with the DPP steps of pattern_row_sum, the group's
-// lane 0 finishes and writes the 64-byte row.  No LDS, no atomics, no scratch; every address is 64-bit.
+// The rows are written by tq_block_rows_kernel<SpeciesQuintetRule> (block_rows.hpp has the kernel, the table walk and the
+// rule): per site of the block one dword per species, the 16 sums; lane 0 finishes the summed f.  A species id >= K, or a
+// row that repeats species so that it breaks the range rule of five, gives a row of zeros.
 #pragma once
 
 // x y modulo 2^32 for any operands (v_mul_lo_u32: quarter rate): where a factor can reach 2^24
@@ -126,52 +125,4 @@ __device__ __forceinline__ bool species_row5_in_range(const int32_t *__restrict_
                        (uint64_t)(offsets[k2 + 1] - offsets[k2]) * (uint64_t)(offsets[k3 + 1] - offsets[k3]) *
                        (uint64_t)(offsets[k4 + 1] - offsets[k4]);
     return (uint64_t)S < (1ull << 32) && p < (1ull << 32) && (uint64_t)S * p < (1ull << 32);
-}
-
-// tab u32[K][Sp] (VALU form of the species table, current for the resident replicate); offsets i32[K + 1] in lineages;
-// ssets5 u32[Q][5]; starts i64[B + 1] with 0 <= starts[0] < ... < starts[B] <= S <= Sp (checked on the host), Q * B < 2^31;
-// classes u32[Q][B][16].  A species id >= K, or a row that repeats species so that S x its own lineage product breaks the
-// range rule, gives a zero row; items past Q * B store nothing.
-__global__ __launch_bounds__(PBLK_THREADS) void tq_species_quintet_blocks_kernel(const uint32_t *__restrict__ tab, int64_t Sp,
-                                                                                 int64_t S, uint32_t K,
-                                                                                 const int32_t *__restrict__ offsets,
-                                                                                 const uint32_t *__restrict__ ssets5, int64_t Q,
-                                                                                 const int64_t *__restrict__ starts, int64_t B,
-                                                                                 uint32_t *__restrict__ classes)
-{
-    const int l = threadIdx.x & 15;
-    const int64_t item = (int64_t)blockIdx.x * PBLK_ITEMS + (threadIdx.x >> 4);
-    const bool live = item < Q * B;             // the same for the 16 lanes of a DPP row
-    // one launch holds fewer than 2^31 items (the host cuts longer calls): a 32-bit division
-    const uint32_t q32 = live ? (uint32_t)item / (uint32_t)B : 0u;
-    const int64_t q = q32, j = live ? item - q * B : 0;
-    // a 20-byte row has no 16-byte alignment: five dwords (row 0 is read by the lanes of a dead item: Q >= 1)
-    const uint32_t *set = ssets5 + q * QNT_TAXA;
-    const uint32_t k0 = set[0], k1 = set[1], k2 = set[2], k3 = set[3], k4 = set[4];
-    const bool inside = live && ((k0 < K) & (k1 < K) & (k2 < K) & (k3 < K) & (k4 < K)) &&
-                        species_row5_in_range(offsets, k0, k1, k2, k3, k4, S);
-    uint32_t f[PAT_ROW];
-#pragma unroll
-    for (int i = 0; i < PAT_ROW; ++i) f[i] = 0;
-    if (inside) {
-        const int64_t s0 = starts[j], s1 = starts[j + 1];       // s0 < s1 <= S
-        const uint32_t *r0 = tab + (int64_t)k0 * Sp, *r1 = tab + (int64_t)k1 * Sp, *r2 = tab + (int64_t)k2 * Sp;
-        const uint32_t *r3 = tab + (int64_t)k3 * Sp, *r4 = tab + (int64_t)k4 * Sp;
-        for (int64_t s = s0 + l; s < s1; s += 16) pooled5_site_f(r0[s], r1[s], r2[s], r3[s], r4[s], f);
-    }
-    // every lane of the wavefront is here: the DPP steps read lanes of the own row only, and a row is one item
-#pragma unroll
-    for (int i = 0; i < PAT_ROW; ++i) f[i] = pattern_row_sum(f[i]);
-    if (live && l == 0) {
-        uint32_t c[PAT_ROW];
-        pooled5_finish(f, c);
-        uint4 *out = reinterpret_cast<uint4 *>(classes + item * PAT_ROW);
-        // (pins each group of four, as in tq_quintet_blocks_kernel: four aligned 16-byte stores)
-#pragma unroll
-        for (int i = 0; i < PAT_ROW; i += 4) asm volatile("" : "+v"(c[i]), "+v"(c[i + 1]), "+v"(c[i + 2]), "+v"(c[i + 3]));
-        out[0] = make_uint4(c[0], c[1], c[2], c[3]);
-        out[1] = make_uint4(c[4], c[5], c[6], c[7]);
-        out[2] = make_uint4(c[8], c[9], c[10], c[11]);
-        out[3] = make_uint4(c[12], c[13], c[14], c[15]);
-    }
 }

@@ -47,11 +47,12 @@
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
-//   species_blocks.hpp tq_species_blocks_kernel: pooled class rows of species sets per block of sites from the species table
+//   pattern_blocks.hpp the class masks of a quartet's block rows + tq_jackknife_kernel: the block jackknife of D
 //   quintet_blocks.hpp tq_quintet_blocks_kernel: five-taxon class rows per block of sites + the mask form of
 //                 tq_jackknife_kernel: the block jackknife on sums of slots (DFOIL, partitioned D)
-//   species_quintet_blocks.hpp tq_species_quintet_blocks_kernel: pooled five-taxon class rows of species sets per block of
-//                 sites from the species table
+//   species_blocks.hpp, species_quintet_blocks.hpp the arithmetic of pooled four- and five-species block rows (species table)
+//   block_rows.hpp tq_block_rows_kernel<Rule>: the per-block class-row kernel, its plane walk and table walk, and the
+//                 rules of quartets, species and species quintets on the arithmetic of the headers above
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
@@ -110,6 +111,7 @@ namespace {
 #include "species_blocks.hpp"
 #include "quintet_blocks.hpp"
 #include "species_quintet_blocks.hpp"
+#include "block_rows.hpp"
 #include "scf.hpp"
 
 }  // namespace
@@ -1590,29 +1592,29 @@ int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, in
     if (block_set_species(kind))
         if (int rc = ensure_species_table(ctx, stream)) return rc;
     const int64_t per = ((int64_t)1 << 30) / B;         // >= 2^18 sets
-    const uint32_t *planes3 = ctx->nat.planes3;
     const int64_t *starts = ctx->d_bstarts;
     for (int64_t q0 = 0; q0 < Q; q0 += per) {
         const int64_t n = (Q - q0) < per ? (Q - q0) : per;
         const dim3 grid((unsigned)((n * B + PBLK_ITEMS - 1) / PBLK_ITEMS)), block(PBLK_THREADS);
         const uint32_t *sets = dq + q0 * block_set_width(kind);
         uint32_t *rows = d_classes + (size_t)q0 * (size_t)B * PAT_ROW;
+        const auto launch = [&](auto rule) {
+            hipLaunchKernelGGL(tq_block_rows_kernel<decltype(rule)>, grid, block, 0, stream, rule, sets, n, starts, B, rows);
+        };
         switch (kind) {
         case BLK_SPECIES:
-            hipLaunchKernelGGL(tq_species_blocks_kernel, grid, block, 0, stream, (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S,
-                               (uint32_t)ctx->sp_K, species_lineage_offsets(ctx), sets, n, starts, B, rows);
+            launch(SpeciesRule{{ctx->d_sp_tab, ctx->nat.Sp, ctx->S, (uint32_t)ctx->sp_K, species_lineage_offsets(ctx)}});
             break;
         case BLK_SPECIES_QUINTET:
-            hipLaunchKernelGGL(tq_species_quintet_blocks_kernel, grid, block, 0, stream, (const uint32_t *)ctx->d_sp_tab,
-                               ctx->nat.Sp, ctx->S, (uint32_t)ctx->sp_K, species_lineage_offsets(ctx), sets, n, starts, B, rows);
+            launch(SpeciesQuintetRule{{ctx->d_sp_tab, ctx->nat.Sp, ctx->S, (uint32_t)ctx->sp_K, species_lineage_offsets(ctx)}});
             break;
         case BLK_QUINTET:
-            hipLaunchKernelGGL(tq_quintet_blocks_kernel, grid, block, 0, stream, planes3, ctx->nat.W, (uint32_t)ctx->T, sets, n,
-                               starts, B, rows);
+            // (not a rule yet: as one its kernel measured slower, see quintet_blocks.hpp)
+            hipLaunchKernelGGL(tq_quintet_blocks_kernel, grid, block, 0, stream, (const uint32_t *)ctx->nat.planes3, ctx->nat.W,
+                               (uint32_t)ctx->T, sets, n, starts, B, rows);
             break;
         default:
-            hipLaunchKernelGGL(tq_pattern_blocks_kernel, grid, block, 0, stream, planes3, ctx->nat.W, (uint32_t)ctx->T, sets, n,
-                               starts, B, ctx->count_invariant ? 0xFFFFFFFFu : 0u, rows);
+            launch(QuartetRule{{ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T}, ctx->count_invariant ? 0xFFFFFFFFu : 0u});
         }
         TQ_HIP(ctx, hipGetLastError());
     }
