@@ -106,7 +106,7 @@ struct SplitTable {
     hipError_t alloc(const tq_ctx *ctx, int32_t words, int64_t chunk_items)
     {
         W = words;
-        hash_bits = ctx->cons_hash_bits;
+        hash_bits = ctx->opt.cons_hash_bits;
         slots = 64;
         while (slots < 2 * max_splits) slots *= 2;
         gather_cap = std::max<int64_t>(1, CONS_GATHER_BYTES / (W * 8));
@@ -144,7 +144,7 @@ struct SplitTable {
     // everything a reset forgets; with a context behind clear(), and the hash width is read again
     void forget(const tq_ctx *ctx)
     {
-        if (ctx) hash_bits = ctx->cons_hash_bits;
+        if (ctx) hash_bits = ctx->opt.cons_hash_bits;
         host.clear();
         dev_entries = unresolved = 0;
         overflow = false;
@@ -165,7 +165,6 @@ struct SplitTable {
     {
         nun = 0;
         if (!order.pending) return TQ_OK;
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
         TQ_HIP(ctx, order.sync());
         dev_entries = std::min<int64_t>((int64_t)p_ctr[CONS_CTR_CLAIMS], max_splits);
         if (p_ctr[CONS_CTR_OVERFLOW]) return overflowed(ctx, who);
@@ -176,7 +175,7 @@ struct SplitTable {
             const int64_t n = std::min<int64_t>(gather_cap, nun - first);
             hipLaunchKernelGGL(tq_cons_gather_kernel, dim3((unsigned)((n * W + CONS_THREADS - 1) / CONS_THREADS)),
                                dim3(CONS_THREADS), 0, st, (const uint32_t *)d_unres, first, n, d_masks, W, d_gather.get());
-            TQ_HIP(ctx, hipGetLastError());
+            TQ_LAUNCHED(ctx, who);
             TQ_HIP(ctx, hipMemcpyAsync(p_gather, d_gather, (size_t)n * W * 8, hipMemcpyDeviceToHost, st));
             TQ_HIP(ctx, hipStreamSynchronize(st));
             for (int64_t e = 0; e < n; ++e) {

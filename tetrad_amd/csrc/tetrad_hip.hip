@@ -55,6 +55,20 @@
 //                 rules of quartets, species and species quintets on the arithmetic of the headers above
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
+// The rules of the C boundary, each written once below:
+//   api()          every entry point that can allocate host memory or that touches the device runs its body under this
+//                  guard: the context's device is selected (no context: host back ends, context-free calls) and no
+//                  exception leaves extern "C".  std::bad_alloc gives TQ_ERR_OOM "<name>: out of host memory";
+//                  std::length_error (a size past max_size(): more memory was asked for than exists) gives TQ_ERR_OOM
+//                  and any other std::exception TQ_ERR_INVALID_ARG, both with "<name>: <what()>".  Helpers below a
+//                  guarded entry point neither select the device nor catch.  Accessors that copy scalars stay bare.
+//   TQ_HIP / TQ_HIPF / TQ_LAUNCHED   early-return checks of a HIP call ("<call> failed: ..." / "<who>: ...") and of the
+//                  launches before it ("<who>: launch failed: ..."); hipErrorOutOfMemory maps to TQ_ERR_OOM, anything
+//                  else to TQ_ERR_HIP.  The accumulator creates hold their object in a std::unique_ptr and release it
+//                  into *out on success; where a failure must release context state (free_data, free_source) an inner
+//                  function returns early and its caller frees.
+//   Options / OPTION_TABLE   the option fields with their defaults, and the one table tq_set_option looks names up in.
+//
 // Bounds: the scan is L2 / LDS-atomic / VALU work on a <= 40 MB resident matrix (HBM only on
 // first touch), the singular-value stage is f64 VALU.  Algorithmic bytes per quartet: 4*S + 48
 // (SURVEY.md 8d).  DESIGN.md section 4 has the per-kernel description and measurements.
@@ -71,8 +85,10 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -122,6 +138,59 @@ namespace {
 enum { TAG_ORIGIN = -1, TAG_ORDER = 0, TAG_SCAN = 1, TAG_BIDIAG = 2, TAG_BDSQR = 3, TAG_SCORE = 4, TAG_COUNT = 5 };
 
 struct tq_ctx {
+    // What tq_set_option sets (OPTION_TABLE below names the fields and their legal values).  These initialisers are the only
+    // place a default is written: "0 = default" reads it from a default-constructed Options.
+    struct Options {
+        int nrep = 1;
+        int waves_per_cu = 0;           // 0 = from the occupancy query
+        int phases = 3;                 // diagnostics only: 1 = scan kernel only, 2 = SVD kernel only
+        int scan_method = -1;           // 0 = EXEC-masked slot per site, 1 = set-bit walk, 6 = bank-private counters (scan_pb.hpp,
+                                        // A/B form; 0 / 1 where it does not apply); -1 = 1 if subsample else 0
+        int64_t batch = 1 << 23;        // quartets per scan batch (8 GiB count slab)
+        int order = 1;                  // 1 = process quartets in (a,b,c)-sorted order
+        int scan_f4 = -1;               // the cooperative scan on 12-byte plane records only (SURVEY 8 row f4 as written; scan_f4.hpp):
+                                        // -1 = in subsample mode (c3 scan 5.81 -> 5.58 ms), 1 = in both modes, 0 = never
+        int scan_dp = 1;                // 1 = full-mode batches of >= dp_min_quartets go to tq_scan_dp_kernel (two quartets that share
+                                        // (a,b,c) per wave, one LDS atomic per site and pair)
+        int64_t dp_min_quartets = 32768;
+        int64_t svd_chunk = 1 << 18;    // quartets per pass of the singular-value stage (and per result D2H piece)
+        int svd_streams = 2;            // chunks alternate between this many streams (1 or 2) so that the tail of one
+                                        // chunk's kernels is filled by the next chunk's (each stream has its own scratch)
+        int svd_method = 1;             // 0 = one-sided Jacobi (tq_svd_kernel), 1 = Householder + bidiagonal QR
+        int bidiag_layout = 1;          // 1 = matrix dealt 2 x 2 over the quad (tq_bidiag2_kernel), 0 = four column groups
+        int bdsqr_maxit = 60;           // QR sweeps per singular value before a matrix is declared not converged
+        int scan_wg = 4;                // waves per workgroup of the cooperative scan kernel (1 = one wave per quartet)
+        int64_t wg_min_quartets = 4096; // smaller batches go to the one-wave-per-quartet kernel: a call of a few thousand quartets does not
+                                        // fill the chip and is bound by the latency of one quartet's 25 dependent steps, which the
+                                        // cooperative kernels' per-step barrier and image hand-over only lengthen (1 000 random
+                                        // quartets 0.185 -> 0.164 ms per call, 3 000: 0.198 -> 0.191; the cooperative kernels win from
+                                        // ~4 000 on: tools/experiments/wg_min_threshold.py)
+        int xcd_remap = 1;              // 1: scan workgroups of one XCD take a contiguous part of the sorted order
+        int count_invariant = 0;        // 1: invariant sites (all four bases equal, none missing) are counted as well -- what the reference's
+                                        // count kernels do when their caller's mask leaves such a site open (resolve_quartets.py:59-64);
+                                        // the worker itself always masks them (:218).  One-wave-per-quartet kernel only.
+        int scan_pair = 0;              // 1: two quartets per wavefront (tq_scan_wg2_kernel)
+        int park_t = 1;                 // 1 (default): transposed pattern park of the set-bit walk (conflict-free byte reads at the price of
+                                        // 2 more VALU per counted site: c3 6.79 -> 6.42 ms); 0: lane-contiguous park (A/B)
+        int share_c = 0;                // 1: scan kernel variant that also shares row c inside a workgroup (scan.hpp: SHC;
+                                        // measured slower everywhere -- the kernel is LDS/VALU-bound, not byte-bound -- kept as an A/B option)
+        int svd_wpc = 0;                // blocks per CU of the bidiag / bdsqr grids (0 = one pass per block)
+        int cons_hash_bits = 64;        // consensus: the table key is the 64-bit mask hash cut to this many bits (results never depend on it;
+                                        // read by tq_cons_create / tq_cons_reset)
+        int64_t cons_scratch_bytes = int64_t(256) << 20;   // consensus: device + page-locked bytes of one chunk of trees (read at create)
+        int64_t fit_scratch_bytes = int64_t(64) << 20;     // quartet fit: device bytes of the tables of one chunk of trees (no result depends on it)
+        int64_t qdist_scratch_bytes = int64_t(256) << 20;  // quartet distances: device + page-locked bytes of one chunk of quartets (read at create)
+        int qdist_kslices = 0;          // quartet distances: k slices of the product, 0 = chosen from the compute units (read at every score)
+        int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
+        int stree_search_dev = 1;       // supertree rule "exact" on device rows: 1 = the search kernel, 0 = the same rule on the host (A/B)
+        int species_method = -1;        // -1: MFMA form when every species holds <= SPECIES_MFMA_MAX lineages, else VALU;
+                                        // 0: VALU form (tq_species_pool_kernel); 1: MFMA form (tq_species_mfma_kernel)
+        int species_alleles = 0;        // 1: every sample is two lineages, the alleles of its IUPAC genotype
+        int site_pack = -1;             // -1: tq_set_data builds the packed set when the predicted scan cost falls (pack.hpp), 1: always
+                                        // (while subsample mode is possible), 0: never, and a built set is not used
+        int boot_pack = 0;              // 1: every replicate is packed, -1: when the rule said so for the source (boot_pack_auto),
+                                        // 0: never (the replicate keeps the natural layout only); site_pack = 0 overrides
+    };
     int device = 0;
     std::string err;
     hipDeviceProp_t prop{};
@@ -151,52 +220,17 @@ struct tq_ctx {
     DevBuf<uint32_t> d_sort;        // 4 arrays of cm_quartets u32: keys/idx in, keys/idx out
     DevBuf<char> d_sort_tmp;
     size_t sort_tmp_bytes = 0;
-    int order = 1;                  // 1 = process quartets in (a,b,c)-sorted order
     DevBuf<uint2> d_units;          // cm_quartets + 2 entries: unit list of the joint-histogram scan (scan_dp.hpp), then its count
-    int scan_f4 = -1;               // the cooperative scan on 12-byte plane records only (SURVEY 8 row f4 as written; scan_f4.hpp):
-                                    // -1 = in subsample mode (c3 scan 5.81 -> 5.58 ms), 1 = in both modes, 0 = never
-    int scan_dp = 1;                // 1 = full-mode batches of >= dp_min_quartets go to tq_scan_dp_kernel (two quartets that share
-                                    // (a,b,c) per wave, one LDS atomic per site and pair)
-    int64_t dp_min_quartets = 32768;
     // singular-value stage scratch, sized for one chunk of `svd_chunk` quartets and re-used chunk after
     // chunk (so the bidiagonals / values of a chunk stay in the Infinity Cache between its three kernels):
     // de f64[3*chunk][32], sv f64[3*chunk][16], nsnps u32[chunk]
     DevBuf<double> d_de, d_sv;
     DevBuf<uint32_t> d_nsnps;
     int64_t svd_quartets = 0;
-    int64_t svd_chunk = 1 << 18;    // quartets per pass of the singular-value stage (and per result D2H piece)
-    int svd_streams = 2;            // chunks alternate between this many streams (1 or 2) so that the tail of one
-                                    // chunk's kernels is filled by the next chunk's (each stream has its own scratch)
     hipStream_t sX = nullptr;       // the second stream of the singular-value stage
     hipEvent_t evFork = nullptr, evJoin = nullptr;
-    int svd_method = 1;             // 0 = one-sided Jacobi (tq_svd_kernel), 1 = Householder + bidiagonal QR
-    int bidiag_layout = 1;          // 1 = matrix dealt 2 x 2 over the quad (tq_bidiag2_kernel), 0 = four column groups
-    int bdsqr_maxit = 60;           // QR sweeps per singular value before a matrix is declared not converged
     DevBuf<uint64_t> d_bdsqr_stats;      // diagnostics (option "bdsqr_stats"): {matrices, rotation steps of all lanes,
                                          // lane-slots issued (64 x wave iterations), sweeps} summed over the launches
-    int scan_wg = 4;                // waves per workgroup of the cooperative scan kernel (1 = one wave per quartet)
-    int64_t wg_min_quartets = 4096; // smaller batches go to the one-wave-per-quartet kernel: a call of a few thousand quartets does not
-                                    // fill the chip and is bound by the latency of one quartet's 25 dependent steps, which the
-                                    // cooperative kernels' per-step barrier and image hand-over only lengthen (1 000 random
-                                    // quartets 0.185 -> 0.164 ms per call, 3 000: 0.198 -> 0.191; the cooperative kernels win from
-                                    // ~4 000 on: tools/experiments/wg_min_threshold.py)
-    int xcd_remap = 1;              // 1: scan workgroups of one XCD take a contiguous part of the sorted order
-    int count_invariant = 0;        // 1: invariant sites (all four bases equal, none missing) are counted as well -- what the reference's
-                                    // count kernels do when their caller's mask leaves such a site open (resolve_quartets.py:59-64);
-                                    // the worker itself always masks them (:218).  One-wave-per-quartet kernel only.
-    int scan_pair = 0;              // 1: two quartets per wavefront (tq_scan_wg2_kernel)
-    int park_t = 1;                 // 1 (default): transposed pattern park of the set-bit walk (conflict-free byte reads at the price of
-                                    // 2 more VALU per counted site: c3 6.79 -> 6.42 ms); 0: lane-contiguous park (A/B)
-    int share_c = 0;                // 1: scan kernel variant that also shares row c inside a workgroup (scan.hpp: SHC;
-                                    // measured slower everywhere -- the kernel is LDS/VALU-bound, not byte-bound -- kept as an A/B option)
-    int svd_wpc = 0;                // blocks per CU of the bidiag / bdsqr grids (0 = one pass per block)
-    int cons_hash_bits = 64;        // consensus: the table key is the 64-bit mask hash cut to this many bits (results never depend on it)
-    int64_t cons_scratch_bytes = int64_t(256) << 20;   // consensus: device + page-locked bytes of one chunk of trees
-    int64_t fit_scratch_bytes = int64_t(64) << 20;     // quartet fit: device bytes of the tables of one chunk of trees (results never depend on it)
-    int64_t qdist_scratch_bytes = int64_t(256) << 20;  // quartet distances: device + page-locked bytes of one chunk of quartets (read at create)
-    int qdist_kslices = 0;          // quartet distances: k slices of the product, 0 = chosen from the compute units (read at every score)
-    int stree_lds = 1;              // supertree graph pass: 1 = private LDS counters where a level's cells fit, 0 = global atomics only
-    int stree_search_dev = 1;       // supertree rule "exact" on device rows: 1 = the search kernel, 0 = the same rule on the host (A/B)
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
     const uint32_t *scanned_q = nullptr;
     int64_t scanned_Q = 0;
@@ -211,15 +245,12 @@ struct tq_ctx {
     DevBuf<int32_t> d_sp_members;   // offsets [K+1], then the member samples grouped by species [T], then 2 x offsets [K+1]
     DevBuf<uint32_t> d_sp_tab;      // u32 [K][Sp]: {n_A, n_C, n_G, n_T} per species and site, then u8 [K][4][Sp] (MFMA form):
                                     // two u32 per (species, site) entry, grow-only
-    int species_method = -1;        // -1: MFMA form when every species holds <= SPECIES_MFMA_MAX lineages, else VALU;
-                                    // 0: VALU form (tq_species_pool_kernel); 1: MFMA form (tq_species_mfma_kernel)
     uint64_t data_gen = 0;          // bumped by tq_set_data / tq_bootstrap(_async)
     uint64_t sp_tab_gen = ~0ull;    // data_gen the species table was built from (~0: none)
     // allele mode (option species_alleles): the table is built from the IUPAC source through the
     // resident replicate's site map (src_col in d_boot), every sample two lineages.  The map is the resident replicate's
     // exactly while boot_gen == data_gen (tq_bootstrap_async built what is resident) and boot_src_gen == src_gen (from
     // the source that is still the current one).
-    int species_alleles = 0;
     uint64_t src_gen = 0;           // bumped by tq_set_source
     uint64_t boot_gen = ~0ull;      // data_gen of the last replicate tq_bootstrap_async built (~0: none)
     uint64_t boot_src_gen = ~0ull;  // src_gen it was built from
@@ -227,8 +258,6 @@ struct tq_ctx {
     // lane word, read by the subsample-mode scans while it is current (pk_gen == data_gen).  tq_set_data builds it under site_pack,
     // tq_bootstrap_async under boot_pack (a replicate built without it leaves the set stale).  Everything else reads the
     // natural set.
-    int site_pack = -1;             // -1: tq_set_data builds the set when the predicted scan cost falls (pack.hpp), 1: always
-                                    // (while subsample mode is possible), 0: never, and a built set is not used
     SiteSet pk;                     // its arrays grow only while T stays
     uint64_t pk_gen = ~0ull;        // data_gen the set was built from (~0: none)
     // the most recent scan launch (tq_debug_fetch which = 6): its kernel form (SCAN_FORM_*, 0 = none yet), T * pitch of
@@ -237,8 +266,6 @@ struct tq_ctx {
     int64_t last_scan_tpitch = 0;
     int last_scan_packed = 0;
     // packed set of a device-built replicate (bootstrap.hpp: tq_boot_pack_*): planned on the host at locus level
-    int boot_pack = 0;              // 1: every replicate is packed, -1: when the rule said so for the source (boot_pack_auto),
-                                    // 0: never (the replicate keeps the natural layout only); site_pack = 0 overrides
     bool boot_pack_auto = false;    // pack_pays for the source matrix (tq_set_source): a replicate resamples its loci
     bool pk_from_boot = false;      // the packed set was built by tq_bootstrap_async (d_pk_src is its map)
     PackPlanner boot_plan;
@@ -260,14 +287,8 @@ struct tq_ctx {
     int64_t *h_bstarts_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_bstarts[2] = {nullptr, nullptr};   // the piece's H2D has been consumed
     unsigned bstarts_turn = 0;
-    // options
-    int nrep = 1;
-    int waves_per_cu = 0;           // 0 = from the occupancy query
-    int phases = 3;                 // diagnostics only: 1 = scan kernel only, 2 = SVD kernel only
-    int scan_method = -1;           // 0 = EXEC-masked slot per site, 1 = set-bit walk, 6 = bank-private counters (scan_pb.hpp,
-                                    // A/B form; 0 / 1 where it does not apply); -1 = 1 if subsample else 0
+    Options opt;                    // tq_set_option
     int pb_ok = 0;                  // tq_scan_pb_kernel's counters sit on a 64 KiB LDS boundary (probed once in tq_create)
-    int64_t batch = 1 << 23;        // quartets per scan batch (8 GiB count slab)
     // timing: a sequence of tagged HIP events on the launch stream; the time between two consecutive
     // marks is attributed to the tag of the later one (TAG_ORIGIN starts a sequence)
     bool timing = false;
@@ -278,6 +299,8 @@ struct tq_ctx {
 };
 
 namespace {
+
+using Options = tq_ctx::Options;
 
 std::string g_create_err;
 
@@ -302,6 +325,41 @@ int fail(tq_ctx *ctx, int code, const char *fmt, ...)
             return fail(ctx, e_ == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "%s failed: %s", \
                         #call, hipGetErrorString(e_));                                        \
     } while (0)
+
+// the same for a step of the function `who`, whose name opens the message
+#define TQ_HIPF(ctx, who, call)                                                               \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(ctx, e_ == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)); \
+    } while (0)
+
+// behind a kernel launch, or a group of launches, of the function `who`
+#define TQ_LAUNCHED(ctx, who)                                                                 \
+    do {                                                                                      \
+        hipError_t e_ = hipGetLastError();                                                    \
+        if (e_ != hipSuccess) return fail(ctx, TQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e_)); \
+    } while (0)
+
+// The guard of the C boundary: `body` runs with the context's device selected (`ctx` is NULL for the host back ends and
+// the context-free calls) and no exception leaves it.  std::bad_alloc and std::length_error (a size past max_size(): the
+// request was for more memory than there is) give TQ_ERR_OOM, any other std::exception TQ_ERR_INVALID_ARG; the message
+// opens with `name`.  Every entry point that can allocate host memory or that touches the device goes through it, so
+// neither it nor a helper below it selects the device or catches for itself.
+template <class Body>
+int api(tq_ctx *ctx, const char *name, Body &&body)
+{
+    try {
+        if (ctx) TQ_HIP(ctx, hipSetDevice(ctx->device));
+        return body();
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, TQ_ERR_OOM, "%s: out of host memory", name);
+    } catch (const std::length_error &e) {
+        return fail(ctx, TQ_ERR_OOM, "%s: %s", name, e.what());
+    } catch (const std::exception &e) {
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: %s", name, e.what());
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Pinned host memory pool (process-wide: blocks handed to a caller may outlive any context).
@@ -532,14 +590,14 @@ int make_order(tq_ctx *ctx, const uint32_t *dq, int64_t n, bool input_sorted, hi
     *order = nullptr;
     // below ~32k quartets the sort's twenty small launches cost more than the shared rows save
     // (tools/small_call_order.py: 8 000 quartets 0.34 ms sorted, 0.31 ms in natural order; 62 500: 1.1 vs 2.4 ms)
-    if (!ctx->order || n < 32768 || ctx->T > 65535 || input_sorted) return TQ_OK;
+    if (!ctx->opt.order || n < 32768 || ctx->T > 65535 || input_sorted) return TQ_OK;
     uint32_t *keys_in = ctx->d_sort, *idx_in = keys_in + ctx->cm_quartets;
     uint32_t *keys_out = idx_in + ctx->cm_quartets, *idx_out = keys_out + ctx->cm_quartets;
     const uint64_t T = (uint64_t)ctx->T;
     const int with_c = T * T * T <= 0xFFFFFFFFull;
     hipLaunchKernelGGL(tq_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dq, n,
                        (uint32_t)ctx->T, with_c, keys_in, idx_in);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     int bits = 1;
     while (bits < 32 && (1ull << bits) < (with_c ? T * T * T : T * T)) ++bits;
     size_t tmp = ctx->sort_tmp_bytes;
@@ -558,7 +616,7 @@ int make_units(tq_ctx *ctx, const uint32_t *dq, int64_t n, bool input_sorted, hi
     const uint64_t T = (uint64_t)ctx->T;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(tq_key_kernel, dim3(blocks), dim3(256), 0, stream, dq, n, (uint32_t)ctx->T, 1, keys_in, idx_in);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     const uint32_t *keys = keys_in, *idx = idx_in;
     uint32_t *flags = keys_out;
     if (!input_sorted) {
@@ -572,12 +630,12 @@ int make_units(tq_ctx *ctx, const uint32_t *dq, int64_t n, bool input_sorted, hi
         flags = keys_in;
     }
     hipLaunchKernelGGL(tq_dp_flag_kernel, dim3(blocks), dim3(256), 0, stream, keys, idx, dq, n, (uint32_t)ctx->T, flags);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     size_t tmp = ctx->sort_tmp_bytes;
     TQ_HIP(ctx, hipcub::DeviceScan::InclusiveSum(ctx->d_sort_tmp, tmp, flags, flags, (int)n, stream));
     hipLaunchKernelGGL(tq_dp_units_kernel, dim3(blocks), dim3(256), 0, stream, keys, idx, (const uint32_t *)flags, n,
                        ctx->d_units, reinterpret_cast<uint32_t *>(ctx->d_units + ctx->cm_quartets));
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     return TQ_OK;
 }
 
@@ -586,7 +644,7 @@ DevData dev_data(const tq_ctx *ctx)
     DevData d;
     ctx->nat.fill(d, ctx->T);
     d.T = (int32_t)ctx->T;
-    d.inv = ctx->count_invariant ? 0xFFFFFFFFu : 0u;
+    d.inv = ctx->opt.count_invariant ? 0xFFFFFFFFu : 0u;
     return d;
 }
 
@@ -595,7 +653,7 @@ DevData dev_data(const tq_ctx *ctx)
 DevData scan_data(const tq_ctx *ctx, int subsample)
 {
     DevData d = dev_data(ctx);
-    if (subsample && ctx->site_pack && ctx->pk.rows && ctx->pk_gen == ctx->data_gen) ctx->pk.fill(d, ctx->T);
+    if (subsample && ctx->opt.site_pack && ctx->pk.rows && ctx->pk_gen == ctx->data_gen) ctx->pk.fill(d, ctx->T);
     return d;
 }
 
@@ -605,9 +663,9 @@ static_assert(SCAN_WAVE == WAVE && SCAN_TILE == TILE && SCAN_PB_NW == PB_NW && S
 // the options choose_scan reads
 ScanKnobs scan_knobs(const tq_ctx *ctx)
 {
-    return {ctx->scan_pair, ctx->scan_wg, ctx->scan_method, ctx->scan_f4, ctx->scan_dp, ctx->park_t, ctx->share_c,
-            ctx->count_invariant, ctx->waves_per_cu, ctx->nrep, ctx->order, ctx->wg_min_quartets, ctx->dp_min_quartets,
-            ctx->pb_ok, ctx->xcd_remap, ctx->prop.multiProcessorCount};
+    const Options &o = ctx->opt;
+    return {o.scan_pair, o.scan_wg, o.scan_method, o.scan_f4, o.scan_dp, o.park_t, o.share_c, o.count_invariant, o.waves_per_cu,
+            o.nrep, o.order, o.wg_min_quartets, o.dp_min_quartets, ctx->pb_ok, o.xcd_remap, ctx->prop.multiProcessorCount};
 }
 
 // remembers which kernel form takes the batch and the layout set it reads (a test hook; decides nothing)
@@ -621,7 +679,7 @@ void note_scan(tq_ctx *ctx, int form, const DevData &d)
 template <typename K>
 int grid_for(tq_ctx *ctx, K kern, int64_t items, int64_t *grid, int wpc_kernel = 0)
 {
-    int wpc = wpc_kernel > 0 ? wpc_kernel : ctx->waves_per_cu;
+    int wpc = wpc_kernel > 0 ? wpc_kernel : ctx->opt.waves_per_cu;
     if (wpc <= 0) {
         int nb = 0;
         TQ_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, WAVE, 0));
@@ -742,7 +800,7 @@ int launch_scan(tq_ctx *ctx, const ScanPlan &p, const DevData &d, const uint32_t
     } else {
         hipLaunchKernelGGL(k->wg, dim3((unsigned)p.grid), dim3(p.threads), 0, stream, d, dq, order, Q, ctx->d_cm, p.xcd_chunk);
     }
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     return TQ_OK;
 }
 
@@ -752,18 +810,16 @@ int probe_scan_pb(tq_ctx *ctx)
 {
     DevBuf<uint32_t> d;
     uint32_t h[2] = {0, 0};
+    const char *who = "probe of tq_scan_pb_kernel";
     TQ_HIP(ctx, d.alloc(2));
-    hipError_t e = hipMemset(d, 0, sizeof h);
-    if (e == hipSuccess) {
-        DevData none{};
-        hipLaunchKernelGGL(tq_scan_pb_kernel<false>, dim3(1), dim3(PB_NW * WAVE), 0, 0, none, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d.get());
-        hipLaunchKernelGGL(tq_scan_pb_kernel<true>, dim3(1), dim3(PB_NW * WAVE), 0, 0, none, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d + 1);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "probe of tq_scan_pb_kernel failed: %s", hipGetErrorString(e));
+    TQ_HIPF(ctx, who, hipMemset(d, 0, sizeof h));
+    DevData none{};
+    hipLaunchKernelGGL(tq_scan_pb_kernel<false>, dim3(1), dim3(PB_NW * WAVE), 0, 0, none, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d.get());
+    hipLaunchKernelGGL(tq_scan_pb_kernel<true>, dim3(1), dim3(PB_NW * WAVE), 0, 0, none, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, (int64_t)-1, (uint32_t *)nullptr, (int64_t)0, d + 1);
+    TQ_LAUNCHED(ctx, who);
+    TQ_HIPF(ctx, who, hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost));
     ctx->pb_ok = (h[0] == 0x80000000u && h[1] == 0x80000000u) ? 1 : -1;
     return TQ_OK;
 }
@@ -775,7 +831,7 @@ int launch_scan_dp(tq_ctx *ctx, const uint32_t *dq, int64_t Q, hipStream_t strea
     hipLaunchKernelGGL(tq_scan_dp_kernel<DP_NW>, dim3((unsigned)scan_dp_grid(Q)), dim3(DP_NW * WAVE), 0, stream, d, dq,
                        (const uint2 *)ctx->d_units, reinterpret_cast<const uint32_t *>(ctx->d_units + ctx->cm_quartets),
                        ctx->d_cm);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     return TQ_OK;
 }
 
@@ -789,7 +845,7 @@ int launch_svd(tq_ctx *ctx, const uint32_t *cm, const uint32_t *dq, int64_t n, c
     int rc = grid_for(ctx, kern, (n + QPW - 1) / QPW, &grid);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WAVE), 0, stream, cm, dq, n, (int32_t)ctx->scanned_T, out);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     return mark(ctx, TAG_BIDIAG, stream, lane);
 }
 
@@ -803,32 +859,32 @@ int launch_hqr(tq_ctx *ctx, const uint32_t *cm, const uint32_t *dq, int64_t n, c
     double *sv = ctx->d_sv + (size_t)lane * (size_t)ctx->svd_quartets * 48;
     uint32_t *nsnps = ctx->d_nsnps + (size_t)lane * (size_t)ctx->svd_quartets;
     int64_t grid;
-    auto k1 = ctx->bidiag_layout ? tq_bidiag2_kernel<DEBUG> : tq_bidiag_kernel<DEBUG>;
+    auto k1 = ctx->opt.bidiag_layout ? tq_bidiag2_kernel<DEBUG> : tq_bidiag_kernel<DEBUG>;
     // one pass per block unless told otherwise: the work per pass varies (QR iterations), and the
     // hardware dispatcher balances it better than a static grid-stride loop (3.8 ms vs 5.1 ms per 1e6)
-    const int svd_wpc = ctx->svd_wpc > 0 ? ctx->svd_wpc : (1 << 20);
+    const int svd_wpc = ctx->opt.svd_wpc > 0 ? ctx->opt.svd_wpc : (1 << 20);
     const int tsplit = n < 32768 ? 1 : 0;          // small batches: one block per (pass, flattening), tq_bidiag_kernel
     int rc = grid_for(ctx, k1, (tsplit ? 3 : 1) * ((n + 15) / 16), &grid, svd_wpc);
     if (rc) return rc;
     hipLaunchKernelGGL(k1, dim3((unsigned)grid), dim3(WAVE), 0, stream, cm, n, de, nsnps, out.cmats, tsplit);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     if ((rc = mark(ctx, TAG_BIDIAG, stream, lane))) return rc;
     const int64_t nmat = 3 * n;
     rc = grid_for(ctx, tq_bdsqr_kernel, (nmat + WAVE - 1) / WAVE, &grid, svd_wpc);
     if (rc) return rc;
     hipLaunchKernelGGL(tq_bdsqr_kernel, dim3((unsigned)grid), dim3(WAVE), 0, stream, (const double *)de, nmat, sv,
-                       ctx->bdsqr_maxit, (unsigned long long *)ctx->d_bdsqr_stats.get());
-    TQ_HIP(ctx, hipGetLastError());
+                       ctx->opt.bdsqr_maxit, (unsigned long long *)ctx->d_bdsqr_stats.get());
+    TQ_LAUNCHED(ctx, __func__);
     if ((rc = mark(ctx, TAG_BDSQR, stream, lane))) return rc;
     hipLaunchKernelGGL(tq_score_kernel<DEBUG>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                        (const double *)sv, (const uint32_t *)nsnps, dq, n, (int32_t)ctx->scanned_T, out);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     return mark(ctx, TAG_SCORE, stream, lane);
 }
 
 bool diagnostic_mode(const tq_ctx *ctx)
 {
-    return (ctx->scan_method >= 2 && ctx->scan_method <= 5) || ctx->phases != 3;
+    return (ctx->opt.scan_method >= 2 && ctx->opt.scan_method <= 5) || ctx->opt.phases != 3;
 }
 
 OutPtrs offset_out(const OutPtrs &o, int64_t q0)
@@ -852,14 +908,14 @@ int check_ready(tq_ctx *ctx, int subsample)
     return TQ_OK;
 }
 
-// Stage 1 of a pass: ordering + site scan of quartets dq[0..n) into the count slab (n <= ctx->batch).
+// Stage 1 of a pass: ordering + site scan of quartets dq[0..n) into the count slab (n <= ctx->opt.batch).
 int stage_scan(tq_ctx *ctx, const uint32_t *dq, int64_t n, int subsample, bool input_sorted, hipStream_t stream)
 {
     int rc = ensure_cm(ctx, n);
     if (rc) return rc;
     ctx->scanned_Q = 0;
     if ((rc = mark(ctx, TAG_ORIGIN, stream))) return rc;
-    if (ctx->phases & 1) {
+    if (ctx->opt.phases & 1) {
         const DevData d = scan_data(ctx, subsample);
         const ScanPlan plan = choose_scan(scan_knobs(ctx), {ctx->T, d.pitch, ctx->nat.Sp, n, subsample, input_sorted});
         const uint32_t *order = nullptr;
@@ -879,14 +935,14 @@ int stage_scan(tq_ctx *ctx, const uint32_t *dq, int64_t n, int subsample, bool i
 }
 
 // lineages per sample of the species map: 2 in allele mode (one per allele of a diploid genotype)
-inline int species_lineages(const tq_ctx *ctx) { return ctx->species_alleles ? 2 : 1; }
+inline int species_lineages(const tq_ctx *ctx) { return ctx->opt.species_alleles ? 2 : 1; }
 
 // Species mode: the map is set, matches the resident replicate and the pooled counts fit u32
 // (allele mode: sizes in lineages = 2 x samples, and the resident data must be a device-built replicate of the current
 // source -- the option can be set after the map, so everything is checked here, at call time)
 int species_ready(tq_ctx *ctx, const char *who)
 {
-    if (ctx->species_alleles) {
+    if (ctx->opt.species_alleles) {
         if (!ctx->d_seqarr)
             return fail(ctx, TQ_ERR_NO_DATA, "%s: species_alleles needs the IUPAC source (call tq_set_source, then tq_bootstrap)", who);
         if (!ctx->have_data || ctx->boot_gen != ctx->data_gen || ctx->boot_src_gen != ctx->src_gen)
@@ -907,7 +963,7 @@ int species_ready(tq_ctx *ctx, const char *who)
         return fail(ctx, TQ_ERR_INVALID_ARG,
                     "%s: pooled counts may exceed u32: S=%lld x product of the four largest species sizes %llu >= 2^32%s",
                     who, (long long)ctx->S, (unsigned long long)bound, lin == 2 ? " (sizes in lineages: 2 per sample)" : "");
-    if (ctx->species_method == 1 && lin * ctx->sp_max > SPECIES_MFMA_MAX)
+    if (ctx->opt.species_method == 1 && lin * ctx->sp_max > SPECIES_MFMA_MAX)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: species_method 1 (MFMA, i8 operands) takes species of at most %d lineages, "
                     "the map has one of %d%s", who, SPECIES_MFMA_MAX, lin * (int)ctx->sp_max,
                     lin == 2 ? " (species_alleles: 2 per sample, i.e. at most 5 samples)" : "");
@@ -926,7 +982,7 @@ int ensure_species_table(tq_ctx *ctx, hipStream_t stream)
             TQ_HIP(ctx, ctx->d_sp_tab.grow((size_t)entries * 2));
         }
         const int32_t *members = ctx->d_sp_members + ctx->sp_K + 1;
-        if (ctx->species_alleles)       // species_ready: d_boot holds the site map of the resident replicate
+        if (ctx->opt.species_alleles)       // species_ready: d_boot holds the site map of the resident replicate
             hipLaunchKernelGGL(tq_species_allele_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
                                (const uint8_t *)ctx->d_seqarr, ctx->src_S0,
                                (const uint32_t *)(ctx->d_boot + 2 * (ctx->nloci + 1)), ctx->S, Sp, members,
@@ -936,7 +992,7 @@ int ensure_species_table(tq_ctx *ctx, hipStream_t stream)
             hipLaunchKernelGGL(tq_species_table_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream,
                                (const uint8_t *)ctx->nat.nib5, Sp, ctx->S, members, (const int32_t *)ctx->d_sp_members,
                                (int32_t)ctx->sp_K, ctx->d_sp_tab, (uint8_t *)(ctx->d_sp_tab + entries));
-        TQ_HIP(ctx, hipGetLastError());
+        TQ_LAUNCHED(ctx, __func__);
         ctx->sp_tab_gen = ctx->data_gen;
     }
     return TQ_OK;
@@ -959,7 +1015,7 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
     if ((rc = ensure_species_table(ctx, stream))) return rc;
     if ((rc = mark(ctx, TAG_ORDER, stream))) return rc;
     const int lin = species_lineages(ctx);
-    const bool mfma = ctx->species_method == 1 || (ctx->species_method < 0 && lin * ctx->sp_max <= SPECIES_MFMA_MAX);
+    const bool mfma = ctx->opt.species_method == 1 || (ctx->opt.species_method < 0 && lin * ctx->sp_max <= SPECIES_MFMA_MAX);
     const int32_t *offsets = species_lineage_offsets(ctx);      // read for the per-row range rule only
     if (mfma)
         hipLaunchKernelGGL(tq_species_mfma_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
@@ -968,7 +1024,7 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
     else
         hipLaunchKernelGGL(tq_species_pool_kernel, dim3((unsigned)n), dim3(WAVE * SPECIES_WAVES), 0, stream,
                            (const uint32_t *)ctx->d_sp_tab, ctx->nat.Sp, ctx->S, dsq, n, (int32_t)ctx->sp_K, offsets, ctx->d_cm);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     if ((rc = mark(ctx, TAG_SCAN, stream))) return rc;
     ctx->scanned_q = dsq;
     ctx->scanned_Q = n;
@@ -980,10 +1036,10 @@ int stage_species(tq_ctx *ctx, const uint32_t *dsq, int64_t n, hipStream_t strea
 // cuts by it and HostSink sizes its staging and picks its single-piece path by it).
 int64_t svd_chunk_rows(const tq_ctx *ctx, int64_t n)
 {
-    int64_t chunk = ctx->svd_chunk < n ? ctx->svd_chunk : n;
+    int64_t chunk = ctx->opt.svd_chunk < n ? ctx->opt.svd_chunk : n;
     // a mid-size batch that would be one chunk is cut in two halves, one per stream: their tails fill each other
     // (125k quartets 1.58 -> 1.53 ms, 300k 3.45 -> 3.35 ms) and the host API gets a result piece to copy early
-    if (ctx->svd_streams > 1 && n >= 65536 && n < 2 * ctx->svd_chunk && chunk > (n + 1) / 2) chunk = (n + 1) / 2;
+    if (ctx->opt.svd_streams > 1 && n >= 65536 && n < 2 * ctx->opt.svd_chunk && chunk > (n + 1) / 2) chunk = (n + 1) / 2;
     return chunk < 1 ? 1 : chunk;
 }
 
@@ -1008,7 +1064,7 @@ int stage_svd(tq_ctx *ctx, int64_t q0, int64_t n, bool debug, const OutPtrs &out
     if (diag && !out.flags)
         return fail(ctx, TQ_ERR_INVALID_ARG, "a timing-diagnostic mode is set (scan_method 2..5 or phases 1 / 2): its rows are "
                                              "not results and are only handed out with a flags array (TQ_FLAG_INVALID_DIAGNOSTIC)");
-    const bool two = ctx->svd_streams > 1 && n > chunk;
+    const bool two = ctx->opt.svd_streams > 1 && n > chunk;
     if (two) {
         TQ_HIP(ctx, hipEventRecord(ctx->evFork, stream));
         TQ_HIP(ctx, hipStreamWaitEvent(ctx->sX, ctx->evFork, 0));
@@ -1018,19 +1074,19 @@ int stage_svd(tq_ctx *ctx, int64_t q0, int64_t n, bool debug, const OutPtrs &out
         const int64_t cn = (n - c0) < chunk ? (n - c0) : chunk;
         const int lane = two ? (int)(ci & 1) : 0;
         hipStream_t st = lane ? ctx->sX : stream;
-        if (!(ctx->phases & 2)) {                   // no score kernel runs: flag the rows here
+        if (!(ctx->opt.phases & 2)) {                   // no score kernel runs: flag the rows here
             if (hipMemsetAsync(out.flags + c0, TQ_FLAG_INVALID_DIAGNOSTIC, (size_t)cn, st) != hipSuccess) {
                 rc = fail(ctx, TQ_ERR_HIP, "hipMemsetAsync(flags) failed");
                 break;
             }
         }
-        if (ctx->phases & 2) {
+        if (ctx->opt.phases & 2) {
             const uint32_t *cm = ctx->d_cm + (size_t)(q0 + c0) * 256;
             const uint32_t *dq = ctx->scanned_q + (q0 + c0) * 4;
             OutPtrs o = offset_out(out, c0);
             o.flag_or = diag ? (uint32_t)TQ_FLAG_INVALID_DIAGNOSTIC : 0u;
             if ((rc = mark(ctx, TAG_ORIGIN, st, lane))) break;
-            if (ctx->svd_method == 0)
+            if (ctx->opt.svd_method == 0)
                 rc = debug ? launch_svd<true>(ctx, cm, dq, cn, o, st, lane) : launch_svd<false>(ctx, cm, dq, cn, o, st, lane);
             else
                 rc = debug ? launch_hqr<true>(ctx, cm, dq, cn, o, st, lane) : launch_hqr<false>(ctx, cm, dq, cn, o, st, lane);
@@ -1049,7 +1105,7 @@ struct NoChunkHook {
     int operator()(int64_t, int64_t, hipStream_t) const { return TQ_OK; }
 };
 
-// One pass of the path over quartets dq[0..Q) with device outputs: scan batches of <= ctx->batch quartets,
+// One pass of the path over quartets dq[0..Q) with device outputs: scan batches of <= ctx->opt.batch quartets,
 // each followed by its singular-value stage.
 template <typename F>
 int launch(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool debug, bool input_sorted,
@@ -1059,7 +1115,7 @@ int launch(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool debug
     if (rc) return rc;
     if (Q == 0) return TQ_OK;
     if (ctx->timing) ctx->timed_calls++;
-    const int64_t batch = Q < ctx->batch ? Q : ctx->batch;
+    const int64_t batch = Q < ctx->opt.batch ? Q : ctx->opt.batch;
     for (int64_t q0 = 0; q0 < Q; q0 += batch) {
         const int64_t n = (Q - q0) < batch ? (Q - q0) : batch;
         rc = species ? stage_species(ctx, dq + q0 * 4, n, stream) : stage_scan(ctx, dq + q0 * 4, n, subsample, input_sorted, stream);
@@ -1152,7 +1208,7 @@ struct HostSink {
         if (!direct) {
             // what stage_svd will cut this call into: one scan batch of min(Q, batch) rows at a time, each in
             // chunks of svd_chunk_rows(batch rows) -- the last batch may be shorter, never longer
-            const int64_t first_batch = Q < ctx->batch ? Q : ctx->batch;
+            const int64_t first_batch = Q < ctx->opt.batch ? Q : ctx->opt.batch;
             stage_rows = svd_chunk_rows(ctx, first_batch);
             if (Q > first_batch) {
                 const int64_t tail = svd_chunk_rows(ctx, Q % first_batch ? Q % first_batch : first_batch);
@@ -1161,7 +1217,7 @@ struct HostSink {
             // small calls (the reference's distributor hands out chunks of a few thousand quartets,
             // run_inference.py:73-96) are dominated by the number of HIP calls: when the whole call is ONE
             // chunk, the device outputs [rstat | rscor | flags] are one contiguous region -> one copy
-            single = Q <= ctx->batch && stage_rows >= Q && dev->flags &&
+            single = Q <= ctx->opt.batch && stage_rows >= Q && dev->flags &&
                      (const char *)dev->rscor > (const char *)dev->rstat && (const char *)dev->flags > (const char *)dev->rscor;
             off_rscor = single ? (size_t)((const char *)dev->rscor - (const char *)dev->rstat) : (size_t)stage_rows * 8;
             off_flags = single ? (size_t)((const char *)dev->flags - (const char *)dev->rstat) : (size_t)stage_rows * 32;
@@ -1351,14 +1407,14 @@ int debug_to_host(tq_ctx *ctx, const HostScratch &h, int64_t Q, int subsample, b
     return TQ_OK;
 }
 
-// Class rows of quartets dq[0..Q) (species quartets with `species`): scan batches of <= ctx->batch quartets into the
+// Class rows of quartets dq[0..Q) (species quartets with `species`): scan batches of <= ctx->opt.batch quartets into the
 // count slab, each followed on the same stream by the class kernel, which writes at the batch's offset of d_classes.
 // The caller has checked that the data are ready and that no diagnostic mode is set.
 int launch_patterns(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool species, uint32_t *d_classes,
                     hipStream_t stream)
 {
     if (ctx->timing) ctx->timed_calls++;
-    const int64_t batch = Q < ctx->batch ? Q : ctx->batch;
+    const int64_t batch = Q < ctx->opt.batch ? Q : ctx->opt.batch;
     for (int64_t q0 = 0; q0 < Q; q0 += batch) {
         const int64_t n = (Q - q0) < batch ? (Q - q0) : batch;
         int rc = species ? stage_species(ctx, dq + q0 * 4, n, stream) : stage_scan(ctx, dq + q0 * 4, n, subsample, false, stream);
@@ -1366,7 +1422,7 @@ int launch_patterns(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, b
         constexpr int per_block = PAT_THREADS / 16;
         hipLaunchKernelGGL(tq_pattern_class_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(PAT_THREADS), 0,
                            stream, (const uint32_t *)ctx->d_cm, n, d_classes + (size_t)q0 * PAT_ROW);
-        TQ_HIP(ctx, hipGetLastError());
+        TQ_LAUNCHED(ctx, __func__);
     }
     ctx->scanned_Q = 0;          // the slab belongs to this call only
     return TQ_OK;
@@ -1425,26 +1481,27 @@ int patterns_to_host(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t
                      uint32_t *classes)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!sets || !classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    int rc = patterns_ready(ctx, who, subsample, species);
-    if (rc) return rc;
-    if (Q == 0) return TQ_OK;
-    if ((rc = check_set_rows(ctx, who, sets, Q, 4, species))) return rc;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_cls = align_up((size_t)Q * 16, 256);
-    TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)));
-    if ((rc = ensure_streams(ctx))) return rc;
-    char *base = ctx->d_scratch;
-    uint32_t *d_classes = (uint32_t *)(base + o_cls);
-    TQ_HIP(ctx, hipMemcpyAsync(base, sets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
-    rc = launch_patterns(ctx, (const uint32_t *)base, Q, subsample, species, d_classes, ctx->sK);
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->sK);
-        return rc;
-    }
-    TQ_HIP(ctx, hipMemcpyAsync(classes, d_classes, (size_t)Q * PAT_ROW * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->sK));
-    TQ_HIP(ctx, hipStreamSynchronize(ctx->sK));
-    return TQ_OK;
+    return api(ctx, who, [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!sets || !classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+        int rc = patterns_ready(ctx, who, subsample, species);
+        if (rc) return rc;
+        if (Q == 0) return TQ_OK;
+        if ((rc = check_set_rows(ctx, who, sets, Q, 4, species))) return rc;
+        const size_t o_cls = align_up((size_t)Q * 16, 256);
+        TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)));
+        if ((rc = ensure_streams(ctx))) return rc;
+        char *base = ctx->d_scratch;
+        uint32_t *d_classes = (uint32_t *)(base + o_cls);
+        TQ_HIP(ctx, hipMemcpyAsync(base, sets, (size_t)Q * 16, hipMemcpyHostToDevice, ctx->sK));
+        rc = launch_patterns(ctx, (const uint32_t *)base, Q, subsample, species, d_classes, ctx->sK);
+        if (rc) {
+            (void)hipStreamSynchronize(ctx->sK);
+            return rc;
+        }
+        TQ_HIP(ctx, hipMemcpyAsync(classes, d_classes, (size_t)Q * PAT_ROW * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->sK));
+        TQ_HIP(ctx, hipStreamSynchronize(ctx->sK));
+        return TQ_OK;
+    });
 }
 
 // device sets -> device class rows, enqueued on `stream`
@@ -1452,13 +1509,14 @@ int patterns_dev(tq_ctx *ctx, const char *who, const uint32_t *d_sets, int64_t Q
                  uint32_t *d_classes, hipStream_t stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!d_sets || !d_classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    if (int rc = patterns_ready(ctx, who, subsample, species)) return rc;
-    if (Q == 0) return TQ_OK;
-    if (int rc = check_dev_alignment(ctx, who, d_sets, 4, d_classes)) return rc;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = enter_dev_api(ctx, stream)) return rc;      // before any shared scratch is touched
-    return note_dev_api(ctx, stream, launch_patterns(ctx, d_sets, Q, subsample, species, d_classes, stream));
+    return api(ctx, who, [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!d_sets || !d_classes))) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+        if (int rc = patterns_ready(ctx, who, subsample, species)) return rc;
+        if (Q == 0) return TQ_OK;
+        if (int rc = check_dev_alignment(ctx, who, d_sets, 4, d_classes)) return rc;
+        if (int rc = enter_dev_api(ctx, stream)) return rc;      // before any shared scratch is touched
+        return note_dev_api(ctx, stream, launch_patterns(ctx, d_sets, Q, subsample, species, d_classes, stream));
+    });
 }
 
 // the block count of every block-row and jackknife call
@@ -1496,9 +1554,8 @@ int launch_per_test(tq_ctx *ctx, const char *who, Kernel kernel, int threads, in
 {
     if (N == 0) return TQ_OK;
     if (N > (int64_t)0x7FFFFFFF * threads) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: N=%lld tests exceed one launch", who, (long long)N);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(kernel, dim3((unsigned)((N + threads - 1) / threads)), dim3(threads), 0, (hipStream_t)stream, args...);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, who);
     return TQ_OK;
 }
 
@@ -1507,9 +1564,11 @@ template <class Tests>
 int jackknife_to_host(const char *who, const uint32_t *bclasses, int64_t n_sets, int64_t B, const uint32_t *set_of,
                       const Tests tests, int64_t N, double *out)
 {
-    if (int rc = check_dstat_tests(nullptr, who, bclasses && out, n_sets, &B, set_of, tests, N, true)) return rc;
-    jackknife_host(bclasses, B, set_of, tests, N, out);
-    return TQ_OK;
+    return api(nullptr, who, [&]() -> int {
+        if (int rc = check_dstat_tests(nullptr, who, bclasses && out, n_sets, &B, set_of, tests, N, true)) return rc;
+        jackknife_host(bclasses, B, set_of, tests, N, out);
+        return TQ_OK;
+    });
 }
 
 template <class Tests>
@@ -1517,9 +1576,11 @@ int jackknife_dev(tq_ctx *ctx, const char *who, const uint32_t *d_bclasses, int6
                   const Tests tests, int64_t N, double *d_out, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (int rc = check_dstat_tests(ctx, who, d_bclasses && d_out, n_sets, &B, d_set_of, tests, N, false)) return rc;
-    return launch_per_test(ctx, who, tq_jackknife_kernel<Tests>, JK_THREADS, N, stream, d_bclasses, n_sets, B, d_set_of, tests, N,
-                           d_out);
+    return api(ctx, who, [&]() -> int {
+        if (int rc = check_dstat_tests(ctx, who, d_bclasses && d_out, n_sets, &B, d_set_of, tests, N, false)) return rc;
+        return launch_per_test(ctx, who, tq_jackknife_kernel<Tests>, JK_THREADS, N, stream, d_bclasses, n_sets, B, d_set_of, tests, N,
+                               d_out);
+    });
 }
 
 // Block rows: of quartets (pattern_blocks.hpp), of species quartets (species_blocks.hpp), of five-taxon sets
@@ -1614,9 +1675,9 @@ int launch_blocks(tq_ctx *ctx, BlockKind kind, const uint32_t *dq, int64_t Q, in
                                (uint32_t)ctx->T, sets, n, starts, B, rows);
             break;
         default:
-            launch(QuartetRule{{ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T}, ctx->count_invariant ? 0xFFFFFFFFu : 0u});
+            launch(QuartetRule{{ctx->nat.planes3, ctx->nat.W, (uint32_t)ctx->T}, ctx->opt.count_invariant ? 0xFFFFFFFFu : 0u});
         }
-        TQ_HIP(ctx, hipGetLastError());
+        TQ_LAUNCHED(ctx, __func__);
     }
     return TQ_OK;
 }
@@ -1627,37 +1688,38 @@ int blocks_to_host(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t 
                    int64_t B, uint32_t *classes)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || !block_starts || (Q > 0 && (!sets || !classes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    int rc = blocks_ready(ctx, who, kind, block_starts, B);
-    if (rc) return rc;
-    const int width = block_set_width(kind);
-    if ((rc = check_set_rows(ctx, who, sets, Q, width, block_set_species(kind)))) return rc;
-    if (Q == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
-    int64_t chunk = ctx->batch / B;
-    if (chunk < 1) chunk = 1;
-    if (chunk > Q) chunk = Q;
-    const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
-    const size_t set_bytes = (size_t)width * sizeof(uint32_t);
-    const size_t o_cls = align_up((size_t)chunk * set_bytes, 256);
-    TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
-    if ((rc = ensure_streams(ctx))) return rc;
-    char *base = ctx->d_scratch;
-    uint32_t *d_classes = (uint32_t *)(base + o_cls);
-    rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
-    for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
-        const int64_t n = (Q - q0) < chunk ? (Q - q0) : chunk;
-        if (hipMemcpyAsync(base, sets + q0 * width, (size_t)n * set_bytes, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
-            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the sets failed", who);
-        if (!rc) rc = launch_blocks(ctx, kind, (const uint32_t *)base, n, B, d_classes, ctx->sK);
-        if (!rc && hipMemcpyAsync((char *)classes + (size_t)q0 * row_bytes, d_classes, (size_t)n * row_bytes, hipMemcpyDeviceToHost,
-                                  ctx->sK) != hipSuccess)
-            rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the block rows failed", who);
-    }
-    if (hipStreamSynchronize(ctx->sK) != hipSuccess && !rc) rc = fail(ctx, TQ_ERR_HIP, "%s: hipStreamSynchronize failed", who);
-    return rc;
+    return api(ctx, who, [&]() -> int {
+        if (Q < 0 || !block_starts || (Q > 0 && (!sets || !classes)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+        int rc = blocks_ready(ctx, who, kind, block_starts, B);
+        if (rc) return rc;
+        const int width = block_set_width(kind);
+        if ((rc = check_set_rows(ctx, who, sets, Q, width, block_set_species(kind)))) return rc;
+        if (Q == 0) return TQ_OK;
+        // chunks of whole sets, at most option "batch" items of Q * B each (one set where B alone exceeds it)
+        int64_t chunk = ctx->opt.batch / B;
+        if (chunk < 1) chunk = 1;
+        if (chunk > Q) chunk = Q;
+        const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
+        const size_t set_bytes = (size_t)width * sizeof(uint32_t);
+        const size_t o_cls = align_up((size_t)chunk * set_bytes, 256);
+        TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
+        if ((rc = ensure_streams(ctx))) return rc;
+        char *base = ctx->d_scratch;
+        uint32_t *d_classes = (uint32_t *)(base + o_cls);
+        rc = stage_block_starts(ctx, block_starts, B, ctx->sK);
+        for (int64_t q0 = 0; q0 < Q && !rc; q0 += chunk) {
+            const int64_t n = (Q - q0) < chunk ? (Q - q0) : chunk;
+            if (hipMemcpyAsync(base, sets + q0 * width, (size_t)n * set_bytes, hipMemcpyHostToDevice, ctx->sK) != hipSuccess)
+                rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the sets failed", who);
+            if (!rc) rc = launch_blocks(ctx, kind, (const uint32_t *)base, n, B, d_classes, ctx->sK);
+            if (!rc && hipMemcpyAsync((char *)classes + (size_t)q0 * row_bytes, d_classes, (size_t)n * row_bytes, hipMemcpyDeviceToHost,
+                                      ctx->sK) != hipSuccess)
+                rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the block rows failed", who);
+        }
+        if (hipStreamSynchronize(ctx->sK) != hipSuccess && !rc) rc = fail(ctx, TQ_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+        return rc;
+    });
 }
 
 // device sets -> device block rows, enqueued on `stream`
@@ -1665,16 +1727,17 @@ int blocks_dev(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *d_s
                int64_t B, uint32_t *d_classes, hipStream_t stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || !block_starts || (Q > 0 && (!d_sets || !d_classes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
-    if (int rc = blocks_ready(ctx, who, kind, block_starts, B)) return rc;
-    if (Q == 0) return TQ_OK;
-    if (int rc = check_dev_alignment(ctx, who, d_sets, block_set_width(kind), d_classes)) return rc;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
-    int rc = stage_block_starts(ctx, block_starts, B, stream);
-    if (!rc) rc = launch_blocks(ctx, kind, d_sets, Q, B, d_classes, stream);
-    return note_dev_api(ctx, stream, rc);
+    return api(ctx, who, [&]() -> int {
+        if (Q < 0 || !block_starts || (Q > 0 && (!d_sets || !d_classes)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+        if (int rc = blocks_ready(ctx, who, kind, block_starts, B)) return rc;
+        if (Q == 0) return TQ_OK;
+        if (int rc = check_dev_alignment(ctx, who, d_sets, block_set_width(kind), d_classes)) return rc;
+        if (int rc = enter_dev_api(ctx, stream)) return rc;          // behind a tq_bootstrap_async that rebuilds the layout
+        int rc = stage_block_starts(ctx, block_starts, B, stream);
+        if (!rc) rc = launch_blocks(ctx, kind, d_sets, Q, B, d_classes, stream);
+        return note_dev_api(ctx, stream, rc);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1747,43 +1810,35 @@ struct tq_scf : TreeAcc {};
 namespace {
 
 // The tree, host totals of edge_words * E + tail_words words and, with a context, the device side.  `who` names the
-// calling function in the messages.  After a failure the caller deletes the accumulator.
+// calling function in the messages.  After a failure the caller's owner frees the accumulator.
 int tree_acc_init(TreeAcc *acc, const char *who, const int32_t *parent, int64_t n_nodes, int64_t T, int edge_words,
                   int64_t tail_words, tq_ctx *ctx)
 {
-    try {
-        const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
-        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: %s", who, err.c_str());
-        acc->words = (int64_t)acc->t.E * edge_words + tail_words;
-        acc->hi.assign(acc->words, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "%s: out of host memory", who);
-    }
+    const std::string err = conc_build_tree(parent, n_nodes, T, acc->t);
+    if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: %s", who, err.c_str());
+    acc->words = (int64_t)acc->t.E * edge_words + tail_words;
+    acc->hi.assign(acc->words, 0);
     if (!ctx) return TQ_OK;
     const ConcTree &t = acc->t;
     acc->ctx = ctx;
     acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
     acc->gmax = (int)std::max<int64_t>(1, std::min<int64_t>(acc->num_cu, (int64_t(64) << 20) / (acc->words * 8)));
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = acc->d_lca.alloc((size_t)T * T);
-    if (e == hipSuccess) e = acc->d_dep.alloc((size_t)t.N);
-    if (e == hipSuccess) e = acc->d_eid.alloc((size_t)t.N);
-    if (e == hipSuccess) e = acc->d_slab.alloc((size_t)acc->gmax * acc->words);
-    if (e == hipSuccess) e = acc->d_tot.alloc((size_t)acc->words);
-    if (e == hipSuccess) e = hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(acc->d_tot, 0, (size_t)acc->words * 8);
-    if (e == hipSuccess) e = acc->order.create();
-    if (e != hipSuccess)
-        return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    TQ_HIPF(ctx, who, acc->d_lca.alloc((size_t)T * T));
+    TQ_HIPF(ctx, who, acc->d_dep.alloc((size_t)t.N));
+    TQ_HIPF(ctx, who, acc->d_eid.alloc((size_t)t.N));
+    TQ_HIPF(ctx, who, acc->d_slab.alloc((size_t)acc->gmax * acc->words));
+    TQ_HIPF(ctx, who, acc->d_tot.alloc((size_t)acc->words));
+    TQ_HIPF(ctx, who, hipMemcpy(acc->d_lca, t.lca.data(), (size_t)T * T * 2, hipMemcpyHostToDevice));
+    TQ_HIPF(ctx, who, hipMemcpy(acc->d_dep, t.dep.data(), (size_t)t.N * 2, hipMemcpyHostToDevice));
+    TQ_HIPF(ctx, who, hipMemcpy(acc->d_eid, t.eid.data(), (size_t)t.N * 4, hipMemcpyHostToDevice));
+    TQ_HIPF(ctx, who, hipMemset(acc->d_tot, 0, (size_t)acc->words * 8));
+    TQ_HIPF(ctx, who, acc->order.create());
     return TQ_OK;
 }
 
 int tree_acc_wait(TreeAcc *acc)
 {
     if (!acc->order.pending) return TQ_OK;
-    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
     TQ_HIP(acc->ctx, acc->order.sync());
     return TQ_OK;
 }
@@ -1810,11 +1865,7 @@ int tree_acc_shape(const TreeAcc *acc, int64_t *T, int64_t *n_edges, int64_t *ma
 // waits for the device adds and copies their totals to `dv` (zeros without a context)
 int tree_acc_read(TreeAcc *acc, const char *who, std::vector<uint64_t> &dv)
 {
-    try {
-        dv.assign(acc->words, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "%s: out of host memory", who);
-    }
+    dv.assign(acc->words, 0);
     if (acc->ctx) {
         if (int rc = tree_acc_wait(acc)) return rc;
         TQ_HIP(acc->ctx, hipMemcpy(dv.data(), acc->d_tot, (size_t)acc->words * 8, hipMemcpyDeviceToHost));
@@ -1832,7 +1883,6 @@ int tree_acc_add_dev(TreeAcc *acc, const char *who, int64_t n, int32_t f64_edges
 {
     tq_ctx *ctx = acc->ctx;
     const ConcTree &t = acc->t;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
     TQ_HIP(ctx, acc->order.join(st));            // slab / totals in call order
     for (int64_t r0 = 0; r0 < n; r0 += CONC_ROWS_PER_LAUNCH) {
         const int64_t m = std::min<int64_t>(CONC_ROWS_PER_LAUNCH, n - r0);
@@ -1847,8 +1897,7 @@ int tree_acc_add_dev(TreeAcc *acc, const char *who, int64_t n, int32_t f64_edges
         }
         hipLaunchKernelGGL(tq_conc_fold_kernel, dim3((unsigned)((acc->words + CONC_THREADS - 1) / CONC_THREADS)),
                            dim3(CONC_THREADS), 0, st, (const uint64_t *)acc->d_slab, G, acc->words, f64_edges, acc->d_tot);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+        TQ_LAUNCHED(ctx, who);
     }
     TQ_HIP(ctx, acc->order.mark(st));
     return TQ_OK;
@@ -1900,8 +1949,7 @@ int cons_launch(tq_cons *a, int64_t n, const int32_t *recs, hipStream_t st)
     const unsigned blocks = (unsigned)((p.items * p.G + CONS_THREADS - 1) / CONS_THREADS);
     hipLaunchKernelGGL(tq_cons_insert_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
     hipLaunchKernelGGL(tq_cons_count_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_cons_add: launch failed: %s", hipGetErrorString(e));
+    TQ_LAUNCHED(ctx, "tq_cons_add");
     TQ_HIP(ctx, a->table.end_chunk(st));
     TQ_HIP(ctx, a->order.mark(st));
     ++a->chunk.chunks;
@@ -1922,7 +1970,6 @@ int cons_table(tq_cons *a, const char *who)
     } else {
         const int64_t n = t.dev_entries;
         std::vector<uint64_t> rep((size_t)n * W), cnt((size_t)n);
-        TQ_HIP(a->ctx, hipSetDevice(a->ctx->device));
         TQ_HIP(a->ctx, hipMemcpy(rep.data(), t.d_rep, rep.size() * 8, hipMemcpyDeviceToHost));
         TQ_HIP(a->ctx, hipMemcpy(cnt.data(), t.d_count, cnt.size() * 8, hipMemcpyDeviceToHost));
         ConsMap all = t.host;
@@ -1978,8 +2025,7 @@ int tbe_launch(tq_tbe *a, int64_t n, const int32_t *recs, hipStream_t st, bool w
     t.T = c.T; t.W = c.W; t.E = (int32_t)a->E;
     TQ_HIP(ctx, a->chunk.stage(n, recs, st, p));
     hipLaunchKernelGGL(tq_tbe_kernel, dim3((unsigned)n, (unsigned)((a->E + BT_ROWS - 1) / BT_ROWS)), dim3(BT_THREADS), 0, st, t);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_tbe_add: launch failed: %s", hipGetErrorString(e));
+    TQ_LAUNCHED(ctx, "tq_tbe_add");
     if (want_phi) TQ_HIP(ctx, hipMemcpyAsync(a->p_phi, a->d_phi, (size_t)n * a->E * 2, hipMemcpyDeviceToHost, st));
     TQ_HIP(ctx, a->order.mark(st));
     ++a->chunk.chunks;
@@ -2059,7 +2105,7 @@ int rf_drain(tq_rf *a)
     TQ_HIP(ctx, hipMemcpyAsync(a->d_newid, a->p_newid, (size_t)nun * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(tq_rf_patch_kernel, dim3((unsigned)((nun + CONS_THREADS - 1) / CONS_THREADS)), dim3(CONS_THREADS), 0, st,
                        (const uint32_t *)t.d_unres, (const uint32_t *)a->d_newid, nun, r, a->chunk.T - 2);
-    TQ_HIP(ctx, hipGetLastError());
+    TQ_LAUNCHED(ctx, __func__);
     TQ_HIP(ctx, hipStreamSynchronize(st));
     return TQ_OK;
 }
@@ -2077,8 +2123,7 @@ int rf_launch(tq_rf *a, int64_t first, int64_t n, const int32_t *recs, hipStream
     const unsigned blocks = (unsigned)((p.items * p.G + CONS_THREADS - 1) / CONS_THREADS);
     hipLaunchKernelGGL(tq_cons_insert_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p);
     hipLaunchKernelGGL(tq_rf_ident_kernel, dim3(blocks), dim3(CONS_THREADS), 0, st, p, r);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_rf_add: launch failed: %s", hipGetErrorString(e));
+    TQ_LAUNCHED(ctx, "tq_rf_add");
     TQ_HIP(ctx, a->table.end_chunk(st));
     TQ_HIP(ctx, a->order.mark(st));
     a->chunk_base = first;
@@ -2114,7 +2159,6 @@ int rf_dev_final(tq_rf *a)
     tq_ctx *ctx = a->ctx;
     const int64_t N = a->ntrees, nd = a->table.dev_entries, nh = (int64_t)a->host_count.size();
     const int64_t max_splits = a->table.max_splits, nodes = a->chunk.nodes();
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
     // columns in entry order: the device entries, then the host's
     std::vector<unsigned long long> cnt((size_t)nd);
     if (nd) TQ_HIP(ctx, hipMemcpy(cnt.data(), a->table.d_count, (size_t)nd * 8, hipMemcpyDeviceToHost));
@@ -2151,8 +2195,7 @@ int rf_dev_final(tq_rf *a)
     }
     hipLaunchKernelGGL(tq_rf_final_kernel, dim3((unsigned)((N * N + RF_THREADS - 1) / RF_THREADS)), dim3(RF_THREADS), 0, st,
                        a->d_shared.get(), a->d_rf.get(), (const int32_t *)a->d_nsplits.get(), (int32_t)N);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_rf_read: launch failed: %s", hipGetErrorString(e));
+    TQ_LAUNCHED(ctx, "tq_rf_read");
     TQ_HIP(ctx, hipStreamSynchronize(st));      // dev_col / host_col live until here
     a->columns = C;
     a->col_chunks = launched;
@@ -2244,11 +2287,10 @@ int qd_launch(tq_qd *a, int64_t nq, hipStream_t st, const char *who)
     g.planes = a->d_planes; g.same = a->d_same; g.both = a->d_both;
     g.N = (int32_t)N; g.cw = (int32_t)cw; g.nt = (int32_t)nt;
     int64_t ks = 1;
-    g.slice_words = (int32_t)qd_kslices(cw, nt, a->num_cu, ctx->qdist_kslices, &ks);
+    g.slice_words = (int32_t)qd_kslices(cw, nt, a->num_cu, ctx->opt.qdist_kslices, &ks);
     g.atomic = ks > 1;
     hipLaunchKernelGGL(tq_qd_gemm_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)ks), dim3(QD_THREADS), 0, st, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(ctx, TQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(err));
+    TQ_LAUNCHED(ctx, who);
     a->kslices = ks;
     ++a->chunks;
     return TQ_OK;
@@ -2297,7 +2339,6 @@ int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t 
         a->q_total += (uint64_t)Q;
         return TQ_OK;
     }
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
     TQ_HIP(ctx, a->order.join(st));
     const int64_t per = a->chunk_words * 64;
     for (int64_t q0 = 0; q0 < Q; q0 += per) {
@@ -2317,7 +2358,7 @@ int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t 
             hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                ranks ? (const uint64_t *)a->d_ranks.get() : (const uint64_t *)nullptr,
                                first_rank + (uint64_t)q0, n, a->T, a->d_quart.get());
-            TQ_HIP(ctx, hipGetLastError());
+            TQ_LAUNCHED(ctx, who);
         }
         a->scored = true;                                           // from here on the matrices hold part of the call
         if (int rc = qd_launch(a, n, st, who)) return rc;
@@ -2331,7 +2372,6 @@ int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t 
 int qd_zero(tq_qd *a)
 {
     if (a->ctx) {
-        TQ_HIP(a->ctx, hipSetDevice(a->ctx->device));
         TQ_HIP(a->ctx, a->order.sync());
         TQ_HIP(a->ctx, a->copy.sync());
         const size_t n = (size_t)(a->ntrees * a->ntrees) * 8;
@@ -2456,7 +2496,7 @@ struct StreeDevBackend : StreeBackend {
         fill(p);
         p.n_nodes = (int32_t)nodes.size();
         p.cells = cells;
-        if (a->ctx->stree_lds && cells <= STREE_LDS_CELLS && n_live >= 4096) {
+        if (a->ctx->opt.stree_lds && cells <= STREE_LDS_CELLS && n_live >= 4096) {
             const int pairs = (int)std::max<int64_t>(1, std::min<int64_t>((n_live + 16383) / 16384, 64));
             hipLaunchKernelGGL(tq_stree_graph_lds_kernel, dim3(2 * pairs), dim3(STREE_LDS_THREADS), 0, st, p);
         } else {
@@ -2465,7 +2505,7 @@ struct StreeDevBackend : StreeBackend {
             hipLaunchKernelGGL(tq_stree_graph_kernel, dim3(G), dim3(STREE_THREADS), 0, st, p);
         }
         STREE_HIP(hipGetLastError());
-        if (exact && a->ctx->stree_search_dev) {                   // the search kernel reads d_mat behind this on `st`
+        if (exact && a->ctx->opt.stree_search_dev) {                   // the search kernel reads d_mat behind this on `st`
             mat = nullptr;
             return TQ_OK;
         }
@@ -2477,7 +2517,7 @@ struct StreeDevBackend : StreeBackend {
     int search(const std::vector<StreeNode> &nodes, int64_t cells, int level, uint64_t seed, std::vector<uint8_t> &sides,
                std::vector<uint8_t> &cuts, std::string &err) override
     {
-        if (!a->ctx->stree_search_dev) {                            // the matrices are in p_mat
+        if (!a->ctx->opt.stree_search_dev) {                            // the matrices are in p_mat
             stree_search_level_host(nodes, a->p_mat, cells, level, seed, sides, cuts);
             return TQ_OK;
         }
@@ -2539,7 +2579,6 @@ struct StreeDevBackend : StreeBackend {
 // orders `st` behind the device adds made on another stream
 int stree_join(tq_stree *acc, hipStream_t st)
 {
-    TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
     TQ_HIP(acc->ctx, acc->order.join(st));
     return TQ_OK;
 }
@@ -2598,12 +2637,12 @@ int nni_scan_once(tq_stree *acc, const NniTree &t, hipStream_t st, const char *w
             1, std::min<int64_t>((acc->rows_in + NNI_ROWS_PER_BLOCK - 1) / NNI_ROWS_PER_BLOCK, NNI_MAX_SLICES));
         NniTableArgs ta{(const int32_t *)acc->d_nni_rec.get(), acc->d_nni_tab, (uint32_t)T};
         hipLaunchKernelGGL(tq_nni_table_kernel, dim3(table_blocks), dim3(NNI_THREADS), 0, st, ta);
-        TQ_HIP(ctx, hipGetLastError());
+        TQ_LAUNCHED(ctx, who);
         NniArgs na{acc->d_root_t, acc->d_root_k, &acc->d_cnt[SC_KEPT], acc->d_nni_tab, acc->d_nni_rec + T, acc->d_nni_w,
                    (uint32_t)T, (uint32_t)t.N, (uint32_t)E};
         if (T <= NNI_T_LDS) hipLaunchKernelGGL(tq_nni_kernel<true>, dim3(slices), dim3(NNI_THREADS), 0, st, na);
         else hipLaunchKernelGGL(tq_nni_kernel<false>, dim3(slices), dim3(NNI_THREADS), 0, st, na);
-        TQ_HIP(ctx, hipGetLastError());
+        TQ_LAUNCHED(ctx, who);
     }
     unsigned long long *cnt = acc->p_nni_w + wn;
     TQ_HIP(ctx, hipMemcpyAsync(acc->p_nni_w, acc->d_nni_w, wn * 8, hipMemcpyDeviceToHost, st));
@@ -2615,6 +2654,109 @@ int nni_scan_once(tq_stree *acc, const NniTree &t, hipStream_t st, const char *w
     return TQ_OK;
 }
 
+// What tq_qd_add and tq_stree_fit share (fit.hpp).  pars[r] = the prepared parent array of tree r: every tree is validated
+// before anything is written.
+int prepare_fit_trees(tq_ctx *ctx, const char *who, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride,
+                      int64_t T, std::vector<std::vector<int32_t>> &pars)
+{
+    pars.assign((size_t)R, {});
+    std::vector<std::vector<int32_t>> nch;
+    for (int64_t r = 0; r < R; ++r) {
+        if (n_nodes[r] > stride)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: n_nodes exceeds the stride", who, (long long)r);
+        const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
+        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: %s", who, (long long)r, err.c_str());
+        if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: internal error: a prepared tree of T taxa has "
+                        "at most 2 T - 2 nodes", who, (long long)r);
+    }
+    return TQ_OK;
+}
+
+// the records tq_fit_table_kernel reads, S = 2 T words a tree: the prepared parents, zeros, the node count in the last word
+void fit_stage_records(int32_t *rec0, const std::vector<std::vector<int32_t>> &pars, int64_t S)
+{
+    memset(rec0, 0, pars.size() * (size_t)S * 4);
+    for (size_t r = 0; r < pars.size(); ++r) {
+        memcpy(rec0 + r * S, pars[r].data(), pars[r].size() * 4);
+        rec0[r * S + S - 1] = (int32_t)pars[r].size();
+    }
+}
+
+// the grid of tq_fit_table_kernel in x (its y: the trees)
+unsigned fit_table_blocks(int64_t T)
+{
+    const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
+}
+
+// One row per option of tq_set_option (bdsqr_stats, which holds no value, aside): the field of Options, its legal values
+// -- lo..hi or, where `listed` is set, exactly the values whose bits it holds --, the value that asks for the default
+// (NO_KEY: none), which is then read from a default-constructed Options, and the message of a refused value.  A flag
+// stores value != 0 and refuses nothing.
+struct OptionRow {
+    const char *name;
+    int Options::*i;                // the field is an int ...
+    int64_t Options::*l;            // ... or an int64_t
+    int64_t lo, hi;
+    uint64_t listed;
+    int64_t default_key;
+    const char *refusal;
+    bool flag;
+};
+constexpr int64_t NO_KEY = INT64_MIN, ANY = INT64_MAX;
+constexpr OptionRow opt(const char *name, int Options::*f, int64_t lo, int64_t hi, int64_t key, const char *refusal)
+{
+    return {name, f, nullptr, lo, hi, 0, key, refusal, false};
+}
+constexpr OptionRow opt(const char *name, int64_t Options::*f, int64_t lo, int64_t hi, int64_t key, const char *refusal)
+{
+    return {name, nullptr, f, lo, hi, 0, key, refusal, false};
+}
+template <class... V>
+constexpr OptionRow opt_listed(const char *name, int Options::*f, const char *refusal, V... values)
+{
+    return {name, f, nullptr, 0, 0, ((uint64_t(1) << values) | ...), 0, refusal, false};
+}
+constexpr OptionRow opt_flag(const char *name, int Options::*f) { return {name, f, nullptr, 0, 0, 0, NO_KEY, "", true}; }
+
+constexpr OptionRow OPTION_TABLE[] = {
+    opt_listed("nrep", &Options::nrep, "nrep must be 1,2,4,8,16 or 32", 1, 2, 4, 8, 16, 32),
+    opt("waves_per_cu", &Options::waves_per_cu, 0, 1 << 20, NO_KEY, "waves_per_cu must be 0..2^20"),
+    opt_flag("xcd_remap", &Options::xcd_remap),
+    opt_flag("count_invariant", &Options::count_invariant),
+    opt_flag("scan_pair", &Options::scan_pair),
+    opt("scan_f4", &Options::scan_f4, -1, 1, NO_KEY, "scan_f4 must be -1 (subsample mode only), 0 or 1"),
+    opt("site_pack", &Options::site_pack, -1, 1, NO_KEY, "site_pack must be -1 (automatic), 0 or 1"),
+    opt("boot_pack", &Options::boot_pack, -1, 1, NO_KEY, "boot_pack must be -1 (automatic), 0 or 1"),
+    opt("scan_dp", &Options::scan_dp, 0, 1, NO_KEY, "scan_dp must be 0 or 1"),
+    opt("dp_min_quartets", &Options::dp_min_quartets, 0, ANY, 0, "dp_min_quartets must be >= 0"),
+    opt("wg_min_quartets", &Options::wg_min_quartets, 0, ANY, 0, "wg_min_quartets must be >= 0"),
+    opt("bidiag_layout", &Options::bidiag_layout, 0, 1, -1, "bidiag_layout must be -1 (default), 0 or 1"),
+    opt_flag("park_t", &Options::park_t),
+    opt_flag("share_c", &Options::share_c),
+    opt("cons_hash_bits", &Options::cons_hash_bits, 1, 64, 0, "cons_hash_bits must be 1..64 (0 = default 64)"),
+    opt("cons_scratch_bytes", &Options::cons_scratch_bytes, 1, ANY, 0, "cons_scratch_bytes must be >= 0 (0 = default 256 MiB)"),
+    opt("stree_search_dev", &Options::stree_search_dev, 0, 1, NO_KEY, "stree_search_dev must be 0 or 1"),
+    opt("fit_scratch_bytes", &Options::fit_scratch_bytes, 1, ANY, NO_KEY, "fit_scratch_bytes must be at least 1"),
+    opt("qdist_scratch_bytes", &Options::qdist_scratch_bytes, 1, ANY, 0, "qdist_scratch_bytes must be >= 0 (0 = default 256 MiB)"),
+    opt("qdist_kslices", &Options::qdist_kslices, 0, 65535, NO_KEY, "qdist_kslices must be 0 (auto) .. 65535"),
+    opt("stree_lds", &Options::stree_lds, 0, 1, NO_KEY, "stree_lds must be 0 or 1"),
+    opt("svd_wpc", &Options::svd_wpc, 0, 1 << 20, NO_KEY, "svd_wpc must be 0..2^20"),
+    opt("svd_chunk", &Options::svd_chunk, 1, ANY, 0, "svd_chunk must be >= 0"),
+    opt("svd_streams", &Options::svd_streams, 1, 2, 0, "svd_streams must be 0 (default), 1 or 2"),
+    opt("bdsqr_maxit", &Options::bdsqr_maxit, 1, 1000, 0, "bdsqr_maxit must be 0..1000"),
+    opt_listed("scan_wg", &Options::scan_wg, "scan_wg must be 0 (default), 1, 2, 3, 4, 6, 8 or 16", 1, 2, 3, 4, 6, 8, 16),
+    opt("svd_method", &Options::svd_method, 0, 1, NO_KEY, "svd_method must be 0 (Jacobi) or 1 (HQR)"),
+    opt("order", &Options::order, 0, 1, NO_KEY, "order must be 0 or 1"),
+    opt("scan_method", &Options::scan_method, -1, 6, NO_KEY, "scan_method must be -1 (auto), 0, 1, 6 (or 2..5: timing diagnostics)"),
+    opt("batch", &Options::batch, 1, ANY, 0, "batch must be >= 0"),
+    opt("species_method", &Options::species_method, -1, 1, NO_KEY, "species_method must be -1 (auto), 0 (VALU form) or 1 (MFMA form)"),
+    opt("species_alleles", &Options::species_alleles, 0, 1, NO_KEY,
+        "species_alleles must be 0 (one lineage per sample) or 1 (two: both alleles)"),
+    opt("phases", &Options::phases, 1, 3, 0, "phases must be 1, 2 or 3"),
+};
+
 }  // namespace
 
 extern "C" {
@@ -2623,29 +2765,25 @@ int tq_create(tq_ctx **out, int device_id)
 {
     if (!out) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_create: out is NULL");
     *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(nullptr, TQ_ERR_NO_DEVICE, "no HIP device available (%s)", hipGetErrorString(e));
-    if (device_id < 0 || device_id >= n)
-        return fail(nullptr, TQ_ERR_INVALID_ARG, "device_id %d out of range (0..%d)", device_id, n - 1);
-    tq_ctx *ctx = new (std::nothrow) tq_ctx();
-    if (!ctx) return fail(nullptr, TQ_ERR_OOM, "out of host memory");
-    ctx->device = device_id;
-    e = hipSetDevice(device_id);
-    if (e == hipSuccess) e = hipGetDeviceProperties(&ctx->prop, device_id);
-    if (e != hipSuccess) {
-        int rc = fail(nullptr, TQ_ERR_HIP, "device %d not usable: %s", device_id, hipGetErrorString(e));
-        delete ctx;
-        return rc;
-    }
-    if (int rc = probe_scan_pb(ctx)) {
-        g_create_err = ctx->err;
-        delete ctx;
-        return rc;
-    }
-    *out = ctx;
-    return TQ_OK;
+    return api(nullptr, "tq_create", [&]() -> int {     // no context yet: messages go to tq_last_error(NULL)
+        int n = 0;
+        hipError_t e = hipGetDeviceCount(&n);
+        if (e != hipSuccess || n <= 0)
+            return fail(nullptr, TQ_ERR_NO_DEVICE, "no HIP device available (%s)", hipGetErrorString(e));
+        if (device_id < 0 || device_id >= n)
+            return fail(nullptr, TQ_ERR_INVALID_ARG, "device_id %d out of range (0..%d)", device_id, n - 1);
+        std::unique_ptr<tq_ctx> ctx(new tq_ctx());      // nothing but its buffers to release until it is handed out
+        ctx->device = device_id;
+        e = hipSetDevice(device_id);
+        if (e == hipSuccess) e = hipGetDeviceProperties(&ctx->prop, device_id);
+        if (e != hipSuccess) return fail(nullptr, TQ_ERR_HIP, "device %d not usable: %s", device_id, hipGetErrorString(e));
+        if (int rc = probe_scan_pb(ctx.get())) {
+            g_create_err = ctx->err;
+            return rc;
+        }
+        *out = ctx.release();
+        return TQ_OK;
+    });
 }
 
 void tq_destroy(tq_ctx *ctx)
@@ -2689,62 +2827,20 @@ int tq_host_free(void *p)
     return pool().release(p);
 }
 
-int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *locus,
-                int64_t locus_stride)
+// the uploads and the layout kernels of tq_set_data, after free_data; the caller frees again on a failure.  The resident
+// sets leave no head-room (the packed one is built at exactly pSp); the three upload temporaries go with their scope
+static int upload_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, int64_t Sp, const std::vector<uint32_t> &loc,
+                       const std::vector<uint32_t> &pack_src)
 {
-    if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!tmparr || !locus) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_data: NULL pointer");
-    if (T < 1 || S < 1 || locus_stride < 1 || T > 0x7FFFFFFF)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_data: bad shape T=%lld S=%lld stride=%lld", (long long)T,
-                    (long long)S, (long long)locus_stride);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    free_data(ctx);
-    ctx->data_gen++;
-
-    // contiguous copy of the locus column + the run-contiguity check: not ok means no subsample mode
-    std::vector<uint32_t> loc;
-    bool ok;
-    try {
-        ok = copy_locus_column(locus, locus_stride, S, loc);
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_set_data: out of host memory");
-    }
-    ctx->locus_runs_ok = ok;
-
-    const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
-    // packed layout for the subsample-mode scans (pack.hpp): planned on the host, taken when forced or when it pays
-    std::vector<uint32_t> pack_src;
-    if (ok && ctx->site_pack != 0 && S < 0xFFFFFFFFll) {        // the map holds site indices as u32
-        try {
-            std::vector<LocusRun> runs;
-            locus_runs(loc.data(), S, runs);
-            pack_sites(runs, pack_src);
-            if (ctx->site_pack < 0) {
-                double cost[2], trips[2];
-                const double gain_low = pack_estimate(tmparr, T, S, runs, pack_src, cost, trips);
-                if (!pack_pays(gain_low) || !pack_fits_offsets(T, pack_src.size(), (size_t)Sp)) pack_src.clear();
-            }
-        } catch (const std::bad_alloc &) {
-            return fail(ctx, TQ_ERR_OOM, "tq_set_data: out of host memory");
-        }
-    }
-
-    ctx->T = T; ctx->S = S;
-    // the resident sets leave no head-room (the packed one is built at exactly pSp); every failure path releases them
-    // through free_data and the three upload temporaries through their scope
+    const char *who = "tq_set_data";
     const int64_t pSp = (int64_t)pack_src.size();
     DevBuf<uint8_t> d_raw;
     DevBuf<uint32_t> d_loc, d_src;
-    hipError_t e = ctx->nat.alloc(T, Sp, true);
-    if (e == hipSuccess) e = d_raw.alloc((size_t)(T * S));
-    if (e == hipSuccess) e = d_loc.alloc((size_t)S);
-    if (e == hipSuccess && pSp) e = ctx->pk.alloc(T, pSp, false);
-    if (e == hipSuccess && pSp) e = d_src.alloc((size_t)pSp);
-    if (e != hipSuccess) {
-        free_data(ctx);
-        return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_set_data: hipMalloc failed: %s",
-                    hipGetErrorString(e));
-    }
+    TQ_HIPF(ctx, who, ctx->nat.alloc(T, Sp, true));
+    TQ_HIPF(ctx, who, d_raw.alloc((size_t)(T * S)));
+    TQ_HIPF(ctx, who, d_loc.alloc((size_t)S));
+    if (pSp) TQ_HIPF(ctx, who, ctx->pk.alloc(T, pSp, false));
+    if (pSp) TQ_HIPF(ctx, who, d_src.alloc((size_t)pSp));
     ctx->nat.set_sites(Sp);
     ctx->pk.set_sites(pSp);
     auto prepare = [&](const SiteSet &s, const uint32_t *src) {
@@ -2752,29 +2848,68 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
         hipLaunchKernelGGL(tq_prepare_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_raw.get(), d_loc.get(), src, S,
                            s.Sp, s.W, (int32_t)T, s.rows.get(), s.nib.get(), s.nib5.get(), s.planes.get(), s.planes3.get(),
                            s.runbeg(T));
-        return hipGetLastError();
     };
-    e = hipMemcpy(d_raw, tmparr, (size_t)(T * S), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_loc, loc.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = prepare(ctx->nat, nullptr);
-    if (e == hipSuccess && pSp) e = hipMemcpy(d_src, pack_src.data(), (size_t)pSp * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && pSp) e = prepare(ctx->pk, d_src);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        free_data(ctx);
-        return fail(ctx, TQ_ERR_HIP, "tq_set_data: %s", hipGetErrorString(e));
+    TQ_HIPF(ctx, who, hipMemcpy(d_raw, tmparr, (size_t)(T * S), hipMemcpyHostToDevice));
+    TQ_HIPF(ctx, who, hipMemcpy(d_loc, loc.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice));
+    prepare(ctx->nat, nullptr);
+    TQ_LAUNCHED(ctx, who);
+    if (pSp) {
+        TQ_HIPF(ctx, who, hipMemcpy(d_src, pack_src.data(), (size_t)pSp * sizeof(uint32_t), hipMemcpyHostToDevice));
+        prepare(ctx->pk, d_src);
+        TQ_LAUNCHED(ctx, who);
     }
-    ctx->have_data = true;
-    if (pSp) ctx->pk_gen = ctx->data_gen;
+    TQ_HIPF(ctx, who, hipDeviceSynchronize());
     return TQ_OK;
+}
+
+int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *locus,
+                int64_t locus_stride)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    return api(ctx, "tq_set_data", [&]() -> int {
+        if (!tmparr || !locus) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_data: NULL pointer");
+        if (T < 1 || S < 1 || locus_stride < 1 || T > 0x7FFFFFFF)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_data: bad shape T=%lld S=%lld stride=%lld", (long long)T,
+                        (long long)S, (long long)locus_stride);
+        free_data(ctx);
+        ctx->data_gen++;
+
+        // contiguous copy of the locus column + the run-contiguity check: not ok means no subsample mode
+        std::vector<uint32_t> loc;
+        const bool ok = copy_locus_column(locus, locus_stride, S, loc);
+        ctx->locus_runs_ok = ok;
+
+        const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
+        // packed layout for the subsample-mode scans (pack.hpp): planned on the host, taken when forced or when it pays
+        std::vector<uint32_t> pack_src;
+        if (ok && ctx->opt.site_pack != 0 && S < 0xFFFFFFFFll) {        // the map holds site indices as u32
+            std::vector<LocusRun> runs;
+            locus_runs(loc.data(), S, runs);
+            pack_sites(runs, pack_src);
+            if (ctx->opt.site_pack < 0) {
+                double cost[2], trips[2];
+                const double gain_low = pack_estimate(tmparr, T, S, runs, pack_src, cost, trips);
+                if (!pack_pays(gain_low) || !pack_fits_offsets(T, pack_src.size(), (size_t)Sp)) pack_src.clear();
+            }
+        }
+
+        ctx->T = T; ctx->S = S;
+        if (int rc = upload_data(ctx, tmparr, T, S, Sp, loc, pack_src)) {
+            free_data(ctx);             // the context holds no half-built replicate
+            return rc;
+        }
+        ctx->have_data = true;
+        if (!pack_src.empty()) ctx->pk_gen = ctx->data_gen;
+        return TQ_OK;
+    });
 }
 
 int tq_pack_sites(const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *locus, int64_t locus_stride, uint32_t *src,
                   int64_t cap, int64_t *packed_sites, int32_t *pays, double *estimate)
 {
-    if (!locus || S < 1 || S >= 0xFFFFFFFFll || locus_stride < 1 || cap < 0 || (cap > 0 && !src) || (tmparr && T < 1))
-        return TQ_ERR_INVALID_ARG;
-    try {
+    return api(nullptr, "tq_pack_sites", [&]() -> int {
+        if (!locus || S < 1 || S >= 0xFFFFFFFFll || locus_stride < 1 || cap < 0 || (cap > 0 && !src) || (tmparr && T < 1))
+            return TQ_ERR_INVALID_ARG;
         std::vector<uint32_t> loc;
         if (!copy_locus_column(locus, locus_stride, S, loc)) return TQ_ERR_LOCUS_ORDER;
         std::vector<LocusRun> runs;
@@ -2795,170 +2930,175 @@ int tq_pack_sites(const uint8_t *tmparr, int64_t T, int64_t S, const uint32_t *l
             }
         }
         if ((int64_t)map.size() <= cap) memcpy(src, map.data(), map.size() * sizeof(uint32_t));
-    } catch (const std::bad_alloc &) {
-        return TQ_ERR_OOM;
-    }
-    return TQ_OK;
+        return TQ_OK;
+    });
 }
 
 int tq_resolve_dev(tq_ctx *ctx, const uint32_t *d_quartets, int64_t Q, int subsample, uint32_t *d_rstat,
                    double *d_rscor, uint8_t *d_flags, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!d_quartets || !d_rstat || !d_rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_dev: NULL pointer or negative Q");
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
-    if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;
-    return note_dev_api(ctx, (hipStream_t)stream,
-                        launch(ctx, d_quartets, Q, subsample, false, false, out, (hipStream_t)stream, NoChunkHook()));
+    return api(ctx, "tq_resolve_dev", [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!d_quartets || !d_rstat || !d_rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_dev: NULL pointer or negative Q");
+        OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
+        if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;
+        return note_dev_api(ctx, (hipStream_t)stream,
+                            launch(ctx, d_quartets, Q, subsample, false, false, out, (hipStream_t)stream, NoChunkHook()));
+    });
 }
 
 int tq_scan_dev(tq_ctx *ctx, const uint32_t *d_quartets, int64_t Q, int subsample, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 1 || !d_quartets) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scan_dev: NULL pointer or Q < 1");
-    if (Q > ctx->batch)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scan_dev: Q=%lld exceeds the scan batch of %lld quartets (option 'batch')",
-                    (long long)Q, (long long)ctx->batch);
-    int rc = check_ready(ctx, subsample);
-    if (rc) return rc;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->timing) ctx->timed_calls++;
-    if ((rc = enter_dev_api(ctx, (hipStream_t)stream))) return rc;
-    return note_dev_api(ctx, (hipStream_t)stream, stage_scan(ctx, d_quartets, Q, subsample, false, (hipStream_t)stream));
+    return api(ctx, "tq_scan_dev", [&]() -> int {
+        if (Q < 1 || !d_quartets) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scan_dev: NULL pointer or Q < 1");
+        if (Q > ctx->opt.batch)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scan_dev: Q=%lld exceeds the scan batch of %lld quartets (option 'batch')",
+                        (long long)Q, (long long)ctx->opt.batch);
+        int rc = check_ready(ctx, subsample);
+        if (rc) return rc;
+        if (ctx->timing) ctx->timed_calls++;
+        if ((rc = enter_dev_api(ctx, (hipStream_t)stream))) return rc;
+        return note_dev_api(ctx, (hipStream_t)stream, stage_scan(ctx, d_quartets, Q, subsample, false, (hipStream_t)stream));
+    });
 }
 
 int tq_svd_dev(tq_ctx *ctx, int64_t q0, int64_t n, uint32_t *d_rstat, double *d_rscor, uint8_t *d_flags, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!d_rstat || !d_rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_svd_dev: NULL pointer or negative n");
-    if (ctx->scanned_Q == 0) return fail(ctx, TQ_ERR_NO_DATA, "tq_svd_dev: no scanned batch (call tq_scan_dev first)");
-    if (n == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
-    if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;
-    return note_dev_api(ctx, (hipStream_t)stream, stage_svd(ctx, q0, n, false, out, (hipStream_t)stream, NoChunkHook()));
+    return api(ctx, "tq_svd_dev", [&]() -> int {
+        if (n < 0 || (n > 0 && (!d_rstat || !d_rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_svd_dev: NULL pointer or negative n");
+        if (ctx->scanned_Q == 0) return fail(ctx, TQ_ERR_NO_DATA, "tq_svd_dev: no scanned batch (call tq_scan_dev first)");
+        if (n == 0) return TQ_OK;
+        OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
+        if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;
+        return note_dev_api(ctx, (hipStream_t)stream, stage_svd(ctx, q0, n, false, out, (hipStream_t)stream, NoChunkHook()));
+    });
 }
 
 int tq_unrank_dev(tq_ctx *ctx, const uint64_t *d_ranks, int64_t Q, uint32_t *d_quartets, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_data has not been called");
-    if (Q < 0 || (Q > 0 && (!d_ranks || !d_quartets)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_unrank_dev: NULL pointer or negative Q");
-    if (Q == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       d_ranks, (uint64_t)0, Q, (int32_t)ctx->T, d_quartets);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    return api(ctx, "tq_unrank_dev", [&]() -> int {
+        if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_data has not been called");
+        if (Q < 0 || (Q > 0 && (!d_ranks || !d_quartets)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_unrank_dev: NULL pointer or negative Q");
+        if (Q == 0) return TQ_OK;
+        hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           d_ranks, (uint64_t)0, Q, (int32_t)ctx->T, d_quartets);
+        TQ_LAUNCHED(ctx, "tq_unrank_dev");
+        return TQ_OK;
+    });
 }
 
 int tq_resolve_range_dev(tq_ctx *ctx, uint64_t first_rank, int64_t Q, int subsample, uint32_t *d_quartets,
                          uint32_t *d_rstat, double *d_rscor, uint8_t *d_flags, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_data has not been called");
-    if (Q < 0 || (Q > 0 && (!d_rstat || !d_rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_range_dev: NULL pointer or negative Q");
-    if (Q == 0) return TQ_OK;
-    const uint64_t total = choose4((uint64_t)ctx->T);
-    if (first_rank + (uint64_t)Q > total)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "rank range [%llu,+%lld) exceeds C(%lld,4)=%llu",
-                    (unsigned long long)first_rank, (long long)Q, (long long)ctx->T, (unsigned long long)total);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *dq = d_quartets;
-    if (!dq) {
-        TQ_HIP(ctx, ctx->d_scratch.grow((size_t)Q * 16));
-        dq = (uint32_t *)ctx->d_scratch.get();
-    }
-    hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint64_t *)nullptr, first_rank, Q, (int32_t)ctx->T, dq);
-    TQ_HIP(ctx, hipGetLastError());
-    OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
-    // consecutive lexicographic ranks are in (a,b,c) order already
-    if (int rc2 = enter_dev_api(ctx, (hipStream_t)stream)) return rc2;
-    return note_dev_api(ctx, (hipStream_t)stream,
-                        launch(ctx, dq, Q, subsample, false, true, out, (hipStream_t)stream, NoChunkHook()));
+    return api(ctx, "tq_resolve_range_dev", [&]() -> int {
+        if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_data has not been called");
+        if (Q < 0 || (Q > 0 && (!d_rstat || !d_rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_range_dev: NULL pointer or negative Q");
+        if (Q == 0) return TQ_OK;
+        const uint64_t total = choose4((uint64_t)ctx->T);
+        if (first_rank + (uint64_t)Q > total)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "rank range [%llu,+%lld) exceeds C(%lld,4)=%llu",
+                        (unsigned long long)first_rank, (long long)Q, (long long)ctx->T, (unsigned long long)total);
+        uint32_t *dq = d_quartets;
+        if (!dq) {
+            TQ_HIP(ctx, ctx->d_scratch.grow((size_t)Q * 16));
+            dq = (uint32_t *)ctx->d_scratch.get();
+        }
+        hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const uint64_t *)nullptr, first_rank, Q, (int32_t)ctx->T, dq);
+        TQ_LAUNCHED(ctx, "tq_resolve_range_dev");
+        OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
+        // consecutive lexicographic ranks are in (a,b,c) order already
+        if (int rc2 = enter_dev_api(ctx, (hipStream_t)stream)) return rc2;
+        return note_dev_api(ctx, (hipStream_t)stream,
+                            launch(ctx, dq, Q, subsample, false, true, out, (hipStream_t)stream, NoChunkHook()));
+    });
 }
 
 int tq_resolve_to_host(tq_ctx *ctx, const uint32_t *d_quartets, int64_t Q, int subsample, uint32_t *rstat,
                        double *rscor, uint8_t *flags)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!d_quartets || !rstat || !rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_to_host: NULL pointer or negative Q");
-    int rc = check_ready(ctx, subsample);
-    if (rc) return rc;
-    if (Q == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_streams(ctx))) return rc;
-    const size_t o_rstat = 0;
-    const size_t o_rscor = align_up(o_rstat + (size_t)Q * 8, 256);
-    const size_t o_flags = align_up(o_rscor + (size_t)Q * 24, 256);
-    TQ_HIP(ctx, ctx->d_scratch.grow(align_up(o_flags + (size_t)Q, 256)));
-    char *base = ctx->d_scratch;
-    return resolve_to_host(ctx, d_quartets, Q, subsample, false, rstat, rscor, flags, (uint32_t *)(base + o_rstat),
-                           (double *)(base + o_rscor), (uint8_t *)(base + o_flags));
+    return api(ctx, "tq_resolve_to_host", [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!d_quartets || !rstat || !rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_to_host: NULL pointer or negative Q");
+        int rc = check_ready(ctx, subsample);
+        if (rc) return rc;
+        if (Q == 0) return TQ_OK;
+        if ((rc = ensure_streams(ctx))) return rc;
+        const size_t o_rstat = 0;
+        const size_t o_rscor = align_up(o_rstat + (size_t)Q * 8, 256);
+        const size_t o_flags = align_up(o_rscor + (size_t)Q * 24, 256);
+        TQ_HIP(ctx, ctx->d_scratch.grow(align_up(o_flags + (size_t)Q, 256)));
+        char *base = ctx->d_scratch;
+        return resolve_to_host(ctx, d_quartets, Q, subsample, false, rstat, rscor, flags, (uint32_t *)(base + o_rstat),
+                               (double *)(base + o_rscor), (uint8_t *)(base + o_flags));
+    });
 }
 
 int tq_resolve_debug(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, int subsample, uint32_t *rstat,
                      double *rscor, uint8_t *flags, uint32_t *cmats, double *svds, int32_t *ranks)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!quartets || !rstat || !rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve: NULL pointer or negative Q");
-    int rc = check_ready(ctx, subsample);
-    if (rc) return rc;
-    if (Q == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    // Taxon indices are checked on the host (the kernels re-check and flag them, and never dereference a bad
-    // one).  For chunks of the size the reference's distributor hands out the same pass notices input that
-    // already is in (a,b,c) order -- its default mode's lexicographic chunks are (combinations.py:40-55) -- so
-    // that the device sort (about twenty small kernels, most of the time of a chunk of a few thousand
-    // quartets) is skipped.  A large batch is checked WHILE THE GPU WORKS on it (the pass over 16 B per quartet
-    // costs ~1 ms per 1e6 on the host, the sort it could save 0.2 ms).
-    constexpr int64_t CHECK_FIRST = 1 << 16;
-    auto check_indices = [ctx, quartets, Q]() -> int {
-        const uint32_t T = (uint32_t)ctx->T;
-        uint32_t worst = 0;
-        for (int64_t i = 0; i < 4 * Q; ++i) worst = quartets[i] > worst ? quartets[i] : worst;      // vectorises
-        if (worst < T) return TQ_OK;
-        for (int64_t i = 0; i < 4 * Q; ++i)
-            if (quartets[i] >= T)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "quartet %lld has taxon index %u >= T=%lld", (long long)(i / 4),
-                            quartets[i], (long long)ctx->T);
-        return TQ_OK;
-    };
-    bool input_sorted = false;
-    if (Q <= CHECK_FIRST) {
-        if ((rc = check_indices())) return rc;
-        bool sorted = true;
-        uint64_t prev_key = 0;
-        for (int64_t i = 0; i < Q; ++i) {
-            const uint32_t *q = quartets + i * 4;
-            const uint64_t key = ((uint64_t)q[0] << 42) | ((uint64_t)q[1] << 21) | (uint64_t)q[2];
-            sorted &= key >= prev_key;
-            prev_key = key;
+    return api(ctx, "tq_resolve_debug", [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!quartets || !rstat || !rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve: NULL pointer or negative Q");
+        int rc = check_ready(ctx, subsample);
+        if (rc) return rc;
+        if (Q == 0) return TQ_OK;
+        // Taxon indices are checked on the host (the kernels re-check and flag them, and never dereference a bad
+        // one).  For chunks of the size the reference's distributor hands out the same pass notices input that
+        // already is in (a,b,c) order -- its default mode's lexicographic chunks are (combinations.py:40-55) -- so
+        // that the device sort (about twenty small kernels, most of the time of a chunk of a few thousand
+        // quartets) is skipped.  A large batch is checked WHILE THE GPU WORKS on it (the pass over 16 B per quartet
+        // costs ~1 ms per 1e6 on the host, the sort it could save 0.2 ms).
+        constexpr int64_t CHECK_FIRST = 1 << 16;
+        auto check_indices = [ctx, quartets, Q]() -> int {
+            const uint32_t T = (uint32_t)ctx->T;
+            uint32_t worst = 0;
+            for (int64_t i = 0; i < 4 * Q; ++i) worst = quartets[i] > worst ? quartets[i] : worst;      // vectorises
+            if (worst < T) return TQ_OK;
+            for (int64_t i = 0; i < 4 * Q; ++i)
+                if (quartets[i] >= T)
+                    return fail(ctx, TQ_ERR_INVALID_ARG, "quartet %lld has taxon index %u >= T=%lld", (long long)(i / 4),
+                                quartets[i], (long long)ctx->T);
+            return TQ_OK;
+        };
+        bool input_sorted = false;
+        if (Q <= CHECK_FIRST) {
+            if ((rc = check_indices())) return rc;
+            bool sorted = true;
+            uint64_t prev_key = 0;
+            for (int64_t i = 0; i < Q; ++i) {
+                const uint32_t *q = quartets + i * 4;
+                const uint64_t key = ((uint64_t)q[0] << 42) | ((uint64_t)q[1] << 21) | (uint64_t)q[2];
+                sorted &= key >= prev_key;
+                prev_key = key;
+            }
+            input_sorted = sorted && ctx->T < (1 << 21);
         }
-        input_sorted = sorted && ctx->T < (1 << 21);
-    }
-    HostScratch h;
-    if ((rc = host_scratch(ctx, quartets, Q, cmats, svds, ranks, &h))) return rc;
-    if (!(cmats || svds || ranks)) {
-        if (Q <= CHECK_FIRST)
-            return resolve_to_host(ctx, h.dq(), Q, subsample, input_sorted, rstat, rscor, flags, h.rstat(), h.rscor(),
-                                   h.flags());
-        return resolve_to_host(ctx, h.dq(), Q, subsample, false, rstat, rscor, flags, h.rstat(), h.rscor(), h.flags(),
-                               check_indices);
-    }
-    if (Q > CHECK_FIRST && (rc = check_indices())) {
-        (void)hipStreamSynchronize(ctx->sK);
-        return rc;
-    }
-    return debug_to_host(ctx, h, Q, subsample, false, input_sorted, rstat, rscor, flags, cmats, svds, ranks);
+        HostScratch h;
+        if ((rc = host_scratch(ctx, quartets, Q, cmats, svds, ranks, &h))) return rc;
+        if (!(cmats || svds || ranks)) {
+            if (Q <= CHECK_FIRST)
+                return resolve_to_host(ctx, h.dq(), Q, subsample, input_sorted, rstat, rscor, flags, h.rstat(), h.rscor(),
+                                       h.flags());
+            return resolve_to_host(ctx, h.dq(), Q, subsample, false, rstat, rscor, flags, h.rstat(), h.rscor(), h.flags(),
+                                   check_indices);
+        }
+        if (Q > CHECK_FIRST && (rc = check_indices())) {
+            (void)hipStreamSynchronize(ctx->sK);
+            return rc;
+        }
+        return debug_to_host(ctx, h, Q, subsample, false, input_sorted, rstat, rscor, flags, cmats, svds, ranks);
+    });
 }
 
 int tq_resolve(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, int subsample, uint32_t *rstat, double *rscor,
@@ -2970,16 +3110,15 @@ int tq_resolve(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, int subsample, 
 int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!species_of) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: NULL pointer");
-    if (K < 4 || K > 0x7FFFFFFF)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: K=%lld species (a species quartet needs K >= 4)", (long long)K);
-    const int64_t known = ctx->have_data ? ctx->T : ctx->d_seqarr ? ctx->src_T : 0;
-    if (T < 1 || (known && T != known))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: T=%lld, the resident / source data have T=%lld", (long long)T,
-                    (long long)known);
-    std::vector<int32_t> size, members;
-    try {
-        size.assign((size_t)K, 0);
+    return api(ctx, "tq_set_species", [&]() -> int {
+        if (!species_of) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: NULL pointer");
+        if (K < 4 || K > 0x7FFFFFFF)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: K=%lld species (a species quartet needs K >= 4)", (long long)K);
+        const int64_t known = ctx->have_data ? ctx->T : ctx->d_seqarr ? ctx->src_T : 0;
+        if (T < 1 || (known && T != known))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_species: T=%lld, the resident / source data have T=%lld", (long long)T,
+                        (long long)known);
+        std::vector<int32_t> size((size_t)K, 0), members;
         for (int64_t i = 0; i < T; ++i) {
             const int32_t k = species_of[i];
             if (k < -1 || k >= K)
@@ -2998,75 +3137,74 @@ int tq_set_species(tq_ctx *ctx, const int32_t *species_of, int64_t T, int64_t K)
         std::vector<int32_t> fill(members.begin(), members.begin() + K);
         for (int64_t i = 0; i < T; ++i)
             if (species_of[i] >= 0) members[(size_t)(K + 1 + fill[(size_t)species_of[i]]++)] = (int32_t)i;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_set_species: out of host memory");
-    }
-    std::vector<int32_t> top(size);
-    std::sort(top.begin(), top.end(), [](int32_t a, int32_t b) { return a > b; });
-    uint64_t bound = 1;
-    for (int i = 0; i < 4; ++i) bound *= (uint64_t)top[(size_t)i];
-    const uint64_t bound5 = bound * (uint64_t)(K > 4 ? top[4] : 1);     // <= 255^5 < 2^40
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    TQ_HIP(ctx, hipDeviceSynchronize());         // a species call may still read the old map / table
-    ctx->sp_K = 0;
-    TQ_HIP(ctx, ctx->d_sp_members.alloc(members.size()));
-    TQ_HIP(ctx, hipMemcpy(ctx->d_sp_members, members.data(), members.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    ctx->sp_size.swap(size);
-    ctx->sp_T = T;
-    ctx->sp_K = K;
-    ctx->sp_bound = bound;
-    ctx->sp_bound5 = bound5;
-    ctx->sp_max = top[0];
-    ctx->sp_tab_gen = ~0ull;
-    return TQ_OK;
+        std::vector<int32_t> top(size);
+        std::sort(top.begin(), top.end(), [](int32_t a, int32_t b) { return a > b; });
+        uint64_t bound = 1;
+        for (int i = 0; i < 4; ++i) bound *= (uint64_t)top[(size_t)i];
+        const uint64_t bound5 = bound * (uint64_t)(K > 4 ? top[4] : 1);     // <= 255^5 < 2^40
+        TQ_HIP(ctx, hipDeviceSynchronize());         // a species call may still read the old map / table
+        ctx->sp_K = 0;
+        TQ_HIP(ctx, ctx->d_sp_members.alloc(members.size()));
+        TQ_HIP(ctx, hipMemcpy(ctx->d_sp_members, members.data(), members.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        ctx->sp_size.swap(size);
+        ctx->sp_T = T;
+        ctx->sp_K = K;
+        ctx->sp_bound = bound;
+        ctx->sp_bound5 = bound5;
+        ctx->sp_max = top[0];
+        ctx->sp_tab_gen = ~0ull;
+        return TQ_OK;
+    });
 }
 
 int tq_resolve_species_dev(tq_ctx *ctx, const uint32_t *d_squartets, int64_t Q, uint32_t *d_rstat, double *d_rscor,
                            uint8_t *d_flags, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!d_squartets || !d_rstat || !d_rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species_dev: NULL pointer or negative Q");
-    if (int rc = species_ready(ctx, "tq_resolve_species_dev")) return rc;
-    if (Q == 0) return TQ_OK;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;      // before any shared scratch is touched
-    OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
-    return note_dev_api(ctx, (hipStream_t)stream,
-                        launch(ctx, d_squartets, Q, 0, false, false, out, (hipStream_t)stream, NoChunkHook(), true));
+    return api(ctx, "tq_resolve_species_dev", [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!d_squartets || !d_rstat || !d_rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species_dev: NULL pointer or negative Q");
+        if (int rc = species_ready(ctx, "tq_resolve_species_dev")) return rc;
+        if (Q == 0) return TQ_OK;
+        if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;      // before any shared scratch is touched
+        OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
+        return note_dev_api(ctx, (hipStream_t)stream,
+                            launch(ctx, d_squartets, Q, 0, false, false, out, (hipStream_t)stream, NoChunkHook(), true));
+    });
 }
 
 int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor,
                              uint8_t *flags, uint32_t *cmats, double *svds, int32_t *ranks)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (Q < 0 || (Q > 0 && (!squartets || !rstat || !rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species: NULL pointer or negative Q");
-    int rc = species_ready(ctx, "tq_resolve_species");
-    if (rc) return rc;
-    if (Q == 0) return TQ_OK;
-    // ids on the host (the kernels re-check them and flag the row); a row that repeats a species can exceed the
-    // call's range bound, so its own product is checked when the bound leaves room for that
-    const uint32_t K = (uint32_t)ctx->sp_K;
-    const uint64_t lin4 = ctx->species_alleles ? 16 : 1;      // lineages per sample, to the fourth
-    const bool per_row = (unsigned __int128)ctx->S * ((uint64_t)ctx->sp_max * ctx->sp_max * ctx->sp_max * ctx->sp_max * lin4) >=
-                         ((unsigned __int128)1 << 32);
-    for (int64_t i = 0; i < Q; ++i) {
-        const uint32_t *q = squartets + 4 * i;
-        if ((q[0] >= K) | (q[1] >= K) | (q[2] >= K) | (q[3] >= K))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld has a species id >= K=%u", (long long)i, K);
-        if (per_row) {
-            const uint64_t p = (uint64_t)ctx->sp_size[q[0]] * ctx->sp_size[q[1]] * ctx->sp_size[q[2]] * ctx->sp_size[q[3]] * lin4;
-            if ((unsigned __int128)ctx->S * p >= ((unsigned __int128)1 << 32))
-                return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld: S=%lld x its lineage product %llu >= 2^32",
-                            (long long)i, (long long)ctx->S, (unsigned long long)p);
+    return api(ctx, "tq_resolve_species_debug", [&]() -> int {
+        if (Q < 0 || (Q > 0 && (!squartets || !rstat || !rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species: NULL pointer or negative Q");
+        int rc = species_ready(ctx, "tq_resolve_species");
+        if (rc) return rc;
+        if (Q == 0) return TQ_OK;
+        // ids on the host (the kernels re-check them and flag the row); a row that repeats a species can exceed the
+        // call's range bound, so its own product is checked when the bound leaves room for that
+        const uint32_t K = (uint32_t)ctx->sp_K;
+        const uint64_t lin4 = ctx->opt.species_alleles ? 16 : 1;      // lineages per sample, to the fourth
+        const bool per_row = (unsigned __int128)ctx->S * ((uint64_t)ctx->sp_max * ctx->sp_max * ctx->sp_max * ctx->sp_max * lin4) >=
+                             ((unsigned __int128)1 << 32);
+        for (int64_t i = 0; i < Q; ++i) {
+            const uint32_t *q = squartets + 4 * i;
+            if ((q[0] >= K) | (q[1] >= K) | (q[2] >= K) | (q[3] >= K))
+                return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld has a species id >= K=%u", (long long)i, K);
+            if (per_row) {
+                const uint64_t p = (uint64_t)ctx->sp_size[q[0]] * ctx->sp_size[q[1]] * ctx->sp_size[q[2]] * ctx->sp_size[q[3]] * lin4;
+                if ((unsigned __int128)ctx->S * p >= ((unsigned __int128)1 << 32))
+                    return fail(ctx, TQ_ERR_INVALID_ARG, "species quartet %lld: S=%lld x its lineage product %llu >= 2^32",
+                                (long long)i, (long long)ctx->S, (unsigned long long)p);
+            }
         }
-    }
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    HostScratch h;
-    if ((rc = host_scratch(ctx, squartets, Q, cmats, svds, ranks, &h))) return rc;
-    if (!(cmats || svds || ranks)) return species_to_host(ctx, h.dq(), Q, rstat, rscor, flags, h.rstat(), h.rscor(), h.flags());
-    return debug_to_host(ctx, h, Q, 0, true, false, rstat, rscor, flags, cmats, svds, ranks);
+        HostScratch h;
+        if ((rc = host_scratch(ctx, squartets, Q, cmats, svds, ranks, &h))) return rc;
+        if (!(cmats || svds || ranks)) return species_to_host(ctx, h.dq(), Q, rstat, rscor, flags, h.rstat(), h.rscor(), h.flags());
+        return debug_to_host(ctx, h, Q, 0, true, false, rstat, rscor, flags, cmats, svds, ranks);
+    });
 }
 
 int tq_resolve_species(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, uint32_t *rstat, double *rscor, uint8_t *flags)
@@ -3083,20 +3221,22 @@ int tq_pattern_class_table(uint8_t *out)
 
 int tq_scan_plan(const int64_t *rows, int64_t n, int64_t *plans, int64_t *n_kernels)
 {
-    if (n < 0 || (n && (!rows || !plans))) return TQ_ERR_INVALID_ARG;
-    if (n_kernels) *n_kernels = (int64_t)SCAN_TABLE.size();
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t *r = rows + i * 22;
-        const ScanKnobs k = {(int)r[0], (int)r[1], (int)r[2], (int)r[3], (int)r[4], (int)r[5], (int)r[6], (int)r[7], (int)r[8],
-                             (int)r[9], (int)r[10], r[11], r[12], (int)r[13], (int)r[14], (int)r[15]};
-        const ScanShape s = {r[16], r[17], r[18], r[19], (int)r[20], (int)r[21]};
-        const ScanPlan p = choose_scan(k, s);
-        const ScanKernel *kern = find_scan_kernel(p);
-        const int64_t out[12] = {p.form, p.sub, p.method, p.nw, p.shc, p.park, p.nrep, p.qpw, p.threads, p.grid, p.xcd_chunk,
-                                 kern ? (int64_t)(kern - SCAN_TABLE.data()) : -1};
-        memcpy(plans + i * 12, out, sizeof out);
-    }
-    return TQ_OK;
+    return api(nullptr, "tq_scan_plan", [&]() -> int {
+        if (n < 0 || (n && (!rows || !plans))) return TQ_ERR_INVALID_ARG;
+        if (n_kernels) *n_kernels = (int64_t)SCAN_TABLE.size();
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t *r = rows + i * 22;
+            const ScanKnobs k = {(int)r[0], (int)r[1], (int)r[2], (int)r[3], (int)r[4], (int)r[5], (int)r[6], (int)r[7], (int)r[8],
+                                 (int)r[9], (int)r[10], r[11], r[12], (int)r[13], (int)r[14], (int)r[15]};
+            const ScanShape s = {r[16], r[17], r[18], r[19], (int)r[20], (int)r[21]};
+            const ScanPlan p = choose_scan(k, s);
+            const ScanKernel *kern = find_scan_kernel(p);
+            const int64_t out[12] = {p.form, p.sub, p.method, p.nw, p.shc, p.park, p.nrep, p.qpw, p.threads, p.grid, p.xcd_chunk,
+                                     kern ? (int64_t)(kern - SCAN_TABLE.data()) : -1};
+            memcpy(plans + i * 12, out, sizeof out);
+        }
+        return TQ_OK;
+    });
 }
 
 int tq_patterns(tq_ctx *ctx, const uint32_t *sets, int64_t Q, int subsample, uint32_t *classes)
@@ -3133,10 +3273,12 @@ int tq_dstat_accumulate_dev(tq_ctx *ctx, const uint32_t *d_classes, int64_t n_se
                             const uint8_t *d_ia, const uint8_t *d_ib, int64_t N, double *d_acc, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    const char *who = "tq_dstat_accumulate_dev";
-    if (int rc = check_dstat_tests(ctx, who, d_classes && d_acc, n_sets, nullptr, d_set_of, ClassPairTests{d_ia, d_ib}, N, false))
-        return rc;
-    return launch_per_test(ctx, who, tq_dstat_kernel, DSTAT_THREADS, N, stream, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc);
+    return api(ctx, "tq_dstat_accumulate_dev", [&]() -> int {
+        const char *who = "tq_dstat_accumulate_dev";
+        if (int rc = check_dstat_tests(ctx, who, d_classes && d_acc, n_sets, nullptr, d_set_of, ClassPairTests{d_ia, d_ib}, N, false))
+            return rc;
+        return launch_per_test(ctx, who, tq_dstat_kernel, DSTAT_THREADS, N, stream, d_classes, n_sets, d_set_of, d_ia, d_ib, N, d_acc);
+    });
 }
 
 int tq_patterns_blocks(tq_ctx *ctx, const uint32_t *sets, int64_t Q, const int64_t *block_starts, int64_t B, uint32_t *classes)
@@ -3254,23 +3396,26 @@ int tq_timing_enable(tq_ctx *ctx, int on)
 int tq_timing_read_kernels(tq_ctx *ctx, double *ms, int n_ms, int64_t *calls)
 {
     if (!ctx || (n_ms > 0 && !ms)) return TQ_ERR_INVALID_ARG;
-    double t[TAG_COUNT] = {0, 0, 0, 0, 0};
-    hipEvent_t prev[2] = {nullptr, nullptr};
-    int rc = TQ_OK;
-    for (auto &m : ctx->marks) {
-        if (!rc && hipEventSynchronize(m.ev) != hipSuccess) rc = fail(ctx, TQ_ERR_HIP, "timing event failed");
-        if (!rc && m.tag >= 0 && m.tag < TAG_COUNT && prev[m.lane]) {
-            float a = 0.f;
-            if (hipEventElapsedTime(&a, prev[m.lane], m.ev) == hipSuccess) t[m.tag] += a;
+    return api(ctx, "tq_timing_read_kernels", [&]() -> int {
+        double t[TAG_COUNT] = {0, 0, 0, 0, 0};
+        hipEvent_t prev[2] = {nullptr, nullptr};
+        int rc = TQ_OK;
+        ctx->event_pool.reserve(ctx->event_pool.size() + ctx->marks.size());      // all or nothing: no push_back below throws
+        for (auto &m : ctx->marks) {
+            if (!rc && hipEventSynchronize(m.ev) != hipSuccess) rc = fail(ctx, TQ_ERR_HIP, "timing event failed");
+            if (!rc && m.tag >= 0 && m.tag < TAG_COUNT && prev[m.lane]) {
+                float a = 0.f;
+                if (hipEventElapsedTime(&a, prev[m.lane], m.ev) == hipSuccess) t[m.tag] += a;
+            }
+            prev[m.lane] = m.ev;
+            ctx->event_pool.push_back(m.ev);
         }
-        prev[m.lane] = m.ev;
-        ctx->event_pool.push_back(m.ev);
-    }
-    ctx->marks.clear();
-    for (int i = 0; i < n_ms; ++i) ms[i] = i < TAG_COUNT ? t[i] : 0.0;
-    if (calls) *calls = ctx->timed_calls;
-    ctx->timed_calls = 0;
-    return rc;
+        ctx->marks.clear();
+        for (int i = 0; i < n_ms; ++i) ms[i] = i < TAG_COUNT ? t[i] : 0.0;
+        if (calls) *calls = ctx->timed_calls;
+        ctx->timed_calls = 0;
+        return rc;
+    });
 }
 
 int tq_timing_read_split(tq_ctx *ctx, double *total_ms, double *scan_ms, double *svd_ms, int64_t *calls)
@@ -3293,186 +3438,37 @@ int tq_timing_read(tq_ctx *ctx, double *kernel_ms, int64_t *launches)
 int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
 {
     if (!ctx || !name) return TQ_ERR_INVALID_ARG;
-    if (!strcmp(name, "nrep")) {
-        if (value == 1 || value == 2 || value == 4 || value == 8 || value == 16 || value == 32) ctx->nrep = (int)value;
-        else if (value != 0) return fail(ctx, TQ_ERR_INVALID_ARG, "nrep must be 1,2,4,8,16 or 32");
-        else ctx->nrep = 1;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "waves_per_cu")) {
-        if (value < 0 || value > (1 << 20)) return fail(ctx, TQ_ERR_INVALID_ARG, "waves_per_cu must be 0..2^20");
-        ctx->waves_per_cu = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "xcd_remap")) {
-        ctx->xcd_remap = value != 0;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "count_invariant")) {
-        ctx->count_invariant = value != 0;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "scan_pair")) {
-        ctx->scan_pair = value != 0;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "scan_f4")) {
-        if (value < -1 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "scan_f4 must be -1 (subsample mode only), 0 or 1");
-        ctx->scan_f4 = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "site_pack")) {
-        if (value < -1 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "site_pack must be -1 (automatic), 0 or 1");
-        ctx->site_pack = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "boot_pack")) {
-        if (value < -1 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "boot_pack must be -1 (automatic), 0 or 1");
-        ctx->boot_pack = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "scan_dp")) {
-        if (value != 0 && value != 1) return fail(ctx, TQ_ERR_INVALID_ARG, "scan_dp must be 0 or 1");
-        ctx->scan_dp = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "dp_min_quartets")) {
-        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "dp_min_quartets must be >= 0");
-        ctx->dp_min_quartets = value ? value : 32768;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "wg_min_quartets")) {
-        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "wg_min_quartets must be >= 0");
-        ctx->wg_min_quartets = value ? value : 4096;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "bidiag_layout")) {
-        if (value < -1 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "bidiag_layout must be -1 (default), 0 or 1");
-        ctx->bidiag_layout = value < 0 ? 1 : (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "park_t")) {
-        ctx->park_t = value != 0;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "share_c")) {
-        ctx->share_c = value != 0;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "cons_hash_bits")) {              // read by tq_cons_create / tq_cons_reset
-        if (value < 0 || value > 64) return fail(ctx, TQ_ERR_INVALID_ARG, "cons_hash_bits must be 1..64 (0 = default 64)");
-        ctx->cons_hash_bits = value ? (int)value : 64;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "cons_scratch_bytes")) {          // read by tq_cons_create
-        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "cons_scratch_bytes must be >= 0 (0 = default 256 MiB)");
-        ctx->cons_scratch_bytes = value ? value : int64_t(256) << 20;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "stree_search_dev")) {
-        if (value < 0 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "stree_search_dev must be 0 or 1");
-        ctx->stree_search_dev = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "fit_scratch_bytes")) {
-        if (value < 1) return fail(ctx, TQ_ERR_INVALID_ARG, "fit_scratch_bytes must be at least 1");
-        ctx->fit_scratch_bytes = value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "qdist_scratch_bytes")) {         // read by tq_qd_create
-        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "qdist_scratch_bytes must be >= 0 (0 = default 256 MiB)");
-        ctx->qdist_scratch_bytes = value ? value : int64_t(256) << 20;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "qdist_kslices")) {               // read by every tq_qd_score*
-        if (value < 0 || value > 65535) return fail(ctx, TQ_ERR_INVALID_ARG, "qdist_kslices must be 0 (auto) .. 65535");
-        ctx->qdist_kslices = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "stree_lds")) {
-        if (value < 0 || value > 1) return fail(ctx, TQ_ERR_INVALID_ARG, "stree_lds must be 0 or 1");
-        ctx->stree_lds = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "svd_wpc")) {
-        if (value < 0 || value > (1 << 20)) return fail(ctx, TQ_ERR_INVALID_ARG, "svd_wpc must be 0..2^20");
-        ctx->svd_wpc = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "svd_chunk")) {
-        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "svd_chunk must be >= 0");
-        ctx->svd_chunk = value ? value : (1 << 18);
-        return TQ_OK;
-    }
-    if (!strcmp(name, "svd_streams")) {
-        if (value < 0 || value > 2) return fail(ctx, TQ_ERR_INVALID_ARG, "svd_streams must be 0 (default), 1 or 2");
-        ctx->svd_streams = value ? (int)value : 2;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "bdsqr_stats")) {                  // 1: allocate + zero the counters, 0: free them
-        ctx->d_bdsqr_stats.reset();
-        if (value) {
-            TQ_HIP(ctx, ctx->d_bdsqr_stats.alloc(8));
-            TQ_HIP(ctx, hipMemset(ctx->d_bdsqr_stats, 0, 8 * sizeof(uint64_t)));
+    return api(ctx, "tq_set_option", [&]() -> int {
+        if (!strcmp(name, "bdsqr_stats")) {                  // 1: allocate + zero the counters, 0: free them
+            ctx->d_bdsqr_stats.reset();
+            if (value) {
+                TQ_HIP(ctx, ctx->d_bdsqr_stats.alloc(8));
+                TQ_HIP(ctx, hipMemset(ctx->d_bdsqr_stats, 0, 8 * sizeof(uint64_t)));
+            }
+            return TQ_OK;
         }
+        const OptionRow *row = std::find_if(std::begin(OPTION_TABLE), std::end(OPTION_TABLE),
+                                            [name](const OptionRow &r) { return !strcmp(r.name, name); });
+        if (row == std::end(OPTION_TABLE)) return fail(ctx, TQ_ERR_INVALID_ARG, "unknown option '%s'", name);
+        const Options defaults;
+        int64_t v = value;
+        if (row->flag)
+            v = value != 0;
+        else if (value == row->default_key && row->default_key != NO_KEY)
+            v = row->i ? defaults.*row->i : defaults.*row->l;
+        else if (row->listed ? value < 0 || value > 63 || !(row->listed >> value & 1) : value < row->lo || value > row->hi)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s", row->refusal);
+        if (row->l == &Options::batch && v > 0x7FFFFFFFll) v = 0x7FFFFFFFll;     // item counts reach hipCUB as int
+        if (row->i == &Options::species_alleles && ctx->opt.species_alleles != (int)v)
+            ctx->sp_tab_gen = ~0ull;                        // the next species call rebuilds the table
+        if (row->i) ctx->opt.*row->i = (int)v;
+        else ctx->opt.*row->l = v;
         return TQ_OK;
-    }
-    if (!strcmp(name, "bdsqr_maxit")) {
-        if (value < 0 || value > 1000) return fail(ctx, TQ_ERR_INVALID_ARG, "bdsqr_maxit must be 0..1000");
-        ctx->bdsqr_maxit = value ? (int)value : 60;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "scan_wg")) {
-        if (value != 0 && value != 1 && value != 2 && value != 3 && value != 4 && value != 6 && value != 8 && value != 16)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "scan_wg must be 0 (default), 1, 2, 3, 4, 6, 8 or 16");
-        ctx->scan_wg = value ? (int)value : 4;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "svd_method")) {
-        if (value != 0 && value != 1) return fail(ctx, TQ_ERR_INVALID_ARG, "svd_method must be 0 (Jacobi) or 1 (HQR)");
-        ctx->svd_method = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "order")) {
-        if (value != 0 && value != 1) return fail(ctx, TQ_ERR_INVALID_ARG, "order must be 0 or 1");
-        ctx->order = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "scan_method")) {
-        if (value < -1 || value > 6)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "scan_method must be -1 (auto), 0, 1, 6 (or 2..5: timing diagnostics)");
-        ctx->scan_method = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "batch")) {
-        if (value < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "batch must be >= 0");
-        if (value > 0x7FFFFFFFll) value = 0x7FFFFFFFll;      // item counts reach hipCUB as int
-        ctx->batch = value ? value : (1 << 23);
-        return TQ_OK;
-    }
-    if (!strcmp(name, "species_method")) {
-        if (value < -1 || value > 1)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "species_method must be -1 (auto), 0 (VALU form) or 1 (MFMA form)");
-        ctx->species_method = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "species_alleles")) {
-        if (value != 0 && value != 1)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "species_alleles must be 0 (one lineage per sample) or 1 (two: both alleles)");
-        if (ctx->species_alleles != (int)value) ctx->sp_tab_gen = ~0ull;      // the next species call rebuilds the table
-        ctx->species_alleles = (int)value;
-        return TQ_OK;
-    }
-    if (!strcmp(name, "phases")) {
-        if (value != 0 && value != 1 && value != 2 && value != 3)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "phases must be 1, 2 or 3");
-        ctx->phases = value ? (int)value : 3;
-        return TQ_OK;
-    }
-    return fail(ctx, TQ_ERR_INVALID_ARG, "unknown option '%s'", name);
+    });
 }
 
-// the uploads, staging pieces and the packing rule of tq_set_source, after free_source; the caller frees again on a failure
+// the uploads, staging pieces and the packing rule of tq_set_source, after free_source; the caller frees again on a failure,
+// a returned code or an exception (the host copies below allocate: the recoded matrix is the largest host block of the library)
 static int build_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, const int64_t *spans, int64_t nloci, int64_t maxw)
 {
     TQ_HIP(ctx, ctx->d_seqarr.alloc((size_t)(T * S0)));
@@ -3480,11 +3476,7 @@ static int build_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S
     TQ_HIP(ctx, ctx->d_lidxs.alloc((size_t)nloci));
     TQ_HIP(ctx, hipMemcpy(ctx->d_seqarr, seqarr, (size_t)(T * S0), hipMemcpyHostToDevice));
     TQ_HIP(ctx, hipMemcpy(ctx->d_spans, spans, (size_t)nloci * 16, hipMemcpyHostToDevice));
-    try {
-        ctx->h_spans.assign(spans, spans + 2 * nloci);
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of host memory");
-    }
+    ctx->h_spans.assign(spans, spans + 2 * nloci);
     for (int i = 0; i < 2; ++i) {
         if (pool().alloc((size_t)nloci * 8, (void **)&ctx->h_lidx_stage[i]) != TQ_OK ||
             pool().alloc((size_t)nloci * 4, (void **)&ctx->h_pstart_stage[i]) != TQ_OK)
@@ -3495,32 +3487,28 @@ static int build_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S
     // the automatic rule of boot_pack = -1, once, on the source: its loci (the spans, in their order) with the bases recoded
     // as tq_set_data takes them -- a two-base IUPAC code counts as present (its first base) -- under the rule and the
     // 32-bit-offset condition of tq_set_data.  A replicate resamples these loci, so their statistics are the replicate's.
-    try {
-        std::vector<LocusRun> runs((size_t)nloci);
-        int64_t Ssrc = 0;
-        for (int64_t i = 0; i < nloci; ++i) {
-            runs[(size_t)i] = {Ssrc, spans[2 * i + 1] - spans[2 * i]};
-            Ssrc += runs[(size_t)i].len;
-        }
-        if (Ssrc < 0xFFFFFFFFll) {
-            uint8_t code[256];
-            memset(code, 78, sizeof code);
-            for (int v = 0; v < 4; ++v) code[v] = (uint8_t)v;
-            code[65] = 0; code[67] = 1; code[71] = 2; code[84] = 3;
-            code[82] = 0; code[75] = 3; code[83] = 1; code[89] = 1; code[87] = 0; code[77] = 0;     // R K S Y W M
-            std::vector<uint8_t> arr((size_t)(T * Ssrc));
-            for (int64_t t = 0; t < T; ++t)
-                for (int64_t i = 0; i < nloci; ++i)
-                    for (int64_t s = 0; s < runs[(size_t)i].len; ++s)
-                        arr[(size_t)(t * Ssrc + runs[(size_t)i].start + s)] = code[seqarr[t * S0 + spans[2 * i] + s]];
-            std::vector<uint32_t> src;
-            pack_sites(runs, src);
-            double cost[2], trips[2];
-            const double gain_low = pack_estimate(arr.data(), T, Ssrc, runs, src, cost, trips);
-            ctx->boot_pack_auto = pack_pays(gain_low) && pack_fits_offsets(T, src.size(), align_up((size_t)Ssrc, TILE));
-        }
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of host memory");
+    std::vector<LocusRun> runs((size_t)nloci);
+    int64_t Ssrc = 0;
+    for (int64_t i = 0; i < nloci; ++i) {
+        runs[(size_t)i] = {Ssrc, spans[2 * i + 1] - spans[2 * i]};
+        Ssrc += runs[(size_t)i].len;
+    }
+    if (Ssrc < 0xFFFFFFFFll) {
+        uint8_t code[256];
+        memset(code, 78, sizeof code);
+        for (int v = 0; v < 4; ++v) code[v] = (uint8_t)v;
+        code[65] = 0; code[67] = 1; code[71] = 2; code[84] = 3;
+        code[82] = 0; code[75] = 3; code[83] = 1; code[89] = 1; code[87] = 0; code[77] = 0;     // R K S Y W M
+        std::vector<uint8_t> arr((size_t)(T * Ssrc));
+        for (int64_t t = 0; t < T; ++t)
+            for (int64_t i = 0; i < nloci; ++i)
+                for (int64_t s = 0; s < runs[(size_t)i].len; ++s)
+                    arr[(size_t)(t * Ssrc + runs[(size_t)i].start + s)] = code[seqarr[t * S0 + spans[2 * i] + s]];
+        std::vector<uint32_t> src;
+        pack_sites(runs, src);
+        double cost[2], trips[2];
+        const double gain_low = pack_estimate(arr.data(), T, Ssrc, runs, src, cost, trips);
+        ctx->boot_pack_auto = pack_pays(gain_low) && pack_fits_offsets(T, src.size(), align_up((size_t)Ssrc, TILE));
     }
     ctx->src_T = T;
     ctx->src_S0 = S0;
@@ -3532,149 +3520,153 @@ static int build_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S
 int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0, const int64_t *spans, int64_t nloci)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!seqarr || !spans) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: NULL pointer");
-    if (T < 1 || S0 < 1 || nloci < 1 || T > 0x7FFFFFFF)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: bad shape T=%lld S0=%lld nloci=%lld", (long long)T,
-                    (long long)S0, (long long)nloci);
-    int64_t maxw = 0;
-    for (int64_t i = 0; i < nloci; ++i) {
-        const int64_t a = spans[2 * i], b = spans[2 * i + 1];
-        if (a < 0 || b <= a || b > S0)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: span %lld = [%lld,%lld) outside [0,%lld)",
-                        (long long)i, (long long)a, (long long)b, (long long)S0);
-        if (b - a > maxw) maxw = b - a;
-    }
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    free_source(ctx);
-    ctx->src_gen++;                     // a replicate of the earlier source is no replicate of this one
-    const int rc = build_source(ctx, seqarr, T, S0, spans, nloci, maxw);
-    if (rc) free_source(ctx);           // the context holds no half-built source
-    return rc;
+    return api(ctx, "tq_set_source", [&]() -> int {
+        if (!seqarr || !spans) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: NULL pointer");
+        if (T < 1 || S0 < 1 || nloci < 1 || T > 0x7FFFFFFF)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: bad shape T=%lld S0=%lld nloci=%lld", (long long)T,
+                        (long long)S0, (long long)nloci);
+        int64_t maxw = 0;
+        for (int64_t i = 0; i < nloci; ++i) {
+            const int64_t a = spans[2 * i], b = spans[2 * i + 1];
+            if (a < 0 || b <= a || b > S0)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_source: span %lld = [%lld,%lld) outside [0,%lld)",
+                            (long long)i, (long long)a, (long long)b, (long long)S0);
+            if (b - a > maxw) maxw = b - a;
+        }
+        free_source(ctx);
+        ctx->src_gen++;                     // a replicate of the earlier source is no replicate of this one
+        // the context holds no half-built source, whether the build returns a code or throws into the guard
+        struct Undo {
+            tq_ctx *ctx;
+            bool keep;
+            ~Undo() { if (!keep) free_source(ctx); }
+        } undo{ctx, false};
+        const int rc = build_source(ctx, seqarr, T, S0, spans, nloci, maxw);
+        undo.keep = rc == TQ_OK;
+        return rc;
+    });
 }
 
 int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t seed_shuffle, uint64_t seed_ambig,
                        int64_t *out_S, void *stream_)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!ctx->d_seqarr) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_source has not been called");
-    if (!lidxs || n != ctx->nloci)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: lidxs must hold nloci=%lld locus indices", (long long)ctx->nloci);
-    hipStream_t stream = (hipStream_t)stream_;
-    // replicate length on the host (jit/resample.py:7-17): no device round trip, the call stays asynchronous
-    int64_t S = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (lidxs[i] < 0 || lidxs[i] >= ctx->nloci)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: locus index %lld out of range", (long long)lidxs[i]);
-        S += ctx->h_spans[2 * lidxs[i] + 1] - ctx->h_spans[2 * lidxs[i]];
-    }
-    // the packed layout of the replicate, planned here at locus level (pack.hpp): the packed length is a launch argument,
-    // so it has to be known at enqueue time; only the packed start of every draw goes to the device
-    const bool pack = ctx->site_pack != 0 && (ctx->boot_pack > 0 || (ctx->boot_pack < 0 && ctx->boot_pack_auto));
-    int64_t pSp = 0;
-    if (pack) {
-        const int64_t *sp = ctx->h_spans.data();
-        try {
+    return api(ctx, "tq_bootstrap_async", [&]() -> int {
+        if (!ctx->d_seqarr) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_source has not been called");
+        if (!lidxs || n != ctx->nloci)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: lidxs must hold nloci=%lld locus indices", (long long)ctx->nloci);
+        hipStream_t stream = (hipStream_t)stream_;
+        // replicate length on the host (jit/resample.py:7-17): no device round trip, the call stays asynchronous
+        int64_t S = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            if (lidxs[i] < 0 || lidxs[i] >= ctx->nloci)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: locus index %lld out of range", (long long)lidxs[i]);
+            S += ctx->h_spans[2 * lidxs[i] + 1] - ctx->h_spans[2 * lidxs[i]];
+        }
+        // the packed layout of the replicate, planned here at locus level (pack.hpp): the packed length is a launch argument,
+        // so it has to be known at enqueue time; only the packed start of every draw goes to the device
+        const bool pack = ctx->opt.site_pack != 0 && (ctx->opt.boot_pack > 0 || (ctx->opt.boot_pack < 0 && ctx->boot_pack_auto));
+        int64_t pSp = 0;
+        if (pack) {
+            const int64_t *sp = ctx->h_spans.data();
             pSp = (int64_t)ctx->boot_plan.plan((size_t)n, [sp, lidxs](size_t i) { return sp[2 * lidxs[i] + 1] - sp[2 * lidxs[i]]; });
-        } catch (const std::bad_alloc &) {
-            return fail(ctx, TQ_ERR_OOM, "tq_bootstrap: out of host memory");
+            if (pSp >= 0xFFFFFFFFll) pSp = 0;              // the map holds positions as u32: such a replicate keeps the natural layout
         }
-        if (pSp >= 0xFFFFFFFFll) pSp = 0;              // the map holds positions as u32: such a replicate keeps the natural layout
-    }
-    const int64_t pW = pSp / 32;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc0 = enter_dev_api(ctx, stream)) return rc0;      // a resolve still scanning the previous replicate on another stream
-    const int64_t T = ctx->src_T;
-    // worst-case replicate length; buffers grow only
-    const int64_t cap = n * ctx->max_width;
-    if (cap > ctx->boot_cap) {
-        TQ_HIP(ctx, hipDeviceSynchronize());
-        ctx->d_boot.reset();
-        ctx->d_boot_tmp.reset();
-        ctx->boot_cap = 0;
-        TQ_HIP(ctx, ctx->d_boot.alloc((size_t)(2 * (n + 1) + 2 * cap)));
-        size_t tmp = 0;
-        uint32_t *u = ctx->d_boot;
-        TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, u, u, (int)(n + 1)));
-        size_t tmp2 = 0;
-        TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, u, u, (int)(cap / 32 + 2)));
-        if (tmp2 > tmp) tmp = tmp2;
-        TQ_HIP(ctx, ctx->d_boot_tmp.alloc(tmp ? tmp : 16));
-        ctx->boot_tmp_bytes = tmp;
-        ctx->boot_cap = cap;
-    }
-    if (S < 1 || S > ctx->boot_cap) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: replicate length %lld", (long long)S);
-    const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
-    const int64_t W = Sp / 32;
-    SiteSet &nat = ctx->nat, &pk = ctx->pk;
-    if (Sp > nat.capSp || T != ctx->T) {
-        TQ_HIP(ctx, hipDeviceSynchronize());           // kernels of the previous replicate may still read the old buffers
-        free_data(ctx);
-        TQ_HIP(ctx, nat.alloc(T, (int64_t)align_up((size_t)(Sp + Sp / 8), TILE), true));   // head-room: replicate lengths vary
-    }
-    // the packed set grows only, with the same head-room; a set tq_set_data allocated serves while it is large enough
-    if (pSp > pk.capSp || (size_t)pSp > ctx->d_pk_src.cap()) {
-        TQ_HIP(ctx, hipDeviceSynchronize());
-        const int64_t capSp = (int64_t)align_up((size_t)(pSp + pSp / 8), TILE);
-        if (pSp > pk.capSp) {
-            ctx->pk_gen = ~0ull;
-            ctx->pk_from_boot = false;
-            TQ_HIP(ctx, pk.alloc(T, capSp, false));
+        const int64_t pW = pSp / 32;
+        if (int rc0 = enter_dev_api(ctx, stream)) return rc0;      // a resolve still scanning the previous replicate on another stream
+        const int64_t T = ctx->src_T;
+        // worst-case replicate length; buffers grow only
+        const int64_t cap = n * ctx->max_width;
+        if (cap > ctx->boot_cap) {
+            TQ_HIP(ctx, hipDeviceSynchronize());
+            ctx->d_boot.reset();
+            ctx->d_boot_tmp.reset();
+            ctx->boot_cap = 0;
+            TQ_HIP(ctx, ctx->d_boot.alloc((size_t)(2 * (n + 1) + 2 * cap)));
+            size_t tmp = 0;
+            uint32_t *u = ctx->d_boot;
+            TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, u, u, (int)(n + 1)));
+            size_t tmp2 = 0;
+            TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, u, u, (int)(cap / 32 + 2)));
+            if (tmp2 > tmp) tmp = tmp2;
+            TQ_HIP(ctx, ctx->d_boot_tmp.alloc(tmp ? tmp : 16));
+            ctx->boot_tmp_bytes = tmp;
+            ctx->boot_cap = cap;
         }
-        TQ_HIP(ctx, ctx->d_pk_src.grow((size_t)capSp));
-    }
-    uint32_t *widths = ctx->d_boot, *offsets = widths + (n + 1);
-    uint32_t *src_col = offsets + (n + 1), *site_locus = src_col + ctx->boot_cap;
-    // locus indices through a page-locked staging piece (two in turn, so that the draws of the next replicate
-    // can be handed over while this copy is still queued)
-    const unsigned turn = ctx->lidx_turn++ & 1u;
-    TQ_HIP(ctx, hipEventSynchronize(ctx->ev_lidx[turn]));
-    memcpy(ctx->h_lidx_stage[turn], lidxs, (size_t)n * 8);
-    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_lidxs, ctx->h_lidx_stage[turn], (size_t)n * 8, hipMemcpyHostToDevice, stream));
-    if (pSp) {
-        uint32_t *stage = ctx->h_pstart_stage[turn];
-        for (int64_t i = 0; i < n; ++i) stage[i] = (uint32_t)ctx->boot_plan.start[(size_t)i];
-        TQ_HIP(ctx, hipMemcpyAsync(ctx->d_pstart, stage, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    }
-    TQ_HIP(ctx, hipEventRecord(ctx->ev_lidx[turn], stream));
-    TQ_HIP(ctx, hipMemsetAsync(widths + n, 0, sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(tq_boot_width_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->d_spans,
-                       ctx->d_lidxs, n, ctx->nloci, widths);
-    size_t tmp = ctx->boot_tmp_bytes;
-    TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ctx->d_boot_tmp, tmp, widths, offsets, (int)(n + 1), stream));
-    hipLaunchKernelGGL(tq_boot_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->d_spans,
-                       ctx->d_lidxs, offsets, n, ctx->nloci, seed_shuffle, src_col, site_locus);
-    const int64_t nw = T * W;
-    hipLaunchKernelGGL(tq_boot_build_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, ctx->d_seqarr,
-                       ctx->src_S0, src_col, site_locus, S, Sp, W, (int32_t)T, seed_ambig, nat.rows, nat.nib, nat.nib5,
-                       nat.planes, nat.planes3, nat.runbeg(T));
-    TQ_HIP(ctx, hipGetLastError());
-    if (pSp) {
-        TQ_HIP(ctx, hipMemsetAsync(ctx->d_pk_src, 0xFF, (size_t)pSp * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(tq_boot_pack_map_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream,
-                           (const uint32_t *)offsets, (const uint32_t *)site_locus, (const uint32_t *)ctx->d_pstart, S, n, pSp,
-                           ctx->d_pk_src);
-        const int64_t np = T * pW;
-        hipLaunchKernelGGL(tq_boot_pack_build_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream,
-                           (const uint32_t *)ctx->d_pk_src, (const uint8_t *)nat.nib5, (const uint32_t *)nat.runbeg(T), S, Sp,
-                           pSp, pW, (int32_t)T, pk.rows, pk.nib, pk.planes, pk.planes3, pk.runbeg(T));
-        TQ_HIP(ctx, hipGetLastError());
-    }
-    ctx->T = T;
-    ctx->S = S;
-    nat.set_sites(Sp);
-    ctx->have_data = true;
-    ctx->locus_runs_ok = true;          // locus ids are the ordinals 0..n-1, one run each
-    ctx->scanned_Q = 0;
-    ctx->data_gen++;                    // the species table is rebuilt by the next species call
-    ctx->boot_gen = ctx->data_gen;
-    ctx->boot_src_gen = ctx->src_gen;
-    if (pSp) {
-        pk.set_sites(pSp);
-        ctx->pk_gen = ctx->data_gen;
-        ctx->pk_from_boot = true;
-    }
-    if (out_S) *out_S = S;
-    return note_dev_api(ctx, stream, TQ_OK);       // the host API must not scan a half-built replicate
+        if (S < 1 || S > ctx->boot_cap) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_bootstrap: replicate length %lld", (long long)S);
+        const int64_t Sp = (int64_t)align_up((size_t)S, TILE);
+        const int64_t W = Sp / 32;
+        SiteSet &nat = ctx->nat, &pk = ctx->pk;
+        if (Sp > nat.capSp || T != ctx->T) {
+            TQ_HIP(ctx, hipDeviceSynchronize());           // kernels of the previous replicate may still read the old buffers
+            free_data(ctx);
+            TQ_HIP(ctx, nat.alloc(T, (int64_t)align_up((size_t)(Sp + Sp / 8), TILE), true));   // head-room: replicate lengths vary
+        }
+        // the packed set grows only, with the same head-room; a set tq_set_data allocated serves while it is large enough
+        if (pSp > pk.capSp || (size_t)pSp > ctx->d_pk_src.cap()) {
+            TQ_HIP(ctx, hipDeviceSynchronize());
+            const int64_t capSp = (int64_t)align_up((size_t)(pSp + pSp / 8), TILE);
+            if (pSp > pk.capSp) {
+                ctx->pk_gen = ~0ull;
+                ctx->pk_from_boot = false;
+                TQ_HIP(ctx, pk.alloc(T, capSp, false));
+            }
+            TQ_HIP(ctx, ctx->d_pk_src.grow((size_t)capSp));
+        }
+        uint32_t *widths = ctx->d_boot, *offsets = widths + (n + 1);
+        uint32_t *src_col = offsets + (n + 1), *site_locus = src_col + ctx->boot_cap;
+        // locus indices through a page-locked staging piece (two in turn, so that the draws of the next replicate
+        // can be handed over while this copy is still queued)
+        const unsigned turn = ctx->lidx_turn++ & 1u;
+        TQ_HIP(ctx, hipEventSynchronize(ctx->ev_lidx[turn]));
+        memcpy(ctx->h_lidx_stage[turn], lidxs, (size_t)n * 8);
+        TQ_HIP(ctx, hipMemcpyAsync(ctx->d_lidxs, ctx->h_lidx_stage[turn], (size_t)n * 8, hipMemcpyHostToDevice, stream));
+        if (pSp) {
+            uint32_t *stage = ctx->h_pstart_stage[turn];
+            for (int64_t i = 0; i < n; ++i) stage[i] = (uint32_t)ctx->boot_plan.start[(size_t)i];
+            TQ_HIP(ctx, hipMemcpyAsync(ctx->d_pstart, stage, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        }
+        TQ_HIP(ctx, hipEventRecord(ctx->ev_lidx[turn], stream));
+        TQ_HIP(ctx, hipMemsetAsync(widths + n, 0, sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(tq_boot_width_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->d_spans,
+                           ctx->d_lidxs, n, ctx->nloci, widths);
+        size_t tmp = ctx->boot_tmp_bytes;
+        TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ctx->d_boot_tmp, tmp, widths, offsets, (int)(n + 1), stream));
+        hipLaunchKernelGGL(tq_boot_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->d_spans,
+                           ctx->d_lidxs, offsets, n, ctx->nloci, seed_shuffle, src_col, site_locus);
+        const int64_t nw = T * W;
+        hipLaunchKernelGGL(tq_boot_build_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, ctx->d_seqarr,
+                           ctx->src_S0, src_col, site_locus, S, Sp, W, (int32_t)T, seed_ambig, nat.rows, nat.nib, nat.nib5,
+                           nat.planes, nat.planes3, nat.runbeg(T));
+        TQ_LAUNCHED(ctx, "tq_bootstrap_async");
+        if (pSp) {
+            TQ_HIP(ctx, hipMemsetAsync(ctx->d_pk_src, 0xFF, (size_t)pSp * sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(tq_boot_pack_map_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, stream,
+                               (const uint32_t *)offsets, (const uint32_t *)site_locus, (const uint32_t *)ctx->d_pstart, S, n, pSp,
+                               ctx->d_pk_src);
+            const int64_t np = T * pW;
+            hipLaunchKernelGGL(tq_boot_pack_build_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream,
+                               (const uint32_t *)ctx->d_pk_src, (const uint8_t *)nat.nib5, (const uint32_t *)nat.runbeg(T), S, Sp,
+                               pSp, pW, (int32_t)T, pk.rows, pk.nib, pk.planes, pk.planes3, pk.runbeg(T));
+            TQ_LAUNCHED(ctx, "tq_bootstrap_async");
+        }
+        ctx->T = T;
+        ctx->S = S;
+        nat.set_sites(Sp);
+        ctx->have_data = true;
+        ctx->locus_runs_ok = true;          // locus ids are the ordinals 0..n-1, one run each
+        ctx->scanned_Q = 0;
+        ctx->data_gen++;                    // the species table is rebuilt by the next species call
+        ctx->boot_gen = ctx->data_gen;
+        ctx->boot_src_gen = ctx->src_gen;
+        if (pSp) {
+            pk.set_sites(pSp);
+            ctx->pk_gen = ctx->data_gen;
+            ctx->pk_from_boot = true;
+        }
+        if (out_S) *out_S = S;
+        return note_dev_api(ctx, stream, TQ_OK);       // the host API must not scan a half-built replicate
+    });
 }
 
 int tq_bootstrap(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t seed_shuffle, uint64_t seed_ambig,
@@ -3689,55 +3681,54 @@ int tq_bootstrap(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t seed_shu
 int tq_sample_quartets_dev(tq_ctx *ctx, uint64_t seed, int64_t Q, uint64_t *d_ranks, uint32_t *d_quartets, void *stream)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!ctx->have_data && !ctx->d_seqarr) return fail(ctx, TQ_ERR_NO_DATA, "no data on the device (T unknown)");
-    if (Q < 0 || (Q > 0 && !d_quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_sample_quartets_dev: NULL pointer or negative Q");
-    const uint64_t T = (uint64_t)(ctx->have_data ? ctx->T : ctx->src_T);
-    const uint64_t total = choose4(T);
-    if ((uint64_t)Q > total)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "cannot draw %lld distinct quartets from C(%llu,4)=%llu", (long long)Q,
-                    (unsigned long long)T, (unsigned long long)total);
-    if (Q == 0) return TQ_OK;
-    int half = 1;
-    while (half < 32 && (1ull << (2 * half)) < total) ++half;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(tq_sample_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, total,
-                       half, Q, (int32_t)T, d_ranks, d_quartets);
-    TQ_HIP(ctx, hipGetLastError());
-    return TQ_OK;
+    return api(ctx, "tq_sample_quartets_dev", [&]() -> int {
+        if (!ctx->have_data && !ctx->d_seqarr) return fail(ctx, TQ_ERR_NO_DATA, "no data on the device (T unknown)");
+        if (Q < 0 || (Q > 0 && !d_quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_sample_quartets_dev: NULL pointer or negative Q");
+        const uint64_t T = (uint64_t)(ctx->have_data ? ctx->T : ctx->src_T);
+        const uint64_t total = choose4(T);
+        if ((uint64_t)Q > total)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "cannot draw %lld distinct quartets from C(%llu,4)=%llu", (long long)Q,
+                        (unsigned long long)T, (unsigned long long)total);
+        if (Q == 0) return TQ_OK;
+        int half = 1;
+        while (half < 32 && (1ull << (2 * half)) < total) ++half;
+        hipLaunchKernelGGL(tq_sample_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, total,
+                           half, Q, (int32_t)T, d_ranks, d_quartets);
+        TQ_LAUNCHED(ctx, "tq_sample_quartets_dev");
+        return TQ_OK;
+    });
 }
 
 int tq_get_data(tq_ctx *ctx, uint8_t *tmparr, uint32_t *tmpmap)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
-    if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "no replicate on the device");
-    if (!tmparr || !tmpmap) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_get_data: NULL pointer");
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    TQ_HIP(ctx, hipDeviceSynchronize());     // a replicate may still be queued (tq_bootstrap_async) on any stream
-    const SiteSet &nat = ctx->nat;
-    const int64_t T = ctx->T, S = ctx->S, W = nat.W;
-    const size_t bytes = align_up((size_t)(T * S), 256) + align_up((size_t)S * 8, 256) + align_up((size_t)(W + 1) * 8, 256);
-    TQ_HIP(ctx, ctx->d_scratch.grow(bytes));
-    uint8_t *d_arr = (uint8_t *)ctx->d_scratch.get();
-    uint32_t *d_map = (uint32_t *)(ctx->d_scratch + align_up((size_t)(T * S), 256));
-    uint32_t *d_cnt = (uint32_t *)((char *)d_map + align_up((size_t)S * 8, 256));
-    uint32_t *d_base = d_cnt + (W + 1);
-    hipLaunchKernelGGL(tq_export_kernel, dim3((unsigned)((T * S + 255) / 256)), dim3(256), 0, 0, nat.rows, nat.planes, S,
-                       nat.Sp, W, (int32_t)T, d_arr, d_map);
-    hipLaunchKernelGGL(tq_export_runcount_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, nat.planes, W, d_cnt);
-    size_t tmp = 0;
-    TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_cnt, d_base, (int)W));
-    DevBuf<char> d_tmp;
-    TQ_HIP(ctx, d_tmp.alloc(tmp ? tmp : 16));
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(d_tmp.get(), tmp, d_cnt, d_base, (int)W);
-    if (e == hipSuccess) {
+    return api(ctx, "tq_get_data", [&]() -> int {
+        if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "no replicate on the device");
+        if (!tmparr || !tmpmap) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_get_data: NULL pointer");
+        TQ_HIP(ctx, hipDeviceSynchronize());     // a replicate may still be queued (tq_bootstrap_async) on any stream
+        const SiteSet &nat = ctx->nat;
+        const int64_t T = ctx->T, S = ctx->S, W = nat.W;
+        const size_t bytes = align_up((size_t)(T * S), 256) + align_up((size_t)S * 8, 256) + align_up((size_t)(W + 1) * 8, 256);
+        TQ_HIP(ctx, ctx->d_scratch.grow(bytes));
+        uint8_t *d_arr = (uint8_t *)ctx->d_scratch.get();
+        uint32_t *d_map = (uint32_t *)(ctx->d_scratch + align_up((size_t)(T * S), 256));
+        uint32_t *d_cnt = (uint32_t *)((char *)d_map + align_up((size_t)S * 8, 256));
+        uint32_t *d_base = d_cnt + (W + 1);
+        hipLaunchKernelGGL(tq_export_kernel, dim3((unsigned)((T * S + 255) / 256)), dim3(256), 0, 0, nat.rows, nat.planes, S,
+                           nat.Sp, W, (int32_t)T, d_arr, d_map);
+        hipLaunchKernelGGL(tq_export_runcount_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, nat.planes, W, d_cnt);
+        size_t tmp = 0;
+        TQ_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_cnt, d_base, (int)W));
+        DevBuf<char> d_tmp;
+        TQ_HIP(ctx, d_tmp.alloc(tmp ? tmp : 16));
+        TQ_HIPF(ctx, "tq_get_data", hipcub::DeviceScan::ExclusiveSum(d_tmp.get(), tmp, d_cnt, d_base, (int)W));
         hipLaunchKernelGGL(tq_export_locus_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, 0, nat.planes,
                            (const uint32_t *)d_base, S, W, d_map);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(tmparr, d_arr, (size_t)(T * S), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(tmpmap, d_map, (size_t)S * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_get_data: %s", hipGetErrorString(e));
-    return TQ_OK;
+        TQ_LAUNCHED(ctx, "tq_get_data");
+        TQ_HIPF(ctx, "tq_get_data", hipMemcpy(tmparr, d_arr, (size_t)(T * S), hipMemcpyDeviceToHost));
+        TQ_HIPF(ctx, "tq_get_data", hipMemcpy(tmpmap, d_map, (size_t)S * 8, hipMemcpyDeviceToHost));
+        return TQ_OK;
+    });
 }
 
 int tq_data_shape(tq_ctx *ctx, int64_t *T, int64_t *S)
@@ -3751,75 +3742,76 @@ int tq_data_shape(tq_ctx *ctx, int64_t *T, int64_t *S)
 int tq_debug_fetch(tq_ctx *ctx, int which, void *dst, int64_t bytes)
 {
     if (!ctx || !dst || bytes < 0) return TQ_ERR_INVALID_ARG;
-    if (which == 4) {                       // the packed layout set: {its sites (0: none), 1 if the subsample scans read it now}
-        const int64_t st[2] = {ctx->pk.Sp, ctx->pk.rows && scan_data(ctx, 1).rows == ctx->pk.rows ? 1 : 0};
-        if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=4 takes 16 bytes");
-        memcpy(dst, st, sizeof st);
-        return TQ_OK;
-    }
-    if (which == 6) {                       // the most recent scan launch: {kernel form, T * pitch of the set it read, packed}
-        const int64_t st[3] = {ctx->last_scan_form, ctx->last_scan_tpitch, ctx->last_scan_packed};
-        if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=6 takes 24 bytes");
-        memcpy(dst, st, sizeof st);
-        return TQ_OK;
-    }
-    if (which == 5) {                       // the map of the current replicate's packed set (option boot_pack)
-        if (!ctx->pk_from_boot || !ctx->pk.rows || ctx->pk_gen != ctx->data_gen)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 needs a current packed set built by tq_bootstrap");
-        if (bytes != ctx->pk.Sp * (int64_t)sizeof(uint32_t))
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 takes %lld bytes", (long long)(ctx->pk.Sp * 4));
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
+    return api(ctx, "tq_debug_fetch", [&]() -> int {
+        if (which == 4) {                       // the packed layout set: {its sites (0: none), 1 if the subsample scans read it now}
+            const int64_t st[2] = {ctx->pk.Sp, ctx->pk.rows && scan_data(ctx, 1).rows == ctx->pk.rows ? 1 : 0};
+            if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=4 takes 16 bytes");
+            memcpy(dst, st, sizeof st);
+            return TQ_OK;
+        }
+        if (which == 6) {                       // the most recent scan launch: {kernel form, T * pitch of the set it read, packed}
+            const int64_t st[3] = {ctx->last_scan_form, ctx->last_scan_tpitch, ctx->last_scan_packed};
+            if (bytes != (int64_t)sizeof st) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=6 takes 24 bytes");
+            memcpy(dst, st, sizeof st);
+            return TQ_OK;
+        }
+        if (which == 5) {                       // the map of the current replicate's packed set (option boot_pack)
+            if (!ctx->pk_from_boot || !ctx->pk.rows || ctx->pk_gen != ctx->data_gen)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 needs a current packed set built by tq_bootstrap");
+            if (bytes != ctx->pk.Sp * (int64_t)sizeof(uint32_t))
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: which=5 takes %lld bytes", (long long)(ctx->pk.Sp * 4));
+            TQ_HIP(ctx, hipDeviceSynchronize());
+            TQ_HIP(ctx, hipMemcpy(dst, ctx->d_pk_src, (size_t)bytes, hipMemcpyDeviceToHost));
+            return TQ_OK;
+        }
+        const void *src = which == 0 ? (const void *)ctx->d_cm.get() : which == 1 ? (const void *)ctx->d_de.get()
+                          : which == 2 ? (const void *)ctx->d_sv.get() : which == 3 ? (const void *)ctx->d_bdsqr_stats.get() : nullptr;
+        if (!src) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: nothing to fetch (which=%d)", which);
         TQ_HIP(ctx, hipDeviceSynchronize());
-        TQ_HIP(ctx, hipMemcpy(dst, ctx->d_pk_src, (size_t)bytes, hipMemcpyDeviceToHost));
+        TQ_HIP(ctx, hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
         return TQ_OK;
-    }
-    const void *src = which == 0 ? (const void *)ctx->d_cm.get() : which == 1 ? (const void *)ctx->d_de.get()
-                      : which == 2 ? (const void *)ctx->d_sv.get() : which == 3 ? (const void *)ctx->d_bdsqr_stats.get() : nullptr;
-    if (!src) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_debug_fetch: nothing to fetch (which=%d)", which);
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    TQ_HIP(ctx, hipDeviceSynchronize());
-    TQ_HIP(ctx, hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
-    return TQ_OK;
+    });
 }
 
 int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint32_t *work, int reps, double *ms)
 {
     if (!ctx || !de || nmat < 1 || reps < 1) return TQ_ERR_INVALID_ARG;
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<double> d_de, d_sv;      // locals: every exit frees them
-    DevBuf<uint32_t> d_work;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = TQ_OK;
-    auto step = [&](hipError_t e, const char *what) {
-        if (!rc && e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_debug_bdsqr: %s: %s", what, hipGetErrorString(e));
-    };
-    step(d_de.alloc((size_t)nmat * 32), "hipMalloc");
-    if (!rc) step(d_sv.alloc((size_t)nmat * 16), "hipMalloc");
-    if (!rc) step(d_work.alloc((size_t)nmat), "hipMalloc");
-    if (!rc) step(hipMemcpy(d_de, de, (size_t)nmat * 256, hipMemcpyHostToDevice), "H2D");
-    if (!rc) step(hipEventCreate(&e0), "event");
-    if (!rc) step(hipEventCreate(&e1), "event");
-    const unsigned grid = (unsigned)((nmat + WAVE - 1) / WAVE);
-    if (!rc) {
-        // once with the per-matrix counters (slower), then `reps` timed launches of the product form
-        hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->bdsqr_maxit,
-                           (unsigned long long *)nullptr, d_work.get());
-        step(hipGetLastError(), "launch");
-        if (!rc) step(hipEventRecord(e0, 0), "record");
-        for (int i = 0; i < reps && !rc; ++i)
-            hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->bdsqr_maxit,
-                               (unsigned long long *)nullptr, (uint32_t *)nullptr);
-        if (!rc) step(hipEventRecord(e1, 0), "record");
-        if (!rc) step(hipEventSynchronize(e1), "sync");
-        float t = 0.f;
-        if (!rc) step(hipEventElapsedTime(&t, e0, e1), "elapsed");
-        if (ms) *ms = (double)t / reps;
-    }
-    if (!rc && sv) step(hipMemcpy(sv, d_sv, (size_t)nmat * 128, hipMemcpyDeviceToHost), "D2H");
-    if (!rc && work) step(hipMemcpy(work, d_work, (size_t)nmat * 4, hipMemcpyDeviceToHost), "D2H");
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    return api(ctx, "tq_debug_bdsqr", [&]() -> int {
+        DevBuf<double> d_de, d_sv;      // locals: every exit frees them
+        DevBuf<uint32_t> d_work;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        int rc = TQ_OK;
+        auto step = [&](hipError_t e, const char *what) {
+            if (!rc && e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_debug_bdsqr: %s: %s", what, hipGetErrorString(e));
+        };
+        step(d_de.alloc((size_t)nmat * 32), "hipMalloc");
+        if (!rc) step(d_sv.alloc((size_t)nmat * 16), "hipMalloc");
+        if (!rc) step(d_work.alloc((size_t)nmat), "hipMalloc");
+        if (!rc) step(hipMemcpy(d_de, de, (size_t)nmat * 256, hipMemcpyHostToDevice), "H2D");
+        if (!rc) step(hipEventCreate(&e0), "event");
+        if (!rc) step(hipEventCreate(&e1), "event");
+        const unsigned grid = (unsigned)((nmat + WAVE - 1) / WAVE);
+        if (!rc) {
+            // once with the per-matrix counters (slower), then `reps` timed launches of the product form
+            hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->opt.bdsqr_maxit,
+                               (unsigned long long *)nullptr, d_work.get());
+            step(hipGetLastError(), "launch");
+            if (!rc) step(hipEventRecord(e0, 0), "record");
+            for (int i = 0; i < reps && !rc; ++i)
+                hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->opt.bdsqr_maxit,
+                                   (unsigned long long *)nullptr, (uint32_t *)nullptr);
+            if (!rc) step(hipEventRecord(e1, 0), "record");
+            if (!rc) step(hipEventSynchronize(e1), "sync");
+            float t = 0.f;
+            if (!rc) step(hipEventElapsedTime(&t, e0, e1), "elapsed");
+            if (ms) *ms = (double)t / reps;
+        }
+        if (!rc && sv) step(hipMemcpy(sv, d_sv, (size_t)nmat * 128, hipMemcpyDeviceToHost), "D2H");
+        if (!rc && work) step(hipMemcpy(work, d_work, (size_t)nmat * 4, hipMemcpyDeviceToHost), "D2H");
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return rc;
+    });
 }
 
 int tq_format_tsv(const uint32_t *quartets, const uint32_t *rstat, const double *rscor, int64_t Q, char *out,
@@ -3874,9 +3866,10 @@ int tq_unrank(const uint64_t *ranks, uint64_t first_rank, int64_t Q, int64_t T, 
 int tq_qmc_tree(const uint32_t *splits, const double *weights, int64_t n, int64_t ntaxa, uint64_t seed, char *out,
                 int64_t cap, int64_t *written)
 {
-    if (n < 0 || cap < 0 || !written || ntaxa < 1 || ntaxa > (1 << 24) || (n > 0 && !splits) || (cap > 0 && !out))
-        return TQ_ERR_INVALID_ARG;
-    try {
+    return api(nullptr, "tq_qmc_tree", [&]() -> int {
+        if (n < 0 || cap < 0 || !written || ntaxa < 1 || ntaxa > (1 << 24) || (n > 0 && !splits) || (cap > 0 && !out))
+            return TQ_ERR_INVALID_ARG;
+        *written = 0;                   // what a failure leaves
         std::string nwk;
         const int rc = qmc_tree(splits, weights, n, ntaxa, seed, nwk);
         if (rc) return rc;
@@ -3884,10 +3877,7 @@ int tq_qmc_tree(const uint32_t *splits, const double *weights, int64_t n, int64_
         if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
         memcpy(out, nwk.data(), nwk.size());
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        *written = 0;
-        return TQ_ERR_OOM;
-    }
+    });
 }
 
 int tq_conc_create(tq_conc **out, const int32_t *parent, int64_t n_nodes, int64_t T, int64_t min_snps, double min_ratio,
@@ -3895,24 +3885,17 @@ int tq_conc_create(tq_conc **out, const int32_t *parent, int64_t n_nodes, int64_
 {
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: out is NULL");
     *out = nullptr;
-    if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: parent is NULL");
-    if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: min_ratio is NaN");
-    tq_conc *acc = new (std::nothrow) tq_conc();
-    if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
-    acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);   // deviation 2
-    acc->min_ratio = min_ratio;
-    int rc = tree_acc_init(acc, "tq_conc_create", parent, n_nodes, T, CONC_EDGE_WORDS, 2 * T + 1, ctx);
-    try {
-        if (!rc) acc->hf.assign(acc->words, 0.0);
-    } catch (const std::bad_alloc &) {
-        rc = fail(ctx, TQ_ERR_OOM, "tq_conc_create: out of host memory");
-    }
-    if (rc) {
-        delete acc;
-        return rc;
-    }
-    *out = acc;
-    return TQ_OK;
+    return api(ctx, "tq_conc_create", [&]() -> int {
+        if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: parent is NULL");
+        if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_create: min_ratio is NaN");
+        std::unique_ptr<tq_conc> acc(new tq_conc());
+        acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);   // deviation 2
+        acc->min_ratio = min_ratio;
+        if (int rc = tree_acc_init(acc.get(), "tq_conc_create", parent, n_nodes, T, CONC_EDGE_WORDS, 2 * T + 1, ctx)) return rc;
+        acc->hf.assign(acc->words, 0.0);
+        *out = acc.release();
+        return TQ_OK;
+    });
 }
 
 void tq_conc_destroy(tq_conc *acc) { delete acc; }
@@ -3920,18 +3903,22 @@ void tq_conc_destroy(tq_conc *acc) { delete acc; }
 int tq_conc_reset(tq_conc *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    std::fill(acc->hf.begin(), acc->hf.end(), 0.0);
-    return tree_acc_reset(acc);
+    return api(acc->ctx, "tq_conc_reset", [&]() -> int {
+        std::fill(acc->hf.begin(), acc->hf.end(), 0.0);
+        return tree_acc_reset(acc);
+    });
 }
 
 int tq_conc_add(tq_conc *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
                 int64_t n)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!quartets || !rstat || !rscor)))
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_conc_add: NULL pointer or negative n");
-    conc_add_host(acc->t, acc->min_snps, acc->min_ratio, quartets, rstat, rscor, flags, n, acc->hi, acc->hf);
-    return TQ_OK;
+    return api(acc->ctx, "tq_conc_add", [&]() -> int {
+        if (n < 0 || (n > 0 && (!quartets || !rstat || !rscor)))
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_conc_add: NULL pointer or negative n");
+        conc_add_host(acc->t, acc->min_snps, acc->min_ratio, quartets, rstat, rscor, flags, n, acc->hi, acc->hf);
+        return TQ_OK;
+    });
 }
 
 int tq_conc_add_dev(tq_conc *acc, const uint32_t *d_quartets, const uint32_t *d_rstat, const double *d_rscor,
@@ -3939,23 +3926,25 @@ int tq_conc_add_dev(tq_conc *acc, const uint32_t *d_quartets, const uint32_t *d_
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: the accumulator was created without a context");
-    if (n < 0 || (n > 0 && (!d_quartets || !d_rstat || !d_rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: NULL pointer or negative n");
-    if (n == 0) return TQ_OK;
-    hipStream_t st = (hipStream_t)stream;
-    return tree_acc_add_dev(acc, "tq_conc_add_dev", n, acc->t.E, st,
-                            [=](int form, int G, int64_t r0, int64_t m, int32_t e_lo, int32_t e_n, int first) {
-        const ConcTree &t = acc->t;
-        const ConcArgs a{d_quartets + 4 * r0, d_rstat + 2 * r0, d_rscor + 3 * r0, d_flags ? d_flags + r0 : nullptr, m,
-                         acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, acc->min_snps, acc->min_ratio, e_lo, e_n, first,
-                         acc->d_slab, acc->words};
-        if (form == 0)
-            hipLaunchKernelGGL((tq_conc_kernel<true, CONC_T_LDS_A, CONC_T_LDS_A>), dim3(G), dim3(CONC_THREADS), 0, st, a);
-        else if (form == 1)
-            hipLaunchKernelGGL((tq_conc_kernel<true, CONC_T_LDS_B, CONC_T_LDS_B>), dim3(G), dim3(CONC_THREADS), 0, st, a);
-        else
-            hipLaunchKernelGGL((tq_conc_kernel<false, CONC_T_MAX, CONC_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+    return api(ctx, "tq_conc_add_dev", [&]() -> int {
+        if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: the accumulator was created without a context");
+        if (n < 0 || (n > 0 && (!d_quartets || !d_rstat || !d_rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_conc_add_dev: NULL pointer or negative n");
+        if (n == 0) return TQ_OK;
+        hipStream_t st = (hipStream_t)stream;
+        return tree_acc_add_dev(acc, "tq_conc_add_dev", n, acc->t.E, st,
+                                [=](int form, int G, int64_t r0, int64_t m, int32_t e_lo, int32_t e_n, int first) {
+            const ConcTree &t = acc->t;
+            const ConcArgs a{d_quartets + 4 * r0, d_rstat + 2 * r0, d_rscor + 3 * r0, d_flags ? d_flags + r0 : nullptr, m,
+                             acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, acc->min_snps, acc->min_ratio, e_lo, e_n, first,
+                             acc->d_slab, acc->words};
+            if (form == 0)
+                hipLaunchKernelGGL((tq_conc_kernel<true, CONC_T_LDS_A, CONC_T_LDS_A>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+            else if (form == 1)
+                hipLaunchKernelGGL((tq_conc_kernel<true, CONC_T_LDS_B, CONC_T_LDS_B>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+            else
+                hipLaunchKernelGGL((tq_conc_kernel<false, CONC_T_MAX, CONC_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+        });
     });
 }
 
@@ -3968,82 +3957,90 @@ int tq_conc_read(tq_conc *acc, int64_t *edge_counts, double *edge_sums, uint64_t
                  int64_t *skipped)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    const ConcTree &t = acc->t;
-    std::vector<uint64_t> dv;
-    if (int rc = tree_acc_read(acc, "tq_conc_read", dv)) return rc;
-    for (int32_t e = 0; e < t.E; ++e) {
-        const uint64_t *d = &dv[(size_t)e * CONC_EDGE_WORDS];
-        const uint64_t *h = &acc->hi[(size_t)e * CONC_EDGE_WORDS];
-        if (edge_counts) {
-            int64_t *o = edge_counts + 6 * (int64_t)e;
-            o[0] = (int64_t)t.nqrts[e];
-            for (int k = 0; k < 5; ++k) o[1 + k] = (int64_t)(d[k] + h[k]);
-        }
-        if (edge_sums)
-            for (int k = 0; k < 2; ++k) {
-                double dvf;
-                memcpy(&dvf, &d[CW_WEIGHT + k], 8);
-                edge_sums[2 * (int64_t)e + k] = dvf + acc->hf[(size_t)e * CONC_EDGE_WORDS + CW_WEIGHT + k];
+    return api(acc->ctx, "tq_conc_read", [&]() -> int {
+        const ConcTree &t = acc->t;
+        std::vector<uint64_t> dv;
+        if (int rc = tree_acc_read(acc, "tq_conc_read", dv)) return rc;
+        for (int32_t e = 0; e < t.E; ++e) {
+            const uint64_t *d = &dv[(size_t)e * CONC_EDGE_WORDS];
+            const uint64_t *h = &acc->hi[(size_t)e * CONC_EDGE_WORDS];
+            if (edge_counts) {
+                int64_t *o = edge_counts + 6 * (int64_t)e;
+                o[0] = (int64_t)t.nqrts[e];
+                for (int k = 0; k < 5; ++k) o[1 + k] = (int64_t)(d[k] + h[k]);
             }
-    }
-    if (masks) memcpy(masks, t.masks.data(), t.masks.size() * 8);
-    const int64_t tb = (int64_t)t.E * CONC_EDGE_WORDS;
-    if (tip_counts)
-        for (int64_t i = 0; i < 2 * (int64_t)t.T; ++i) tip_counts[i] = (int64_t)(dv[tb + i] + acc->hi[tb + i]);
-    if (skipped) *skipped = (int64_t)(dv[tb + 2 * t.T] + acc->hi[tb + 2 * t.T]);
-    return TQ_OK;
+            if (edge_sums)
+                for (int k = 0; k < 2; ++k) {
+                    double dvf;
+                    memcpy(&dvf, &d[CW_WEIGHT + k], 8);
+                    edge_sums[2 * (int64_t)e + k] = dvf + acc->hf[(size_t)e * CONC_EDGE_WORDS + CW_WEIGHT + k];
+                }
+        }
+        if (masks) memcpy(masks, t.masks.data(), t.masks.size() * 8);
+        const int64_t tb = (int64_t)t.E * CONC_EDGE_WORDS;
+        if (tip_counts)
+            for (int64_t i = 0; i < 2 * (int64_t)t.T; ++i) tip_counts[i] = (int64_t)(dv[tb + i] + acc->hi[tb + i]);
+        if (skipped) *skipped = (int64_t)(dv[tb + 2 * t.T] + acc->hi[tb + 2 * t.T]);
+        return TQ_OK;
+    });
 }
 
 int tq_scf_create(tq_scf **out, const int32_t *parent, int64_t n_nodes, int64_t T, tq_ctx *ctx)
 {
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: out is NULL");
     *out = nullptr;
-    if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: parent is NULL");
-    tq_scf *acc = new (std::nothrow) tq_scf();
-    if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
-    if (int rc = tree_acc_init(acc, "tq_scf_create", parent, n_nodes, T, SCF_EDGE_WORDS, 1, ctx)) {
-        delete acc;
-        return rc;
-    }
-    *out = acc;
-    return TQ_OK;
+    return api(ctx, "tq_scf_create", [&]() -> int {
+        if (!parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_create: parent is NULL");
+        std::unique_ptr<tq_scf> acc(new tq_scf());
+        if (int rc = tree_acc_init(acc.get(), "tq_scf_create", parent, n_nodes, T, SCF_EDGE_WORDS, 1, ctx)) return rc;
+        *out = acc.release();
+        return TQ_OK;
+    });
 }
 
 void tq_scf_destroy(tq_scf *acc) { delete acc; }
 
-int tq_scf_reset(tq_scf *acc) { return acc ? tree_acc_reset(acc) : TQ_ERR_INVALID_ARG; }
+int tq_scf_reset(tq_scf *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return api(acc->ctx, "tq_scf_reset", [&]() -> int { return tree_acc_reset(acc); });
+}
 
 int tq_scf_add(tq_scf *acc, const uint32_t *sets, const uint32_t *classes, int64_t n)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!sets || !classes)))
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_scf_add: NULL pointer or negative n");
-    scf_add_host(acc->t, sets, classes, n, acc->hi);
-    return TQ_OK;
+    return api(acc->ctx, "tq_scf_add", [&]() -> int {
+        if (n < 0 || (n > 0 && (!sets || !classes)))
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_scf_add: NULL pointer or negative n");
+        scf_add_host(acc->t, sets, classes, n, acc->hi);
+        return TQ_OK;
+    });
 }
 
 int tq_scf_add_dev(tq_scf *acc, const uint32_t *d_sets, const uint32_t *d_classes, int64_t n, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: the accumulator was created without a context");
-    if (n < 0 || (n > 0 && (!d_sets || !d_classes)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: NULL pointer or negative n");
-    if (n == 0) return TQ_OK;
-    if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // sets are read as 16-byte words
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: d_sets and d_classes must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    return tree_acc_add_dev(acc, "tq_scf_add_dev", n, 0, st,
-                            [=](int form, int G, int64_t r0, int64_t m, int32_t e_lo, int32_t e_n, int first) {
-        const ConcTree &t = acc->t;
-        const ScfArgs a{d_sets + 4 * r0, d_classes + 16 * r0, m, acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, e_lo, e_n,
-                        first, acc->d_slab, acc->words};
-        if (form == 0)
-            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_A, SCF_T_LDS_A>), dim3(G), dim3(CONC_THREADS), 0, st, a);
-        else if (form == 1)
-            hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_B, SCF_T_LDS_B>), dim3(G), dim3(CONC_THREADS), 0, st, a);
-        else
-            hipLaunchKernelGGL((tq_scf_kernel<false, CONC_T_MAX, SCF_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+    return api(ctx, "tq_scf_add_dev", [&]() -> int {
+        if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: the accumulator was created without a context");
+        if (n < 0 || (n > 0 && (!d_sets || !d_classes)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: NULL pointer or negative n");
+        if (n == 0) return TQ_OK;
+        if ((((uintptr_t)d_sets) | ((uintptr_t)d_classes)) & 15)     // sets are read as 16-byte words
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_scf_add_dev: d_sets and d_classes must be 16-byte aligned");
+        hipStream_t st = (hipStream_t)stream;
+        return tree_acc_add_dev(acc, "tq_scf_add_dev", n, 0, st,
+                                [=](int form, int G, int64_t r0, int64_t m, int32_t e_lo, int32_t e_n, int first) {
+            const ConcTree &t = acc->t;
+            const ScfArgs a{d_sets + 4 * r0, d_classes + 16 * r0, m, acc->d_lca, acc->d_dep, acc->d_eid, t.T, t.N, t.E, e_lo, e_n,
+                            first, acc->d_slab, acc->words};
+            if (form == 0)
+                hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_A, SCF_T_LDS_A>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+            else if (form == 1)
+                hipLaunchKernelGGL((tq_scf_kernel<true, SCF_T_LDS_B, SCF_T_LDS_B>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+            else
+                hipLaunchKernelGGL((tq_scf_kernel<false, CONC_T_MAX, SCF_EDGE_TILE>), dim3(G), dim3(CONC_THREADS), 0, st, a);
+        });
     });
 }
 
@@ -4055,73 +4052,72 @@ int tq_scf_shape(const tq_scf *acc, int64_t *T, int64_t *n_edges, int64_t *mask_
 int tq_scf_read(tq_scf *acc, int64_t *edge_counts, uint64_t *masks, int64_t *skipped)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    const ConcTree &t = acc->t;
-    std::vector<uint64_t> dv;
-    if (int rc = tree_acc_read(acc, "tq_scf_read", dv)) return rc;
-    const int64_t eb = (int64_t)t.E * SCF_EDGE_WORDS;
-    if (edge_counts)
-        for (int64_t i = 0; i < eb; ++i) edge_counts[i] = (int64_t)(dv[i] + acc->hi[i]);
-    if (masks) memcpy(masks, t.masks.data(), t.masks.size() * 8);
-    if (skipped) *skipped = (int64_t)(dv[eb] + acc->hi[eb]);
-    return TQ_OK;
+    return api(acc->ctx, "tq_scf_read", [&]() -> int {
+        const ConcTree &t = acc->t;
+        std::vector<uint64_t> dv;
+        if (int rc = tree_acc_read(acc, "tq_scf_read", dv)) return rc;
+        const int64_t eb = (int64_t)t.E * SCF_EDGE_WORDS;
+        if (edge_counts)
+            for (int64_t i = 0; i < eb; ++i) edge_counts[i] = (int64_t)(dv[i] + acc->hi[i]);
+        if (masks) memcpy(masks, t.masks.data(), t.masks.size() * 8);
+        if (skipped) *skipped = (int64_t)(dv[eb] + acc->hi[eb]);
+        return TQ_OK;
+    });
 }
 
 int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int weights, int64_t min_snps, double min_ratio,
                     tq_ctx *ctx)
 {
+    const char *who = "tq_stree_create";
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: out is NULL");
     *out = nullptr;
-    if (ntaxa < 1 || ntaxa > 65535) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: ntaxa must be 1..65535");
-    if (ctx && (ntaxa < 4 || ntaxa > STREE_T_MAX))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: the device path takes 4 <= ntaxa <= %d", STREE_T_MAX);
-    if (capacity_rows < 0 || capacity_rows >= (int64_t(1) << 31))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: capacity_rows must be 0..2^31-1");
-    if (weights < 0 || weights > 3) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: no weight strategy %d", weights);
-    if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: min_ratio is NaN");
-    tq_stree *acc = new (std::nothrow) tq_stree();
-    if (!acc) return fail(ctx, TQ_ERR_OOM, "out of host memory");
-    acc->ctx = ctx;
-    acc->ntaxa = ntaxa;
-    acc->capacity = capacity_rows;
-    acc->weights = weights;
-    acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);
-    acc->min_ratio = min_ratio;
-    if (ctx) {
-        acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
-        acc->max_nodes = 3 * ntaxa;                                  // the taxa of a level number fewer than 3 ntaxa
-        acc->max_cells = 3 * ntaxa * ntaxa / 2 + 16;                 // sum of n (n - 1) / 2 with n <= ntaxa, sum of n < 3 ntaxa
-        const size_t rows = (size_t)std::max<int64_t>(1, capacity_rows);
-        hipError_t e = hipSetDevice(ctx->device);
-        const size_t cells = (size_t)acc->max_cells, nodes = (size_t)acc->max_nodes;
-        if (e == hipSuccess) e = acc->d_root_t.alloc(rows);
-        if (e == hipSuccess) e = acc->d_root_k.alloc(rows);
-        for (int b = 0; b < 2; ++b) {
-            if (e == hipSuccess) e = acc->d_wt[b].alloc(rows);
-            if (e == hipSuccess) e = acc->d_wk[b].alloc(rows);
-            if (e == hipSuccess) e = acc->d_wn[b].alloc(rows);
+    return api(ctx, who, [&]() -> int {
+        if (ntaxa < 1 || ntaxa > 65535) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: ntaxa must be 1..65535");
+        if (ctx && (ntaxa < 4 || ntaxa > STREE_T_MAX))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: the device path takes 4 <= ntaxa <= %d", STREE_T_MAX);
+        if (capacity_rows < 0 || capacity_rows >= (int64_t(1) << 31))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: capacity_rows must be 0..2^31-1");
+        if (weights < 0 || weights > 3) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: no weight strategy %d", weights);
+        if (std::isnan(min_ratio)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_create: min_ratio is NaN");
+        std::unique_ptr<tq_stree> acc(new tq_stree());
+        acc->ctx = ctx;
+        acc->ntaxa = ntaxa;
+        acc->capacity = capacity_rows;
+        acc->weights = weights;
+        acc->min_snps = (uint32_t)std::min<int64_t>(std::max<int64_t>(1, min_snps), 0xFFFFFFFFll);
+        acc->min_ratio = min_ratio;
+        if (ctx) {
+            acc->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+            acc->max_nodes = 3 * ntaxa;                                  // the taxa of a level number fewer than 3 ntaxa
+            acc->max_cells = 3 * ntaxa * ntaxa / 2 + 16;                 // sum of n (n - 1) / 2 with n <= ntaxa, sum of n < 3 ntaxa
+            const size_t rows = (size_t)std::max<int64_t>(1, capacity_rows);
+            const size_t cells = (size_t)acc->max_cells, nodes = (size_t)acc->max_nodes;
+            TQ_HIPF(ctx, who, acc->d_root_t.alloc(rows));
+            TQ_HIPF(ctx, who, acc->d_root_k.alloc(rows));
+            for (int b = 0; b < 2; ++b) {
+                TQ_HIPF(ctx, who, acc->d_wt[b].alloc(rows));
+                TQ_HIPF(ctx, who, acc->d_wk[b].alloc(rows));
+                TQ_HIPF(ctx, who, acc->d_wn[b].alloc(rows));
+            }
+            TQ_HIPF(ctx, who, acc->d_cnt.alloc(SC_WORDS));
+            TQ_HIPF(ctx, who, acc->d_mat.alloc(cells * 2));
+            TQ_HIPF(ctx, who, acc->d_nodes.alloc(nodes));
+            TQ_HIPF(ctx, who, acc->d_map.alloc(nodes * 3));
+            TQ_HIPF(ctx, who, acc->p_mat.alloc(cells * 2));
+            TQ_HIPF(ctx, who, acc->p_nodes.alloc(nodes));
+            TQ_HIPF(ctx, who, acc->p_map.alloc(nodes * 3));
+            TQ_HIPF(ctx, who, acc->p_cnt.alloc(SC_WORDS));
+            TQ_HIPF(ctx, who, acc->d_side.alloc(nodes * 3));
+            TQ_HIPF(ctx, who, acc->d_cut.alloc(nodes));
+            TQ_HIPF(ctx, who, acc->p_side.alloc(nodes * 3));
+            TQ_HIPF(ctx, who, acc->p_cut.alloc(nodes));
+            TQ_HIPF(ctx, who, hipMemset(acc->d_cnt, 0, SC_WORDS * 8));
+            TQ_HIPF(ctx, who, acc->order.create());
+            TQ_HIPF(ctx, who, hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking));
         }
-        if (e == hipSuccess) e = acc->d_cnt.alloc(SC_WORDS);
-        if (e == hipSuccess) e = acc->d_mat.alloc(cells * 2);
-        if (e == hipSuccess) e = acc->d_nodes.alloc(nodes);
-        if (e == hipSuccess) e = acc->d_map.alloc(nodes * 3);
-        if (e == hipSuccess) e = acc->p_mat.alloc(cells * 2);
-        if (e == hipSuccess) e = acc->p_nodes.alloc(nodes);
-        if (e == hipSuccess) e = acc->p_map.alloc(nodes * 3);
-        if (e == hipSuccess) e = acc->p_cnt.alloc(SC_WORDS);
-        if (e == hipSuccess) e = acc->d_side.alloc(nodes * 3);
-        if (e == hipSuccess) e = acc->d_cut.alloc(nodes);
-        if (e == hipSuccess) e = acc->p_side.alloc(nodes * 3);
-        if (e == hipSuccess) e = acc->p_cut.alloc(nodes);
-        if (e == hipSuccess) e = hipMemset(acc->d_cnt, 0, SC_WORDS * 8);
-        if (e == hipSuccess) e = acc->order.create();
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete acc;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_stree_create: %s", hipGetErrorString(e));
-        }
-    }
-    *out = acc;
-    return TQ_OK;
+        *out = acc.release();
+        return TQ_OK;
+    });
 }
 
 void tq_stree_destroy(tq_stree *acc) { delete acc; }
@@ -4129,54 +4125,53 @@ void tq_stree_destroy(tq_stree *acc) { delete acc; }
 int tq_stree_reset(tq_stree *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    acc->h_t.clear();
-    acc->h_k.clear();
-    acc->h_skipped = 0;
-    acc->h_sum = 0;
-    acc->rows_in = 0;
-    acc->mode = 0;
-    if (acc->ctx) {
-        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        TQ_HIP(acc->ctx, acc->order.sync());
-        TQ_HIP(acc->ctx, hipMemsetAsync(acc->d_cnt, 0, SC_WORDS * 8, acc->own));   // not the null stream: it would wait
-        TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));                           // for every other stream's work
-    }
-    return TQ_OK;
+    return api(acc->ctx, "tq_stree_reset", [&]() -> int {
+        acc->h_t.clear();
+        acc->h_k.clear();
+        acc->h_skipped = 0;
+        acc->h_sum = 0;
+        acc->rows_in = 0;
+        acc->mode = 0;
+        if (acc->ctx) {
+            TQ_HIP(acc->ctx, acc->order.sync());
+            TQ_HIP(acc->ctx, hipMemsetAsync(acc->d_cnt, 0, SC_WORDS * 8, acc->own));   // not the null stream: it would wait
+            TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));                           // for every other stream's work
+        }
+        return TQ_OK;
+    });
 }
 
 int tq_stree_add(tq_stree *acc, const uint32_t *quartets, const uint32_t *rstat, const double *rscor, const uint8_t *flags,
                  int64_t n)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!quartets || !rstat || !rscor)))
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: NULL pointer or negative n");
-    if (acc->mode == 2) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: device rows were added; host rows do not mix");
-    if (acc->rows_in + n > acc->capacity)
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: %lld rows added, %lld more exceed the capacity of %lld",
-                    (long long)acc->rows_in, (long long)n, (long long)acc->capacity);
-    if (n == 0) return TQ_OK;
-    try {
+    return api(acc->ctx, "tq_stree_add", [&]() -> int {
+        if (n < 0 || (n > 0 && (!quartets || !rstat || !rscor)))
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: NULL pointer or negative n");
+        if (acc->mode == 2) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: device rows were added; host rows do not mix");
+        if (acc->rows_in + n > acc->capacity)
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_add: %lld rows added, %lld more exceed the capacity of %lld",
+                        (long long)acc->rows_in, (long long)n, (long long)acc->capacity);
+        if (n == 0) return TQ_OK;
         acc->h_t.reserve(acc->h_t.size() + (size_t)n);
         acc->h_k.reserve(acc->h_k.size() + (size_t)n);
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_add: out of host memory");
-    }
-    acc->mode = 1;
-    acc->rows_in += n;
-    for (int64_t i = 0; i < n; ++i) {
-        const uint32_t *q = quartets + 4 * i;
-        uint32_t sp[4];
-        uint64_t k;
-        if (!stree_row((uint32_t)acc->ntaxa, acc->weights, acc->min_snps, acc->min_ratio, q[0], q[1], q[2], q[3], rstat[2 * i],
-                       rstat[2 * i + 1], rscor[3 * i], rscor[3 * i + 1], rscor[3 * i + 2], flags ? flags[i] : 0u, sp, k)) {
-            ++acc->h_skipped;
-            continue;
+        acc->mode = 1;
+        acc->rows_in += n;
+        for (int64_t i = 0; i < n; ++i) {
+            const uint32_t *q = quartets + 4 * i;
+            uint32_t sp[4];
+            uint64_t k;
+            if (!stree_row((uint32_t)acc->ntaxa, acc->weights, acc->min_snps, acc->min_ratio, q[0], q[1], q[2], q[3], rstat[2 * i],
+                           rstat[2 * i + 1], rscor[3 * i], rscor[3 * i + 1], rscor[3 * i + 2], flags ? flags[i] : 0u, sp, k)) {
+                ++acc->h_skipped;
+                continue;
+            }
+            acc->h_t.push_back((uint64_t)sp[0] | (uint64_t)sp[1] << 16 | (uint64_t)sp[2] << 32 | (uint64_t)sp[3] << 48);
+            acc->h_k.push_back(k);
+            acc->h_sum += k;
         }
-        acc->h_t.push_back((uint64_t)sp[0] | (uint64_t)sp[1] << 16 | (uint64_t)sp[2] << 32 | (uint64_t)sp[3] << 48);
-        acc->h_k.push_back(k);
-        acc->h_sum += k;
-    }
-    return TQ_OK;
+        return TQ_OK;
+    });
 }
 
 int tq_stree_add_dev(tq_stree *acc, const uint32_t *d_quartets, const uint32_t *d_rstat, const double *d_rscor,
@@ -4184,44 +4179,45 @@ int tq_stree_add_dev(tq_stree *acc, const uint32_t *d_quartets, const uint32_t *
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: the accumulator was created without a context");
-    if (n < 0 || (n > 0 && (!d_quartets || !d_rstat || !d_rscor)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: NULL pointer or negative n");
-    if (acc->mode == 1) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: host rows were added; device rows do not mix");
-    if (acc->rows_in + n > acc->capacity)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: %lld rows added, %lld more exceed the capacity of %lld",
-                    (long long)acc->rows_in, (long long)n, (long long)acc->capacity);
-    if (n == 0) return TQ_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = stree_join(acc, st)) return rc;                    // appends in call order
-    StreeAddArgs a{d_quartets, d_rstat, d_rscor, d_flags, n, (uint32_t)acc->ntaxa, acc->min_snps, acc->weights,
-                   acc->min_ratio, acc->d_root_t, acc->d_root_k, acc->capacity, acc->d_cnt};
-    hipLaunchKernelGGL(tq_stree_rows_kernel, dim3((unsigned)((n + STREE_THREADS - 1) / STREE_THREADS)), dim3(STREE_THREADS), 0,
-                       st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_stree_add_dev: launch failed: %s", hipGetErrorString(e));
-    TQ_HIP(ctx, acc->order.mark(st));
-    acc->mode = 2;
-    acc->rows_in += n;
-    return TQ_OK;
+    return api(ctx, "tq_stree_add_dev", [&]() -> int {
+        if (!ctx) return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: the accumulator was created without a context");
+        if (n < 0 || (n > 0 && (!d_quartets || !d_rstat || !d_rscor)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: NULL pointer or negative n");
+        if (acc->mode == 1) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: host rows were added; device rows do not mix");
+        if (acc->rows_in + n > acc->capacity)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_add_dev: %lld rows added, %lld more exceed the capacity of %lld",
+                        (long long)acc->rows_in, (long long)n, (long long)acc->capacity);
+        if (n == 0) return TQ_OK;
+        hipStream_t st = (hipStream_t)stream;
+        if (int rc = stree_join(acc, st)) return rc;                    // appends in call order
+        StreeAddArgs a{d_quartets, d_rstat, d_rscor, d_flags, n, (uint32_t)acc->ntaxa, acc->min_snps, acc->weights,
+                       acc->min_ratio, acc->d_root_t, acc->d_root_k, acc->capacity, acc->d_cnt};
+        hipLaunchKernelGGL(tq_stree_rows_kernel, dim3((unsigned)((n + STREE_THREADS - 1) / STREE_THREADS)), dim3(STREE_THREADS), 0,
+                           st, a);
+        TQ_LAUNCHED(ctx, "tq_stree_add_dev");
+        TQ_HIP(ctx, acc->order.mark(st));
+        acc->mode = 2;
+        acc->rows_in += n;
+        return TQ_OK;
+    });
 }
 
 int tq_stree_graph(tq_stree *acc, uint64_t *G, uint64_t *B, int64_t *kept, int64_t *skipped, uint64_t *sum_k)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    int64_t nk = 0, ns = 0;
-    unsigned __int128 sum = 0;
-    if (int rc = stree_counts(acc, acc->own, nk, ns, sum)) return rc;
-    if (kept) *kept = nk;
-    if (skipped) *skipped = ns;
-    if (sum_k) *sum_k = (sum >> 64) ? ~0ull : (uint64_t)sum;
-    if (!G && !B) return TQ_OK;
-    if (sum >> 63) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_graph: the sum of k exceeds 2^63, a cell could wrap");
-    const int64_t T = acc->ntaxa;
-    if (G) memset(G, 0, (size_t)T * T * 8);
-    if (B) memset(B, 0, (size_t)T * T * 8);
-    if (T < 4 || nk == 0) return TQ_OK;
-    try {
+    return api(acc->ctx, "tq_stree_graph", [&]() -> int {
+        int64_t nk = 0, ns = 0;
+        unsigned __int128 sum = 0;
+        if (int rc = stree_counts(acc, acc->own, nk, ns, sum)) return rc;
+        if (kept) *kept = nk;
+        if (skipped) *skipped = ns;
+        if (sum_k) *sum_k = (sum >> 64) ? ~0ull : (uint64_t)sum;
+        if (!G && !B) return TQ_OK;
+        if (sum >> 63) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_graph: the sum of k exceeds 2^63, a cell could wrap");
+        const int64_t T = acc->ntaxa;
+        if (G) memset(G, 0, (size_t)T * T * 8);
+        if (B) memset(B, 0, (size_t)T * T * 8);
+        if (T < 4 || nk == 0) return TQ_OK;
         std::vector<StreeNode> nodes(1);
         nodes[0].n = (int32_t)T;
         nodes[0].childA = nodes[0].childB = -1;
@@ -4250,56 +4246,52 @@ int tq_stree_graph(tq_stree *acc, uint64_t *G, uint64_t *B, int64_t *kept, int64
                 if (G) G[u * T + v] = G[v * T + u] = mat[c];
                 if (B) B[u * T + v] = B[v * T + u] = mat[cells + c];
             }
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_graph: out of host memory");
-    }
-    return TQ_OK;
+        return TQ_OK;
+    });
 }
 
 int tq_stree_rows(tq_stree *acc, uint32_t *splits, uint64_t *k, int64_t *n)
 {
     if (!acc || !n) return TQ_ERR_INVALID_ARG;
-    int64_t nk = 0, ns = 0;
-    unsigned __int128 sum = 0;
-    if (int rc = stree_counts(acc, acc->own, nk, ns, sum)) return rc;
-    *n = nk;
-    if (nk == 0 || (!splits && !k)) return TQ_OK;
-    const uint64_t *t4 = acc->h_t.data(), *kk = acc->h_k.data();
-    std::vector<uint64_t> tmp;
-    if (acc->mode == 2) {
-        try {
+    return api(acc->ctx, "tq_stree_rows", [&]() -> int {
+        int64_t nk = 0, ns = 0;
+        unsigned __int128 sum = 0;
+        if (int rc = stree_counts(acc, acc->own, nk, ns, sum)) return rc;
+        *n = nk;
+        if (nk == 0 || (!splits && !k)) return TQ_OK;
+        const uint64_t *t4 = acc->h_t.data(), *kk = acc->h_k.data();
+        std::vector<uint64_t> tmp;
+        if (acc->mode == 2) {
             tmp.resize((size_t)nk * 2);
-        } catch (const std::bad_alloc &) {
-            return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_rows: out of host memory");
+            TQ_HIP(acc->ctx, hipMemcpyAsync(tmp.data(), acc->d_root_t, (size_t)nk * 8, hipMemcpyDeviceToHost, acc->own));
+            TQ_HIP(acc->ctx, hipMemcpyAsync(tmp.data() + nk, acc->d_root_k, (size_t)nk * 8, hipMemcpyDeviceToHost, acc->own));
+            TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));
+            t4 = tmp.data();
+            kk = tmp.data() + nk;
         }
-        TQ_HIP(acc->ctx, hipMemcpyAsync(tmp.data(), acc->d_root_t, (size_t)nk * 8, hipMemcpyDeviceToHost, acc->own));
-        TQ_HIP(acc->ctx, hipMemcpyAsync(tmp.data() + nk, acc->d_root_k, (size_t)nk * 8, hipMemcpyDeviceToHost, acc->own));
-        TQ_HIP(acc->ctx, hipStreamSynchronize(acc->own));
-        t4 = tmp.data();
-        kk = tmp.data() + nk;
-    }
-    for (int64_t i = 0; i < nk; ++i) {
-        if (splits)
-            for (int j = 0; j < 4; ++j) splits[4 * i + j] = (uint32_t)((t4[i] >> (16 * j)) & 0xFFFF);
-        if (k) k[i] = kk[i];
-    }
-    return TQ_OK;
+        for (int64_t i = 0; i < nk; ++i) {
+            if (splits)
+                for (int j = 0; j < 4; ++j) splits[4 * i + j] = (uint32_t)((t4[i] >> (16 * j)) & 0xFFFF);
+            if (k) k[i] = kk[i];
+        }
+        return TQ_OK;
+    });
 }
 
 int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_t cap, int64_t *written, int64_t *levels)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (cap < 0 || !written || (cap > 0 && !out))
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_build: NULL pointer or negative cap");
-    *written = 0;
-    int64_t nk = 0, ns = 0;
-    unsigned __int128 sum = 0;
-    if (int rc = stree_counts(acc, (hipStream_t)stream, nk, ns, sum)) return rc;
-    if (sum >= STREE_SUM_LIMIT)
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG,
-                    "tq_stree_build: 6 x the sum of the integer weights reaches 2^53 (sum of k >= %llu): the graph would "
-                    "not be exact in doubles", (unsigned long long)STREE_SUM_LIMIT);
-    try {
+    return api(acc->ctx, "tq_stree_build", [&]() -> int {
+        if (cap < 0 || !written || (cap > 0 && !out))
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_stree_build: NULL pointer or negative cap");
+        *written = 0;
+        int64_t nk = 0, ns = 0;
+        unsigned __int128 sum = 0;
+        if (int rc = stree_counts(acc, (hipStream_t)stream, nk, ns, sum)) return rc;
+        if (sum >= STREE_SUM_LIMIT)
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG,
+                        "tq_stree_build: 6 x the sum of the integer weights reaches 2^53 (sum of k >= %llu): the graph would "
+                        "not be exact in doubles", (unsigned long long)STREE_SUM_LIMIT);
         std::string nwk, err;
         int64_t lv = 0;
         int rc;
@@ -4322,9 +4314,7 @@ int tq_stree_build(tq_stree *acc, uint64_t seed, void *stream, char *out, int64_
         if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
         memcpy(out, nwk.data(), nwk.size());
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_stree_build: out of host memory");
-    }
+    });
 }
 
 int tq_stree_set_search(tq_stree *acc, int search)
@@ -4341,23 +4331,13 @@ int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, 
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes || !out)))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: NULL pointer or negative size");
-    if (R == 0) return TQ_OK;
-    const int64_t T = acc->ntaxa;
-    try {
-        std::vector<std::vector<int32_t>> pars((size_t)R);          // every tree is validated before anything is written
-        std::vector<std::vector<int32_t>> nch;
-        for (int64_t r = 0; r < R; ++r) {
-            if (n_nodes[r] > stride)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: tree %lld: n_nodes exceeds the stride", (long long)r);
-            const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
-            if (!err.empty())
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: tree %lld: %s", (long long)r, err.c_str());
-            if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: tree %lld: internal error: a prepared tree of T taxa has "
-                            "at most 2 T - 2 nodes", (long long)r);
-        }
+    return api(ctx, "tq_stree_fit", [&]() -> int {
+        if (R < 0 || stride < 0 || (R > 0 && (!parents || !n_nodes || !out)))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_fit: NULL pointer or negative size");
+        if (R == 0) return TQ_OK;
+        const int64_t T = acc->ntaxa;
+        std::vector<std::vector<int32_t>> pars;
+        if (int rc = prepare_fit_trees(ctx, "tq_stree_fit", parents, n_nodes, R, stride, T, pars)) return rc;
         const char *wide = "tq_stree_fit: the sum of k does not fit in 64 bits";
         if (acc->mode != 2) {                                       // host rows, or none yet
             if (acc->h_sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s", wide);
@@ -4375,7 +4355,7 @@ int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, 
         hipStream_t st = (hipStream_t)stream;
         if (int rc = stree_join(acc, st)) return rc;                // behind the adds made on other streams
         const int64_t S = 2 * T;
-        if (!acc->fit_bytes) acc->fit_bytes = ctx->fit_scratch_bytes;
+        if (!acc->fit_bytes) acc->fit_bytes = ctx->opt.fit_scratch_bytes;
         const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(acc->fit_bytes / (2 * T * T), FIT_MAX_CHUNK_TREES));
         const int64_t tab_trees = std::min(R, chunk);
         if (R > acc->fit_trees) {                                   // no fit is in flight: each one ends with a synchronisation
@@ -4388,30 +4368,23 @@ int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, 
             acc->fit_trees = R;
         }
         TQ_HIP(ctx, acc->d_fit_tab.grow((size_t)tab_trees * T * T));
-        memset(acc->p_fit_rec, 0, (size_t)R * S * 4);
-        for (int64_t r = 0; r < R; ++r) {
-            int32_t *rec = acc->p_fit_rec + r * S;
-            memcpy(rec, pars[(size_t)r].data(), pars[(size_t)r].size() * 4);
-            rec[S - 1] = (int32_t)pars[(size_t)r].size();
-        }
+        fit_stage_records(acc->p_fit_rec, pars, S);
         TQ_HIP(ctx, hipMemcpyAsync(acc->d_fit_rec, acc->p_fit_rec, (size_t)R * S * 4, hipMemcpyHostToDevice, st));
         TQ_HIP(ctx, hipMemsetAsync(acc->d_fit_out, 0, (size_t)R * FIT_WORDS * 8, st));
-        const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
-        const unsigned table_blocks = (unsigned)std::max<int64_t>(
-            1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
+        const unsigned table_blocks = fit_table_blocks(T);
         const unsigned slices = (unsigned)std::max<int64_t>(
             1, std::min<int64_t>((acc->rows_in + FIT_ROWS_PER_BLOCK - 1) / FIT_ROWS_PER_BLOCK, FIT_MAX_SLICES));
         for (int64_t r0 = 0; r0 < R; r0 += chunk) {                 // the next chunk's tables follow this chunk's fit on `st`
             const unsigned n = (unsigned)std::min<int64_t>(chunk, R - r0);
             FitTableArgs ta{acc->d_fit_rec + r0 * S, acc->d_fit_tab, (uint32_t)T};
             hipLaunchKernelGGL(tq_fit_table_kernel, dim3(table_blocks, n), dim3(FIT_THREADS), 0, st, ta);
-            TQ_HIP(ctx, hipGetLastError());
+            TQ_LAUNCHED(ctx, "tq_stree_fit");
             if (acc->rows_in == 0) continue;
             FitArgs fa{acc->d_root_t, acc->d_root_k, &acc->d_cnt[SC_KEPT], acc->d_fit_tab, acc->d_fit_out + r0 * FIT_WORDS,
                        (uint32_t)T};
             if (T <= FIT_T_LDS) hipLaunchKernelGGL(tq_fit_kernel<true>, dim3(slices, n), dim3(FIT_THREADS), 0, st, fa);
             else hipLaunchKernelGGL(tq_fit_kernel<false>, dim3(slices, n), dim3(FIT_THREADS), 0, st, fa);
-            TQ_HIP(ctx, hipGetLastError());
+            TQ_LAUNCHED(ctx, "tq_stree_fit");
         }
         unsigned long long *cnt = acc->p_fit_out + R * FIT_WORDS;
         TQ_HIP(ctx, hipMemcpyAsync(acc->p_fit_out, acc->d_fit_out, (size_t)R * FIT_WORDS * 8, hipMemcpyDeviceToHost, st));
@@ -4421,9 +4394,7 @@ int tq_stree_fit(tq_stree *acc, const int32_t *parents, const int64_t *n_nodes, 
         if (sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s", wide);
         memcpy(out, acc->p_fit_out, (size_t)R * FIT_WORDS * 8);
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_stree_fit: out of host memory");
-    }
+    });
 }
 
 int tq_stree_nni_scan(tq_stree *acc, const int32_t *parent, int64_t n_nodes, void *stream, int64_t *n_edges,
@@ -4431,8 +4402,8 @@ int tq_stree_nni_scan(tq_stree *acc, const int32_t *parent, int64_t n_nodes, voi
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (!parent || n_nodes < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_nni_scan: NULL pointer or negative size");
-    try {
+    return api(ctx, "tq_stree_nni_scan", [&]() -> int {
+        if (!parent || n_nodes < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_nni_scan: NULL pointer or negative size");
         NniTree t;
         const std::string err = nni_prepare(parent, n_nodes, acc->ntaxa, t);    // validated before anything is written
         if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_nni_scan: tree 0: %s", err.c_str());
@@ -4443,9 +4414,7 @@ int tq_stree_nni_scan(tq_stree *acc, const int32_t *parent, int64_t n_nodes, voi
         if (corners) nni_corner_masks(t, corners);
         if (w && t.E) memcpy(w, sums.data(), (size_t)t.E * 3 * 8);
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_stree_nni_scan: out of host memory");
-    }
+    });
 }
 
 int tq_stree_polish(tq_stree *acc, const int32_t *parent, int64_t n_nodes, int64_t max_rounds, void *stream, char *out,
@@ -4453,11 +4422,11 @@ int tq_stree_polish(tq_stree *acc, const int32_t *parent, int64_t n_nodes, int64
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (!parent || n_nodes < 0 || cap < 0 || !written || (cap > 0 && !out))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: NULL pointer or negative size");
-    if (max_rounds < 0 || max_rounds > NNI_MAX_ROUNDS)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: max_rounds must be 0..%lld", (long long)NNI_MAX_ROUNDS);
-    try {
+    return api(ctx, "tq_stree_polish", [&]() -> int {
+        if (!parent || n_nodes < 0 || cap < 0 || !written || (cap > 0 && !out))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: NULL pointer or negative size");
+        if (max_rounds < 0 || max_rounds > NNI_MAX_ROUNDS)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: max_rounds must be 0..%lld", (long long)NNI_MAX_ROUNDS);
         NniTree t;
         const std::string err = nni_prepare(parent, n_nodes, acc->ntaxa, t);    // validated before anything is written
         if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_polish: tree 0: %s", err.c_str());
@@ -4482,17 +4451,15 @@ int tq_stree_polish(tq_stree *acc, const int32_t *parent, int64_t n_nodes, int64
         if (rounds) *rounds = (int64_t)(tr.size() / 2);
         if (converged) *converged = conv;
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_stree_polish: out of host memory");
-    }
+    });
 }
 
 int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const uint64_t *G, const uint64_t *B,
                     const uint64_t *node_seeds, uint8_t *side, uint8_t *cut, int32_t *rounds)
 {
-    if (n_nodes < 1 || n_nodes > (int64_t(1) << 20) || !sizes || !G || !B || !node_seeds || !side || !cut)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_search: NULL pointer or n_nodes not in 1..2^20");
-    try {
+    return api(ctx, "tq_stree_search", [&]() -> int {
+        if (n_nodes < 1 || n_nodes > (int64_t(1) << 20) || !sizes || !G || !B || !node_seeds || !side || !cut)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_stree_search: NULL pointer or n_nodes not in 1..2^20");
         std::vector<StreeNode> nodes((size_t)n_nodes);
         uint64_t cells = 0, moff = 0;
         for (int64_t i = 0; i < n_nodes; ++i) {
@@ -4518,51 +4485,40 @@ int tq_stree_search(tq_ctx *ctx, int64_t n_nodes, const int32_t *sizes, const ui
             }
             return TQ_OK;
         }
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
         DevBuf<unsigned long long> d_mat;                           // locals: every exit frees them
         DevBuf<StreeNode> d_nodes;
         DevBuf<uint64_t> d_seeds;
         DevBuf<uint8_t> d_out;                                      // side bytes, cut bytes, round bytes
         std::vector<uint8_t> out((size_t)moff + 2 * (size_t)n_nodes);
-        int rc = TQ_OK;
-        auto step = [&](hipError_t e, const char *what) {
-            if (!rc && e != hipSuccess)
-                rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_stree_search: %s: %s", what,
-                          hipGetErrorString(e));
-        };
-        step(d_mat.alloc((size_t)cells * 2), "hipMalloc");
-        if (!rc) step(d_nodes.alloc((size_t)n_nodes), "hipMalloc");
-        if (!rc) step(d_seeds.alloc((size_t)n_nodes), "hipMalloc");
-        if (!rc) step(d_out.alloc(out.size()), "hipMalloc");
-        if (!rc) step(hipMemcpy(d_mat, G, (size_t)cells * 8, hipMemcpyHostToDevice), "H2D");
-        if (!rc) step(hipMemcpy(d_mat + cells, B, (size_t)cells * 8, hipMemcpyHostToDevice), "H2D");
-        if (!rc) step(hipMemcpy(d_nodes, nodes.data(), (size_t)n_nodes * sizeof(StreeNode), hipMemcpyHostToDevice), "H2D");
-        if (!rc) step(hipMemcpy(d_seeds, node_seeds, (size_t)n_nodes * 8, hipMemcpyHostToDevice), "H2D");
-        if (!rc) step(hipMemset(d_out, 0, out.size()), "hipMemset");
-        if (!rc) {
-            StreeSearchArgs p{};
-            p.nodes = d_nodes;
-            p.n_nodes = (int32_t)n_nodes;
-            p.cells = (int64_t)cells;
-            p.mat = d_mat;
-            p.seeds = d_seeds;
-            p.side = d_out;
-            p.cut = d_out + moff;
-            p.rounds = d_out + moff + n_nodes;
-            hipLaunchKernelGGL(tq_stree_search_kernel, dim3((unsigned)n_nodes), dim3(STREE_SEARCH_THREADS), 0, 0, p);
-            step(hipGetLastError(), "launch");
-        }
-        if (!rc) step(hipDeviceSynchronize(), "sync");
-        if (!rc) step(hipMemcpy(out.data(), d_out, out.size(), hipMemcpyDeviceToHost), "D2H");
-        if (rc) return rc;
+        const char *who = "tq_stree_search";
+        TQ_HIPF(ctx, who, d_mat.alloc((size_t)cells * 2));
+        TQ_HIPF(ctx, who, d_nodes.alloc((size_t)n_nodes));
+        TQ_HIPF(ctx, who, d_seeds.alloc((size_t)n_nodes));
+        TQ_HIPF(ctx, who, d_out.alloc(out.size()));
+        TQ_HIPF(ctx, who, hipMemcpy(d_mat, G, (size_t)cells * 8, hipMemcpyHostToDevice));
+        TQ_HIPF(ctx, who, hipMemcpy(d_mat + cells, B, (size_t)cells * 8, hipMemcpyHostToDevice));
+        TQ_HIPF(ctx, who, hipMemcpy(d_nodes, nodes.data(), (size_t)n_nodes * sizeof(StreeNode), hipMemcpyHostToDevice));
+        TQ_HIPF(ctx, who, hipMemcpy(d_seeds, node_seeds, (size_t)n_nodes * 8, hipMemcpyHostToDevice));
+        TQ_HIPF(ctx, who, hipMemset(d_out, 0, out.size()));
+        StreeSearchArgs p{};
+        p.nodes = d_nodes;
+        p.n_nodes = (int32_t)n_nodes;
+        p.cells = (int64_t)cells;
+        p.mat = d_mat;
+        p.seeds = d_seeds;
+        p.side = d_out;
+        p.cut = d_out + moff;
+        p.rounds = d_out + moff + n_nodes;
+        hipLaunchKernelGGL(tq_stree_search_kernel, dim3((unsigned)n_nodes), dim3(STREE_SEARCH_THREADS), 0, 0, p);
+        TQ_LAUNCHED(ctx, who);
+        TQ_HIPF(ctx, who, hipDeviceSynchronize());
+        TQ_HIPF(ctx, who, hipMemcpy(out.data(), d_out, out.size(), hipMemcpyDeviceToHost));
         memcpy(side, out.data(), (size_t)moff);
         memcpy(cut, out.data() + moff, (size_t)n_nodes);
         if (rounds)
             for (int64_t i = 0; i < n_nodes; ++i) rounds[i] = out[(size_t)moff + (size_t)n_nodes + (size_t)i];
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_stree_search: out of host memory");
-    }
+    });
 }
 
 int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out)
@@ -4581,35 +4537,29 @@ int tq_stree_level_stats(const tq_stree *acc, int64_t *n_levels, double *out)
 
 int tq_cons_create(tq_cons **out, int64_t T, int64_t max_splits, tq_ctx *ctx)
 {
+    const char *who = "tq_cons_create";
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: out is NULL");
     *out = nullptr;
-    if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: T must be 4..%d", CONS_T_MAX);
-    if (max_splits < 1 || max_splits > (int64_t(1) << 26))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: max_splits must be 1..2^26");
-    tq_cons *a = new (std::nothrow) tq_cons();
-    if (!a) return fail(ctx, TQ_ERR_OOM, "tq_cons_create: out of host memory");
-    a->ctx = ctx;
-    a->chunk.shape(T);
-    a->table.max_splits = max_splits;
-    if (ctx) {
-        const int64_t nodes = a->chunk.nodes();
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = a->chunk.alloc(ctx->cons_scratch_bytes, nodes * 4);        // the unresolved items
-        if (e == hipSuccess) e = a->table.alloc(ctx, a->chunk.W, a->chunk.chunk_trees * nodes);
-        if (e == hipSuccess) e = a->chunk.alloc_host();
-        if (e == hipSuccess) e = a->table.alloc_host();
-        if (e == hipSuccess) e = a->order.create();
-        if (e != hipSuccess) {
-            delete a;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_cons_create: %s", hipGetErrorString(e));
+    return api(ctx, who, [&]() -> int {
+        if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: T must be 4..%d", CONS_T_MAX);
+        if (max_splits < 1 || max_splits > (int64_t(1) << 26))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_cons_create: max_splits must be 1..2^26");
+        std::unique_ptr<tq_cons> a(new tq_cons());
+        a->ctx = ctx;
+        a->chunk.shape(T);
+        a->table.max_splits = max_splits;
+        if (ctx) {
+            const int64_t nodes = a->chunk.nodes();
+            TQ_HIPF(ctx, who, a->chunk.alloc(ctx->opt.cons_scratch_bytes, nodes * 4));        // the unresolved items
+            TQ_HIPF(ctx, who, a->table.alloc(ctx, a->chunk.W, a->chunk.chunk_trees * nodes));
+            TQ_HIPF(ctx, who, a->chunk.alloc_host());
+            TQ_HIPF(ctx, who, a->table.alloc_host());
+            TQ_HIPF(ctx, who, a->order.create());
+            if (int rc = a->table.clear(ctx)) return rc;
         }
-        if (int rc = a->table.clear(ctx)) {
-            delete a;
-            return rc;
-        }
-    }
-    *out = a;
-    return TQ_OK;
+        *out = a.release();
+        return TQ_OK;
+    });
 }
 
 void tq_cons_destroy(tq_cons *acc) { delete acc; }
@@ -4617,28 +4567,29 @@ void tq_cons_destroy(tq_cons *acc) { delete acc; }
 int tq_cons_reset(tq_cons *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx) {
-        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        TQ_HIP(acc->ctx, acc->order.sync());
-        if (int rc = acc->table.clear(acc->ctx)) return rc;
-    }
-    acc->table.forget(acc->ctx);
-    acc->ntrees = 0;
-    acc->chunk.chunks = 0;
-    acc->table_ok = false;
-    return TQ_OK;
+    return api(acc->ctx, "tq_cons_reset", [&]() -> int {
+        if (acc->ctx) {
+            TQ_HIP(acc->ctx, acc->order.sync());
+            if (int rc = acc->table.clear(acc->ctx)) return rc;
+        }
+        acc->table.forget(acc->ctx);
+        acc->ntrees = 0;
+        acc->chunk.chunks = 0;
+        acc->table_ok = false;
+        return TQ_OK;
+    });
 }
 
 int tq_cons_add(tq_cons *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    SplitTable &t = acc->table;
-    const int32_t T = acc->chunk.T, W = acc->chunk.W;
-    if (int rc = tree_set_args(ctx, "tq_cons_add", parents, n_nodes, R, stride)) return rc;
-    if (t.overflow) return t.overflowed(ctx, "tq_cons_add");
-    if (R == 0) return TQ_OK;
-    try {
+    return api(ctx, "tq_cons_add", [&]() -> int {
+        SplitTable &t = acc->table;
+        const int32_t T = acc->chunk.T, W = acc->chunk.W;
+        if (int rc = tree_set_args(ctx, "tq_cons_add", parents, n_nodes, R, stride)) return rc;
+        if (t.overflow) return t.overflowed(ctx, "tq_cons_add");
+        if (R == 0) return TQ_OK;
         const int64_t S = cons_stride(T);
         std::vector<int32_t> recs;
         if (int rc = prepare_trees(ctx, "tq_cons_add", parents, n_nodes, R, stride, T, recs)) return rc;
@@ -4659,16 +4610,13 @@ int tq_cons_add(tq_cons *acc, const int32_t *parents, const int64_t *n_nodes, in
             }
             return TQ_OK;
         }
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
         for (int64_t r0 = 0; r0 < R; r0 += acc->chunk.chunk_trees) {
             const int64_t n = std::min<int64_t>(acc->chunk.chunk_trees, R - r0);
             if (int rc = cons_drain(acc)) return rc;        // the staging buffer and the mask scratch are free again
             if (int rc = cons_launch(acc, n, &recs[(size_t)r0 * S], (hipStream_t)stream)) return rc;
         }
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_cons_add: out of host memory");
-    }
+    });
 }
 
 int tq_cons_shape(tq_cons *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits)
@@ -4677,57 +4625,50 @@ int tq_cons_shape(tq_cons *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t
     if (T) *T = acc->chunk.T;
     if (W) *W = acc->chunk.W;
     if (ntrees) *ntrees = acc->ntrees;
-    if (nsplits) {
-        try {
-            if (int rc = cons_table(acc, "tq_cons_shape")) return rc;
-        } catch (const std::bad_alloc &) {
-            return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_shape: out of host memory");
-        }
+    if (!nsplits) return TQ_OK;                 // scalars only: nothing to guard
+    return api(acc->ctx, "tq_cons_shape", [&]() -> int {
+        if (int rc = cons_table(acc, "tq_cons_shape")) return rc;
         *nsplits = (int64_t)acc->tcounts.size();
-    }
-    return TQ_OK;
+        return TQ_OK;
+    });
 }
 
 int tq_cons_read(tq_cons *acc, uint64_t *masks, int64_t *counts)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    try {
+    return api(acc->ctx, "tq_cons_read", [&]() -> int {
         if (int rc = cons_table(acc, "tq_cons_read")) return rc;
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_read: out of host memory");
-    }
-    if (masks && !acc->tmasks.empty()) memcpy(masks, acc->tmasks.data(), acc->tmasks.size() * 8);
-    if (counts && !acc->tcounts.empty()) memcpy(counts, acc->tcounts.data(), acc->tcounts.size() * 8);
-    return TQ_OK;
+        if (masks && !acc->tmasks.empty()) memcpy(masks, acc->tmasks.data(), acc->tmasks.size() * 8);
+        if (counts && !acc->tcounts.empty()) memcpy(counts, acc->tcounts.data(), acc->tcounts.size() * 8);
+        return TQ_OK;
+    });
 }
 
 int tq_cons_tree(tq_cons *acc, int64_t min_count, char *out, int64_t cap, int64_t *written)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (cap < 0 || !written || (cap > 0 && !out))
-        return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: NULL pointer or negative cap");
-    *written = 0;
-    if (min_count < 1) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: min_count must be at least 1");
-    try {
+    return api(acc->ctx, "tq_cons_tree", [&]() -> int {
+        if (cap < 0 || !written || (cap > 0 && !out))
+            return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: NULL pointer or negative cap");
+        *written = 0;
+        if (min_count < 1) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_tree: min_count must be at least 1");
         if (int rc = cons_table(acc, "tq_cons_tree")) return rc;
         const std::string nwk = cons_newick(acc->tmasks, acc->tcounts, acc->chunk.T, acc->chunk.W, acc->ntrees, min_count);
         *written = (int64_t)nwk.size();
         if ((int64_t)nwk.size() > cap) return TQ_ERR_OOM;
         memcpy(out, nwk.data(), nwk.size());
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_tree: out of host memory");
-    }
+    });
 }
 
 int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_t *counts_out, uint64_t *masks_out,
                     int64_t *n_edges)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (!parent || !n_edges) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: NULL pointer");
-    *n_edges = 0;
-    const int32_t T = acc->chunk.T, W = acc->chunk.W;
-    try {
+    return api(acc->ctx, "tq_cons_support", [&]() -> int {
+        if (!parent || !n_edges) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: NULL pointer");
+        *n_edges = 0;
+        const int32_t T = acc->chunk.T, W = acc->chunk.W;
         std::vector<int32_t> rec((size_t)cons_stride(T));
         const std::string err = cons_prepare(parent, n_nodes, T, rec.data());
         if (!err.empty()) return fail(acc->ctx, TQ_ERR_INVALID_ARG, "tq_cons_support: %s", err.c_str());
@@ -4754,69 +4695,61 @@ int tq_cons_support(tq_cons *acc, const int32_t *parent, int64_t n_nodes, int64_
         }
         *n_edges = E;
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_cons_support: out of host memory");
-    }
+    });
 }
 
 int tq_cons_stats(tq_cons *acc, int64_t *out)
 {
     if (!acc || !out) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx && !acc->table.overflow)
-        if (int rc = cons_drain(acc)) return rc;
-    out[0] = acc->chunk.chunk_trees;
-    out[1] = acc->chunk.chunks;
-    out[2] = acc->table.dev_entries;
-    out[3] = (int64_t)acc->table.host.size();
-    out[4] = acc->table.unresolved;
-    out[5] = acc->table.hash_bits;
-    return TQ_OK;
+    return api(acc->ctx, "tq_cons_stats", [&]() -> int {
+        if (acc->ctx && !acc->table.overflow)
+            if (int rc = cons_drain(acc)) return rc;
+        out[0] = acc->chunk.chunk_trees;
+        out[1] = acc->chunk.chunks;
+        out[2] = acc->table.dev_entries;
+        out[3] = (int64_t)acc->table.host.size();
+        out[4] = acc->table.unresolved;
+        out[5] = acc->table.hash_bits;
+        return TQ_OK;
+    });
 }
 
 int tq_tbe_create(tq_tbe **out, int64_t T, const int32_t *ref_parent, int64_t n_nodes, tq_ctx *ctx)
 {
+    const char *who = "tq_tbe_create";
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: out is NULL");
     *out = nullptr;
-    if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: T must be 4..%d", CONS_T_MAX);
-    if (!ref_parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: ref_parent is NULL");
-    tq_tbe *a = nullptr;
-    try {
+    return api(ctx, who, [&]() -> int {
+        if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: T must be 4..%d", CONS_T_MAX);
+        if (!ref_parent) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: ref_parent is NULL");
         std::vector<int32_t> rec((size_t)cons_stride(T));
         const std::string err = cons_prepare(ref_parent, n_nodes, T, rec.data());
         if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_tbe_create: %s", err.c_str());
-        a = new tq_tbe();
+        std::unique_ptr<tq_tbe> a(new tq_tbe());
         a->ctx = ctx;
         a->chunk.shape(T);
         tbe_reference(rec.data(), a->chunk.T, a->chunk.W, a->masks, a->p);
         a->E = (int64_t)a->p.size();
         a->phi_sum.assign((size_t)a->E, 0);
-    } catch (const std::bad_alloc &) {
-        delete a;
-        return fail(ctx, TQ_ERR_OOM, "tq_tbe_create: out of host memory");
-    }
-    if (ctx) {
-        const int64_t W = a->chunk.W, E1 = std::max<int64_t>(1, a->E);
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = a->chunk.alloc(ctx->cons_scratch_bytes, E1 * 2);       // the phi row
-        const int64_t C = a->chunk.chunk_trees;
-        if (e == hipSuccess) e = a->d_phi.alloc((size_t)C * E1);
-        if (e == hipSuccess) e = a->d_ref.alloc((size_t)E1 * W);
-        if (e == hipSuccess) e = a->d_p.alloc((size_t)E1);
-        if (e == hipSuccess) e = a->d_phi_sum.alloc((size_t)E1);
-        if (e == hipSuccess) e = a->chunk.alloc_host();
-        if (e == hipSuccess) e = a->p_phi.alloc((size_t)C * E1);
-        if (e == hipSuccess) e = a->order.create();
-        if (e == hipSuccess && a->E) e = hipMemcpy(a->d_ref, a->masks.data(), (size_t)a->E * W * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && a->E) e = hipMemcpy(a->d_p, a->p.data(), (size_t)a->E * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(a->d_phi_sum, 0, (size_t)E1 * 8);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            delete a;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_tbe_create: %s", hipGetErrorString(e));
+        if (ctx) {
+            const int64_t W = a->chunk.W, E1 = std::max<int64_t>(1, a->E);
+            TQ_HIPF(ctx, who, a->chunk.alloc(ctx->opt.cons_scratch_bytes, E1 * 2));       // the phi row
+            const int64_t C = a->chunk.chunk_trees;
+            TQ_HIPF(ctx, who, a->d_phi.alloc((size_t)C * E1));
+            TQ_HIPF(ctx, who, a->d_ref.alloc((size_t)E1 * W));
+            TQ_HIPF(ctx, who, a->d_p.alloc((size_t)E1));
+            TQ_HIPF(ctx, who, a->d_phi_sum.alloc((size_t)E1));
+            TQ_HIPF(ctx, who, a->chunk.alloc_host());
+            TQ_HIPF(ctx, who, a->p_phi.alloc((size_t)C * E1));
+            TQ_HIPF(ctx, who, a->order.create());
+            if (a->E) TQ_HIPF(ctx, who, hipMemcpy(a->d_ref, a->masks.data(), (size_t)a->E * W * 8, hipMemcpyHostToDevice));
+            if (a->E) TQ_HIPF(ctx, who, hipMemcpy(a->d_p, a->p.data(), (size_t)a->E * 4, hipMemcpyHostToDevice));
+            TQ_HIPF(ctx, who, hipMemset(a->d_phi_sum, 0, (size_t)E1 * 8));
+            TQ_HIPF(ctx, who, hipDeviceSynchronize());
         }
-    }
-    *out = a;
-    return TQ_OK;
+        *out = a.release();
+        return TQ_OK;
+    });
 }
 
 void tq_tbe_destroy(tq_tbe *acc) { delete acc; }
@@ -4824,16 +4757,17 @@ void tq_tbe_destroy(tq_tbe *acc) { delete acc; }
 int tq_tbe_reset(tq_tbe *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx) {
-        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        TQ_HIP(acc->ctx, acc->order.sync());
-        TQ_HIP(acc->ctx, hipMemset(acc->d_phi_sum, 0, (size_t)std::max<int64_t>(1, acc->E) * 8));
-        TQ_HIP(acc->ctx, hipDeviceSynchronize());
-    }
-    std::fill(acc->phi_sum.begin(), acc->phi_sum.end(), uint64_t(0));
-    acc->ntrees = 0;
-    acc->chunk.chunks = 0;
-    return TQ_OK;
+    return api(acc->ctx, "tq_tbe_reset", [&]() -> int {
+        if (acc->ctx) {
+            TQ_HIP(acc->ctx, acc->order.sync());
+            TQ_HIP(acc->ctx, hipMemset(acc->d_phi_sum, 0, (size_t)std::max<int64_t>(1, acc->E) * 8));
+            TQ_HIP(acc->ctx, hipDeviceSynchronize());
+        }
+        std::fill(acc->phi_sum.begin(), acc->phi_sum.end(), uint64_t(0));
+        acc->ntrees = 0;
+        acc->chunk.chunks = 0;
+        return TQ_OK;
+    });
 }
 
 int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream,
@@ -4841,10 +4775,10 @@ int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int6
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    const int32_t T = acc->chunk.T, W = acc->chunk.W;
-    if (int rc = tree_set_args(ctx, "tq_tbe_add", parents, n_nodes, R, stride)) return rc;
-    if (R == 0) return TQ_OK;
-    try {
+    return api(ctx, "tq_tbe_add", [&]() -> int {
+        const int32_t T = acc->chunk.T, W = acc->chunk.W;
+        if (int rc = tree_set_args(ctx, "tq_tbe_add", parents, n_nodes, R, stride)) return rc;
+        if (R == 0) return TQ_OK;
         const int64_t S = cons_stride(T), E = acc->E;
         std::vector<int32_t> recs;
         if (int rc = prepare_trees(ctx, "tq_tbe_add", parents, n_nodes, R, stride, T, recs)) return rc;
@@ -4862,7 +4796,6 @@ int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int6
             }
             return TQ_OK;
         }
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
         for (int64_t r0 = 0; r0 < R; r0 += acc->chunk.chunk_trees) {
             const int64_t n = std::min<int64_t>(acc->chunk.chunk_trees, R - r0);
             TQ_HIP(ctx, acc->order.sync());             // the staging buffer and the mask scratch are free again
@@ -4873,9 +4806,7 @@ int tq_tbe_add(tq_tbe *acc, const int32_t *parents, const int64_t *n_nodes, int6
             }
         }
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_tbe_add: out of host memory");
-    }
+    });
 }
 
 int tq_tbe_shape(tq_tbe *acc, int64_t *T, int64_t *W, int64_t *E, int64_t *ntrees)
@@ -4891,18 +4822,19 @@ int tq_tbe_shape(tq_tbe *acc, int64_t *T, int64_t *W, int64_t *E, int64_t *ntree
 int tq_tbe_read(tq_tbe *acc, uint64_t *masks, int64_t *p, uint64_t *phi_sum)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    const int64_t E = acc->E;
-    if (acc->ctx) {
-        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        TQ_HIP(acc->ctx, acc->order.sync());
-        if (phi_sum && E) TQ_HIP(acc->ctx, hipMemcpy(phi_sum, acc->d_phi_sum, (size_t)E * 8, hipMemcpyDeviceToHost));
-    } else if (phi_sum && E) {
-        memcpy(phi_sum, acc->phi_sum.data(), (size_t)E * 8);
-    }
-    if (masks && E) memcpy(masks, acc->masks.data(), (size_t)E * acc->chunk.W * 8);
-    if (p)
-        for (int64_t e = 0; e < E; ++e) p[e] = acc->p[e];
-    return TQ_OK;
+    return api(acc->ctx, "tq_tbe_read", [&]() -> int {
+        const int64_t E = acc->E;
+        if (acc->ctx) {
+            TQ_HIP(acc->ctx, acc->order.sync());
+            if (phi_sum && E) TQ_HIP(acc->ctx, hipMemcpy(phi_sum, acc->d_phi_sum, (size_t)E * 8, hipMemcpyDeviceToHost));
+        } else if (phi_sum && E) {
+            memcpy(phi_sum, acc->phi_sum.data(), (size_t)E * 8);
+        }
+        if (masks && E) memcpy(masks, acc->masks.data(), (size_t)E * acc->chunk.W * 8);
+        if (p)
+            for (int64_t e = 0; e < E; ++e) p[e] = acc->p[e];
+        return TQ_OK;
+    });
 }
 
 int tq_tbe_stats(tq_tbe *acc, int64_t *out)
@@ -4915,51 +4847,45 @@ int tq_tbe_stats(tq_tbe *acc, int64_t *out)
 
 int tq_rf_create(tq_rf **out, int64_t T, int64_t max_trees, int64_t max_splits, tq_ctx *ctx)
 {
+    const char *who = "tq_rf_create";
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: out is NULL");
     *out = nullptr;
-    if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: T must be 4..%d", CONS_T_MAX);
-    if (max_trees < 1 || max_trees > RF_MAX_TREES)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: max_trees must be 1..%lld", (long long)RF_MAX_TREES);
-    if (max_splits < 1 || max_splits > (int64_t(1) << 26))
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: max_splits must be 1..2^26");
-    tq_rf *a = new (std::nothrow) tq_rf();
-    if (!a) return fail(ctx, TQ_ERR_OOM, "tq_rf_create: out of host memory");
-    a->ctx = ctx;
-    a->chunk.shape(T);
-    a->max_trees = max_trees;
-    a->table.max_splits = max_splits;
-    if (ctx) {
-        const int64_t nodes = a->chunk.nodes();
-        // a column is a split of at least two trees
-        const int64_t max_cols = std::max<int64_t>(1, std::min<int64_t>(max_splits, max_trees * (T - 3) / 2));
-        a->cw_chunk = std::max<int64_t>(1, std::min<int64_t>((max_cols + 63) / 64, ctx->cons_scratch_bytes / (max_trees * 8)));
-        hipError_t e = hipSetDevice(ctx->device);
-        // beside a tree's masks: its unresolved items and their ids, device and page-locked
-        if (e == hipSuccess) e = a->chunk.alloc(ctx->cons_scratch_bytes, nodes * 4 * 3, max_trees);
-        const int64_t items = a->chunk.chunk_trees * nodes;
-        if (e == hipSuccess) e = a->table.alloc(ctx, a->chunk.W, items);
-        if (e == hipSuccess) e = a->d_newid.alloc((size_t)items);
-        if (e == hipSuccess) e = a->d_colmap.alloc((size_t)max_splits);
-        if (e == hipSuccess) e = a->d_ids.alloc((size_t)max_trees * nodes);
-        if (e == hipSuccess) e = a->d_nsplits.alloc((size_t)max_trees);
-        if (e == hipSuccess) e = a->d_bits.alloc((size_t)max_trees * a->cw_chunk);
-        if (e == hipSuccess) e = a->d_shared.alloc((size_t)max_trees * max_trees);
-        if (e == hipSuccess) e = a->d_rf.alloc((size_t)max_trees * max_trees);
-        if (e == hipSuccess) e = a->chunk.alloc_host();
-        if (e == hipSuccess) e = a->table.alloc_host();
-        if (e == hipSuccess) e = a->p_newid.alloc((size_t)items);
-        if (e == hipSuccess) e = a->order.create();
-        if (e != hipSuccess) {
-            delete a;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_rf_create: %s", hipGetErrorString(e));
+    return api(ctx, who, [&]() -> int {
+        if (T < 4 || T > CONS_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: T must be 4..%d", CONS_T_MAX);
+        if (max_trees < 1 || max_trees > RF_MAX_TREES)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: max_trees must be 1..%lld", (long long)RF_MAX_TREES);
+        if (max_splits < 1 || max_splits > (int64_t(1) << 26))
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_create: max_splits must be 1..2^26");
+        std::unique_ptr<tq_rf> a(new tq_rf());
+        a->ctx = ctx;
+        a->chunk.shape(T);
+        a->max_trees = max_trees;
+        a->table.max_splits = max_splits;
+        if (ctx) {
+            const int64_t nodes = a->chunk.nodes();
+            // a column is a split of at least two trees
+            const int64_t max_cols = std::max<int64_t>(1, std::min<int64_t>(max_splits, max_trees * (T - 3) / 2));
+            a->cw_chunk = std::max<int64_t>(1, std::min<int64_t>((max_cols + 63) / 64, ctx->opt.cons_scratch_bytes / (max_trees * 8)));
+            // beside a tree's masks: its unresolved items and their ids, device and page-locked
+            TQ_HIPF(ctx, who, a->chunk.alloc(ctx->opt.cons_scratch_bytes, nodes * 4 * 3, max_trees));
+            const int64_t items = a->chunk.chunk_trees * nodes;
+            TQ_HIPF(ctx, who, a->table.alloc(ctx, a->chunk.W, items));
+            TQ_HIPF(ctx, who, a->d_newid.alloc((size_t)items));
+            TQ_HIPF(ctx, who, a->d_colmap.alloc((size_t)max_splits));
+            TQ_HIPF(ctx, who, a->d_ids.alloc((size_t)max_trees * nodes));
+            TQ_HIPF(ctx, who, a->d_nsplits.alloc((size_t)max_trees));
+            TQ_HIPF(ctx, who, a->d_bits.alloc((size_t)max_trees * a->cw_chunk));
+            TQ_HIPF(ctx, who, a->d_shared.alloc((size_t)max_trees * max_trees));
+            TQ_HIPF(ctx, who, a->d_rf.alloc((size_t)max_trees * max_trees));
+            TQ_HIPF(ctx, who, a->chunk.alloc_host());
+            TQ_HIPF(ctx, who, a->table.alloc_host());
+            TQ_HIPF(ctx, who, a->p_newid.alloc((size_t)items));
+            TQ_HIPF(ctx, who, a->order.create());
+            if (int rc = rf_clear_dev(a.get())) return rc;
         }
-        if (int rc = rf_clear_dev(a)) {
-            delete a;
-            return rc;
-        }
-    }
-    *out = a;
-    return TQ_OK;
+        *out = a.release();
+        return TQ_OK;
+    });
 }
 
 void tq_rf_destroy(tq_rf *acc) { delete acc; }
@@ -4967,34 +4893,35 @@ void tq_rf_destroy(tq_rf *acc) { delete acc; }
 int tq_rf_reset(tq_rf *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx) {
-        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        TQ_HIP(acc->ctx, acc->order.sync());
-        if (int rc = rf_clear_dev(acc)) return rc;
-    }
-    acc->table.forget(acc->ctx);
-    acc->host_count.clear();
-    acc->lists.clear();
-    acc->ntrees = 0;
-    acc->chunk.chunks = 0;
-    acc->columns = acc->col_chunks = 0;
-    acc->final_ok = false;
-    return TQ_OK;
+    return api(acc->ctx, "tq_rf_reset", [&]() -> int {
+        if (acc->ctx) {
+            TQ_HIP(acc->ctx, acc->order.sync());
+            if (int rc = rf_clear_dev(acc)) return rc;
+        }
+        acc->table.forget(acc->ctx);
+        acc->host_count.clear();
+        acc->lists.clear();
+        acc->ntrees = 0;
+        acc->chunk.chunks = 0;
+        acc->columns = acc->col_chunks = 0;
+        acc->final_ok = false;
+        return TQ_OK;
+    });
 }
 
 int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    SplitTable &t = acc->table;
-    const int32_t T = acc->chunk.T, W = acc->chunk.W;
-    if (int rc = tree_set_args(ctx, "tq_rf_add", parents, n_nodes, R, stride)) return rc;
-    if (t.overflow) return t.overflowed(ctx, "tq_rf_add");
-    if (R == 0) return TQ_OK;
-    if (acc->ntrees + R > acc->max_trees)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: %lld trees held and %lld offered exceed max_trees = %lld",
-                    (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
-    try {
+    return api(ctx, "tq_rf_add", [&]() -> int {
+        SplitTable &t = acc->table;
+        const int32_t T = acc->chunk.T, W = acc->chunk.W;
+        if (int rc = tree_set_args(ctx, "tq_rf_add", parents, n_nodes, R, stride)) return rc;
+        if (t.overflow) return t.overflowed(ctx, "tq_rf_add");
+        if (R == 0) return TQ_OK;
+        if (acc->ntrees + R > acc->max_trees)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_rf_add: %lld trees held and %lld offered exceed max_trees = %lld",
+                        (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
         const int64_t S = cons_stride(T);
         std::vector<int32_t> recs;
         if (int rc = prepare_trees(ctx, "tq_rf_add", parents, n_nodes, R, stride, T, recs)) return rc;
@@ -5019,7 +4946,6 @@ int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_
             }
             return TQ_OK;
         }
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
         for (int64_t r0 = 0; r0 < R; r0 += acc->chunk.chunk_trees) {
             const int64_t n = std::min<int64_t>(acc->chunk.chunk_trees, R - r0);
             if (int rc = rf_drain(acc)) return rc;          // the staging buffer and the mask scratch are free again
@@ -5028,119 +4954,105 @@ int tq_rf_add(tq_rf *acc, const int32_t *parents, const int64_t *n_nodes, int64_
             acc->ntrees += n;
         }
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_rf_add: out of host memory");
-    }
+    });
 }
 
 int tq_rf_shape(tq_rf *acc, int64_t *T, int64_t *W, int64_t *ntrees, int64_t *nsplits, int64_t *columns)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->chunk.T;
-    if (W) *W = acc->chunk.W;
-    if (ntrees) *ntrees = acc->ntrees;
-    if (nsplits) {
-        if (acc->ctx && !acc->table.overflow) {
-            try {
+    return api(acc->ctx, "tq_rf_shape", [&]() -> int {
+        if (T) *T = acc->chunk.T;
+        if (W) *W = acc->chunk.W;
+        if (ntrees) *ntrees = acc->ntrees;
+        if (nsplits) {
+            if (acc->ctx && !acc->table.overflow)
                 if (int rc = rf_drain(acc)) return rc;
-            } catch (const std::bad_alloc &) {
-                return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_shape: out of host memory");
-            }
+            *nsplits = (acc->ctx ? acc->table.dev_entries : 0) + (int64_t)acc->table.host.size();
         }
-        *nsplits = (acc->ctx ? acc->table.dev_entries : 0) + (int64_t)acc->table.host.size();
-    }
-    if (columns) *columns = acc->columns;
-    return TQ_OK;
+        if (columns) *columns = acc->columns;
+        return TQ_OK;
+    });
 }
 
 int tq_rf_read(tq_rf *acc, int32_t *nsplits, uint32_t *shared, uint32_t *rf)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    try {
+    return api(acc->ctx, "tq_rf_read", [&]() -> int {
         if (int rc = rf_final(acc, "tq_rf_read")) return rc;
-    } catch (const std::bad_alloc &) {
-        return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_read: out of host memory");
-    }
-    const size_t N = (size_t)acc->ntrees;
-    if (N == 0) return TQ_OK;
-    if (acc->ctx) {
-        TQ_HIP(acc->ctx, hipSetDevice(acc->ctx->device));
-        if (nsplits) TQ_HIP(acc->ctx, hipMemcpy(nsplits, acc->d_nsplits, N * 4, hipMemcpyDeviceToHost));
-        if (shared) TQ_HIP(acc->ctx, hipMemcpy(shared, acc->d_shared, N * N * 4, hipMemcpyDeviceToHost));
-        if (rf) TQ_HIP(acc->ctx, hipMemcpy(rf, acc->d_rf, N * N * 4, hipMemcpyDeviceToHost));
-    } else {
-        if (nsplits) memcpy(nsplits, acc->h_nsplits.data(), N * 4);
-        if (shared) memcpy(shared, acc->h_shared.data(), N * N * 4);
-        if (rf) memcpy(rf, acc->h_rf.data(), N * N * 4);
-    }
-    return TQ_OK;
+        const size_t N = (size_t)acc->ntrees;
+        if (N == 0) return TQ_OK;
+        if (acc->ctx) {
+            if (nsplits) TQ_HIP(acc->ctx, hipMemcpy(nsplits, acc->d_nsplits, N * 4, hipMemcpyDeviceToHost));
+            if (shared) TQ_HIP(acc->ctx, hipMemcpy(shared, acc->d_shared, N * N * 4, hipMemcpyDeviceToHost));
+            if (rf) TQ_HIP(acc->ctx, hipMemcpy(rf, acc->d_rf, N * N * 4, hipMemcpyDeviceToHost));
+        } else {
+            if (nsplits) memcpy(nsplits, acc->h_nsplits.data(), N * 4);
+            if (shared) memcpy(shared, acc->h_shared.data(), N * N * 4);
+            if (rf) memcpy(rf, acc->h_rf.data(), N * N * 4);
+        }
+        return TQ_OK;
+    });
 }
 
 int tq_rf_stats(tq_rf *acc, int64_t *out)
 {
     if (!acc || !out) return TQ_ERR_INVALID_ARG;
-    if (acc->ctx && !acc->table.overflow) {
-        try {
+    return api(acc->ctx, "tq_rf_stats", [&]() -> int {
+        if (acc->ctx && !acc->table.overflow)
             if (int rc = rf_drain(acc)) return rc;
-        } catch (const std::bad_alloc &) {
-            return fail(acc->ctx, TQ_ERR_OOM, "tq_rf_stats: out of host memory");
-        }
-    }
-    out[0] = acc->chunk.chunk_trees;
-    out[1] = acc->chunk.chunks;
-    out[2] = acc->columns;
-    out[3] = acc->cw_chunk;
-    out[4] = acc->col_chunks;
-    out[5] = acc->table.unresolved;
-    out[6] = acc->table.hash_bits;
-    out[7] = acc->table.dev_entries;
-    return TQ_OK;
+        out[0] = acc->chunk.chunk_trees;
+        out[1] = acc->chunk.chunks;
+        out[2] = acc->columns;
+        out[3] = acc->cw_chunk;
+        out[4] = acc->col_chunks;
+        out[5] = acc->table.unresolved;
+        out[6] = acc->table.hash_bits;
+        out[7] = acc->table.dev_entries;
+        return TQ_OK;
+    });
 }
 
 uint32_t tq_rf_word_shared(uint64_t x, uint64_t y) { return rf_word_shared(x, y); }
 
 int tq_qd_create(tq_qd **out, int64_t T, int64_t max_trees, tq_ctx *ctx)
 {
+    const char *who = "tq_qd_create";
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: out is NULL");
     *out = nullptr;
-    if (T < 4 || T > STREE_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: T must be 4..%d", STREE_T_MAX);
-    if (max_trees < 1 || max_trees > QD_MAX_TREES)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: max_trees must be 1..%lld", (long long)QD_MAX_TREES);
-    tq_qd *a = new (std::nothrow) tq_qd();
-    if (!a) return fail(ctx, TQ_ERR_OOM, "tq_qd_create: out of host memory");
-    a->ctx = ctx;
-    a->T = (int32_t)T;
-    a->max_trees = max_trees;
-    a->chunk_words = QD_HOST_CHUNK_WORDS;
-    if (ctx) {
-        // per plane word of a chunk: 64 quartets as taxa and as ranks on the device, 16 page-locked bytes each, and
-        // three plane words of every tree
-        const int64_t per_word = 64 * (16 + 8 + 16) + max_trees * 3 * 8;
-        a->chunk_words = std::max<int64_t>(1, std::min<int64_t>(ctx->qdist_scratch_bytes / per_word, QD_MAX_CHUNK_WORDS));
-        a->num_cu = std::max(1, ctx->prop.multiProcessorCount);
-        const size_t cq = (size_t)a->chunk_words * 64, mm = (size_t)(max_trees * max_trees);
-        hipError_t e = hipSetDevice(ctx->device);
-        if (e == hipSuccess) e = a->d_tab.alloc((size_t)max_trees * T * T);
-        if (e == hipSuccess) e = a->d_rec.alloc((size_t)max_trees * 2 * T);
-        if (e == hipSuccess) e = a->p_rec.alloc((size_t)max_trees * 2 * T);
-        if (e == hipSuccess) e = a->d_same.alloc(mm);
-        if (e == hipSuccess) e = a->d_both.alloc(mm);
-        if (e == hipSuccess) e = a->d_quart.alloc(cq * 4);
-        if (e == hipSuccess) e = a->d_ranks.alloc(cq);
-        if (e == hipSuccess) e = a->d_planes.alloc((size_t)max_trees * 3 * a->chunk_words);
-        if (e == hipSuccess) e = a->p_stage.alloc(cq * 2);
-        if (e == hipSuccess) e = a->order.create();
-        if (e == hipSuccess) e = a->copy.create();
-        if (e == hipSuccess) e = hipMemset(a->d_same, 0, mm * 8);
-        if (e == hipSuccess) e = hipMemset(a->d_both, 0, mm * 8);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            delete a;
-            return fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_qd_create: %s", hipGetErrorString(e));
+    return api(ctx, who, [&]() -> int {
+        if (T < 4 || T > STREE_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: T must be 4..%d", STREE_T_MAX);
+        if (max_trees < 1 || max_trees > QD_MAX_TREES)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: max_trees must be 1..%lld", (long long)QD_MAX_TREES);
+        std::unique_ptr<tq_qd> a(new tq_qd());
+        a->ctx = ctx;
+        a->T = (int32_t)T;
+        a->max_trees = max_trees;
+        a->chunk_words = QD_HOST_CHUNK_WORDS;
+        if (ctx) {
+            // per plane word of a chunk: 64 quartets as taxa and as ranks on the device, 16 page-locked bytes each, and
+            // three plane words of every tree
+            const int64_t per_word = 64 * (16 + 8 + 16) + max_trees * 3 * 8;
+            a->chunk_words = std::max<int64_t>(1, std::min<int64_t>(ctx->opt.qdist_scratch_bytes / per_word, QD_MAX_CHUNK_WORDS));
+            a->num_cu = std::max(1, ctx->prop.multiProcessorCount);
+            const size_t cq = (size_t)a->chunk_words * 64, mm = (size_t)(max_trees * max_trees);
+            TQ_HIPF(ctx, who, a->d_tab.alloc((size_t)max_trees * T * T));
+            TQ_HIPF(ctx, who, a->d_rec.alloc((size_t)max_trees * 2 * T));
+            TQ_HIPF(ctx, who, a->p_rec.alloc((size_t)max_trees * 2 * T));
+            TQ_HIPF(ctx, who, a->d_same.alloc(mm));
+            TQ_HIPF(ctx, who, a->d_both.alloc(mm));
+            TQ_HIPF(ctx, who, a->d_quart.alloc(cq * 4));
+            TQ_HIPF(ctx, who, a->d_ranks.alloc(cq));
+            TQ_HIPF(ctx, who, a->d_planes.alloc((size_t)max_trees * 3 * a->chunk_words));
+            TQ_HIPF(ctx, who, a->p_stage.alloc(cq * 2));
+            TQ_HIPF(ctx, who, a->order.create());
+            TQ_HIPF(ctx, who, a->copy.create());
+            TQ_HIPF(ctx, who, hipMemset(a->d_same, 0, mm * 8));
+            TQ_HIPF(ctx, who, hipMemset(a->d_both, 0, mm * 8));
+            TQ_HIPF(ctx, who, hipDeviceSynchronize());
         }
-    }
-    *out = a;
-    return TQ_OK;
+        *out = a.release();
+        return TQ_OK;
+    });
 }
 
 void tq_qd_destroy(tq_qd *acc) { delete acc; }
@@ -5148,44 +5060,36 @@ void tq_qd_destroy(tq_qd *acc) { delete acc; }
 int tq_qd_clear(tq_qd *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    return qd_zero(acc);
+    return api(acc->ctx, "tq_qd_clear", [&]() -> int { return qd_zero(acc); });
 }
 
 int tq_qd_reset(tq_qd *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (int rc = qd_zero(acc)) return rc;
-    acc->h_tab.clear();
-    acc->ntrees = 0;
-    acc->chunks = acc->kslices = acc->tables = 0;
-    return TQ_OK;
+    return api(acc->ctx, "tq_qd_reset", [&]() -> int {
+        if (int rc = qd_zero(acc)) return rc;
+        acc->h_tab.clear();
+        acc->ntrees = 0;
+        acc->chunks = acc->kslices = acc->tables = 0;
+        return TQ_OK;
+    });
 }
 
 int tq_qd_add(tq_qd *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (int rc = tree_set_args(ctx, "tq_qd_add", parents, n_nodes, R, stride)) return rc;
-    if (R == 0) return TQ_OK;
-    if (acc->scored)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: quartets have been scored; clear or reset the accumulator first");
-    if (acc->ntrees + R > acc->max_trees)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: %lld trees held and %lld offered exceed max_trees = %lld",
-                    (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
-    const int64_t T = acc->T;
-    try {
-        std::vector<std::vector<int32_t>> pars((size_t)R);          // every tree is validated before the first one is added
-        std::vector<std::vector<int32_t>> nch;
-        for (int64_t r = 0; r < R; ++r) {
-            if (n_nodes[r] > stride)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: tree %lld: n_nodes exceeds the stride", (long long)r);
-            const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
-            if (!err.empty())
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: tree %lld: %s", (long long)r, err.c_str());
-            if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: tree %lld: internal error: a prepared tree of T taxa has "
-                            "at most 2 T - 2 nodes", (long long)r);
-        }
+    return api(ctx, "tq_qd_add", [&]() -> int {
+        if (int rc = tree_set_args(ctx, "tq_qd_add", parents, n_nodes, R, stride)) return rc;
+        if (R == 0) return TQ_OK;
+        if (acc->scored)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: quartets have been scored; clear or reset the accumulator first");
+        if (acc->ntrees + R > acc->max_trees)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: %lld trees held and %lld offered exceed max_trees = %lld",
+                        (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
+        const int64_t T = acc->T;
+        std::vector<std::vector<int32_t>> pars;
+        if (int rc = prepare_fit_trees(ctx, "tq_qd_add", parents, n_nodes, R, stride, T, pars)) return rc;
         if (!ctx) {
             acc->h_tab.resize((size_t)((acc->ntrees + R) * T * T));
             std::vector<uint32_t> dep;
@@ -5196,72 +5100,57 @@ int tq_qd_add(tq_qd *acc, const int32_t *parents, const int64_t *n_nodes, int64_
             return TQ_OK;
         }
         hipStream_t st = (hipStream_t)stream;
-        TQ_HIP(ctx, hipSetDevice(ctx->device));
         TQ_HIP(ctx, acc->order.join(st));
         const int64_t S = 2 * T, first = acc->ntrees;
         int32_t *rec0 = acc->p_rec + first * S;                     // every tree has a record of its own: none is reused
-        memset(rec0, 0, (size_t)(R * S) * 4);
-        for (int64_t r = 0; r < R; ++r) {
-            memcpy(rec0 + r * S, pars[(size_t)r].data(), pars[(size_t)r].size() * 4);
-            rec0[r * S + S - 1] = (int32_t)pars[(size_t)r].size();
-        }
+        fit_stage_records(rec0, pars, S);
         TQ_HIP(ctx, hipMemcpyAsync(acc->d_rec + first * S, rec0, (size_t)(R * S) * 4, hipMemcpyHostToDevice, st));
-        const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
-        const unsigned table_blocks = (unsigned)std::max<int64_t>(
-            1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
         FitTableArgs ta{acc->d_rec + first * S, acc->d_tab + first * T * T, (uint32_t)T};
-        hipLaunchKernelGGL(tq_fit_table_kernel, dim3(table_blocks, (unsigned)R), dim3(FIT_THREADS), 0, st, ta);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_qd_add: launch failed: %s", hipGetErrorString(e));
+        hipLaunchKernelGGL(tq_fit_table_kernel, dim3(fit_table_blocks(T), (unsigned)R), dim3(FIT_THREADS), 0, st, ta);
+        TQ_LAUNCHED(ctx, "tq_qd_add");
         TQ_HIP(ctx, acc->order.mark(st));
         acc->ntrees += R;
         acc->tables += R;
         return TQ_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_qd_add: out of host memory");
-    }
+    });
 }
 
 int tq_qd_score(tq_qd *acc, const int32_t *quartets, int64_t Q, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (Q < 0 || (Q > 0 && !quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: NULL pointer or negative Q");
-    const int32_t T = acc->T;
-    for (int64_t i = 0; i < Q; ++i) {                               // every quartet is validated before anything is scored
-        const int32_t *q = quartets + 4 * i;
-        if (q[0] < 0 || q[0] >= T || q[1] < 0 || q[1] >= T || q[2] < 0 || q[2] >= T || q[3] < 0 || q[3] >= T)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: taxon out of range 0..%d", (long long)i, T - 1);
-        if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: repeated taxon", (long long)i);
-    }
-    try {
+    return api(ctx, "tq_qd_score", [&]() -> int {
+        if (Q < 0 || (Q > 0 && !quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: NULL pointer or negative Q");
+        const int32_t T = acc->T;
+        for (int64_t i = 0; i < Q; ++i) {                               // every quartet is validated before anything is scored
+            const int32_t *q = quartets + 4 * i;
+            if (q[0] < 0 || q[0] >= T || q[1] < 0 || q[1] >= T || q[2] < 0 || q[2] >= T || q[3] < 0 || q[3] >= T)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: taxon out of range 0..%d", (long long)i, T - 1);
+            if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
+                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: repeated taxon", (long long)i);
+        }
         return qd_score(acc, quartets, nullptr, 0, Q, (hipStream_t)stream, "tq_qd_score");
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_qd_score: out of host memory");
-    }
+    });
 }
 
 int tq_qd_score_ranks(tq_qd *acc, const uint64_t *ranks, uint64_t first_rank, int64_t Q, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    if (Q < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: negative Q");
-    const uint64_t total = choose4((uint64_t)acc->T);
-    if (ranks) {
-        for (int64_t i = 0; i < Q; ++i)
-            if (ranks[i] >= total)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank %lld: %llu is not below C(%d,4) = %llu",
-                            (long long)i, (unsigned long long)ranks[i], acc->T, (unsigned long long)total);
-    } else if (Q > 0 && (first_rank > total || (uint64_t)Q > total - first_rank)) {
-        return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank range [%llu,+%lld) exceeds C(%d,4) = %llu",
-                    (unsigned long long)first_rank, (long long)Q, acc->T, (unsigned long long)total);
-    }
-    try {
+    return api(ctx, "tq_qd_score_ranks", [&]() -> int {
+        if (Q < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: negative Q");
+        const uint64_t total = choose4((uint64_t)acc->T);
+        if (ranks) {
+            for (int64_t i = 0; i < Q; ++i)
+                if (ranks[i] >= total)
+                    return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank %lld: %llu is not below C(%d,4) = %llu",
+                                (long long)i, (unsigned long long)ranks[i], acc->T, (unsigned long long)total);
+        } else if (Q > 0 && (first_rank > total || (uint64_t)Q > total - first_rank)) {
+            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank range [%llu,+%lld) exceeds C(%d,4) = %llu",
+                        (unsigned long long)first_rank, (long long)Q, acc->T, (unsigned long long)total);
+        }
         return qd_score(acc, nullptr, ranks, ranks ? 0 : first_rank, Q, (hipStream_t)stream, "tq_qd_score_ranks");
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, TQ_ERR_OOM, "tq_qd_score_ranks: out of host memory");
-    }
+    });
 }
 
 int tq_qd_shape(tq_qd *acc, int64_t *T, int64_t *ntrees, uint64_t *q_total)
@@ -5277,32 +5166,32 @@ int tq_qd_read(tq_qd *acc, uint64_t *same, uint64_t *both)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
     tq_ctx *ctx = acc->ctx;
-    const int64_t N = acc->ntrees;
-    const size_t bytes = (size_t)(N * N) * 8;
-    if (N == 0) return TQ_OK;
-    if (!ctx) {
-        if (!acc->scored) {
-            if (same) memset(same, 0, bytes);
-            if (both) memset(both, 0, bytes);
+    return api(ctx, "tq_qd_read", [&]() -> int {
+        const int64_t N = acc->ntrees;
+        const size_t bytes = (size_t)(N * N) * 8;
+        if (N == 0) return TQ_OK;
+        if (!ctx) {
+            if (!acc->scored) {
+                if (same) memset(same, 0, bytes);
+                if (both) memset(both, 0, bytes);
+                return TQ_OK;
+            }
+            if (same) memcpy(same, acc->h_same.data(), bytes);
+            if (both) memcpy(both, acc->h_both.data(), bytes);
             return TQ_OK;
         }
-        if (same) memcpy(same, acc->h_same.data(), bytes);
-        if (both) memcpy(both, acc->h_both.data(), bytes);
+        hipStream_t st = acc->order.last;
+        if (acc->scored && N > QD_BT) {                                 // the tiles below the diagonal, behind the last score
+            hipLaunchKernelGGL(tq_qd_final_kernel, dim3((unsigned)((N * N + QD_THREADS - 1) / QD_THREADS)), dim3(QD_THREADS), 0, st,
+                               acc->d_same.get(), acc->d_both.get(), (int32_t)N);
+            TQ_LAUNCHED(ctx, "tq_qd_read");
+            TQ_HIP(ctx, acc->order.mark(st));
+        }
+        TQ_HIP(ctx, acc->order.sync());
+        if (same) TQ_HIP(ctx, hipMemcpy(same, acc->d_same, bytes, hipMemcpyDeviceToHost));
+        if (both) TQ_HIP(ctx, hipMemcpy(both, acc->d_both, bytes, hipMemcpyDeviceToHost));
         return TQ_OK;
-    }
-    TQ_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = acc->order.last;
-    if (acc->scored && N > QD_BT) {                                 // the tiles below the diagonal, behind the last score
-        hipLaunchKernelGGL(tq_qd_final_kernel, dim3((unsigned)((N * N + QD_THREADS - 1) / QD_THREADS)), dim3(QD_THREADS), 0, st,
-                           acc->d_same.get(), acc->d_both.get(), (int32_t)N);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ctx, TQ_ERR_HIP, "tq_qd_read: launch failed: %s", hipGetErrorString(e));
-        TQ_HIP(ctx, acc->order.mark(st));
-    }
-    TQ_HIP(ctx, acc->order.sync());
-    if (same) TQ_HIP(ctx, hipMemcpy(same, acc->d_same, bytes, hipMemcpyDeviceToHost));
-    if (both) TQ_HIP(ctx, hipMemcpy(both, acc->d_both, bytes, hipMemcpyDeviceToHost));
-    return TQ_OK;
+    });
 }
 
 int tq_qd_stats(tq_qd *acc, int64_t *out)
@@ -5329,7 +5218,7 @@ int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t 
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
     if (num_cu) *num_cu = ctx->prop.multiProcessorCount;
-    if (waves_per_cu) *waves_per_cu = ctx->waves_per_cu;
+    if (waves_per_cu) *waves_per_cu = ctx->opt.waves_per_cu;
     if (row_pitch) *row_pitch = ctx->nat.Sp;
     return TQ_OK;
 }

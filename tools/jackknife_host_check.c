@@ -1,11 +1,6 @@
 /* jackknife_host_check.c -- the host execution of the block jackknife (tq_dstat_jackknife) on
- * designed block rows, driven from a plain C program, meant to be built with the host sanitizers:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/jackknife_host_check.c -o /tmp/jackknife_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/jackknife_host_check.o -o /tmp/jackknife_host_check
- *   /tmp/jackknife_host_check
+ * designed block rows, driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched: the call takes no context.  Every buffer is allocated at its exact size, so a read or
  * write past a row, a block or a test shows as a sanitizer report.  The values are checked against a restatement of

@@ -1,12 +1,6 @@
 /* nni_host_check.c -- the host paths of the NNI scan and the polish search (tq_stree_nni_scan / tq_stree_polish on an
- * accumulator without a context), driven from a plain C program, meant to be built with the host
- * sanitizers exactly as tools/scf_host_check.c is:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/nni_host_check.c -o /tmp/nni_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/nni_host_check.o -o /tmp/nni_host_check
- *   /tmp/nni_host_check
+ * accumulator without a context), driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched.  Scans are recounted from the corner masks the library reports (a row counts on an edge
  * when its four taxa fall one into each mask); polishes are checked through tq_stree_fit of the tree before and after.

@@ -1,12 +1,6 @@
 /* qdist_host_check.c -- the host back end of the quartet distance accumulator (tq_qd_* without a context, DESIGN.md
- * section 27), driven from a plain C program, meant to be built with the host sanitizers exactly as
- * tools/treedist_host_check.c is:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/qdist_host_check.c -o /tmp/qdist_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/qdist_host_check.o -o /tmp/qdist_host_check
- *   /tmp/qdist_host_check
+ * section 27), driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched.  The word rule is recounted from a loop over the bits; the matrices of a few
  * hard-coded trees are known by hand, and those of random trees are recounted from taxon sets: a tree displays a,b|c,d

@@ -1,12 +1,6 @@
 /* quintet_host_check.c -- the host-only calls of DESIGN.md section 22 (tq_quintet_class_table and the jackknife on sums of
- * slots, tq_dstat_jackknife_masks) on designed block rows, driven from a plain C program, meant to be built with the host
- * sanitizers:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/quintet_host_check.c -o /tmp/quintet_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/quintet_host_check.o -o /tmp/quintet_host_check
- *   /tmp/quintet_host_check
+ * slots, tq_dstat_jackknife_masks) on designed block rows, driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched: neither call takes a context.  Every buffer is allocated at its exact size, so a read
  * or write past a row, a block, a test or the table shows as a sanitizer report.  The values are checked against a

@@ -1,14 +1,8 @@
 /* scf_host_check.c -- the host paths of the two accumulators on a fixed tree, which share their host code: the site
  * concordance accumulator (tq_scf_create / tq_scf_add / tq_scf_read with a NULL context) and the
  * quartet concordance accumulator (tq_conc_create / tq_conc_add / tq_conc_read / tq_conc_reset, section 11, its counts
- * against a recount from the split masks in this file), driven from a plain C program, meant to be built with the host
- * sanitizers:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/scf_host_check.c -o /tmp/scf_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/scf_host_check.o -o /tmp/scf_host_check
- *   /tmp/scf_host_check
+ * against a recount from the split masks in this file), driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched: every accumulator is created without a context.  Prints "scf_host_check: ok" and
  * returns 0 when every check held; a sanitizer report or a failed check ends it with a non-zero status. */

@@ -1,12 +1,6 @@
 /* species_quintet_host_check.c -- the host-only call of DESIGN.md section 23 (tq_pooled_quintet_site_classes: the pooled
- * five-taxon rule for one site, through the functions the kernel runs), driven from a plain C program, meant to be built
- * with the host sanitizers:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/species_quintet_host_check.c -o /tmp/sq_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/sq_host_check.o -o /tmp/sq_host_check
- *   /tmp/sq_host_check
+ * five-taxon rule for one site, through the functions the kernel runs), driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched: the call takes no context.  The five packed words and the sixteen slots are allocated at
  * their exact sizes, so a read or write past either shows as a sanitizer report.  The values are checked against an

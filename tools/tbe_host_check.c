@@ -1,12 +1,6 @@
 /* tbe_host_check.c -- the host back end of the transfer bootstrap accumulator (tq_tbe_* without a context, DESIGN.md
- * section 25), driven from a plain C program, meant to be built with the host sanitizers exactly as
- * tools/nni_host_check.c is:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/tbe_host_check.c -o /tmp/tbe_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/tbe_host_check.o -o /tmp/tbe_host_check
- *   /tmp/tbe_host_check
+ * section 25), driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched.  Every phi is recounted here from taxon lists: the taxa below every node of the
  * replicate as bytes, the distance to a branch as a loop over the taxa, the minimum over every edge, tip edges included.

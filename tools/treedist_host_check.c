@@ -1,12 +1,6 @@
 /* treedist_host_check.c -- the host back end of the tree distance accumulator (tq_rf_* without a context, DESIGN.md
- * section 26), driven from a plain C program, meant to be built with the host sanitizers exactly as
- * tools/tbe_host_check.c is:
- *
- *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Wno-inline-asm -Xarch_host -fsanitize=address,undefined \
- *         -c tetrad_amd/csrc/tetrad_hip.hip -o /tmp/tetrad_hip_san.o
- *   clang -O1 -g -fsanitize=address,undefined -Iinclude -c tools/treedist_host_check.c -o /tmp/treedist_host_check.o
- *   hipcc -fsanitize=address,undefined /tmp/tetrad_hip_san.o /tmp/treedist_host_check.o -o /tmp/treedist_host_check
- *   /tmp/treedist_host_check
+ * section 26), driven from a plain C program.
+ * Built and run under the host sanitizers by tools/host_checks.sh.
  *
  * No device is needed or touched.  Every count is recounted here from taxon lists: the taxa below every node as bytes,
  * named by the side without taxon 0; two trees share a split when some node of each has the same bytes.
