@@ -679,6 +679,49 @@ int tq_qd_stats(tq_qd *acc, int64_t *out);
 void tq_qd_word_counts(uint64_t x0, uint64_t x1, uint64_t x2, uint64_t y0, uint64_t y1, uint64_t y2, uint32_t *same,
                        uint32_t *both);
 
+/* Quartet frequencies of a set of trees and the sums of the leaf stability index (Thorley &
+ * Wilkinson 1999, on quartets because the trees are unrooted): which taxa the trees disagree about.  Integers only; the
+ * host and the device execution return identical arrays.  No reference counterpart.
+ *   Trees, their limits and the code of a quartet in a tree are those of tq_qd above.  Over the N trees held, for a
+ *   quartet row (a, b, c, d) as given:
+ *   counts        u16[4] = (n_0, n_1, n_2, n_3): the trees with code 0 = ab|cd, 1 = ac|bd, 2 = ad|bc, and n_3 = N - n_0 -
+ *                 n_1 - n_2 unresolved.  A row sums to N.
+ *   top, second   the largest and the second largest of n_0..n_2 (equal when the largest is tied); dif = top - second,
+ *                 res = n_0 + n_1 + n_2.
+ *   acc[t][4]     u64 (quartets, res, top, dif): the sums over every scored row that holds taxon t; a row given twice
+ *                 counts twice.  The order of the taxa inside a row permutes n_0..n_2 and moves nothing of acc.  No result
+ *                 depends on the launch shape, the chunking of quartets, streams or the order of score calls.
+ *   tq_ls_create  limits, refusals and back ends as tq_qd_create.  With a context everything is allocated here: tables and
+ *                 parent records as tq_qd_create, acc, and one chunk of quartets within "qdist_scratch_bytes" -- per
+ *                 quartet what tq_qd_create takes plus a counts row of 8 bytes on the device and 8 page-locked.  A failed
+ *                 allocation is TQ_ERR_OOM / TQ_ERR_HIP with a message and frees everything.
+ *   tq_ls_add     as tq_qd_add, under its own name.  Refused once anything has been scored, until a clear or reset: N is
+ *                 the denominator of every scored row.
+ *   tq_ls_score   quartets i32[Q][4], checked as tq_qd_score checks them; repeated rows are allowed.  `counts` u16[Q][4] or
+ *                 NULL.  Device back end: chunk by chunk on `stream` tq_qd_encode_kernel writes the planes and
+ *                 tq_ls_count_kernel sums them along the trees.  With counts NULL the call returns with the last chunk
+ *                 in flight; with an array the rows come back chunk by chunk through the page-locked staging and the call
+ *                 returns once the array is filled.
+ *   tq_ls_score_ranks  ranks u64[Q], or NULL for the Q consecutive ranks from first_rank; checked as tq_qd_score_ranks.
+ *                 Q = 0 and an accumulator without trees are valid no-ops of both score calls: counts is not written.
+ *   tq_ls_clear   zeroes acc and the quartet total and keeps the trees.   tq_ls_reset  forgets everything.  Both wait.
+ *   tq_ls_shape   T, trees held, quartet rows scored since create / clear / reset (any may be NULL).
+ *   tq_ls_read    out u64[T][4]; waits.  May be called between score calls.
+ *   tq_ls_stats   out i64[7] = {quartets per chunk, quartet chunks launched since create / reset, tree tables built since
+ *                 create / reset, table form (0 host, 1 LDS, 2 through L2), plane words per chunk, workgroups of the last
+ *                 count launch (0 on the host), trees per staged tile of tq_ls_count_kernel}.  */
+typedef struct tq_ls tq_ls;
+int tq_ls_create(tq_ls **out, int64_t T, int64_t max_trees, tq_ctx *ctx);
+void tq_ls_destroy(tq_ls *acc);
+int tq_ls_reset(tq_ls *acc);
+int tq_ls_clear(tq_ls *acc);
+int tq_ls_add(tq_ls *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream);
+int tq_ls_score(tq_ls *acc, const int32_t *quartets, int64_t Q, uint16_t *counts, void *stream);
+int tq_ls_score_ranks(tq_ls *acc, const uint64_t *ranks, uint64_t first_rank, int64_t Q, uint16_t *counts, void *stream);
+int tq_ls_shape(tq_ls *acc, int64_t *T, int64_t *ntrees, uint64_t *q_total);
+int tq_ls_read(tq_ls *acc, uint64_t *out);
+int tq_ls_stats(tq_ls *acc, int64_t *out);
+
 /* Species-tree mode: quartets of SPECIES resolved from pooled lineages, as SVDquartets' species
  * mode does.  No reference counterpart: the reference only plans a sample-to-clade table (`imap`, schema.py:50-51,
  * cli.py:8, parsed at write_database.py:198-201) and would use it to select samples.

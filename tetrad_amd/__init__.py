@@ -8,7 +8,8 @@ over the GPUs of a node), ``replicates`` (bootstrap-replicate loop), ``bootstrap
 (quartet concordance on a fixed tree), ``consensus`` (split counts over many trees, majority-rule consensus),
 ``scf`` (site concordance factors per branch of a fixed tree), ``tbe`` (transfer bootstrap supports of a tree's
 branches over replicate trees), ``treedist`` (all-pairs Robinson-Foulds distances of a set of trees),
-``qdist`` (all-pairs quartet distances of a set of trees).
+``qdist`` (all-pairs quartet distances of a set of trees), ``stability`` (quartet frequencies of a set of trees and the
+leaf stability of its taxa).
 Importing the package does not load the HIP library; the first compute call does, and fails loudly if it is missing.
 """
 __version__ = "0.2.0"
@@ -17,7 +18,8 @@ _SCF_EXPORTS = ("SiteConcordance", "sample_edge_quartets", "run_scf")
 _TBE_EXPORTS = ("TransferSupport", "transfer_supports")
 _TREEDIST_EXPORTS = ("TreeDistances", "rf_matrix")
 _QDIST_EXPORTS = ("QuartetDistances", "quartet_distance_matrix")
-__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS + _TREEDIST_EXPORTS + _QDIST_EXPORTS)
+_STABILITY_EXPORTS = ("LeafStability", "quartet_frequencies", "dominant_splits")
+__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS + _TREEDIST_EXPORTS + _QDIST_EXPORTS + _STABILITY_EXPORTS)
 
 
 def __getattr__(name):
@@ -34,4 +36,7 @@ def __getattr__(name):
     if name in _QDIST_EXPORTS:
         from . import qdist
         return getattr(qdist, name)
+    if name in _STABILITY_EXPORTS:
+        from . import stability
+        return getattr(stability, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -139,6 +139,17 @@ PROTOTYPES = {
     "tq_qd_read": _sig(vp, vp, vp),
     "tq_qd_stats": _sig(vp, vp),
     "tq_qd_word_counts": _sig(u64, u64, u64, u64, u64, u64, P(u32), P(u32), ret=None),
+    # -- quartet frequencies and leaf stability
+    "tq_ls_create": _sig(P(vp), i64, i64, vp),
+    "tq_ls_destroy": _sig(vp, ret=None),
+    "tq_ls_reset": _sig(vp),
+    "tq_ls_clear": _sig(vp),
+    "tq_ls_add": _sig(vp, vp, vp, i64, i64, vp),
+    "tq_ls_score": _sig(vp, vp, i64, vp, vp),
+    "tq_ls_score_ranks": _sig(vp, vp, u64, i64, vp, vp),
+    "tq_ls_shape": _sig(vp, P(i64), P(i64), P(u64)),
+    "tq_ls_read": _sig(vp, vp),
+    "tq_ls_stats": _sig(vp, vp),
     # -- species mode
     "tq_set_species": _sig(vp, vp, i64, i64),
     "tq_resolve_species": _sig(vp, vp, i64, vp, vp, vp),

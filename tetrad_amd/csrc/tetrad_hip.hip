@@ -44,6 +44,7 @@
 //   tbe.hpp       tq_tbe_kernel: transfer distances of a reference tree's branches to every node of many trees (TBE)
 //   treedist.hpp  tq_rf_*_kernel: split ids, bit rows and their product: all-pairs Robinson-Foulds distances of a tree set
 //   qdist.hpp     tq_qd_*_kernel: quartet topology planes of every tree and their product: all-pairs quartet distances of a tree set
+//   stability.hpp tq_ls_count_kernel: the same planes summed along the trees: quartet frequencies and leaf stability sums
 //   species.hpp   tq_species_table_kernel / tq_species_allele_table_kernel (base counts per species from the resident
 //                 rows / from both alleles of the IUPAC source) + tq_species_mfma_kernel / tq_species_pool_kernel: pooled
 //                 count matrices of species quartets (species mode; MFMA form, VALU form)
@@ -121,6 +122,7 @@ namespace {
 #include "treedist.hpp"
 #include "fit.hpp"
 #include "qdist.hpp"
+#include "stability.hpp"
 #include "nni.hpp"
 #include "patterns.hpp"
 #include "pattern_blocks.hpp"
@@ -2223,38 +2225,297 @@ int rf_final(tq_rf *a, const char *who)
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
-// Quartet distance accumulator (qdist.hpp).  Both back ends keep the depth table of every tree added and two u64
-// matrices; a score call walks its quartets a chunk at a time: the planes of every tree, then their product.
+// Accumulators over the quartet planes of a tree set: quartet distances (qdist.hpp) and leaf stability (stability.hpp).
+// Both back ends keep the depth table of every tree added; a score call walks its quartets a chunk at a time: the planes
+// of every tree, then their product (two u64 matrices) or their sums along the trees (counts rows and per-taxon sums).
 // ---------------------------------------------------------------------------------------------
-struct tq_qd {
+namespace {
+
+// What QuartetPlanes::add and tq_stree_fit share (fit.hpp).  pars[r] = the prepared parent array of tree r: every tree is
+// validated before anything is written.
+int prepare_fit_trees(tq_ctx *ctx, const char *who, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride,
+                      int64_t T, std::vector<std::vector<int32_t>> &pars)
+{
+    pars.assign((size_t)R, {});
+    std::vector<std::vector<int32_t>> nch;
+    for (int64_t r = 0; r < R; ++r) {
+        if (n_nodes[r] > stride)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: n_nodes exceeds the stride", who, (long long)r);
+        const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
+        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: %s", who, (long long)r, err.c_str());
+        if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: internal error: a prepared tree of T taxa has "
+                        "at most 2 T - 2 nodes", who, (long long)r);
+    }
+    return TQ_OK;
+}
+
+// the records tq_fit_table_kernel reads, S = 2 T words a tree: the prepared parents, zeros, the node count in the last word
+void fit_stage_records(int32_t *rec0, const std::vector<std::vector<int32_t>> &pars, int64_t S)
+{
+    memset(rec0, 0, pars.size() * (size_t)S * 4);
+    for (size_t r = 0; r < pars.size(); ++r) {
+        memcpy(rec0 + r * S, pars[r].data(), pars[r].size() * 4);
+        rec0[r * S + S - 1] = (int32_t)pars[r].size();
+    }
+}
+
+// the grid of tq_fit_table_kernel in x (its y: the trees)
+unsigned fit_table_blocks(int64_t T)
+{
+    const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
+}
+
+// What the accumulators over the quartet planes of a tree set share (quartet distances, qdist.hpp; leaf stability,
+// stability.hpp): the depth table of every tree added with the add path, one chunk of quartets with its page-locked
+// staging, and the walk of a score call, chunk by chunk: unrank where ranks come in, the planes of every tree, then
+// whatever the owner does with the planes.
+struct QuartetPlanes {
     tq_ctx *ctx = nullptr;          // NULL: host back end; messages go to tq_last_error(ctx)
     int32_t T = 0;
     int64_t max_trees = 0, ntrees = 0;
     uint64_t q_total = 0;           // quartets scored since create / clear / reset
     bool scored = false;            // adds are refused until a clear or reset
     int64_t chunk_words = 0;        // plane words (of 64 quartets) of one chunk
-    int64_t chunks = 0, kslices = 0, tables = 0;
+    int64_t chunks = 0, tables = 0;
     // host back end
     std::vector<uint16_t> h_tab;    // [ntrees][T][T]
-    std::vector<uint64_t> h_same, h_both;   // [ntrees][ntrees] once something has been scored
     // device back end
     int num_cu = 1;
     DevBuf<uint16_t> d_tab;         // [max_trees][T][T]
     DevBuf<int32_t> d_rec;          // [max_trees][2 T]: the prepared parents, as tq_fit_table_kernel reads them
     PinnedBuf<int32_t> p_rec;
-    DevBuf<unsigned long long> d_same, d_both;      // [max_trees^2], row pitch = ntrees
     DevBuf<uint32_t> d_quart;       // [64 chunk_words][4]
     DevBuf<uint64_t> d_ranks, d_planes;     // [64 chunk_words], [max_trees][3][chunk_words]
     PinnedBuf<uint64_t> p_stage;    // 16 bytes per quartet of a chunk: its taxa or its rank on the way to the device
     StreamOrder copy;               // behind the last copy out of p_stage
     StreamOrder order;              // behind the last add / score
-    tq_qd() = default;
-    tq_qd(const tq_qd &) = delete;
-    ~tq_qd()
+    QuartetPlanes() = default;
+    QuartetPlanes(const QuartetPlanes &) = delete;
+    ~QuartetPlanes() { finish(); }
+    // the owner calls this in its destructor's body, ahead of its own buffers
+    void finish()
     {
         order.finish(ctx);
         copy.finish(ctx);
     }
+    int table_form() const { return !ctx ? 0 : T <= FIT_T_LDS ? 1 : 2; }
+
+    // The limits, and with a context every allocation but the owner's.  `own_per_word`: the bytes per plane word of a
+    // chunk the owner allocates on top.
+    int create(const char *who, int64_t T_, int64_t max_trees_, tq_ctx *ctx_, int64_t own_per_word)
+    {
+        if (T_ < 4 || T_ > STREE_T_MAX) return fail(ctx_, TQ_ERR_INVALID_ARG, "%s: T must be 4..%d", who, STREE_T_MAX);
+        if (max_trees_ < 1 || max_trees_ > QD_MAX_TREES)
+            return fail(ctx_, TQ_ERR_INVALID_ARG, "%s: max_trees must be 1..%lld", who, (long long)QD_MAX_TREES);
+        ctx = ctx_;
+        T = (int32_t)T_;
+        max_trees = max_trees_;
+        chunk_words = QD_HOST_CHUNK_WORDS;
+        if (!ctx) return TQ_OK;
+        // per plane word of a chunk: 64 quartets as taxa and as ranks on the device, 16 page-locked bytes each, and
+        // three plane words of every tree
+        const int64_t per_word = 64 * (16 + 8 + 16) + max_trees * 3 * 8 + own_per_word;
+        chunk_words = std::max<int64_t>(1, std::min<int64_t>(ctx->opt.qdist_scratch_bytes / per_word, QD_MAX_CHUNK_WORDS));
+        num_cu = std::max(1, ctx->prop.multiProcessorCount);
+        const size_t cq = (size_t)chunk_words * 64;
+        TQ_HIPF(ctx, who, d_tab.alloc((size_t)max_trees * T * T));
+        TQ_HIPF(ctx, who, d_rec.alloc((size_t)max_trees * 2 * T));
+        TQ_HIPF(ctx, who, p_rec.alloc((size_t)max_trees * 2 * T));
+        TQ_HIPF(ctx, who, d_quart.alloc(cq * 4));
+        TQ_HIPF(ctx, who, d_ranks.alloc(cq));
+        TQ_HIPF(ctx, who, d_planes.alloc((size_t)max_trees * 3 * chunk_words));
+        TQ_HIPF(ctx, who, p_stage.alloc(cq * 2));
+        TQ_HIPF(ctx, who, order.create());
+        TQ_HIPF(ctx, who, copy.create());
+        return TQ_OK;
+    }
+
+    // Every tree is validated first; the tables of the new trees are built and kept.
+    int add(const char *who, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, hipStream_t st)
+    {
+        if (int rc = tree_set_args(ctx, who, parents, n_nodes, R, stride)) return rc;
+        if (R == 0) return TQ_OK;
+        if (scored) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: quartets have been scored; clear or reset the accumulator first", who);
+        if (ntrees + R > max_trees)
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: %lld trees held and %lld offered exceed max_trees = %lld", who,
+                        (long long)ntrees, (long long)R, (long long)max_trees);
+        const int64_t T64 = T;
+        std::vector<std::vector<int32_t>> pars;
+        if (int rc = prepare_fit_trees(ctx, who, parents, n_nodes, R, stride, T64, pars)) return rc;
+        if (!ctx) {
+            h_tab.resize((size_t)((ntrees + R) * T64 * T64));
+            std::vector<uint32_t> dep;
+            for (int64_t r = 0; r < R; ++r)
+                fit_host_table(pars[(size_t)r], (uint32_t)T64, dep, &h_tab[(size_t)((ntrees + r) * T64 * T64)]);
+            ntrees += R;
+            tables += R;
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, order.join(st));
+        const int64_t S = 2 * T64, first = ntrees;
+        int32_t *rec0 = p_rec + first * S;                          // every tree has a record of its own: none is reused
+        fit_stage_records(rec0, pars, S);
+        TQ_HIP(ctx, hipMemcpyAsync(d_rec + first * S, rec0, (size_t)(R * S) * 4, hipMemcpyHostToDevice, st));
+        FitTableArgs ta{d_rec + first * S, d_tab + first * T64 * T64, (uint32_t)T64};
+        hipLaunchKernelGGL(tq_fit_table_kernel, dim3(fit_table_blocks(T64), (unsigned)R), dim3(FIT_THREADS), 0, st, ta);
+        TQ_LAUNCHED(ctx, who);
+        TQ_HIP(ctx, order.mark(st));
+        ntrees += R;
+        tables += R;
+        return TQ_OK;
+    }
+
+    // quartets i32 [Q][4]: every one is validated before anything is scored
+    int check_quartets(const char *who, const int32_t *quartets, int64_t Q) const
+    {
+        if (Q < 0 || (Q > 0 && !quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer or negative Q", who);
+        for (int64_t i = 0; i < Q; ++i) {
+            const int32_t *q = quartets + 4 * i;
+            if (q[0] < 0 || q[0] >= T || q[1] < 0 || q[1] >= T || q[2] < 0 || q[2] >= T || q[3] < 0 || q[3] >= T)
+                return fail(ctx, TQ_ERR_INVALID_ARG, "%s: quartet %lld: taxon out of range 0..%d", who, (long long)i, T - 1);
+            if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
+                return fail(ctx, TQ_ERR_INVALID_ARG, "%s: quartet %lld: repeated taxon", who, (long long)i);
+        }
+        return TQ_OK;
+    }
+
+    // ranks u64 [Q], or NULL for the Q consecutive ranks from first_rank
+    int check_ranks(const char *who, const uint64_t *ranks, uint64_t first_rank, int64_t Q) const
+    {
+        if (Q < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: negative Q", who);
+        const uint64_t total = choose4((uint64_t)T);
+        if (ranks) {
+            for (int64_t i = 0; i < Q; ++i)
+                if (ranks[i] >= total)
+                    return fail(ctx, TQ_ERR_INVALID_ARG, "%s: rank %lld: %llu is not below C(%d,4) = %llu", who, (long long)i,
+                                (unsigned long long)ranks[i], T, (unsigned long long)total);
+        } else if (Q > 0 && (first_rank > total || (uint64_t)Q > total - first_rank)) {
+            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: rank range [%llu,+%lld) exceeds C(%d,4) = %llu", who,
+                        (unsigned long long)first_rank, (long long)Q, T, (unsigned long long)total);
+        }
+        return TQ_OK;
+    }
+
+    // One score call: explicit quartets (`quartets`), explicit ranks (`ranks`) or the range from first_rank (both NULL).
+    // Everything has been validated.  Per chunk of n quartets that begins at quartet q0 of the call, behind the planes:
+    //   host back end   host(planes u64 [N][3][cw], cw, taxa u32 [n][4], n, q0)
+    //   device          dev(n, q0) -> a return code: what it enqueues on `st` finds the taxa in d_quart and the planes in
+    //                   d_planes ([N][3][(n + 63) / 64])
+    template <class Host, class Dev>
+    int score(const int32_t *quartets, const uint64_t *ranks, uint64_t first_rank, int64_t Q, hipStream_t st, const char *who,
+              Host &&host, Dev &&dev)
+    {
+        if (Q == 0 || ntrees == 0) return TQ_OK;
+        const int64_t N = ntrees;
+        if (!ctx) {
+            const int64_t per = QD_HOST_CHUNK_WORDS * 64, piece = per * 16;     // unranked a piece at a time
+            std::vector<uint32_t> q;
+            std::vector<uint64_t> planes;
+            for (int64_t p0 = 0; p0 < Q; p0 += piece) {
+                const int64_t np = std::min(piece, Q - p0);
+                const uint32_t *src = quartets ? (const uint32_t *)quartets + 4 * p0 : nullptr;
+                if (!quartets) {
+                    q.resize((size_t)np * 4);
+                    unrank_host(ranks ? ranks + p0 : nullptr, first_rank + (uint64_t)p0, np, T, q.data());
+                    src = q.data();
+                }
+                for (int64_t q0 = 0; q0 < np; q0 += per) {
+                    const int64_t nq = std::min(per, np - q0), cw = (nq + 63) / 64;
+                    planes.resize((size_t)(N * 3 * cw));
+                    for (int64_t t = 0; t < N; ++t)
+                        qd_host_encode(&h_tab[(size_t)(t * T * T)], (uint32_t)T, src + 4 * q0, nq, cw, &planes[(size_t)(t * 3 * cw)]);
+                    host(planes.data(), cw, src + 4 * q0, nq, p0 + q0);
+                    ++chunks;
+                }
+                scored = true;
+            }
+            q_total += (uint64_t)Q;
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, order.join(st));
+        const int64_t per = chunk_words * 64;
+        for (int64_t q0 = 0; q0 < Q; q0 += per) {
+            const int64_t n = std::min(per, Q - q0);
+            if (quartets || ranks) {
+                TQ_HIP(ctx, copy.sync());                               // the staging buffer is free again
+                if (quartets) {
+                    memcpy(p_stage, quartets + 4 * q0, (size_t)n * 16);
+                    TQ_HIP(ctx, hipMemcpyAsync(d_quart, p_stage, (size_t)n * 16, hipMemcpyHostToDevice, st));
+                } else {
+                    memcpy(p_stage, ranks + q0, (size_t)n * 8);
+                    TQ_HIP(ctx, hipMemcpyAsync(d_ranks, p_stage, (size_t)n * 8, hipMemcpyHostToDevice, st));
+                }
+                TQ_HIP(ctx, copy.mark(st));
+            }
+            if (!quartets) {
+                hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                                   ranks ? (const uint64_t *)d_ranks.get() : (const uint64_t *)nullptr,
+                                   first_rank + (uint64_t)q0, n, T, d_quart.get());
+                TQ_LAUNCHED(ctx, who);
+            }
+            scored = true;                                              // from here on the results hold part of the call
+            const int64_t cw = (n + 63) / 64;
+            QdEncodeArgs e{(const uint4 *)d_quart.get(), d_tab, d_planes, n, (int32_t)cw, (uint32_t)T};
+            const unsigned slices = (unsigned)std::max<int64_t>(
+                1, std::min<int64_t>((cw + QD_ENC_WORDS_PER_BLOCK - 1) / QD_ENC_WORDS_PER_BLOCK, 4096));
+            if (T <= FIT_T_LDS)
+                hipLaunchKernelGGL(tq_qd_encode_kernel<true>, dim3(slices, (unsigned)N), dim3(QD_THREADS), 0, st, e);
+            else
+                hipLaunchKernelGGL(tq_qd_encode_kernel<false>, dim3(slices, (unsigned)N), dim3(QD_THREADS), 0, st, e);
+            TQ_LAUNCHED(ctx, who);
+            if (int rc = dev(n, q0)) return rc;
+            ++chunks;
+            TQ_HIP(ctx, order.mark(st));
+        }
+        q_total += (uint64_t)Q;
+        return TQ_OK;
+    }
+
+    // before the owner zeroes its results: the device is idle
+    int quiesce()
+    {
+        if (!ctx) return TQ_OK;
+        TQ_HIP(ctx, order.sync());
+        TQ_HIP(ctx, copy.sync());
+        return TQ_OK;
+    }
+    void forget_scores() { q_total = 0; scored = false; }
+    void forget_trees()
+    {
+        h_tab.clear();
+        ntrees = 0;
+        chunks = tables = 0;
+    }
+};
+
+}  // namespace
+
+struct tq_qd {
+    QuartetPlanes set;
+    int64_t kslices = 0;
+    std::vector<uint64_t> h_same, h_both;   // host back end: [ntrees][ntrees] once something has been scored
+    DevBuf<unsigned long long> d_same, d_both;      // device back end: [max_trees^2], row pitch = ntrees
+    tq_qd() = default;
+    tq_qd(const tq_qd &) = delete;
+    ~tq_qd() { set.finish(); }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Leaf stability accumulator (stability.hpp).  The trees, the chunk and the walk are a QuartetPlanes; behind the planes of
+// a chunk the counts of every quartet along the trees, and the u64 sums per taxon.
+// ---------------------------------------------------------------------------------------------
+struct tq_ls {
+    QuartetPlanes set;
+    int64_t groups = 0;             // workgroups of the last count launch (0 on the host)
+    std::vector<uint64_t> h_acc;    // host back end: [T][4]
+    DevBuf<unsigned long long> d_acc;       // [T][4]
+    DevBuf<uint2> d_counts;         // [64 chunk_words] rows of u16 x 4
+    PinnedBuf<uint2> p_counts;
+    tq_ls() = default;
+    tq_ls(const tq_ls &) = delete;
+    ~tq_ls() { set.finish(); }
 };
 
 namespace {
@@ -2271,120 +2532,100 @@ int64_t qd_kslices(int64_t cw, int64_t nt, int num_cu, int want, int64_t *slices
     return per * BT_KW;
 }
 
-// planes and product of the nq quartets in d_quart, on `st`
-int qd_launch(tq_qd *a, int64_t nq, hipStream_t st, const char *who)
+// the product of the planes of the nq quartets of a chunk, on `st`
+int qd_product(tq_qd *a, int64_t nq, hipStream_t st, const char *who)
 {
-    tq_ctx *ctx = a->ctx;
-    const int64_t N = a->ntrees, cw = (nq + 63) / 64, nt = (N + QD_BT - 1) / QD_BT;
-    QdEncodeArgs e{(const uint4 *)a->d_quart.get(), a->d_tab, a->d_planes, nq, (int32_t)cw, (uint32_t)a->T};
-    const unsigned slices = (unsigned)std::max<int64_t>(
-        1, std::min<int64_t>((cw + QD_ENC_WORDS_PER_BLOCK - 1) / QD_ENC_WORDS_PER_BLOCK, 4096));
-    if (a->T <= FIT_T_LDS)
-        hipLaunchKernelGGL(tq_qd_encode_kernel<true>, dim3(slices, (unsigned)N), dim3(QD_THREADS), 0, st, e);
-    else
-        hipLaunchKernelGGL(tq_qd_encode_kernel<false>, dim3(slices, (unsigned)N), dim3(QD_THREADS), 0, st, e);
+    tq_ctx *ctx = a->set.ctx;
+    const int64_t N = a->set.ntrees, cw = (nq + 63) / 64, nt = (N + QD_BT - 1) / QD_BT;
     QdGemmArgs g{};
-    g.planes = a->d_planes; g.same = a->d_same; g.both = a->d_both;
+    g.planes = a->set.d_planes; g.same = a->d_same; g.both = a->d_both;
     g.N = (int32_t)N; g.cw = (int32_t)cw; g.nt = (int32_t)nt;
     int64_t ks = 1;
-    g.slice_words = (int32_t)qd_kslices(cw, nt, a->num_cu, ctx->opt.qdist_kslices, &ks);
+    g.slice_words = (int32_t)qd_kslices(cw, nt, a->set.num_cu, ctx->opt.qdist_kslices, &ks);
     g.atomic = ks > 1;
     hipLaunchKernelGGL(tq_qd_gemm_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)ks), dim3(QD_THREADS), 0, st, g);
     TQ_LAUNCHED(ctx, who);
     a->kslices = ks;
-    ++a->chunks;
     return TQ_OK;
 }
 
-// Host back end: the quartets q[Q][4] against every table
-void qd_host_score(tq_qd *a, const uint32_t *q, int64_t Q)
-{
-    const int64_t N = a->ntrees, T = a->T, per = QD_HOST_CHUNK_WORDS * 64;
-    if (!a->scored) {
-        a->h_same.assign((size_t)(N * N), 0);
-        a->h_both.assign((size_t)(N * N), 0);
-    }
-    std::vector<uint64_t> planes;
-    for (int64_t q0 = 0; q0 < Q; q0 += per) {
-        const int64_t nq = std::min(per, Q - q0), cw = (nq + 63) / 64;
-        planes.resize((size_t)(N * 3 * cw));
-        for (int64_t t = 0; t < N; ++t)
-            qd_host_encode(&a->h_tab[(size_t)(t * T * T)], (uint32_t)T, q + 4 * q0, nq, cw, &planes[(size_t)(t * 3 * cw)]);
-        qd_host_product(planes.data(), N, cw, a->h_same.data(), a->h_both.data());
-        ++a->chunks;
-    }
-}
-
-// One score call: explicit quartets (`quartets`), explicit ranks (`ranks`) or the range from first_rank (both NULL).
-// Everything has been validated.
+// One score call of the quartet distances; everything has been validated
 int qd_score(tq_qd *a, const int32_t *quartets, const uint64_t *ranks, uint64_t first_rank, int64_t Q, hipStream_t st,
              const char *who)
 {
-    tq_ctx *ctx = a->ctx;
-    if (Q == 0 || a->ntrees == 0) return TQ_OK;
-    if (!ctx) {
-        const int64_t per = QD_HOST_CHUNK_WORDS * 64 * 16;          // unranked a piece at a time
-        std::vector<uint32_t> q;
-        for (int64_t q0 = 0; q0 < Q; q0 += per) {
-            const int64_t n = std::min(per, Q - q0);
-            const uint32_t *src = quartets ? (const uint32_t *)quartets + 4 * q0 : nullptr;
-            if (!quartets) {
-                q.resize((size_t)n * 4);
-                unrank_host(ranks ? ranks + q0 : nullptr, first_rank + (uint64_t)q0, n, a->T, q.data());
-                src = q.data();
+    const int64_t N = a->set.ntrees;
+    return a->set.score(
+        quartets, ranks, first_rank, Q, st, who,
+        [&](const uint64_t *planes, int64_t cw, const uint32_t *, int64_t, int64_t) {
+            if (a->h_same.empty()) {
+                a->h_same.assign((size_t)(N * N), 0);
+                a->h_both.assign((size_t)(N * N), 0);
             }
-            qd_host_score(a, src, n);
-            a->scored = true;
-        }
-        a->q_total += (uint64_t)Q;
-        return TQ_OK;
-    }
-    TQ_HIP(ctx, a->order.join(st));
-    const int64_t per = a->chunk_words * 64;
-    for (int64_t q0 = 0; q0 < Q; q0 += per) {
-        const int64_t n = std::min(per, Q - q0);
-        if (quartets || ranks) {
-            TQ_HIP(ctx, a->copy.sync());                            // the staging buffer is free again
-            if (quartets) {
-                memcpy(a->p_stage, quartets + 4 * q0, (size_t)n * 16);
-                TQ_HIP(ctx, hipMemcpyAsync(a->d_quart, a->p_stage, (size_t)n * 16, hipMemcpyHostToDevice, st));
-            } else {
-                memcpy(a->p_stage, ranks + q0, (size_t)n * 8);
-                TQ_HIP(ctx, hipMemcpyAsync(a->d_ranks, a->p_stage, (size_t)n * 8, hipMemcpyHostToDevice, st));
-            }
-            TQ_HIP(ctx, a->copy.mark(st));
-        }
-        if (!quartets) {
-            hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                               ranks ? (const uint64_t *)a->d_ranks.get() : (const uint64_t *)nullptr,
-                               first_rank + (uint64_t)q0, n, a->T, a->d_quart.get());
-            TQ_LAUNCHED(ctx, who);
-        }
-        a->scored = true;                                           // from here on the matrices hold part of the call
-        if (int rc = qd_launch(a, n, st, who)) return rc;
-        TQ_HIP(ctx, a->order.mark(st));
-    }
-    a->q_total += (uint64_t)Q;
-    return TQ_OK;
+            qd_host_product(planes, N, cw, a->h_same.data(), a->h_both.data());
+        },
+        [&](int64_t n, int64_t) { return qd_product(a, n, st, who); });
 }
 
 // zero counts (device: the part of the matrices that N trees use; the rest has not been written since create)
 int qd_zero(tq_qd *a)
 {
-    if (a->ctx) {
-        TQ_HIP(a->ctx, a->order.sync());
-        TQ_HIP(a->ctx, a->copy.sync());
-        const size_t n = (size_t)(a->ntrees * a->ntrees) * 8;
-        if (n && a->scored) {
-            TQ_HIP(a->ctx, hipMemset(a->d_same, 0, n));
-            TQ_HIP(a->ctx, hipMemset(a->d_both, 0, n));
-            TQ_HIP(a->ctx, hipDeviceSynchronize());
+    tq_ctx *ctx = a->set.ctx;
+    if (int rc = a->set.quiesce()) return rc;
+    if (ctx) {
+        const size_t n = (size_t)(a->set.ntrees * a->set.ntrees) * 8;
+        if (n && a->set.scored) {
+            TQ_HIP(ctx, hipMemset(a->d_same, 0, n));
+            TQ_HIP(ctx, hipMemset(a->d_both, 0, n));
+            TQ_HIP(ctx, hipDeviceSynchronize());
         }
     }
     a->h_same.clear();
     a->h_both.clear();
-    a->q_total = 0;
-    a->scored = false;
+    a->set.forget_scores();
+    return TQ_OK;
+}
+
+// One score call of the leaf stability; everything has been validated.  With a counts array (u16 [Q][4]) the rows of a
+// chunk come back through the page-locked staging before the next chunk is enqueued.
+int ls_score(tq_ls *a, const int32_t *quartets, const uint64_t *ranks, uint64_t first_rank, int64_t Q, uint16_t *counts,
+             hipStream_t st, const char *who)
+{
+    QuartetPlanes &s = a->set;
+    tq_ctx *ctx = s.ctx;
+    const int64_t N = s.ntrees;
+    return s.score(
+        quartets, ranks, first_rank, Q, st, who,
+        [&](const uint64_t *planes, int64_t cw, const uint32_t *q, int64_t nq, int64_t q0) {
+            ls_host_count(planes, N, cw, q, nq, counts ? counts + 4 * q0 : nullptr, a->h_acc.data());
+        },
+        [&](int64_t n, int64_t q0) -> int {
+            LsCountArgs c{(const uint4 *)s.d_quart.get(), s.d_planes, counts ? a->d_counts.get() : nullptr, a->d_acc,
+                          n, (int32_t)((n + 63) / 64), (int32_t)N, (uint32_t)s.T};
+            const int64_t groups = (c.cw + LS_GROUP_WORDS - 1) / LS_GROUP_WORDS;
+            const size_t lds = (size_t)(LS_TILE_WORDS + 4 * s.T) * 8;
+            hipLaunchKernelGGL(tq_ls_count_kernel, dim3((unsigned)groups), dim3(LS_THREADS), lds, st, c);
+            TQ_LAUNCHED(ctx, who);
+            a->groups = groups;
+            if (counts) {
+                TQ_HIP(ctx, hipMemcpyAsync(a->p_counts, a->d_counts, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+                TQ_HIP(ctx, hipStreamSynchronize(st));
+                memcpy(counts + 4 * q0, a->p_counts, (size_t)n * 8);
+            }
+            return TQ_OK;
+        });
+}
+
+// zero sums; the trees stay
+int ls_zero(tq_ls *a)
+{
+    tq_ctx *ctx = a->set.ctx;
+    if (int rc = a->set.quiesce()) return rc;
+    if (ctx && a->set.scored) {
+        TQ_HIP(ctx, hipMemset(a->d_acc, 0, (size_t)a->set.T * 4 * 8));
+        TQ_HIP(ctx, hipDeviceSynchronize());
+    }
+    std::fill(a->h_acc.begin(), a->h_acc.end(), 0);
+    a->set.forget_scores();
     return TQ_OK;
 }
 
@@ -2652,42 +2893,6 @@ int nni_scan_once(tq_stree *acc, const NniTree &t, hipStream_t st, const char *w
     if (sum >> 64) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: the sum of k does not fit in 64 bits", who);
     w.assign(acc->p_nni_w.get(), acc->p_nni_w.get() + (size_t)E * 3);
     return TQ_OK;
-}
-
-// What tq_qd_add and tq_stree_fit share (fit.hpp).  pars[r] = the prepared parent array of tree r: every tree is validated
-// before anything is written.
-int prepare_fit_trees(tq_ctx *ctx, const char *who, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride,
-                      int64_t T, std::vector<std::vector<int32_t>> &pars)
-{
-    pars.assign((size_t)R, {});
-    std::vector<std::vector<int32_t>> nch;
-    for (int64_t r = 0; r < R; ++r) {
-        if (n_nodes[r] > stride)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: n_nodes exceeds the stride", who, (long long)r);
-        const std::string err = conc_prepare_tree(parents + r * stride, n_nodes[r], T, pars[(size_t)r], nch);
-        if (!err.empty()) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: %s", who, (long long)r, err.c_str());
-        if ((int64_t)pars[(size_t)r].size() > 2 * T - 2)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "%s: tree %lld: internal error: a prepared tree of T taxa has "
-                        "at most 2 T - 2 nodes", who, (long long)r);
-    }
-    return TQ_OK;
-}
-
-// the records tq_fit_table_kernel reads, S = 2 T words a tree: the prepared parents, zeros, the node count in the last word
-void fit_stage_records(int32_t *rec0, const std::vector<std::vector<int32_t>> &pars, int64_t S)
-{
-    memset(rec0, 0, pars.size() * (size_t)S * 4);
-    for (size_t r = 0; r < pars.size(); ++r) {
-        memcpy(rec0 + r * S, pars[r].data(), pars[r].size() * 4);
-        rec0[r * S + S - 1] = (int32_t)pars[r].size();
-    }
-}
-
-// the grid of tq_fit_table_kernel in x (its y: the trees)
-unsigned fit_table_blocks(int64_t T)
-{
-    const int64_t span = (int64_t)fit_pairs_span((uint32_t)T);
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((span + 4 * FIT_THREADS - 1) / (4 * FIT_THREADS), FIT_TABLE_BLOCKS));
 }
 
 // One row per option of tq_set_option (bdsqr_stats, which holds no value, aside): the field of Options, its legal values
@@ -5020,32 +5225,12 @@ int tq_qd_create(tq_qd **out, int64_t T, int64_t max_trees, tq_ctx *ctx)
     if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: out is NULL");
     *out = nullptr;
     return api(ctx, who, [&]() -> int {
-        if (T < 4 || T > STREE_T_MAX) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: T must be 4..%d", STREE_T_MAX);
-        if (max_trees < 1 || max_trees > QD_MAX_TREES)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_create: max_trees must be 1..%lld", (long long)QD_MAX_TREES);
         std::unique_ptr<tq_qd> a(new tq_qd());
-        a->ctx = ctx;
-        a->T = (int32_t)T;
-        a->max_trees = max_trees;
-        a->chunk_words = QD_HOST_CHUNK_WORDS;
+        if (int rc = a->set.create(who, T, max_trees, ctx, 0)) return rc;
         if (ctx) {
-            // per plane word of a chunk: 64 quartets as taxa and as ranks on the device, 16 page-locked bytes each, and
-            // three plane words of every tree
-            const int64_t per_word = 64 * (16 + 8 + 16) + max_trees * 3 * 8;
-            a->chunk_words = std::max<int64_t>(1, std::min<int64_t>(ctx->opt.qdist_scratch_bytes / per_word, QD_MAX_CHUNK_WORDS));
-            a->num_cu = std::max(1, ctx->prop.multiProcessorCount);
-            const size_t cq = (size_t)a->chunk_words * 64, mm = (size_t)(max_trees * max_trees);
-            TQ_HIPF(ctx, who, a->d_tab.alloc((size_t)max_trees * T * T));
-            TQ_HIPF(ctx, who, a->d_rec.alloc((size_t)max_trees * 2 * T));
-            TQ_HIPF(ctx, who, a->p_rec.alloc((size_t)max_trees * 2 * T));
+            const size_t mm = (size_t)(max_trees * max_trees);
             TQ_HIPF(ctx, who, a->d_same.alloc(mm));
             TQ_HIPF(ctx, who, a->d_both.alloc(mm));
-            TQ_HIPF(ctx, who, a->d_quart.alloc(cq * 4));
-            TQ_HIPF(ctx, who, a->d_ranks.alloc(cq));
-            TQ_HIPF(ctx, who, a->d_planes.alloc((size_t)max_trees * 3 * a->chunk_words));
-            TQ_HIPF(ctx, who, a->p_stage.alloc(cq * 2));
-            TQ_HIPF(ctx, who, a->order.create());
-            TQ_HIPF(ctx, who, a->copy.create());
             TQ_HIPF(ctx, who, hipMemset(a->d_same, 0, mm * 8));
             TQ_HIPF(ctx, who, hipMemset(a->d_both, 0, mm * 8));
             TQ_HIPF(ctx, who, hipDeviceSynchronize());
@@ -5060,17 +5245,16 @@ void tq_qd_destroy(tq_qd *acc) { delete acc; }
 int tq_qd_clear(tq_qd *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    return api(acc->ctx, "tq_qd_clear", [&]() -> int { return qd_zero(acc); });
+    return api(acc->set.ctx, "tq_qd_clear", [&]() -> int { return qd_zero(acc); });
 }
 
 int tq_qd_reset(tq_qd *acc)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    return api(acc->ctx, "tq_qd_reset", [&]() -> int {
+    return api(acc->set.ctx, "tq_qd_reset", [&]() -> int {
         if (int rc = qd_zero(acc)) return rc;
-        acc->h_tab.clear();
-        acc->ntrees = 0;
-        acc->chunks = acc->kslices = acc->tables = 0;
+        acc->set.forget_trees();
+        acc->kslices = 0;
         return TQ_OK;
     });
 }
@@ -5078,57 +5262,15 @@ int tq_qd_reset(tq_qd *acc)
 int tq_qd_add(tq_qd *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    tq_ctx *ctx = acc->ctx;
-    return api(ctx, "tq_qd_add", [&]() -> int {
-        if (int rc = tree_set_args(ctx, "tq_qd_add", parents, n_nodes, R, stride)) return rc;
-        if (R == 0) return TQ_OK;
-        if (acc->scored)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: quartets have been scored; clear or reset the accumulator first");
-        if (acc->ntrees + R > acc->max_trees)
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_add: %lld trees held and %lld offered exceed max_trees = %lld",
-                        (long long)acc->ntrees, (long long)R, (long long)acc->max_trees);
-        const int64_t T = acc->T;
-        std::vector<std::vector<int32_t>> pars;
-        if (int rc = prepare_fit_trees(ctx, "tq_qd_add", parents, n_nodes, R, stride, T, pars)) return rc;
-        if (!ctx) {
-            acc->h_tab.resize((size_t)((acc->ntrees + R) * T * T));
-            std::vector<uint32_t> dep;
-            for (int64_t r = 0; r < R; ++r)
-                fit_host_table(pars[(size_t)r], (uint32_t)T, dep, &acc->h_tab[(size_t)((acc->ntrees + r) * T * T)]);
-            acc->ntrees += R;
-            acc->tables += R;
-            return TQ_OK;
-        }
-        hipStream_t st = (hipStream_t)stream;
-        TQ_HIP(ctx, acc->order.join(st));
-        const int64_t S = 2 * T, first = acc->ntrees;
-        int32_t *rec0 = acc->p_rec + first * S;                     // every tree has a record of its own: none is reused
-        fit_stage_records(rec0, pars, S);
-        TQ_HIP(ctx, hipMemcpyAsync(acc->d_rec + first * S, rec0, (size_t)(R * S) * 4, hipMemcpyHostToDevice, st));
-        FitTableArgs ta{acc->d_rec + first * S, acc->d_tab + first * T * T, (uint32_t)T};
-        hipLaunchKernelGGL(tq_fit_table_kernel, dim3(fit_table_blocks(T), (unsigned)R), dim3(FIT_THREADS), 0, st, ta);
-        TQ_LAUNCHED(ctx, "tq_qd_add");
-        TQ_HIP(ctx, acc->order.mark(st));
-        acc->ntrees += R;
-        acc->tables += R;
-        return TQ_OK;
-    });
+    return api(acc->set.ctx, "tq_qd_add",
+               [&]() -> int { return acc->set.add("tq_qd_add", parents, n_nodes, R, stride, (hipStream_t)stream); });
 }
 
 int tq_qd_score(tq_qd *acc, const int32_t *quartets, int64_t Q, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    tq_ctx *ctx = acc->ctx;
-    return api(ctx, "tq_qd_score", [&]() -> int {
-        if (Q < 0 || (Q > 0 && !quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: NULL pointer or negative Q");
-        const int32_t T = acc->T;
-        for (int64_t i = 0; i < Q; ++i) {                               // every quartet is validated before anything is scored
-            const int32_t *q = quartets + 4 * i;
-            if (q[0] < 0 || q[0] >= T || q[1] < 0 || q[1] >= T || q[2] < 0 || q[2] >= T || q[3] < 0 || q[3] >= T)
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: taxon out of range 0..%d", (long long)i, T - 1);
-            if (q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3])
-                return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score: quartet %lld: repeated taxon", (long long)i);
-        }
+    return api(acc->set.ctx, "tq_qd_score", [&]() -> int {
+        if (int rc = acc->set.check_quartets("tq_qd_score", quartets, Q)) return rc;
         return qd_score(acc, quartets, nullptr, 0, Q, (hipStream_t)stream, "tq_qd_score");
     });
 }
@@ -5136,19 +5278,8 @@ int tq_qd_score(tq_qd *acc, const int32_t *quartets, int64_t Q, void *stream)
 int tq_qd_score_ranks(tq_qd *acc, const uint64_t *ranks, uint64_t first_rank, int64_t Q, void *stream)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    tq_ctx *ctx = acc->ctx;
-    return api(ctx, "tq_qd_score_ranks", [&]() -> int {
-        if (Q < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: negative Q");
-        const uint64_t total = choose4((uint64_t)acc->T);
-        if (ranks) {
-            for (int64_t i = 0; i < Q; ++i)
-                if (ranks[i] >= total)
-                    return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank %lld: %llu is not below C(%d,4) = %llu",
-                                (long long)i, (unsigned long long)ranks[i], acc->T, (unsigned long long)total);
-        } else if (Q > 0 && (first_rank > total || (uint64_t)Q > total - first_rank)) {
-            return fail(ctx, TQ_ERR_INVALID_ARG, "tq_qd_score_ranks: rank range [%llu,+%lld) exceeds C(%d,4) = %llu",
-                        (unsigned long long)first_rank, (long long)Q, acc->T, (unsigned long long)total);
-        }
+    return api(acc->set.ctx, "tq_qd_score_ranks", [&]() -> int {
+        if (int rc = acc->set.check_ranks("tq_qd_score_ranks", ranks, first_rank, Q)) return rc;
         return qd_score(acc, nullptr, ranks, ranks ? 0 : first_rank, Q, (hipStream_t)stream, "tq_qd_score_ranks");
     });
 }
@@ -5156,22 +5287,23 @@ int tq_qd_score_ranks(tq_qd *acc, const uint64_t *ranks, uint64_t first_rank, in
 int tq_qd_shape(tq_qd *acc, int64_t *T, int64_t *ntrees, uint64_t *q_total)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    if (T) *T = acc->T;
-    if (ntrees) *ntrees = acc->ntrees;
-    if (q_total) *q_total = acc->q_total;
+    if (T) *T = acc->set.T;
+    if (ntrees) *ntrees = acc->set.ntrees;
+    if (q_total) *q_total = acc->set.q_total;
     return TQ_OK;
 }
 
 int tq_qd_read(tq_qd *acc, uint64_t *same, uint64_t *both)
 {
     if (!acc) return TQ_ERR_INVALID_ARG;
-    tq_ctx *ctx = acc->ctx;
+    tq_ctx *ctx = acc->set.ctx;
     return api(ctx, "tq_qd_read", [&]() -> int {
-        const int64_t N = acc->ntrees;
+        QuartetPlanes &set = acc->set;
+        const int64_t N = set.ntrees;
         const size_t bytes = (size_t)(N * N) * 8;
         if (N == 0) return TQ_OK;
         if (!ctx) {
-            if (!acc->scored) {
+            if (!set.scored) {
                 if (same) memset(same, 0, bytes);
                 if (both) memset(both, 0, bytes);
                 return TQ_OK;
@@ -5180,14 +5312,14 @@ int tq_qd_read(tq_qd *acc, uint64_t *same, uint64_t *both)
             if (both) memcpy(both, acc->h_both.data(), bytes);
             return TQ_OK;
         }
-        hipStream_t st = acc->order.last;
-        if (acc->scored && N > QD_BT) {                                 // the tiles below the diagonal, behind the last score
+        hipStream_t st = set.order.last;
+        if (set.scored && N > QD_BT) {                                  // the tiles below the diagonal, behind the last score
             hipLaunchKernelGGL(tq_qd_final_kernel, dim3((unsigned)((N * N + QD_THREADS - 1) / QD_THREADS)), dim3(QD_THREADS), 0, st,
                                acc->d_same.get(), acc->d_both.get(), (int32_t)N);
             TQ_LAUNCHED(ctx, "tq_qd_read");
-            TQ_HIP(ctx, acc->order.mark(st));
+            TQ_HIP(ctx, set.order.mark(st));
         }
-        TQ_HIP(ctx, acc->order.sync());
+        TQ_HIP(ctx, set.order.sync());
         if (same) TQ_HIP(ctx, hipMemcpy(same, acc->d_same, bytes, hipMemcpyDeviceToHost));
         if (both) TQ_HIP(ctx, hipMemcpy(both, acc->d_both, bytes, hipMemcpyDeviceToHost));
         return TQ_OK;
@@ -5197,12 +5329,12 @@ int tq_qd_read(tq_qd *acc, uint64_t *same, uint64_t *both)
 int tq_qd_stats(tq_qd *acc, int64_t *out)
 {
     if (!acc || !out) return TQ_ERR_INVALID_ARG;
-    out[0] = acc->chunk_words * 64;
-    out[1] = acc->chunks;
+    out[0] = acc->set.chunk_words * 64;
+    out[1] = acc->set.chunks;
     out[2] = acc->kslices;
-    out[3] = acc->tables;
-    out[4] = !acc->ctx ? 0 : acc->T <= FIT_T_LDS ? 1 : 2;
-    out[5] = acc->chunk_words;
+    out[3] = acc->set.tables;
+    out[4] = acc->set.table_form();
+    out[5] = acc->set.chunk_words;
     return TQ_OK;
 }
 
@@ -5212,6 +5344,112 @@ void tq_qd_word_counts(uint64_t x0, uint64_t x1, uint64_t x2, uint64_t y0, uint6
     const QdCounts c = qd_word(x0, x1, x2, y0, y1, y2);
     if (same) *same = c.same;
     if (both) *both = c.both;
+}
+
+int tq_ls_create(tq_ls **out, int64_t T, int64_t max_trees, tq_ctx *ctx)
+{
+    const char *who = "tq_ls_create";
+    if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_ls_create: out is NULL");
+    *out = nullptr;
+    return api(ctx, who, [&]() -> int {
+        std::unique_ptr<tq_ls> a(new tq_ls());
+        // on top of the planes' chunk: a counts row of 8 bytes per quartet on the device and as many page-locked
+        if (int rc = a->set.create(who, T, max_trees, ctx, 64 * (8 + 8))) return rc;
+        if (!ctx) {
+            a->h_acc.assign((size_t)T * 4, 0);
+        } else {
+            const size_t cq = (size_t)a->set.chunk_words * 64;
+            TQ_HIPF(ctx, who, a->d_acc.alloc((size_t)T * 4));
+            TQ_HIPF(ctx, who, a->d_counts.alloc(cq));
+            TQ_HIPF(ctx, who, a->p_counts.alloc(cq));
+            TQ_HIPF(ctx, who, hipMemset(a->d_acc, 0, (size_t)T * 4 * 8));
+            TQ_HIPF(ctx, who, hipDeviceSynchronize());
+        }
+        *out = a.release();
+        return TQ_OK;
+    });
+}
+
+void tq_ls_destroy(tq_ls *acc) { delete acc; }
+
+int tq_ls_clear(tq_ls *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return api(acc->set.ctx, "tq_ls_clear", [&]() -> int { return ls_zero(acc); });
+}
+
+int tq_ls_reset(tq_ls *acc)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return api(acc->set.ctx, "tq_ls_reset", [&]() -> int {
+        if (int rc = ls_zero(acc)) return rc;
+        acc->set.forget_trees();
+        acc->groups = 0;
+        return TQ_OK;
+    });
+}
+
+int tq_ls_add(tq_ls *acc, const int32_t *parents, const int64_t *n_nodes, int64_t R, int64_t stride, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return api(acc->set.ctx, "tq_ls_add",
+               [&]() -> int { return acc->set.add("tq_ls_add", parents, n_nodes, R, stride, (hipStream_t)stream); });
+}
+
+int tq_ls_score(tq_ls *acc, const int32_t *quartets, int64_t Q, uint16_t *counts, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return api(acc->set.ctx, "tq_ls_score", [&]() -> int {
+        if (int rc = acc->set.check_quartets("tq_ls_score", quartets, Q)) return rc;
+        return ls_score(acc, quartets, nullptr, 0, Q, counts, (hipStream_t)stream, "tq_ls_score");
+    });
+}
+
+int tq_ls_score_ranks(tq_ls *acc, const uint64_t *ranks, uint64_t first_rank, int64_t Q, uint16_t *counts, void *stream)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    return api(acc->set.ctx, "tq_ls_score_ranks", [&]() -> int {
+        if (int rc = acc->set.check_ranks("tq_ls_score_ranks", ranks, first_rank, Q)) return rc;
+        return ls_score(acc, nullptr, ranks, ranks ? 0 : first_rank, Q, counts, (hipStream_t)stream, "tq_ls_score_ranks");
+    });
+}
+
+int tq_ls_shape(tq_ls *acc, int64_t *T, int64_t *ntrees, uint64_t *q_total)
+{
+    if (!acc) return TQ_ERR_INVALID_ARG;
+    if (T) *T = acc->set.T;
+    if (ntrees) *ntrees = acc->set.ntrees;
+    if (q_total) *q_total = acc->set.q_total;
+    return TQ_OK;
+}
+
+int tq_ls_read(tq_ls *acc, uint64_t *out)
+{
+    if (!acc || !out) return TQ_ERR_INVALID_ARG;
+    tq_ctx *ctx = acc->set.ctx;
+    return api(ctx, "tq_ls_read", [&]() -> int {
+        const size_t bytes = (size_t)acc->set.T * 4 * 8;
+        if (!ctx) {
+            memcpy(out, acc->h_acc.data(), bytes);
+            return TQ_OK;
+        }
+        TQ_HIP(ctx, acc->set.order.sync());
+        TQ_HIP(ctx, hipMemcpy(out, acc->d_acc, bytes, hipMemcpyDeviceToHost));
+        return TQ_OK;
+    });
+}
+
+int tq_ls_stats(tq_ls *acc, int64_t *out)
+{
+    if (!acc || !out) return TQ_ERR_INVALID_ARG;
+    out[0] = acc->set.chunk_words * 64;
+    out[1] = acc->set.chunks;
+    out[2] = acc->set.tables;
+    out[3] = acc->set.table_form();
+    out[4] = acc->set.chunk_words;
+    out[5] = acc->groups;
+    out[6] = LS_TILE;
+    return TQ_OK;
 }
 
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch)

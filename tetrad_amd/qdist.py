@@ -30,17 +30,13 @@ from .concordance import TreeSetInput, newick_to_parent
 RANGE_STEP = 1 << 24        # ranks per call of score_range / score_all
 
 
-class QuartetDistances(TreeSetInput, Handle):
-    """Quartet distances between all trees added, on the taxa 0..ntaxa-1.
+class QuartetScoring(TreeSetInput, Handle):
+    """What the accumulators over the quartets of a tree set share (`QuartetDistances` here, `stability.LeafStability`):
+    create, adding trees, every way of naming the quartets to score, and the shape.  A family sets `_prefix`; one whose
+    library calls return a table of counts per quartet row sets `_row_counts`, and then `counts=True` makes a score
+    method return that table (u16 [Q, 4])."""
 
-    ntaxa       4..1024
-    max_trees   1..8192: the room for trees (the device back end allocates their tables and two max_trees^2 matrices at
-                create)
-    samples     names of the taxa for `add_newick`
-    engine      a `QuartetEngine`: the work is done on its device; None: on the host
-    """
-
-    _prefix = "tq_qd"
+    _row_counts = False
 
     def __init__(self, ntaxa: int, max_trees: int, samples=None, engine=None):
         self.ntaxa, self.max_trees, self.engine, self.samples = int(ntaxa), int(max_trees), engine, samples
@@ -49,7 +45,7 @@ class QuartetDistances(TreeSetInput, Handle):
 
     def clear(self):
         """Zeroes the counts and keeps the trees."""
-        self._check(self._lib.tq_qd_clear(self._h))
+        self._check(self._fn("clear")(self._h))
 
     def reset(self):
         """Forgets the trees and the counts."""
@@ -58,37 +54,58 @@ class QuartetDistances(TreeSetInput, Handle):
     # -- adding trees ---------------------------------------------------------------------------------------
     def _add(self, block, n_nodes, stride, stream):
         """Refused once quartets have been scored, until `clear` or `reset`."""
-        self._check(self._lib.tq_qd_add(self._h, block.ctypes.data, n_nodes.ctypes.data, len(n_nodes), stride, stream))
+        self._check(self._fn("add")(self._h, block.ctypes.data, n_nodes.ctypes.data, len(n_nodes), stride, stream))
 
     # -- scoring quartets -----------------------------------------------------------------------------------
-    def score(self, quartets, stream: int = 0):
+    def _table(self, Q: int, counts: bool):
+        """The array a score call fills ([Q, 4] u16; zero rows stay where the library has nothing to score), or None."""
+        if not counts:
+            return None
+        if not self._row_counts:
+            raise ValueError(f"{type(self).__name__} has no counts per quartet")
+        return np.zeros((Q, 4), np.uint16)
+
+    def _call(self, name, *args, table=None, offset=0, stream=0):
+        """tq_<family>_<name>(handle, *args[, the rows of `table` from `offset`], stream)."""
+        if isinstance(stream, bool):        # score(quartets, True) meant counts=True: never hand 1 to the device as a stream
+            raise TypeError("stream is a hipStream_t address; counts is given by keyword")
+        if self._row_counts:
+            args += (table[offset:].ctypes.data if table is not None and offset < len(table) else None,)
+        self._check(self._fn(name)(self._h, *args, stream or None))
+
+    def score(self, quartets, stream: int = 0, *, counts: bool = False):
         """Quartets as an integer array [Q, 4]: four distinct taxa each, in any order.  All are checked first."""
         q = np.ascontiguousarray(quartets, dtype=np.int32)
         if q.size == 0:
-            return
+            return self._table(0, counts)
         if q.ndim != 2 or q.shape[1] != 4:
             raise ValueError("quartets must have the shape [Q, 4]")
-        self._check(self._lib.tq_qd_score(self._h, q.ctypes.data, q.shape[0], stream or None))
+        table = self._table(q.shape[0], counts)
+        self._call("score", q.ctypes.data, q.shape[0], table=table, stream=stream)
+        return table
 
-    def score_ranks(self, ranks, stream: int = 0):
+    def score_ranks(self, ranks, stream: int = 0, *, counts: bool = False):
         """Quartets as lexicographic ranks of 4-combinations of the taxa, each below C(ntaxa, 4)."""
         r = np.ascontiguousarray(ranks, dtype=np.uint64).reshape(-1)
-        if r.size == 0:
-            return
-        self._check(self._lib.tq_qd_score_ranks(self._h, r.ctypes.data, 0, r.shape[0], stream or None))
+        table = self._table(r.shape[0], counts)
+        if r.size:
+            self._call("score_ranks", r.ctypes.data, 0, r.shape[0], table=table, stream=stream)
+        return table
 
-    def score_range(self, first: int, count: int, stream: int = 0):
+    def score_range(self, first: int, count: int, stream: int = 0, *, counts: bool = False):
         """The `count` consecutive ranks from `first`, issued in ranges of at most 2^24.  Checked as a whole first."""
         first, count = int(first), int(count)
         if first < 0 or count < 0 or first + count > self.total_quartets:
             raise ValueError(f"rank range [{first},+{count}) exceeds C({self.ntaxa},4) = {self.total_quartets}")
+        table = self._table(count, counts)
         for lo in range(first, first + count, RANGE_STEP):
             n = min(RANGE_STEP, first + count - lo)
-            self._check(self._lib.tq_qd_score_ranks(self._h, None, lo, n, stream or None))
+            self._call("score_ranks", None, lo, n, table=table, offset=lo - first, stream=stream)
+        return table
 
-    def score_all(self, stream: int = 0):
+    def score_all(self, stream: int = 0, *, counts: bool = False):
         """All C(ntaxa, 4) quartets."""
-        self.score_range(0, self.total_quartets, stream)
+        return self.score_range(0, self.total_quartets, stream, counts=counts)
 
     def sample_ranks(self, n: int, seed) -> np.ndarray:
         """`n` distinct ranks drawn with numpy.random.default_rng(seed), ascending."""
@@ -98,16 +115,17 @@ class QuartetDistances(TreeSetInput, Handle):
         ranks = np.random.default_rng(seed).choice(self.total_quartets, size=n, replace=False)
         return np.sort(ranks).astype(np.uint64)
 
-    def score_sample(self, n: int, seed, stream: int = 0) -> np.ndarray:
-        """Scores `n` distinct sampled quartets (see `sample_ranks`) and returns their ranks."""
+    def score_sample(self, n: int, seed, stream: int = 0, *, counts: bool = False):
+        """Scores `n` distinct sampled quartets (see `sample_ranks`) and returns their ranks; with `counts=True`
+        (ranks, the table of their counts)."""
         ranks = self.sample_ranks(n, seed)
-        self.score_ranks(ranks, stream)
-        return ranks
+        table = self.score_ranks(ranks, stream, counts=counts)
+        return (ranks, table) if counts else ranks
 
     # -- reading --------------------------------------------------------------------------------------------
     def _shape(self):
         T, n, q = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_uint64()
-        self._check(self._lib.tq_qd_shape(self._h, ctypes.byref(T), ctypes.byref(n), ctypes.byref(q)))
+        self._check(self._fn("shape")(self._h, ctypes.byref(T), ctypes.byref(n), ctypes.byref(q)))
         return T.value, n.value, q.value
 
     @property
@@ -118,6 +136,19 @@ class QuartetDistances(TreeSetInput, Handle):
     def nquartets(self) -> int:
         """Quartets scored since create, `clear` or `reset`."""
         return self._shape()[2]
+
+
+class QuartetDistances(QuartetScoring):
+    """Quartet distances between all trees added, on the taxa 0..ntaxa-1.
+
+    ntaxa       4..1024
+    max_trees   1..8192: the room for trees (the device back end allocates their tables and two max_trees^2 matrices at
+                create)
+    samples     names of the taxa for `add_newick`
+    engine      a `QuartetEngine`: the work is done on its device; None: on the host
+    """
+
+    _prefix = "tq_qd"
 
     def raw(self):
         """(same u64[N, N], both u64[N, N]) as the library returns them; waits for the device."""

@@ -232,7 +232,7 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
                     rng: Optional[np.random.Generator] = None, sampler: str = "host", group=None, workers: int = 4,
                     concordance=None, supertree: str = "host", consensus=None, search: str = "f64", restarts: int = 1,
                     fit_out=None, polish: bool = False, transfer=None, distances=None,
-                    quartet_distances=None) -> list:
+                    quartet_distances=None, stability=None) -> list:
     """The bootstrap part of run_inference.py:378-407 including the supertree step (:394): `nboots` replicates through
     `ReplicateRunner`, each replicate's rows turned into a quartet supertree by the clean-room weighted Quartet MaxCut
     (`qmc.infer_supertree_from_arrays`: same filters and weight strategies as :254-305) on a small thread pool while
@@ -256,7 +256,9 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
     `distances` (a `treedist.TreeDistances`) receives them in the same way (`distances.rf()` is then the Robinson-Foulds
     matrix of the replicates).
     `quartet_distances` (a `qdist.QuartetDistances`) receives them in the same way; score quartets on it afterwards
-    (`quartet_distances.score_all()`, then `.distance()`)."""
+    (`quartet_distances.score_all()`, then `.distance()`).
+    `stability` (a `stability.LeafStability`) receives them in the same way; score quartets on it afterwards
+    (`stability.score_all()`, then `.rogues(k)`)."""
     trees = _bootstrap_trees(engine, seqarr, spans, nquartets, nboots, subsample_snps, weights, min_snps, min_ratio, seed,
                              rng, sampler, group, workers, concordance, supertree, search, restarts, fit_out, polish)
     if consensus is not None and trees:
@@ -267,6 +269,8 @@ def bootstrap_trees(engine: QuartetEngine, seqarr: np.ndarray, spans: np.ndarray
         distances.add_newick(trees)
     if quartet_distances is not None and trees:
         quartet_distances.add_newick(trees)
+    if stability is not None and trees:
+        stability.add_newick(trees)
     return trees
 
 

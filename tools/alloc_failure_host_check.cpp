@@ -183,6 +183,20 @@ int qd(Blob &out)
     return TQ_OK;
 }
 
+int ls(Blob &out)
+{
+    Owner<tq_ls, tq_ls_destroy> a;
+    uint16_t counts[Q * 4];
+    uint64_t sums[T * 4];
+    TRY(tq_ls_create(&a.p, T, R, nullptr));
+    TRY(tq_ls_add(a.p, g_parents, g_nodes, R, STRIDE, nullptr));
+    TRY(tq_ls_score(a.p, g_iquartets, Q, counts, nullptr));
+    TRY(tq_ls_read(a.p, sums));
+    out.put(counts, sizeof counts);
+    out.put(sums, sizeof sums);
+    return TQ_OK;
+}
+
 int conc(Blob &out)
 {
     Owner<tq_conc, tq_conc_destroy> a;
@@ -324,6 +338,7 @@ int main()
     sweep("tbe", tbe);
     sweep("rf", rf);
     sweep("qd", qd);
+    sweep("ls", ls);
     sweep("conc", conc);
     sweep("scf", scf);
     sweep("stree", stree);
