@@ -1006,6 +1006,45 @@ int tq_scf_add_dev(tq_scf *acc, const uint32_t *d_sets, const uint32_t *d_classe
 int tq_scf_shape(const tq_scf *acc, int64_t *T, int64_t *n_edges, int64_t *mask_words);
 int tq_scf_read(tq_scf *acc, int64_t *edge_counts, uint64_t *masks, int64_t *skipped);
 
+/* All-pairs taxon counts per block of sites, and neighbour joining.  No reference counterpart.
+ *   Rule (full mode, every site counts; "count_invariant" is not read): for taxa i, j and the sites of a block, both = the
+ *   sites present (tmparr <= 3) in i and in j, diff = of those the sites whose bases differ, ts = of the differing ones
+ *   the transitions (A<->G, C<->T with A, C, G, T = 0..3), tv = diff - ts.  A pair row is u32[4] = (both, diff, ts, tv);
+ *   row (i, i) is (sites present in i, 0, 0, 0); the matrix is symmetric.  Blocks and block_starts exactly as
+ *   tq_patterns_blocks takes them (host memory, B + 1 strictly increasing boundaries inside [0, S], 1 <= B <= 4096; sites
+ *   outside every block count nowhere).  Output u32[B][T][T][4].  Exact integers: host and device, any option value, any
+ *   stream give the same array.
+ *   tq_taxon_counts        host buffer, synchronous.  Reads the resident replicate in the natural layout always.  Refuses
+ *                     NULL, no data and the block rule before anything is launched.  Works in chunks of whole blocks
+ *                     whose rows fit option "taxdist_scratch_bytes" (default 256 MiB, 0 = default, negative refused; one
+ *                     block where a block alone exceeds it).
+ *   tq_taxon_counts_dev    d_out a device pointer, 16-byte aligned or refused; enqueued on `stream` under the stream rule
+ *                     above, so it is ordered behind a tq_bootstrap_async.  block_starts is read before the call returns;
+ *                     the work items made of it reach the device through two page-locked staging pieces in turn, without
+ *                     a synchronisation of the caller's stream (the host waits only for the copy that used the piece two
+ *                     launches earlier; a launch holds 65 535 work items).
+ *   tq_taxon_counts_host   the same rule on tmparr u8[T][S] (a cell above 3 is missing), no context: T >= 2, S >= 1, the
+ *                     block rule against S; messages go to tq_last_error(NULL).
+ *   tq_taxon_counts_stats  out i64[5], of the last counts call of the context: tile pairs, work items, u64 words of a work
+ *                     item (option "taxdist_slice_words", a multiple of 8, 0 = default; no result depends on it), blocks
+ *                     per chunk, chunks.
+ *   Neither counts call records a timing mark or counts as a call of tq_timing_read*.
+ *   tq_nj_tree   neighbour joining, host code, no context.  dist f64[T][T], T >= 3; refused when an off-diagonal entry is
+ *                not finite or dist[i][j] != dist[j][i] (the message names the pair); the diagonal is ignored, negative
+ *                entries are allowed.  Nodes 0..T-1 are the taxa, new nodes T, T+1, ...; the active list is kept in
+ *                ascending id.  A round with n > 3 active nodes: r_i = the sum of d(i, k) over the active k != i in ascending
+ *                id; Q(i, j) = ((n - 2) d(i, j) - r_i) - r_j; the smallest Q is joined, ties to the lexicographically
+ *                lowest (i, j), i < j; l_i = 0.5 d(i, j) + (r_i - r_j) / (2 (n - 2)), l_j = d(i, j) - l_i, d(u, k) = 0.5
+ *                ((d(i, k) + d(j, k)) - d(i, j)).  With n = 3 the active i < j < k become children of node 2T - 3 with l_i =
+ *                0.5 ((d_ij + d_ik) - d_jk), l_j = 0.5 ((d_ij + d_jk) - d_ik), l_k = 0.5 ((d_ik + d_jk) - d_ij).  Every
+ *                floating operation is one correctly rounded double operation in that order.  parent i32[2T - 2]
+ *                (parent[root] = -1), length f64[2T - 2] (the root's is 0; negative lengths are returned as computed). */
+int tq_taxon_counts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, uint32_t *out);
+int tq_taxon_counts_dev(tq_ctx *ctx, const int64_t *block_starts, int64_t B, uint32_t *d_out, void *stream);
+int tq_taxon_counts_host(const uint8_t *tmparr, int64_t T, int64_t S, const int64_t *block_starts, int64_t B, uint32_t *out);
+int tq_taxon_counts_stats(tq_ctx *ctx, int64_t *out);
+int tq_nj_tree(const double *dist, int64_t T, int32_t *parent, double *length);
+
 /* Device facts used by bench.py: writes CU count, wave slots used by the resolve
  * kernel per CU and the padded row pitch in bytes.                                 */
 int tq_device_info(tq_ctx *ctx, int32_t *num_cu, int32_t *waves_per_cu, int64_t *row_pitch);

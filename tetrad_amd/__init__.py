@@ -9,7 +9,8 @@ over the GPUs of a node), ``replicates`` (bootstrap-replicate loop), ``bootstrap
 ``scf`` (site concordance factors per branch of a fixed tree), ``tbe`` (transfer bootstrap supports of a tree's
 branches over replicate trees), ``treedist`` (all-pairs Robinson-Foulds distances of a set of trees),
 ``qdist`` (all-pairs quartet distances of a set of trees), ``stability`` (quartet frequencies of a set of trees and the
-leaf stability of its taxa).
+leaf stability of its taxa), ``distance`` (pairwise taxon counts and distances from the SNP matrix, neighbour-joining
+trees and their supports).
 Importing the package does not load the HIP library; the first compute call does, and fails loudly if it is missing.
 """
 __version__ = "0.2.0"
@@ -19,7 +20,9 @@ _TBE_EXPORTS = ("TransferSupport", "transfer_supports")
 _TREEDIST_EXPORTS = ("TreeDistances", "rf_matrix")
 _QDIST_EXPORTS = ("QuartetDistances", "quartet_distance_matrix")
 _STABILITY_EXPORTS = ("LeafStability", "quartet_frequencies", "dominant_splits")
-__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS + _TREEDIST_EXPORTS + _QDIST_EXPORTS + _STABILITY_EXPORTS)
+_DISTANCE_EXPORTS = ("taxon_counts_host", "distances", "sharing", "fill_undefined", "pool_counts", "nj_tree", "nj_parents",
+                     "jackknife_nj_trees", "bootstrap_nj_trees", "run_distance_tree")
+__all__ = list(_SCF_EXPORTS + _TBE_EXPORTS + _TREEDIST_EXPORTS + _QDIST_EXPORTS + _STABILITY_EXPORTS + _DISTANCE_EXPORTS)
 
 
 def __getattr__(name):
@@ -39,4 +42,7 @@ def __getattr__(name):
     if name in _STABILITY_EXPORTS:
         from . import stability
         return getattr(stability, name)
+    if name in _DISTANCE_EXPORTS:
+        from . import distance
+        return getattr(distance, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -187,6 +187,12 @@ PROTOTYPES = {
     "tq_scf_add_dev": _sig(vp, vp, vp, i64, vp),
     "tq_scf_shape": _sig(vp, P(i64), P(i64), P(i64)),
     "tq_scf_read": _sig(vp, vp, vp, P(i64)),
+    # -- taxon counts per block of sites, neighbour joining
+    "tq_taxon_counts": _sig(vp, vp, i64, vp),
+    "tq_taxon_counts_dev": _sig(vp, vp, i64, vp, vp),
+    "tq_taxon_counts_host": _sig(vp, i64, i64, vp, i64, vp),
+    "tq_taxon_counts_stats": _sig(vp, vp),
+    "tq_nj_tree": _sig(vp, i64, vp, vp),
     "tq_device_info": _sig(vp, P(i32), P(i32), P(i64)),
 }
 #: the names alone

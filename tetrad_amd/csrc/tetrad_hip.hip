@@ -54,6 +54,9 @@
 //   species_blocks.hpp, species_quintet_blocks.hpp the arithmetic of pooled four- and five-species block rows (species table)
 //   block_rows.hpp tq_block_rows_kernel<Rule>: the per-block class-row kernel, its plane walk and table walk, and the
 //                 rules of quartets, species and species quintets on the arithmetic of the headers above
+//   taxdist.hpp   tq_taxon_counts_kernel + tq_taxon_finish_kernel: the tile product on the plane records themselves: shared
+//                 sites, differences, transitions and transversions of every pair of taxa per block of sites
+//   nj.hpp        (host) neighbour joining on a distance matrix
 // This file holds the context, the launch logic and the C ABI (include/tetrad_hip.h).
 //
 // The rules of the C boundary, each written once below:
@@ -131,6 +134,8 @@ namespace {
 #include "species_quintet_blocks.hpp"
 #include "block_rows.hpp"
 #include "scf.hpp"
+#include "taxdist.hpp"
+#include "nj.hpp"
 
 }  // namespace
 
@@ -190,6 +195,9 @@ struct tq_ctx {
         int species_alleles = 0;        // 1: every sample is two lineages, the alleles of its IUPAC genotype
         int site_pack = -1;             // -1: tq_set_data builds the packed set when the predicted scan cost falls (pack.hpp), 1: always
                                         // (while subsample mode is possible), 0: never, and a built set is not used
+        int64_t taxdist_scratch_bytes = int64_t(256) << 20;    // taxon counts: device bytes of one chunk of whole blocks of the host-buffer
+                                        // call (one block where a block alone exceeds it; no result depends on it)
+        int taxdist_slice_words = TD_SLICE_WORDS;   // taxon counts: u64 words of a work item, a multiple of 8 (A/B: no result depends on it)
         int boot_pack = 0;              // 1: every replicate is packed, -1: when the rule said so for the source (boot_pack_auto),
                                         // 0: never (the replicate keeps the natural layout only); site_pack = 0 overrides
     };
@@ -289,6 +297,13 @@ struct tq_ctx {
     int64_t *h_bstarts_stage[2] = {nullptr, nullptr};
     hipEvent_t ev_bstarts[2] = {nullptr, nullptr};   // the piece's H2D has been consumed
     unsigned bstarts_turn = 0;
+    // work items of tq_taxon_counts* (taxdist.hpp): one device array of TD_LAUNCH_ITEMS items, filled launch by launch on
+    // the call's stream from page-locked staging, two pieces in turn as the boundaries above
+    DevBuf<TdItem> d_td_items;
+    TdItem *h_td_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_td[2] = {nullptr, nullptr};
+    unsigned td_turn = 0;
+    int64_t td_stats[5] = {0, 0, 0, 0, 0};      // of the last call: tile pairs, work items, slice words, blocks per chunk, chunks
     Options opt;                    // tq_set_option
     int pb_ok = 0;                  // tq_scan_pb_kernel's counters sit on a 64 KiB LDS boundary (probed once in tq_create)
     // timing: a sequence of tagged HIP events on the launch stream; the time between two consecutive
@@ -1605,12 +1620,10 @@ int species_quintet_ready(tq_ctx *ctx, const char *who)
     return TQ_OK;
 }
 
-// What every form checks before anything is launched: the data (and the species map) and the block rule.
-int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *block_starts, int64_t B)
+// The block rule: 1 <= B <= PBLK_MAX_BLOCKS blocks whose B + 1 boundaries increase strictly inside [0, S], the sites of
+// `what` (ctx NULL: the context-free form of the taxon counts).
+int check_block_rule(tq_ctx *ctx, const char *who, const int64_t *block_starts, int64_t B, int64_t S, const char *what)
 {
-    if (int rc = block_set_species(kind) ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
-    if (kind == BLK_SPECIES_QUINTET)
-        if (int rc = species_quintet_ready(ctx, who)) return rc;
     if (int rc = check_block_count(ctx, who, B)) return rc;
     if (block_starts[0] < 0)
         return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[0]=%lld is negative", who, (long long)block_starts[0]);
@@ -1618,10 +1631,19 @@ int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *bl
         if (block_starts[j + 1] <= block_starts[j])
             return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[%lld]=%lld is not above block_starts[%lld]=%lld", who,
                         (long long)(j + 1), (long long)block_starts[j + 1], (long long)j, (long long)block_starts[j]);
-    if (block_starts[B] > ctx->S)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[%lld]=%lld is past the S=%lld sites of the resident replicate",
-                    who, (long long)B, (long long)block_starts[B], (long long)ctx->S);
+    if (block_starts[B] > S)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "%s: block_starts[%lld]=%lld is past the S=%lld sites of the %s", who, (long long)B,
+                    (long long)block_starts[B], (long long)S, what);
     return TQ_OK;
+}
+
+// What every form checks before anything is launched: the data (and the species map) and the block rule.
+int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *block_starts, int64_t B)
+{
+    if (int rc = block_set_species(kind) ? species_ready(ctx, who) : check_ready(ctx, 0)) return rc;
+    if (kind == BLK_SPECIES_QUINTET)
+        if (int rc = species_quintet_ready(ctx, who)) return rc;
+    return check_block_rule(ctx, who, block_starts, B, ctx->S, "resident replicate");
 }
 
 // The boundaries reach the device behind the work already on `stream`, without waiting for it: a copy into the next
@@ -1740,6 +1762,72 @@ int blocks_dev(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *d_s
         if (!rc) rc = launch_blocks(ctx, kind, d_sets, Q, B, d_classes, stream);
         return note_dev_api(ctx, stream, rc);
     });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Taxon counts (taxdist.hpp): pair rows u32[B][T][T][4] of the resident replicate, natural layout always.
+// ---------------------------------------------------------------------------------------------
+
+// The items of one launch reach the device as the boundaries do (stage_block_starts): the next of two page-locked
+// pieces, then an asynchronous H2D behind the work already on `stream`.  The host waits only for the copy that used the
+// piece two launches ago, so a call of up to two launches never waits for the stream.
+int stage_td_items(tq_ctx *ctx, const TdItem *items, int64_t n, hipStream_t stream)
+{
+    constexpr size_t bytes = (size_t)TD_LAUNCH_ITEMS * sizeof(TdItem);
+    if (!ctx->d_td_items) TQ_HIP(ctx, ctx->d_td_items.alloc((size_t)TD_LAUNCH_ITEMS));
+    for (int i = 0; i < 2; ++i) {
+        if (!ctx->h_td_stage[i] && pool().alloc(bytes, (void **)&ctx->h_td_stage[i]) != TQ_OK)
+            return fail(ctx, TQ_ERR_OOM, "out of page-locked host memory for the work items of the taxon counts");
+        if (!ctx->ev_td[i]) TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_td[i], hipEventDisableTiming));
+    }
+    const unsigned turn = ctx->td_turn++ & 1u;
+    TQ_HIP(ctx, hipEventSynchronize(ctx->ev_td[turn]));
+    memcpy(ctx->h_td_stage[turn], items, (size_t)n * sizeof(TdItem));
+    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_td_items, ctx->h_td_stage[turn], (size_t)n * sizeof(TdItem), hipMemcpyHostToDevice, stream));
+    TQ_HIP(ctx, hipEventRecord(ctx->ev_td[turn], stream));
+    return TQ_OK;
+}
+
+// blocks per piece of the rows: a piece holds at most 2^30 pair rows (the finish grid) and, with `bytes`, fits them
+int64_t td_piece_blocks(int64_t T, int64_t B, int64_t bytes)
+{
+    const int64_t TT = T * T;
+    int64_t n = (int64_t(1) << 30) / TT;
+    if (bytes > 0 && bytes / (TT * 16) < n) n = bytes / (TT * 16);
+    return n < 1 ? 1 : (n > B ? B : n);
+}
+
+// Blocks [b0, b1) of `block_starts` into d_out = the rows of block b0, on `stream`: the region zeroed, the product in
+// launches of at most TD_LAUNCH_ITEMS work items, then tv and the mirror.  Adds the items to *n_items.
+int launch_taxon_counts(tq_ctx *ctx, const char *who, const int64_t *block_starts, int64_t b0, int64_t b1, uint32_t *d_out,
+                        hipStream_t stream, int64_t *n_items)
+{
+    const int64_t T = ctx->T, nt = (T + TD_BT - 1) / TD_BT, pairs = nt * (nt + 1) / 2, rows = (b1 - b0) * T * T;
+    std::vector<TdItem> items;
+    td_make_items(block_starts, b0, b1, ctx->opt.taxdist_slice_words, items);
+    TQ_HIPF(ctx, who, hipMemsetAsync(d_out, 0, (size_t)rows * 16, stream));
+    for (int64_t i0 = 0; i0 < (int64_t)items.size(); i0 += TD_LAUNCH_ITEMS) {
+        const int64_t n = std::min<int64_t>(TD_LAUNCH_ITEMS, (int64_t)items.size() - i0);
+        if (int rc = stage_td_items(ctx, items.data() + i0, n, stream)) return rc;
+        const TdArgs a{ctx->nat.planes3, ctx->d_td_items, d_out, ctx->nat.W, (int32_t)T, (int32_t)nt, (int32_t)b0};
+        hipLaunchKernelGGL(tq_taxon_counts_kernel, dim3((unsigned)pairs, (unsigned)n), dim3(TD_THREADS), 0, stream, a);
+        TQ_LAUNCHED(ctx, who);
+    }
+    hipLaunchKernelGGL(tq_taxon_finish_kernel, dim3((unsigned)((rows + TD_THREADS - 1) / TD_THREADS)), dim3(TD_THREADS), 0, stream,
+                       (uint4 *)d_out, b1 - b0, (int32_t)T);
+    TQ_LAUNCHED(ctx, who);
+    *n_items += (int64_t)items.size();
+    return TQ_OK;
+}
+
+void note_taxon_counts(tq_ctx *ctx, int64_t items, int64_t piece, int64_t pieces)
+{
+    const int64_t nt = (ctx->T + TD_BT - 1) / TD_BT;
+    ctx->td_stats[0] = nt * (nt + 1) / 2;
+    ctx->td_stats[1] = items;
+    ctx->td_stats[2] = ctx->opt.taxdist_slice_words;
+    ctx->td_stats[3] = piece;
+    ctx->td_stats[4] = pieces;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2945,6 +3033,9 @@ constexpr OptionRow OPTION_TABLE[] = {
     opt("stree_search_dev", &Options::stree_search_dev, 0, 1, NO_KEY, "stree_search_dev must be 0 or 1"),
     opt("fit_scratch_bytes", &Options::fit_scratch_bytes, 1, ANY, NO_KEY, "fit_scratch_bytes must be at least 1"),
     opt("qdist_scratch_bytes", &Options::qdist_scratch_bytes, 1, ANY, 0, "qdist_scratch_bytes must be >= 0 (0 = default 256 MiB)"),
+    opt("taxdist_scratch_bytes", &Options::taxdist_scratch_bytes, 1, ANY, 0, "taxdist_scratch_bytes must be >= 0 (0 = default 256 MiB)"),
+    opt("taxdist_slice_words", &Options::taxdist_slice_words, 8, TD_MAX_SLICE_WORDS, 0,
+        "taxdist_slice_words must be a multiple of 8 in 8..65536 (0 = default)"),
     opt("qdist_kslices", &Options::qdist_kslices, 0, 65535, NO_KEY, "qdist_kslices must be 0 (auto) .. 65535"),
     opt("stree_lds", &Options::stree_lds, 0, 1, NO_KEY, "stree_lds must be 0 or 1"),
     opt("svd_wpc", &Options::svd_wpc, 0, 1 << 20, NO_KEY, "svd_wpc must be 0..2^20"),
@@ -3010,6 +3101,11 @@ void tq_destroy(tq_ctx *ctx)
             (void)hipEventDestroy(ctx->ev_bstarts[i]);
         }
         if (ctx->h_bstarts_stage[i]) (void)pool().release(ctx->h_bstarts_stage[i]);
+        if (ctx->ev_td[i]) {
+            (void)hipEventSynchronize(ctx->ev_td[i]);
+            (void)hipEventDestroy(ctx->ev_td[i]);
+        }
+        if (ctx->h_td_stage[i]) (void)pool().release(ctx->h_td_stage[i]);
     }
     for (auto e : ctx->pipe_events) (void)hipEventDestroy(e);
     for (auto &m : ctx->marks) (void)hipEventDestroy(m.ev);
@@ -3591,6 +3687,95 @@ int tq_dstat_jackknife_masks_dev(tq_ctx *ctx, const uint32_t *d_bclasses, int64_
                          N, d_out, stream);
 }
 
+int tq_taxon_counts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, uint32_t *out)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    const char *who = "tq_taxon_counts";
+    return api(ctx, who, [&]() -> int {
+        if (!block_starts) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
+        int rc = blocks_ready(ctx, who, BLK_QUARTET, block_starts, B);
+        if (rc) return rc;
+        if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
+        const int64_t T = ctx->T, chunk = td_piece_blocks(T, B, ctx->opt.taxdist_scratch_bytes);
+        const size_t block_bytes = (size_t)(T * T) * 16;
+        TQ_HIP(ctx, ctx->d_scratch.grow((size_t)chunk * block_bytes));
+        if ((rc = ensure_streams(ctx))) return rc;
+        uint32_t *d_rows = (uint32_t *)ctx->d_scratch.get();
+        int64_t items = 0, chunks = 0;
+        for (int64_t b0 = 0; b0 < B && !rc; b0 += chunk, ++chunks) {
+            const int64_t b1 = std::min(B, b0 + chunk);
+            rc = launch_taxon_counts(ctx, who, block_starts, b0, b1, d_rows, ctx->sK, &items);
+            if (!rc && hipMemcpyAsync((char *)out + (size_t)b0 * block_bytes, d_rows, (size_t)(b1 - b0) * block_bytes,
+                                      hipMemcpyDeviceToHost, ctx->sK) != hipSuccess)
+                rc = fail(ctx, TQ_ERR_HIP, "%s: copy of the pair rows failed", who);
+        }
+        if (hipStreamSynchronize(ctx->sK) != hipSuccess && !rc) rc = fail(ctx, TQ_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+        if (!rc) note_taxon_counts(ctx, items, chunk, chunks);
+        return rc;
+    });
+}
+
+int tq_taxon_counts_dev(tq_ctx *ctx, const int64_t *block_starts, int64_t B, uint32_t *d_out, void *stream)
+{
+    if (!ctx) return TQ_ERR_INVALID_ARG;
+    const char *who = "tq_taxon_counts_dev";
+    return api(ctx, who, [&]() -> int {
+        if (!block_starts) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
+        if (int rc = blocks_ready(ctx, who, BLK_QUARTET, block_starts, B)) return rc;
+        if (!d_out) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
+        if ((uintptr_t)d_out & 15) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: d_out must be 16-byte aligned", who);
+        if (int rc = enter_dev_api(ctx, (hipStream_t)stream)) return rc;     // behind a tq_bootstrap_async that rebuilds the layout
+        const int64_t T = ctx->T, piece = td_piece_blocks(T, B, 0);
+        int64_t items = 0, pieces = 0;
+        int rc = TQ_OK;
+        for (int64_t b0 = 0; b0 < B && !rc; b0 += piece, ++pieces)
+            rc = launch_taxon_counts(ctx, who, block_starts, b0, std::min(B, b0 + piece), d_out + (size_t)b0 * (size_t)(T * T) * 4,
+                                     (hipStream_t)stream, &items);
+        if (!rc) note_taxon_counts(ctx, items, piece, pieces);
+        return note_dev_api(ctx, (hipStream_t)stream, rc);
+    });
+}
+
+int tq_taxon_counts_host(const uint8_t *tmparr, int64_t T, int64_t S, const int64_t *block_starts, int64_t B, uint32_t *out)
+{
+    const char *who = "tq_taxon_counts_host";
+    return api(nullptr, who, [&]() -> int {
+        if (!tmparr || !block_starts || !out) return fail(nullptr, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
+        if (T < 2 || S < 1) return fail(nullptr, TQ_ERR_INVALID_ARG, "%s: T=%lld, S=%lld: need T >= 2 and S >= 1", who, (long long)T, (long long)S);
+        if (int rc = check_block_rule(nullptr, who, block_starts, B, S, "matrix")) return rc;
+        td_host_counts(tmparr, T, S, block_starts, B, out);
+        return TQ_OK;
+    });
+}
+
+int tq_taxon_counts_stats(tq_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return TQ_ERR_INVALID_ARG;
+    for (int i = 0; i < 5; ++i) out[i] = ctx->td_stats[i];
+    return TQ_OK;
+}
+
+int tq_nj_tree(const double *dist, int64_t T, int32_t *parent, double *length)
+{
+    const char *who = "tq_nj_tree";
+    return api(nullptr, who, [&]() -> int {
+        if (!dist || !parent || !length) return fail(nullptr, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
+        if (T < 3 || T > 0x3FFFFFFF) return fail(nullptr, TQ_ERR_INVALID_ARG, "%s: T=%lld taxa, need at least 3", who, (long long)T);
+        for (int64_t i = 0; i < T; ++i)
+            for (int64_t j = i + 1; j < T; ++j) {
+                const double a = dist[i * T + j], b = dist[j * T + i];
+                if (!std::isfinite(a) || !std::isfinite(b))
+                    return fail(nullptr, TQ_ERR_INVALID_ARG, "%s: the distance of the pair (%lld, %lld) is not finite", who, (long long)i,
+                                (long long)j);
+                if (a != b)
+                    return fail(nullptr, TQ_ERR_INVALID_ARG, "%s: dist is not symmetric at the pair (%lld, %lld): %.17g against %.17g", who,
+                                (long long)i, (long long)j, a, b);
+            }
+        nj_host_tree(dist, T, parent, length);
+        return TQ_OK;
+    });
+}
+
 int tq_timing_enable(tq_ctx *ctx, int on)
 {
     if (!ctx) return TQ_ERR_INVALID_ARG;
@@ -3663,6 +3848,7 @@ int tq_set_option(tq_ctx *ctx, const char *name, int64_t value)
             v = row->i ? defaults.*row->i : defaults.*row->l;
         else if (row->listed ? value < 0 || value > 63 || !(row->listed >> value & 1) : value < row->lo || value > row->hi)
             return fail(ctx, TQ_ERR_INVALID_ARG, "%s", row->refusal);
+        if (row->i == &Options::taxdist_slice_words && v % BT_KW) return fail(ctx, TQ_ERR_INVALID_ARG, "%s", row->refusal);
         if (row->l == &Options::batch && v > 0x7FFFFFFFll) v = 0x7FFFFFFFll;     // item counts reach hipCUB as int
         if (row->i == &Options::species_alleles && ctx->opt.species_alleles != (int)v)
             ctx->sp_tab_gen = ~0ull;                        // the next species call rebuilds the table

@@ -380,6 +380,31 @@ class QuartetEngine(Handle):
         responsibility (an id >= K gives zeros)."""
         self._blocks_dev(self._lib.tq_patterns_quintet_blocks_species_dev, d_ssets5, Q, block_starts, d_classes, stream)
 
+    # -- all-pairs taxon counts per block of sites (DESIGN.md section 29, tetrad_amd/distance.py) ----
+    def taxon_counts(self, block_starts=None) -> np.ndarray:
+        """Pair rows u32[B,T,T,4] = (both, diff, ts, tv) of the resident replicate, full mode: the sites of block j present
+        in both taxa, of those the differing ones, of those the transitions, and the transversions.  `block_starts` None
+        means one block [0, S)."""
+        from .distance import block_starts_of
+        b = block_starts_of(block_starts, self.S)
+        B = b.shape[0] - 1
+        out = np.zeros((B, self.T, self.T, 4), np.uint32)
+        self._check(self._lib.tq_taxon_counts(self._h, _ptr(b), B, _ptr(out)))
+        return out
+
+    def taxon_counts_dev(self, block_starts, d_out: int, stream: int = 0):
+        """The same into a device pointer (u32[B,T,T,4], 16-byte aligned), enqueued on `stream`; `block_starts` is a host
+        array (None: one block), read before the call returns."""
+        from .distance import block_starts_of
+        b = block_starts_of(block_starts, self.S)
+        self._check(self._lib.tq_taxon_counts_dev(self._h, _ptr(b), b.shape[0] - 1, d_out, stream or None))
+
+    def taxon_counts_stats(self) -> dict:
+        """Of the last counts call: tile pairs, work items, u64 words of a work item, blocks per chunk, chunks."""
+        out = np.zeros(5, np.int64)
+        self._check(self._lib.tq_taxon_counts_stats(self._h, _ptr(out)))
+        return dict(zip(("tile_pairs", "work_items", "slice_words", "chunk_blocks", "chunks"), (int(x) for x in out)))
+
     # -- device-pointer API (addresses as ints, e.g. torch.Tensor.data_ptr()) -------
     def resolve_dev(self, d_quartets: int, Q: int, subsample_snps: bool, d_rstat: int,
                     d_rscor: int, d_flags: int = 0, stream: int = 0):

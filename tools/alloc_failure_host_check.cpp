@@ -281,6 +281,26 @@ int jackknife(Blob &out)
     return TQ_OK;
 }
 
+int taxdist(Blob &out)
+{
+    constexpr int64_t S = 150, B = 2;
+    const int64_t starts[B + 1] = {3, 70, 150};
+    uint8_t arr[T * S];
+    uint32_t counts[B * T * T * 4];
+    double dist[T * T];
+    int32_t parent[2 * T - 2];
+    double length[2 * T - 2];
+    for (int64_t i = 0; i < T * S; ++i) arr[i] = (uint8_t)((i * 5 + i / 7) % 5 == 4 ? 78 : (i * 5 + i / 7) % 5);
+    TRY(tq_taxon_counts_host(arr, T, S, starts, B, counts));
+    for (int64_t i = 0; i < T * T; ++i)        /* p-distances of the two blocks together */
+        dist[i] = (double)(counts[4 * i + 1] + counts[4 * (T * T + i) + 1]) / (double)(counts[4 * i] + counts[4 * (T * T + i)]);
+    TRY(tq_nj_tree(dist, T, parent, length));
+    out.put(counts, sizeof counts);
+    out.put(parent, sizeof parent);
+    out.put(length, sizeof length);
+    return TQ_OK;
+}
+
 void sweep(const char *name, int (*scenario)(Blob &))
 {
     static Blob want, got;
@@ -344,6 +364,7 @@ int main()
     sweep("stree", stree);
     sweep("pack_sites", pack_sites);
     sweep("jackknife", jackknife);
+    sweep("taxdist", taxdist);
     printf("alloc_failure_host_check: ok\n");
     return 0;
 }
