@@ -1,6 +1,8 @@
-// device_mem.hpp -- (host) owners of device and page-locked memory, and the struct of one resident site layout.
+// device_mem.hpp -- (host) owners of device and page-locked memory, of events, streams and pool blocks, the two-piece
+// staging ring, and the struct of one resident site layout.
 //
-// Nothing here synchronises: a caller that regrows a buffer the device may still read waits for the device first.
+// Nothing here synchronises: a caller that regrows a buffer the device may still read waits for the device first.  (The
+// one exception is the staging ring, which waits for its own two copies before it gives its pieces back.)
 // Nothing here selects a device either: the owner of a buffer does, before the buffer's first and last use.
 #pragma once
 
@@ -50,6 +52,88 @@ public:
 };
 template <typename T> using DevBuf = OwnedBuf<T, false>;
 template <typename T> using PinnedBuf = OwnedBuf<T, true>;
+
+// Move-only owner of one handle that FREE gives back: the base of Event, Stream and PoolBuf.  Converts to the bare handle.
+template <typename H, auto FREE>
+class Handle {
+protected:
+    H h_ = nullptr;
+
+public:
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Handle &operator=(Handle &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            std::swap(h_, o.h_);
+        }
+        return *this;
+    }
+    ~Handle() { reset(); }
+    operator H() const { return h_; }
+    explicit operator bool() const { return h_ != nullptr; }
+    void reset()
+    {
+        if (h_) (void)FREE(h_);
+        h_ = nullptr;
+    }
+};
+// one event, without timing unless it is asked for
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(bool timing = false)
+    {
+        reset();
+        return timing ? hipEventCreate(&h_) : hipEventCreateWithFlags(&h_, hipEventDisableTiming);
+    }
+};
+// one non-blocking stream (destroyed with work queued, it goes once that work is done)
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create()
+    {
+        reset();
+        return hipStreamCreateWithFlags(&h_, hipStreamNonBlocking);
+    }
+};
+// one block of n elements out of the page-locked pool (pinned_pool.hpp); alloc answers with a TQ_* code
+inline int pool_release(void *p) { return pool().release(p); }
+template <typename T>
+struct PoolBuf : Handle<T *, pool_release> {
+    int alloc(size_t n)
+    {
+        this->reset();
+        return pool().alloc(n * sizeof(T), (void **)&this->h_);
+    }
+};
+
+// A small host array on its way to the device without a wait for the stream: two page-locked pieces in turn, each with
+// the event behind the H2D copy that last read it.  The caller fills next() and issues its hipMemcpyAsync from it, then
+// calls sent(); the host waits only for the copy that read this piece two turns ago, so the next call can hand its
+// array over while this copy is queued.  The one rule of release, whoever releases: the pool hands a released block to
+// any caller, so reset() and the destructor first wait for both copies.
+template <typename T>
+struct StagingRing {
+    PoolBuf<T> piece[2];
+    Event ev[2];
+    int turn = 1;                   // the piece handed out last
+    ~StagingRing() { reset(); }
+    // pieces of n elements and their events, where absent: TQ_ERR_OOM without a piece, TQ_ERR_HIP without an event
+    int ensure(size_t n)
+    {
+        for (int i = 0; i < 2; ++i) {
+            if (!piece[i] && piece[i].alloc(n) != TQ_OK) return TQ_ERR_OOM;
+            if (!ev[i] && ev[i].create() != hipSuccess) return TQ_ERR_HIP;
+        }
+        return TQ_OK;
+    }
+    hipError_t next(T *&p) { p = piece[turn ^= 1]; return hipEventSynchronize(ev[turn]); }
+    hipError_t sent(hipStream_t stream) { return hipEventRecord(ev[turn], stream); }
+    void reset()
+    {
+        for (Event &e : ev) if (e) (void)hipEventSynchronize(e);
+        for (int i = 0; i < 2; ++i) { piece[i].reset(); ev[i].reset(); }
+    }
+};
 
 // One resident site layout (tetrad_hip.hip, "Data layout in HBM"): rows, nibbles, the optional nibbles with 4 = missing,
 // uint4 planes and the 12-byte plane records with runbeg behind them.  The arrays are allocated for capSp sites per row

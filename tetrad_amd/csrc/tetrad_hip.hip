@@ -19,7 +19,9 @@
 //   and, when it pays, a second rows / nib / planes / planes3 + runbeg set in the packed site order (pack.hpp)
 //
 // Kernels (each in its own header of this directory, all included below into one translation unit):
-//   device_mem.hpp (host) DevBuf / PinnedBuf, the owners of every device and page-locked block, and SiteSet, one layout set
+//   pinned_pool.hpp (host) the process-wide pool of page-locked blocks (tq_host_alloc, result and array staging)
+//   device_mem.hpp (host) DevBuf / PinnedBuf, the owners of every device and page-locked block; Event / Stream / PoolBuf,
+//                 the owners of every event, stream and pool block; StagingRing; and SiteSet, one layout set
 //   prepare.hpp   layout build, lexicographic unranking, sort keys
 //   pack.hpp      (host) packed site order for the subsample-mode scans: whole loci per lane word (option site_pack)
 //   scan.hpp      tq_scan_wg_kernel / tq_scan_kernel: site scan -> 256 pattern counts per quartet (nibble codes + plane
@@ -103,6 +105,7 @@
 namespace {
 
 #include "common.hpp"
+#include "pinned_pool.hpp"
 #include "device_mem.hpp"
 #include "prepare.hpp"
 #include "pack.hpp"
@@ -144,6 +147,9 @@ namespace {
 // ======================================================================================
 enum { TAG_ORIGIN = -1, TAG_ORDER = 0, TAG_SCAN = 1, TAG_BIDIAG = 2, TAG_BDSQR = 3, TAG_SCORE = 4, TAG_COUNT = 5 };
 
+// Every HIP resource below sits in an owner (device_mem.hpp), so `delete ctx` with the device selected releases all of
+// it and the order of the members does not matter: a staging ring waits for its own copies before it gives its pieces
+// back, and hipFree and hipStreamDestroy are safe with work queued.  Nothing is created before its first use.
 struct tq_ctx {
     // What tq_set_option sets (OPTION_TABLE below names the fields and their legal values).  These initialisers are the only
     // place a default is written: "0 = default" reads it from a default-constructed Options.
@@ -215,10 +221,8 @@ struct tq_ctx {
     int64_t src_T = 0, src_S0 = 0, nloci = 0, max_width = 0;
     DevBuf<int64_t> d_lidxs;        // [nloci]
     std::vector<int64_t> h_spans;   // host copy of the spans (replicate lengths are computed on the host)
-    int64_t *h_lidx_stage[2] = {nullptr, nullptr};   // page-locked staging of the resampled locus indices
-    hipEvent_t ev_lidx[2] = {nullptr, nullptr};      // its H2D has been consumed
-    unsigned lidx_turn = 0;
-    DevBuf<uint32_t> d_boot;        // widths/offsets [nloci+1] | src_col [cap] | site_locus [cap]
+    StagingRing<int64_t> lidx_ring; // a piece: the resampled locus indices i64 [nloci], behind them the packed starts u32 [nloci]
+    DevBuf<uint32_t> d_boot;       // widths/offsets [nloci+1] | src_col [cap] | site_locus [cap]
     int64_t boot_cap = 0;
     DevBuf<char> d_boot_tmp;
     size_t boot_tmp_bytes = 0;
@@ -237,8 +241,8 @@ struct tq_ctx {
     DevBuf<double> d_de, d_sv;
     DevBuf<uint32_t> d_nsnps;
     int64_t svd_quartets = 0;
-    hipStream_t sX = nullptr;       // the second stream of the singular-value stage
-    hipEvent_t evFork = nullptr, evJoin = nullptr;
+    Stream sX;                      // the second stream of the singular-value stage
+    Event evFork, evJoin;
     DevBuf<uint64_t> d_bdsqr_stats;      // diagnostics (option "bdsqr_stats"): {matrices, rotation steps of all lanes,
                                          // lane-slots issued (64 x wave iterations), sweeps} summed over the launches
     // what tq_scan_dev left in the count slab (consumed by tq_svd_dev)
@@ -279,39 +283,34 @@ struct tq_ctx {
     bool boot_pack_auto = false;    // pack_pays for the source matrix (tq_set_source): a replicate resamples its loci
     bool pk_from_boot = false;      // the packed set was built by tq_bootstrap_async (d_pk_src is its map)
     PackPlanner boot_plan;
-    DevBuf<uint32_t> d_pstart;      // [nloci] packed start of every resampled locus
-    uint32_t *h_pstart_stage[2] = {nullptr, nullptr};    // page-locked staging, in turn with h_lidx_stage
+    DevBuf<uint32_t> d_pstart;      // [nloci] packed start of every resampled locus (staged behind the indices in lidx_ring)
     DevBuf<uint32_t> d_pk_src;      // packed position -> natural site of the replicate, 0xFFFFFFFF = pad (grow-only)
     // host-buffer API: own compute and copy streams, events for the D2H pipeline
-    hipStream_t sK = nullptr, sC = nullptr;
-    std::vector<hipEvent_t> pipe_events;
+    Stream sK, sC;
+    std::vector<Event> pipe_events;
     // the asynchronous device API (caller's stream) and the synchronous host API (stream sK) share the count
     // slab, the ordering scratch and the singular-value scratch: the last device-API enqueue records this event
     // and the host API makes sK wait for it before it touches any of them
-    hipEvent_t evDevApi = nullptr;
+    Event evDevApi;
     bool dev_api_pending = false;
     hipStream_t last_dev_stream = nullptr;   // stream of the last device-API enqueue (enter_dev_api orders across streams)
-    // block boundaries of tq_patterns_blocks* (pattern_blocks.hpp): one device array, filled on the call's stream from
-    // page-locked staging (two pieces in turn, so the next call can hand its boundaries over while this copy is queued)
+    // block boundaries of tq_patterns_blocks* (pattern_blocks.hpp): one device array, filled on the call's stream through
+    // a staging ring
     DevBuf<int64_t> d_bstarts;      // [PBLK_MAX_BLOCKS + 1]
-    int64_t *h_bstarts_stage[2] = {nullptr, nullptr};
-    hipEvent_t ev_bstarts[2] = {nullptr, nullptr};   // the piece's H2D has been consumed
-    unsigned bstarts_turn = 0;
+    StagingRing<int64_t> bstarts_ring;
     // work items of tq_taxon_counts* (taxdist.hpp): one device array of TD_LAUNCH_ITEMS items, filled launch by launch on
-    // the call's stream from page-locked staging, two pieces in turn as the boundaries above
+    // the call's stream through a staging ring
     DevBuf<TdItem> d_td_items;
-    TdItem *h_td_stage[2] = {nullptr, nullptr};
-    hipEvent_t ev_td[2] = {nullptr, nullptr};
-    unsigned td_turn = 0;
+    StagingRing<TdItem> td_ring;
     int64_t td_stats[5] = {0, 0, 0, 0, 0};      // of the last call: tile pairs, work items, slice words, blocks per chunk, chunks
     Options opt;                    // tq_set_option
     int pb_ok = 0;                  // tq_scan_pb_kernel's counters sit on a 64 KiB LDS boundary (probed once in tq_create)
     // timing: a sequence of tagged HIP events on the launch stream; the time between two consecutive
     // marks is attributed to the tag of the later one (TAG_ORIGIN starts a sequence)
     bool timing = false;
-    struct Mark { int tag; int lane; hipEvent_t ev; };      // lane: 0 = caller's stream, 1 = sX
+    struct Mark { int tag; int lane; Event ev; };           // lane: 0 = caller's stream, 1 = sX
     std::vector<Mark> marks;
-    std::vector<hipEvent_t> event_pool;
+    std::vector<Event> event_pool;
     int64_t timed_calls = 0;
 };
 
@@ -378,95 +377,11 @@ int api(tq_ctx *ctx, const char *name, Body &&body)
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Pinned host memory pool (process-wide: blocks handed to a caller may outlive any context).
-// Result arrays that live in such a block are written by the copy engine directly (no staging, no
-// host pass); blocks are recycled because pinning pages costs about as much as a resolve call.
-// ---------------------------------------------------------------------------------------------
-struct PinnedPool {
-    std::mutex mu;
-    std::map<uintptr_t, size_t> live;              // base -> bytes of blocks handed out
-    std::multimap<size_t, void *> idle;            // bytes -> base of cached blocks
-    size_t idle_bytes = 0;
-    static constexpr size_t IDLE_CAP = (size_t)4 << 30;
-    static size_t round_up(size_t b)
-    {
-        size_t g = (size_t)1 << 16;
-        while (g < b && g < ((size_t)1 << 24)) g <<= 1;         // 64 KiB .. 16 MiB: powers of two
-        if (g >= b) return g;
-        const size_t step = (size_t)1 << 24;                   // beyond: multiples of 16 MiB
-        return (b + step - 1) / step * step;
-    }
-    int alloc(size_t bytes, void **out)
-    {
-        const size_t want = round_up(bytes ? bytes : 1);
-        std::lock_guard<std::mutex> g(mu);
-        try {
-            auto it = idle.lower_bound(want);
-            if (it != idle.end() && it->first <= want * 2) {
-                void *p = it->second;
-                const size_t sz = it->first;
-                idle.erase(it);
-                idle_bytes -= sz;
-                live[(uintptr_t)p] = sz;
-                *out = p;
-                return TQ_OK;
-            }
-            void *p = nullptr;
-            if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess || !p) return TQ_ERR_OOM;
-            live[(uintptr_t)p] = want;
-            *out = p;
-            return TQ_OK;
-        } catch (...) {
-            return TQ_ERR_OOM;
-        }
-    }
-    int release(void *p)
-    {
-        std::lock_guard<std::mutex> g(mu);
-        auto it = live.find((uintptr_t)p);
-        if (it == live.end()) return TQ_ERR_INVALID_ARG;
-        const size_t sz = it->second;
-        live.erase(it);
-        bool cached = false;
-        if (idle_bytes + sz <= IDLE_CAP) {
-            try {
-                idle.emplace(sz, p);
-                idle_bytes += sz;
-                cached = true;
-            } catch (...) {
-            }
-        }
-        if (!cached) (void)hipHostFree(p);
-        return TQ_OK;
-    }
-    bool owns(const void *p, size_t bytes)
-    {
-        std::lock_guard<std::mutex> g(mu);
-        auto it = live.upper_bound((uintptr_t)p);
-        if (it == live.begin()) return false;
-        --it;
-        return (uintptr_t)p + bytes <= it->first + it->second;
-    }
-};
-
-PinnedPool &pool()
+// the message for what StagingRing::ensure refused: `no_memory` where the pool had no piece, else the event's error
+int ring_fail(tq_ctx *ctx, int rc, const char *no_memory)
 {
-    static PinnedPool *p = new PinnedPool();       // never destroyed: blocks may be alive at exit
-    return *p;
-}
-
-// true when [p, p+bytes) is page-locked memory the copy engine can write asynchronously
-bool is_pinned(const void *p, size_t bytes)
-{
-    if (!p) return false;
-    if (pool().owns(p, bytes)) return true;
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();                               // unregistered memory: clear the sticky error
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
+    if (rc == TQ_ERR_OOM) return fail(ctx, rc, "%s", no_memory);
+    return fail(ctx, rc, "hipEventCreateWithFlags failed: %s", hipGetErrorString(hipGetLastError()));
 }
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -524,14 +439,7 @@ void free_source(tq_ctx *ctx)
     ctx->boot_pack_auto = false;
     ctx->boot_cap = 0;
     ctx->nloci = 0;
-    for (int i = 0; i < 2; ++i) {
-        if (ctx->h_lidx_stage[i]) (void)pool().release(ctx->h_lidx_stage[i]);
-        if (ctx->h_pstart_stage[i]) (void)pool().release(ctx->h_pstart_stage[i]);
-        ctx->h_pstart_stage[i] = nullptr;
-        if (ctx->ev_lidx[i]) (void)hipEventDestroy(ctx->ev_lidx[i]);
-        ctx->h_lidx_stage[i] = nullptr;
-        ctx->ev_lidx[i] = nullptr;
-    }
+    ctx->lidx_ring.reset();
 }
 
 // count slab + ordering scratch for a scan batch of `quartets`
@@ -563,9 +471,9 @@ int ensure_cm(tq_ctx *ctx, int64_t quartets)
 int ensure_svd(tq_ctx *ctx, int64_t quartets)
 {
     if (!ctx->sX) {
-        TQ_HIP(ctx, hipStreamCreateWithFlags(&ctx->sX, hipStreamNonBlocking));
-        TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->evFork, hipEventDisableTiming));
-        TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->evJoin, hipEventDisableTiming));
+        TQ_HIP(ctx, ctx->sX.create());
+        TQ_HIP(ctx, ctx->evFork.create());
+        TQ_HIP(ctx, ctx->evJoin.create());
     }
     if (quartets <= ctx->svd_quartets) return TQ_OK;
     ctx->d_de.reset();
@@ -583,20 +491,15 @@ int ensure_svd(tq_ctx *ctx, int64_t quartets)
 int mark(tq_ctx *ctx, int tag, hipStream_t stream, int lane = 0)
 {
     if (!ctx->timing) return TQ_OK;
-    hipEvent_t ev;
+    Event ev;                       // a push_back that throws (into the guard) destroys it
     if (!ctx->event_pool.empty()) {
-        ev = ctx->event_pool.back();
+        ev = std::move(ctx->event_pool.back());
         ctx->event_pool.pop_back();
     } else {
-        TQ_HIP(ctx, hipEventCreate(&ev));
+        TQ_HIP(ctx, ev.create(true));
     }
-    try {
-        ctx->marks.push_back({tag, lane, ev});
-    } catch (...) {
-        (void)hipEventDestroy(ev);
-        return fail(ctx, TQ_ERR_OOM, "out of host memory");
-    }
-    TQ_HIP(ctx, hipEventRecord(ev, stream));
+    ctx->marks.push_back({tag, lane, std::move(ev)});
+    TQ_HIP(ctx, hipEventRecord(ctx->marks.back().ev, stream));
     return TQ_OK;
 }
 
@@ -1148,8 +1051,8 @@ int launch(tq_ctx *ctx, const uint32_t *dq, int64_t Q, int subsample, bool debug
 int ensure_streams(tq_ctx *ctx)
 {
     if (!ctx->sK) {
-        TQ_HIP(ctx, hipStreamCreateWithFlags(&ctx->sK, hipStreamNonBlocking));
-        TQ_HIP(ctx, hipStreamCreateWithFlags(&ctx->sC, hipStreamNonBlocking));
+        TQ_HIP(ctx, ctx->sK.create());
+        TQ_HIP(ctx, ctx->sC.create());
     }
     if (ctx->dev_api_pending) {                  // work of the device API may still be using the shared scratch
         TQ_HIP(ctx, hipStreamWaitEvent(ctx->sK, ctx->evDevApi, 0));
@@ -1171,7 +1074,7 @@ int enter_dev_api(tq_ctx *ctx, hipStream_t stream)
 // called after a device-API entry point has enqueued work on the caller's stream
 int note_dev_api(tq_ctx *ctx, hipStream_t stream, int rc)
 {
-    if (!ctx->evDevApi) TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->evDevApi, hipEventDisableTiming));
+    if (!ctx->evDevApi) TQ_HIP(ctx, ctx->evDevApi.create());
     TQ_HIP(ctx, hipEventRecord(ctx->evDevApi, stream));
     ctx->dev_api_pending = true;
     ctx->last_dev_stream = stream;
@@ -1180,14 +1083,10 @@ int note_dev_api(tq_ctx *ctx, hipStream_t stream, int rc)
 
 int pipe_event(tq_ctx *ctx, size_t i, hipEvent_t *ev)
 {
-    try {
-        while (ctx->pipe_events.size() <= i) {
-            hipEvent_t e;
-            TQ_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->pipe_events.push_back(e);
-        }
-    } catch (...) {
-        return fail(ctx, TQ_ERR_OOM, "out of host memory");
+    while (ctx->pipe_events.size() <= i) {
+        Event e;
+        TQ_HIP(ctx, e.create());
+        ctx->pipe_events.push_back(std::move(e));
     }
     *ev = ctx->pipe_events[i];
     return TQ_OK;
@@ -1207,7 +1106,7 @@ struct HostSink {
     bool direct = false;
     bool single = false;           // pageable destinations, one piece: ONE D2H of the contiguous device region
     size_t off_rscor = 0, off_flags = 0;           // byte offsets of rscor / flags inside a staging piece
-    char *stage[2] = {nullptr, nullptr};
+    PoolBuf<char> stage[2];
     int64_t stage_rows = 0, total_rows = 0;
     int64_t single_q0 = 0, single_n = 0;
     hipStream_t single_stream = nullptr;
@@ -1240,7 +1139,7 @@ struct HostSink {
             off_flags = single ? (size_t)((const char *)dev->flags - (const char *)dev->rstat) : (size_t)stage_rows * 32;
             const size_t bytes = off_flags + (size_t)stage_rows;
             for (int i = 0; i < (single ? 1 : 2); ++i)
-                if (pool().alloc(bytes, (void **)&stage[i]) != TQ_OK)
+                if (stage[i].alloc(bytes) != TQ_OK)
                     return fail(ctx, TQ_ERR_OOM, "out of page-locked host memory for the result staging");
         }
         return TQ_OK;
@@ -1326,11 +1225,10 @@ struct HostSink {
     }
     ~HostSink()
     {
-        // never leave copies in flight into memory the caller may free
+        // never leave copies in flight into memory the caller may free, nor into the staging pieces, which go back to
+        // the pool behind this body
         (void)hipStreamSynchronize(ctx->sK);
         (void)hipStreamSynchronize(ctx->sC);
-        for (int i = 0; i < 2; ++i)
-            if (stage[i]) (void)pool().release(stage[i]);
     }
 };
 
@@ -1646,24 +1544,18 @@ int blocks_ready(tq_ctx *ctx, const char *who, BlockKind kind, const int64_t *bl
     return check_block_rule(ctx, who, block_starts, B, ctx->S, "resident replicate");
 }
 
-// The boundaries reach the device behind the work already on `stream`, without waiting for it: a copy into the next
-// staging piece (the host waits only for the copy that used this piece two calls ago), then an asynchronous H2D.
-// Calls of one context are ordered (enter_dev_api / ensure_streams), so one device array serves.
+// The boundaries reach the device behind the work already on `stream`, without waiting for it (StagingRing).  Calls of
+// one context are ordered (enter_dev_api / ensure_streams), so one device array serves.
 int stage_block_starts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, hipStream_t stream)
 {
-    constexpr size_t bytes = (size_t)(PBLK_MAX_BLOCKS + 1) * sizeof(int64_t);
     if (!ctx->d_bstarts) TQ_HIP(ctx, ctx->d_bstarts.alloc(PBLK_MAX_BLOCKS + 1));
-    for (int i = 0; i < 2; ++i) {
-        if (!ctx->h_bstarts_stage[i] && pool().alloc(bytes, (void **)&ctx->h_bstarts_stage[i]) != TQ_OK)
-            return fail(ctx, TQ_ERR_OOM, "out of page-locked host memory for the block boundaries");
-        if (!ctx->ev_bstarts[i]) TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_bstarts[i], hipEventDisableTiming));
-    }
-    const unsigned turn = ctx->bstarts_turn++ & 1u;
-    TQ_HIP(ctx, hipEventSynchronize(ctx->ev_bstarts[turn]));
-    memcpy(ctx->h_bstarts_stage[turn], block_starts, (size_t)(B + 1) * sizeof(int64_t));
-    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_bstarts, ctx->h_bstarts_stage[turn], (size_t)(B + 1) * sizeof(int64_t),
-                               hipMemcpyHostToDevice, stream));
-    TQ_HIP(ctx, hipEventRecord(ctx->ev_bstarts[turn], stream));
+    if (int rc = ctx->bstarts_ring.ensure(PBLK_MAX_BLOCKS + 1))
+        return ring_fail(ctx, rc, "out of page-locked host memory for the block boundaries");
+    int64_t *piece;
+    TQ_HIP(ctx, ctx->bstarts_ring.next(piece));
+    memcpy(piece, block_starts, (size_t)(B + 1) * sizeof(int64_t));
+    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_bstarts, piece, (size_t)(B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    TQ_HIP(ctx, ctx->bstarts_ring.sent(stream));
     return TQ_OK;
 }
 
@@ -1768,23 +1660,18 @@ int blocks_dev(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t *d_s
 // Taxon counts (taxdist.hpp): pair rows u32[B][T][T][4] of the resident replicate, natural layout always.
 // ---------------------------------------------------------------------------------------------
 
-// The items of one launch reach the device as the boundaries do (stage_block_starts): the next of two page-locked
-// pieces, then an asynchronous H2D behind the work already on `stream`.  The host waits only for the copy that used the
-// piece two launches ago, so a call of up to two launches never waits for the stream.
+// The items of one launch reach the device through a StagingRing too: a call of up to two launches never waits for the
+// stream.
 int stage_td_items(tq_ctx *ctx, const TdItem *items, int64_t n, hipStream_t stream)
 {
-    constexpr size_t bytes = (size_t)TD_LAUNCH_ITEMS * sizeof(TdItem);
     if (!ctx->d_td_items) TQ_HIP(ctx, ctx->d_td_items.alloc((size_t)TD_LAUNCH_ITEMS));
-    for (int i = 0; i < 2; ++i) {
-        if (!ctx->h_td_stage[i] && pool().alloc(bytes, (void **)&ctx->h_td_stage[i]) != TQ_OK)
-            return fail(ctx, TQ_ERR_OOM, "out of page-locked host memory for the work items of the taxon counts");
-        if (!ctx->ev_td[i]) TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_td[i], hipEventDisableTiming));
-    }
-    const unsigned turn = ctx->td_turn++ & 1u;
-    TQ_HIP(ctx, hipEventSynchronize(ctx->ev_td[turn]));
-    memcpy(ctx->h_td_stage[turn], items, (size_t)n * sizeof(TdItem));
-    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_td_items, ctx->h_td_stage[turn], (size_t)n * sizeof(TdItem), hipMemcpyHostToDevice, stream));
-    TQ_HIP(ctx, hipEventRecord(ctx->ev_td[turn], stream));
+    if (int rc = ctx->td_ring.ensure((size_t)TD_LAUNCH_ITEMS))
+        return ring_fail(ctx, rc, "out of page-locked host memory for the work items of the taxon counts");
+    TdItem *piece;
+    TQ_HIP(ctx, ctx->td_ring.next(piece));
+    memcpy(piece, items, (size_t)n * sizeof(TdItem));
+    TQ_HIP(ctx, hipMemcpyAsync(ctx->d_td_items, piece, (size_t)n * sizeof(TdItem), hipMemcpyHostToDevice, stream));
+    TQ_HIP(ctx, ctx->td_ring.sent(stream));
     return TQ_OK;
 }
 
@@ -1841,20 +1728,17 @@ void note_taxon_counts(tq_ctx *ctx, int64_t items, int64_t piece, int64_t pieces
 // The event behind the last device work of an accumulator: an enqueue on another stream first waits for it, a read or
 // reset synchronises on it.  The owner calls create() with its device selected and finish() in its destructor's body.
 struct StreamOrder {
-    hipEvent_t ev = nullptr;        // recorded behind the last device work
+    Event ev;                       // recorded behind the last device work
     bool pending = false;
     hipStream_t last = nullptr;
-    hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
-    // The end of an owner on `ctx` (NULL: a host back end, nothing to do): device selected, the work waited for, the
-    // event destroyed.  A destructor's body runs before its members' destructors, so the owner's buffers are freed
-    // behind this.
+    hipError_t create() { return ev.create(); }
+    // The end of an owner on `ctx` (NULL: a host back end, nothing to do): device selected, the work waited for.  A
+    // destructor's body runs before its members' destructors, so the event and the owner's buffers go behind this.
     void finish(const tq_ctx *ctx)
     {
         if (!ctx) return;
         (void)hipSetDevice(ctx->device);
         (void)sync();
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
     }
     hipError_t join(hipStream_t st) { return pending && st != last ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
     hipError_t mark(hipStream_t st)
@@ -2752,7 +2636,7 @@ struct tq_stree {
     int64_t max_cells = 0, max_nodes = 0;
     int num_cu = 1;
     StreamOrder order;              // behind the last device add
-    hipStream_t own = nullptr;      // stream of tq_stree_graph / tq_stree_rows, which take none
+    Stream own;                     // stream of tq_stree_graph / tq_stree_rows, which take none
     std::vector<StreeLevelStat> stats;   // of the last build
     // quartet fit (fit.hpp): allocated at the first fit, grow-only, freed with the accumulator
     int64_t fit_bytes = 0;          // bound of the table region, the option "fit_scratch_bytes" as the first fit read it
@@ -2770,11 +2654,7 @@ struct tq_stree {
     PinnedBuf<unsigned long long> p_nni_w;
     tq_stree() = default;
     tq_stree(const tq_stree &) = delete;
-    ~tq_stree()
-    {
-        order.finish(ctx);
-        if (ctx && own) (void)hipStreamDestroy(own);
-    }
+    ~tq_stree() { order.finish(ctx); }
 };
 
 namespace {
@@ -3085,31 +2965,7 @@ int tq_create(tq_ctx **out, int device_id)
 void tq_destroy(tq_ctx *ctx)
 {
     if (!ctx) return;
-    (void)hipSetDevice(ctx->device);     // for the buffers too: `delete ctx` below frees them
-    free_source(ctx);
-    if (ctx->sK) (void)hipStreamDestroy(ctx->sK);
-    if (ctx->sC) (void)hipStreamDestroy(ctx->sC);
-    if (ctx->sX) {
-        (void)hipStreamDestroy(ctx->sX);
-        (void)hipEventDestroy(ctx->evFork);
-        (void)hipEventDestroy(ctx->evJoin);
-    }
-    if (ctx->evDevApi) (void)hipEventDestroy(ctx->evDevApi);
-    for (int i = 0; i < 2; ++i) {
-        if (ctx->ev_bstarts[i]) {
-            (void)hipEventSynchronize(ctx->ev_bstarts[i]);      // no copy may still read the staging piece
-            (void)hipEventDestroy(ctx->ev_bstarts[i]);
-        }
-        if (ctx->h_bstarts_stage[i]) (void)pool().release(ctx->h_bstarts_stage[i]);
-        if (ctx->ev_td[i]) {
-            (void)hipEventSynchronize(ctx->ev_td[i]);
-            (void)hipEventDestroy(ctx->ev_td[i]);
-        }
-        if (ctx->h_td_stage[i]) (void)pool().release(ctx->h_td_stage[i]);
-    }
-    for (auto e : ctx->pipe_events) (void)hipEventDestroy(e);
-    for (auto &m : ctx->marks) (void)hipEventDestroy(m.ev);
-    for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
+    (void)hipSetDevice(ctx->device);     // every member that holds a HIP resource releases it in its destructor
     delete ctx;
 }
 
@@ -3798,7 +3654,7 @@ int tq_timing_read_kernels(tq_ctx *ctx, double *ms, int n_ms, int64_t *calls)
                 if (hipEventElapsedTime(&a, prev[m.lane], m.ev) == hipSuccess) t[m.tag] += a;
             }
             prev[m.lane] = m.ev;
-            ctx->event_pool.push_back(m.ev);
+            ctx->event_pool.push_back(std::move(m.ev));
         }
         ctx->marks.clear();
         for (int i = 0; i < n_ms; ++i) ms[i] = i < TAG_COUNT ? t[i] : 0.0;
@@ -3868,12 +3724,8 @@ static int build_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S
     TQ_HIP(ctx, hipMemcpy(ctx->d_seqarr, seqarr, (size_t)(T * S0), hipMemcpyHostToDevice));
     TQ_HIP(ctx, hipMemcpy(ctx->d_spans, spans, (size_t)nloci * 16, hipMemcpyHostToDevice));
     ctx->h_spans.assign(spans, spans + 2 * nloci);
-    for (int i = 0; i < 2; ++i) {
-        if (pool().alloc((size_t)nloci * 8, (void **)&ctx->h_lidx_stage[i]) != TQ_OK ||
-            pool().alloc((size_t)nloci * 4, (void **)&ctx->h_pstart_stage[i]) != TQ_OK)
-            return fail(ctx, TQ_ERR_OOM, "tq_set_source: out of page-locked host memory");
-        TQ_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_lidx[i], hipEventDisableTiming));
-    }
+    if (int rc = ctx->lidx_ring.ensure((size_t)nloci + (size_t)(nloci + 1) / 2))       // i64 [nloci], then u32 [nloci]
+        return ring_fail(ctx, rc, "tq_set_source: out of page-locked host memory");
     TQ_HIP(ctx, ctx->d_pstart.alloc((size_t)nloci));
     // the automatic rule of boot_pack = -1, once, on the source: its loci (the spans, in their order) with the bases recoded
     // as tq_set_data takes them -- a two-base IUPAC code counts as present (its first base) -- under the rule and the
@@ -4006,18 +3858,18 @@ int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t se
         }
         uint32_t *widths = ctx->d_boot, *offsets = widths + (n + 1);
         uint32_t *src_col = offsets + (n + 1), *site_locus = src_col + ctx->boot_cap;
-        // locus indices through a page-locked staging piece (two in turn, so that the draws of the next replicate
-        // can be handed over while this copy is still queued)
-        const unsigned turn = ctx->lidx_turn++ & 1u;
-        TQ_HIP(ctx, hipEventSynchronize(ctx->ev_lidx[turn]));
-        memcpy(ctx->h_lidx_stage[turn], lidxs, (size_t)n * 8);
-        TQ_HIP(ctx, hipMemcpyAsync(ctx->d_lidxs, ctx->h_lidx_stage[turn], (size_t)n * 8, hipMemcpyHostToDevice, stream));
+        // locus indices, and behind them the packed starts, through one piece of the staging ring: the draws of the next
+        // replicate can be handed over while these copies are still queued
+        int64_t *piece;
+        TQ_HIP(ctx, ctx->lidx_ring.next(piece));
+        memcpy(piece, lidxs, (size_t)n * 8);
+        TQ_HIP(ctx, hipMemcpyAsync(ctx->d_lidxs, piece, (size_t)n * 8, hipMemcpyHostToDevice, stream));
         if (pSp) {
-            uint32_t *stage = ctx->h_pstart_stage[turn];
+            uint32_t *stage = (uint32_t *)(piece + n);
             for (int64_t i = 0; i < n; ++i) stage[i] = (uint32_t)ctx->boot_plan.start[(size_t)i];
             TQ_HIP(ctx, hipMemcpyAsync(ctx->d_pstart, stage, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         }
-        TQ_HIP(ctx, hipEventRecord(ctx->ev_lidx[turn], stream));
+        TQ_HIP(ctx, ctx->lidx_ring.sent(stream));
         TQ_HIP(ctx, hipMemsetAsync(widths + n, 0, sizeof(uint32_t), stream));
         hipLaunchKernelGGL(tq_boot_width_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ctx->d_spans,
                            ctx->d_lidxs, n, ctx->nloci, widths);
@@ -4170,7 +4022,7 @@ int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint
     return api(ctx, "tq_debug_bdsqr", [&]() -> int {
         DevBuf<double> d_de, d_sv;      // locals: every exit frees them
         DevBuf<uint32_t> d_work;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        Event e0, e1;
         int rc = TQ_OK;
         auto step = [&](hipError_t e, const char *what) {
             if (!rc && e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? TQ_ERR_OOM : TQ_ERR_HIP, "tq_debug_bdsqr: %s: %s", what, hipGetErrorString(e));
@@ -4179,8 +4031,8 @@ int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint
         if (!rc) step(d_sv.alloc((size_t)nmat * 16), "hipMalloc");
         if (!rc) step(d_work.alloc((size_t)nmat), "hipMalloc");
         if (!rc) step(hipMemcpy(d_de, de, (size_t)nmat * 256, hipMemcpyHostToDevice), "H2D");
-        if (!rc) step(hipEventCreate(&e0), "event");
-        if (!rc) step(hipEventCreate(&e1), "event");
+        if (!rc) step(e0.create(true), "event");
+        if (!rc) step(e1.create(true), "event");
         const unsigned grid = (unsigned)((nmat + WAVE - 1) / WAVE);
         if (!rc) {
             // once with the per-matrix counters (slower), then `reps` timed launches of the product form
@@ -4199,8 +4051,6 @@ int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint
         }
         if (!rc && sv) step(hipMemcpy(sv, d_sv, (size_t)nmat * 128, hipMemcpyDeviceToHost), "D2H");
         if (!rc && work) step(hipMemcpy(work, d_work, (size_t)nmat * 4, hipMemcpyDeviceToHost), "D2H");
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
         return rc;
     });
 }
@@ -4504,7 +4354,7 @@ int tq_stree_create(tq_stree **out, int64_t ntaxa, int64_t capacity_rows, int we
             TQ_HIPF(ctx, who, acc->p_cut.alloc(nodes));
             TQ_HIPF(ctx, who, hipMemset(acc->d_cnt, 0, SC_WORDS * 8));
             TQ_HIPF(ctx, who, acc->order.create());
-            TQ_HIPF(ctx, who, hipStreamCreateWithFlags(&acc->own, hipStreamNonBlocking));
+            TQ_HIPF(ctx, who, acc->own.create());
         }
         *out = acc.release();
         return TQ_OK;
