@@ -111,8 +111,10 @@ int tq_set_source(tq_ctx *ctx, const uint8_t *seqarr, int64_t T, int64_t S0,
 int tq_bootstrap(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t seed_shuffle,
                  uint64_t seed_ambig, int64_t *out_S);
 /* Same, enqueued on `stream` without waiting (the replicate length is computed on the host from the
- * spans): the replicate of iteration k+1 is built right behind the kernels of iteration k.  Resolve
- * calls for the new replicate must be ordered after it (same stream, or an event).              */
+ * spans): the replicate of iteration k+1 is built right behind the kernels of iteration k.  It is a
+ * *_dev call under the stream rule above: the library orders it behind the *_dev calls made before it
+ * and every later call of this context -- *_dev on any stream, or host-buffer -- behind it; the caller
+ * adds no event (tests/test_gpu_stream_rule.py holds the build back and checks each consumer).          */
 int tq_bootstrap_async(tq_ctx *ctx, const int64_t *lidxs, int64_t n, uint64_t seed_shuffle,
                        uint64_t seed_ambig, int64_t *out_S, void *stream);
 int tq_get_data(tq_ctx *ctx, uint8_t *tmparr, uint32_t *tmpmap);

@@ -428,7 +428,8 @@ def test_end_to_end_engine_rows_to_supertree(engine):
 
 def test_diagnostic_modes_mark_every_row_and_refuse_unflagged_outputs():
     """Timing-diagnostic modes (scan_method 2..5, phases 1 / 2) produce wrong rows.  None may leave the library
-    unmarked: every row carries TQ_FLAG_INVALID_DIAGNOSTIC, a device-API call without a flags array fails, the Python
+    unmarked: every row carries TQ_FLAG_INVALID_DIAGNOSTIC, a device-API call without a flags array fails, so does every
+    host-buffer call whose caller passes no flags array (the library's own staging array does not count), the Python
     mirror of the reference's worker raises, and resetting the option gives clean rows again."""
     import torch
     from tetrad_amd import _lib, synth
@@ -439,6 +440,8 @@ def test_diagnostic_modes_mark_every_row_and_refuse_unflagged_outputs():
     q = synth.random_quartets(T, 4000, seed=2)
     with QuartetEngine(0) as eng:
         eng.set_data(tmparr, tmpmap)
+        eng.set_species(np.arange(T) % 6)
+        sq = np.ascontiguousarray(synth.all_quartets(6), dtype=np.uint32)
         clean = eng.resolve(q, True)
         assert not (clean[2] & _lib.FLAG_INVALID_DIAGNOSTIC).any()
         for name, value, default in (("scan_method", 2, -1), ("scan_method", 4, -1), ("scan_method", 5, -1),
@@ -452,7 +455,29 @@ def test_diagnostic_modes_mark_every_row_and_refuse_unflagged_outputs():
             with pytest.raises(_lib.TetradHipError, match="diagnostic"):
                 eng.resolve_dev(d_q.data_ptr(), len(q), True, d_rstat.data_ptr(), d_rscor.data_ptr(), 0, 0)
             torch.cuda.synchronize()
+            # the host-buffer calls without the caller's flags array: refused, and no row is written
+            lib, h = _lib.load(), eng._h
+            rstat = np.full((len(q), 2), 0xFFFFFFFF, np.uint32)
+            rscor = np.full((len(q), 3), -1.0)
+            ptr = lambda a: a.ctypes.data
+            for call, rc in (
+                    ("tq_resolve", lambda: lib.tq_resolve(h, ptr(q), len(q), 1, ptr(rstat), ptr(rscor), None)),
+                    ("tq_resolve_to_host", lambda: lib.tq_resolve_to_host(h, d_q.data_ptr(), len(q), 1, ptr(rstat), ptr(rscor), None)),
+                    ("tq_resolve_debug", lambda: lib.tq_resolve_debug(h, ptr(q), len(q), 1, ptr(rstat), ptr(rscor), None,
+                                                                      None, None, None)),
+                    ("tq_resolve_species", lambda: lib.tq_resolve_species(h, ptr(sq), len(sq), ptr(rstat), ptr(rscor), None))):
+                assert rc() == _lib.TQ_OK - 1, (call, name, value)            # TQ_ERR_INVALID_ARG
+                assert b"diagnostic" in lib.tq_last_error(h), (call, name, value)
+                assert (rstat == 0xFFFFFFFF).all() and (rscor == -1.0).all(), (call, name, value)
+            sflags = np.zeros(len(sq), np.uint8)                               # with one, the species call marks its rows
+            assert lib.tq_resolve_species(h, ptr(sq), len(sq), ptr(rstat[:len(sq)]), ptr(rscor[:len(sq)]), ptr(sflags)) == 0
+            assert (sflags & _lib.FLAG_INVALID_DIAGNOSTIC).all(), (name, value)
             eng.set_option(name, default)
+        for call in (lambda f: lib.tq_resolve(h, ptr(q), len(q), 1, ptr(rstat), ptr(rscor), f),
+                     lambda f: lib.tq_resolve_to_host(h, d_q.data_ptr(), len(q), 1, ptr(rstat), ptr(rscor), f)):
+            assert call(None) == 0                                             # no mode set: flags may be NULL again
+            np.testing.assert_array_equal(rstat, clean[0])
+            np.testing.assert_array_equal(rscor, clean[1])
         again = eng.resolve(q, True)
         for a, b in zip(clean, again):
             np.testing.assert_array_equal(a, b)

@@ -3,6 +3,7 @@ between the library's arrays and Python that several of them need."""
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -13,11 +14,16 @@ from ._lib import TetradHipError
 class Handle:
     """One handle of the library (`_h`) and its life cycle.  A class names its family of functions in `_prefix`
     (`tq_cons` -> tq_cons_create / tq_cons_destroy / tq_cons_reset) and sets `engine` before `_create` when it reports
-    through an engine's context.  The reference to the engine is kept, so the engine outlives the handle."""
+    through an engine's context.  The library asks that the context outlive such a handle (its destructor selects the
+    context's device and waits for its own work).  The reference to the engine is kept, so the engine OBJECT outlives the
+    handle; an engine that is CLOSED first (a `with` block, a fixture) closes the handles made on it before its context
+    goes, whether they are still in use, waiting in a reference cycle for the collector, or forgotten.  A handle whose
+    engine is gone all the same (both were collected in one sweep, the engine first) is dropped without a call."""
 
     _prefix = ""
     _h = None
     engine = None
+    _dependants = None              # weak set of the open handles made on this one (an engine's accumulators)
 
     def _fn(self, name):
         return getattr(self._lib, f"{self._prefix}_{name}")
@@ -33,15 +39,26 @@ class Handle:
         h = ctypes.c_void_p()
         self._check(self._fn("create")(ctypes.byref(h), *args))
         self._h = h
+        if self.engine is not None:
+            if self.engine._dependants is None:
+                self.engine._dependants = weakref.WeakSet()
+            self.engine._dependants.add(self)
 
     def _check(self, rc: int):
         if rc != 0:
             raise TetradHipError(rc, self._lib.tq_last_error(self._ctx()).decode())
 
     def close(self):
+        if self._dependants:
+            for dependant in list(self._dependants):
+                dependant.close()
+            self._dependants = None
         if self._h:
-            self._fn("destroy")(self._h)
+            if self.engine is None or self.engine._h:           # else the context is gone: its destructor would read it
+                self._fn("destroy")(self._h)
             self._h = None
+            if self.engine is not None and self.engine._dependants is not None:
+                self.engine._dependants.discard(self)
 
     def __enter__(self):
         return self

@@ -442,10 +442,28 @@ void free_source(tq_ctx *ctx)
     ctx->lidx_ring.reset();
 }
 
+// Before shared scratch is regrown: the host waits for the last *_dev call, whose kernels may still read the old block
+// on any stream (device_mem.hpp: "a caller that regrows a buffer the device may still read waits for the device first").
+// The host-buffer calls have drained their own streams when they return.  Only on the regrow path: no HIP call otherwise
+// (tq_set_data frees its replicate on every call, so it waits on every call).
+hipError_t regrow_wait(tq_ctx *ctx)
+{
+    return ctx->evDevApi ? hipEventSynchronize(ctx->evDevApi) : hipSuccess;
+}
+
+// the scratch of the host-buffer calls and of a range call without a quartet array, grow-only
+hipError_t grow_scratch(tq_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->d_scratch.cap()) return hipSuccess;
+    const hipError_t e = regrow_wait(ctx);
+    return e != hipSuccess ? e : ctx->d_scratch.grow(bytes);
+}
+
 // count slab + ordering scratch for a scan batch of `quartets`
 int ensure_cm(tq_ctx *ctx, int64_t quartets)
 {
     if (quartets <= ctx->cm_quartets) return TQ_OK;
+    TQ_HIP(ctx, regrow_wait(ctx));
     ctx->d_cm.reset();
     ctx->d_sort.reset();
     ctx->d_sort_tmp.reset();
@@ -476,6 +494,7 @@ int ensure_svd(tq_ctx *ctx, int64_t quartets)
         TQ_HIP(ctx, ctx->evJoin.create());
     }
     if (quartets <= ctx->svd_quartets) return TQ_OK;
+    TQ_HIP(ctx, regrow_wait(ctx));
     ctx->d_de.reset();
     ctx->d_sv.reset();
     ctx->d_nsnps.reset();
@@ -807,6 +826,16 @@ bool diagnostic_mode(const tq_ctx *ctx)
     return (ctx->opt.scan_method >= 2 && ctx->opt.scan_method <= 5) || ctx->opt.phases != 3;
 }
 
+// timing-diagnostic modes produce wrong rows: none leaves the library unmarked.  `flags` is the array the CALLER gave: a
+// host-buffer call judges it at its entry, since the device array it hands `launch` is the library's own and never NULL.
+int refuse_unflagged(tq_ctx *ctx, const uint8_t *flags)
+{
+    if (diagnostic_mode(ctx) && !flags)
+        return fail(ctx, TQ_ERR_INVALID_ARG, "a timing-diagnostic mode is set (scan_method 2..5 or phases 1 / 2): its rows are "
+                                             "not results and are only handed out with a flags array (TQ_FLAG_INVALID_DIAGNOSTIC)");
+    return TQ_OK;
+}
+
 OutPtrs offset_out(const OutPtrs &o, int64_t q0)
 {
     OutPtrs r = o;
@@ -979,11 +1008,8 @@ int stage_svd(tq_ctx *ctx, int64_t q0, int64_t n, bool debug, const OutPtrs &out
     const int64_t chunk = svd_chunk_rows(ctx, n);
     int rc = ensure_svd(ctx, chunk);
     if (rc) return rc;
-    // timing-diagnostic modes produce wrong rows: none leaves the library unmarked
     const bool diag = diagnostic_mode(ctx);
-    if (diag && !out.flags)
-        return fail(ctx, TQ_ERR_INVALID_ARG, "a timing-diagnostic mode is set (scan_method 2..5 or phases 1 / 2): its rows are "
-                                             "not results and are only handed out with a flags array (TQ_FLAG_INVALID_DIAGNOSTIC)");
+    if ((rc = refuse_unflagged(ctx, out.flags))) return rc;
     const bool two = ctx->opt.svd_streams > 1 && n > chunk;
     if (two) {
         TQ_HIP(ctx, hipEventRecord(ctx->evFork, stream));
@@ -1288,7 +1314,7 @@ int host_scratch(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, bool cmats, b
     h->o_sv = align_up(h->o_cm + (cmats ? (size_t)Q * 3072 : 0), 256);
     h->o_rk = align_up(h->o_sv + (svds ? (size_t)Q * 384 : 0), 256);
     const size_t total = align_up(h->o_rk + (ranks ? (size_t)Q * 12 : 0), 256);
-    TQ_HIP(ctx, ctx->d_scratch.grow(total));
+    TQ_HIP(ctx, grow_scratch(ctx, total));
     if (int rc = ensure_streams(ctx)) return rc;
     h->base = ctx->d_scratch;
     // quartets H2D on the compute stream (asynchronous when the caller's array is page-locked)
@@ -1403,7 +1429,7 @@ int patterns_to_host(tq_ctx *ctx, const char *who, const uint32_t *sets, int64_t
         if (Q == 0) return TQ_OK;
         if ((rc = check_set_rows(ctx, who, sets, Q, 4, species))) return rc;
         const size_t o_cls = align_up((size_t)Q * 16, 256);
-        TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)));
+        TQ_HIP(ctx, grow_scratch(ctx, o_cls + (size_t)Q * PAT_ROW * sizeof(uint32_t)));
         if ((rc = ensure_streams(ctx))) return rc;
         char *base = ctx->d_scratch;
         uint32_t *d_classes = (uint32_t *)(base + o_cls);
@@ -1619,7 +1645,7 @@ int blocks_to_host(tq_ctx *ctx, const char *who, BlockKind kind, const uint32_t 
         const size_t row_bytes = (size_t)B * PAT_ROW * sizeof(uint32_t);
         const size_t set_bytes = (size_t)width * sizeof(uint32_t);
         const size_t o_cls = align_up((size_t)chunk * set_bytes, 256);
-        TQ_HIP(ctx, ctx->d_scratch.grow(o_cls + (size_t)chunk * row_bytes));
+        TQ_HIP(ctx, grow_scratch(ctx, o_cls + (size_t)chunk * row_bytes));
         if ((rc = ensure_streams(ctx))) return rc;
         char *base = ctx->d_scratch;
         uint32_t *d_classes = (uint32_t *)(base + o_cls);
@@ -3028,6 +3054,9 @@ int tq_set_data(tq_ctx *ctx, const uint8_t *tmparr, int64_t T, int64_t S, const 
         if (T < 1 || S < 1 || locus_stride < 1 || T > 0x7FFFFFFF)
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_set_data: bad shape T=%lld S=%lld stride=%lld", (long long)T,
                         (long long)S, (long long)locus_stride);
+        // a *_dev call still queued reads the replicate that goes now.  tq_set_data always frees, so for it every call is
+        // the regrow path: one hipEventSynchronize per call once a *_dev call has been made, queued work or not
+        TQ_HIP(ctx, regrow_wait(ctx));
         free_data(ctx);
         ctx->data_gen++;
 
@@ -3163,9 +3192,12 @@ int tq_resolve_range_dev(tq_ctx *ctx, uint64_t first_rank, int64_t Q, int subsam
         if (first_rank + (uint64_t)Q > total)
             return fail(ctx, TQ_ERR_INVALID_ARG, "rank range [%llu,+%lld) exceeds C(%lld,4)=%llu",
                         (unsigned long long)first_rank, (long long)Q, (long long)ctx->T, (unsigned long long)total);
+        // before any shared scratch is touched: without d_quartets the unrank writes into d_scratch, which the scan of a
+        // range call still queued on another stream reads its quartets from
+        if (int rc2 = enter_dev_api(ctx, (hipStream_t)stream)) return rc2;
         uint32_t *dq = d_quartets;
         if (!dq) {
-            TQ_HIP(ctx, ctx->d_scratch.grow((size_t)Q * 16));
+            TQ_HIP(ctx, grow_scratch(ctx, (size_t)Q * 16));
             dq = (uint32_t *)ctx->d_scratch.get();
         }
         hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -3173,7 +3205,6 @@ int tq_resolve_range_dev(tq_ctx *ctx, uint64_t first_rank, int64_t Q, int subsam
         TQ_LAUNCHED(ctx, "tq_resolve_range_dev");
         OutPtrs out{d_rstat, d_rscor, d_flags, nullptr, nullptr, nullptr};
         // consecutive lexicographic ranks are in (a,b,c) order already
-        if (int rc2 = enter_dev_api(ctx, (hipStream_t)stream)) return rc2;
         return note_dev_api(ctx, (hipStream_t)stream,
                             launch(ctx, dq, Q, subsample, false, true, out, (hipStream_t)stream, NoChunkHook()));
     });
@@ -3188,12 +3219,13 @@ int tq_resolve_to_host(tq_ctx *ctx, const uint32_t *d_quartets, int64_t Q, int s
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_to_host: NULL pointer or negative Q");
         int rc = check_ready(ctx, subsample);
         if (rc) return rc;
+        if ((rc = refuse_unflagged(ctx, flags))) return rc;
         if (Q == 0) return TQ_OK;
         if ((rc = ensure_streams(ctx))) return rc;
         const size_t o_rstat = 0;
         const size_t o_rscor = align_up(o_rstat + (size_t)Q * 8, 256);
         const size_t o_flags = align_up(o_rscor + (size_t)Q * 24, 256);
-        TQ_HIP(ctx, ctx->d_scratch.grow(align_up(o_flags + (size_t)Q, 256)));
+        TQ_HIP(ctx, grow_scratch(ctx, align_up(o_flags + (size_t)Q, 256)));
         char *base = ctx->d_scratch;
         return resolve_to_host(ctx, d_quartets, Q, subsample, false, rstat, rscor, flags, (uint32_t *)(base + o_rstat),
                                (double *)(base + o_rscor), (uint8_t *)(base + o_flags));
@@ -3209,6 +3241,7 @@ int tq_resolve_debug(tq_ctx *ctx, const uint32_t *quartets, int64_t Q, int subsa
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve: NULL pointer or negative Q");
         int rc = check_ready(ctx, subsample);
         if (rc) return rc;
+        if ((rc = refuse_unflagged(ctx, flags))) return rc;
         if (Q == 0) return TQ_OK;
         // Taxon indices are checked on the host (the kernels re-check and flag them, and never dereference a bad
         // one).  For chunks of the size the reference's distributor hands out the same pass notices input that
@@ -3339,6 +3372,7 @@ int tq_resolve_species_debug(tq_ctx *ctx, const uint32_t *squartets, int64_t Q, 
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_species: NULL pointer or negative Q");
         int rc = species_ready(ctx, "tq_resolve_species");
         if (rc) return rc;
+        if ((rc = refuse_unflagged(ctx, flags))) return rc;
         if (Q == 0) return TQ_OK;
         // ids on the host (the kernels re-check them and flag the row); a row that repeats a species can exceed the
         // call's range bound, so its own product is checked when the bound leaves room for that
@@ -3554,7 +3588,7 @@ int tq_taxon_counts(tq_ctx *ctx, const int64_t *block_starts, int64_t B, uint32_
         if (!out) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: NULL pointer", who);
         const int64_t T = ctx->T, chunk = td_piece_blocks(T, B, ctx->opt.taxdist_scratch_bytes);
         const size_t block_bytes = (size_t)(T * T) * 16;
-        TQ_HIP(ctx, ctx->d_scratch.grow((size_t)chunk * block_bytes));
+        TQ_HIP(ctx, grow_scratch(ctx, (size_t)chunk * block_bytes));
         if ((rc = ensure_streams(ctx))) return rc;
         uint32_t *d_rows = (uint32_t *)ctx->d_scratch.get();
         int64_t items = 0, chunks = 0;
@@ -3952,7 +3986,7 @@ int tq_get_data(tq_ctx *ctx, uint8_t *tmparr, uint32_t *tmpmap)
         const SiteSet &nat = ctx->nat;
         const int64_t T = ctx->T, S = ctx->S, W = nat.W;
         const size_t bytes = align_up((size_t)(T * S), 256) + align_up((size_t)S * 8, 256) + align_up((size_t)(W + 1) * 8, 256);
-        TQ_HIP(ctx, ctx->d_scratch.grow(bytes));
+        TQ_HIP(ctx, grow_scratch(ctx, bytes));
         uint8_t *d_arr = (uint8_t *)ctx->d_scratch.get();
         uint32_t *d_map = (uint32_t *)(ctx->d_scratch + align_up((size_t)(T * S), 256));
         uint32_t *d_cnt = (uint32_t *)((char *)d_map + align_up((size_t)S * 8, 256));
@@ -4035,6 +4069,10 @@ int tq_debug_bdsqr(tq_ctx *ctx, const double *de, int64_t nmat, double *sv, uint
         if (!rc) step(e1.create(true), "event");
         const unsigned grid = (unsigned)((nmat + WAVE - 1) / WAVE);
         if (!rc) {
+            // The launch is judged by the thread's last error, and that is sticky: an error that another user of the HIP
+            // runtime in this thread left unread (a finaliser run by the host language, say) is not this launch's.  Every
+            // call above was judged by its own return value, so whatever is pending here is foreign: read it away.
+            (void)hipGetLastError();
             // once with the per-matrix counters (slower), then `reps` timed launches of the product form
             hipLaunchKernelGGL(tq_bdsqr_kernel, dim3(grid), dim3(WAVE), 0, 0, (const double *)d_de, nmat, d_sv.get(), ctx->opt.bdsqr_maxit,
                                (unsigned long long *)nullptr, d_work.get());
