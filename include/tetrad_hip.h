@@ -155,7 +155,9 @@ int tq_resolve_dev(tq_ctx *ctx, const uint32_t *d_quartets, int64_t Q, int subsa
 /* Full-mode quartet generation on the device: resolves the quartets whose
  * lexicographic ranks are [first_rank, first_rank+Q) among C(T,4), i.e. what
  * islice(combinations(range(T),4), start, end) yields (combinations.py:40-55),
- * without any quartet H2D.  d_quartets (u32[Q,4], may be NULL) receives them.     */
+ * without any quartet H2D.  d_quartets (u32[Q,4], may be NULL) receives them.
+ * TQ_ERR_INVALID_ARG when the range does not end at or below C(T,4), or T > 145 056
+ * (see tq_unrank).                                                                 */
 int tq_resolve_range_dev(tq_ctx *ctx, uint64_t first_rank, int64_t Q, int subsample,
                          uint32_t *d_quartets, uint32_t *d_rstat, double *d_rscor,
                          uint8_t *d_flags, void *stream);
@@ -172,7 +174,9 @@ int tq_svd_dev(tq_ctx *ctx, int64_t q0, int64_t n, uint32_t *d_rstat, double *d_
                uint8_t *d_flags, void *stream);
 
 /* Random-mode quartet generation on the device: unranks host-sampled
- * lexicographic ranks (combinations.py:94-114) into d_quartets.                    */
+ * lexicographic ranks (combinations.py:94-114) into d_quartets.  The ranks are on
+ * the device and are not checked: each must be below C(T,4).  T > 145 056 is
+ * TQ_ERR_INVALID_ARG (see tq_unrank).                                              */
 int tq_unrank_dev(tq_ctx *ctx, const uint64_t *d_ranks, int64_t Q, uint32_t *d_quartets,
                   void *stream);
 
@@ -181,7 +185,9 @@ int tq_unrank_dev(tq_ctx *ctx, const uint64_t *d_ranks, int64_t Q, uint32_t *d_q
  * lexicographic ranks to d_ranks (u64[Q]).  Same distribution as
  * random_combination_sample_via_index (combinations.py:109-114: rng.choice(C(T,4), size, replace=False)
  * + unranking) but NOT the project Generator's stream (a keyed permutation of the rank space,
- * counter-based): for runs that do not need to reproduce a reference run's sample.               */
+ * counter-based): for runs that do not need to reproduce a reference run's sample.  Element i of the sample
+ * depends on (seed, T, i) alone (a call with a smaller Q returns a prefix); tests/rank_model.py states it in
+ * Python integers.  TQ_ERR_INVALID_ARG when Q > C(T,4) or T > 145 056 (see tq_unrank).            */
 int tq_sample_quartets_dev(tq_ctx *ctx, uint64_t seed, int64_t Q, uint64_t *d_ranks,
                            uint32_t *d_quartets, void *stream);
 
@@ -328,7 +334,11 @@ int tq_numpy_choice_tail(void *np_bitgen, uint64_t pop, int64_t size, int64_t *o
 /* Lexicographic unranking on the host (no device involved): quartets[i] = the 4-combination of range(T) with
  * rank ranks[i] (or first_rank + i when ranks is NULL), i.e. _index_to_combination (combinations.py:94-106) for
  * every sampled index / islice(combinations(range(T), 4), first_rank, first_rank + Q) (combinations.py:40-55).
- * TQ_ERR_INVALID_ARG when a rank is >= C(T,4).                                                     */
+ * Ranks are 64-bit: C(T,4) is below 2^64 up to T = 145 056, and every call that takes or makes ranks (this one,
+ * tq_unrank_dev, tq_resolve_range_dev, tq_sample_quartets_dev, tq_qd_score_ranks, tq_ls_score_ranks) refuses a larger T
+ * with TQ_ERR_INVALID_ARG and one message ("C(T,4) does not fit 64 bits").  TQ_ERR_INVALID_ARG too when a rank is
+ * >= C(T,4) or the range [first_rank, first_rank + Q) does not end at or below C(T,4) (tested without forming the sum,
+ * which wraps near 2^64); the message is read with tq_last_error(NULL).                              */
 int tq_unrank(const uint64_t *ranks, uint64_t first_rank, int64_t Q, int64_t T, uint32_t *quartets);
 
 /* The rows tq_format_qmc would write, as arrays (no text round trip): splits u32[n,4] = "a,b|c,d" and weights f64[n]

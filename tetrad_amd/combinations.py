@@ -32,7 +32,7 @@ def unrank(ranks=None, nsamples: int = 0, first_rank: int = 0, count: int = 0) -
         out = np.empty((n, 4), np.uint32)
         rc = lib.tq_unrank(None, int(first_rank), n, int(nsamples), out.ctypes.data)
     if rc != 0:
-        raise _lib.TetradHipError(rc, f"tq_unrank: rank out of range for C({nsamples},4)={comb(int(nsamples), 4)}")
+        raise _lib.TetradHipError(rc, (lib.tq_last_error(None) or b"").decode() or "tq_unrank failed")
     return out
 
 

@@ -188,7 +188,15 @@ inline uint64_t host_choose(uint64_t n, int k)
     }
 }
 
-inline uint64_t host_choose4(uint64_t n) { return n < 4 ? 0 : n * (n - 1) / 2 * (n - 2) / 3 * (n - 3) / 4; }
+// C(n, 4), exact wherever it is below 2^64 (n <= CHOOSE4_MAX_T): C(n, 3) * (n - 3) passes 2^64 from n = 102 571 on, long
+// before its quarter does, so that product is taken in 128 bits
+constexpr uint64_t CHOOSE4_MAX_T = 145056;
+
+inline uint64_t host_choose4(uint64_t n)
+{
+    if (n < 4) return 0;
+    return (uint64_t)((unsigned __int128)host_choose(n, 3) * (n - 3) / 4);
+}
 
 inline void unrank_host(const uint64_t *ranks, uint64_t first_rank, int64_t Q, int32_t T, uint32_t *quartets)
 {

@@ -386,8 +386,18 @@ int ring_fail(tq_ctx *ctx, int rc, const char *no_memory)
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// C(T, 4), the number of quartets of T taxa (64 bits hold it up to T = 100 000)
-uint64_t choose4(uint64_t T) { return T < 4 ? 0 : T * (T - 1) / 2 * (T - 2) / 3 * (T - 3) / 4; }
+// C(T, 4), the number of quartets of T taxa and the size of the rank space: exact for every T at which it is below 2^64,
+// which rank_space_fits says (T <= 145 056; format.hpp's host_choose4 takes the last product in 128 bits).  Every call
+// that takes or makes ranks asks rank_space_fits first and refuses with RANK_SPACE_MSG.
+uint64_t choose4(uint64_t T) { return host_choose4(T); }
+bool rank_space_fits(int64_t T) { return T >= 0 && (uint64_t)T <= CHOOSE4_MAX_T; }
+#define RANK_SPACE_MSG "%s: C(%lld,4) does not fit 64 bits: quartet ranks are defined for at most 145056 taxa"
+
+// whether the Q ranks from first_rank all lie below total, without forming first_rank + Q (which wraps near 2^64)
+bool rank_range_fits(uint64_t first_rank, int64_t Q, uint64_t total)
+{
+    return Q <= 0 || (first_rank <= total && (uint64_t)Q <= total - first_rank);
+}
 
 // The cooperative kernels address a set with 32-bit offsets: a packed set past that range while the natural one is inside
 // it would send the batch to the one-wave kernel, so such a set is not built automatically.
@@ -2383,13 +2393,14 @@ struct QuartetPlanes {
     int check_ranks(const char *who, const uint64_t *ranks, uint64_t first_rank, int64_t Q) const
     {
         if (Q < 0) return fail(ctx, TQ_ERR_INVALID_ARG, "%s: negative Q", who);
+        if (!rank_space_fits(T)) return fail(ctx, TQ_ERR_INVALID_ARG, RANK_SPACE_MSG, who, (long long)T);
         const uint64_t total = choose4((uint64_t)T);
         if (ranks) {
             for (int64_t i = 0; i < Q; ++i)
                 if (ranks[i] >= total)
                     return fail(ctx, TQ_ERR_INVALID_ARG, "%s: rank %lld: %llu is not below C(%d,4) = %llu", who, (long long)i,
                                 (unsigned long long)ranks[i], T, (unsigned long long)total);
-        } else if (Q > 0 && (first_rank > total || (uint64_t)Q > total - first_rank)) {
+        } else if (!rank_range_fits(first_rank, Q, total)) {
             return fail(ctx, TQ_ERR_INVALID_ARG, "%s: rank range [%llu,+%lld) exceeds C(%d,4) = %llu", who,
                         (unsigned long long)first_rank, (long long)Q, T, (unsigned long long)total);
         }
@@ -3171,6 +3182,7 @@ int tq_unrank_dev(tq_ctx *ctx, const uint64_t *d_ranks, int64_t Q, uint32_t *d_q
         if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_data has not been called");
         if (Q < 0 || (Q > 0 && (!d_ranks || !d_quartets)))
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_unrank_dev: NULL pointer or negative Q");
+        if (!rank_space_fits(ctx->T)) return fail(ctx, TQ_ERR_INVALID_ARG, RANK_SPACE_MSG, "tq_unrank_dev", (long long)ctx->T);
         if (Q == 0) return TQ_OK;
         hipLaunchKernelGGL(tq_unrank_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            d_ranks, (uint64_t)0, Q, (int32_t)ctx->T, d_quartets);
@@ -3187,9 +3199,11 @@ int tq_resolve_range_dev(tq_ctx *ctx, uint64_t first_rank, int64_t Q, int subsam
         if (!ctx->have_data) return fail(ctx, TQ_ERR_NO_DATA, "tq_set_data has not been called");
         if (Q < 0 || (Q > 0 && (!d_rstat || !d_rscor)))
             return fail(ctx, TQ_ERR_INVALID_ARG, "tq_resolve_range_dev: NULL pointer or negative Q");
+        if (!rank_space_fits(ctx->T))
+            return fail(ctx, TQ_ERR_INVALID_ARG, RANK_SPACE_MSG, "tq_resolve_range_dev", (long long)ctx->T);
         if (Q == 0) return TQ_OK;
         const uint64_t total = choose4((uint64_t)ctx->T);
-        if (first_rank + (uint64_t)Q > total)
+        if (!rank_range_fits(first_rank, Q, total))
             return fail(ctx, TQ_ERR_INVALID_ARG, "rank range [%llu,+%lld) exceeds C(%lld,4)=%llu",
                         (unsigned long long)first_rank, (long long)Q, (long long)ctx->T, (unsigned long long)total);
         // before any shared scratch is touched: without d_quartets the unrank writes into d_scratch, which the scan of a
@@ -3962,6 +3976,7 @@ int tq_sample_quartets_dev(tq_ctx *ctx, uint64_t seed, int64_t Q, uint64_t *d_ra
         if (!ctx->have_data && !ctx->d_seqarr) return fail(ctx, TQ_ERR_NO_DATA, "no data on the device (T unknown)");
         if (Q < 0 || (Q > 0 && !d_quartets)) return fail(ctx, TQ_ERR_INVALID_ARG, "tq_sample_quartets_dev: NULL pointer or negative Q");
         const uint64_t T = (uint64_t)(ctx->have_data ? ctx->T : ctx->src_T);
+        if (!rank_space_fits((int64_t)T)) return fail(ctx, TQ_ERR_INVALID_ARG, RANK_SPACE_MSG, "tq_sample_quartets_dev", (long long)T);
         const uint64_t total = choose4(T);
         if ((uint64_t)Q > total)
             return fail(ctx, TQ_ERR_INVALID_ARG, "cannot draw %lld distinct quartets from C(%llu,4)=%llu", (long long)Q,
@@ -4130,13 +4145,18 @@ int tq_numpy_choice_tail(void *np_bitgen, uint64_t pop, int64_t size, int64_t *o
 
 int tq_unrank(const uint64_t *ranks, uint64_t first_rank, int64_t Q, int64_t T, uint32_t *quartets)
 {
-    if (Q < 0 || T < 4 || T > 100000 || (Q > 0 && !quartets)) return TQ_ERR_INVALID_ARG;     // C(T,4) must fit 64 bits
+    if (Q < 0 || T < 4 || (Q > 0 && !quartets))
+        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_unrank: NULL pointer, negative Q or fewer than 4 taxa");
+    if (!rank_space_fits(T)) return fail(nullptr, TQ_ERR_INVALID_ARG, RANK_SPACE_MSG, "tq_unrank", (long long)T);
     const uint64_t total = choose4((uint64_t)T);
     if (ranks) {
         for (int64_t i = 0; i < Q; ++i)
-            if (ranks[i] >= total) return TQ_ERR_INVALID_ARG;
-    } else if (first_rank + (uint64_t)Q > total) {
-        return TQ_ERR_INVALID_ARG;
+            if (ranks[i] >= total)
+                return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_unrank: rank %lld: %llu is not below C(%lld,4) = %llu", (long long)i,
+                            (unsigned long long)ranks[i], (long long)T, (unsigned long long)total);
+    } else if (!rank_range_fits(first_rank, Q, total)) {
+        return fail(nullptr, TQ_ERR_INVALID_ARG, "tq_unrank: rank range [%llu,+%lld) exceeds C(%lld,4) = %llu",
+                    (unsigned long long)first_rank, (long long)Q, (long long)T, (unsigned long long)total);
     }
     unrank_host(ranks, first_rank, Q, (int32_t)T, quartets);
     return TQ_OK;
